@@ -10,6 +10,10 @@ One "step" = one pass of the hot path over one batch: FastGenModel.generator_fn(
 before the timed region.  Ranks are independent replicas (sampling shards by image, no collective on the data path);
 the timed region is bracketed by barrier + device synchronize on both sides and the MAX over ranks is reported.
 
+--dump-outputs DIR writes, on rank 0, the samples the last timed step returned as float32 .npy files: DIR/samples.npy
+(the headline mode) and DIR/samples_bf16.npy (the bf16 line beside it, when measured).  Inputs, weights and per-step seeds
+depend only on the arguments, so two builds run with the same arguments can be compared output for output.
+
 Rank 0 prints ONE JSON line with the contract fields plus
   roofline     — the dominant kernel (fused GN+SiLU+conv3x3 at 32x32) timed live with HIP events on its launch stream
   cpu_baseline — the CPU oracle (torch fp32 restatement of the reference path, oracle/edm_ref.py) on this host's cores
@@ -214,6 +218,14 @@ def transformer_rows(dev):
     return out
 
 
+def dump_output(out_dir: str, name: str, t: torch.Tensor) -> None:
+    """One output array as out_dir/name.npy in float32 (a [512, 3, 32, 32] batch is 6.3 MB)."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, f"{name}.npy"), t.detach().to(device="cpu", dtype=torch.float32).numpy())
+
+
 def result_line(value, world, steps, warmup, dt, dtype, batch, sample_steps, graph, roofline, cpu):
     """The ONE JSON line of the driver contract (fields and meanings: the task brief, 'Measurement')."""
     return {
@@ -238,7 +250,11 @@ def main():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-graph", action="store_true")
     ap.add_argument("--no-secondary", action="store_true", help="skip the bf16 line and the transformer-row timings reported beside the headline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the samples of the last timed step as DIR/<name>.npy (float32, rank 0)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     rank, local_rank, world = dist_env()
     if world != args.gpus:
@@ -267,15 +283,19 @@ def main():
         # default init scales the residual branches by 1e-5, which makes the data trivial)
         net = EDMPrecond(compute_dtype=dtype, **EDM_CIFAR10).randomize_parameters_(seed=1234).to(dev).eval()
         step_seed = [0]
+        last = [None]  # what the latest step returned (a fresh tensor per call)
 
         def step():
             step_seed[0] += 1
-            return FastGenModel.generator_fn(net, noise, condition=cond, student_sample_steps=args.sample_steps,
-                                             student_sample_type="sde", seed=step_seed[0] * world + rank,
-                                             use_graph=not args.no_graph)
+            last[0] = FastGenModel.generator_fn(net, noise, condition=cond, student_sample_steps=args.sample_steps,
+                                                student_sample_type="sde", seed=step_seed[0] * world + rank,
+                                                use_graph=not args.no_graph)
+            return last[0]
 
         dt = timed_region(step, args.steps, args.warmup, world, lambda: torch.cuda.synchronize(dev), dev)
         value = B * args.steps * world / dt
+        if args.dump_outputs and rank == 0:
+            dump_output(args.dump_outputs, "samples" if dtype == args.dtype else f"samples_{dtype}", last[0])
         out = step()
         assert torch.isfinite(out).all(), "non-finite samples"
         # ---- roofline of the dominant kernel, measured live with HIP events on its launch stream -------------------

@@ -82,3 +82,16 @@ def test_bench_line_contract():
     assert "model" not in line["config"]
     assert set(roof) <= set(line["roofline"]) and {"value", "unit", "cores", "kind", "sample"} <= set(line["cpu_baseline"])
     assert abs(line["ms_per_step"] - 170.0) < 1e-9
+
+
+def test_dump_output_writes_float32_npy(tmp_path):
+    """bench.py --dump-outputs: one array per name, float32, the values unchanged."""
+    import numpy as np
+
+    import bench
+
+    t = torch.randn(2, 3, 4, 4, dtype=torch.float64, generator=torch.Generator().manual_seed(0))
+    bench.dump_output(str(tmp_path / "out"), "samples", t)
+    a = np.load(tmp_path / "out" / "samples.npy")
+    assert a.dtype == np.float32 and a.shape == (2, 3, 4, 4)
+    assert np.array_equal(a, t.float().numpy())
