@@ -15,6 +15,7 @@ FG_LOOP_X0, FG_LOOP_MEANFLOW, FG_LOOP_EULER = 0, 1, 2
 FG_SCHEDULE_EDM, FG_SCHEDULE_RF = 0, 1
 FG_DROP_PRECOND_INPUT, FG_DROP_PRECOND_OUTPUT = 1, 2
 FG_BWD_DECODER, FG_BWD_ENCODER, FG_BWD_EMBED = 1, 2, 4
+FG_MODEL_SONGUNET, FG_MODEL_DHARIWAL = 0, 1
 
 
 class fg_edm_config(ctypes.Structure):
@@ -24,7 +25,7 @@ class fg_edm_config(ctypes.Structure):
         ("channel_mult_emb", c_int), ("num_blocks", c_int), ("num_attn_resolutions", c_int),
         ("attn_resolutions", c_int * FG_MAX_LEVELS), ("channel_mult_noise", c_int), ("sigma_data", c_double),
         ("sigma_shift", c_double), ("compute_dtype", c_int), ("r_timestep", c_int), ("drop_precond", c_int),
-        ("schedule", c_int),
+        ("schedule", c_int), ("model_type", c_int),
     ]
 
 

@@ -13,6 +13,7 @@
 
 #include "../../include/fastgen_amd.h"
 #include "common.h"
+#include "adm.h"
 #include "conv.h"
 #include "misc.h"
 
@@ -91,7 +92,17 @@ struct Act {
     int slots = 0;
 };
 
+// Buffers of the DhariwalUNet forward (engine_adm.inc); unused by the SongUNet path.
+struct AdmWs {
+    float *e2 = nullptr, *lab = nullptr;  // map_layer1 output, map_label(labels)
+    float2* part = nullptr;               // GroupNorm partial statistics
+    std::vector<float*> skip;             // encoder outputs (stem first)
+    float *xa = nullptr, *xb = nullptr, *h = nullptr, *s = nullptr, *t1 = nullptr, *qkv = nullptr, *a = nullptr;
+};
+struct AdmNet;
+
 struct Workspace {
+    AdmWs adm;
     float *coef, *emb0, *emb1, *emb, *temb;
     float2 *ab0, *ab1, *ab2;
     float2 *mr0 = nullptr, *mr1 = nullptr, *mr2 = nullptr;  // {mean, rstd} of norm0 / norm1 / norm2, kept when a backward pass follows
@@ -139,6 +150,7 @@ struct GraphKey {
 
 struct fg_edm {
     fg_edm_config cfg;
+    AdmNet* adm = nullptr;  // cfg.model_type == FG_MODEL_DHARIWAL: the ADM layout (engine_adm.inc); nullptr for SongUNet
     int dtype = 0;  // storage type of the activation tensors and mode of every non-conv kernel: 0 fp32, 1 bf16
     int cmode = 0;  // arithmetic of the convolutions: FG_DTYPE_F32 / FG_DTYPE_BF16 / FG_DTYPE_BF16X3 (fp32 storage)
     int num_taps = 0;  // encoder `block3` outputs available as feature taps
@@ -367,7 +379,19 @@ int check_supported(const fg_edm* h) {
     return FG_OK;
 }
 
+// DhariwalUNet engine (engine_adm.inc, included at the end of this namespace)
+void adm_build_layout(fg_edm* h);
+int adm_check_supported(const fg_edm* h);
+size_t adm_plan_workspace(const fg_edm* h, int B, Arena& A, Workspace& w);
+int adm_pack_weights(fg_edm* h, hipStream_t s);
+int adm_forward(fg_edm* h, const float* x_t, const double* t, int t_stride, const float* labels, float* out, int B, Workspace& w,
+                hipStream_t s);
+int adm_refuse(const fg_edm* h, const char* what) {
+    return fail(FG_EINVAL, "%s is not implemented for DhariwalUNet (forward and sampling only)", what);
+}
+
 size_t plan_workspace(const fg_edm* h, int B, Arena& A, Workspace& w) {
+    if (h->adm) return adm_plan_workspace(h, B, A, w);
     const fg_edm_config& c = h->cfg;
     const size_t tsz = h->dtype ? 2 : 4;
     const int R = c.img_resolution;
@@ -567,6 +591,7 @@ int run_mapping(fg_edm* h, const float* labels, int B, Workspace& w, hipStream_t
 int run_forward(fg_edm* h, const float* x_t, const double* t, int t_stride, const double* r, int r_stride,
                 const float* labels, float* out, int B, Workspace& w, hipStream_t s, float* const* feats = nullptr,
                 bool early = false, TrainStash* ts = nullptr) {
+    if (h->adm) return adm_forward(h, x_t, t, t_stride, labels, out, B, w, s);
     const fg_edm_config& c = h->cfg;
     HIP_TRY(launch_precond_coef(t, t_stride, c.r_timestep ? r : nullptr, r_stride, c.sigma_data, h->shift(), 1e-6,
                                 c.drop_precond, w.coef, B, s));
@@ -744,6 +769,8 @@ int ensure_device_state(fg_edm* h) {
     return FG_OK;
 }
 
+#include "engine_adm.inc"  // the DhariwalUNet layout, workspace plan and forward schedule
+
 }  // namespace
 
 // ================================================ C ABI =====================================================
@@ -764,15 +791,32 @@ int fg_edm_create(const fg_edm_config* cfg, fg_edm** out) {
         return fail(FG_EINVAL, "bad r_timestep / drop_precond / schedule");
     if (cfg->model_channels <= 0 || cfg->model_channels % 16 || cfg->channel_mult_noise < 1 || cfg->channel_mult_emb < 1)
         return fail(FG_EINVAL, "bad channel configuration");
+    if (cfg->model_type != FG_MODEL_SONGUNET && cfg->model_type != FG_MODEL_DHARIWAL) return fail(FG_EINVAL, "bad model_type");
     fg_edm* h = new fg_edm();
     h->cfg = *cfg;
     h->cmode = cfg->compute_dtype;
     h->dtype = cfg->compute_dtype == FG_DTYPE_BF16 ? 1 : 0;
     h->emb_ch = cfg->model_channels * cfg->channel_mult_emb;
+    int rc;
+    if (cfg->model_type == FG_MODEL_DHARIWAL) {
+        // DhariwalUNet: cond_channels = model_channels (no channel_mult_noise), activations fp32 in both convolution modes
+        h->adm = new AdmNet();
+        h->dtype = 0;
+        h->noise_ch = h->cond_ch = cfg->model_channels;
+        adm_build_layout(h);
+        rc = adm_check_supported(h);
+        if (rc) {
+            delete h->adm;
+            delete h;
+            return rc;
+        }
+        *out = h;
+        return FG_OK;
+    }
     h->noise_ch = cfg->model_channels * cfg->channel_mult_noise;
     h->cond_ch = h->noise_ch * (cfg->r_timestep ? 2 : 1);
     build_layout(h);
-    int rc = check_supported(h);
+    rc = check_supported(h);
     if (rc) {
         delete h;
         return rc;
@@ -790,6 +834,7 @@ void fg_edm_destroy(fg_edm* h) {
         if (e) (void)hipEventDestroy(e);
     if (h->cap_stream) (void)hipStreamDestroy(h->cap_stream);
     for (hipEvent_t e : h->prof_ev) (void)hipEventDestroy(e);
+    delete h->adm;
     delete h;
 }
 
@@ -819,6 +864,18 @@ int fg_edm_bind_param(fg_edm* h, const char* name, const float* device_ptr, int6
 int fg_edm_pack_weights(fg_edm* h, void* stream) {
     if (!h) return fail(FG_EINVAL, "null handle");
     hipStream_t s = (hipStream_t)stream;
+    if (h->adm) {
+        for (const Param& p : h->params) {
+            const bool unused = p.name == "model.map_augment.weight" || p.name.rfind("model.logvar_linear", 0) == 0;
+            if (!p.ptr && !unused) return fail(FG_ENOTREADY, "parameter '%s' is not bound", p.name.c_str());
+        }
+        ++h->pack_epoch;
+        const int rc = adm_pack_weights(h, s);
+        if (rc) return rc;
+        drop_graph(h);
+        h->packed = true;
+        return FG_OK;
+    }
     int rc0 = ensure_device_state(h);
     if (rc0) return rc0;
     for (const Param& p : h->params) {
@@ -901,6 +958,7 @@ int fg_edm_forward_features(fg_edm* h, const float* x_t, const double* t, const 
                             float* out, float* const* features, int batch, void* workspace, size_t workspace_bytes,
                             void* stream) {
     if (!h || !x_t || !t || !features) return fail(FG_EINVAL, "null argument");
+    if (h->adm) return adm_refuse(h, "fg_edm_forward_features");
     if (!h->packed) return fail(FG_ENOTREADY, "weights are not packed (call fg_edm_pack_weights)");
     if (out == x_t) return fail(FG_EINVAL, "out must not alias x_t");
     if (r && !h->cfg.r_timestep) return fail(FG_EINVAL, "r_noise_labels provided, but r_timestep is not set");
@@ -1116,6 +1174,7 @@ int fg_edm_block_info(const fg_edm* h, int index, const char** key, int* cin, in
 int fg_edm_run_block(fg_edm* h, int index, const float* x1, int c1, const float* x2, int c2, const float* emb, float* out,
                      int batch, void* workspace, size_t workspace_bytes, void* stream) {
     if (!h || !x1 || !emb || !out) return fail(FG_EINVAL, "null argument");
+    if (h->adm) return adm_refuse(h, "fg_edm_run_block");
     if (!h->packed) return fail(FG_ENOTREADY, "weights are not packed (call fg_edm_pack_weights)");
     if (index < 0 || index >= (int)h->blocks.size()) return fail(FG_EINVAL, "block index out of range");
     Workspace w;

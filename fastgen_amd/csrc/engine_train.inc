@@ -641,6 +641,7 @@ int run_jvp(fg_edm* h, const float* x_t, const double* t, const double* r, const
 int fg_edm_jvp(fg_edm* h, const float* x_t, const double* t, const double* r, const float* labels, const float* vx, const float* vt,
                const float* vr, float* out, float* jvp, int batch, void* workspace, size_t workspace_bytes, void* stream) {
     if (!h || !x_t || !t || !vx || !out || !jvp) return fail(FG_EINVAL, "null argument");
+    if (h->adm) return adm_refuse(h, "fg_edm_jvp");
     if (!h->packed) return fail(FG_ENOTREADY, "weights are not packed (call fg_edm_pack_weights)");
     if (h->cmode == FG_DTYPE_F32) return fail(FG_EINVAL, "the forward-mode pass runs in the bf16 and bf16x3 compute modes (not in exact fp32)");
     if (h->cfg.r_timestep && !r) return fail(FG_EINVAL, "r is required by an r_timestep network");
@@ -656,7 +657,7 @@ int fg_edm_jvp(fg_edm* h, const float* x_t, const double* t, const double* r, co
 }
 
 size_t fg_edm_backward_workspace_bytes(const fg_edm* h, int batch) {
-    if (!h || batch <= 0) return 0;
+    if (!h || batch <= 0 || h->adm) return 0;
     Arena A;
     A.dry = true;
     Workspace w;
@@ -668,6 +669,7 @@ size_t fg_edm_backward_workspace_bytes(const fg_edm* h, int batch) {
 int fg_edm_forward_train(fg_edm* h, const float* x_t, const double* t, const double* r, const float* labels, float* out,
                          float* const* features, int batch, void* workspace, size_t workspace_bytes, void* stream) {
     if (!h || !x_t || !t || (!out && !features)) return fail(FG_EINVAL, "null argument");
+    if (h->adm) return adm_refuse(h, "fg_edm_forward_train");
     if (!h->packed) return fail(FG_ENOTREADY, "weights are not packed (call fg_edm_pack_weights)");
     if (h->cmode == FG_DTYPE_F32) return fail(FG_EINVAL, "the backward pass runs in the bf16 and bf16x3 compute modes (not in exact fp32)");
     if (features)
@@ -702,6 +704,7 @@ int fg_edm_backward_part(fg_edm* h, const float* x_t, const double* t, const dou
                          const float* const* dfeatures, float* out, float* dx_t, int have_forward, int parts, int batch,
                          void* workspace, size_t workspace_bytes, void* stream) {
     if (!h || !x_t || !t || (!dout && !dfeatures)) return fail(FG_EINVAL, "null argument");
+    if (h->adm) return adm_refuse(h, "the backward pass");
     if (parts <= 0 || (parts & ~7)) return fail(FG_EINVAL, "parts must be a non-empty mask of FG_BWD_*");
     if (dout && !out && !have_forward) return fail(FG_EINVAL, "out is required when the forward runs here");
     if (!h->packed) return fail(FG_ENOTREADY, "weights are not packed (call fg_edm_pack_weights)");
@@ -744,6 +747,7 @@ int fg_edm_run_block_backward(fg_edm* h, int index, const float* x1, int c1, con
                               const float* dout, float* dx1, float* dx2, float* demb, int batch, void* workspace,
                               size_t workspace_bytes, void* stream) {
     if (!h || !x1 || !emb || !dout) return fail(FG_EINVAL, "null argument");
+    if (h->adm) return adm_refuse(h, "the backward pass");
     if (!h->packed) return fail(FG_ENOTREADY, "weights are not packed (call fg_edm_pack_weights)");
     if (h->cmode == FG_DTYPE_F32) return fail(FG_EINVAL, "the backward pass runs in the bf16 and bf16x3 compute modes (not in exact fp32)");
     if (index < 0 || index >= (int)h->blocks.size()) return fail(FG_EINVAL, "block index out of range");

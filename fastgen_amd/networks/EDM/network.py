@@ -19,8 +19,14 @@ config_mf_cifar10.py: r_timestep=True, drop_precond='both', schedule_type='rf', 
 `feature_indices` / `return_features_early` (the encoder `block3` taps the DMD2 discriminator reads,
 EDM/network.py:525-544) are served by the same engine, forward only.
 
-Not provided on this path (raises, never falls back): non-SongUNet model types, and any device but a
-HIP GPU.
+`model_type="DhariwalUNet"` (the ADM network of EDM_ImageNet64_Config, fastgen/configs/net.py:50-66, and the reference's own
+default) is served for sampling: `forward` (any `fwd_pred_type`, `return_logvar`), the fused few-step loop behind
+`FastGenModel.generator_fn` and `sample()`, in the 'bf16x3' and 'bf16' compute modes, same 555-entry state dict at the in64 size.
+Its training-side paths (autograd, jvp, feature taps, dropout in train() mode, FSDP2), r_timestep and the exact-fp32 mode raise
+NotImplementedError; the SongUNet-only keywords (embedding_type, channel_mult_noise, encoder_type, decoder_type, resample_filter)
+raise ValueError with it.
+
+Not provided on this path (raises, never falls back): other model types, and any device but a HIP GPU.
 """
 from __future__ import annotations
 
@@ -295,8 +301,11 @@ class EDMPrecond(FastGenNetwork):
         **model_kwargs,
     ):
         super().__init__(net_pred_type=net_pred_type, schedule_type=schedule_type, **model_kwargs)
-        if model_type != "SongUNet":
-            raise ValueError(f"fastgen_amd implements model_type='SongUNet' only, got '{model_type}'")
+        if model_type not in ("SongUNet", "DhariwalUNet"):
+            raise ValueError(f"fastgen_amd implements model_type 'SongUNet' and 'DhariwalUNet', got '{model_type}'")
+        self.model_type = model_type
+        if model_type == "DhariwalUNet":
+            model_kwargs = self._dhariwal_kwargs(model_kwargs, compute_dtype)
         if drop_precond is not None and drop_precond not in ["input", "output", "both"]:
             raise ValueError(f"drop_precond must be one of 'input', 'output', 'both', or None, got {drop_precond}")
         if self.noise_scheduler.schedule_id < 0:
@@ -346,17 +355,20 @@ class EDMPrecond(FastGenNetwork):
         cfg.drop_precond = {None: 0, "input": _lib.FG_DROP_PRECOND_INPUT, "output": _lib.FG_DROP_PRECOND_OUTPUT,
                             "both": _lib.FG_DROP_PRECOND_INPUT | _lib.FG_DROP_PRECOND_OUTPUT}[drop_precond]
         cfg.schedule = self.noise_scheduler.schedule_id
+        cfg.model_type = _lib.FG_MODEL_DHARIWAL if self.is_adm else _lib.FG_MODEL_SONGUNET
         self._cfg = cfg
         self._engines: Dict[int, ctypes.c_void_p] = {}
         self._bound_sig: Dict[int, Any] = {}
         self._pack_refs: Dict[int, list] = {}
         self._ws: Dict[int, torch.Tensor] = {}
-        self._noise_channels = cfg.model_channels * cfg.channel_mult_noise
+        self._noise_channels = cfg.model_channels * (1 if self.is_adm else cfg.channel_mult_noise)
 
         # parameter tree with the reference's key paths; names/shapes come from the library's own plan
         self.model = _UNet()
         self._param_names: List[str] = []
-        h = self._make_engine(_lib.FG_DTYPE_F32)
+        # (DhariwalUNet has no exact-fp32 engine: its parameter plan is read from a split-bf16 one)
+        plan_dt = _lib.FG_DTYPE_BF16X3 if self.is_adm else _lib.FG_DTYPE_F32
+        h = self._make_engine(plan_dt)
         L = _lib.lib()
         name, ndim, shape = ctypes.c_char_p(), ctypes.c_int(), (ctypes.c_int64 * 4)()
         for i in range(L.fg_edm_num_params(h)):
@@ -373,7 +385,16 @@ class EDMPrecond(FastGenNetwork):
             # the reference keeps the constant 2x2 resampling kernel as a persistent buffer (EDM/network.py:89-91)
             if parts[-1] == "weight" and parts[-2] in ("conv0", "skip") and (parts[-3].endswith("_down") or parts[-3].endswith("_up")):
                 node.register_buffer("resample_filter", torch.full((1, 1, 2, 2), 0.25))
-        self._engines[_lib.FG_DTYPE_F32] = h
+        if self.is_adm:
+            # DhariwalUNet's up / down blocks keep their width: their skip is a weightless resampling Conv2d (kernel 0) whose only
+            # state is the filter buffer (EDM/network.py:249-259)
+            for group in (self.model._modules["enc"], self.model._modules["dec"]):
+                for key, block in group._modules.items():
+                    if key.endswith("_down") or key.endswith("_up"):
+                        skip = _Node()
+                        skip.register_buffer("resample_filter", torch.full((1, 1, 2, 2), 0.25))
+                        block.add_module("skip", skip)
+        self._engines[plan_dt] = h
         # (leaf module, parameter name) of every engine parameter, in engine order (see _engine)
         self._leafs = []
         for full in self._param_names:
@@ -381,6 +402,29 @@ class EDMPrecond(FastGenNetwork):
             for p_ in parts[:-1]:
                 node = node._modules[p_]
             self._leafs.append((node, parts[-1]))
+
+    @property
+    def is_adm(self) -> bool:
+        return self.model_type == "DhariwalUNet"
+
+    @staticmethod
+    def _dhariwal_kwargs(mk: Dict[str, Any], compute_dtype: Optional[str]) -> Dict[str, Any]:
+        """DhariwalUNet's constructor defaults (EDM/network.py:585-600) and the refusals of this path."""
+        song_only = [k for k in ("embedding_type", "channel_mult_noise", "encoder_type", "decoder_type", "resample_filter") if k in mk]
+        if song_only:
+            raise ValueError(f"{', '.join(song_only)}: SongUNet-only keyword(s), not accepted with model_type='DhariwalUNet'")
+        if mk.get("r_timestep", False):
+            raise NotImplementedError("r_timestep=True is not implemented for DhariwalUNet by the fused MI355X path")
+        if compute_dtype == "fp32":
+            raise NotImplementedError("DhariwalUNet runs in the 'bf16x3' (default) and 'bf16' compute modes, not in exact fp32")
+        out = dict(model_channels=192, channel_mult=[1, 2, 3, 4], channel_mult_emb=4, num_blocks=3, attn_resolutions=[32, 16, 8],
+                   dropout=0.10)
+        out.update(mk)
+        return out
+
+    def _refuse_adm(self, what: str):
+        if self.is_adm:
+            raise NotImplementedError(f"{what} is not implemented for DhariwalUNet by the fused MI355X path (forward and sampling only)")
 
     # ------------------------------------------------------------------------------------------------
     def _make_engine(self, dtype: int):
@@ -410,6 +454,8 @@ class EDMPrecond(FastGenNetwork):
                      if not n.startswith("model.logvar_linear") and (with_augment or n != "model.map_augment.weight"))
 
     def _select_dtype(self) -> int:
+        if self.is_adm and (self.compute_dtype or (None if torch.is_autocast_enabled() else DEFAULT_FP32_MODE)) == "fp32":
+            raise NotImplementedError("DhariwalUNet runs in the 'bf16x3' and 'bf16' compute modes, not in exact fp32")
         if self.compute_dtype is not None:
             return _lib.DTYPE_NAMES[self.compute_dtype]
         if torch.is_autocast_enabled():
@@ -485,6 +531,7 @@ class EDMPrecond(FastGenNetwork):
         the parameters and to x_t - what the DMD2 student / fake-score updates and its GAN branch need (dmd2.py) - in the
         split-bf16 mode (fp32 tensors, the default outside autocast: the reference's `precision="float32"` training,
         configs/config.py:167-169) and in the bf16 mode (under bf16 autocast).  The exact-fp32 mode has no backward."""
+        self._refuse_adm("a forward with autograd (or train() mode with dropout)")
         if self._select_dtype() == _lib.FG_DTYPE_F32:
             raise NotImplementedError(
                 "fastgen_amd.EDMPrecond: the backward pass runs in the 'bf16x3' (default) and 'bf16' compute modes, not in the "
@@ -570,6 +617,7 @@ class EDMPrecond(FastGenNetwork):
         Function all-gathers the blocks, the engine writes whole gradients, autograd accumulates them into the unsharded
         parameters' .grad, and FSDP2's post-backward callback reduce-scatters every group (reduce dtype fp32, as configured by
         utils/distributed/fsdp.py:116-122) and reshards."""
+        self._refuse_adm("fully_shard")
         from torch.distributed.fsdp import fully_shard
 
         for group in (self.model._modules["enc"], self.model._modules["dec"]):
@@ -632,6 +680,8 @@ class EDMPrecond(FastGenNetwork):
     ):
         if feature_indices is None:
             feature_indices = {}
+        if self.is_adm and (return_features_early or len(feature_indices)):
+            self._refuse_adm("feature_indices / return_features_early")
         if return_features_early and len(feature_indices) == 0:
             return []
         if fwd_pred_type is None:
@@ -651,6 +701,8 @@ class EDMPrecond(FastGenNetwork):
         needs_grad = self._needs_grad(x_t)
         if needs_grad or (self.training and self.dropout):
             self._check_trainable_call(return_logvar)
+        if self.is_adm:
+            self._select_dtype()  # refuses the exact-fp32 mode before anything else
         if x_t.device.type != "cuda":
             raise RuntimeError("fastgen_amd runs on a HIP GPU only (no CPU path); got a tensor on " + str(x_t.device))
         if x_t.dim() != 4 or x_t.shape[1] != self.img_channels or x_t.shape[2] != self.img_resolution or x_t.shape[3] != self.img_resolution:
@@ -749,6 +801,7 @@ class EDMPrecond(FastGenNetwork):
         """(output, directional derivative) of `forward(x_t, t, condition=condition, r=r)` along (v_x, v_t, v_r) - what
         `torch.func.jvp(net_wrapper, (x_t, t, r), tangents)` returns in MeanFlowModel._jvp / sCM (mean_flow.py:240-250, sCM.py:179),
         as one library call (fg_edm_jvp, bf16 compute mode).  No graph is built (the reference detaches the result too)."""
+        self._refuse_adm("jvp")
         if fwd_pred_type is not None and fwd_pred_type != self.net_pred_type:
             raise NotImplementedError("jvp is provided for the network's own prediction type")
         if r is None and self.r_timestep:
@@ -786,13 +839,14 @@ class EDMPrecond(FastGenNetwork):
         return out.to(x_t.dtype), jv.to(x_t.dtype)
 
     def _logvar(self, t64: torch.Tensor) -> torch.Tensor:
-        """logvar_linear(PositionalEmbedding(c_noise)) — the un-flipped [cos|sin] embedding (EDM/network.py:501,571)."""
+        """logvar_linear(PositionalEmbedding(c_noise)) — the un-flipped [cos|sin] embedding (EDM/network.py:501,571; DhariwalUNet:
+        endpoint=False, :697, 737-738)."""
         if self.drop_precond in ("input", "both"):
             c_noise = t64.to(torch.float32)
         else:
             c_noise = (t64.clamp(min=self.noise_scheduler.clamp_min).log() / 4).to(torch.float32)
         half = self._noise_channels // 2
-        freqs = torch.arange(half, dtype=torch.float32, device=t64.device) / (half - 1)
+        freqs = torch.arange(half, dtype=torch.float32, device=t64.device) / (half if self.is_adm else half - 1)
         freqs = (1 / 10000) ** freqs
         ang = c_noise.ger(freqs)
         emb = torch.cat([ang.cos(), ang.sin()], dim=1)

@@ -62,6 +62,16 @@ extern "C" {
 
 #define FG_MAX_LEVELS 8
 
+/* fg_edm_config.model_type: the U-Net inside EDMPrecond (EDM/network.py:830-836). */
+#define FG_MODEL_SONGUNET 0  /* DDPM++ (SongUNet, :322-574): everything below unless stated otherwise */
+/* ADM (DhariwalUNet, :584-740; configs/net.py:50-66, the ImageNet-64 teacher): adaptive-scale blocks with GroupNorm eps 1e-5,
+ * skip_scale 1, 64-channel attention heads, a [cos | sin] noise embedding and a bias-free map_label added after map_layer1.
+ * Forward and sampling only: fg_edm_create / param_info / bind / pack / workspace_bytes / fg_edm_forward / fg_sampler_run.
+ * The feature taps, fg_edm_run_block, backward, jvp and training entry points return FG_EINVAL on such a handle.  compute_dtype
+ * FG_DTYPE_BF16X3 or FG_DTYPE_BF16 (activations stay fp32 in both); r_timestep 0; img_resolution 8 .. 64; every level's width
+ * a multiple of 64; attention at 8x8 .. 32x32.  cfg.channel_mult_noise is ignored (cond_channels = model_channels). */
+#define FG_MODEL_DHARIWAL 1
+
 /* kwargs of EDMPrecond(model_type="SongUNet", embedding_type="positional", encoder_type=decoder_type="standard",
  * resample_filter=[1,1], dropout=0) — fastgen/configs/net.py:29-48 and EDM/network.py:347-367, 809-821. */
 typedef struct fg_edm_config {
@@ -83,6 +93,7 @@ typedef struct fg_edm_config {
     int r_timestep;                      /* 1: second (target-time) embedding, cond_channels doubled (EDM/network.py:376,401-408) */
     int drop_precond;                    /* bit mask of FG_DROP_PRECOND_* (0 = full EDM preconditioning) */
     int schedule;                        /* FG_SCHEDULE_*: the noise schedule the sampler loop re-noises with */
+    int model_type;                      /* FG_MODEL_*: 0 (a zero-initialised config) = SongUNet */
 } fg_edm_config;
 
 typedef struct fg_edm fg_edm; /* opaque */
