@@ -78,6 +78,15 @@ SIGNATURES = {
     "fg_edm_run_block": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p,
                                  c_size_t, c_void_p]),
     "fg_op_gn_coeffs": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_float, c_void_p, c_int, c_int, c_void_p]),
+    "fg_op_adm_conv_pack_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "fg_op_adm_conv_pack": (c_int, [c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
+    "fg_op_adm_conv": (c_int, [c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p,
+                               c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p]),
+    "fg_op_adm_gn_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "fg_op_adm_gn_coeffs": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_float, c_void_p, c_int, c_void_p, c_int,
+                                    c_int, c_void_p, c_size_t, c_void_p]),
+    "fg_op_adm_attention": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
+    "fg_op_adm_map_in": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p]),
     "fg_op_latents": (c_int, [c_void_p, c_double, c_void_p, c_int64, c_void_p]),
     "fg_op_forward_process": (c_int, [c_void_p, c_void_p, c_double, c_int, c_void_p, c_int64, c_void_p]),
     "fg_op_x0_to_eps": (c_int, [c_void_p, c_void_p, c_double, c_int, c_void_p, c_int64, c_void_p]),

@@ -1156,10 +1156,14 @@ FG_API int fg_debug_conv_bench(int dtype, int batch, int cin, int res, int ks, i
     return FG_OK;
 }
 
-int fg_edm_num_blocks(const fg_edm* h) { return h ? (int)h->blocks.size() : 0; }
+int fg_edm_num_blocks(const fg_edm* h) {
+    if (h && h->adm) return adm_num_blocks(h);
+    return h ? (int)h->blocks.size() : 0;
+}
 
 int fg_edm_block_info(const fg_edm* h, int index, const char** key, int* cin, int* cout, int* res_in, int* res_out,
                       int* has_attention) {
+    if (h && h->adm) return adm_block_info(h, index, key, cin, cout, res_in, res_out, has_attention);
     if (!h || index < 0 || index >= (int)h->blocks.size()) return fail(FG_EINVAL, "block index out of range");
     const Block* b = h->blocks[index];
     if (key) *key = b->key.c_str();
@@ -1174,7 +1178,7 @@ int fg_edm_block_info(const fg_edm* h, int index, const char** key, int* cin, in
 int fg_edm_run_block(fg_edm* h, int index, const float* x1, int c1, const float* x2, int c2, const float* emb, float* out,
                      int batch, void* workspace, size_t workspace_bytes, void* stream) {
     if (!h || !x1 || !emb || !out) return fail(FG_EINVAL, "null argument");
-    if (h->adm) return adm_refuse(h, "fg_edm_run_block");
+    if (h->adm) return adm_run_block(h, index, x1, c1, x2, c2, emb, out, batch, workspace, workspace_bytes, (hipStream_t)stream);
     if (!h->packed) return fail(FG_ENOTREADY, "weights are not packed (call fg_edm_pack_weights)");
     if (index < 0 || index >= (int)h->blocks.size()) return fail(FG_EINVAL, "block index out of range");
     Workspace w;
@@ -1208,6 +1212,82 @@ int fg_op_gn_coeffs(const float* x1, int c1, const float* x2, int c2, const floa
                     float* ab_out, int batch, int hw, void* stream) {
     if (!x1 || !gamma || !beta || !ab_out) return fail(FG_EINVAL, "null argument");
     HIP_TRY(launch_gn_coeffs(0, x1, c1, c2 ? x2 : nullptr, c2, gamma, beta, eps, (float2*)ab_out, batch, hw, (hipStream_t)stream));
+    return FG_OK;
+}
+
+size_t fg_op_adm_conv_pack_bytes(int mode, int cout, int cin, int ks) {
+    if ((mode != FG_DTYPE_BF16 && mode != FG_DTYPE_BF16X3) || (ks != 1 && ks != 3) || cout <= 0 || cin <= 0 || cin % 32) return 0;
+    return adm_conv_pack_elems(mode, cout, cin, ks) * sizeof(__bf16);
+}
+int fg_op_adm_conv_pack(int mode, const float* w_oihw, void* packed, int cout, int cin, int ks, void* stream) {
+    if (!fg_op_adm_conv_pack_bytes(mode, cout, cin, ks))
+        return fail(FG_EINVAL, "fg_op_adm_conv_pack: mode %d (1 bf16, 2 bf16x3), ks %d (1, 3), cout %d > 0, cin %d (multiple of 32)", mode,
+                    ks, cout, cin);
+    if (!w_oihw || !packed) return fail(FG_EINVAL, "fg_op_adm_conv_pack: null pointer");
+    HIP_TRY(adm_pack_conv_weights(mode, w_oihw, packed, cout, cin, ks, (hipStream_t)stream));
+    return FG_OK;
+}
+int fg_op_adm_conv(int mode, int ks, const float* src1, int c1, const float* src2, int c2, int batch, int hs, int h, int res_mode,
+                   const float* ab, int silu, const void* packed, const float* bias, const float* resid, int resid_mode, float* out,
+                   int cout, void* stream) {
+    if ((mode != FG_DTYPE_BF16 && mode != FG_DTYPE_BF16X3) || (ks != 1 && ks != 3))
+        return fail(FG_EINVAL, "fg_op_adm_conv: mode %d (1 bf16, 2 bf16x3), ks %d (1, 3)", mode, ks);
+    if (c1 <= 0 || c1 % 32 || c2 < 0 || c2 % 32 || cout <= 0 || batch <= 0 || batch > 65535)
+        return fail(FG_EINVAL, "fg_op_adm_conv: c1 %d > 0 and c2 %d >= 0 multiples of 32, cout %d > 0, batch %d in 1 .. 65535", c1, c2,
+                    cout, batch);
+    const bool res_ok = (res_mode == 0 && hs == h) || (res_mode == 1 && hs == 2 * h) || (res_mode == 2 && h == 2 * hs);
+    if (h <= 0 || h > 4096 || !res_ok) return fail(FG_EINVAL, "fg_op_adm_conv: res_mode %d with hs %d, h %d", res_mode, hs, h);
+    if (resid && (resid_mode < 0 || resid_mode > 2 || (resid_mode == 2 && h % 2)))
+        return fail(FG_EINVAL, "fg_op_adm_conv: resid_mode %d (0, 1, 2 with h even) at h %d", resid_mode, h);
+    if (!src1 || (c2 && !src2) || !packed || !out) return fail(FG_EINVAL, "fg_op_adm_conv: null pointer");
+    if (((uintptr_t)src1 | (uintptr_t)(c2 ? src2 : nullptr) | (uintptr_t)packed) & 15 || (uintptr_t)ab & 7)
+        return fail(FG_EINVAL, "fg_op_adm_conv: src1 / src2 / packed must be 16-byte aligned, ab 8-byte aligned");
+    AdmConvArgs a;
+    a.src1 = src1, a.src2 = c2 ? src2 : nullptr, a.C1 = c1, a.C2 = c2, a.Hs = hs, a.H = h, a.B = batch, a.res_mode = res_mode;
+    a.ab = (const float2*)ab, a.silu = silu ? 1 : 0, a.w = packed, a.bias = bias, a.resid = resid, a.resid_mode = resid ? resid_mode : 0;
+    a.out = out, a.Cout = cout;
+    HIP_TRY(adm_launch_conv(mode, ks, a, (hipStream_t)stream));
+    return FG_OK;
+}
+size_t fg_op_adm_gn_workspace_bytes(int batch, int hw, int c) {
+    if (batch <= 0 || hw <= 0 || c <= 0) return 0;
+    return adm_gn_part_elems(batch, hw, c) * sizeof(float2);
+}
+int fg_op_adm_gn_coeffs(const float* x1, int c1, const float* x2, int c2, const float* gamma, const float* beta, float eps,
+                        const float* temb, int temb_stride, float* ab_out, int batch, int hw, void* workspace, size_t workspace_bytes,
+                        void* stream) {
+    const int C = c1 + c2;
+    if (c1 <= 0 || c1 % 2 || c2 < 0 || c2 % 2 || C < 8)
+        return fail(FG_EINVAL, "fg_op_adm_gn_coeffs: c1 %d > 0 and c2 %d >= 0 must be even, c1 + c2 >= 8", c1, c2);
+    const int G = std::min(32, C / 4);
+    if (C % G || (C / G) % 2)
+        return fail(FG_EINVAL, "fg_op_adm_gn_coeffs: %d channels in %d groups: the group size must be a whole, even number", C, G);
+    if (batch <= 0 || batch > 65535 || hw <= 0 || hw > (1 << 22))
+        return fail(FG_EINVAL, "fg_op_adm_gn_coeffs: batch %d (1 .. 65535), hw %d (1 .. 2^22)", batch, hw);
+    if (temb && temb_stride < 2 * C) return fail(FG_EINVAL, "fg_op_adm_gn_coeffs: temb_stride %d < 2 C = %d", temb_stride, 2 * C);
+    if (!x1 || (c2 && !x2) || !gamma || !beta || !ab_out || !workspace) return fail(FG_EINVAL, "fg_op_adm_gn_coeffs: null pointer");
+    if (((uintptr_t)x1 | (uintptr_t)(c2 ? x2 : nullptr) | (uintptr_t)ab_out | (uintptr_t)workspace) & 7)
+        return fail(FG_EINVAL, "fg_op_adm_gn_coeffs: x1 / x2 / ab_out / workspace must be 8-byte aligned");
+    const size_t need = fg_op_adm_gn_workspace_bytes(batch, hw, C);
+    if (workspace_bytes < need)
+        return fail(FG_EINVAL, "fg_op_adm_gn_coeffs: workspace too small (%zu < %zu bytes)", workspace_bytes, need);
+    HIP_TRY(adm_launch_gn(x1, c1, c2 ? x2 : nullptr, c2, gamma, beta, eps, temb, temb_stride, (float2*)workspace, (float2*)ab_out, batch,
+                          hw, (hipStream_t)stream));
+    return FG_OK;
+}
+int fg_op_adm_attention(const float* qkv, float* out, int batch, int t, int heads, void* stream) {
+    if (t <= 0 || t % 64 || heads <= 0 || heads > 65535 || batch <= 0 || batch > 65535)
+        return fail(FG_EINVAL, "fg_op_adm_attention: t %d (a positive multiple of 64), heads %d, batch %d (1 .. 65535)", t, heads, batch);
+    if (!qkv || !out) return fail(FG_EINVAL, "fg_op_adm_attention: null pointer");
+    HIP_TRY(adm_launch_attention(qkv, out, batch, t, heads, (hipStream_t)stream));
+    return FG_OK;
+}
+int fg_op_adm_map_in(const float* c_noise, const float* freqs, const float* aug, const float* wa, int aug_dim, float* out, int batch,
+                     int n, void* stream) {
+    if (batch <= 0 || n <= 0 || n % 2 || (int64_t)batch * n > (1 << 30) || (aug && aug_dim <= 0))
+        return fail(FG_EINVAL, "fg_op_adm_map_in: batch %d > 0, n %d > 0 even, aug_dim %d > 0 with aug", batch, n, aug_dim);
+    if (!c_noise || !freqs || !out || (aug && !wa)) return fail(FG_EINVAL, "fg_op_adm_map_in: null pointer");
+    HIP_TRY(adm_launch_map_in(c_noise, freqs, aug, aug ? wa : nullptr, aug ? aug_dim : 0, out, batch, n, (hipStream_t)stream));
     return FG_OK;
 }
 int fg_op_latents(const float* noise, double t_init, float* out, int64_t total, void* stream) {

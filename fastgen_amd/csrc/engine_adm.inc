@@ -320,3 +320,42 @@ int adm_forward(fg_edm* h, const float* x_t, const double* t, int t_stride, cons
     HIP_TRY(launch_aux_out(0, x, w.ab0, h->P(n->out_conv_w), h->P(n->out_conv_b), x_t, w.coef, out, B, R, n->out_cin, c.img_channels, s));
     return FG_OK;
 }
+
+// fg_edm_num_blocks / fg_edm_block_info / fg_edm_run_block on an ADM handle: the encoder blocks, then the decoder blocks.
+int adm_num_blocks(const fg_edm* h) { return (int)(h->adm->enc.size() + h->adm->dec.size()); }
+
+const AdmBlock* adm_block_at(const fg_edm* h, int index) {
+    const AdmNet* n = h->adm;
+    const int ne = (int)n->enc.size();
+    if (index < 0 || index >= adm_num_blocks(h)) return nullptr;
+    return index < ne ? &n->enc[index] : &n->dec[index - ne];
+}
+
+int adm_block_info(const fg_edm* h, int index, const char** key, int* cin, int* cout, int* res_in, int* res_out, int* has_attention) {
+    const AdmBlock* b = adm_block_at(h, index);
+    if (!b) return fail(FG_EINVAL, "block index out of range");
+    if (key) *key = b->key.c_str();
+    if (cin) *cin = b->cin;
+    if (cout) *cout = b->cout;
+    if (res_in) *res_in = b->res_in;
+    if (res_out) *res_out = b->res_out;
+    if (has_attention) *has_attention = b->attn ? 1 : 0;
+    return FG_OK;
+}
+
+// One block on caller tensors (fp32 NHWC, as the network keeps them): temb = affine(emb) as adm_forward computes it, then adm_block.
+int adm_run_block(fg_edm* h, int index, const float* x1, int c1, const float* x2, int c2, const float* emb, float* out, int B,
+                  void* workspace, size_t workspace_bytes, hipStream_t s) {
+    const AdmBlock* b = adm_block_at(h, index);
+    if (!b) return fail(FG_EINVAL, "block index out of range");
+    if (c1 <= 0 || c2 != b->skip_c || c1 + c2 != b->cin)
+        return fail(FG_EINVAL, "%s: channel split c1 = %d, c2 = %d; the block takes %d + %d (its skip)", b->key.c_str(), c1, c2,
+                    b->cin - b->skip_c, b->skip_c);
+    if (c2 && !x2) return fail(FG_EINVAL, "%s: x2 is null", b->key.c_str());
+    if (!h->packed) return fail(FG_ENOTREADY, "weights are not packed (call fg_edm_pack_weights)");
+    Workspace w;
+    int rc = setup_ws(h, B, workspace, workspace_bytes, w);
+    if (rc) return rc;
+    HIP_TRY(launch_linear(emb, h->aff_w, h->aff_b, w.temb, B, h->emb_ch, h->temb_total, 0, s));
+    return adm_block(h, *b, x1, c1, c2 ? x2 : nullptr, c2, out, B, w, s);
+}

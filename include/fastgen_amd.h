@@ -67,7 +67,8 @@ extern "C" {
 /* ADM (DhariwalUNet, :584-740; configs/net.py:50-66, the ImageNet-64 teacher): adaptive-scale blocks with GroupNorm eps 1e-5,
  * skip_scale 1, 64-channel attention heads, a [cos | sin] noise embedding and a bias-free map_label added after map_layer1.
  * Forward and sampling only: fg_edm_create / param_info / bind / pack / workspace_bytes / fg_edm_forward / fg_sampler_run.
- * The feature taps, fg_edm_run_block, backward, jvp and training entry points return FG_EINVAL on such a handle.  compute_dtype
+ * fg_edm_num_blocks / fg_edm_block_info / fg_edm_run_block serve its UNetBlocks (below); the feature taps, backward, jvp and
+ * training entry points return FG_EINVAL on such a handle.  compute_dtype
  * FG_DTYPE_BF16X3 or FG_DTYPE_BF16 (activations stay fp32 in both); r_timestep 0; img_resolution 8 .. 64; every level's width
  * a multiple of 64; attention at 8x8 .. 32x32.  cfg.channel_mult_noise is ignored (cond_channels = model_channels). */
 #define FG_MODEL_DHARIWAL 1
@@ -178,11 +179,43 @@ FG_API int fg_edm_block_info(const fg_edm* h, int index, const char** key, int* 
                       int* has_attention);
 FG_API int fg_edm_run_block(fg_edm* h, int index, const float* x1, int c1, const float* x2, int c2, const float* emb,
                      float* out, int batch, void* workspace, size_t workspace_bytes, void* stream);
+/* On an FG_MODEL_DHARIWAL handle the list is the encoder's UNetBlocks, then the decoder's (the stem and the output head are not
+ * blocks); key "model.enc.<res>x<res>_<name>" / "model.dec...."; res_in = 2 res_out for a down block, res_out / 2 for an up block.
+ * A decoder block's c2 is its skip width (cin minus the previous block's cout), 0 elsewhere; any other c1 / c2 split is FG_EINVAL. */
 
 /* GroupNorm statistics folded with the affine parameters: ab[b][c] = {a, b} with y = a*x + b
  * (GroupNorm.forward, EDM/network.py:141-149; groups = min(32, C/4)).  x NHWC fp32 [B,HW,C]. */
 FG_API int fg_op_gn_coeffs(const float* x1, int c1, const float* x2, int c2, const float* gamma, const float* beta,
                     float eps, float* ab_out, int batch, int hw, void* stream);
+
+/* ---- DhariwalUNet single-op entry points: the kernels fg_edm_forward runs on an FG_MODEL_DHARIWAL handle (fp32 NHWC tensors).
+ * Arguments are checked before anything is launched: a bad shape, mode or pointer is FG_EINVAL. */
+/* Convolution weights OIHW fp32 [cout][cin][ks][ks] -> the operand of fg_op_adm_conv.  mode FG_DTYPE_BF16 or FG_DTYPE_BF16X3 (hi and
+ * lo bf16 planes), ks 1 or 3, cin % 32 == 0.  _bytes: size of `packed`, 0 for an unsupported argument. */
+FG_API size_t fg_op_adm_conv_pack_bytes(int mode, int cout, int cin, int ks);
+FG_API int fg_op_adm_conv_pack(int mode, const float* w_oihw, void* packed, int cout, int cin, int ks, void* stream);
+/* out[b,y,x,co] = conv_ks(R(pro(x)))[co] + bias[co] (+ resid) with zero padding.  x = the channel concat [src1 (c1) | src2 (c2)]
+ * at resolution hs, c1 > 0 and c2 >= 0 multiples of 32; ab (nullable) [batch][c1 + c2] {a, b}: pro(x) = a x + b, then SiLU when
+ * silu != 0.  R: res_mode 0 identity (h = hs), 1 2x2 mean (hs = 2 h), 2 nearest 2x (h = 2 hs).  bias nullable.  resid
+ * (nullable) [batch][.][.][cout]: resid_mode 0 at h, 1 the 2x2 mean of a 2h tensor, 2 nearest from h / 2.  out [batch][h][h][cout].
+ * src1 / src2 / packed 16-byte aligned. */
+FG_API int fg_op_adm_conv(int mode, int ks, const float* src1, int c1, const float* src2, int c2, int batch, int hs, int h,
+                          int res_mode, const float* ab, int silu, const void* packed, const float* bias, const float* resid,
+                          int resid_mode, float* out, int cout, void* stream);
+/* GroupNorm (groups = min(32, C / 4), C = c1 + c2 even-sized groups, c1 / c2 even) of the concat [x1 | x2], NHWC [batch][hw][C]:
+ * ab_out[b][c] = {a, b} with norm(x) = a x + b; temb (nullable, row stride temb_stride >= 2C) folds the adaptive scale / shift:
+ * a (1 + temb[c]), b (1 + temb[c]) + temb[C + c].  workspace: fg_op_adm_gn_workspace_bytes (0: unsupported). */
+FG_API size_t fg_op_adm_gn_workspace_bytes(int batch, int hw, int c);
+FG_API int fg_op_adm_gn_coeffs(const float* x1, int c1, const float* x2, int c2, const float* gamma, const float* beta, float eps,
+                               const float* temb, int temb_stride, float* ab_out, int batch, int hw, void* workspace,
+                               size_t workspace_bytes, void* stream);
+/* Self-attention with head dim 64: qkv [batch][t][heads * 192], channel h * 192 + 3 c + j (j = q, k, v); out [batch][t][heads * 64]
+ * = softmax_k(q . k / 8) v.  t % 64 == 0. */
+FG_API int fg_op_adm_attention(const float* qkv, float* out, int batch, int t, int heads, void* stream);
+/* Mapping-network input: out[b] = [cos | sin](c_noise[b] * freqs) (+ wa aug[b] when aug != nullptr), freqs [n / 2], wa [n][aug_dim],
+ * out [batch][n], n even. */
+FG_API int fg_op_adm_map_in(const float* c_noise, const float* freqs, const float* aug, const float* wa, int aug_dim, float* out,
+                            int batch, int n, void* stream);
 
 /* Elementwise sampler steps in fp64 (noise_schedule.py:72-88, 425-449, 544-574); n = elements per sample. */
 FG_API int fg_op_latents(const float* noise, double t_init, float* out, int64_t total, void* stream);

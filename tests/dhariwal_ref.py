@@ -14,7 +14,8 @@ import torch
 import torch.nn.functional as F
 from torch import Tensor
 
-from oracle.edm_ref import attention, conv2d, edm_t_list, forward_process, group_norm, latents, linear, x0_to_eps
+from oracle.edm_ref import attention as attention_fp32
+from oracle.edm_ref import conv2d, edm_t_list, forward_process, group_norm, latents, linear, x0_to_eps
 
 EPS = 1e-5  # GroupNorm / UNetBlock eps of DhariwalUNet (EDM/network.py:134, 218)
 
@@ -190,6 +191,18 @@ def resample(x: Tensor, up: bool, down: bool) -> Tensor:
 
 def conv(x: Tensor, w: Optional[Tensor], b: Optional[Tensor], up=False, down=False) -> Tensor:
     return conv2d(resample(x, up, down), w, b)
+
+
+def attention(qkv: Tensor, heads: int) -> Tensor:
+    """oracle.edm_ref.attention (logits and softmax in fp32, as the reference runs them); an fp64 qkv stays fp64 throughout, so that
+    the fp64 references of the kernel-parity tests carry no fp32 rounding."""
+    if qkv.dtype != torch.float64:
+        return attention_fp32(qkv, heads)
+    B, C3, H, W = qkv.shape
+    C = C3 // 3
+    q, k, v = qkv.reshape(B * heads, C // heads, 3, H * W).unbind(2)
+    w = torch.einsum("ncq,nck->nqk", q, k / math.sqrt(k.shape[1])).softmax(dim=2)
+    return torch.einsum("nqk,nck->ncq", w, v).reshape(B, C, H, W)
 
 
 def unet_block(sd, prefix: str, b: Block, x: Tensor, emb: Tensor) -> Tensor:

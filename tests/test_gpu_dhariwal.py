@@ -122,3 +122,14 @@ def test_full_in64(mode, tol):
     for steps in (1, 4):
         img = FastGenModel.generator_fn(net, noise, student_sample_steps=steps, condition=cond, student_sample_type="sde", seed=3)
         assert img.shape == noise.shape and torch.isfinite(img).all()
+    # the 4-step sampler equals the per-step loop through forward() and the noise schedule with the same explicit noise
+    eps = torch.stack([seeded((2, 3, 64, 64), s) for s in (14, 15, 16)]).cuda()
+    fused = FastGenModel.generator_fn(net, noise, student_sample_steps=4, condition=cond, student_sample_type="sde", eps=eps)
+    ns = net.noise_scheduler
+    tl = ns.get_t_list(4, device="cpu")
+    x = ns.latents(noise=noise, t_init=tl[0].cuda())
+    for i in range(4):
+        x0 = net(x, tl[i].cuda().expand(2), condition=cond)
+        if tl[i + 1] > 0:
+            x = ns.forward_process(x0, eps[i], tl[i + 1].cuda().expand(2))
+    assert (fused - x0).abs().max().item() <= 1e-4 * x0.abs().max().item()
