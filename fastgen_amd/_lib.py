@@ -29,6 +29,16 @@ class fg_edm_config(ctypes.Structure):
     ]
 
 
+class fg_edm2_config(ctypes.Structure):
+    _fields_ = [
+        ("img_resolution", c_int), ("img_channels", c_int), ("label_dim", c_int), ("model_channels", c_int), ("num_levels", c_int),
+        ("channel_mult", c_int * FG_MAX_LEVELS), ("channel_mult_noise", c_int), ("channel_mult_emb", c_int), ("num_blocks", c_int),
+        ("num_attn_resolutions", c_int), ("attn_resolutions", c_int * FG_MAX_LEVELS), ("label_balance", c_double),
+        ("concat_balance", c_double), ("res_balance", c_double), ("attn_balance", c_double), ("clip_act", c_double),
+        ("sigma_data", c_double), ("sigma_shift", c_double), ("compute_dtype", c_int), ("drop_precond", c_int),
+    ]
+
+
 class fg_dit_config(ctypes.Structure):
     _fields_ = [("input_size", c_int), ("patch_size", c_int), ("in_channels", c_int), ("hidden_size", c_int), ("depth", c_int),
                 ("num_heads", c_int), ("mlp_hidden", c_int), ("embedding_rows", c_int), ("r_timestep", c_int), ("compute_dtype", c_int)]
@@ -106,6 +116,22 @@ SIGNATURES = {
                                    c_int, c_void_p, c_size_t, c_void_p]),
     "fg_edm_backward_part": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
                                      c_int, c_int, c_void_p, c_size_t, c_void_p]),
+    "fg_edm2_create": (c_int, [POINTER(fg_edm2_config), POINTER(c_void_p)]),
+    "fg_edm2_destroy": (None, [c_void_p]),
+    "fg_edm2_num_params": (c_int, [c_void_p]),
+    "fg_edm2_param_info": (c_int, [c_void_p, c_int, POINTER(c_char_p), POINTER(c_int), POINTER(c_int64)]),
+    "fg_edm2_bind_param": (c_int, [c_void_p, c_char_p, c_void_p, c_int64]),
+    "fg_edm2_pack_weights": (c_int, [c_void_p, c_void_p]),
+    "fg_edm2_workspace_bytes": (c_size_t, [c_void_p, c_int]),
+    "fg_edm2_forward": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_size_t, c_void_p]),
+    "fg_edm2_set_training": (c_int, [c_void_p, c_int]),
+    "fg_edm2_sampler_run": (c_int, [c_void_p, c_void_p, c_void_p, POINTER(c_double), c_int, c_int, c_int, c_void_p, c_uint64,
+                                    c_void_p, c_int, c_void_p, c_size_t, c_int, c_void_p]),
+    "fg_edm2_num_blocks": (c_int, [c_void_p]),
+    "fg_edm2_block_info": (c_int, [c_void_p, c_int, POINTER(c_char_p), POINTER(c_int), POINTER(c_int), POINTER(c_int),
+                                   POINTER(c_int), POINTER(c_int)]),
+    "fg_edm2_run_block": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p,
+                                  c_size_t, c_void_p]),
     "fg_dit_create": (c_int, [POINTER(fg_dit_config), POINTER(c_void_p)]),
     "fg_dit_destroy": (None, [c_void_p]),
     "fg_dit_num_params": (c_int, [c_void_p]),

@@ -10,6 +10,8 @@
 //   input: the virtual concat [src1 (C1) | src2 (C2)] at resolution Hs; res_mode 0: H = Hs, 1: 2x2 mean of the transformed input
 //   (H = Hs / 2), 2: nearest 2x replication (H = 2 Hs).  pro: ab == nullptr -> identity, else a*x + b, then SiLU when silu != 0.
 //   resid (nullable): Cout channels NHWC; resid_mode 0: same resolution, 1: 2x2 mean of a [2H, 2H] tensor, 2: nearest from [H/2, H/2].
+//   EDM2 additions: ab_stride (per-image stride of ab in float2; -1: C1 + C2, 0: one row for every image), resid_scale (the residual
+//   enters as resid_scale * resid: mp_sum's skip weight), clip (> 0: the output is clamped to [-clip, clip] after the residual).
 struct AdmConvArgs {
     const float* src1 = nullptr;
     const float* src2 = nullptr;
@@ -24,6 +26,9 @@ struct AdmConvArgs {
     int resid_mode = 0;
     float* out = nullptr;
     int Cout = 0;
+    int ab_stride = -1;
+    float resid_scale = 1.0f;
+    float clip = 0.0f;
 };
 // packed weights: [Np][taps * Cin] bf16 (Np = Cout rounded up to 64, rows >= Cout zero), K index = tap * Cin + ci; the split-bf16
 // mode stores the lo plane behind the hi plane.  Elements (bf16) of that storage:
@@ -44,6 +49,9 @@ int adm_launch_gn(const float* x1, int C1, const float* x2, int C2, const float*
 // Multi-head self-attention of UNetBlock (EDM/network.py:290-296) with head dim 64: qkv [B, T, 3 C] NHWC as the qkv conv writes it,
 // channel h * 192 + 3 c + j (j = q, k, v); out [B, T, C] with channel h * 64 + c.  softmax_k(q . k / 8) in fp32.  T % 64 == 0.
 int adm_launch_attention(const float* qkv, float* out, int B, int T, int heads, hipStream_t s);
+// EDM2's cosine attention (Block.forward): the same layout, but each of q, k, v is pixel-normalised over its 64 channels on load,
+// x / (1e-4 + |x| / 8), before softmax_k(q . k / 8) v.
+int adm_launch_attention_mp(const float* qkv, float* out, int B, int T, int heads, hipStream_t s);
 
 // Mapping-network input of DhariwalUNet (EDM/network.py:697-716): [cos | sin] positional embedding of c_noise (endpoint=False,
 // no flip) + map_augment(aug) (nullable).  out [B][N].

@@ -48,7 +48,7 @@ __device__ __forceinline__ void load_src8(const AdmConvArgs& a, int b, int sy, i
 
 __device__ __forceinline__ void pro8(const AdmConvArgs& a, int b, int ch, float (&v)[8]) {
     if (!a.ab) return;
-    const float2* ab = a.ab + (size_t)b * (a.C1 + a.C2) + ch;
+    const float2* ab = a.ab + (size_t)b * (a.ab_stride < 0 ? a.C1 + a.C2 : a.ab_stride) + ch;
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
         const float2 k = ab[j];
@@ -179,18 +179,22 @@ __global__ __launch_bounds__(NTHR) void adm_conv_kernel(const AdmConvArgs a) {
             float v = acc[nt][i] + bo;
             if (a.resid) {
                 const int b = m / HW, rem = m % HW, y = rem / H, x = rem % H;
+                float r;
                 if (a.resid_mode == 0) {
-                    v += a.resid[(size_t)m * a.Cout + co];
+                    r = a.resid[(size_t)m * a.Cout + co];
                 } else if (a.resid_mode == 1) {
                     const int R = 2 * H;
                     const float* p = a.resid + (((size_t)b * R + 2 * y) * R + 2 * x) * a.Cout + co;
                     const size_t rs = (size_t)R * a.Cout;
-                    v += 0.25f * ((p[0] + p[a.Cout]) + (p[rs] + p[rs + a.Cout]));
+                    r = 0.25f * ((p[0] + p[a.Cout]) + (p[rs] + p[rs + a.Cout]));
                 } else {
                     const int R = H / 2;
-                    v += a.resid[(((size_t)b * R + (y >> 1)) * R + (x >> 1)) * a.Cout + co];
+                    r = a.resid[(((size_t)b * R + (y >> 1)) * R + (x >> 1)) * a.Cout + co];
                 }
+                if (a.resid_scale != 1.0f) r *= a.resid_scale;
+                v += r;
             }
+            if (a.clip > 0.0f) v = fminf(fmaxf(v, -a.clip), a.clip);
             a.out[(size_t)m * a.Cout + co] = v;
         }
     }
@@ -265,6 +269,30 @@ int gn_slots(int hw) { return hw >= 128 ? hw / 64 : 1; }
 // softmax (running max / sum per query, output rescaled).  Thread (tq, tk) = (tid / 16, tid % 16) owns queries 4 tq .. 4 tq + 3
 // and, for the scores, keys tk + 16 j (j < 2); for the output, dims tk + 16 j (j < 4).  LDS 41 KB.
 constexpr int AKT = 32;  // keys per tile
+
+// MP (EDM2) variant: rows [r0, r0 + n) of a [*][pitch] fp32 LDS tile divided by 1e-4 + |row| / 8 (normalize() over 64 channels).
+// Four threads per row; n * 4 <= NTHR.
+__device__ __forceinline__ void mp_norm_rows(float* tile, int pitch, int n, int tid) {
+    const int row = tid >> 2, part = tid & 3;
+    float ss = 0.f, inv = 0.f;
+    if (row < n) {
+        const float* p = tile + (size_t)row * pitch + part * 16;
+#pragma unroll
+        for (int d = 0; d < 16; ++d) ss = fmaf(p[d], p[d], ss);
+    }
+    ss += __shfl_xor(ss, 1);
+    ss += __shfl_xor(ss, 2);
+    __syncthreads();
+    if (row < n) {
+        inv = 1.0f / (1e-4f + sqrtf(ss) * 0.125f);
+        float* p = tile + (size_t)row * pitch + part * 16;
+#pragma unroll
+        for (int d = 0; d < 16; ++d) p[d] *= inv;
+    }
+    __syncthreads();
+}
+
+template <bool MP>
 __global__ __launch_bounds__(NTHR) void adm_attention_kernel(const float* __restrict__ qkv, float* __restrict__ out, int T, int heads) {
     __shared__ float Qs[64][65];                                // [q][d]
     __shared__ float Ks[AKT][65];                               // [k][d], pre-scaled by 1/sqrt(64) = 1/8 (exact)
@@ -278,6 +306,10 @@ __global__ __launch_bounds__(NTHR) void adm_attention_kernel(const float* __rest
         const int q = e >> 6, d = e & 63;
         Qs[q][d] = base[(size_t)(q0 + q) * C3 + 3 * d];
     }
+    if constexpr (MP) {
+        __syncthreads();
+        mp_norm_rows(&Qs[0][0], 65, 64, tid);
+    }
     float m[4], l[4], o[4][4];
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
@@ -290,10 +322,15 @@ __global__ __launch_bounds__(NTHR) void adm_attention_kernel(const float* __rest
         for (int e = tid; e < AKT * 64; e += NTHR) {
             const int k = e >> 6, d = e & 63;
             const float* p = base + (size_t)(k0 + k) * C3 + 3 * d;
-            Ks[k][d] = p[1] * 0.125f;
+            Ks[k][d] = MP ? p[1] : p[1] * 0.125f;
             Vs[k][d] = p[2];
         }
         __syncthreads();
+        if constexpr (MP) {  // rows 0..31 of Ks, then of Vs; the 1/8 of the logits after the normalisation
+            mp_norm_rows(tid < 128 ? &Ks[0][0] : &Vs[0][0], tid < 128 ? 65 : 64, AKT, tid & 127);
+            for (int e = tid; e < AKT * 64; e += NTHR) Ks[e >> 6][e & 63] *= 0.125f;
+            __syncthreads();
+        }
         float s[4][2];
 #pragma unroll
         for (int i = 0; i < 4; ++i) s[i][0] = s[i][1] = 0.f;
@@ -421,7 +458,13 @@ int adm_launch_gn(const float* x1, int C1, const float* x2, int C2, const float*
 
 int adm_launch_attention(const float* qkv, float* out, int B, int T, int heads, hipStream_t s) {
     if (T % 64 || T <= 0 || heads <= 0) return (int)hipErrorInvalidValue;  // whole query tiles, whole key tiles
-    hipLaunchKernelGGL(adm_attention_kernel, dim3(T / 64, heads, B), dim3(NTHR), 0, s, qkv, out, T, heads);
+    hipLaunchKernelGGL(adm_attention_kernel<false>, dim3(T / 64, heads, B), dim3(NTHR), 0, s, qkv, out, T, heads);
+    RET_LAST();
+}
+
+int adm_launch_attention_mp(const float* qkv, float* out, int B, int T, int heads, hipStream_t s) {
+    if (T % 64 || T <= 0 || heads <= 0) return (int)hipErrorInvalidValue;
+    hipLaunchKernelGGL(adm_attention_kernel<true>, dim3(T / 64, heads, B), dim3(NTHR), 0, s, qkv, out, T, heads);
     RET_LAST();
 }
 

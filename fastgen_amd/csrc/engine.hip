@@ -14,6 +14,7 @@
 #include "../../include/fastgen_amd.h"
 #include "common.h"
 #include "adm.h"
+#include "edm2.h"
 #include "conv.h"
 #include "misc.h"
 
@@ -1207,6 +1208,7 @@ int fg_edm_run_block(fg_edm* h, int index, const float* x1, int c1, const float*
 #include "engine_dit.inc"    // the DiT engine (fg_dit_*)
 #include "engine_wan.inc"    // the causal video DiT engine (fg_wan_*)
 #include "engine_sampler.inc"  // fg_dit_sampler_run / fg_wan_sampler_run: the student loops of the two transformer networks
+#include "engine_edm2.inc"     // the EDM2 U-Net engine (fg_edm2_*)
 
 int fg_op_gn_coeffs(const float* x1, int c1, const float* x2, int c2, const float* gamma, const float* beta, float eps,
                     float* ab_out, int batch, int hw, void* stream) {

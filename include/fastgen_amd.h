@@ -508,6 +508,72 @@ FG_API int fg_op_attention_split(const void* q, const void* k, const void* v, vo
 FG_API int fg_op_gemm_bf16(const void* a, const void* w, const float* bias, void* out, int m, int n, int k, int act, const float* gate,
                            int gate_stride, int gate_rows, const void* resid, int tile_order, void* stream);
 
+/* ================================ EDM2 U-Net (EDM2Precond, reference fastgen/networks/EDM2/network.py) ================================
+ * The magnitude-preserving ImageNet-64 network of the EDM2 consistency-model recipes, forward and few-step sampling only.  A handle of
+ * its own: EDM2's knobs (balances, clipping, gains, Fourier buffers) are not fg_edm_config fields.  Activations are fp32 NHWC inside;
+ * the convolutions run in FG_DTYPE_BF16X3 or FG_DTYPE_BF16.  Supported envelope (checked by fg_edm2_create, FG_EINVAL otherwise):
+ * img_resolution 8 .. 64 (power of two), img_channels 1 .. 4, every level width a multiple of 64, attention at resolutions >= 8 with
+ * 64-channel heads, lowest resolution >= 8. */
+typedef struct fg_edm2_config {
+    int img_resolution;                  /* 64 */
+    int img_channels;                    /* 3 */
+    int label_dim;                       /* 1000 (0 = unconditional) */
+    int model_channels;                  /* 192 (S) / 384 (XL) */
+    int num_levels;                      /* len(channel_mult) */
+    int channel_mult[FG_MAX_LEVELS];     /* {1,2,3,4} */
+    int channel_mult_noise;              /* 0 = None: noise embedding width = the first level's width */
+    int channel_mult_emb;                /* 0 = None: embedding width = the widest level's width */
+    int num_blocks;                      /* 3 */
+    int num_attn_resolutions;
+    int attn_resolutions[FG_MAX_LEVELS]; /* {16, 8} */
+    double label_balance;                /* 0.5 */
+    double concat_balance;               /* 0.5 */
+    double res_balance;                  /* 0.3 */
+    double attn_balance;                 /* 0.3 */
+    double clip_act;                     /* 256 (<= 0: no clipping) */
+    double sigma_data;                   /* 0.5 */
+    double sigma_shift;                  /* 0.0 (applied in eval mode only: see fg_edm2_set_training) */
+    int compute_dtype;                   /* FG_DTYPE_BF16X3 or FG_DTYPE_BF16 */
+    int drop_precond;                    /* bit mask of FG_DROP_PRECOND_* */
+} fg_edm2_config;
+
+typedef struct fg_edm2 fg_edm2; /* opaque */
+
+FG_API int fg_edm2_create(const fg_edm2_config* cfg, fg_edm2** out);
+FG_API void fg_edm2_destroy(fg_edm2* h);
+/* The engine's parameters in the reference's state_dict() order with its names ("unet.out_gain", "unet.emb_fourier.freqs",
+ * "unet.emb_fourier.phases", "unet.emb_noise.weight", ...): every weight-carrying entry of the U-Net plus the two Fourier buffers.
+ * The logvar head (logvar_fourier, logvar_linear) is not part of the engine. */
+FG_API int fg_edm2_num_params(const fg_edm2* h);
+FG_API int fg_edm2_param_info(const fg_edm2* h, int index, const char** name, int* ndim, int64_t shape[4]);
+/* Borrow a device fp32 tensor for a parameter (raw, un-normalised weights, as the module holds them). */
+FG_API int fg_edm2_bind_param(fg_edm2* h, const char* name, const float* device_ptr, int64_t numel);
+/* Normalise and pack every weight from the bound tensors: w / (1e-4 + |w_o| / sqrt(fan_in)) * gain / sqrt(fan_in) per output row,
+ * with mp_silu's 1/0.596 and mp_sum's / mp_cat's constant weights folded in.  Must run again after any bound tensor changed, the
+ * gains (emb_gain, out_gain) included. */
+FG_API int fg_edm2_pack_weights(fg_edm2* h, void* stream);
+FG_API size_t fg_edm2_workspace_bytes(const fg_edm2* h, int batch);
+/* EDM2Precond.forward in eval mode with fwd_pred_type = 'x0': x_t / out NCHW fp32 [B, C, R, R], t fp64 [B], class_labels fp32
+ * [B, label_dim] or NULL (= zeros).  emb_out (nullable): the embedding mp_silu(...) [B, emb_channels]. */
+FG_API int fg_edm2_forward(fg_edm2* h, const float* x_t, const double* t, const float* class_labels, float* out, float* emb_out,
+                           int batch, void* workspace, size_t workspace_bytes, void* stream);
+/* train() / eval(): sigma_shift applies in eval mode only (training != 0 disables it). */
+FG_API int fg_edm2_set_training(fg_edm2* h, int training);
+/* The FG_LOOP_X0 student loop of fg_sampler_run (same arguments and semantics, EDM schedule) around fg_edm2_forward; use_graph != 0
+ * replays one cached hipGraph per (batch, steps, sample type, pointers) key. */
+FG_API int fg_edm2_sampler_run(fg_edm2* h, const float* noise, const float* class_labels, const double* t_list, int steps,
+                               int sample_type, int loop_kind, const float* eps, uint64_t seed, float* out, int batch,
+                               void* workspace, size_t workspace_bytes, int use_graph, void* stream);
+/* The U-Net's Blocks, encoder then decoder (not the stem conv or out_conv): key "unet.enc.<res>x<res>_<name>" / "unet.dec....",
+ * res_in = 2 res_out for a down block, res_out / 2 for an up block.  run_block runs one on NHWC fp32 tensors with emb [B, emb_channels]
+ * (the mp_silu output).  A decoder block with a skip takes the two raw producers (x1: the main path, c1 channels; x2: the popped skip,
+ * c2 channels) and applies mp_cat itself; any other (c1, c2) split is FG_EINVAL before anything runs. */
+FG_API int fg_edm2_num_blocks(const fg_edm2* h);
+FG_API int fg_edm2_block_info(const fg_edm2* h, int index, const char** key, int* cin, int* cout, int* res_in, int* res_out,
+                              int* has_attention);
+FG_API int fg_edm2_run_block(fg_edm2* h, int index, const float* x1, int c1, const float* x2, int c2, const float* emb, float* out,
+                             int batch, void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
