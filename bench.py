@@ -11,12 +11,17 @@ before the timed region.  Ranks are independent replicas (sampling shards by ima
 the timed region is bracketed by barrier + device synchronize on both sides and the MAX over ranks is reported.
 
 --dump-outputs DIR writes, on rank 0, the samples the last timed step returned as float32 .npy files: DIR/samples.npy
-(the headline mode) and DIR/samples_bf16.npy (the bf16 line beside it, when measured).  Inputs, weights and per-step seeds
-depend only on the arguments, so two builds run with the same arguments can be compared output for output.
+(the headline mode) and DIR/samples_bf16.npy (the bf16 line beside it, unless --dtype bf16 or --no-secondary).  Inputs,
+weights and per-step seeds depend only on the arguments, so two builds run with the same arguments can be compared output
+for output.
 
-Rank 0 prints ONE JSON line with the contract fields plus
+A plain run sets up, warms up, times the K steps, writes its outputs and prints ONE JSON line with the contract fields
+(roofline and cpu_baseline null); it does not time the bf16 line, but with --dump-outputs it samples that line's last timed
+step once, untimed, from the same weights, inputs and seed.  --full adds, on rank 0,
   roofline     — the dominant kernel (fused GN+SiLU+conv3x3 at 32x32) timed live with HIP events on its launch stream
   cpu_baseline — the CPU oracle (torch fp32 restatement of the reference path, oracle/edm_ref.py) on this host's cores
+  secondary    — the bf16 line (timed like the headline, with its roofline) and, on one GPU, the transformer rows
+(--no-cpu-baseline and --no-secondary drop the last two).
 """
 import argparse
 import ctypes
@@ -247,9 +252,12 @@ def main():
     ap.add_argument("--batch", type=int, default=512, help="images per GPU per step")
     ap.add_argument("--sample-steps", type=int, default=4)
     ap.add_argument("--dtype", choices=["bf16x3", "fp32", "bf16"], default="bf16x3")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure the roofline, the CPU baseline, the bf16 line and the transformer rows beside the headline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--no-graph", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the bf16 line and the transformer-row timings reported beside the headline")
+    ap.add_argument("--no-secondary", action="store_true",
+                    help="skip the bf16 line (its samples too) and, with --full, the transformer-row timings reported beside the headline")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="write the samples of the last timed step as DIR/<name>.npy (float32, rank 0)")
     args = ap.parse_args()
@@ -277,30 +285,36 @@ def main():
     noise = torch.randn(B, 3, 32, 32, device=dev, generator=gen)
     cond = torch.nn.functional.one_hot(torch.arange(B, device=dev) % 10, 10).float()
 
-    def measure(dtype: str):
-        """(img/s, seconds of the timed region, roofline block) of one compute mode: W warm-up + exactly K timed steps."""
+    def make_net(dtype: str):
         # random-init weights of the named architecture; seeded N(0, 1/fan_in) so activations stay O(1) (the reference's
         # default init scales the residual branches by 1e-5, which makes the data trivial)
-        net = EDMPrecond(compute_dtype=dtype, **EDM_CIFAR10).randomize_parameters_(seed=1234).to(dev).eval()
+        return EDMPrecond(compute_dtype=dtype, **EDM_CIFAR10).randomize_parameters_(seed=1234).to(dev).eval()
+
+    def sample(net, step_seed: int):
+        """The samples of step number `step_seed` (1-based, warm-up steps included)."""
+        return FastGenModel.generator_fn(net, noise, condition=cond, student_sample_steps=args.sample_steps,
+                                         student_sample_type="sde", seed=step_seed * world + rank, use_graph=not args.no_graph)
+
+    def measure(dtype: str):
+        """(img/s, seconds of the timed region, roofline block or None) of one compute mode: W warm-up + exactly K timed
+        steps; the roofline block only with --full."""
+        net = make_net(dtype)
         step_seed = [0]
         last = [None]  # what the latest step returned (a fresh tensor per call)
 
         def step():
             step_seed[0] += 1
-            last[0] = FastGenModel.generator_fn(net, noise, condition=cond, student_sample_steps=args.sample_steps,
-                                                student_sample_type="sde", seed=step_seed[0] * world + rank,
-                                                use_graph=not args.no_graph)
+            last[0] = sample(net, step_seed[0])
             return last[0]
 
         dt = timed_region(step, args.steps, args.warmup, world, lambda: torch.cuda.synchronize(dev), dev)
         value = B * args.steps * world / dt
         if args.dump_outputs and rank == 0:
             dump_output(args.dump_outputs, "samples" if dtype == args.dtype else f"samples_{dtype}", last[0])
-        out = step()
-        assert torch.isfinite(out).all(), "non-finite samples"
+        assert torch.isfinite(last[0]).all(), "non-finite samples"
         # ---- roofline of the dominant kernel, measured live with HIP events on its launch stream -------------------
         roof = None
-        if rank == 0:
+        if rank == 0 and args.full:
             with torch.inference_mode():
                 _, h = net._engine(dev)
             L = _lib.lib()
@@ -336,14 +350,21 @@ def main():
     value, dt, roof = measure(args.dtype)
     # the narrower bf16-storage mode (what the reference computes under precision_amp=bfloat16), reported beside the headline
     secondary = None
-    if args.dtype != "bf16" and not args.no_secondary:
+    bf16_line = args.dtype != "bf16" and not args.no_secondary
+    if bf16_line and args.full:
         v2, dt2, roof2 = measure("bf16")
         secondary = {"bf16": {"value": round(v2, 2), "unit": "img/s", "ms_per_step": round(dt2 / args.steps * 1e3, 3),
                               "note": "bf16 MFMA operands AND bf16 activation storage: narrower than the reference's fp32 "
                                       "config, not the headline", "roofline": roof2}}
+    elif bf16_line and args.dump_outputs and rank == 0:
+        # untimed: the samples of the bf16 line's last timed step depend only on its weights, the inputs and that step's seed
+        net = make_net("bf16")
+        dump_output(args.dump_outputs, "samples_bf16", sample(net, args.warmup + args.steps))
+        del net
+        torch.cuda.empty_cache()
     # the rows next to the headline path, one GPU only: DiT-XL/2 forward and the causal video DiT's network call,
     # both at the precision their reference configs run (bf16), random-init weights of the named architectures
-    if world == 1 and not args.no_secondary:
+    if world == 1 and args.full and not args.no_secondary:
         try:
             secondary = dict(secondary or {})
             secondary["transformer_rows"] = transformer_rows(dev)
@@ -354,7 +375,7 @@ def main():
 
     if rank == 0:
         cpu = None
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             cpu = cpu_baseline()
         line = result_line(value, world, args.steps, args.warmup, dt, args.dtype, B, args.sample_steps, not args.no_graph, roof, cpu)
         if secondary:
