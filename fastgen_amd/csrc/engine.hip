@@ -136,32 +136,252 @@ struct TrainStash {
     float* raw_out = nullptr;        // the network's own output F (before precond_output), [B, C, H, W] fp32
 };
 
-struct GraphKey {
-    int B = 0, steps = 0, type = 0, loop = 0;
-    uint64_t zero_mask = 0;
-    const void *noise = nullptr, *labels = nullptr, *eps = nullptr, *out = nullptr, *ws = nullptr;
-    bool device_rng = false;
-    bool operator==(const GraphKey& o) const {
-        return B == o.B && steps == o.steps && type == o.type && loop == o.loop && zero_mask == o.zero_mask && noise == o.noise &&
-               labels == o.labels && eps == o.eps && out == o.out && ws == o.ws && device_rng == o.device_rng;
+// What every handle (fg_edm, fg_edm2, fg_dit, fg_wan) keeps: its parameter table in the reference's state-dict order, the device
+// memory it owns (freed with the handle) and whether its weights are packed.
+struct HandleBase {
+    std::vector<Param> params;
+    std::string name_prefix;  // put in front of every name add() registers
+    std::vector<void*> owned;
+    bool packed = false, device_ready = false;
+
+    HandleBase() = default;
+    HandleBase(const HandleBase&) = delete;
+    HandleBase& operator=(const HandleBase&) = delete;
+    ~HandleBase() {
+        for (void* p : owned) (void)hipFree(p);
+    }
+    int find(const std::string& n) const {
+        for (size_t i = 0; i < params.size(); ++i)
+            if (params[i].name == n) return (int)i;
+        return -1;
+    }
+    int add(const std::string& n, std::initializer_list<int64_t> shp) {
+        Param p;
+        p.name = name_prefix + n;
+        p.ndim = (int)shp.size();
+        p.numel = 1;
+        int i = 0;
+        for (int64_t s : shp) {
+            p.shape[i++] = s;
+            p.numel *= s;
+        }
+        params.push_back(p);
+        return (int)params.size() - 1;
+    }
+    // FG_ENOTREADY for the first parameter that is neither bound nor optional(index)
+    template <typename F>
+    int check_bound(F&& optional) const {
+        for (size_t i = 0; i < params.size(); ++i)
+            if (!params[i].ptr && !optional((int)i)) return fail(FG_ENOTREADY, "parameter '%s' is not bound", params[i].name.c_str());
+        return FG_OK;
+    }
+    int alloc(void** p, size_t bytes) {
+        HIP_TRY(hipMalloc(p, bytes));
+        owned.push_back(*p);
+        return FG_OK;
+    }
+    void free(void* p) {
+        if (!p) return;
+        for (size_t i = 0; i < owned.size(); ++i)
+            if (owned[i] == p) {
+                owned.erase(owned.begin() + i);
+                break;
+            }
+        (void)hipFree(p);
     }
 };
 
+// The bodies of fg_*_param_info and fg_*_bind_param (fg_wan_param_info widens the shape to 5-D; index: the bound parameter).
+int param_info(const HandleBase* h, int index, const char** name, int* ndim, int64_t shape[4]) {
+    if (!h || index < 0 || index >= (int)h->params.size()) return fail(FG_EINVAL, "param index out of range");
+    const Param& p = h->params[index];
+    if (name) *name = p.name.c_str();
+    if (ndim) *ndim = p.ndim;
+    if (shape)
+        for (int i = 0; i < 4; ++i) shape[i] = p.shape[i];
+    return FG_OK;
+}
+int bind_param(HandleBase* h, const char* name, const float* device_ptr, int64_t numel, int* index = nullptr) {
+    if (!h || !name || !device_ptr) return fail(FG_EINVAL, "null argument");
+    const int i = h->find(name);
+    if (i < 0) return fail(FG_EINVAL, "unknown parameter '%s'", name);
+    if (h->params[i].numel != numel)
+        return fail(FG_EINVAL, "parameter '%s': expected %lld elements, got %lld", name, (long long)h->params[i].numel, (long long)numel);
+    h->params[i].ptr = device_ptr;
+    h->packed = false;
+    if (index) *index = i;
+    return FG_OK;
+}
+
+// Per-call scalars (timesteps, RNG seed) reach the device through a ring of pinned host slots, copied on the caller's stream BEFORE the
+// graph launch (not a graph node: a node would re-read host memory that the next call may already have overwritten).  A slot is reused
+// only after the event recorded behind its copy has completed.
+struct ScalarRing {
+    static constexpr int kSlots = 8, kDoubles = 72;
+    struct Slot {
+        double tl[kDoubles];
+        uint64_t seed[8];
+    };
+    Slot* slots = nullptr;  // pinned
+    hipEvent_t ev[kSlots] = {};
+    bool used[kSlots] = {};
+    int next = 0;
+    int ensure() {
+        if (slots) return FG_OK;
+        HIP_TRY(hipHostMalloc((void**)&slots, sizeof(Slot) * kSlots));
+        for (int i = 0; i < kSlots; ++i) HIP_TRY(hipEventCreateWithFlags(&ev[i], hipEventDisableTiming));
+        return FG_OK;
+    }
+    int upload(const double* tl, int n, uint64_t seed, double* tl_dev, uint64_t* seed_dev, hipStream_t s) {
+        int rc = ensure();
+        if (rc) return rc;
+        const int si = next;
+        next = (si + 1) % kSlots;
+        if (used[si]) HIP_TRY(hipEventSynchronize(ev[si]));
+        Slot& sl = slots[si];
+        for (int i = 0; i < n; ++i) sl.tl[i] = tl[i];
+        sl.seed[0] = seed;
+        sl.seed[1] = 0;
+        HIP_TRY(hipMemcpyAsync(tl_dev, sl.tl, sizeof(double) * n, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemcpyAsync(seed_dev, sl.seed, sizeof(uint64_t) * 2, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipEventRecord(ev[si], s));
+        used[si] = true;
+        return FG_OK;
+    }
+    void destroy() {
+        if (slots) (void)hipHostFree(slots);
+        for (int i = 0; i < kSlots; ++i)
+            if (ev[i]) (void)hipEventDestroy(ev[i]);
+        slots = nullptr;
+    }
+};
+
+// One cached graph: what was captured (every pointer, shape and host-decided branch that the launches bake in) and its executable.
+struct GraphEntry {
+    std::vector<int64_t> key;
+    hipGraph_t graph = nullptr;
+    hipGraphExec_t exec = nullptr;
+    void drop() {
+        if (exec) (void)hipGraphExecDestroy(exec);
+        if (graph) (void)hipGraphDestroy(graph);
+        exec = nullptr, graph = nullptr;
+        key.clear();
+    }
+};
+
+// Capture `enqueue(capture_stream)` into `e` unless its key matches, then launch it on s.  The capture stream only records (the legacy
+// default stream cannot be captured); the graph runs on the caller's stream.
+template <typename F>
+int graph_run(GraphEntry& e, const std::vector<int64_t>& key, hipStream_t& cap, hipStream_t s, F&& enqueue) {
+    if (!e.exec || e.key != key) {
+        e.drop();
+        if (!cap) HIP_TRY(hipStreamCreateWithFlags(&cap, hipStreamNonBlocking));
+        HIP_TRY(hipStreamBeginCapture(cap, hipStreamCaptureModeThreadLocal));
+        const int rc = enqueue(cap);
+        hipGraph_t g = nullptr;
+        const hipError_t err = hipStreamEndCapture(cap, &g);
+        if (rc) {
+            if (g) (void)hipGraphDestroy(g);
+            return rc;
+        }
+        if (err != hipSuccess) return fail(FG_EHIP, "hipStreamEndCapture failed: %s", hipGetErrorString(err));
+        e.graph = g;
+        HIP_TRY(hipGraphInstantiate(&e.exec, e.graph, nullptr, nullptr, 0));
+        e.key = key;
+    }
+    HIP_TRY(hipGraphLaunch(e.exec, s));
+    return FG_OK;
+}
+
+// A handle's sampler state: the scalar ring, the cached graph of its sampler loop and the capture stream.
+struct SamplerCache {
+    ScalarRing ring;
+    GraphEntry graph;
+    hipStream_t cap = nullptr;
+    void release() {
+        graph.drop();
+        ring.destroy();
+        if (cap) (void)hipStreamDestroy(cap);
+        cap = nullptr;
+    }
+};
+
+// Bit i set where t_list[i] > 0 (i in [1, steps]): which steps re-noise, decided on the host and baked into a captured graph.
+int64_t zero_mask(const double* t_list, int steps) {
+    uint64_t m = 0;
+    for (int i = 1; i <= steps; ++i)
+        if (t_list[i] > 0) m |= 1ull << i;
+    return (int64_t)m;
+}
+
+int check_t_list(const double* t_list, int steps, int schedule) {
+    if (steps < 1 || steps > 64) return fail(FG_EINVAL, "steps must be in [1, 64]");
+    if (schedule != FG_SCHEDULE_EDM && schedule != FG_SCHEDULE_RF) return fail(FG_EINVAL, "bad schedule");
+    if (t_list[steps] != 0.0) return fail(FG_EINVAL, "t_list[-1] must be zero");  // methods/model.py:410
+    // is_t_valid (noise_schedule.py:409-423) allows one ulp of the timesteps' dtype beyond the range; the callers' lists are float64 or
+    // float32 (generator_fn_extrapolation casts its t_list, causvid.py:262-268: fp32(0.999) > 0.999), so the slack is an fp32 ulp
+    const double t_lo = nextafterf(schedule == FG_SCHEDULE_RF ? 0.0f : 0.002f, -INFINITY), t_hi = nextafterf(schedule == FG_SCHEDULE_RF ? 0.999f : 80.0f, INFINITY);
+    for (int i = 0; i < steps; ++i)
+        if (!(t_list[i] >= t_lo && t_list[i] <= t_hi))
+            return fail(FG_EINVAL, "t_list[%d] = %g outside [%g, %g]", i, t_list[i], t_lo, t_hi);
+    return FG_OK;
+}
+
+// Check the caller's workspace and lay `plan`'s buffers out in it (fg_edm / fg_edm2 entry points).
+template <typename H, typename W>
+int setup_ws(size_t (*plan)(const H*, int, Arena&, W&), const H* h, int B, void* workspace, size_t bytes, W& w) {
+    if (B <= 0) return fail(FG_EINVAL, "batch must be positive");
+    if (!workspace) return fail(FG_EINVAL, "workspace is null");
+    if (((uintptr_t)workspace) & 255) return fail(FG_EINVAL, "workspace must be 256-byte aligned");
+    Arena A;
+    A.base = (char*)workspace;
+    const size_t need = plan(h, B, A, w);
+    if (need > bytes) return fail(FG_ENOMEM, "workspace too small: need %zu bytes for batch %d, got %zu", need, B, bytes);
+    return FG_OK;
+}
+
+// The parameters one fg_dit_pack_group / fg_wan_pack_group call packs: names that start with `pre` and not with `exc` (if not empty),
+// the unit FSDP2 gathers at a time.
+struct ParamGroup {
+    std::string pre, exc;
+    bool operator()(const std::string& n) const { return n.rfind(pre, 0) == 0 && (exc.empty() || n.rfind(exc, 0) != 0); }
+};
+
+// The frame of fg_dit_pack_group / fg_wan_pack_group.  Every parameter of the group must be bound (logvar_linear excepted: nothing
+// reads it); pack(h, group, s) packs the group's GEMM weights, the group's other parameters are copied into the handle's own storage,
+// and the handle counts as packed once no parameter is left dirty.
+template <typename H>
+int pack_group(H* h, const char* prefix, const char* exclude, void* stream, int (*pack)(H*, const ParamGroup&, hipStream_t)) {
+    if (!h || !prefix) return fail(FG_EINVAL, "null argument");
+    hipStream_t s = (hipStream_t)stream;
+    const ParamGroup in_group{prefix, exclude ? exclude : ""};
+    int rc = h->check_bound([&](int i) { return !in_group(h->params[i].name) || h->is_logvar(i); });
+    if (rc || (rc = pack(h, in_group, s))) return rc;
+    // every parameter the kernels read at call time: into the engine's own storage
+    for (size_t i = 0; i < h->params.size(); ++i)
+        if (h->own[i] && in_group(h->params[i].name))
+            HIP_TRY(hipMemcpyAsync(h->own[i], h->params[i].ptr, sizeof(float) * (size_t)h->params[i].numel, hipMemcpyDeviceToDevice, s));
+    bool all = true;
+    for (size_t i = 0; i < h->params.size(); ++i) {
+        if (in_group(h->params[i].name)) h->dirty[i] = 0;
+        if (h->dirty[i] && !h->is_logvar((int)i)) all = false;
+    }
+    h->packed = all;
+    return FG_OK;
+}
+
 }  // namespace
 
-struct fg_edm {
+struct fg_edm : HandleBase {
     fg_edm_config cfg;
     AdmNet* adm = nullptr;  // cfg.model_type == FG_MODEL_DHARIWAL: the ADM layout (engine_adm.inc); nullptr for SongUNet
     int dtype = 0;  // storage type of the activation tensors and mode of every non-conv kernel: 0 fp32, 1 bf16
     int cmode = 0;  // arithmetic of the convolutions: FG_DTYPE_F32 / FG_DTYPE_BF16 / FG_DTYPE_BF16X3 (fp32 storage)
     int num_taps = 0;  // encoder `block3` outputs available as feature taps
     int emb_ch = 0, noise_ch = 0, cond_ch = 0;  // cond_ch = noise_ch * (1 + r_timestep), EDM/network.py:376
-    std::vector<Param> params;
     std::vector<Block> enc, dec;  // dec includes aux_norm / aux_conv entries
     std::vector<Block*> blocks;   // UNetBlocks only, encoder then decoder order
     int temb_total = 0;
-    bool packed = false;
-    bool device_ready = false;
     // data-gradient weights (transposed, flipped, packed), built on first use per weight version (fg_edm_pack_weights)
     struct DgradW {
         void* packed = nullptr;
@@ -181,47 +401,12 @@ struct fg_edm {
     float* freqs = nullptr;      // [noise_ch/2]
     float* aff_w = nullptr;      // [temb_total][emb_ch]
     float* aff_b = nullptr;      // [temb_total]
-    std::vector<void*> owned;
-    // graph cache
-    hipGraph_t graph = nullptr;
-    hipGraphExec_t graph_exec = nullptr;
-    GraphKey graph_key;
-    // Per-call scalars (timesteps, RNG seed) reach the device through a ring of pinned host slots, copied on the
-    // caller's stream BEFORE the graph launch (not a graph node: a node would re-read host memory that the next call
-    // may already have overwritten).  A slot is reused only after the event recorded behind its copy has completed.
-    static constexpr int kSlots = 8;
-    struct Slot {
-        double tl[72];
-        uint64_t seed[8];
-    };
-    Slot* slots = nullptr;  // pinned
-    hipEvent_t slot_ev[kSlots] = {};
-    bool slot_used[kSlots] = {};
-    int slot_next = 0;
+    SamplerCache sampler;  // fg_sampler_run
     // live timing of the dominant kernel (conv 3x3, no resample, 32x32 output): HIP events on the launch stream
     bool prof_on = false;
     std::vector<hipEvent_t> prof_ev;  // start/stop pairs
     double prof_flops = 0.0;
-    hipStream_t cap_stream = nullptr;  // capture-only stream (the legacy default stream cannot be captured)
 
-    int find(const std::string& n) const {
-        for (size_t i = 0; i < params.size(); ++i)
-            if (params[i].name == n) return (int)i;
-        return -1;
-    }
-    int add(const std::string& n, std::initializer_list<int64_t> shp) {
-        Param p;
-        p.name = n;
-        p.ndim = (int)shp.size();
-        p.numel = 1;
-        int i = 0;
-        for (int64_t s : shp) {
-            p.shape[i++] = s;
-            p.numel *= s;
-        }
-        params.push_back(p);
-        return (int)params.size() - 1;
-    }
     const float* P(int idx) const { return idx >= 0 ? params[idx].ptr : nullptr; }
     float* G(int idx) const { return idx >= 0 ? params[idx].grad : nullptr; }
 };
@@ -439,15 +624,9 @@ size_t plan_workspace(const fg_edm* h, int B, Arena& A, Workspace& w) {
     w.x = A.get<float>(img);
     w.x_pred = A.get<float>(img);
     w.eps = A.get<float>(img);
-    w.tl = A.get<double>(72);
+    w.tl = A.get<double>(ScalarRing::kDoubles);
     w.seed = A.get<uint64_t>(8);
     return (A.off + 255) & ~(size_t)255;
-}
-
-int dev_alloc(fg_edm* h, void** p, size_t bytes) {
-    HIP_TRY(hipMalloc(p, bytes));
-    h->owned.push_back(*p);
-    return FG_OK;
 }
 
 // launch_conv_fused + optional event pair when profiling the dominant kernel class
@@ -707,65 +886,45 @@ int enqueue_sampler(fg_edm* h, const float* noise, const float* labels, const do
     return FG_OK;
 }
 
-void drop_graph(fg_edm* h) {
-    if (h->graph_exec) (void)hipGraphExecDestroy(h->graph_exec);
-    if (h->graph) (void)hipGraphDestroy(h->graph);
-    h->graph_exec = nullptr;
-    h->graph = nullptr;
-}
-
-int setup_ws(const fg_edm* h, int B, void* workspace, size_t bytes, Workspace& w) {
-    if (B <= 0) return fail(FG_EINVAL, "batch must be positive");
-    if (!workspace) return fail(FG_EINVAL, "workspace is null");
-    if (((uintptr_t)workspace) & 255) return fail(FG_EINVAL, "workspace must be 256-byte aligned");
-    Arena A;
-    A.base = (char*)workspace;
-    const size_t need = plan_workspace(h, B, A, w);
-    if (need > bytes) return fail(FG_ENOMEM, "workspace too small: need %zu bytes for batch %d, got %zu", need, B, bytes);
-    return FG_OK;
-}
-
-// Device-side state (packed-weight storage, stacked affine matrix, frequency table, pinned staging).  Deferred to the
+// Device-side state (packed-weight storage, stacked affine matrix, frequency table).  Deferred to the
 // first fg_edm_pack_weights() so that fg_edm_create() is host-only and works without a GPU.
 int ensure_device_state(fg_edm* h) {
     if (h->device_ready) return FG_OK;
     int rc;
     const size_t tsz = h->dtype ? 2 : 4;
     for (Block* b : h->blocks) {
-        if ((rc = dev_alloc(h, &b->p_conv0, conv_pack_elems(b->cout, b->cin, 3) * tsz))) return rc;
-        if ((rc = dev_alloc(h, &b->p_conv1, conv_pack_elems(b->cout, b->cout, 3) * tsz))) return rc;
+        if ((rc = h->alloc(&b->p_conv0, conv_pack_elems(b->cout, b->cin, 3) * tsz))) return rc;
+        if ((rc = h->alloc(&b->p_conv1, conv_pack_elems(b->cout, b->cout, 3) * tsz))) return rc;
         const bool x3 = h->cmode == FG_DTYPE_BF16X3;  // conv_ws3.hip packing: two bf16 planes per weight = 4 bytes, as tsz
         if ((x3 ? conv_x3ws_shape_ok(b->cout, b->cin, b->res_out) : conv_ws_shape_ok(h->cmode, b->cout, b->cin, b->res_out)) && !b->down &&
-            (rc = dev_alloc(h, &b->p_conv0_ws, conv_pack_elems(b->cout, b->cin, 3) * tsz)))
+            (rc = h->alloc(&b->p_conv0_ws, conv_pack_elems(b->cout, b->cin, 3) * tsz)))
             return rc;
         if ((x3 ? conv_x3ws_shape_ok(b->cout, b->cout, b->res_out) : conv_ws_shape_ok(h->cmode, b->cout, b->cout, b->res_out)) &&
-            (rc = dev_alloc(h, &b->p_conv1_ws, conv_pack_elems(b->cout, b->cout, 3) * tsz)))
+            (rc = h->alloc(&b->p_conv1_ws, conv_pack_elems(b->cout, b->cout, 3) * tsz)))
             return rc;
-        if (b->has_skip && (rc = dev_alloc(h, &b->p_skip, conv_pack_elems(b->cout, b->cin, 1) * tsz))) return rc;
+        if (b->has_skip && (rc = h->alloc(&b->p_skip, conv_pack_elems(b->cout, b->cin, 1) * tsz))) return rc;
         if (b->attn) {
-            if ((rc = dev_alloc(h, &b->p_qkv, conv_pack_elems(3 * b->cout, b->cout, 1) * tsz))) return rc;
-            if ((rc = dev_alloc(h, &b->p_proj, conv_pack_elems(b->cout, b->cout, 1) * tsz))) return rc;
-            if ((rc = dev_alloc(h, (void**)&b->qkv_bias, sizeof(float) * 3 * b->cout))) return rc;
+            if ((rc = h->alloc(&b->p_qkv, conv_pack_elems(3 * b->cout, b->cout, 1) * tsz))) return rc;
+            if ((rc = h->alloc(&b->p_proj, conv_pack_elems(b->cout, b->cout, 1) * tsz))) return rc;
+            if ((rc = h->alloc((void**)&b->qkv_bias, sizeof(float) * 3 * b->cout))) return rc;
         }
     }
     for (Block& b : h->enc)
         if (b.kind == K_STEM && stem_supported(b.res_out, b.cin, b.cout))
-            if ((rc = dev_alloc(h, &b.p_stem, stem_pack_elems() * tsz))) return rc;
+            if ((rc = h->alloc(&b.p_stem, stem_pack_elems() * tsz))) return rc;
     for (Block& b : h->dec)
         if (b.kind == K_AUX_CONV && aux_head_supported(h->cmode, b.res_out, b.cin, b.cout))
-            if ((rc = dev_alloc(h, &b.p_aux, aux_pack_elems(b.cin) * tsz))) return rc;
-    if ((rc = dev_alloc(h, (void**)&h->aff_w, sizeof(float) * (size_t)h->temb_total * h->emb_ch))) return rc;
-    if ((rc = dev_alloc(h, (void**)&h->aff_b, sizeof(float) * (size_t)h->temb_total))) return rc;
+            if ((rc = h->alloc(&b.p_aux, aux_pack_elems(b.cin) * tsz))) return rc;
+    if ((rc = h->alloc((void**)&h->aff_w, sizeof(float) * (size_t)h->temb_total * h->emb_ch))) return rc;
+    if ((rc = h->alloc((void**)&h->aff_b, sizeof(float) * (size_t)h->temb_total))) return rc;
     // PositionalEmbedding(endpoint=True) frequencies in fp32, EDM/network.py:314-316
     const int half = h->noise_ch / 2;
     std::vector<float> fr(half);
     for (int j = 0; j < half; ++j) fr[j] = powf(1.0f / 10000.0f, (float)j / (float)(half - 1));
-    if ((rc = dev_alloc(h, (void**)&h->freqs, sizeof(float) * half))) return rc;
+    if ((rc = h->alloc((void**)&h->freqs, sizeof(float) * half))) return rc;
     HIP_TRY(hipMemcpy(h->freqs, fr.data(), sizeof(float) * half, hipMemcpyHostToDevice));
     if (conv_prepare_all(h->cmode) != 0) return fail(FG_EHIP, "hipFuncSetAttribute(dynamic LDS) failed");
     if (launch_attention(h->cmode, nullptr, nullptr, nullptr, nullptr, 1, 256, nullptr) != 0) return fail(FG_EHIP, "attention prepare failed");
-    HIP_TRY(hipHostMalloc((void**)&h->slots, sizeof(fg_edm::Slot) * fg_edm::kSlots));
-    for (int i = 0; i < fg_edm::kSlots; ++i) HIP_TRY(hipEventCreateWithFlags(&h->slot_ev[i], hipEventDisableTiming));
     h->device_ready = true;
     return FG_OK;
 }
@@ -828,12 +987,7 @@ int fg_edm_create(const fg_edm_config* cfg, fg_edm** out) {
 
 void fg_edm_destroy(fg_edm* h) {
     if (!h) return;
-    drop_graph(h);
-    for (void* p : h->owned) (void)hipFree(p);
-    if (h->slots) (void)hipHostFree(h->slots);
-    for (hipEvent_t e : h->slot_ev)
-        if (e) (void)hipEventDestroy(e);
-    if (h->cap_stream) (void)hipStreamDestroy(h->cap_stream);
+    h->sampler.release();
     for (hipEvent_t e : h->prof_ev) (void)hipEventDestroy(e);
     delete h->adm;
     delete h;
@@ -842,47 +996,31 @@ void fg_edm_destroy(fg_edm* h) {
 int fg_edm_num_params(const fg_edm* h) { return h ? (int)h->params.size() : 0; }
 
 int fg_edm_param_info(const fg_edm* h, int index, const char** name, int* ndim, int64_t shape[4]) {
-    if (!h || index < 0 || index >= (int)h->params.size()) return fail(FG_EINVAL, "param index out of range");
-    const Param& p = h->params[index];
-    if (name) *name = p.name.c_str();
-    if (ndim) *ndim = p.ndim;
-    if (shape)
-        for (int i = 0; i < 4; ++i) shape[i] = p.shape[i];
-    return FG_OK;
+    return param_info(h, index, name, ndim, shape);
 }
 
 int fg_edm_bind_param(fg_edm* h, const char* name, const float* device_ptr, int64_t numel) {
-    if (!h || !name || !device_ptr) return fail(FG_EINVAL, "null argument");
-    const int i = h->find(name);
-    if (i < 0) return fail(FG_EINVAL, "unknown parameter '%s'", name);
-    if (h->params[i].numel != numel)
-        return fail(FG_EINVAL, "parameter '%s': expected %lld elements, got %lld", name, (long long)h->params[i].numel, (long long)numel);
-    h->params[i].ptr = device_ptr;
-    h->packed = false;
-    return FG_OK;
+    return bind_param(h, name, device_ptr, numel);
 }
 
 int fg_edm_pack_weights(fg_edm* h, void* stream) {
     if (!h) return fail(FG_EINVAL, "null handle");
     hipStream_t s = (hipStream_t)stream;
+    // parameters the forward never reads: logvar_linear, and map_augment without augment labels (DhariwalUNet: always)
+    auto unused = [&](int i) {
+        const std::string& n = h->params[i].name;
+        return (n == "model.map_augment.weight" && (h->adm || !h->augment)) || n.rfind("model.logvar_linear", 0) == 0;
+    };
+    int rc;
     if (h->adm) {
-        for (const Param& p : h->params) {
-            const bool unused = p.name == "model.map_augment.weight" || p.name.rfind("model.logvar_linear", 0) == 0;
-            if (!p.ptr && !unused) return fail(FG_ENOTREADY, "parameter '%s' is not bound", p.name.c_str());
-        }
+        if ((rc = h->check_bound(unused))) return rc;
         ++h->pack_epoch;
-        const int rc = adm_pack_weights(h, s);
-        if (rc) return rc;
-        drop_graph(h);
+        if ((rc = adm_pack_weights(h, s))) return rc;
+        h->sampler.graph.drop();
         h->packed = true;
         return FG_OK;
     }
-    int rc0 = ensure_device_state(h);
-    if (rc0) return rc0;
-    for (const Param& p : h->params) {
-        const bool unused = (p.name == "model.map_augment.weight" && !h->augment) || p.name.rfind("model.logvar_linear", 0) == 0;
-        if (!p.ptr && !unused) return fail(FG_ENOTREADY, "parameter '%s' is not bound", p.name.c_str());
-    }
+    if ((rc = ensure_device_state(h)) || (rc = h->check_bound(unused))) return rc;
     ++h->pack_epoch;
     for (Block* b : h->blocks) {
         HIP_TRY(launch_pack_conv_weights(h->cmode, h->P(b->conv0_w), b->p_conv0, b->cout, b->cin, 3, 0, s));
@@ -911,7 +1049,7 @@ int fg_edm_pack_weights(fg_edm* h, void* stream) {
         if (b.kind == K_STEM && b.p_stem) HIP_TRY(launch_pack_stem_weights(h->dtype, h->P(b.w), b.p_stem, b.cin, s));
     for (Block& b : h->dec)
         if (b.kind == K_AUX_CONV && b.p_aux) HIP_TRY(launch_pack_aux_weights(h->cmode, h->P(b.w), b.p_aux, b.cin, b.cout, s));
-    drop_graph(h);
+    h->sampler.graph.drop();
     h->packed = true;
     return FG_OK;
 }
@@ -932,7 +1070,7 @@ int fg_edm_forward(fg_edm* h, const float* x_t, const double* t, const double* r
     if (!h->packed) return fail(FG_ENOTREADY, "weights are not packed (call fg_edm_pack_weights)");
     if (out == x_t) return fail(FG_EINVAL, "out must not alias x_t");
     Workspace w;
-    int rc = setup_ws(h, batch, workspace, workspace_bytes, w);
+    int rc = setup_ws(plan_workspace, h, batch, workspace, workspace_bytes, w);
     if (rc) return rc;
     hipStream_t s = (hipStream_t)stream;
     rc = run_forward(h, x_t, t, 1, r, 1, class_labels, out, batch, w, s);
@@ -968,7 +1106,7 @@ int fg_edm_forward_features(fg_edm* h, const float* x_t, const double* t, const 
         if (b.tap >= 0 && features[b.tap] && ((b.cout % 32) || ((b.res_out * b.res_out) % 32)))
             return fail(FG_EINVAL, "feature tap %d: channels and pixels must be multiples of 32", b.tap);
     Workspace w;
-    int rc = setup_ws(h, batch, workspace, workspace_bytes, w);
+    int rc = setup_ws(plan_workspace, h, batch, workspace, workspace_bytes, w);
     if (rc) return rc;
     return run_forward(h, x_t, t, 1, r, 1, class_labels, out, batch, w, (hipStream_t)stream, features, out == nullptr);
 }
@@ -1027,50 +1165,19 @@ int fg_sampler_run(fg_edm* h, const float* noise, const float* class_labels, con
         if (!(t_list[i] >= t_lo * (1 - 1e-12) && t_list[i] <= t_hi * (1 + 1e-12)))  // is_t_valid, noise_schedule.py:409-423
             return fail(FG_EINVAL, "t_list[%d] = %g outside [%g, %g]", i, t_list[i], t_lo, t_hi);
     Workspace w;
-    int rc = setup_ws(h, batch, workspace, workspace_bytes, w);
+    int rc = setup_ws(plan_workspace, h, batch, workspace, workspace_bytes, w);
     if (rc) return rc;
     hipStream_t s = (hipStream_t)stream;
-    {   // upload this call's timesteps and seed (see fg_edm::Slot)
-        const int si = h->slot_next;
-        h->slot_next = (si + 1) % fg_edm::kSlots;
-        if (h->slot_used[si]) HIP_TRY(hipEventSynchronize(h->slot_ev[si]));
-        fg_edm::Slot& sl = h->slots[si];
-        for (int i = 0; i <= steps; ++i) sl.tl[i] = t_list[i];
-        sl.seed[0] = seed;
-        sl.seed[1] = 0;
-        HIP_TRY(hipMemcpyAsync(w.tl, sl.tl, sizeof(double) * (steps + 1), hipMemcpyHostToDevice, s));
-        HIP_TRY(hipMemcpyAsync(w.seed, sl.seed, sizeof(uint64_t) * 2, hipMemcpyHostToDevice, s));
-        HIP_TRY(hipEventRecord(h->slot_ev[si], s));
-        h->slot_used[si] = true;
-    }
-    if (!use_graph || h->prof_on)
-        return enqueue_sampler(h, noise, class_labels, t_list, steps, sample_type, loop_kind, eps, out, batch, w, s);
-
-    GraphKey key;
-    key.B = batch; key.steps = steps; key.type = sample_type; key.loop = loop_kind;
-    for (int i = 1; i <= steps; ++i)
-        if (t_list[i] > 0) key.zero_mask |= (1ull << i);
-    key.noise = noise; key.labels = class_labels; key.eps = eps; key.out = out; key.ws = workspace;
-    key.device_rng = (sample_type == FG_SAMPLE_SDE && !eps);
-    if (!h->graph_exec || !(h->graph_key == key)) {
-        drop_graph(h);
-        if (!h->cap_stream) HIP_TRY(hipStreamCreateWithFlags(&h->cap_stream, hipStreamNonBlocking));
-        hipStream_t cs = h->cap_stream;  // capture records, it does not execute: the graph is launched on `s` below
-        HIP_TRY(hipStreamBeginCapture(cs, hipStreamCaptureModeThreadLocal));
-        rc = enqueue_sampler(h, noise, class_labels, t_list, steps, sample_type, loop_kind, eps, out, batch, w, cs);
-        hipGraph_t g = nullptr;
-        hipError_t e = hipStreamEndCapture(cs, &g);
-        if (rc) {
-            if (g) (void)hipGraphDestroy(g);
-            return rc;
-        }
-        if (e != hipSuccess) return fail(FG_EHIP, "hipStreamEndCapture failed: %s", hipGetErrorString(e));
-        h->graph = g;
-        HIP_TRY(hipGraphInstantiate(&h->graph_exec, h->graph, nullptr, nullptr, 0));
-        h->graph_key = key;
-    }
-    HIP_TRY(hipGraphLaunch(h->graph_exec, s));
-    return FG_OK;
+    SamplerCache& st = h->sampler;
+    if ((rc = st.ring.upload(t_list, steps + 1, seed, w.tl, w.seed, s))) return rc;
+    auto enqueue = [&](hipStream_t q) {
+        return enqueue_sampler(h, noise, class_labels, t_list, steps, sample_type, loop_kind, eps, out, batch, w, q);
+    };
+    if (!use_graph || h->prof_on) return enqueue(s);
+    const std::vector<int64_t> key = {batch, steps, sample_type, loop_kind, zero_mask(t_list, steps), (int64_t)(uintptr_t)noise,
+                                      (int64_t)(uintptr_t)class_labels, (int64_t)(uintptr_t)eps, (int64_t)(uintptr_t)out,
+                                      (int64_t)(uintptr_t)workspace, sample_type == FG_SAMPLE_SDE && !eps};
+    return graph_run(st.graph, key, st.cap, s, enqueue);
 }
 
 int fg_edm_profile_begin(fg_edm* h) {
@@ -1183,7 +1290,7 @@ int fg_edm_run_block(fg_edm* h, int index, const float* x1, int c1, const float*
     if (!h->packed) return fail(FG_ENOTREADY, "weights are not packed (call fg_edm_pack_weights)");
     if (index < 0 || index >= (int)h->blocks.size()) return fail(FG_EINVAL, "block index out of range");
     Workspace w;
-    int rc0 = setup_ws(h, batch, workspace, workspace_bytes, w);
+    int rc0 = setup_ws(plan_workspace, h, batch, workspace, workspace_bytes, w);
     if (rc0) return rc0;
     hipStream_t s = (hipStream_t)stream;
     HIP_TRY(launch_linear(emb, h->aff_w, h->aff_b, w.temb, batch, h->emb_ch, h->temb_total, 0, s));
@@ -1321,7 +1428,7 @@ int fg_op_dropout_mask(float* out, int64_t total, float p, uint32_t block_index,
 }
 int fg_edm_set_training(fg_edm* h, int training) {
     if (!h) return fail(FG_EINVAL, "null handle");
-    if ((training != 0) != h->training && h->cfg.sigma_shift != 0.0) drop_graph(h);  // a captured sampler baked the old shift in
+    if ((training != 0) != h->training && h->cfg.sigma_shift != 0.0) h->sampler.graph.drop();  // a captured sampler baked the old shift in
     h->training = training != 0;
     return FG_OK;
 }

@@ -192,7 +192,7 @@ size_t adm_plan_workspace(const fg_edm* h, int B, Arena& A, Workspace& w) {
     w.x = A.get<float>(img);
     w.x_pred = A.get<float>(img);
     w.eps = A.get<float>(img);
-    w.tl = A.get<double>(72);
+    w.tl = A.get<double>(ScalarRing::kDoubles);
     w.seed = A.get<uint64_t>(8);
     return (A.off + 255) & ~(size_t)255;
 }
@@ -202,21 +202,19 @@ int adm_pack_weights(fg_edm* h, hipStream_t s) {
     int rc;
     const int mode = h->cmode;
     auto pack = [&](void** dst, int widx, int cout, int cin, int ks) -> int {
-        if (!*dst && (rc = dev_alloc(h, dst, adm_conv_pack_elems(mode, cout, cin, ks) * sizeof(__bf16)))) return rc;
+        if (!*dst && (rc = h->alloc(dst, adm_conv_pack_elems(mode, cout, cin, ks) * sizeof(__bf16)))) return rc;
         HIP_TRY(adm_pack_conv_weights(mode, h->P(widx), *dst, cout, cin, ks, s));
         return FG_OK;
     };
     if (!h->device_ready) {
-        if ((rc = dev_alloc(h, (void**)&h->aff_w, sizeof(float) * (size_t)h->temb_total * h->emb_ch))) return rc;
-        if ((rc = dev_alloc(h, (void**)&h->aff_b, sizeof(float) * (size_t)h->temb_total))) return rc;
+        if ((rc = h->alloc((void**)&h->aff_w, sizeof(float) * (size_t)h->temb_total * h->emb_ch))) return rc;
+        if ((rc = h->alloc((void**)&h->aff_b, sizeof(float) * (size_t)h->temb_total))) return rc;
         // PositionalEmbedding(num_channels=model_channels), endpoint=False (EDM/network.py:306-319): (1/10000)^(j / half)
         const int half = h->cond_ch / 2;
         std::vector<float> fr(half);
         for (int j = 0; j < half; ++j) fr[j] = powf(1.0f / 10000.0f, (float)j / (float)half);
-        if ((rc = dev_alloc(h, (void**)&n->freqs, sizeof(float) * half))) return rc;
+        if ((rc = h->alloc((void**)&n->freqs, sizeof(float) * half))) return rc;
         HIP_TRY(hipMemcpy(n->freqs, fr.data(), sizeof(float) * half, hipMemcpyHostToDevice));
-        HIP_TRY(hipHostMalloc((void**)&h->slots, sizeof(fg_edm::Slot) * fg_edm::kSlots));
-        for (int i = 0; i < fg_edm::kSlots; ++i) HIP_TRY(hipEventCreateWithFlags(&h->slot_ev[i], hipEventDisableTiming));
         h->device_ready = true;
     }
     for (auto* list : {&n->enc, &n->dec})
@@ -354,7 +352,7 @@ int adm_run_block(fg_edm* h, int index, const float* x1, int c1, const float* x2
     if (c2 && !x2) return fail(FG_EINVAL, "%s: x2 is null", b->key.c_str());
     if (!h->packed) return fail(FG_ENOTREADY, "weights are not packed (call fg_edm_pack_weights)");
     Workspace w;
-    int rc = setup_ws(h, B, workspace, workspace_bytes, w);
+    int rc = setup_ws(plan_workspace, h, B, workspace, workspace_bytes, w);
     if (rc) return rc;
     HIP_TRY(launch_linear(emb, h->aff_w, h->aff_b, w.temb, B, h->emb_ch, h->temb_total, 0, s));
     return adm_block(h, *b, x1, c1, c2 ? x2 : nullptr, c2, out, B, w, s);

@@ -1,14 +1,13 @@
 // DiT engine (SURVEY §8(f)2): parameter plan with the reference's state-dict names, packed GEMM weights, workspace plan, forward
 // orchestration and the C ABI of include/fastgen_amd.h (fg_dit_*).  Textually included by engine.hip inside its `extern "C"` region
-// (shares fail / HIP_TRY / Arena / Param with the EDM engine).  Reference: fastgen/networks/DiT/network.py:153-201 (DiTBlock),
+// (the handle is a HandleBase; pack_group is engine.hip's).  Reference: fastgen/networks/DiT/network.py:153-201 (DiTBlock),
 // :204-225 (OutputProjection), :464-574 (DiT.forward); kernels: dit.hip + conv.hip's token GEMM modes.
 }  // extern "C" (reopened below: the structures and helpers are C++)
 
-struct fg_dit {
+struct fg_dit : HandleBase {
     fg_dit_config cfg;
     int dtype = 0, cmode = 0;  // as fg_edm: storage of the token tensors (0 fp32 / 1 bf16), arithmetic of the GEMMs (FG_DTYPE_*)
     int D = 0, Hd = 0, hd = 0, T = 0, grid = 0;  // hidden size, MLP hidden size, head dim, tokens per image, patches per side
-    std::vector<Param> params;
     struct Blk {
         int qkv_w, qkv_b, proj_w, proj_b, fc1_w, fc1_b, fc2_w, fc2_b, mod_w, mod_b;
         void *p_qkv = nullptr, *p_proj = nullptr, *p_fc1 = nullptr, *p_fc2 = nullptr;  // packed (owned)
@@ -18,9 +17,7 @@ struct fg_dit {
         fmw = -1, fmb = -1;
     void* p_modw = nullptr;   // bf16 GEMM path: all blocks' conditioning_net weights stacked [depth * 6 D][D] bf16 ...
     float* modb = nullptr;    // ... and their biases [depth * 6 D]: one GEMM per forward instead of one 256-row linear per block
-    std::vector<void*> owned;
-    struct DitSamplerState* sampler = nullptr;  // fg_dit_sampler_run's pinned scalar slots and graph (engine_sampler.inc)
-    bool packed = false, device_ready = false;
+    SamplerCache sampler;  // fg_dit_sampler_run (engine_sampler.inc)
     bool gemm3 = false;  // bf16x3 mode: the four block linears on gemm.hip's split-bf16 flavour ([hi | lo | hi] weights, [hi | lo] activation planes)
     bool gemm = false;  // bf16 mode: the four block linears on gemm.hip (plain [N][K] bf16 weights) instead of conv.hip's token modes
     // a kernel that met an out-of-range class index raises *err_host (pinned, mapped: err_dev is its device address); the next call on
@@ -30,24 +27,6 @@ struct fg_dit {
         if (!err_host || !*err_host) return 0;
         *err_host = 0;
         return 1;
-    }
-    int find(const std::string& n) const {
-        for (size_t i = 0; i < params.size(); ++i)
-            if (params[i].name == n) return (int)i;
-        return -1;
-    }
-    int add(const std::string& n, std::initializer_list<int64_t> shp) {
-        Param p;
-        p.name = n;
-        p.ndim = (int)shp.size();
-        p.numel = 1;
-        int i = 0;
-        for (int64_t s : shp) {
-            p.shape[i++] = s;
-            p.numel *= s;
-        }
-        params.push_back(p);
-        return (int)params.size() - 1;
     }
     // Parameters as the kernels read them.  The four block linears are read from the caller's tensors at PACK time only (into the
     // GEMM layouts of p_qkv ...); every other parameter is copied into `own` at pack time, so that between two packs nothing points into
@@ -61,8 +40,6 @@ struct fg_dit {
 };
 
 namespace {
-
-void dit_sampler_release(fg_dit* h);  // engine_sampler.inc
 
 struct DitWs {
     float *tf, *th, *temb, *remb, *c, *sc, *mod, *fmod, *mod_all;
@@ -95,12 +72,6 @@ size_t dit_plan(const fg_dit* h, int B, Arena& A, DitWs& w) {
     w.hid = A.take(ntok * (size_t)h->Hd * tsz);
     w.qkv = A.take(ntok * 3 * D * tsz);  // token-major q | k | v of the LDS-staged attention (bf16 GEMM path, head dim 72)
     return (A.off + 255) & ~(size_t)255;
-}
-
-int dit_alloc(fg_dit* h, void** p, size_t bytes) {
-    HIP_TRY(hipMalloc(p, bytes));
-    h->owned.push_back(*p);
-    return FG_OK;
 }
 
 // one token GEMM: out[tok][n] = epilogue(sum_k src[tok][k] W[n][k] + bias[n])
@@ -220,6 +191,61 @@ int dit_forward(fg_dit* h, const float* x_t, const float* t, const float* r, con
     return FG_OK;
 }
 
+// fg_dit_pack_group's part: device storage on the first call, then the GEMM weights of the group's blocks
+int dit_pack(fg_dit* h, const ParamGroup& in_group, hipStream_t s) {
+    const char* e3 = getenv("FASTGEN_AMD_DIT_GEMM3");
+    const bool want3 = h->cmode == FG_DTYPE_BF16X3 && !(e3 && e3[0] == '0') && (h->D % 64) == 0 && (h->Hd % 64) == 0 && h->D >= 256;
+    // bytes per packed weight element: bf16 2; bf16x3 two bf16 planes = 4, or [hi | lo | hi] = 6 for the split-bf16 token GEMM
+    const size_t wsz = h->cmode == FG_DTYPE_BF16 ? 2 : (want3 ? 6 : 4);
+    const size_t D = h->D, Hd = h->Hd;
+    int rc;
+    if (!h->device_ready) {
+        for (fg_dit::Blk& b : h->blocks) {
+            if ((rc = h->alloc(&b.p_qkv, 3 * D * D * wsz)) || (rc = h->alloc(&b.p_proj, D * D * wsz)) ||
+                (rc = h->alloc(&b.p_fc1, Hd * D * wsz)) || (rc = h->alloc(&b.p_fc2, D * Hd * wsz)))
+                return rc;
+        }
+        for (size_t i = 0; i < h->params.size(); ++i)
+            if (!h->pack_only[i] && !h->is_logvar((int)i) && (rc = h->alloc((void**)&h->own[i], sizeof(float) * (size_t)h->params[i].numel))) return rc;
+        if (conv_prepare_all(h->cmode) != 0) return fail(FG_EHIP, "hipFuncSetAttribute(dynamic LDS) failed");
+        HIP_TRY(hipHostMalloc((void**)&h->err_host, sizeof(int), hipHostMallocMapped));
+        *h->err_host = 0;
+        HIP_TRY(hipHostGetDevicePointer((void**)&h->err_dev, h->err_host, 0));
+        const char* e = getenv("FASTGEN_AMD_DIT_GEMM");
+        h->gemm = h->cmode == FG_DTYPE_BF16 && !(e && e[0] == '0') && (D % 64) == 0 && (Hd % 64) == 0;
+        h->gemm3 = want3;
+        if ((h->gemm || h->gemm3) && launch_gemm_bf16(GemmArgs{}, s, true) != 0) return fail(FG_EHIP, "hipFuncSetAttribute(dynamic LDS) failed");
+        if (h->gemm && ((rc = h->alloc(&h->p_modw, h->blocks.size() * 6 * D * D * 2)) || (rc = h->alloc((void**)&h->modb, h->blocks.size() * 6 * D * 4))))
+            return rc;
+        h->device_ready = true;
+    }
+    size_t bi = 0;
+    for (fg_dit::Blk& b : h->blocks) {
+        const size_t me = bi++;
+        if (!in_group(h->params[b.qkv_w].name)) continue;  // (a block's parameters share their prefix: all of them in the group or none)
+        const float *qkv = h->params[b.qkv_w].ptr, *proj = h->params[b.proj_w].ptr, *fc1 = h->params[b.fc1_w].ptr, *fc2 = h->params[b.fc2_w].ptr;
+        if (h->gemm3) {
+            HIP_TRY(launch_split3_weights(qkv, b.p_qkv, (int)(3 * D), (int)D, s));
+            HIP_TRY(launch_split3_weights(proj, b.p_proj, (int)D, (int)D, s));
+            HIP_TRY(launch_split3_weights(fc1, b.p_fc1, (int)Hd, (int)D, s));
+            HIP_TRY(launch_split3_weights(fc2, b.p_fc2, (int)D, (int)Hd, s));
+        } else if (h->gemm) {
+            HIP_TRY(launch_cvt_bf16(h->params[b.mod_w].ptr, (__bf16*)h->p_modw + me * 6 * D * D, 6 * D * D, s));
+            HIP_TRY(hipMemcpyAsync(h->modb + me * 6 * D, h->params[b.mod_b].ptr, 6 * D * 4, hipMemcpyDeviceToDevice, s));
+            HIP_TRY(launch_cvt_bf16(qkv, b.p_qkv, 3 * D * D, s));
+            HIP_TRY(launch_cvt_bf16(proj, b.p_proj, D * D, s));
+            HIP_TRY(launch_cvt_bf16(fc1, b.p_fc1, Hd * D, s));
+            HIP_TRY(launch_cvt_bf16(fc2, b.p_fc2, D * Hd, s));
+        } else {
+            HIP_TRY(launch_pack_conv_weights(h->cmode, qkv, b.p_qkv, 3 * h->D, h->D, 1, 0, s));
+            HIP_TRY(launch_pack_conv_weights(h->cmode, proj, b.p_proj, h->D, h->D, 1, 0, s));
+            HIP_TRY(launch_pack_conv_weights(h->cmode, fc1, b.p_fc1, h->Hd, h->D, 1, 0, s));
+            HIP_TRY(launch_pack_conv_weights(h->cmode, fc2, b.p_fc2, h->D, h->Hd, 1, 0, s));
+        }
+    }
+    return FG_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -290,108 +316,29 @@ int fg_dit_create(const fg_dit_config* cfg, fg_dit** out) {
 
 void fg_dit_destroy(fg_dit* h) {
     if (!h) return;
-    dit_sampler_release(h);
+    h->sampler.release();
     if (h->err_host) (void)hipHostFree(h->err_host);
-    for (void* p : h->owned) (void)hipFree(p);
     delete h;
 }
 
 int fg_dit_num_params(const fg_dit* h) { return h ? (int)h->params.size() : 0; }
 
 int fg_dit_param_info(const fg_dit* h, int index, const char** name, int* ndim, int64_t shape[4]) {
-    if (!h || index < 0 || index >= (int)h->params.size()) return fail(FG_EINVAL, "param index out of range");
-    const Param& p = h->params[index];
-    if (name) *name = p.name.c_str();
-    if (ndim) *ndim = p.ndim;
-    if (shape)
-        for (int i = 0; i < 4; ++i) shape[i] = p.shape[i];
-    return FG_OK;
+    return param_info(h, index, name, ndim, shape);
 }
 
 int fg_dit_bind_param(fg_dit* h, const char* name, const float* device_ptr, int64_t numel) {
-    if (!h || !name || !device_ptr) return fail(FG_EINVAL, "null argument");
-    const int i = h->find(name);
-    if (i < 0) return fail(FG_EINVAL, "unknown parameter '%s'", name);
-    if (h->params[i].numel != numel)
-        return fail(FG_EINVAL, "parameter '%s': expected %lld elements, got %lld", name, (long long)h->params[i].numel, (long long)numel);
-    h->params[i].ptr = device_ptr;
-    h->dirty[i] = 1;
-    h->packed = false;
-    return FG_OK;
+    int i;
+    const int rc = bind_param(h, name, device_ptr, numel, &i);
+    if (!rc) h->dirty[i] = 1;
+    return rc;
 }
 
 int fg_dit_pack_weights(fg_dit* h, void* stream) { return fg_dit_pack_group(h, "", nullptr, stream); }
 
 // Pack the parameters whose names start with `prefix` (and not with `exclude`, nullable): the unit FSDP2 gathers at a time.
 int fg_dit_pack_group(fg_dit* h, const char* prefix, const char* exclude, void* stream) {
-    if (!h || !prefix) return fail(FG_EINVAL, "null argument");
-    hipStream_t s = (hipStream_t)stream;
-    const std::string pre(prefix), exc(exclude ? exclude : "");
-    auto in_group = [&](const std::string& n) { return n.rfind(pre, 0) == 0 && (exc.empty() || n.rfind(exc, 0) != 0); };
-    for (size_t i = 0; i < h->params.size(); ++i)
-        if (in_group(h->params[i].name) && !h->params[i].ptr && !h->is_logvar((int)i))
-            return fail(FG_ENOTREADY, "parameter '%s' is not bound", h->params[i].name.c_str());
-    const char* e3 = getenv("FASTGEN_AMD_DIT_GEMM3");
-    const bool want3 = h->cmode == FG_DTYPE_BF16X3 && !(e3 && e3[0] == '0') && (h->D % 64) == 0 && (h->Hd % 64) == 0 && h->D >= 256;
-    // bytes per packed weight element: bf16 2; bf16x3 two bf16 planes = 4, or [hi | lo | hi] = 6 for the split-bf16 token GEMM
-    const size_t wsz = h->cmode == FG_DTYPE_BF16 ? 2 : (want3 ? 6 : 4);
-    const size_t D = h->D, Hd = h->Hd;
-    int rc;
-    if (!h->device_ready) {
-        for (fg_dit::Blk& b : h->blocks) {
-            if ((rc = dit_alloc(h, &b.p_qkv, 3 * D * D * wsz)) || (rc = dit_alloc(h, &b.p_proj, D * D * wsz)) ||
-                (rc = dit_alloc(h, &b.p_fc1, Hd * D * wsz)) || (rc = dit_alloc(h, &b.p_fc2, D * Hd * wsz)))
-                return rc;
-        }
-        for (size_t i = 0; i < h->params.size(); ++i)
-            if (!h->pack_only[i] && !h->is_logvar((int)i) && (rc = dit_alloc(h, (void**)&h->own[i], sizeof(float) * (size_t)h->params[i].numel))) return rc;
-        if (conv_prepare_all(h->cmode) != 0) return fail(FG_EHIP, "hipFuncSetAttribute(dynamic LDS) failed");
-        HIP_TRY(hipHostMalloc((void**)&h->err_host, sizeof(int), hipHostMallocMapped));
-        *h->err_host = 0;
-        HIP_TRY(hipHostGetDevicePointer((void**)&h->err_dev, h->err_host, 0));
-        const char* e = getenv("FASTGEN_AMD_DIT_GEMM");
-        h->gemm = h->cmode == FG_DTYPE_BF16 && !(e && e[0] == '0') && (D % 64) == 0 && (Hd % 64) == 0;
-        h->gemm3 = want3;
-        if ((h->gemm || h->gemm3) && launch_gemm_bf16(GemmArgs{}, s, true) != 0) return fail(FG_EHIP, "hipFuncSetAttribute(dynamic LDS) failed");
-        if (h->gemm && ((rc = dit_alloc(h, &h->p_modw, h->blocks.size() * 6 * D * D * 2)) || (rc = dit_alloc(h, (void**)&h->modb, h->blocks.size() * 6 * D * 4))))
-            return rc;
-        h->device_ready = true;
-    }
-    // every parameter the kernels read at call time: into the engine's own storage
-    for (size_t i = 0; i < h->params.size(); ++i)
-        if (h->own[i] && in_group(h->params[i].name))
-            HIP_TRY(hipMemcpyAsync(h->own[i], h->params[i].ptr, sizeof(float) * (size_t)h->params[i].numel, hipMemcpyDeviceToDevice, s));
-    size_t bi = 0;
-    for (fg_dit::Blk& b : h->blocks) {
-        const size_t me = bi++;
-        if (!in_group(h->params[b.qkv_w].name)) continue;  // (a block's parameters share their prefix: all of them in the group or none)
-        const float *qkv = h->params[b.qkv_w].ptr, *proj = h->params[b.proj_w].ptr, *fc1 = h->params[b.fc1_w].ptr, *fc2 = h->params[b.fc2_w].ptr;
-        if (h->gemm3) {
-            HIP_TRY(launch_split3_weights(qkv, b.p_qkv, (int)(3 * D), (int)D, s));
-            HIP_TRY(launch_split3_weights(proj, b.p_proj, (int)D, (int)D, s));
-            HIP_TRY(launch_split3_weights(fc1, b.p_fc1, (int)Hd, (int)D, s));
-            HIP_TRY(launch_split3_weights(fc2, b.p_fc2, (int)D, (int)Hd, s));
-        } else if (h->gemm) {
-            HIP_TRY(launch_cvt_bf16(h->params[b.mod_w].ptr, (__bf16*)h->p_modw + me * 6 * D * D, 6 * D * D, s));
-            HIP_TRY(hipMemcpyAsync(h->modb + me * 6 * D, h->params[b.mod_b].ptr, 6 * D * 4, hipMemcpyDeviceToDevice, s));
-            HIP_TRY(launch_cvt_bf16(qkv, b.p_qkv, 3 * D * D, s));
-            HIP_TRY(launch_cvt_bf16(proj, b.p_proj, D * D, s));
-            HIP_TRY(launch_cvt_bf16(fc1, b.p_fc1, Hd * D, s));
-            HIP_TRY(launch_cvt_bf16(fc2, b.p_fc2, D * Hd, s));
-        } else {
-            HIP_TRY(launch_pack_conv_weights(h->cmode, qkv, b.p_qkv, 3 * h->D, h->D, 1, 0, s));
-            HIP_TRY(launch_pack_conv_weights(h->cmode, proj, b.p_proj, h->D, h->D, 1, 0, s));
-            HIP_TRY(launch_pack_conv_weights(h->cmode, fc1, b.p_fc1, h->Hd, h->D, 1, 0, s));
-            HIP_TRY(launch_pack_conv_weights(h->cmode, fc2, b.p_fc2, h->D, h->Hd, 1, 0, s));
-        }
-    }
-    bool all = true;
-    for (size_t i = 0; i < h->params.size(); ++i) {
-        if (in_group(h->params[i].name)) h->dirty[i] = 0;
-        if (h->dirty[i] && !h->is_logvar((int)i)) all = false;
-    }
-    h->packed = all;
-    return FG_OK;
+    return pack_group(h, prefix, exclude, stream, dit_pack);
 }
 
 size_t fg_dit_workspace_bytes(const fg_dit* h, int batch) {

@@ -1,8 +1,7 @@
 // EDM2 U-Net engine (EDM2Precond, reference fastgen/networks/EDM2/network.py): module layout and state-dict order, weight normalisation
 // and packing with the magnitude-preserving constants folded in, workspace plan, the forward schedule, the per-block entry points and
-// the x0 sampler loop.  Textually included by engine.hip inside its `extern "C"` region behind engine_sampler.inc (shares fail /
-// HIP_TRY / Arena / Param and the sampler's ScalarRing / GraphEntry / graph_run).  Convolutions and attention are adm.hip's kernels;
-// the rest is edm2.hip.  Forward only, split-bf16 and bf16 convolutions, fp32 activations.
+// the x0 sampler loop.  Textually included by engine.hip inside its `extern "C"` region (the handle is a HandleBase; setup_ws and the
+// SamplerCache are engine.hip's).  Convolutions and attention are adm.hip's kernels; the rest is edm2.hip.  Forward only, split-bf16 and bf16 convolutions, fp32 activations.
 }  // extern "C" (reopened below)
 
 namespace {
@@ -36,49 +35,24 @@ double mp_sum_norm(double t) { return std::sqrt((1 - t) * (1 - t) + t * t); }
 
 }  // namespace
 
-struct fg_edm2 {
+struct fg_edm2 : HandleBase {
     fg_edm2_config cfg;
     int cmode = 0;
     int cnoise = 0, cemb = 0, total = 0, stem_c = 0, out_cin = 0;
-    std::vector<Param> params;
     std::vector<E2Block> enc, dec;
     std::vector<int> skip_c, skip_res;
     int out_gain = -1, freqs = -1, phases = -1, emb_noise = -1, emb_label = -1, stem_w = -1, out_w = -1;
-    bool packed = false, device_ready = false, training = false;
+    bool training = false;
     // owned device memory
-    std::vector<void*> owned;
     float *w_noise = nullptr, *w_label = nullptr, *w_mod = nullptr, *scratch = nullptr;
     float2* ones = nullptr;  // [max width] {1, 0}: conv_res0's plain silu(x) prologue
     void *p_stem = nullptr, *p_out = nullptr;
     size_t scratch_elems = 0;
     int max_c = 0;
-    // sampler
-    ScalarRing ring;
-    GraphEntry graph;
-    hipStream_t cap = nullptr;
+    SamplerCache sampler;  // fg_edm2_sampler_run
 
     double shift() const { return training ? 0.0 : cfg.sigma_shift; }
-    int find(const std::string& n) const {
-        for (size_t i = 0; i < params.size(); ++i)
-            if (params[i].name == n) return (int)i;
-        return -1;
-    }
-    int add(const std::string& n, std::initializer_list<int64_t> shp) {
-        Param p;
-        p.name = n;
-        p.ndim = (int)shp.size();
-        p.numel = 1;
-        int i = 0;
-        for (int64_t v : shp) p.shape[i++] = v, p.numel *= v;
-        params.push_back(p);
-        return (int)params.size() - 1;
-    }
     const float* P(int idx) const { return idx >= 0 ? params[idx].ptr : nullptr; }
-    int alloc(void** p, size_t bytes) {
-        HIP_TRY(hipMalloc(p, bytes));
-        owned.push_back(*p);
-        return FG_OK;
-    }
 };
 
 namespace {
@@ -223,17 +197,6 @@ size_t e2_plan(const fg_edm2* h, int B, Arena& A, E2Ws& w) {
     w.tl = A.get<double>(ScalarRing::kDoubles);
     w.seed = A.get<uint64_t>(8);
     return (A.off + 255) & ~(size_t)255;
-}
-
-int e2_setup_ws(const fg_edm2* h, int B, void* workspace, size_t bytes, E2Ws& w) {
-    if (B <= 0) return fail(FG_EINVAL, "batch must be positive");
-    if (!workspace) return fail(FG_EINVAL, "workspace is null");
-    if (((uintptr_t)workspace) & 255) return fail(FG_EINVAL, "workspace must be 256-byte aligned");
-    Arena A;
-    A.base = (char*)workspace;
-    const size_t need = e2_plan(h, B, A, w);
-    if (need > bytes) return fail(FG_ENOMEM, "workspace too small: need %zu bytes for batch %d, got %zu", need, B, bytes);
-    return FG_OK;
 }
 
 // normalize + MP scaling (+ folds) of one conv's weights into the scratch copy, then the ADM conv packing
@@ -472,43 +435,25 @@ int fg_edm2_create(const fg_edm2_config* cfg, fg_edm2** out) {
 
 void fg_edm2_destroy(fg_edm2* h) {
     if (!h) return;
-    h->graph.drop();
-    h->ring.destroy();
-    if (h->cap) (void)hipStreamDestroy(h->cap);
-    for (void* p : h->owned) (void)hipFree(p);
+    h->sampler.release();
     delete h;
 }
 
 int fg_edm2_num_params(const fg_edm2* h) { return h ? (int)h->params.size() : 0; }
 
 int fg_edm2_param_info(const fg_edm2* h, int index, const char** name, int* ndim, int64_t shape[4]) {
-    if (!h || index < 0 || index >= (int)h->params.size()) return fail(FG_EINVAL, "param index out of range");
-    const Param& p = h->params[index];
-    if (name) *name = p.name.c_str();
-    if (ndim) *ndim = p.ndim;
-    if (shape)
-        for (int i = 0; i < 4; ++i) shape[i] = p.shape[i];
-    return FG_OK;
+    return param_info(h, index, name, ndim, shape);
 }
 
 int fg_edm2_bind_param(fg_edm2* h, const char* name, const float* device_ptr, int64_t numel) {
-    if (!h || !name || !device_ptr) return fail(FG_EINVAL, "null argument");
-    const int i = h->find(name);
-    if (i < 0) return fail(FG_EINVAL, "unknown parameter '%s'", name);
-    if (h->params[i].numel != numel)
-        return fail(FG_EINVAL, "parameter '%s': expected %lld elements, got %lld", name, (long long)h->params[i].numel, (long long)numel);
-    h->params[i].ptr = device_ptr;
-    h->packed = false;
-    return FG_OK;
+    return bind_param(h, name, device_ptr, numel);
 }
 
 int fg_edm2_pack_weights(fg_edm2* h, void* stream) {
     if (!h) return fail(FG_EINVAL, "null handle");
-    for (const Param& p : h->params)
-        if (!p.ptr) return fail(FG_ENOTREADY, "parameter '%s' is not bound", p.name.c_str());
-    const int rc = e2_pack(h, (hipStream_t)stream);
-    if (rc) return rc;
-    h->graph.drop();
+    int rc = h->check_bound([](int) { return false; });
+    if (rc || (rc = e2_pack(h, (hipStream_t)stream))) return rc;
+    h->sampler.graph.drop();
     h->packed = true;
     return FG_OK;
 }
@@ -523,6 +468,7 @@ size_t fg_edm2_workspace_bytes(const fg_edm2* h, int batch) {
 
 int fg_edm2_set_training(fg_edm2* h, int training) {
     if (!h) return fail(FG_EINVAL, "null handle");
+    if ((training != 0) != h->training && h->cfg.sigma_shift != 0.0) h->sampler.graph.drop();  // a captured sampler baked the old shift in
     h->training = training != 0;
     return FG_OK;
 }
@@ -533,7 +479,7 @@ int fg_edm2_forward(fg_edm2* h, const float* x_t, const double* t, const float* 
     if (!h->packed) return fail(FG_ENOTREADY, "weights are not packed (call fg_edm2_pack_weights)");
     if (out == x_t) return fail(FG_EINVAL, "out must not alias x_t");
     E2Ws w;
-    int rc = e2_setup_ws(h, batch, workspace, workspace_bytes, w);
+    int rc = setup_ws(e2_plan, h, batch, workspace, workspace_bytes, w);
     if (rc) return rc;
     hipStream_t s = (hipStream_t)stream;
     if ((rc = e2_forward(h, x_t, t, 1, class_labels, out, batch, w, s))) return rc;
@@ -551,17 +497,15 @@ int fg_edm2_sampler_run(fg_edm2* h, const float* noise, const float* class_label
     int rc = check_t_list(t_list, steps, FG_SCHEDULE_EDM);
     if (rc) return rc;
     E2Ws w;
-    if ((rc = e2_setup_ws(h, batch, workspace, workspace_bytes, w))) return rc;
+    if ((rc = setup_ws(e2_plan, h, batch, workspace, workspace_bytes, w))) return rc;
     hipStream_t s = (hipStream_t)stream;
-    if ((rc = h->ring.upload(t_list, steps + 1, seed, w.tl, w.seed, s))) return rc;
+    SamplerCache& st = h->sampler;
+    if ((rc = st.ring.upload(t_list, steps + 1, seed, w.tl, w.seed, s))) return rc;
     auto enqueue = [&](hipStream_t q) { return e2_enqueue_sampler(h, noise, class_labels, t_list, steps, sample_type, eps, out, batch, w, q); };
     if (!use_graph) return enqueue(s);
-    int64_t zero_mask = 0;
-    for (int i = 1; i <= steps; ++i)
-        if (t_list[i] > 0) zero_mask |= (int64_t)1 << i;
-    const std::vector<int64_t> key = {batch, steps, sample_type, zero_mask, (int64_t)(uintptr_t)noise, (int64_t)(uintptr_t)class_labels,
-                                      (int64_t)(uintptr_t)eps, (int64_t)(uintptr_t)out, (int64_t)(uintptr_t)workspace};
-    return graph_run(h->graph, key, h->cap, s, enqueue);
+    const std::vector<int64_t> key = {batch, steps, sample_type, zero_mask(t_list, steps), (int64_t)(uintptr_t)noise,
+                                      (int64_t)(uintptr_t)class_labels, (int64_t)(uintptr_t)eps, (int64_t)(uintptr_t)out, (int64_t)(uintptr_t)workspace};
+    return graph_run(st.graph, key, st.cap, s, enqueue);
 }
 
 int fg_edm2_num_blocks(const fg_edm2* h) { return h ? (int)(h->enc.size() + h->dec.size()) : 0; }
@@ -590,7 +534,7 @@ int fg_edm2_run_block(fg_edm2* h, int index, const float* x1, int c1, const floa
     if (c2 && !x2) return fail(FG_EINVAL, "%s: x2 is null", b->key.c_str());
     if (!h->packed) return fail(FG_ENOTREADY, "weights are not packed (call fg_edm2_pack_weights)");
     E2Ws w;
-    int rc = e2_setup_ws(h, batch, workspace, workspace_bytes, w);
+    int rc = setup_ws(e2_plan, h, batch, workspace, workspace_bytes, w);
     if (rc) return rc;
     hipStream_t s = (hipStream_t)stream;
     if ((rc = e2_modulation(h, emb, batch, w, s))) return rc;

@@ -5,136 +5,14 @@
 //   fg_wan_sampler_run   CausVidModel._student_sample_loop (distribution_matching/causvid.py:87-185), the segment loop of
 //                        generator_fn_extrapolation (:188-397) and SelfForcingModel.rollout_with_gradient's no-grad form
 //                        (self_forcing.py:92-241) around fg_wan_forward: per chunk N x {x0 prediction; re-noise}, then the cache-fill call
-// Textually included by engine.hip behind engine_dit.inc / engine_wan.inc (shares fail / HIP_TRY / Arena with them).  The reference's
+// Textually included by engine.hip behind engine_dit.inc / engine_wan.inc; the scalar ring and graph cache are engine.hip's.  The reference's
 // host syncs (`t_next > 0` on a device tensor, `assert is_t_valid(t)` in every schedule call, `rescale_t`) are hoisted to host scalars
 // checked once per call; timesteps and the RNG seed live in device memory, so a captured graph is replayed with new values.
 }  // extern "C" (reopened below)
 
 namespace {
 
-// Per-call scalars (timesteps, RNG seed) reach the device through a ring of pinned host slots, copied on the caller's stream BEFORE the
-// graph launch (not a graph node: a node would re-read host memory that the next call may already have overwritten).  A slot is reused
-// only after the event recorded behind its copy has completed.  (fg_edm keeps the same mechanism inline.)
-struct ScalarRing {
-    static constexpr int kSlots = 8, kDoubles = 72;
-    struct Slot {
-        double tl[kDoubles];
-        uint64_t seed[8];
-    };
-    Slot* slots = nullptr;  // pinned
-    hipEvent_t ev[kSlots] = {};
-    bool used[kSlots] = {};
-    int next = 0;
-    int ensure() {
-        if (slots) return FG_OK;
-        HIP_TRY(hipHostMalloc((void**)&slots, sizeof(Slot) * kSlots));
-        for (int i = 0; i < kSlots; ++i) HIP_TRY(hipEventCreateWithFlags(&ev[i], hipEventDisableTiming));
-        return FG_OK;
-    }
-    int upload(const double* tl, int n, uint64_t seed, double* tl_dev, uint64_t* seed_dev, hipStream_t s) {
-        int rc = ensure();
-        if (rc) return rc;
-        const int si = next;
-        next = (si + 1) % kSlots;
-        if (used[si]) HIP_TRY(hipEventSynchronize(ev[si]));
-        Slot& sl = slots[si];
-        for (int i = 0; i < n; ++i) sl.tl[i] = tl[i];
-        sl.seed[0] = seed;
-        sl.seed[1] = 0;
-        HIP_TRY(hipMemcpyAsync(tl_dev, sl.tl, sizeof(double) * n, hipMemcpyHostToDevice, s));
-        HIP_TRY(hipMemcpyAsync(seed_dev, sl.seed, sizeof(uint64_t) * 2, hipMemcpyHostToDevice, s));
-        HIP_TRY(hipEventRecord(ev[si], s));
-        used[si] = true;
-        return FG_OK;
-    }
-    void destroy() {
-        if (slots) (void)hipHostFree(slots);
-        for (int i = 0; i < kSlots; ++i)
-            if (ev[i]) (void)hipEventDestroy(ev[i]);
-        slots = nullptr;
-    }
-};
-
-// One cached graph: what was captured (every pointer, shape and host-decided branch that the launches bake in) and its executable.
-struct GraphEntry {
-    std::vector<int64_t> key;
-    hipGraph_t graph = nullptr;
-    hipGraphExec_t exec = nullptr;
-    void drop() {
-        if (exec) (void)hipGraphExecDestroy(exec);
-        if (graph) (void)hipGraphDestroy(graph);
-        exec = nullptr, graph = nullptr;
-        key.clear();
-    }
-};
-
-// Capture `enqueue(capture_stream)` into `e` unless its key matches, then launch it on s.  The capture stream only records (the legacy
-// default stream cannot be captured); the graph runs on the caller's stream.
-template <typename F>
-int graph_run(GraphEntry& e, const std::vector<int64_t>& key, hipStream_t& cap, hipStream_t s, F&& enqueue) {
-    if (!e.exec || e.key != key) {
-        e.drop();
-        if (!cap) HIP_TRY(hipStreamCreateWithFlags(&cap, hipStreamNonBlocking));
-        HIP_TRY(hipStreamBeginCapture(cap, hipStreamCaptureModeThreadLocal));
-        const int rc = enqueue(cap);
-        hipGraph_t g = nullptr;
-        const hipError_t err = hipStreamEndCapture(cap, &g);
-        if (rc) {
-            if (g) (void)hipGraphDestroy(g);
-            return rc;
-        }
-        if (err != hipSuccess) return fail(FG_EHIP, "hipStreamEndCapture failed: %s", hipGetErrorString(err));
-        e.graph = g;
-        HIP_TRY(hipGraphInstantiate(&e.exec, e.graph, nullptr, nullptr, 0));
-        e.key = key;
-    }
-    HIP_TRY(hipGraphLaunch(e.exec, s));
-    return FG_OK;
-}
-
-int check_t_list(const double* t_list, int steps, int schedule) {
-    if (steps < 1 || steps > 64) return fail(FG_EINVAL, "steps must be in [1, 64]");
-    if (schedule != FG_SCHEDULE_EDM && schedule != FG_SCHEDULE_RF) return fail(FG_EINVAL, "bad schedule");
-    if (t_list[steps] != 0.0) return fail(FG_EINVAL, "t_list[-1] must be zero");  // methods/model.py:410
-    // is_t_valid (noise_schedule.py:409-423) allows one ulp of the timesteps' dtype beyond the range; the callers' lists are float64 or
-    // float32 (generator_fn_extrapolation casts its t_list, causvid.py:262-268: fp32(0.999) > 0.999), so the slack is an fp32 ulp
-    const double t_lo = nextafterf(schedule == FG_SCHEDULE_RF ? 0.0f : 0.002f, -INFINITY), t_hi = nextafterf(schedule == FG_SCHEDULE_RF ? 0.999f : 80.0f, INFINITY);
-    for (int i = 0; i < steps; ++i)
-        if (!(t_list[i] >= t_lo && t_list[i] <= t_hi))
-            return fail(FG_EINVAL, "t_list[%d] = %g outside [%g, %g]", i, t_list[i], t_lo, t_hi);
-    return FG_OK;
-}
-
 // ---- DiT ----------------------------------------------------------------------------------------------------------------------
-}  // namespace
-struct DitSamplerState {  // owned by the handle (fg_dit::sampler)
-    ScalarRing ring;
-    GraphEntry graph;
-    hipStream_t cap = nullptr;
-};
-struct WanSamplerState {  // fg_wan::sampler
-    ScalarRing ring;
-    std::vector<GraphEntry> graphs;  // one per chunk of the loop (the chunk's start frame, frame count and key length are baked in)
-    hipStream_t cap = nullptr;
-};
-namespace {
-void dit_sampler_release(fg_dit* h) {
-    if (!h->sampler) return;
-    h->sampler->graph.drop();
-    h->sampler->ring.destroy();
-    if (h->sampler->cap) (void)hipStreamDestroy(h->sampler->cap);
-    delete h->sampler;
-    h->sampler = nullptr;
-}
-void wan_sampler_release(fg_wan* h) {
-    if (!h->sampler) return;
-    for (GraphEntry& g : h->sampler->graphs) g.drop();
-    h->sampler->ring.destroy();
-    if (h->sampler->cap) (void)hipStreamDestroy(h->sampler->cap);
-    delete h->sampler;
-    h->sampler = nullptr;
-}
-
 struct DitLoopWs {
     DitWs net;
     float *x, *v, *pred, *eps, *te, *re;
@@ -258,24 +136,21 @@ int fg_dit_sampler_run(fg_dit* h, const fg_dit_sampler_config* sc, const float* 
     DitLoopWs w;
     const size_t need = dit_sampler_plan(h, batch, guided, A, w);
     if (need > workspace_bytes) return fail(FG_ENOMEM, "workspace too small: need %zu bytes for batch %d, got %zu", need, batch, workspace_bytes);
-    if (!h->sampler) h->sampler = new DitSamplerState();
-    DitSamplerState* st = h->sampler;
+    SamplerCache& st = h->sampler;
     hipStream_t s = (hipStream_t)stream;
-    if ((rc = st->ring.upload(t_list, steps + 1, seed, w.tl, w.seed, s))) return rc;
+    if ((rc = st.ring.upload(t_list, steps + 1, seed, w.tl, w.seed, s))) return rc;
     auto enqueue = [&](hipStream_t q) {
         return dit_enqueue_sampler(h, *sc, noise, class_ids, neg_class_ids, t_list, steps, sample_type, loop_kind, eps, out, batch, w, q);
     };
     if (!use_graph) return enqueue(s);
-    int64_t zero_mask = 0;
-    for (int i = 1; i <= steps; ++i)
-        if (t_list[i] > 0) zero_mask |= (1ll << i);
     int64_t tsb, gsb;
     memcpy(&tsb, &sc->t_scale, 8);
     memcpy(&gsb, &sc->guidance_scale, 8);
-    const std::vector<int64_t> key = {batch, steps, sample_type, loop_kind, zero_mask, (int64_t)(uintptr_t)noise, (int64_t)(uintptr_t)class_ids,
-                                      (int64_t)(uintptr_t)neg_class_ids, (int64_t)(uintptr_t)eps, (int64_t)(uintptr_t)out, (int64_t)(uintptr_t)workspace,
-                                      tsb, gsb, sc->use_sit_convention, sc->time_cond_diff, sc->net_pred_flow, sc->schedule, (int64_t)h->cmode};
-    return graph_run(st->graph, key, st->cap, s, enqueue);
+    const std::vector<int64_t> key = {batch, steps, sample_type, loop_kind, zero_mask(t_list, steps), (int64_t)(uintptr_t)noise,
+                                      (int64_t)(uintptr_t)class_ids, (int64_t)(uintptr_t)neg_class_ids, (int64_t)(uintptr_t)eps, (int64_t)(uintptr_t)out,
+                                      (int64_t)(uintptr_t)workspace, tsb, gsb, sc->use_sit_convention, sc->time_cond_diff, sc->net_pred_flow,
+                                      sc->schedule, (int64_t)h->cmode};
+    return graph_run(st.graph, key, st.cap, s, enqueue);
 }
 
 }  // extern "C"
@@ -369,10 +244,9 @@ int fg_wan_sampler_run(fg_wan* h, const fg_wan_sampler_config* sc, float* x, con
     // condition stays: the caller set it for THIS call.)
     if ((rc = wan_ensure_caches(h, batch, height, width, s))) return rc;  // (allocation must not fall inside a capture)
     h->stored_rows = 0;
-    if (!h->sampler) h->sampler = new WanSamplerState();
-    WanSamplerState* st = h->sampler;
-    if ((rc = st->ring.upload(t_list, steps + 1, seed, w.tl, w.seed, s))) return rc;
-    if (st->graphs.size() < chunks.size()) st->graphs.resize(chunks.size());
+    SamplerCache& st = h->sampler;
+    if ((rc = st.ring.upload(t_list, steps + 1, seed, w.tl, w.seed, s))) return rc;
+    if (h->chunk_graphs.size() < chunks.size()) h->chunk_graphs.resize(chunks.size());
 
     const int C = h->cfg.in_channels;
     const int64_t hw = (int64_t)height * width, rows = (int64_t)batch * C, vid_pitch = (int64_t)frames * hw;
@@ -435,20 +309,18 @@ int fg_wan_sampler_run(fg_wan* h, const fg_wan_sampler_config* sc, float* x, con
         }
         // what the chunk's launches bake in; the graph of a chunk also depends on the host-side cache bookkeeping (stored_rows), which the
         // loop leaves in the same state at this point of every call
-        int64_t zero_mask = 0;
-        for (int i = 1; i <= steps; ++i)
-            if (t_list[i] > 0) zero_mask |= (1ll << i);
         int64_t tsb, cnb;
         memcpy(&tsb, &sc->t_scale, 8);
         memcpy(&cnb, &sc->context_noise, 8);
-        const std::vector<int64_t> key = {batch, frames, height, width, steps, sample_type, last, f0, f1, fill_only, zero_mask, (int64_t)(uintptr_t)x,
-                                          (int64_t)(uintptr_t)eps, (int64_t)(uintptr_t)workspace, tsb, cnb, sc->net_pred_flow, sc->schedule, nsde,
-                                          (int64_t)h->text_L, (int64_t)(uintptr_t)h->blocks[0].kc, (int64_t)(uintptr_t)h->blocks[0].kv2};
+        const std::vector<int64_t> key = {batch, frames, height, width, steps, sample_type, last, f0, f1, fill_only, zero_mask(t_list, steps),
+                                          (int64_t)(uintptr_t)x, (int64_t)(uintptr_t)eps, (int64_t)(uintptr_t)workspace, tsb, cnb, sc->net_pred_flow,
+                                          sc->schedule, nsde, (int64_t)h->text_L, (int64_t)(uintptr_t)h->blocks[0].kc,
+                                          (int64_t)(uintptr_t)h->blocks[0].kv2};
         // (capture runs the same host bookkeeping as an eager pass; a replay must apply it too)
         const int stored_before = h->stored_rows;
-        GraphEntry& ge = st->graphs[ci];
+        GraphEntry& ge = h->chunk_graphs[ci];
         const bool hit = ge.exec && ge.key == key;
-        if ((rc = graph_run(ge, key, st->cap, s, enqueue))) return rc;
+        if ((rc = graph_run(ge, key, st.cap, s, enqueue))) return rc;
         if (hit) {
             const int end_rows = f1 * (height / 2) * (width / 2);
             h->stored_rows = end_rows > stored_before ? end_rows : stored_before;

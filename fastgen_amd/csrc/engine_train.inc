@@ -67,9 +67,9 @@ int conv_dgrad(fg_edm* h, const float* w_oihw, int cout, int cin, int ks, const 
         // where a wave-specialised kernel applies (conv_ws.hip / conv_ws3.hip; both want the operand as it lies and >= 8 steps)
         const bool ws = ks == 3 && cout >= 256 && (x3 ? conv_x3ws_shape_ok(cp, cout, res) : conv_ws_shape_ok(1, cp, cout, res));
         if (!e.packed) {
-            int rc = dev_alloc(h, &e.packed, (size_t)cp * cout * ks * ks * wsz);
+            int rc = h->alloc(&e.packed, (size_t)cp * cout * ks * ks * wsz);
             if (rc) return rc;
-            if (ws && (rc = dev_alloc(h, &e.packed_ws, (size_t)cp * cout * 9 * wsz))) return rc;
+            if (ws && (rc = h->alloc(&e.packed_ws, (size_t)cp * cout * 9 * wsz))) return rc;
         }
         if (e.epoch != h->pack_epoch) {
             HIP_TRY(launch_dgrad_weights(w_oihw, q.wt, cout, cin, cp, ks * ks, s));
@@ -451,7 +451,7 @@ int run_backward(fg_edm* h, const float* x_t, const double* t, const double* r, 
     {
         const int E = h->emb_ch, TT = h->temb_total;
         if (!h->aff_wT) {
-            int rc2 = dev_alloc(h, (void**)&h->aff_wT, sizeof(float) * (size_t)E * TT);
+            int rc2 = h->alloc((void**)&h->aff_wT, sizeof(float) * (size_t)E * TT);
             if (rc2) return rc2;
         }
         if (h->aff_wT_epoch != h->pack_epoch) {

@@ -1,14 +1,14 @@
 // Causal video DiT engine (SURVEY 8(f)3 / CausVid row of 8(a)): parameter plan with the state-dict names of the reference's
 // CausalWan (`transformer.` + diffusers' WanTransformer3DModel keys), bf16 weight copies, per-handle KV caches, forward
-// orchestration and the C ABI of include/fastgen_amd.h (fg_wan_*).  Textually included by engine.hip inside its `extern "C"` region.
+// orchestration and the C ABI of include/fastgen_amd.h (fg_wan_*).  Textually included by engine.hip inside its `extern "C"` region
+// (the handle is a HandleBase; pack_group is engine.hip's).
 // Reference: fastgen/networks/Wan/network_causal.py:467-550 (block), :568-705 (prepare), :815-913 (block loop, cache positions),
 // fastgen/networks/Wan/network.py:156-279 (classify_forward); kernels: wan.hip + gemm.hip + dit.hip's LayerNorm-modulate.
 }  // extern "C" (reopened below)
 
-struct fg_wan {
+struct fg_wan : HandleBase {
     fg_wan_config cfg;
     int D = 0, Fd = 0, H = 0;
-    std::vector<Param> params;
     struct Blk {
         int sst, q_w, q_b, k_w, k_b, v_w, v_b, o_w, o_b, nq, nk;          // attn1
         int q2_w, q2_b, k2_w, k2_b, v2_w, v2_b, o2_w, o2_b, nq2, nk2;      // attn2
@@ -24,29 +24,12 @@ struct fg_wan {
     void *p_x1 = nullptr, *p_x2 = nullptr;  // text embedder weights, bf16
     float2 *tab_t = nullptr, *tab_h = nullptr, *tab_w = nullptr;  // RoPE axis tables
     int npt = 0, nph = 0, npw = 0;
-    std::vector<void*> owned;
-    struct WanSamplerState* sampler = nullptr;  // fg_wan_sampler_run's pinned scalar slots and per-chunk graphs (engine_sampler.inc)
-    bool packed = false, device_ready = false;
+    // fg_wan_sampler_run (engine_sampler.inc): the scalar ring and capture stream, and one graph per chunk of the loop (the chunk's
+    // start frame, frame count and key length are baked in) in place of sampler.graph
+    SamplerCache sampler;
+    std::vector<GraphEntry> chunk_graphs;
     int cache_B = 0, cache_cap = 0, text_B = 0, text_L = 0;
     int stored_rows = 0;  // cache rows [0, stored_rows) hold K / V that a store_kv = 1 call wrote (the reference's per_tag["len"], network_causal.py:385-390)
-    int find(const std::string& n) const {
-        for (size_t i = 0; i < params.size(); ++i)
-            if (params[i].name == n) return (int)i;
-        return -1;
-    }
-    int add(const std::string& n, std::initializer_list<int64_t> shp) {
-        Param p;
-        p.name = "transformer." + n;
-        p.ndim = (int)shp.size();
-        p.numel = 1;
-        int i = 0;
-        for (int64_t s : shp) {
-            p.shape[i++] = s;
-            p.numel *= s;
-        }
-        params.push_back(p);
-        return (int)params.size() - 1;
-    }
     // As in fg_dit: the GEMM weights are read from the caller's tensors at pack time only (into the bf16 copies p_qkv ...); every other
     // parameter is copied into `own` then, so that nothing points into the caller's memory between two packs (FSDP2 gathers one block,
     // packs it and frees it again: CausalWan.fully_shard).
@@ -57,23 +40,6 @@ struct fg_wan {
 };
 
 namespace {
-
-void wan_sampler_release(fg_wan* h);  // engine_sampler.inc
-
-int wan_alloc(fg_wan* h, void** p, size_t bytes) {
-    HIP_TRY(hipMalloc(p, bytes));
-    h->owned.push_back(*p);
-    return FG_OK;
-}
-void wan_free(fg_wan* h, void* p) {
-    if (!p) return;
-    for (size_t i = 0; i < h->owned.size(); ++i)
-        if (h->owned[i] == p) {
-            h->owned.erase(h->owned.begin() + i);
-            break;
-        }
-    (void)hipFree(p);
-}
 
 struct WanWs {
     float *tf, *th, *temb, *st, *tproj, *mod, *omod;
@@ -138,7 +104,7 @@ int wan_build_rope(fg_wan* h) {
                 const double f = 1.0 / pow(10000.0, (double)(2 * i) / (double)dims[a]);
                 t[(size_t)p * np + i] = make_float2((float)cos((double)p * f), (float)sin((double)p * f));
             }
-        int rc = wan_alloc(h, (void**)dst[a], t.size() * sizeof(float2));
+        int rc = h->alloc((void**)dst[a], t.size() * sizeof(float2));
         if (rc) return rc;
         HIP_TRY(hipMemcpy(*dst[a], t.data(), t.size() * sizeof(float2), hipMemcpyHostToDevice));
     }
@@ -158,6 +124,54 @@ __global__ void wan_cat_kernel(const float* a, const float* b, const float* c, f
     }
 }
 
+// fg_wan_pack_group's part: device storage on the first call, then the bf16 GEMM weights and fused biases of the group
+int wan_pack(fg_wan* h, const ParamGroup& in_group, hipStream_t s) {
+    const size_t D = h->D, Fd = h->Fd, Td = h->cfg.text_dim;
+    int rc;
+    if (!h->device_ready) {
+        if ((rc = h->alloc(&h->p_x1, D * Td * 2)) || (rc = h->alloc(&h->p_x2, D * D * 2))) return rc;
+        for (fg_wan::Blk& b : h->blocks) {
+            if ((rc = h->alloc(&b.p_qkv, 3 * D * D * 2)) || (rc = h->alloc(&b.p_o, D * D * 2)) || (rc = h->alloc(&b.p_q2, D * D * 2)) ||
+                (rc = h->alloc(&b.p_kv2, 2 * D * D * 2)) || (rc = h->alloc(&b.p_o2, D * D * 2)) || (rc = h->alloc(&b.p_f0, Fd * D * 2)) ||
+                (rc = h->alloc(&b.p_f2, D * Fd * 2)) || (rc = h->alloc((void**)&b.b_qkv, 3 * D * 4)) ||
+                (rc = h->alloc((void**)&b.b_kv2, 2 * D * 4)) || (rc = h->alloc((void**)&b.n2mod, 2 * D * 4)))
+                return rc;
+        }
+        for (size_t i = 0; i < h->params.size(); ++i)
+            if (!h->pack_only[i] && !h->is_logvar((int)i) && (rc = h->alloc((void**)&h->own[i], sizeof(float) * (size_t)h->params[i].numel))) return rc;
+        if ((rc = wan_build_rope(h))) return rc;
+        if (launch_gemm_bf16(GemmArgs{}, s, true) != 0) return fail(FG_EHIP, "hipFuncSetAttribute(dynamic LDS) failed");
+        h->device_ready = true;
+    }
+    auto raw = [&](int idx) { return h->params[idx].ptr; };
+    if (in_group(h->params[h->x1_w].name)) {
+        HIP_TRY(launch_cvt_bf16(raw(h->x1_w), h->p_x1, D * Td, s));
+        HIP_TRY(launch_cvt_bf16(raw(h->x2_w), h->p_x2, D * D, s));
+    }
+    const int g1 = (int)((D + 255) / 256);
+    for (fg_wan::Blk& b : h->blocks) {
+        if (!in_group(h->params[b.q_w].name)) continue;  // (a block's parameters share their prefix: all of them in the group or none)
+        __bf16* qkv = (__bf16*)b.p_qkv;
+        HIP_TRY(launch_cvt_bf16(raw(b.q_w), qkv, D * D, s));
+        HIP_TRY(launch_cvt_bf16(raw(b.k_w), qkv + D * D, D * D, s));
+        HIP_TRY(launch_cvt_bf16(raw(b.v_w), qkv + 2 * D * D, D * D, s));
+        HIP_TRY(launch_cvt_bf16(raw(b.o_w), b.p_o, D * D, s));
+        HIP_TRY(launch_cvt_bf16(raw(b.q2_w), b.p_q2, D * D, s));
+        __bf16* kv2 = (__bf16*)b.p_kv2;
+        HIP_TRY(launch_cvt_bf16(raw(b.k2_w), kv2, D * D, s));
+        HIP_TRY(launch_cvt_bf16(raw(b.v2_w), kv2 + D * D, D * D, s));
+        HIP_TRY(launch_cvt_bf16(raw(b.o2_w), b.p_o2, D * D, s));
+        HIP_TRY(launch_cvt_bf16(raw(b.f0_w), b.p_f0, Fd * D, s));
+        HIP_TRY(launch_cvt_bf16(raw(b.f2_w), b.p_f2, D * Fd, s));
+        hipLaunchKernelGGL(wan_cat_kernel, dim3(g1), dim3(256), 0, s, raw(b.q_b), raw(b.k_b), raw(b.v_b), b.b_qkv, (int)D);
+        hipLaunchKernelGGL(wan_cat_kernel, dim3(g1), dim3(256), 0, s, raw(b.k2_b), raw(b.v2_b), (const float*)nullptr, b.b_kv2, (int)D);
+        hipLaunchKernelGGL(wan_n2mod_kernel, dim3(g1), dim3(256), 0, s, raw(b.n2_w), raw(b.n2_b), b.n2mod, (int)D);
+        HIP_TRY(hipGetLastError());
+    }
+    h->text_B = 0;  // the text caches were computed with the previous weights
+    return FG_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -172,6 +186,7 @@ int fg_wan_create(const fg_wan_config* cfg, fg_wan** out) {
         cfg->total_num_frames <= 0)
         return fail(FG_EINVAL, "bad channels / depth / ffn_dim / text_dim / freq_dim");
     fg_wan* h = new fg_wan();
+    h->name_prefix = "transformer.";
     h->cfg = *cfg;
     h->D = D, h->Fd = cfg->ffn_dim, h->H = cfg->num_heads;
     const int C = cfg->in_channels, Fd = cfg->ffn_dim;
@@ -226,39 +241,30 @@ int fg_wan_create(const fg_wan_config* cfg, fg_wan** out) {
 
 void fg_wan_destroy(fg_wan* h) {
     if (!h) return;
-    wan_sampler_release(h);
-    for (void* p : h->owned) (void)hipFree(p);
+    for (GraphEntry& g : h->chunk_graphs) g.drop();
+    h->sampler.release();
     delete h;
 }
 
 int fg_wan_num_params(const fg_wan* h) { return h ? (int)h->params.size() : 0; }
 
 int fg_wan_param_info(const fg_wan* h, int index, const char** name, int* ndim, int64_t shape[5]) {
-    if (!h || index < 0 || index >= (int)h->params.size()) return fail(FG_EINVAL, "param index out of range");
-    const Param& p = h->params[index];
-    if (name) *name = p.name.c_str();
-    if (ndim) *ndim = p.ndim;
+    int nd = 0;
+    const int rc = param_info(h, index, name, &nd, shape);
+    if (rc) return rc;
+    if (ndim) *ndim = nd;
     if (shape) {
-        if (p.ndim == 5) {  // the Conv3d patch embedding [D, C, 1, 2, 2]
-            shape[0] = p.shape[0], shape[1] = p.shape[1], shape[2] = 1, shape[3] = 2, shape[4] = 2;
-        } else {
-            for (int i = 0; i < 4; ++i) shape[i] = p.shape[i];
-            shape[4] = 1;
-        }
+        if (nd == 5) shape[2] = 1, shape[3] = 2, shape[4] = 2;  // the Conv3d patch embedding [D, C, 1, 2, 2]
+        else shape[4] = 1;
     }
     return FG_OK;
 }
 
 int fg_wan_bind_param(fg_wan* h, const char* name, const float* device_ptr, int64_t numel) {
-    if (!h || !name || !device_ptr) return fail(FG_EINVAL, "null argument");
-    const int i = h->find(name);
-    if (i < 0) return fail(FG_EINVAL, "unknown parameter '%s'", name);
-    if (h->params[i].numel != numel)
-        return fail(FG_EINVAL, "parameter '%s': expected %lld elements, got %lld", name, (long long)h->params[i].numel, (long long)numel);
-    h->params[i].ptr = device_ptr;
-    h->dirty[i] = 1;
-    h->packed = false;
-    return FG_OK;
+    int i;
+    const int rc = bind_param(h, name, device_ptr, numel, &i);
+    if (!rc) h->dirty[i] = 1;
+    return rc;
 }
 
 int fg_wan_pack_weights(fg_wan* h, void* stream) { return fg_wan_pack_group(h, "", nullptr, stream); }
@@ -266,66 +272,7 @@ int fg_wan_pack_weights(fg_wan* h, void* stream) { return fg_wan_pack_group(h, "
 // Pack the parameters whose names start with `prefix` (and not with `exclude`, nullable): the unit FSDP2 gathers at a time
 // ("transformer.blocks.7.", or "transformer." without "transformer.blocks." for the root group).
 int fg_wan_pack_group(fg_wan* h, const char* prefix, const char* exclude, void* stream) {
-    if (!h || !prefix) return fail(FG_EINVAL, "null argument");
-    hipStream_t s = (hipStream_t)stream;
-    const std::string pre(prefix), exc(exclude ? exclude : "");
-    auto in_group = [&](const std::string& n) { return n.rfind(pre, 0) == 0 && (exc.empty() || n.rfind(exc, 0) != 0); };
-    for (size_t i = 0; i < h->params.size(); ++i)
-        if (in_group(h->params[i].name) && !h->params[i].ptr && !h->is_logvar((int)i))
-            return fail(FG_ENOTREADY, "parameter '%s' is not bound", h->params[i].name.c_str());
-    const size_t D = h->D, Fd = h->Fd, Td = h->cfg.text_dim;
-    int rc;
-    if (!h->device_ready) {
-        if ((rc = wan_alloc(h, &h->p_x1, D * Td * 2)) || (rc = wan_alloc(h, &h->p_x2, D * D * 2))) return rc;
-        for (fg_wan::Blk& b : h->blocks) {
-            if ((rc = wan_alloc(h, &b.p_qkv, 3 * D * D * 2)) || (rc = wan_alloc(h, &b.p_o, D * D * 2)) || (rc = wan_alloc(h, &b.p_q2, D * D * 2)) ||
-                (rc = wan_alloc(h, &b.p_kv2, 2 * D * D * 2)) || (rc = wan_alloc(h, &b.p_o2, D * D * 2)) || (rc = wan_alloc(h, &b.p_f0, Fd * D * 2)) ||
-                (rc = wan_alloc(h, &b.p_f2, D * Fd * 2)) || (rc = wan_alloc(h, (void**)&b.b_qkv, 3 * D * 4)) ||
-                (rc = wan_alloc(h, (void**)&b.b_kv2, 2 * D * 4)) || (rc = wan_alloc(h, (void**)&b.n2mod, 2 * D * 4)))
-                return rc;
-        }
-        for (size_t i = 0; i < h->params.size(); ++i)
-            if (!h->pack_only[i] && !h->is_logvar((int)i) && (rc = wan_alloc(h, (void**)&h->own[i], sizeof(float) * (size_t)h->params[i].numel))) return rc;
-        if ((rc = wan_build_rope(h))) return rc;
-        if (launch_gemm_bf16(GemmArgs{}, s, true) != 0) return fail(FG_EHIP, "hipFuncSetAttribute(dynamic LDS) failed");
-        h->device_ready = true;
-    }
-    for (size_t i = 0; i < h->params.size(); ++i)
-        if (h->own[i] && in_group(h->params[i].name))
-            HIP_TRY(hipMemcpyAsync(h->own[i], h->params[i].ptr, sizeof(float) * (size_t)h->params[i].numel, hipMemcpyDeviceToDevice, s));
-    auto raw = [&](int idx) { return h->params[idx].ptr; };
-    if (in_group(h->params[h->x1_w].name)) {
-        HIP_TRY(launch_cvt_bf16(raw(h->x1_w), h->p_x1, D * Td, s));
-        HIP_TRY(launch_cvt_bf16(raw(h->x2_w), h->p_x2, D * D, s));
-    }
-    const int g1 = (int)((D + 255) / 256);
-    for (fg_wan::Blk& b : h->blocks) {
-        if (!in_group(h->params[b.q_w].name)) continue;  // (a block's parameters share their prefix: all of them in the group or none)
-        __bf16* qkv = (__bf16*)b.p_qkv;
-        HIP_TRY(launch_cvt_bf16(raw(b.q_w), qkv, D * D, s));
-        HIP_TRY(launch_cvt_bf16(raw(b.k_w), qkv + D * D, D * D, s));
-        HIP_TRY(launch_cvt_bf16(raw(b.v_w), qkv + 2 * D * D, D * D, s));
-        HIP_TRY(launch_cvt_bf16(raw(b.o_w), b.p_o, D * D, s));
-        HIP_TRY(launch_cvt_bf16(raw(b.q2_w), b.p_q2, D * D, s));
-        __bf16* kv2 = (__bf16*)b.p_kv2;
-        HIP_TRY(launch_cvt_bf16(raw(b.k2_w), kv2, D * D, s));
-        HIP_TRY(launch_cvt_bf16(raw(b.v2_w), kv2 + D * D, D * D, s));
-        HIP_TRY(launch_cvt_bf16(raw(b.o2_w), b.p_o2, D * D, s));
-        HIP_TRY(launch_cvt_bf16(raw(b.f0_w), b.p_f0, Fd * D, s));
-        HIP_TRY(launch_cvt_bf16(raw(b.f2_w), b.p_f2, D * Fd, s));
-        hipLaunchKernelGGL(wan_cat_kernel, dim3(g1), dim3(256), 0, s, raw(b.q_b), raw(b.k_b), raw(b.v_b), b.b_qkv, (int)D);
-        hipLaunchKernelGGL(wan_cat_kernel, dim3(g1), dim3(256), 0, s, raw(b.k2_b), raw(b.v2_b), (const float*)nullptr, b.b_kv2, (int)D);
-        hipLaunchKernelGGL(wan_n2mod_kernel, dim3(g1), dim3(256), 0, s, raw(b.n2_w), raw(b.n2_b), b.n2mod, (int)D);
-        HIP_TRY(hipGetLastError());
-    }
-    bool all = true;
-    for (size_t i = 0; i < h->params.size(); ++i) {
-        if (in_group(h->params[i].name)) h->dirty[i] = 0;
-        if (h->dirty[i] && !h->is_logvar((int)i)) all = false;
-    }
-    h->packed = all;
-    h->text_B = 0;  // the text caches were computed with the previous weights
-    return FG_OK;
+    return pack_group(h, prefix, exclude, stream, wan_pack);
 }
 
 size_t fg_wan_workspace_bytes(const fg_wan* h, int batch, int frames, int height, int width) {
@@ -366,9 +313,9 @@ int fg_wan_set_text(fg_wan* h, const float* text, int batch, int text_len, void*
     void* e2 = (char*)e1 + ((M * D * 2 + 255) & ~(size_t)255);
     if (h->text_B != batch || h->text_L != text_len) {
         for (fg_wan::Blk& b : h->blocks) {
-            wan_free(h, b.kv2);
+            h->free(b.kv2);
             b.kv2 = nullptr;
-            int rc = wan_alloc(h, &b.kv2, M * 2 * D * 2);
+            int rc = h->alloc(&b.kv2, M * 2 * D * 2);
             if (rc) return rc;
         }
     }
@@ -393,12 +340,12 @@ int wan_ensure_caches(fg_wan* h, int batch, int height, int width, hipStream_t s
     const int cap = h->cfg.total_num_frames * (height / 2) * (width / 2), D = h->D;
     if (h->cache_B == batch && h->cache_cap == cap) return FG_OK;
     for (fg_wan::Blk& b : h->blocks) {
-        wan_free(h, b.kc);
-        wan_free(h, b.vc);
+        h->free(b.kc);
+        h->free(b.vc);
         b.kc = b.vc = nullptr;
         const size_t bytes = (size_t)batch * cap * D * 2;
         int rc;
-        if ((rc = wan_alloc(h, &b.kc, bytes)) || (rc = wan_alloc(h, &b.vc, bytes))) return rc;
+        if ((rc = h->alloc(&b.kc, bytes)) || (rc = h->alloc(&b.vc, bytes))) return rc;
         HIP_TRY(hipMemsetAsync(b.kc, 0, bytes, s));
         HIP_TRY(hipMemsetAsync(b.vc, 0, bytes, s));
     }

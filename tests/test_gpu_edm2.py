@@ -142,7 +142,7 @@ def test_generator_fn_narrow(narrow, mode):
 
 @pytest.mark.parametrize("mode", MODES)
 def test_graph_replay_bit_equal_to_eager(narrow, mode):
-    _, _, net = narrow
+    _, sd, net = narrow
     net.compute_dtype = mode
     noise = seeded((3, 3, 64, 64), 31).cuda()
     cond = torch.nn.functional.one_hot(torch.arange(3), 10).float().cuda()
@@ -166,6 +166,19 @@ def test_graph_replay_bit_equal_to_eager(narrow, mode):
         if tl[i + 1] > 0:
             x = ns.forward_process(x0, eps[i], tl[i + 1].cuda().expand(3))
     assert (fused - x0).abs().max().item() <= 1e-4 * x0.abs().max().item()
+    # sigma_shift (eval mode only) is baked into the captured graph: with every buffer the same, so that the graph key matches, a
+    # train() / eval() flip must still not replay the graph captured in the other mode
+    shifted = make_net(D.NARROW, sd, sigma_shift=0.05, compute_dtype=mode)
+    out = torch.empty_like(noise)
+    runs = []
+    with torch.no_grad():
+        for training in (False, True, False):
+            shifted.train(training)
+            g = shifted.few_step_sample(noise, cond, tl, sample_type="sde", seed=7, use_graph=True, out=out).clone()
+            e = shifted.few_step_sample(noise, cond, tl, sample_type="sde", seed=7, use_graph=False)
+            assert torch.equal(g, e), f"training={training}"
+            runs.append(g)
+    assert not torch.equal(runs[0], runs[1]) and torch.equal(runs[0], runs[2])
 
 
 def test_ragged_batches(narrow):
