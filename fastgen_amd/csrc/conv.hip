@@ -718,7 +718,8 @@ int conv_prepare_all(int dtype) {
     if (!rc && dtype == 2) {
         ConvArgs w{};
         for (int res : {RES_NONE, RES_UP})
-            for (int ww : {32, 16}) {
+            for (int ww : {32, 16, 8}) {
+                if (ww == 8 && res != RES_NONE) continue;
                 w.W = w.H = ww;
                 if (!rc) rc = launch_conv_x3ws(res, w, nullptr, true, PRO_GN_SILU);
                 if (!rc && res == RES_NONE) rc = launch_conv_x3ws(res, w, nullptr, true, PRO_NONE);

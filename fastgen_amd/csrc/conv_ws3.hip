@@ -2,7 +2,8 @@
 // memory, every product a_lo*b_hi + a_hi*b_lo + a_hi*b_hi on v_mfma_f32_16x16x32_bf16 with fp32 accumulation (common.h).
 // Same operation as conv_fused_kernel<bf16x3, 3, ...> (GroupNorm-apply + SiLU -> conv -> bias / temb / residual / scale + the
 // GroupNorm partial statistics of the result; reference fastgen/networks/EDM/network.py:93-126, 274-299), for 256 output
-// channels at 32x32 / 16x16 with or without the nearest 2x up-sampling folded into the load.
+// channels at 32x32 / 16x16 with or without the nearest 2x up-sampling folded into the load, and at 8x8 (two whole images per
+// tile, X3Geom).
 //
 // Why not conv_fused_kernel: measured there (profiles/r02_x3a_*), the matrix pipe is 76 % busy but the chip holds only
 // 1.72 GHz under the 32x32x16 shape; the 16x16x32 shape sustains a higher clock on real data (profiles/r01_micro_mfma_peak_vs_data.txt),
@@ -41,15 +42,20 @@ constexpr int X3_HOFF = 128 * 512;         // 65536
 constexpr int X3_LDS = X3_HOFF + X3_RING * X3_ABUF;  // 163840 = the CU's whole LDS
 constexpr int X3_STEPB = 9 * 2048;         // bytes of packed weights per step and 16-channel group: [tap][part][lane][8] bf16
 
+// 32x32 / 16x16: a tile is an 8x16-pixel window of one image.  8x8: a tile is TWO whole images side by side (image 2t in columns
+// 0-7, image 2t+1 in columns 8-15); their halos share the zero column between them, so a halo row is 1 + 8 + 1 + 8 + 1 = 19
+// pixels and the consumer lanes of columns 8-15 read one pixel further right.
 template <int LOGW>
 struct X3Geom {
     static constexpr int W = 1 << LOGW;
     static constexpr int TW = 16, TH = 8;
-    static constexpr int TCOLS = W / TW;
-    static constexpr int TPI = (W / TH) * TCOLS;  // tiles per image
-    static constexpr int HW_ = TW + 2, HH_ = TH + 2;
-    static constexpr int HALO_PIX = HW_ * HH_;    // 180
-    static constexpr int RS = HW_ * X3_PA;        // 288
+    static constexpr int IPT = LOGW == 3 ? 2 : 1;                 // images per tile
+    static constexpr int TCOLS = LOGW == 3 ? 1 : W / TW;
+    static constexpr int TPI = LOGW == 3 ? 1 : (W / TH) * TCOLS;  // tiles per image (8x8: per image pair)
+    static constexpr int HW_ = LOGW == 3 ? 2 * W + 3 : TW + 2, HH_ = TH + 2;
+    static constexpr int HALO_PIX = HW_ * HH_;    // 180 (8x8: 190)
+    static constexpr int RS = HW_ * X3_PA;        // 288 (8x8: 304)
+    static_assert(HALO_PIX * X3_PA <= X3_PLANE && HALO_PIX <= 192, "one halo plane; three producer passes of 64 pixels");
 };
 
 __device__ __forceinline__ void x3_barrier() {
@@ -111,7 +117,7 @@ __global__ __launch_bounds__(X3_NTHR) void conv3_x3ws_kernel(const ConvArgs a, c
 #pragma unroll
             for (int nt = 0; nt < 2; ++nt) acc[m][nt] = f32x4{0.f, 0.f, 0.f, 0.f};
 
-        const int lane_off = g4 * X3_PLANE + col * X3_PA;
+        const int lane_off = g4 * X3_PLANE + (col + ((G::IPT == 2 && col >= 8) ? 1 : 0)) * X3_PA;
         // hand-off slot of this lane's channel quad (8 wl + 4 nt + g4 of the half's 32) for pixel (row m, column col)
         const int dl0 = col * 512 + ((8 * wl + ((g4) ^ (col & 7))) << 4);
         const int dl1 = col * 512 + ((8 * wl + ((4 + g4) ^ (col & 7))) << 4);
@@ -197,19 +203,34 @@ __global__ __launch_bounds__(X3_NTHR) void conv3_x3ws_kernel(const ConvArgs a, c
     const float* src1 = reinterpret_cast<const float*>(a.src1);
     const float* src2 = reinterpret_cast<const float*>(a.src2);
     int hdy[3], hdx[3], hlds[3];
+    bool third;  // item 2 exists for 52 (8x8: 62) of the 64 pixel slots
+    // 8x8: halo columns 0-8 are x = -1..7 of the tile's first image (slots 0-29, 90 pixels), columns 9-18 x = -1..8 of its second
+    // (slots 30-63, 100 pixels; the shared column 9 is staged as the second image's x = -1): a thread's pixels lie in ONE image,
+    // so it needs one image's GroupNorm coefficients
+    const int pslot = ptid >> 2;
+    const int pimg = (G::IPT == 2 && pslot >= 30) ? 1 : 0;
 #pragma unroll
     for (int i = 0; i < 3; ++i) {
-        const int hq = min((ptid >> 2) + 64 * i, G::HALO_PIX - 1);
-        const int hy = hq / G::HW_, hx = hq - hy * G::HW_;
+        int hy, hx;
+        if (G::IPT == 2) {
+            const int l = pimg ? min(pslot - 30 + 34 * i, 99) : pslot + 30 * i;
+            hy = pimg ? l / 10 : l / 9;
+            hx = pimg ? 9 + (l - hy * 10) : l - hy * 9;
+            third = pimg ? pslot - 30 + 68 < 100 : true;
+        } else {
+            const int hq = min(pslot + 64 * i, G::HALO_PIX - 1);
+            hy = hq / G::HW_;
+            hx = hq - hy * G::HW_;
+            third = pslot + 128 < G::HALO_PIX;
+        }
         hdy[i] = hy - 1;
-        hdx[i] = hx - 1;
+        hdx[i] = hx - 1 - pimg * (G::W + 1);
         hlds[i] = oct * X3_PLANE + hy * G::RS + hx * X3_PA;
     }
-    const bool third = (ptid >> 2) + 128 < G::HALO_PIX;  // item 2 exists for 52 of the 64 pixel slots
 
     auto tile_coord = [&](int t, int& n, int& slot, int& row0, int& col0) {
-        n = t / G::TPI;
-        slot = t - n * G::TPI;
+        n = t * G::IPT / G::TPI;  // 8x8: the first image of the pair
+        slot = t - n * G::TPI / G::IPT;
         row0 = (slot / G::TCOLS) * G::TH;
         col0 = (slot % G::TCOLS) * G::TW;
     };
@@ -224,10 +245,16 @@ __global__ __launch_bounds__(X3_NTHR) void conv3_x3ws_kernel(const ConvArgs a, c
     auto tile_setup = [&](int t) __attribute__((always_inline)) {
         int n, slot, row0, col0;
         tile_coord(t, n, slot, row0, col0);
+        bool in_batch = true;
+        if (G::IPT == 2) {  // this thread's image of the pair; the second image of the last pair lies past an odd batch
+            n += pimg;
+            in_batch = n < a.B;
+            n = min(n, a.B - 1);
+        }
 #pragma unroll
         for (int i = 0; i < 3; ++i) {
             const int y = row0 + hdy[i], x = col0 + hdx[i];
-            valid[i] = (y >= 0) && (y < H) && (x >= 0) && (x < G::W) && (i < 2 || third);
+            valid[i] = (y >= 0) && (y < H) && (x >= 0) && (x < G::W) && (i < 2 || third) && in_batch;
             const int yc = min(max(y, 0), H - 1), xc = min(max(x, 0), G::W - 1);
             const int sy = (RES == RES_UP) ? (yc >> 1) : yc, sx = (RES == RES_UP) ? (xc >> 1) : xc;
             const unsigned pix = (unsigned)((n * a.Hs + sy) * a.Ws + sx);
@@ -292,12 +319,20 @@ __global__ __launch_bounds__(X3_NTHR) void conv3_x3ws_kernel(const ConvArgs a, c
         int n, slot, row0, col0;
         tile_coord(t, n, slot, row0, col0);
         const int co = half * 128 + chq * 4;
-        f32x4 radd = {0.f, 0.f, 0.f, 0.f};
-        if (a.bias) radd = *reinterpret_cast<const f32x4*>(a.bias + co);
-        if (a.temb) radd += *reinterpret_cast<const f32x4*>(a.temb + (size_t)n * a.temb_stride + co);
-        radd *= a.scale;  // (acc + add + resid) * scale evaluated as fma(acc, scale, add * scale) [+ fma(resid, scale, .)]
+        // 8x8: the pixels of pass j < 4 lie in the tile's first image, those of j >= 4 in its second (column 2 j + psub); `nimg` of the
+        // two exist (the second image of the last pair lies past an odd batch)
+        const int nimg = G::IPT == 2 ? min(2, a.B - n) : 1;
+        f32x4 radd[G::IPT];
+#pragma unroll
+        for (int k = 0; k < G::IPT; ++k) {
+            radd[k] = f32x4{0.f, 0.f, 0.f, 0.f};
+            if (a.bias) radd[k] = *reinterpret_cast<const f32x4*>(a.bias + co);
+            const int nk = G::IPT == 2 ? min(n + k, a.B - 1) : n;
+            if (a.temb) radd[k] += *reinterpret_cast<const f32x4*>(a.temb + (size_t)nk * a.temb_stride + co);
+            radd[k] *= a.scale;  // (acc + add + resid) * scale evaluated as fma(acc, scale, add * scale) [+ fma(resid, scale, .)]
+        }
         const size_t tb = (((size_t)n * H + row0) * G::W + col0) * 256 + co;
-        float ssum = 0.f, ssq = 0.f;
+        float ssum[G::IPT] = {}, ssq[G::IPT] = {};
 #pragma unroll 1
         for (int grp8 = 0; grp8 < 2; ++grp8) {
             f32x4 rr[8], dv[8];
@@ -305,29 +340,38 @@ __global__ __launch_bounds__(X3_NTHR) void conv3_x3ws_kernel(const ConvArgs a, c
 #pragma unroll
             for (int j = 0; j < 8; ++j) {
                 const int px = pw * 32 + 2 * (grp8 * 8 + j) + psub;
-                go[j] = (unsigned)(((px >> 4) * G::W + (px & 15)) * 256);
+                if (G::IPT == 2)
+                    go[j] = (unsigned)((((j >> 2) * G::W + (px >> 4)) * G::W + (px & 7)) * 256);
+                else
+                    go[j] = (unsigned)(((px >> 4) * G::W + (px & 15)) * 256);
                 rr[j] = f32x4{0.f, 0.f, 0.f, 0.f};
-                if (has_resid) rr[j] = *reinterpret_cast<const f32x4*>(resid + tb + go[j]);
+                if (has_resid && (G::IPT == 1 || (j >> 2) < nimg)) rr[j] = *reinterpret_cast<const f32x4*>(resid + tb + go[j]);
                 dv[j] = *reinterpret_cast<const f32x4*>(hbuf + px * 512 + ((chq ^ (px & 7)) << 4));
             }
 #pragma unroll
             for (int j = 0; j < 8; ++j) {
+                const int k = G::IPT == 2 ? j >> 2 : 0;
+                if (G::IPT == 2 && k >= nimg) continue;
                 f32x4 v;
 #pragma unroll
-                for (int e = 0; e < 4; ++e) v[e] = fmaf(dv[j][e], a.scale, radd[e]);
+                for (int e = 0; e < 4; ++e) v[e] = fmaf(dv[j][e], a.scale, radd[k][e]);
                 if (has_resid) {
 #pragma unroll
                     for (int e = 0; e < 4; ++e) v[e] = fmaf(rr[j][e], a.scale, v[e]);
                 }
                 *reinterpret_cast<f32x4*>(out + tb + go[j]) = v;
-                ssum += (v[0] + v[1]) + (v[2] + v[3]);
-                ssq += (v[0] * v[0] + v[1] * v[1]) + (v[2] * v[2] + v[3] * v[3]);
+                ssum[k] += (v[0] + v[1]) + (v[2] + v[3]);
+                ssq[k] += (v[0] * v[0] + v[1] * v[1]) + (v[2] * v[2] + v[3] * v[3]);
             }
         }
-        ssum += __shfl_xor(ssum, 32);
-        ssq += __shfl_xor(ssq, 32);
-        // one statistics slot per (tile, producer wave): [n][TPI * 4][64 quads]
-        if (a.stats && psub == 0) a.stats[(((size_t)n * G::TPI + slot) * 4 + pw) * 64 + half * 32 + chq] = make_float2(ssum, ssq);
+#pragma unroll
+        for (int k = 0; k < G::IPT; ++k) {
+            ssum[k] += __shfl_xor(ssum[k], 32);
+            ssq[k] += __shfl_xor(ssq[k], 32);
+            // one statistics slot per (tile, producer wave) and image: [n][TPI * 4][64 quads] (8x8: [n][4][64])
+            if (a.stats && psub == 0 && k < nimg)
+                a.stats[(((size_t)(n + k) * G::TPI + slot) * 4 + pw) * 64 + half * 32 + chq] = make_float2(ssum[k], ssq[k]);
+        }
     };
 
     // ---- step machine: during global step s the producers (1) issue the loads of step s+1, (2) retire the half tile a consumer
@@ -403,7 +447,7 @@ int launch_x3_one(const ConvArgs& a, hipStream_t stream, bool prepare_only) {
         g_x3_cus[dev] = n;
     }
     if (prepare_only) return 0;
-    const int ntiles = a.B * G::TPI;
+    const int ntiles = (a.B * G::TPI + G::IPT - 1) / G::IPT;
     const int grid = ntiles < g_x3_cus[dev] ? ntiles : g_x3_cus[dev];
     hipLaunchKernelGGL(kern, dim3(grid), dim3(X3_NTHR), X3_LDS, stream, a, ntiles);
     return (int)hipGetLastError();
@@ -412,22 +456,28 @@ int launch_x3_one(const ConvArgs& a, hipStream_t stream, bool prepare_only) {
 }  // namespace
 
 // statistics slots per image written by this kernel: one per (tile, producer wave)
-int conv_x3ws_stat_slots(int W) { return (W == 32 ? X3Geom<5>::TPI : X3Geom<4>::TPI) * 4; }
+int conv_x3ws_stat_slots(int W) { return (W == 32 ? X3Geom<5>::TPI : W == 16 ? X3Geom<4>::TPI : X3Geom<3>::TPI) * 4; }
 
-bool conv_x3ws_shape_ok(int cout, int cin, int res) { return cout == 256 && (res == 32 || res == 16) && (cin % X3_KC) == 0 && cin / X3_KC >= 4; }
+bool conv_x3ws_shape_ok(int cout, int cin, int res) {
+    return cout == 256 && (res == 32 || res == 16 || res == 8) && (cin % X3_KC) == 0 && cin / X3_KC >= 4;
+}
 
 bool conv_x3ws_supported(int ks, int pro, int res, int outmode, const ConvArgs& a) {
     const int cin = a.C1 + a.C2;
     const size_t src_bytes = (size_t)a.B * a.Hs * a.Ws * (size_t)(a.C1 > a.C2 ? a.C1 : a.C2) * 4;
     if (src_bytes >= (1ull << 32)) return false;  // the staged loads use 32-bit byte offsets into each source tensor
     if (ks != 3 || outmode != OUT_NHWC || a.H != a.W || !conv_x3ws_shape_ok(a.Cout, cin, a.W) || (a.C1 % X3_KC) || !a.wpack_ws) return false;
+    if (a.W == 8 && res != RES_NONE) return false;
     if (pro == PRO_NONE) return res == RES_NONE && a.Hs == a.H && a.Ws == a.W;
     return pro == PRO_GN_SILU && (res == RES_NONE || res == RES_UP) && a.ab != nullptr;
 }
 
 int launch_conv_x3ws(int res, const ConvArgs& a, hipStream_t stream, bool prepare_only, int pro) {
-    if (pro == PRO_NONE) {
+    if (pro == PRO_NONE || a.W == 8) {
         if (res != RES_NONE) return (int)hipErrorInvalidValue;
+        if (a.W == 8)
+            return pro == PRO_NONE ? launch_x3_one<RES_NONE, 3, PRO_NONE>(a, stream, prepare_only)
+                                   : launch_x3_one<RES_NONE, 3, PRO_GN_SILU>(a, stream, prepare_only);
         return a.W == 32 ? launch_x3_one<RES_NONE, 5, PRO_NONE>(a, stream, prepare_only) : launch_x3_one<RES_NONE, 4, PRO_NONE>(a, stream, prepare_only);
     }
     if (a.W == 32)
