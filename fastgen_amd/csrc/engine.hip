@@ -1566,5 +1566,41 @@ int fg_op_gemm_bf16(const void* a, const void* w, const float* bias, void* out, 
     HIP_TRY(rc);
     return FG_OK;
 }
+int fg_op_gemm_x3(const float* a, const float* w, const float* bias, void* out, int m, int n, int k, int act, const float* gate,
+                  int gate_stride, int gate_rows, const float* resid, int out_mode, void* stream) {
+    // the checks of launch_gemm_x3 (and its row cutting: every launch keeps whole 256-row tiles) before anything is allocated or launched
+    if (m < 256 || n < 256 || (n % 16) || k <= 0 || (k % 64) || (size_t)n * 3 * k * 2 >= (1ull << 31))
+        return fail(FG_EINVAL, "fg_op_gemm_x3: unsupported shape m %d (>= 256), n %d (>= 256, %% 16), k %d (%% 64), 6 n k < 2^31", m, n, k);
+    const int rows_max = (int)(((1ull << 31) - 1) / ((size_t)k * 4)) / 256 * 256;
+    if (m % rows_max && m % rows_max < 256) return fail(FG_EINVAL, "fg_op_gemm_x3: m %d leaves a last launch of fewer than 256 rows", m);
+    if (act != 0 && act != 1) return fail(FG_EINVAL, "fg_op_gemm_x3: act must be 0 (none) or 1 (GELU tanh), got %d", act);
+    if (out_mode != 0 && out_mode != 1) return fail(FG_EINVAL, "fg_op_gemm_x3: out_mode must be 0 (fp32) or 1 ([hi | lo] planes), got %d", out_mode);
+    if (!a || !w || !out) return fail(FG_EINVAL, "fg_op_gemm_x3: null pointer");
+    if (gate && (gate_rows <= 0 || gate_stride < n || (gate_stride % 4)))
+        return fail(FG_EINVAL, "fg_op_gemm_x3: gate_rows %d > 0, gate_stride %d >= n and a multiple of 4", gate_rows, gate_stride);
+    if ((((uintptr_t)a) | ((uintptr_t)w) | ((uintptr_t)out) | ((uintptr_t)bias) | ((uintptr_t)gate) | ((uintptr_t)resid)) & 15)
+        return fail(FG_EINVAL, "fg_op_gemm_x3: a / w / out / bias / gate / resid must be 16-byte aligned");
+    if (resid && out_mode == 1 && (const void*)resid == out) return fail(FG_EINVAL, "fg_op_gemm_x3: out_mode 1 cannot write over resid");
+    const hipStream_t s = (hipStream_t)stream;
+    HIP_TRY(launch_gemm_bf16(GemmArgs{}, s, true));
+    // A as [hi | lo] planes [m][2 k], W as [hi | lo | hi] [n][3 k] (what the DiT's layers produce and pack)
+    void *ap = nullptr, *wp = nullptr;
+    hipError_t herr = hipMalloc(&ap, (size_t)m * k * 4);
+    if (herr == hipSuccess) herr = hipMalloc(&wp, (size_t)n * k * 6);
+    int rc = (int)herr;
+    if (!rc) rc = launch_split_planes(a, ap, (int64_t)m, k, s);
+    if (!rc) rc = launch_split3_weights(w, wp, n, k, s);
+    if (!rc) {
+        GemmArgs g;
+        g.A = ap; g.W = wp; g.bias = bias; g.out = out; g.M = m; g.N = n; g.K = k; g.act = act;
+        g.gate = gate; g.gate_stride = gate_stride; g.gate_rows = gate_rows; g.resid = resid;
+        rc = launch_gemm_x3(g, out_mode, s);
+    }
+    (void)hipStreamSynchronize(s);
+    if (ap) (void)hipFree(ap);
+    if (wp) (void)hipFree(wp);
+    HIP_TRY(rc);
+    return FG_OK;
+}
 
 }  // extern "C"

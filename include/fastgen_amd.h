@@ -507,6 +507,14 @@ FG_API int fg_op_attention_split(const void* q, const void* k, const void* v, vo
  * half the CUs split K (fp32 partial sums + a finishing pass).  Exposed for the parity tests and scripts/gemm_bench.py. */
 FG_API int fg_op_gemm_bf16(const void* a, const void* w, const float* bias, void* out, int m, int n, int k, int act, const float* gate,
                            int gate_stride, int gate_rows, const void* resid, int tile_order, void* stream);
+/* The same token GEMM in the split-bf16 (FG_DTYPE_BF16X3) mode, the DiT's default: a [m][k] and w [n][k] fp32 are split into bf16
+ * hi / lo planes (scratch allocated here, freed once the stream has drained: a test entry point, not a hot path) and contracted as
+ * a_hi w_hi + a_hi w_lo + a_lo w_hi with fp32 accumulation; out[m][n] = resid[m][n] + gate[(m / gate_rows) * gate_stride + n] *
+ * act(... + bias[n]) in fp32.  out_mode 0: out fp32 [m][n] (out may alias resid); 1: out [m][2 n] bf16, row r = [hi | lo] of the
+ * fp32 value.  act 0 none, 1 GELU(tanh); bias, gate, resid nullable (fp32; every pointer 16-byte aligned; gate_stride a multiple of 4, >= n).
+ * m >= 256, n >= 256, n % 16 == 0, k % 64 == 0, n * 3 k * 2 < 2^31; anything else: FG_EINVAL before any launch. */
+FG_API int fg_op_gemm_x3(const float* a, const float* w, const float* bias, void* out, int m, int n, int k, int act, const float* gate,
+                         int gate_stride, int gate_rows, const float* resid, int out_mode, void* stream);
 
 /* ================================ EDM2 U-Net (EDM2Precond, reference fastgen/networks/EDM2/network.py) ================================
  * The magnitude-preserving ImageNet-64 network of the EDM2 consistency-model recipes, forward and few-step sampling only.  A handle of

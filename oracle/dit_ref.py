@@ -99,10 +99,12 @@ def random_state_dict(cfg: DiTConfig, seed: int = 0) -> Dict[str, Tensor]:
 
 
 def fourier_features(t: Tensor, dim: int = 256, max_freq: float = 10000.0) -> Tensor:
-    """FourierTimeEmbedding.encode_timesteps, :67-96: [cos | sin] of t * exp(-ln(max_freq) * i / half), fp32."""
+    """FourierTimeEmbedding.encode_timesteps, :67-96: [cos | sin] of t * exp(-ln(max_freq) * i / half), fp32 (fp64 for an fp64 t:
+    the per-op pins of tests/test_gpu_dit_blocks.py evaluate the whole network in fp64)."""
     half = dim // 2
-    freq = torch.exp(-math.log(max_freq) * torch.arange(0, half, dtype=torch.float32) / half)
-    ang = t[:, None].float() * freq[None, :]
+    ct = torch.promote_types(t.dtype, torch.float32)
+    freq = torch.exp(-math.log(max_freq) * torch.arange(0, half, dtype=ct) / half)
+    ang = t[:, None].to(ct) * freq[None, :]
     return torch.cat([torch.cos(ang), torch.sin(ang)], dim=-1).to(t.dtype)
 
 
@@ -143,13 +145,26 @@ def dit_block(sd, i: int, x: Tensor, c: Tensor, heads: int) -> Tensor:
     return x + f_gate.unsqueeze(1) * h
 
 
+def patch_embed(sd, cfg: DiTConfig, x_t: Tensor) -> Tensor:
+    """PatchEmbed (restated): Conv2d(kernel = stride = patch) -> [B, N, D], + pos_embed (:511)."""
+    w, b = sd["x_embedder.proj.weight"], sd["x_embedder.proj.bias"]
+    return F.conv2d(x_t, w, b, stride=cfg.patch_size).flatten(2).transpose(1, 2) + sd["pos_embed"]
+
+
+def final_layer(sd, cfg: DiTConfig, x: Tensor, c: Tensor) -> Tensor:
+    """OutputProjection (:204-225) on the last block's tokens [B, N, D], then unpatchify (:437-455) -> [B, C, H, W]."""
+    B, p, C = x.shape[0], cfg.patch_size, cfg.in_channels
+    shift, scale = F.linear(F.silu(c), sd["final_layer.adaptive_params.1.weight"], sd["final_layer.adaptive_params.1.bias"]).chunk(2, dim=1)
+    x = F.linear(modulate(layer_norm(x), shift, scale), sd["final_layer.projection.weight"], sd["final_layer.projection.bias"])
+    g = math.isqrt(x.shape[1])
+    return torch.einsum("bhwpqc->bchpwq", x.reshape(B, g, g, p, p, C)).reshape(B, C, g * p, g * p)
+
+
 def dit_forward(sd, cfg: DiTConfig, x_t: Tensor, t: Tensor, condition: Tensor, r: Optional[Tensor] = None, trace=None) -> Tensor:
     """DiT.forward with fwd_pred_type = net_pred_type (identity conversion) in eval mode, :464-574.  t, r: the schedule's
     timesteps (float64 on entry, rescaled by num_steps = 1000 for the 'rf' schedule when scale_t, :457-462 and
     noise_schedule.py:1325-1326, then cast to x_t.dtype); condition: one-hot [B, num_classes] (an all-zero row is the
     unconditional class, :493-498) or class indices [B]."""
-    B, C, Hh, Ww = x_t.shape
-    p, D = cfg.patch_size, cfg.hidden_size
     if condition.ndim == 2:
         mask = torch.any(condition != 0, dim=1)
         condition = torch.where(~mask, cfg.num_classes, condition.argmax(dim=1))
@@ -157,8 +172,7 @@ def dit_forward(sd, cfg: DiTConfig, x_t: Tensor, t: Tensor, condition: Tensor, r
     t_, r_ = prep(t), prep(r)
     if cfg.use_sit_convention:
         t_ = 1 - t_
-    # PatchEmbed (restated): Conv2d(kernel = stride = patch) -> [B, N, D], + pos_embed (:511)
-    x = F.conv2d(x_t, sd["x_embedder.proj.weight"], sd["x_embedder.proj.bias"], stride=p).flatten(2).transpose(1, 2) + sd["pos_embed"]
+    x = patch_embed(sd, cfg, x_t)
     t_emb = time_embedding(sd, "t_embedder", t_)
     if cfg.r_timestep and r_ is not None:
         r_emb = time_embedding(sd, "r_embedder", (t_ - r_) if cfg.time_cond_type == "diff" else r_)
@@ -171,10 +185,7 @@ def dit_forward(sd, cfg: DiTConfig, x_t: Tensor, t: Tensor, condition: Tensor, r
         x = dit_block(sd, i, x, c, cfg.num_heads)
         if trace is not None:
             trace[f"block{i}"] = x
-    shift, scale = F.linear(F.silu(c), sd["final_layer.adaptive_params.1.weight"], sd["final_layer.adaptive_params.1.bias"]).chunk(2, dim=1)
-    x = F.linear(modulate(layer_norm(x), shift, scale), sd["final_layer.projection.weight"], sd["final_layer.projection.bias"])
-    g = Hh // p  # unpatchify, :437-455
-    x = torch.einsum("bhwpqc->bchpwq", x.reshape(B, g, g, p, p, C)).reshape(B, C, g * p, g * p)
+    x = final_layer(sd, cfg, x, c)
     if cfg.use_sit_convention:
         x = -x  # flow prediction under the SiT convention, :555-558
     return x

@@ -299,3 +299,37 @@ def test_feature_taps(golden_dir, mode):
         smp = v[:: max(1, v.numel() // 1024)][:1024]
         assert float((smp - fx[f"s/block{i}/sample"]).norm() / fx[f"s/block{i}/sample"].norm()) <= tol, i
     assert torch.equal(early[0], feats[0]) and torch.equal(early[1], feats[1]) and torch.equal(feats_lv[0], feats[2]) and torch.equal(feats_past[0], feats[1])
+
+
+def test_gemm_x3_refusals():
+    """fg_op_gemm_x3 (the split-bf16 token GEMM of the bf16x3 DiT blocks) refuses what launch_gemm_x3 cannot run - shapes, the 2 GiB
+    weight limit, a last row launch under one tile, act / out_mode values, null or misaligned pointers, bad gate strides - with
+    FG_EINVAL before it allocates or launches anything (this runs without a GPU)."""
+    import ctypes
+
+    from fastgen_amd import _lib
+
+    L = _lib.lib()
+    buf = ctypes.create_string_buffer(1 << 12)
+    p = ctypes.c_void_p(ctypes.addressof(buf) + (-ctypes.addressof(buf)) % 64)  # 64-byte aligned, never dereferenced here
+    q = ctypes.c_void_p(p.value + 1024)
+    odd = ctypes.c_void_p(p.value + 4)
+
+    def call(**kw):
+        a = dict(a=p, w=p, bias=None, out=p, m=512, n=1152, k=1152, act=0, gate=None, gate_stride=0, gate_rows=256, resid=None,
+                 out_mode=0)
+        a.update(kw)
+        return L.fg_op_gemm_x3(*a.values(), None)
+
+    for kw in (dict(m=255), dict(m=0), dict(n=240), dict(n=1160), dict(k=96), dict(k=0), dict(k=-64),
+               dict(n=4096, k=87424),                 # 6 n k >= 2^31: the weight staging offsets
+               dict(k=4608, m=116480 + 128),          # the second launch of the row cutting would be 128 rows
+               dict(act=2), dict(act=-1), dict(act=4), dict(out_mode=2), dict(out_mode=-1),
+               dict(a=None), dict(w=None), dict(out=None), dict(a=odd), dict(w=odd), dict(out=odd), dict(bias=odd),
+               dict(resid=odd), dict(gate=odd, gate_stride=6912), dict(gate=p, gate_stride=1148), dict(gate=p, gate_stride=1154),
+               dict(gate=p, gate_stride=6912, gate_rows=0), dict(resid=p, out_mode=1)):
+        assert call(**kw) == 1, kw
+        assert b"fg_op_gemm_x3" in L.fg_last_error(), kw
+    assert call(act=3) == 1 and b"act must be" in L.fg_last_error()
+    assert call(out_mode=3) == 1 and b"out_mode" in L.fg_last_error()
+    assert call(resid=q, out_mode=1, out=q) == 1
