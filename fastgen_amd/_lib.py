@@ -11,7 +11,9 @@ FG_MAX_LEVELS = 8
 FG_DTYPE_F32, FG_DTYPE_BF16, FG_DTYPE_BF16X3 = 0, 1, 2
 DTYPE_NAMES = {"fp32": FG_DTYPE_F32, "bf16": FG_DTYPE_BF16, "bf16x3": FG_DTYPE_BF16X3}
 FG_SAMPLE_SDE, FG_SAMPLE_ODE = 0, 1
+SAMPLE_TYPES = {"sde": FG_SAMPLE_SDE, "ode": FG_SAMPLE_ODE}
 FG_LOOP_X0, FG_LOOP_MEANFLOW, FG_LOOP_EULER = 0, 1, 2
+LOOP_KINDS = {"x0": FG_LOOP_X0, "meanflow": FG_LOOP_MEANFLOW, "euler": FG_LOOP_EULER}
 FG_SCHEDULE_EDM, FG_SCHEDULE_RF = 0, 1
 FG_DROP_PRECOND_INPUT, FG_DROP_PRECOND_OUTPUT = 1, 2
 FG_BWD_DECODER, FG_BWD_ENCODER, FG_BWD_EMBED = 1, 2, 4

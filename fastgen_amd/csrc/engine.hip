@@ -340,6 +340,105 @@ int setup_ws(size_t (*plan)(const H*, int, Arena&, W&), const H* h, int B, void*
     return FG_OK;
 }
 
+// ---- the frame and loop bodies of the sampler entry points (fg_sampler_run, fg_edm2_sampler_run, fg_dit_sampler_run, fg_wan_sampler_run)
+
+// The argument checks every sampler entry point makes first, before it looks at the handle's state: the sample and loop kinds, then the
+// timestep list.  Which loops a network runs is the entry point's own check.
+int check_sampler_args(const double* t_list, int steps, int sample_type, int loop_kind, int schedule) {
+    if (sample_type != FG_SAMPLE_SDE && sample_type != FG_SAMPLE_ODE) return fail(FG_EINVAL, "bad sample_type");
+    if (loop_kind != FG_LOOP_X0 && loop_kind != FG_LOOP_MEANFLOW && loop_kind != FG_LOOP_EULER) return fail(FG_EINVAL, "bad loop_kind");
+    return check_t_list(t_list, steps, schedule);
+}
+
+// The end of a single-graph sampler entry point: the step scalars go up through the ring, then `enqueue` runs eagerly or as the cached
+// graph keyed by the call's shape, its host-decided branches (zero_mask) and what the entry point adds in `more` (its buffers, settings).
+template <typename F>
+int sampler_launch(SamplerCache& st, int batch, const double* t_list, int steps, int sample_type, int loop_kind, uint64_t seed, double* tl_dev,
+                   uint64_t* seed_dev, bool use_graph, std::initializer_list<int64_t> more, hipStream_t s, F&& enqueue) {
+    const int rc = st.ring.upload(t_list, steps + 1, seed, tl_dev, seed_dev, s);
+    if (rc) return rc;
+    if (!use_graph) return enqueue(s);
+    std::vector<int64_t> key = {batch, steps, sample_type, loop_kind, zero_mask(t_list, steps)};
+    key.insert(key.end(), more);
+    return graph_run(st.graph, key, st.cap, s, enqueue);
+}
+
+// One call of a student loop on a network's buffers: the host timesteps, which decide the re-noising branches baked into a captured
+// graph, and the device state the loop steps.
+struct StudentLoop {
+    const float* noise;
+    const double* t_list;  // host, steps + 1 entries ending in 0
+    int steps, type, sched;
+    int64_t total;         // elements of the latents
+    float *x, *eps_buf;    // the latents; a drawn or implied noise tensor
+    const float* eps;      // injected 'sde' noise [steps - 1][total], or nullptr: Philox normals of stream i from *seed
+    const double* tl;      // t_list on the device
+    const uint64_t* seed;
+    float* out;
+    hipStream_t s;
+
+    int draw(int i, const float** e) const {  // the 'sde' noise of step i
+        if (eps) {
+            *e = eps + (size_t)i * total;
+            return FG_OK;
+        }
+        HIP_TRY(launch_randn(eps_buf, total, 0, (uint64_t)i, seed, s));
+        *e = eps_buf;
+        return FG_OK;
+    }
+};
+
+// The x0 loop's re-noise of step i (methods/model.py:356-363): dst = forward_process(pred, e, t_{i+1}) with e the 'sde' draw(i, &e) or,
+// for 'ode', the noise implied by (x, pred) at t_i.
+template <typename Draw>
+int renoise_x0(int i, int type, int sched, const float* x, const float* pred, float* dst, float* eps_buf, const double* tl, int64_t total,
+               hipStream_t s, Draw&& draw) {
+    const float* e = eps_buf;
+    if (type == FG_SAMPLE_SDE) {
+        const int rc = draw(i, &e);
+        if (rc) return rc;
+    } else {
+        HIP_TRY(launch_x0_to_eps(x, pred, 0.0, tl, i, sched, 1e-6, eps_buf, total, s));
+    }
+    HIP_TRY(launch_forward_process(pred, e, 0.0, tl, i + 1, sched, dst, total, s));
+    return FG_OK;
+}
+
+// FastGenModel._student_sample_loop (methods/model.py:315-372): latents = noise * sigma(t_0) (noise_schedule.py:72-88), then per step
+// net(i, pred) writes the network's x0 prediction at t_i (the last into L.out) and the latents are re-noised to t_{i+1} unless it is 0.
+template <typename Net>
+int x0_loop(const StudentLoop& L, float* pred_buf, Net&& net) {
+    HIP_TRY(launch_latents(L.noise, 0.0, L.tl, 0, L.x, L.total, L.s));
+    auto draw = [&](int i, const float** e) { return L.draw(i, e); };
+    for (int i = 0; i < L.steps; ++i) {
+        float* pred = i == L.steps - 1 ? L.out : pred_buf;
+        int rc = net(i, pred);
+        if (!rc && L.t_list[i + 1] > 0) rc = renoise_x0(i, L.type, L.sched, L.x, pred, L.x, L.eps_buf, L.tl, L.total, L.s, draw);
+        if (rc) return rc;
+    }
+    return FG_OK;
+}
+
+// MeanFlowModel._student_sample_loop (consistency_model/mean_flow.py:336-381): net(i, u) writes the average velocity u(x, t_i, r), r = 0
+// for 'sde' (jump to the data end, then re-noise to t_{i+1} unless it is 0), r = t_{i+1} for 'ode' (integrate t_i -> t_{i+1}).
+template <typename Net>
+int meanflow_loop(const StudentLoop& L, float* u, Net&& net) {
+    HIP_TRY(launch_latents(L.noise, 0.0, L.tl, 0, L.x, L.total, L.s));
+    const bool sde = L.type == FG_SAMPLE_SDE;
+    for (int i = 0; i < L.steps; ++i) {
+        int rc = net(i, u);
+        if (rc) return rc;
+        const bool renoise = sde && L.t_list[i + 1] > 0;
+        HIP_TRY(launch_meanflow_update(L.x, u, L.tl, i, sde ? -1 : i + 1, (i == L.steps - 1 && !renoise) ? L.out : L.x, L.total, L.s));
+        if (renoise) {
+            const float* e = nullptr;
+            if ((rc = L.draw(i, &e))) return rc;
+            HIP_TRY(launch_forward_process(L.x, e, 0.0, L.tl, i + 1, L.sched, L.x, L.total, L.s));
+        }
+    }
+    return FG_OK;
+}
+
 // The parameters one fg_dit_pack_group / fg_wan_pack_group call packs: names that start with `pre` and not with `exc` (if not empty),
 // the unit FSDP2 gathers at a time.
 struct ParamGroup {
@@ -836,54 +935,13 @@ int run_forward(fg_edm* h, const float* x_t, const double* t, int t_stride, cons
 int enqueue_sampler(fg_edm* h, const float* noise, const float* labels, const double* t_list, int steps, int type,
                     int loop, const float* eps, float* out, int B, Workspace& w, hipStream_t s) {
     const fg_edm_config& c = h->cfg;
-    const int sched = c.schedule;
     const int64_t total = (int64_t)B * c.img_channels * c.img_resolution * c.img_resolution;
-    HIP_TRY(launch_latents(noise, 0.0, w.tl, 0, w.x, total, s));  // latents = noise * sigma(t_0), noise_schedule.py:72-88
-    auto sde_noise = [&](int i, const float** e) -> int {
-        if (eps) {
-            *e = eps + (size_t)i * total;
-        } else {
-            HIP_TRY(launch_randn(w.eps, total, 0, (uint64_t)i, w.seed, s));
-            *e = w.eps;
-        }
-        return FG_OK;
-    };
-    if (loop == FG_LOOP_MEANFLOW) {
-        // MeanFlowModel._student_sample_loop (consistency_model/mean_flow.py:336-381): the network output is the
-        // average velocity u(x, t, r); 'sde' jumps to r = 0 and re-noises, 'ode' integrates t_cur -> t_next.
-        for (int i = 0; i < steps; ++i) {
-            const double* r = (type == FG_SAMPLE_SDE) ? w.tl + steps : w.tl + i + 1;  // t_list[steps] == 0
-            int rc = run_forward(h, w.x, w.tl + i, 0, r, 0, labels, w.x_pred, B, w, s);
-            if (rc) return rc;
-            const bool renoise = type == FG_SAMPLE_SDE && t_list[i + 1] > 0;
-            float* dst = (i == steps - 1 && !renoise) ? out : w.x;
-            HIP_TRY(launch_meanflow_update(w.x, w.x_pred, w.tl, i, type == FG_SAMPLE_SDE ? -1 : i + 1, dst, total, s));
-            if (renoise) {
-                const float* e = nullptr;
-                if ((rc = sde_noise(i, &e))) return rc;
-                HIP_TRY(launch_forward_process(w.x, e, 0.0, w.tl, i + 1, sched, w.x, total, s));
-            }
-        }
-        return FG_OK;
-    }
-    // FastGenModel._student_sample_loop (methods/model.py:315-372): x0 prediction, then re-noise to t_next
-    for (int i = 0; i < steps; ++i) {
-        float* pred = (i == steps - 1) ? out : w.x_pred;
-        int rc = run_forward(h, w.x, w.tl + i, 0, w.tl + steps, 0, labels, pred, B, w, s);
-        if (rc) return rc;
-        if (t_list[i + 1] > 0) {  // methods/model.py:356 — decided on the host, baked into the graph
-            const float* e = nullptr;
-            if (type == FG_SAMPLE_SDE) {
-                if ((rc = sde_noise(i, &e))) return rc;
-            } else {
-                HIP_TRY(launch_x0_to_eps(w.x, pred, 0.0, w.tl, i, sched, 1e-6, w.eps, total, s));
-                e = w.eps;
-            }
-            // t_list[-1] must be 0 (model.py:410), so the last step never re-noises
-            HIP_TRY(launch_forward_process(pred, e, 0.0, w.tl, i + 1, sched, w.x, total, s));
-        }
-    }
-    return FG_OK;
+    const StudentLoop L{noise, t_list, steps, type, c.schedule, total, w.x, w.eps, eps, w.tl, w.seed, out, s};
+    if (loop == FG_LOOP_MEANFLOW)  // r = 0 ('sde': t_list[steps]) or t_{i+1} ('ode')
+        return meanflow_loop(L, w.x_pred, [&](int i, float* u) {
+            return run_forward(h, w.x, w.tl + i, 0, w.tl + (type == FG_SAMPLE_SDE ? steps : i + 1), 0, labels, u, B, w, s);
+        });
+    return x0_loop(L, w.x_pred, [&](int i, float* pred) { return run_forward(h, w.x, w.tl + i, 0, w.tl + steps, 0, labels, pred, B, w, s); });
 }
 
 // Device-side state (packed-weight storage, stacked affine matrix, frequency table).  Deferred to the
@@ -1153,31 +1211,20 @@ int fg_sampler_run(fg_edm* h, const float* noise, const float* class_labels, con
                    int sample_type, int loop_kind, const float* eps, uint64_t seed, float* out, int batch, void* workspace,
                    size_t workspace_bytes, int use_graph, void* stream) {
     if (!h || !noise || !t_list || !out) return fail(FG_EINVAL, "null argument");
-    if (!h->packed) return fail(FG_ENOTREADY, "weights are not packed (call fg_edm_pack_weights)");
-    if (steps < 1 || steps > 64) return fail(FG_EINVAL, "steps must be in [1, 64]");
-    if (sample_type != FG_SAMPLE_SDE && sample_type != FG_SAMPLE_ODE) return fail(FG_EINVAL, "bad sample_type");
-    if (t_list[steps] != 0.0) return fail(FG_EINVAL, "t_list[-1] must be zero");  // methods/model.py:410
+    int rc = check_sampler_args(t_list, steps, sample_type, loop_kind, h->cfg.schedule);
+    if (rc) return rc;
     if (loop_kind != FG_LOOP_X0 && loop_kind != FG_LOOP_MEANFLOW) return fail(FG_EINVAL, "bad loop_kind");
     if ((loop_kind == FG_LOOP_MEANFLOW) != (h->cfg.r_timestep != 0))
         return fail(FG_EINVAL, "FG_LOOP_MEANFLOW needs an r_timestep network and FG_LOOP_X0 a network without one");
-    const double t_lo = h->cfg.schedule == FG_SCHEDULE_RF ? 0.0 : 0.002, t_hi = h->cfg.schedule == FG_SCHEDULE_RF ? 0.999 : 80.0;
-    for (int i = 0; i < steps; ++i)
-        if (!(t_list[i] >= t_lo * (1 - 1e-12) && t_list[i] <= t_hi * (1 + 1e-12)))  // is_t_valid, noise_schedule.py:409-423
-            return fail(FG_EINVAL, "t_list[%d] = %g outside [%g, %g]", i, t_list[i], t_lo, t_hi);
     Workspace w;
-    int rc = setup_ws(plan_workspace, h, batch, workspace, workspace_bytes, w);
-    if (rc) return rc;
-    hipStream_t s = (hipStream_t)stream;
-    SamplerCache& st = h->sampler;
-    if ((rc = st.ring.upload(t_list, steps + 1, seed, w.tl, w.seed, s))) return rc;
-    auto enqueue = [&](hipStream_t q) {
-        return enqueue_sampler(h, noise, class_labels, t_list, steps, sample_type, loop_kind, eps, out, batch, w, q);
-    };
-    if (!use_graph || h->prof_on) return enqueue(s);
-    const std::vector<int64_t> key = {batch, steps, sample_type, loop_kind, zero_mask(t_list, steps), (int64_t)(uintptr_t)noise,
-                                      (int64_t)(uintptr_t)class_labels, (int64_t)(uintptr_t)eps, (int64_t)(uintptr_t)out,
-                                      (int64_t)(uintptr_t)workspace, sample_type == FG_SAMPLE_SDE && !eps};
-    return graph_run(st.graph, key, st.cap, s, enqueue);
+    if ((rc = setup_ws(plan_workspace, h, batch, workspace, workspace_bytes, w))) return rc;
+    if (!h->packed) return fail(FG_ENOTREADY, "weights are not packed (call fg_edm_pack_weights)");
+    return sampler_launch(h->sampler, batch, t_list, steps, sample_type, loop_kind, seed, w.tl, w.seed, use_graph && !h->prof_on,
+                          {(int64_t)(uintptr_t)noise, (int64_t)(uintptr_t)class_labels, (int64_t)(uintptr_t)eps, (int64_t)(uintptr_t)out,
+                           (int64_t)(uintptr_t)workspace, sample_type == FG_SAMPLE_SDE && !eps},
+                          (hipStream_t)stream, [&](hipStream_t q) {
+                              return enqueue_sampler(h, noise, class_labels, t_list, steps, sample_type, loop_kind, eps, out, batch, w, q);
+                          });
 }
 
 int fg_edm_profile_begin(fg_edm* h) {

@@ -1,7 +1,7 @@
 // EDM2 U-Net engine (EDM2Precond, reference fastgen/networks/EDM2/network.py): module layout and state-dict order, weight normalisation
 // and packing with the magnitude-preserving constants folded in, workspace plan, the forward schedule, the per-block entry points and
-// the x0 sampler loop.  Textually included by engine.hip inside its `extern "C"` region (the handle is a HandleBase; setup_ws and the
-// SamplerCache are engine.hip's).  Convolutions and attention are adm.hip's kernels; the rest is edm2.hip.  Forward only, split-bf16 and bf16 convolutions, fp32 activations.
+// the x0 sampler loop.  Textually included by engine.hip inside its `extern "C"` region (the handle is a HandleBase; setup_ws, the
+// SamplerCache and the student loop are engine.hip's).  Convolutions and attention are adm.hip's kernels; the rest is edm2.hip.  Forward only, split-bf16 and bf16 convolutions, fp32 activations.
 }  // extern "C" (reopened below)
 
 namespace {
@@ -370,35 +370,6 @@ int e2_forward(fg_edm2* h, const float* x_t, const double* t, int t_stride, cons
     return FG_OK;
 }
 
-// FastGenModel._student_sample_loop (methods/model.py:315-372) around e2_forward, as enqueue_sampler's x0 branch
-int e2_enqueue_sampler(fg_edm2* h, const float* noise, const float* labels, const double* t_list, int steps, int type, const float* eps,
-                       float* out, int B, E2Ws& w, hipStream_t s) {
-    const fg_edm2_config& c = h->cfg;
-    const int64_t total = (int64_t)B * c.img_channels * c.img_resolution * c.img_resolution;
-    HIP_TRY(launch_latents(noise, 0.0, w.tl, 0, w.x, total, s));
-    for (int i = 0; i < steps; ++i) {
-        float* pred = (i == steps - 1) ? out : w.x_pred;
-        int rc = e2_forward(h, w.x, w.tl + i, 0, labels, pred, B, w, s);
-        if (rc) return rc;
-        if (t_list[i + 1] > 0) {
-            const float* e = nullptr;
-            if (type == FG_SAMPLE_SDE) {
-                if (eps) {
-                    e = eps + (size_t)i * total;
-                } else {
-                    HIP_TRY(launch_randn(w.eps, total, 0, (uint64_t)i, w.seed, s));
-                    e = w.eps;
-                }
-            } else {
-                HIP_TRY(launch_x0_to_eps(w.x, pred, 0.0, w.tl, i, FG_SCHEDULE_EDM, 1e-6, w.eps, total, s));
-                e = w.eps;
-            }
-            HIP_TRY(launch_forward_process(pred, e, 0.0, w.tl, i + 1, FG_SCHEDULE_EDM, w.x, total, s));
-        }
-    }
-    return FG_OK;
-}
-
 const E2Block* e2_block_at(const fg_edm2* h, int index) {
     const int ne = (int)h->enc.size();
     if (index < 0 || index >= ne + (int)h->dec.size()) return nullptr;
@@ -491,21 +462,20 @@ int fg_edm2_sampler_run(fg_edm2* h, const float* noise, const float* class_label
                         int loop_kind, const float* eps, uint64_t seed, float* out, int batch, void* workspace, size_t workspace_bytes,
                         int use_graph, void* stream) {
     if (!h || !noise || !t_list || !out) return fail(FG_EINVAL, "null argument");
-    if (!h->packed) return fail(FG_ENOTREADY, "weights are not packed (call fg_edm2_pack_weights)");
-    if (sample_type != FG_SAMPLE_SDE && sample_type != FG_SAMPLE_ODE) return fail(FG_EINVAL, "bad sample_type");
-    if (loop_kind != FG_LOOP_X0) return fail(FG_EINVAL, "EDM2 runs the FG_LOOP_X0 loop only");
-    int rc = check_t_list(t_list, steps, FG_SCHEDULE_EDM);
+    int rc = check_sampler_args(t_list, steps, sample_type, loop_kind, FG_SCHEDULE_EDM);
     if (rc) return rc;
+    if (loop_kind != FG_LOOP_X0) return fail(FG_EINVAL, "EDM2 runs the FG_LOOP_X0 loop only");
     E2Ws w;
     if ((rc = setup_ws(e2_plan, h, batch, workspace, workspace_bytes, w))) return rc;
-    hipStream_t s = (hipStream_t)stream;
-    SamplerCache& st = h->sampler;
-    if ((rc = st.ring.upload(t_list, steps + 1, seed, w.tl, w.seed, s))) return rc;
-    auto enqueue = [&](hipStream_t q) { return e2_enqueue_sampler(h, noise, class_labels, t_list, steps, sample_type, eps, out, batch, w, q); };
-    if (!use_graph) return enqueue(s);
-    const std::vector<int64_t> key = {batch, steps, sample_type, zero_mask(t_list, steps), (int64_t)(uintptr_t)noise,
-                                      (int64_t)(uintptr_t)class_labels, (int64_t)(uintptr_t)eps, (int64_t)(uintptr_t)out, (int64_t)(uintptr_t)workspace};
-    return graph_run(st.graph, key, st.cap, s, enqueue);
+    if (!h->packed) return fail(FG_ENOTREADY, "weights are not packed (call fg_edm2_pack_weights)");
+    const int64_t total = (int64_t)batch * h->cfg.img_channels * h->cfg.img_resolution * h->cfg.img_resolution;
+    return sampler_launch(h->sampler, batch, t_list, steps, sample_type, loop_kind, seed, w.tl, w.seed, use_graph,
+                          {(int64_t)(uintptr_t)noise, (int64_t)(uintptr_t)class_labels, (int64_t)(uintptr_t)eps, (int64_t)(uintptr_t)out,
+                           (int64_t)(uintptr_t)workspace},
+                          (hipStream_t)stream, [&](hipStream_t q) {
+                              const StudentLoop L{noise, t_list, steps, sample_type, FG_SCHEDULE_EDM, total, w.x, w.eps, eps, w.tl, w.seed, out, q};
+                              return x0_loop(L, w.x_pred, [&](int i, float* pred) { return e2_forward(h, w.x, w.tl + i, 0, class_labels, pred, batch, w, q); });
+                          });
 }
 
 int fg_edm2_num_blocks(const fg_edm2* h) { return h ? (int)(h->enc.size() + h->dec.size()) : 0; }

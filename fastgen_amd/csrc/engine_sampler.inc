@@ -5,15 +5,17 @@
 //   fg_wan_sampler_run   CausVidModel._student_sample_loop (distribution_matching/causvid.py:87-185), the segment loop of
 //                        generator_fn_extrapolation (:188-397) and SelfForcingModel.rollout_with_gradient's no-grad form
 //                        (self_forcing.py:92-241) around fg_wan_forward: per chunk N x {x0 prediction; re-noise}, then the cache-fill call
-// Textually included by engine.hip behind engine_dit.inc / engine_wan.inc; the scalar ring and graph cache are engine.hip's.  The reference's
-// host syncs (`t_next > 0` on a device tensor, `assert is_t_valid(t)` in every schedule call, `rescale_t`) are hoisted to host scalars
-// checked once per call; timesteps and the RNG seed live in device memory, so a captured graph is replayed with new values.
+// Textually included by engine.hip behind engine_dit.inc / engine_wan.inc; the argument check, scalar ring, graph cache and the
+// student loops (x0_loop, meanflow_loop, renoise_x0) are engine.hip's.  The reference's host syncs (`t_next > 0` on a device tensor,
+// `assert is_t_valid(t)` in every schedule call, `rescale_t`) are hoisted to host scalars checked once per call; timesteps and the RNG
+// seed live in device memory, so a captured graph is replayed with new values.
 }  // extern "C" (reopened below)
 
 namespace {
 
 // ---- DiT ----------------------------------------------------------------------------------------------------------------------
 struct DitLoopWs {
+    bool guided = false;  // the plan's input: room for the doubled batch of a guided FG_LOOP_EULER call
     DitWs net;
     float *x, *v, *pred, *eps, *te, *re;
     double* tl;
@@ -21,8 +23,8 @@ struct DitLoopWs {
     int64_t* cls2;
 };
 
-size_t dit_sampler_plan(const fg_dit* h, int B, int guided, Arena& A, DitLoopWs& w) {
-    const int Be = guided ? 2 * B : B;
+size_t dit_sampler_plan(const fg_dit* h, int B, Arena& A, DitLoopWs& w) {
+    const int Be = w.guided ? 2 * B : B;
     dit_plan(h, Be, A, w.net);
     const size_t per = (size_t)h->cfg.in_channels * h->cfg.input_size * h->cfg.input_size;
     w.x = A.get<float>(per * Be);
@@ -41,60 +43,37 @@ int dit_enqueue_sampler(fg_dit* h, const fg_dit_sampler_config& sc, const float*
                         int steps, int type, int loop, const float* eps, float* out, int B, DitLoopWs& w, hipStream_t s) {
     const fg_dit_config& c = h->cfg;
     const int64_t total = (int64_t)B * c.in_channels * c.input_size * c.input_size;
-    const bool guided = loop == FG_LOOP_EULER && neg != nullptr;
-    const int Be = guided ? 2 * B : B;
+    const int Be = w.guided ? 2 * B : B;
     const float sign = (sc.use_sit_convention && sc.net_pred_flow) ? -1.0f : 1.0f;  // DiT/network.py:555-558
+    const int64_t* ids = w.guided ? w.cls2 : cls;
+    // the network on w.x at t_i into v; ri: MeanFlow's r (-1: 0, else t_list[ri]), -2: none
+    auto net = [&](int i, int ri, float* v) -> int {
+        HIP_TRY(launch_embed_times(w.tl, i, 0.0, ri, 0.0, sc.t_scale, sc.use_sit_convention, sc.time_cond_diff, 0, w.te, w.re, Be, s));
+        return dit_forward(h, w.x, w.te, ri == -2 ? nullptr : w.re, ids, v, nullptr, Be, w.net, s);
+    };
+    const StudentLoop L{noise, t_list, steps, type, sc.schedule, total, w.x, w.eps, eps, w.tl, w.seed, out, s};
+    if (loop == FG_LOOP_X0)  // the network's flow prediction -> x0 (convert_model_output, :560-566)
+        return x0_loop(L, w.pred, [&](int i, float* pred) -> int {
+            const int rc = net(i, -2, w.v);
+            if (rc) return rc;
+            if (sc.net_pred_flow) HIP_TRY(launch_flow_to_x0(w.x, w.v, w.tl, i, sign, pred, total, s));
+            else HIP_TRY(hipMemcpyAsync(pred, w.v, sizeof(float) * total, hipMemcpyDeviceToDevice, s));
+            return FG_OK;
+        });
+    if (loop == FG_LOOP_MEANFLOW)  // r: 0 for the 'sde' jump to the data end, the next timestep for 'ode' (mean_flow.py:362-368)
+        return meanflow_loop(L, w.v, [&](int i, float* u) { return net(i, type == FG_SAMPLE_SDE ? -1 : i + 1, u); });
+    // FG_LOOP_EULER
     HIP_TRY(launch_latents(noise, 0.0, w.tl, 0, w.x, total, s));  // latents = noise * sigma(t_0), noise_schedule.py:72-88
-    const int64_t* ids = cls;
-    if (guided) {  // the doubled batch of the guided call: [x | x], [neg_condition | condition] (:636-640)
+    if (w.guided) {  // the doubled batch of the guided call: [x | x], [neg_condition | condition] (:636-640)
         HIP_TRY(hipMemcpyAsync(w.x + total, w.x, sizeof(float) * total, hipMemcpyDeviceToDevice, s));
         HIP_TRY(hipMemcpyAsync(w.cls2, neg, sizeof(int64_t) * B, hipMemcpyDeviceToDevice, s));
         HIP_TRY(hipMemcpyAsync(w.cls2 + B, cls, sizeof(int64_t) * B, hipMemcpyDeviceToDevice, s));
-        ids = w.cls2;
     }
-    auto sde_noise = [&](int i, const float** e) -> int {
-        if (eps) {
-            *e = eps + (size_t)i * total;
-        } else {
-            HIP_TRY(launch_randn(w.eps, total, 0, (uint64_t)i, w.seed, s));
-            *e = w.eps;
-        }
-        return FG_OK;
-    };
-    int rc;
     for (int i = 0; i < steps; ++i) {
-        // r: MeanFlow's target time - 0 for the 'sde' jump to the data end, the next timestep for 'ode' (mean_flow.py:362-368)
-        const int ri = loop != FG_LOOP_MEANFLOW ? -2 : (type == FG_SAMPLE_SDE ? -1 : i + 1);
-        HIP_TRY(launch_embed_times(w.tl, i, 0.0, ri, 0.0, sc.t_scale, sc.use_sit_convention, sc.time_cond_diff, 0, w.te, w.re, Be, s));
-        if ((rc = dit_forward(h, w.x, w.te, ri == -2 ? nullptr : w.re, ids, w.v, nullptr, Be, w.net, s))) return rc;
-        if (loop == FG_LOOP_EULER) {
-            float* dst = i == steps - 1 ? out : w.x;
-            HIP_TRY(launch_euler_step(w.x, w.v, w.tl, i, (float)sc.guidance_scale, guided, sign, dst, guided && i + 1 < steps ? w.x + total : nullptr, total, s));
-        } else if (loop == FG_LOOP_MEANFLOW) {
-            const bool renoise = type == FG_SAMPLE_SDE && t_list[i + 1] > 0;
-            float* dst = (i == steps - 1 && !renoise) ? out : w.x;
-            HIP_TRY(launch_meanflow_update(w.x, w.v, w.tl, i, type == FG_SAMPLE_SDE ? -1 : i + 1, dst, total, s));
-            if (renoise) {
-                const float* e = nullptr;
-                if ((rc = sde_noise(i, &e))) return rc;
-                HIP_TRY(launch_forward_process(w.x, e, 0.0, w.tl, i + 1, sc.schedule, w.x, total, s));
-            }
-        } else {
-            // x0 loop: the network's flow prediction -> x0 (convert_model_output, :560-566), then re-noise to t_next unless it is 0
-            float* pred = i == steps - 1 ? out : w.pred;
-            if (sc.net_pred_flow) HIP_TRY(launch_flow_to_x0(w.x, w.v, w.tl, i, sign, pred, total, s));
-            else HIP_TRY(hipMemcpyAsync(pred, w.v, sizeof(float) * total, hipMemcpyDeviceToDevice, s));
-            if (t_list[i + 1] > 0) {  // methods/model.py:356 - decided on the host, baked into the graph
-                const float* e = nullptr;
-                if (type == FG_SAMPLE_SDE) {
-                    if ((rc = sde_noise(i, &e))) return rc;
-                } else {
-                    HIP_TRY(launch_x0_to_eps(w.x, pred, 0.0, w.tl, i, sc.schedule, 1e-6, w.eps, total, s));
-                    e = w.eps;
-                }
-                HIP_TRY(launch_forward_process(pred, e, 0.0, w.tl, i + 1, sc.schedule, w.x, total, s));
-            }
-        }
+        const int rc = net(i, -2, w.v);
+        if (rc) return rc;
+        HIP_TRY(launch_euler_step(w.x, w.v, w.tl, i, (float)sc.guidance_scale, w.guided, sign, i == steps - 1 ? out : w.x,
+                                  w.guided && i + 1 < steps ? w.x + total : nullptr, total, s));
     }
     return FG_OK;
 }
@@ -108,49 +87,40 @@ size_t fg_dit_sampler_workspace_bytes(const fg_dit* h, int batch, int guided) {
     Arena A;
     A.dry = true;
     DitLoopWs w;
-    return dit_sampler_plan(h, batch, guided != 0, A, w);
+    w.guided = guided != 0;
+    return dit_sampler_plan(h, batch, A, w);
 }
 
 int fg_dit_sampler_run(fg_dit* h, const fg_dit_sampler_config* sc, const float* noise, const int64_t* class_ids, const int64_t* neg_class_ids,
                        const double* t_list, int steps, int sample_type, int loop_kind, const float* eps, uint64_t seed, float* out, int batch,
                        void* workspace, size_t workspace_bytes, int use_graph, void* stream) {
     if (!h || !sc || !noise || !class_ids || !t_list || !out) return fail(FG_EINVAL, "null argument");
-    if (!h->packed) return fail(FG_ENOTREADY, "weights are not packed (call fg_dit_pack_weights)");
-    if (sample_type != FG_SAMPLE_SDE && sample_type != FG_SAMPLE_ODE) return fail(FG_EINVAL, "bad sample_type");
-    if (loop_kind != FG_LOOP_X0 && loop_kind != FG_LOOP_MEANFLOW && loop_kind != FG_LOOP_EULER) return fail(FG_EINVAL, "bad loop_kind");
+    int rc = check_sampler_args(t_list, steps, sample_type, loop_kind, sc->schedule);
+    if (rc) return rc;
     if (loop_kind == FG_LOOP_MEANFLOW && (!h->cfg.r_timestep || !sc->net_pred_flow))
         return fail(FG_EINVAL, "FG_LOOP_MEANFLOW needs a flow-predicting r_timestep network");
     if (loop_kind == FG_LOOP_MEANFLOW && sc->use_sit_convention) return fail(FG_EINVAL, "FG_LOOP_MEANFLOW with use_sit_convention is not implemented");
     if (loop_kind == FG_LOOP_EULER && !sc->net_pred_flow) return fail(FG_EINVAL, "FG_LOOP_EULER needs a flow-predicting network");
     if (neg_class_ids && loop_kind != FG_LOOP_EULER) return fail(FG_EINVAL, "neg_class_ids belong to FG_LOOP_EULER (classifier-free guidance)");
     if (!(sc->t_scale > 0.0)) return fail(FG_EINVAL, "t_scale must be positive");
-    int rc = check_t_list(t_list, steps, sc->schedule);
-    if (rc) return rc;
-    if (batch <= 0 || !workspace || (((uintptr_t)workspace) & 255)) return fail(FG_EINVAL, "bad batch / workspace");
+    DitLoopWs w;
+    w.guided = neg_class_ids != nullptr;
+    if ((rc = setup_ws(dit_sampler_plan, h, batch, workspace, workspace_bytes, w))) return rc;
+    if (!h->packed) return fail(FG_ENOTREADY, "weights are not packed (call fg_dit_pack_weights)");
     if (h->take_error())
         return fail(FG_EINVAL, "an earlier call on this handle met a class index outside the %d rows of y_embedder.class_embeddings (its output is NaN)",
                     h->cfg.embedding_rows);
-    const bool guided = loop_kind == FG_LOOP_EULER && neg_class_ids;
-    Arena A;
-    A.base = (char*)workspace;
-    DitLoopWs w;
-    const size_t need = dit_sampler_plan(h, batch, guided, A, w);
-    if (need > workspace_bytes) return fail(FG_ENOMEM, "workspace too small: need %zu bytes for batch %d, got %zu", need, batch, workspace_bytes);
-    SamplerCache& st = h->sampler;
-    hipStream_t s = (hipStream_t)stream;
-    if ((rc = st.ring.upload(t_list, steps + 1, seed, w.tl, w.seed, s))) return rc;
-    auto enqueue = [&](hipStream_t q) {
-        return dit_enqueue_sampler(h, *sc, noise, class_ids, neg_class_ids, t_list, steps, sample_type, loop_kind, eps, out, batch, w, q);
-    };
-    if (!use_graph) return enqueue(s);
     int64_t tsb, gsb;
     memcpy(&tsb, &sc->t_scale, 8);
     memcpy(&gsb, &sc->guidance_scale, 8);
-    const std::vector<int64_t> key = {batch, steps, sample_type, loop_kind, zero_mask(t_list, steps), (int64_t)(uintptr_t)noise,
-                                      (int64_t)(uintptr_t)class_ids, (int64_t)(uintptr_t)neg_class_ids, (int64_t)(uintptr_t)eps, (int64_t)(uintptr_t)out,
-                                      (int64_t)(uintptr_t)workspace, tsb, gsb, sc->use_sit_convention, sc->time_cond_diff, sc->net_pred_flow,
-                                      sc->schedule, (int64_t)h->cmode};
-    return graph_run(st.graph, key, st.cap, s, enqueue);
+    return sampler_launch(h->sampler, batch, t_list, steps, sample_type, loop_kind, seed, w.tl, w.seed, use_graph,
+                          {(int64_t)(uintptr_t)noise, (int64_t)(uintptr_t)class_ids, (int64_t)(uintptr_t)neg_class_ids, (int64_t)(uintptr_t)eps,
+                           (int64_t)(uintptr_t)out, (int64_t)(uintptr_t)workspace, tsb, gsb, sc->use_sit_convention, sc->time_cond_diff,
+                           sc->net_pred_flow, sc->schedule, (int64_t)h->cmode},
+                          (hipStream_t)stream, [&](hipStream_t q) {
+                              return dit_enqueue_sampler(h, *sc, noise, class_ids, neg_class_ids, t_list, steps, sample_type, loop_kind, eps, out,
+                                                         batch, w, q);
+                          });
 }
 
 }  // extern "C"
@@ -181,7 +151,7 @@ size_t wan_sampler_plan(const fg_wan* h, int B, int fmax, int H, int W, Arena& A
 }
 
 // frames per chunk of the student loops: `chunk_size` each, the remainder of num_frames joins the FIRST chunk (causvid.py:120-128)
-void wan_chunks(int frames, int chunk, int prefill, std::vector<std::pair<int, int>>& out) {
+void wan_chunks(int frames, int chunk, std::vector<std::pair<int, int>>& out) {
     out.clear();
     const int n = frames / chunk, rem = frames % chunk;
     if (n == 0) {
@@ -192,7 +162,6 @@ void wan_chunks(int frames, int chunk, int prefill, std::vector<std::pair<int, i
         const int a = i == 0 ? 0 : chunk * i + rem, b = chunk * (i + 1) + rem;
         out.push_back({a, b});
     }
-    (void)prefill;
 }
 
 }  // namespace
@@ -212,15 +181,12 @@ int fg_wan_sampler_run(fg_wan* h, const fg_wan_sampler_config* sc, float* x, con
                        const float* eps, uint64_t seed, int batch, int frames, int height, int width, void* workspace, size_t workspace_bytes,
                        int use_graph, void* stream) {
     if (!h || !sc || !x || !t_list) return fail(FG_EINVAL, "null argument");
-    if (!h->packed) return fail(FG_ENOTREADY, "weights are not packed (call fg_wan_pack_weights)");
-    if (sample_type != FG_SAMPLE_SDE && sample_type != FG_SAMPLE_ODE) return fail(FG_EINVAL, "bad sample_type");
-    int rc = check_t_list(t_list, steps, sc->schedule);
+    int rc = check_sampler_args(t_list, steps, sample_type, FG_LOOP_X0, sc->schedule);
     if (rc) return rc;
     if (!(sc->t_scale > 0.0)) return fail(FG_EINVAL, "t_scale must be positive");
     if (batch <= 0 || frames <= 0 || frames > h->cfg.total_num_frames || height <= 0 || width <= 0 || (height & 1) || (width & 1) || !workspace ||
         (((uintptr_t)workspace) & 255))
         return fail(FG_EINVAL, "bad batch / frames (<= total_num_frames = %d) / size / workspace", h->cfg.total_num_frames);
-    if (h->text_B != batch) return fail(FG_ENOTREADY, "no text condition for batch %d (call fg_wan_set_text)", batch);
     const int chunk = h->cfg.chunk_size, prefill = sc->prefill_frames;
     if (prefill < 0 || prefill >= frames || (prefill > 0 && ((prefill % chunk) || (frames % chunk))))
         return fail(FG_EINVAL, "prefill_frames must be in [0, frames) and, like frames then, a multiple of chunk_size = %d", chunk);
@@ -228,7 +194,7 @@ int fg_wan_sampler_run(fg_wan* h, const fg_wan_sampler_config* sc, float* x, con
     if (sc->context_noise < 0.0 || (sc->context_noise > 0.0 && (double)cn32 > (sc->schedule == FG_SCHEDULE_RF ? 0.999 : 80.0)))
         return fail(FG_EINVAL, "context_noise outside the schedule's range");
     std::vector<std::pair<int, int>> chunks;
-    wan_chunks(frames, chunk, prefill, chunks);
+    wan_chunks(frames, chunk, chunks);
     if (exit_steps)
         for (size_t ci = 0; ci < chunks.size(); ++ci)
             if (exit_steps[ci] < 0 || exit_steps[ci] >= steps) return fail(FG_EINVAL, "exit_steps[%zu] = %d outside [0, %d)", ci, exit_steps[ci], steps);
@@ -238,6 +204,8 @@ int fg_wan_sampler_run(fg_wan* h, const fg_wan_sampler_config* sc, float* x, con
     WanLoopWs w;
     const size_t need = wan_sampler_plan(h, batch, fmax, height, width, A, w);
     if (need > workspace_bytes) return fail(FG_ENOMEM, "workspace too small: need %zu bytes, got %zu", need, workspace_bytes);
+    if (!h->packed) return fail(FG_ENOTREADY, "weights are not packed (call fg_wan_pack_weights)");
+    if (h->text_B != batch) return fail(FG_ENOTREADY, "no text condition for batch %d (call fg_wan_set_text)", batch);
     hipStream_t s = (hipStream_t)stream;
     // `net.clear_caches()` of the loop's first line (causvid.py:113): nothing is stored any more.  (No memset here: this loop writes every
     // cache row before any call reads it; the clear at the end of the loop leaves the buffers zeroed for whoever calls next.  The text
@@ -277,14 +245,7 @@ int fg_wan_sampler_run(fg_wan* h, const fg_wan_sampler_config* sc, float* x, con
                     if (sc->net_pred_flow) HIP_TRY(launch_flow_to_x0(cur, w.v, w.tl, i, 1.0f, nxt, total, q));  // fwd_pred_type = "x0"
                     else HIP_TRY(hipMemcpyAsync(nxt, w.v, sizeof(float) * total, hipMemcpyDeviceToDevice, q));
                     if (i < last && t_list[i + 1] > 0) {  // causvid.py:150-163; an exit step's prediction is the chunk's output as it is
-                        const float* e = nullptr;
-                        if (sample_type == FG_SAMPLE_SDE) {
-                            if ((r = draw(i, &e))) return r;
-                        } else {
-                            HIP_TRY(launch_x0_to_eps(cur, nxt, 0.0, w.tl, i, sc->schedule, 1e-6, w.eps, total, q));
-                            e = w.eps;
-                        }
-                        HIP_TRY(launch_forward_process(nxt, e, 0.0, w.tl, i + 1, sc->schedule, nxt, total, q));
+                        if ((r = renoise_x0(i, sample_type, sc->schedule, cur, nxt, nxt, w.eps, w.tl, total, q, draw))) return r;
                     }
                     std::swap(cur, nxt);
                 }

@@ -25,7 +25,7 @@ import torch.nn as nn
 from fastgen_amd import _lib
 from fastgen_amd.networks import _weights
 from fastgen_amd.networks.EDM import network as _edm
-from fastgen_amd.networks.network import FastGenNetwork
+from fastgen_amd.networks.network import FastGenNetwork, _fused_sample_args
 from fastgen_amd.networks.noise_schedule import NET_PRED_TYPES
 
 
@@ -293,25 +293,12 @@ class DiT(FastGenNetwork):
         if not self.supports_fused_loop(loop):
             raise NotImplementedError(f"the fused sampler has no loop {loop!r} for net_pred_type={self.net_pred_type!r}, "
                                       f"r_timestep={self.r_timestep}, schedule_type={self.schedule_type!r}")
-        if noise.device.type != "cuda":
-            raise RuntimeError("fastgen_amd runs on a HIP GPU only (no CPU path); got a tensor on " + str(noise.device))
-        if sample_type not in ("sde", "ode"):
-            raise NotImplementedError(f"student_sample_type must be one of 'sde', 'ode' but got {sample_type}")
-        B, dev = noise.shape[0], noise.device
+        n32, steps, tl_arr, eps, seed = _fused_sample_args(noise, t_list, sample_type, eps, seed)
         if tuple(noise.shape[1:]) != (self.in_channels, self.input_size, self.input_size):
             raise ValueError(f"noise must be [B,{self.in_channels},{self.input_size},{self.input_size}], got {tuple(noise.shape)}")
-        tl = [float(v) for v in (t_list.tolist() if isinstance(t_list, torch.Tensor) else t_list)]
-        steps = len(tl) - 1
-        assert tl[-1] == 0, "t_list[-1] must be zero"
-        n32 = noise if (noise.dtype == torch.float32 and noise.is_contiguous()) else noise.to(torch.float32).contiguous()
+        B, dev = noise.shape[0], noise.device
         cls = self._class_ids(condition, B, dev)
         neg = self._class_ids(neg_condition, B, dev) if (loop == "euler" and neg_condition is not None) else None
-        if eps is not None:
-            eps = eps.to(device=dev, dtype=torch.float32).contiguous()
-            if eps.numel() != max(steps - 1, 0) * n32.numel():
-                raise ValueError(f"eps must hold steps-1 = {steps - 1} noise tensors shaped like `noise`")
-        if seed is None:
-            seed = int(torch.randint(0, 2**62, (1,)).item())  # host RNG: follows torch.manual_seed / set_random_seed
         sc = _lib.fg_dit_sampler_config()
         rf = self.schedule_type != "edm"
         sc.t_scale = float(self.noise_scheduler.num_steps) if (self.scale_t and rf) else 1.0  # rescale_t (noise_schedule.py:140-148)
@@ -329,9 +316,8 @@ class DiT(FastGenNetwork):
         self._keep = (n32, cls, neg, eps, out)  # graph replays read these buffers; keep them alive
         p = lambda a: ctypes.c_void_p(a.data_ptr() if a is not None and a.numel() else None)  # noqa: E731
         _lib.check(L.fg_dit_sampler_run(
-            h, ctypes.byref(sc), p(n32), p(cls), p(neg), (ctypes.c_double * (steps + 1))(*tl), steps,
-            _lib.FG_SAMPLE_SDE if sample_type == "sde" else _lib.FG_SAMPLE_ODE,
-            {"x0": _lib.FG_LOOP_X0, "meanflow": _lib.FG_LOOP_MEANFLOW, "euler": _lib.FG_LOOP_EULER}[loop], p(eps), ctypes.c_uint64(seed), p(out), B,
+            h, ctypes.byref(sc), p(n32), p(cls), p(neg), tl_arr, steps, _lib.SAMPLE_TYPES[sample_type], _lib.LOOP_KINDS[loop], p(eps),
+            ctypes.c_uint64(seed), p(out), B,
             ctypes.c_void_p(ws.data_ptr()), ws.numel(), 1 if use_graph else 0, ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
         return out.to(noise.dtype)
 

@@ -27,8 +27,8 @@ import torch
 import torch.nn as nn
 
 from fastgen_amd import _lib
-from fastgen_amd.networks.network import FastGenNetwork
-from fastgen_amd.networks.noise_schedule import NET_PRED_TYPES, expand_like
+from fastgen_amd.networks.network import FastGenNetwork, _edm_euler_sample, _fused_sample_args
+from fastgen_amd.networks.noise_schedule import NET_PRED_TYPES
 
 DEFAULT_FP32_MODE = "bf16x3"  # as fastgen_amd.networks.EDM.network
 
@@ -341,31 +341,17 @@ class EDM2Precond(FastGenNetwork):
         loop = loop or self.fused_loop()
         if loop is None or loop != self.fused_loop():
             raise NotImplementedError(f"the fused sampler has no loop {loop!r} for net_pred_type={self.net_pred_type!r}")
-        if noise.device.type != "cuda":
-            raise RuntimeError("fastgen_amd runs on a HIP GPU only (no CPU path); got a tensor on " + str(noise.device))
-        if sample_type not in ("sde", "ode"):
-            raise NotImplementedError(f"student_sample_type must be one of 'sde', 'ode' but got {sample_type}")
+        n32, steps, tl_arr, eps, seed = _fused_sample_args(noise, t_list, sample_type, eps, seed)
         B, dev = noise.shape[0], noise.device
-        tl = [float(v) for v in (t_list.tolist() if isinstance(t_list, torch.Tensor) else t_list)]
-        steps = len(tl) - 1
-        assert tl[-1] == 0, "t_list[-1] must be zero"
-        n32 = noise if (noise.dtype == torch.float32 and noise.is_contiguous()) else noise.to(torch.float32).contiguous()
         labels = self._labels(condition, B, dev)
-        if eps is not None:
-            eps = eps.to(device=dev, dtype=torch.float32).contiguous()
-            if eps.numel() != max(steps - 1, 0) * n32.numel():
-                raise ValueError(f"eps must hold steps-1 = {steps - 1} noise tensors shaped like `noise`")
-        if seed is None:
-            seed = int(torch.randint(0, 2**62, (1,)).item())
         if out is None:
             out = torch.empty_like(n32)
-        tl_arr = (ctypes.c_double * (steps + 1))(*tl)
         self._keep = (n32, labels, eps)  # graph replays read these buffers; keep them alive
         dt, h = self._engine(dev)
         ws = self._workspace(dt, h, B, dev)
         _lib.check(_lib.lib().fg_edm2_sampler_run(
             h, ctypes.c_void_p(n32.data_ptr()), ctypes.c_void_p(labels.data_ptr() if labels is not None else None), tl_arr, steps,
-            _lib.FG_SAMPLE_SDE if sample_type == "sde" else _lib.FG_SAMPLE_ODE, _lib.FG_LOOP_X0,
+            _lib.SAMPLE_TYPES[sample_type], _lib.LOOP_KINDS[loop],
             ctypes.c_void_p(eps.data_ptr() if eps is not None and eps.numel() else None), ctypes.c_uint64(seed),
             ctypes.c_void_p(out.data_ptr()), B, ctypes.c_void_p(ws.data_ptr()), ws.numel(), 1 if use_graph else 0, self._stream(dev)))
         return out
@@ -373,18 +359,4 @@ class EDM2Precond(FastGenNetwork):
     def sample(self, noise: torch.Tensor, condition: Optional[torch.Tensor] = None, neg_condition: Optional[torch.Tensor] = None,
                guidance_scale: Optional[float] = 5.0, num_steps: int = 50, **kwargs) -> torch.Tensor:
         """EDM2's deterministic Euler sampler with optional classifier-free guidance, one forward() per step."""
-        assert self.schedule_type == "edm", f"{self.schedule_type} is not supported"
-        sigmas = self.noise_scheduler.get_t_list(num_steps, device=noise.device)
-        x = self.noise_scheduler.latents(noise=noise, t_init=sigmas[0])
-        for sigma, sigma_next in zip(sigmas[:-1], sigmas[1:]):
-            t = sigma.expand(x.shape[0])
-            if guidance_scale is not None and guidance_scale > 1.0 and neg_condition is not None:
-                x0 = self(torch.cat([x, x], 0), torch.cat([t, t], 0), condition=torch.cat([neg_condition, condition], 0),
-                          fwd_pred_type="x0")
-                x0_uncond, x0_cond = x0.chunk(2)
-                x0 = x0_uncond + guidance_scale * (x0_cond - x0_uncond)
-            else:
-                x0 = self(x, t, condition=condition, fwd_pred_type="x0")
-            d = (x - x0) / expand_like(t, x)
-            x = x + (sigma_next - sigma).to(x.dtype) * d
-        return x
+        return _edm_euler_sample(self, noise, condition, neg_condition, guidance_scale, num_steps)

@@ -211,7 +211,7 @@ class CausalWan(FastGenNetwork):
         > 0), B, C, F, H, W].  The caches are empty afterwards, as after the reference's loop."""
         if x.device.type != "cuda":
             raise RuntimeError("fastgen_amd runs on a HIP GPU only (no CPU path); got a tensor on " + str(x.device))
-        if sample_type not in ("sde", "ode"):
+        if sample_type not in _lib.SAMPLE_TYPES:
             raise NotImplementedError(f"student_sample_type must be one of 'sde', 'ode' but got {sample_type}")
         if self.net_pred_type not in ("flow", "x0"):
             raise NotImplementedError(f"net_pred_type {self.net_pred_type!r} has no fused loop")
@@ -259,7 +259,7 @@ class CausalWan(FastGenNetwork):
         try:
             _lib.check(L.fg_wan_sampler_run(
                 self._h, ctypes.byref(sc), ctypes.c_void_p(x32.data_ptr()), (ctypes.c_double * (steps + 1))(*tl), steps,
-                _lib.FG_SAMPLE_SDE if sample_type == "sde" else _lib.FG_SAMPLE_ODE, ex,
+                _lib.SAMPLE_TYPES[sample_type], ex,
                 ctypes.c_void_p(eps.data_ptr() if eps is not None and eps.numel() else None), ctypes.c_uint64(seed), B, F, H, W,
                 ctypes.c_void_p(ws.data_ptr()), ws.numel(), 1 if use_graph else 0, self._stream(dev)))
         finally:

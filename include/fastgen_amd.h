@@ -150,7 +150,9 @@ FG_API int fg_edm_forward_features(fg_edm* h, const float* x_t, const double* t,
  *   FG_LOOP_MEANFLOW (mean_flow.py:336-381, flow-predicting r_timestep network):
  *     'sde': x -= t_i * forward(x, t_i, r=0); if t_{i+1} > 0: x = forward_process(x, eps_i, t_{i+1});
  *     'ode': x -= (t_i - t_{i+1}) * forward(x, t_i, r=t_{i+1});   return x.
- * t_list: HOST array of steps+1 doubles, t_list[steps] must be 0 (model.py:410).  sample_type FG_SAMPLE_*.
+ * t_list: HOST array of steps+1 doubles, steps in [1, 64], t_list[steps] must be 0 (model.py:410) and every other entry inside
+ * the schedule's [min_t, max_t] up to one fp32 ulp (is_t_valid, noise_schedule.py:409-423: float32 lists pass).  sample_type
+ * FG_SAMPLE_*.  These checks, shared by every *_sampler_run, come before the handle's state: FG_EINVAL before FG_ENOTREADY.
  * eps: device [steps-1][B,C,H,W] noise to inject in 'sde' mode, or NULL to draw it on device from
  * (seed, step) with Philox4x32-10.  use_graph != 0 replays a cached hipGraph of the whole loop. */
 FG_API int fg_sampler_run(fg_edm* h, const float* noise, const float* class_labels, const double* t_list, int steps,
@@ -567,8 +569,8 @@ FG_API int fg_edm2_forward(fg_edm2* h, const float* x_t, const double* t, const 
                            int batch, void* workspace, size_t workspace_bytes, void* stream);
 /* train() / eval(): sigma_shift applies in eval mode only (training != 0 disables it). */
 FG_API int fg_edm2_set_training(fg_edm2* h, int training);
-/* The FG_LOOP_X0 student loop of fg_sampler_run (same arguments and semantics, EDM schedule) around fg_edm2_forward; use_graph != 0
- * replays one cached hipGraph per (batch, steps, sample type, pointers) key. */
+/* The FG_LOOP_X0 student loop of fg_sampler_run (same arguments, checks and semantics, EDM schedule) around fg_edm2_forward;
+ * use_graph != 0 replays one cached hipGraph per (batch, steps, sample type, pointers) key. */
 FG_API int fg_edm2_sampler_run(fg_edm2* h, const float* noise, const float* class_labels, const double* t_list, int steps,
                                int sample_type, int loop_kind, const float* eps, uint64_t seed, float* out, int batch,
                                void* workspace, size_t workspace_bytes, int use_graph, void* stream);

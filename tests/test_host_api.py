@@ -480,3 +480,54 @@ def test_label_dropout_follows_reference_semantics():
     assert torch.equal(got, want) and 0 < int(got.sum()) < 8
     n.eval()
     assert torch.equal(n._labels(c, 8, torch.device("cpu")), c)
+
+
+def test_sampler_entry_points_share_their_argument_checks():
+    """fg_sampler_run, fg_edm2_sampler_run and fg_dit_sampler_run refuse a bad step count, a t_list that does not end in 0, a timestep
+    outside the schedule's range and an unknown sample_type / loop_kind with FG_EINVAL and the same message, before they look at the
+    (here unpacked) weights; a list rounded to fp32 (one fp32 ulp beyond the range, as is_t_valid allows) passes those checks on all
+    three and meets FG_ENOTREADY.  Dummy pointers: nothing is dereferenced or launched, so this runs without a GPU."""
+    import numpy as np
+
+    from fastgen_amd.networks.DiT.network import DiT
+    from fastgen_amd.networks.EDM2.network import EDM2Precond
+
+    L = _lib.lib()
+    buf = ctypes.create_string_buffer(1 << 12)
+    p = ctypes.c_void_p(ctypes.addressof(buf) + (-ctypes.addressof(buf)) % 256)  # 256-byte aligned, never dereferenced here
+    edm = EDMPrecond(**KW)
+    edm_mf = EDMPrecond(**KW_MF)
+    edm2 = EDM2Precond(img_resolution=16, img_channels=3, label_dim=0, model_channels=64, channel_mult=[1, 2], num_blocks=1,
+                       attn_resolutions=[8])
+    dit = DiT(hidden_size=384, depth=1, num_heads=6)
+    h_edm, h_mf, h_edm2, h_dit = (edm._make_engine(_lib.FG_DTYPE_BF16), edm_mf._make_engine(_lib.FG_DTYPE_BF16),
+                                  edm2._make_engine(_lib.FG_DTYPE_BF16X3), dit._make_engine(_lib.FG_DTYPE_F32))
+    sc = _lib.fg_dit_sampler_config(t_scale=1.0, guidance_scale=1.0, net_pred_flow=1, schedule=_lib.FG_SCHEDULE_EDM)
+    tail = (None, ctypes.c_uint64(1), p, 2, p, 1 << 40, 1, None)  # eps, seed, out, batch, workspace, bytes, use_graph, stream
+
+    def run(tl, steps=None, sample_type=_lib.FG_SAMPLE_SDE, loop=_lib.FG_LOOP_X0):
+        """{entry point: (return code, message)} of the three calls on the EDM schedule"""
+        steps = len(tl) - 1 if steps is None else steps
+        tl = (ctypes.c_double * len(tl))(*tl)
+        calls = {"fg_sampler_run": lambda: L.fg_sampler_run(h_edm, p, None, tl, steps, sample_type, loop, *tail),
+                 "fg_edm2_sampler_run": lambda: L.fg_edm2_sampler_run(h_edm2, p, None, tl, steps, sample_type, loop, *tail),
+                 "fg_dit_sampler_run": lambda: L.fg_dit_sampler_run(h_dit, ctypes.byref(sc), p, p, None, tl, steps, sample_type, loop, *tail)}
+        return {name: (call(), L.fg_last_error()) for name, call in calls.items()}
+
+    try:
+        below_min = float(np.nextafter(np.float32(0.002), np.float32(0)))  # fp32(0.002) one ulp down: 0.0019999998
+        ok = [80.0, below_min, 0.0]
+        bad = {"steps 0": run(ok, steps=0), "steps 65": run([1.0] * 65 + [0.0]), "t_list[-1] != 0": run([80.0, 1.0]),
+               "t_list[0] > max_t": run([80.01, 1.0, 0.0]), "t_list[1] < min_t": run([80.0, 0.0019999, 0.0]),
+               "sample_type": run(ok, sample_type=2), "loop_kind": run(ok, loop=7)}
+        for case, results in bad.items():
+            assert {rc for rc, _ in results.values()} == {1}, (case, results)
+            assert len({msg for _, msg in results.values()}) == 1, (case, results)
+        for name, (rc, msg) in run(ok).items():
+            assert rc == 2 and b"not packed" in msg, (name, rc, msg)
+        # the RF schedule of a MeanFlow EDMPrecond: fp32(0.999) > 0.999 is one fp32 ulp inside is_t_valid's slack
+        tl = (ctypes.c_double * 3)(float(np.float32(0.999)), float(np.float32(0.5)), 0.0)
+        rc = L.fg_sampler_run(h_mf, p, None, tl, 2, _lib.FG_SAMPLE_SDE, _lib.FG_LOOP_MEANFLOW, *tail)
+        assert rc == 2 and b"not packed" in L.fg_last_error(), L.fg_last_error()
+    finally:
+        L.fg_edm_destroy(h_edm), L.fg_edm_destroy(h_mf), L.fg_edm2_destroy(h_edm2), L.fg_dit_destroy(h_dit)
