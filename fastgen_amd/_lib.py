@@ -52,6 +52,10 @@ class fg_wan_config(ctypes.Structure):
                 ("total_num_frames", c_int), ("eps", c_float)]
 
 
+class fg_wan_block_taps(ctypes.Structure):
+    _fields_ = [("attn1", c_void_p), ("x_attn1", c_void_p), ("attn2", c_void_p), ("x_attn2", c_void_p), ("x_ffn", c_void_p)]
+
+
 class fg_dit_sampler_config(ctypes.Structure):
     _fields_ = [("t_scale", c_double), ("guidance_scale", c_double), ("use_sit_convention", c_int), ("time_cond_diff", c_int),
                 ("net_pred_flow", c_int), ("schedule", c_int)]
@@ -164,6 +168,8 @@ SIGNATURES = {
     "fg_wan_forward": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_size_t,
                                c_void_p]),
     "fg_wan_forward_block_causal": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p]),
+    "fg_wan_forward_features": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, POINTER(c_int),
+                                        POINTER(fg_wan_block_taps), c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "fg_disc_edm_num_params": (c_int, [c_int]),
     "fg_disc_edm_workspace_bytes": (c_size_t, [c_int, c_int]),
     "fg_disc_edm_run": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_size_t, c_void_p]),

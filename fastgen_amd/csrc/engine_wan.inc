@@ -354,8 +354,17 @@ int wan_ensure_caches(fg_wan* h, int batch, int height, int width, hipStream_t s
     return FG_OK;
 }
 
+// fg_wan_forward_features' taps (the parity tests): fp32 copies of the buffers the next kernel consumes, on the same stream
+struct WanTaps {
+    const int* blocks;
+    const fg_wan_block_taps* taps;
+    int n;
+    float *tokens, *temb;
+};
+
 int wan_forward(fg_wan* h, const float* x_t, const float* t_frames, float* out, int batch, int frames, int height, int width,
-                int cur_start_frame, int store_kv, int block_causal, void* workspace, size_t workspace_bytes, void* stream) {
+                int cur_start_frame, int store_kv, int block_causal, void* workspace, size_t workspace_bytes, void* stream,
+                const WanTaps* tp = nullptr) {
     if (!h || !x_t || !t_frames || !out) return fail(FG_EINVAL, "null argument");
     if (!h->packed) return fail(FG_ENOTREADY, "weights are not packed (call fg_wan_pack_weights)");
     if (batch <= 0 || frames <= 0 || height <= 0 || width <= 0 || (height & 1) || (width & 1) || !workspace || (((uintptr_t)workspace) & 255))
@@ -399,7 +408,13 @@ int wan_forward(fg_wan* h, const float* x_t, const float* t_frames, float* out, 
     void *x = w.x0, *xn = w.x1;
     int rc;
     const int64_t cbs = (int64_t)cap * D;
+    const int64_t MD = (int64_t)M * D;
+    if (tp && tp->temb) HIP_TRY(hipMemcpyAsync(tp->temb, w.temb, sizeof(float) * (size_t)BF * D, hipMemcpyDeviceToDevice, s));
+    if (tp && tp->tokens) HIP_TRY(launch_from_act(1, x, tp->tokens, MD, s));
+    int ti = 0, blk_idx = 0;
     for (fg_wan::Blk& b : h->blocks) {
+        const fg_wan_block_taps* bt = (tp && ti < tp->n && tp->blocks[ti] == blk_idx) ? &tp->taps[ti++] : nullptr;
+        ++blk_idx;
         HIP_TRY(launch_wan_mod(h->P(b.sst), w.tproj, w.mod, BF, 6, D, s));
         // 1. self-attention over the cached frames and this chunk.  K / V of the chunk go to their cache rows in every call (a call
         // with store_kv = 0 leaves rows that the chunk's store_kv = 1 call rewrites; the reference's cache length only moves there)
@@ -426,8 +441,10 @@ int wan_forward(fg_wan* h, const float* x_t, const float* t_frames, float* out, 
             HIP_TRY(launch_rms_rope(D, qkv + 2 * D, 3 * D, nullptr, c.eps, nullptr, b.vc, cbs, cache_start, D, M, L, s));
             HIP_TRY(launch_fa128(w.qn, D, (int64_t)L * D, b.kc, b.vc, D, cbs, w.att, D, (int64_t)L * D, batch, h->H, L, cache_start + L, s, w.fa));
         }
+        if (bt && bt->attn1) HIP_TRY(launch_from_act(1, w.att, bt->attn1, MD, s));
         if ((rc = wan_gemm(w.att, b.p_o, h->P(b.o_b), xn, M, D, D, s, 0, w.mod + 2 * D, 6 * D, fs, x, w.gs, w.gs_bytes))) return rc;
         std::swap(x, xn);
+        if (bt && bt->x_attn1) HIP_TRY(launch_from_act(1, x, bt->x_attn1, MD, s));
         // 2. cross-attention to the text
         HIP_TRY(launch_dit_ln_modulate(1, D, x, b.n2mod, 0, 0, D, w.y, M, M, s));
         if ((rc = wan_gemm(w.y, b.p_q2, h->P(b.q2_b), w.qkv, M, D, D, s, 0, nullptr, 0, 1, nullptr, w.gs, w.gs_bytes))) return rc;
@@ -435,13 +452,16 @@ int wan_forward(fg_wan* h, const float* x_t, const float* t_frames, float* out, 
         const int64_t tbs = (int64_t)h->text_L * 2 * D;
         HIP_TRY(launch_fa128(w.qn, D, (int64_t)L * D, b.kv2, (const __bf16*)b.kv2 + D, 2 * D, tbs, w.att, D, (int64_t)L * D, batch, h->H, L,
                              h->text_L, s, w.fa));
+        if (bt && bt->attn2) HIP_TRY(launch_from_act(1, w.att, bt->attn2, MD, s));
         if ((rc = wan_gemm(w.att, b.p_o2, h->P(b.o2_b), xn, M, D, D, s, 0, nullptr, 0, 1, x, w.gs, w.gs_bytes))) return rc;
         std::swap(x, xn);
+        if (bt && bt->x_attn2) HIP_TRY(launch_from_act(1, x, bt->x_attn2, MD, s));
         // 3. feed-forward
         HIP_TRY(launch_dit_ln_modulate(1, D, x, w.mod, 6 * D, 3 * D, 4 * D, w.y, M, fs, s));
         if ((rc = wan_gemm(w.y, b.p_f0, h->P(b.f0_b), w.hid, M, h->Fd, D, s, 1))) return rc;
         if ((rc = wan_gemm(w.hid, b.p_f2, h->P(b.f2_b), xn, M, D, h->Fd, s, 0, w.mod + 5 * D, 6 * D, fs, x, w.gs, w.gs_bytes))) return rc;
         std::swap(x, xn);
+        if (bt && bt->x_ffn) HIP_TRY(launch_from_act(1, x, bt->x_ffn, MD, s));
     }
     if (!block_causal && store_kv && cache_start + L > h->stored_rows) h->stored_rows = cache_start + L;
     HIP_TRY(launch_wan_outmod(h->P(h->sst), w.temb, w.omod, BF, D, s));
@@ -458,4 +478,18 @@ int fg_wan_forward(fg_wan* h, const float* x_t, const float* t_frames, float* ou
 int fg_wan_forward_block_causal(fg_wan* h, const float* x_t, const float* t_frames, float* out, int batch, int frames, int height, int width,
                                 void* workspace, size_t workspace_bytes, void* stream) {
     return wan_forward(h, x_t, t_frames, out, batch, frames, height, width, 0, 0, 1, workspace, workspace_bytes, stream);
+}
+
+int fg_wan_forward_features(fg_wan* h, const float* x_t, const float* t_frames, float* out, int batch, int frames, int height, int width,
+                            int cur_start_frame, int store_kv, int block_causal, const int* tap_blocks, const fg_wan_block_taps* taps,
+                            int num_taps, float* tokens_out, float* temb_out, void* workspace, size_t workspace_bytes, void* stream) {
+    if (!h) return fail(FG_EINVAL, "null argument");
+    if (num_taps < 0 || (num_taps > 0 && (!tap_blocks || !taps))) return fail(FG_EINVAL, "bad tap arguments");
+    for (int i = 0; i < num_taps; ++i)
+        if (tap_blocks[i] < 0 || tap_blocks[i] >= (int)h->blocks.size() || (i > 0 && tap_blocks[i] <= tap_blocks[i - 1]))
+            return fail(FG_EINVAL, "tap_blocks must be ascending block indices in [0, %d)", (int)h->blocks.size());
+    if (block_causal && (cur_start_frame != 0 || store_kv)) return fail(FG_EINVAL, "the block-causal call starts at frame 0 and stores nothing");
+    const WanTaps tp{tap_blocks, taps, num_taps, tokens_out, temb_out};
+    return wan_forward(h, x_t, t_frames, out, batch, frames, height, width, cur_start_frame, store_kv, block_causal ? 1 : 0, workspace,
+                       workspace_bytes, stream, &tp);
 }

@@ -456,6 +456,23 @@ FG_API int fg_wan_forward(fg_wan* h, const float* x_t, const float* t_frames, fl
 FG_API int fg_wan_forward_block_causal(fg_wan* h, const float* x_t, const float* t_frames, float* out, int batch, int frames, int height,
                                        int width, void* workspace, size_t workspace_bytes, void* stream);
 
+/* Exposed for the parity tests (tests/test_gpu_wan_blocks.py): fg_wan_forward (block_causal == 0) or fg_wan_forward_block_causal
+ * (block_causal != 0; cur_start_frame and store_kv must be 0) with taps inside the blocks.  tap_blocks: HOST array of num_taps
+ * ascending block indices; taps: HOST array of as many structs of nullable fp32 device buffers [B, frames * frame_seqlen, inner dim],
+ * each the exact widening of the bf16 buffer the next kernel consumes.  tokens_out (nullable): [B, L, D] the patch embedding;
+ * temb_out (nullable): [B * frames, D] the fp32 time embedding (a copy).  The copies run on `stream` behind the kernel that wrote the
+ * buffer; `out` and the caches are what the untapped call leaves. */
+typedef struct fg_wan_block_taps {
+    float* attn1;    /* self-attention output before to_out */
+    float* x_attn1;  /* token stream after the gated self-attention residual */
+    float* attn2;    /* cross-attention output before to_out */
+    float* x_attn2;  /* token stream after the cross-attention residual */
+    float* x_ffn;    /* token stream after the feed-forward: the block's output */
+} fg_wan_block_taps;
+FG_API int fg_wan_forward_features(fg_wan* h, const float* x_t, const float* t_frames, float* out, int batch, int frames, int height, int width,
+                                   int cur_start_frame, int store_kv, int block_causal, const int* tap_blocks, const fg_wan_block_taps* taps,
+                                   int num_taps, float* tokens_out, float* temb_out, void* workspace, size_t workspace_bytes, void* stream);
+
 /* The chunk-by-chunk student loop of the causal video DiT as ONE call: `CausVidModel._student_sample_loop` (causvid.py:87-185), the
  * segment loop of `generator_fn_extrapolation` (:283-345, prefill_frames > 0) and the no-grad form of
  * `SelfForcingModel.rollout_with_gradient` (self_forcing.py:92-241, exit_steps != NULL).  x: [B, C, frames, H, W] fp32 latents (already

@@ -105,14 +105,16 @@ def random_state_dict(cfg: WanConfig, seed: int = 0) -> Dict[str, torch.Tensor]:
 
 
 def timesteps_proj(t: torch.Tensor, dim: int) -> torch.Tensor:
-    """diffusers `Timesteps(dim, flip_sin_to_cos=True, downscale_freq_shift=0)`: [cos | sin] of t * 10000^(-j / half)."""
+    """diffusers `Timesteps(dim, flip_sin_to_cos=True, downscale_freq_shift=0)`: [cos | sin] of t * 10000^(-j / half), in fp32 (or in
+    fp64 when t is fp64)."""
+    dt = torch.float64 if t.dtype == torch.float64 else torch.float32
     half = dim // 2
-    freq = torch.exp(-math.log(10000.0) * torch.arange(half, dtype=torch.float32) / half)
-    ang = t.float()[:, None] * freq[None, :]
+    freq = torch.exp(-math.log(10000.0) * torch.arange(half, dtype=dt) / half)
+    ang = t.to(dt)[:, None] * freq[None, :]
     return torch.cat([torch.cos(ang), torch.sin(ang)], dim=-1)
 
 
-def rope_tables(cfg: WanConfig):
+def rope_tables(cfg: WanConfig, dtype=torch.float32):
     """`WanRotaryPosEmbed.__init__`: per-axis cos / sin [max_seq_len, axis_dim] with every frequency repeated twice, float64 angles."""
     hd = cfg.head_dim
     h_dim = w_dim = 2 * (hd // 6)
@@ -121,15 +123,15 @@ def rope_tables(cfg: WanConfig):
     for d in (t_dim, h_dim, w_dim):
         freqs = 1.0 / (10000.0 ** (torch.arange(0, d, 2, dtype=torch.float64)[: d // 2] / d))
         ang = torch.outer(torch.arange(cfg.rope_max_seq_len, dtype=torch.float64), freqs)
-        cos.append(ang.cos().repeat_interleave(2, dim=1).float())
-        sin.append(ang.sin().repeat_interleave(2, dim=1).float())
+        cos.append(ang.cos().repeat_interleave(2, dim=1).to(dtype))
+        sin.append(ang.sin().repeat_interleave(2, dim=1).to(dtype))
     return cos, sin, (t_dim, h_dim, w_dim)
 
 
-def rope_for_chunk(cfg: WanConfig, frames: int, gh: int, gw: int, start_frame: int):
+def rope_for_chunk(cfg: WanConfig, frames: int, gh: int, gw: int, start_frame: int, dtype=torch.float32):
     """`_rope_forward_with_time_offset` (network_causal.py:79-128): [frames * gh * gw, head_dim] cos and sin with the temporal rows taken
     from `start_frame` on (clamped to the table's last row)."""
-    cos, sin, _ = rope_tables(cfg)
+    cos, sin, _ = rope_tables(cfg, dtype)
     total = cos[0].shape[0]
     idx = torch.clamp(torch.arange(start_frame, start_frame + frames), max=total - 1)
     cf, sf = cos[0][idx], sin[0][idx]
@@ -181,100 +183,173 @@ def blockwise_causal_mask(num_frames: int, frame_seqlen: int, chunk_size: int) -
     return (idx[None, :] < ends[:, None]) | (idx[None, :] == idx[:, None])
 
 
+# ---- the network's pieces.  Each runs in the dtype of its inputs: p = the state dict without its `transformer.` prefix, cast by the
+# caller (fp32: CausalWanRef; `.double()`: the per-block pin of tests/test_gpu_wan_blocks.py) -------------------------------------------
+def _lin(p, x, name):
+    return F.linear(x, p[name + ".weight"], p[name + ".bias"])
+
+
+def patch_embed(p, x_t: torch.Tensor) -> torch.Tensor:
+    """Conv3d kernel = stride = (1, 2, 2); tokens ordered (f, h, w): [B, C, F, H, W] -> [B, F * H/2 * W/2, D]."""
+    return F.conv3d(x_t, p["patch_embedding.weight"], p["patch_embedding.bias"], stride=(1, 2, 2)).flatten(2).transpose(1, 2)
+
+
+def time_embedding(p, cfg: WanConfig, ts: torch.Tensor) -> torch.Tensor:
+    """condition_embedder.time_embedder on the per-frame timesteps ts [B * F] (the embedder's units): temb [B * F, D]."""
+    return _lin(p, F.silu(_lin(p, timesteps_proj(ts, cfg.freq_dim), "condition_embedder.time_embedder.linear_1")),
+                "condition_embedder.time_embedder.linear_2")
+
+
+def time_projection(p, temb: torch.Tensor) -> torch.Tensor:
+    """time_proj(silu(temb)): [B * F, 6 D]."""
+    return _lin(p, F.silu(temb), "condition_embedder.time_proj")
+
+
+def text_embedding(p, text: torch.Tensor) -> torch.Tensor:
+    """condition_embedder.text_embedder (PixArtAlphaTextProjection): [B, Lt, text_dim] -> [B, Lt, D]."""
+    return _lin(p, F.gelu(_lin(p, text, "condition_embedder.text_embedder.linear_1"), approximate="tanh"),
+                "condition_embedder.text_embedder.linear_2")
+
+
+def modulation(p, i: int, tproj: torch.Tensor, B: int, Fr: int) -> torch.Tensor:
+    """Per-frame adaLN rows of block i: scale_shift_table + time projection, [B, F, 6, D] (shift, scale, gate | the same for the MLP)."""
+    D = tproj.shape[-1] // 6
+    return p[f"blocks.{i}.scale_shift_table"].view(1, 1, 6, D) + tproj.view(B, Fr, 6, D)
+
+
+def per_frame(x: torch.Tensor, sc: torch.Tensor, sh: torch.Tensor) -> torch.Tensor:
+    """x [B, F * fs, D] * (1 + sc [B, F, D]) + sh [B, F, D], frame by frame."""
+    B, L, D = x.shape
+    Fr = sc.shape[1]
+    return (x.view(B, Fr, L // Fr, D) * (1 + sc[:, :, None]) + sh[:, :, None]).reshape(B, L, D)
+
+
+def self_attn_qkv(p, cfg: WanConfig, i: int, hs: torch.Tensor, mod: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor):
+    """norm1 + modulation, to_q / to_k / to_v, RMSNorm across heads on q and k, RoPE on q and k: three [B, L, H, hd] tensors."""
+    b = f"blocks.{i}."
+    B, L, _ = hs.shape
+    y = per_frame(layer_norm(hs, cfg.eps), mod[:, :, 1], mod[:, :, 0])
+    q = rms_norm(_lin(p, y, b + "attn1.to_q"), p[b + "attn1.norm_q.weight"], cfg.eps).view(B, L, cfg.num_heads, -1)
+    k = rms_norm(_lin(p, y, b + "attn1.to_k"), p[b + "attn1.norm_k.weight"], cfg.eps).view(B, L, cfg.num_heads, -1)
+    v = _lin(p, y, b + "attn1.to_v").view(B, L, cfg.num_heads, -1)
+    return apply_rope(q, cos, sin), apply_rope(k, cos, sin), v
+
+
+def self_attn_out(p, i: int, hs: torch.Tensor, att: torch.Tensor, mod: torch.Tensor) -> torch.Tensor:
+    """to_out on the attention output att [B, L, D], gated per frame, added to the stream."""
+    B, L, D = hs.shape
+    Fr = mod.shape[1]
+    o = _lin(p, att, f"blocks.{i}.attn1.to_out.0")
+    return hs + (o.view(B, Fr, L // Fr, D) * mod[:, :, 2][:, :, None]).reshape(B, L, D)
+
+
+def cross_kv(p, cfg: WanConfig, i: int, ctx: torch.Tensor):
+    """The static cross-attention cache of block i: k = norm_k(to_k(ctx)), v = to_v(ctx), [B, Lt, H, hd] each."""
+    b = f"blocks.{i}."
+    B = ctx.shape[0]
+    k2 = rms_norm(_lin(p, ctx, b + "attn2.to_k"), p[b + "attn2.norm_k.weight"], cfg.eps).view(B, -1, cfg.num_heads, cfg.head_dim)
+    v2 = _lin(p, ctx, b + "attn2.to_v").view(B, -1, cfg.num_heads, cfg.head_dim)
+    return k2, v2
+
+
+def cross_attn(p, cfg: WanConfig, i: int, hs: torch.Tensor, k2: torch.Tensor, v2: torch.Tensor):
+    """norm2 (affine), to_q + RMSNorm, attention to the text, to_out, residual: (attention output before to_out, new stream)."""
+    b = f"blocks.{i}."
+    B, L, _ = hs.shape
+    y = layer_norm(hs, cfg.eps, p[b + "norm2.weight"], p[b + "norm2.bias"])
+    q2 = rms_norm(_lin(p, y, b + "attn2.to_q"), p[b + "attn2.norm_q.weight"], cfg.eps).view(B, L, cfg.num_heads, -1)
+    att = sdpa(q2, k2, v2)
+    return att, hs + _lin(p, att, b + "attn2.to_out.0")
+
+
+def ffn(p, cfg: WanConfig, i: int, hs: torch.Tensor, mod: torch.Tensor) -> torch.Tensor:
+    """norm3 + modulation, Linear - GELU(tanh) - Linear, gated per frame, added to the stream."""
+    b = f"blocks.{i}."
+    B, L, D = hs.shape
+    Fr = mod.shape[1]
+    y = per_frame(layer_norm(hs, cfg.eps), mod[:, :, 4], mod[:, :, 3])
+    ff = _lin(p, F.gelu(_lin(p, y, b + "ffn.net.0.proj"), approximate="tanh"), b + "ffn.net.2")
+    return hs + (ff.view(B, Fr, L // Fr, D) * mod[:, :, 5][:, :, None]).reshape(B, L, D)
+
+
+def final_layer(p, cfg: WanConfig, hs: torch.Tensor, temb: torch.Tensor, Fr: int, gh: int, gw: int) -> torch.Tensor:
+    """Per-frame output modulation (Wan/network.py:226-247), proj_out, un-patchify: [B, L, D] -> [B, C, F, 2 gh, 2 gw]."""
+    B, L, D = hs.shape
+    so = p["scale_shift_table"].view(1, 1, 2, D) + temb.view(B, Fr, 1, D)
+    y = (layer_norm(hs, cfg.eps).view(B, Fr, L // Fr, D) * (1 + so[:, :, 1, None]) + so[:, :, 0, None]).reshape(B, L, D)
+    o = _lin(p, y, "proj_out").view(B, Fr, gh, gw, 1, 2, 2, -1)
+    return o.permute(0, 7, 1, 4, 2, 5, 3, 6).reshape(B, -1, Fr, 2 * gh, 2 * gw)
+
+
 class CausalWanRef:
     """The network with its external KV caches (network_causal.py:708-812): per block a self-attention cache of
-    `total_num_frames * frame_seqlen` tokens and a static cross-attention cache."""
+    `total_num_frames * frame_seqlen` tokens and a static cross-attention cache.  dtype: what the weights and every tensor are cast to
+    (fp32: the oracle of tests/test_wan.py; fp64: the composition the per-block pin takes its pieces from)."""
 
-    def __init__(self, sd: Dict[str, torch.Tensor], cfg: WanConfig):
-        self.cfg = cfg
-        self.p = {k[len("transformer."):]: v.float() for k, v in sd.items()}
+    def __init__(self, sd: Dict[str, torch.Tensor], cfg: WanConfig, dtype=torch.float32):
+        self.cfg, self.dtype = cfg, dtype
+        self.p = {k[len("transformer."):]: v.to(dtype) for k, v in sd.items()}
         self.clear_caches()
 
     def clear_caches(self):
         self.self_kv: List[Optional[dict]] = [None] * self.cfg.num_layers
         self.cross_kv: List[Optional[dict]] = [None] * self.cfg.num_layers
 
-    def _lin(self, x, name):
-        return F.linear(x, self.p[name + ".weight"], self.p[name + ".bias"])
-
     def forward(self, x_t: torch.Tensor, t: torch.Tensor, text: torch.Tensor, cur_start_frame: int = 0, store_kv: bool = False,
                 trace: Optional[dict] = None, block_causal: bool = False) -> torch.Tensor:
         """The raw network output (net_pred_type: flow) of `CausalWan.forward(..., is_ar=True)`.  x_t [B, C, F, H, W]; t [B] in the
         schedule's units (rescaled by 1000 here, `_compute_timestep_inputs` :1063-1075) - every frame of the chunk gets t - or [B, F]
-        (one per frame: diffusion forcing).
+        (one per frame: diffusion forcing).  The embedder sees the fp32 value of 1000 t in every dtype (as the C ABI's t_frames).
         block_causal: the `is_ar=False` call over all total_num_frames frames - self-attention under the block-wise causal mask, no
         self-attention cache read or written (the reference allocates none for a full-length call, :681-690)."""
-        cfg, p = self.cfg, self.p
+        cfg, p, dt = self.cfg, self.p, self.dtype
         B, C, Fr, H, W = x_t.shape
-        gh, gw, D = H // 2, W // 2, cfg.dim
+        gh, gw = H // 2, W // 2
         fs = gh * gw  # frame_seqlen
         L = Fr * fs
-        ts = (1000.0 * t.float()).view(B, -1).expand(B, Fr).reshape(-1)  # [B * F]
+        ts = (1000.0 * t.float()).view(B, -1).expand(B, Fr).reshape(-1).to(dt)  # [B * F]
+        mask = None
         if block_causal:
             assert Fr == cfg.total_num_frames and cur_start_frame == 0 and not store_kv
             mask = blockwise_causal_mask(Fr, fs, cfg.chunk_size)
-        cos, sin = rope_for_chunk(cfg, Fr, gh, gw, cur_start_frame)
-        # patch embedding: Conv3d kernel = stride = (1, 2, 2); tokens ordered (f, h, w)
-        hs = F.conv3d(x_t.float(), p["patch_embedding.weight"], p["patch_embedding.bias"], stride=(1, 2, 2)).flatten(2).transpose(1, 2)
-        # condition embedder (per frame)
-        temb = self._lin(F.silu(self._lin(timesteps_proj(ts, cfg.freq_dim), "condition_embedder.time_embedder.linear_1")),
-                         "condition_embedder.time_embedder.linear_2")  # [B * F, D]
-        tproj = self._lin(F.silu(temb), "condition_embedder.time_proj").view(B, Fr, 6, D)
-        ctx = self._lin(F.gelu(self._lin(text.float(), "condition_embedder.text_embedder.linear_1"), approximate="tanh"),
-                        "condition_embedder.text_embedder.linear_2")  # [B, Lt, D]
+        cos, sin = rope_for_chunk(cfg, Fr, gh, gw, cur_start_frame, dt)
+        hs = patch_embed(p, x_t.to(dt))
+        temb = time_embedding(p, cfg, ts)  # [B * F, D]
+        tproj = time_projection(p, temb)
+        ctx = text_embedding(p, text.to(dt))  # [B, Lt, D]
         if trace is not None:
             trace["tokens"], trace["temb"], trace["ctx"] = hs.clone(), temb.clone(), ctx.clone()
         cache_start = cur_start_frame * fs
         cap = cfg.total_num_frames * fs
         for i in range(cfg.num_layers):
-            b = f"blocks.{i}."
-            mod = p[b + "scale_shift_table"].view(1, 1, 6, D) + tproj  # [B, F, 6, D]
-            shift, scale, gate, c_shift, c_scale, c_gate = [mod[:, :, j] for j in range(6)]
-
-            def per_frame(x, sc, sh):
-                return (x.view(B, Fr, fs, D) * (1 + sc[:, :, None]) + sh[:, :, None]).reshape(B, L, D)
-
+            mod = modulation(p, i, tproj, B, Fr)
             # 1. self-attention over the cached frames and this chunk (:377-412)
-            y = per_frame(layer_norm(hs, cfg.eps), scale, shift)
-            q = rms_norm(self._lin(y, b + "attn1.to_q"), p[b + "attn1.norm_q.weight"], cfg.eps).view(B, L, cfg.num_heads, -1)
-            k = rms_norm(self._lin(y, b + "attn1.to_k"), p[b + "attn1.norm_k.weight"], cfg.eps).view(B, L, cfg.num_heads, -1)
-            v = self._lin(y, b + "attn1.to_v").view(B, L, cfg.num_heads, -1)
-            q, k = apply_rope(q, cos, sin), apply_rope(k, cos, sin)
+            q, k, v = self_attn_qkv(p, cfg, i, hs, mod, cos, sin)
             if block_causal:
-                att = self._lin(sdpa(q, k, v, mask), b + "attn1.to_out.0")
+                att = sdpa(q, k, v, mask)
             else:
                 if self.self_kv[i] is None:
-                    self.self_kv[i] = {"k": torch.zeros(B, cap, cfg.num_heads, cfg.head_dim), "v": torch.zeros(B, cap, cfg.num_heads, cfg.head_dim)}
+                    self.self_kv[i] = {"k": torch.zeros(B, cap, cfg.num_heads, cfg.head_dim, dtype=dt),
+                                       "v": torch.zeros(B, cap, cfg.num_heads, cfg.head_dim, dtype=dt)}
                 kv = self.self_kv[i]
                 if store_kv:
                     kv["k"][:, cache_start:cache_start + L] = k
                     kv["v"][:, cache_start:cache_start + L] = v
-                k_full = torch.cat([kv["k"][:, :cache_start], k], dim=1)
-                v_full = torch.cat([kv["v"][:, :cache_start], v], dim=1)
-                att = self._lin(sdpa(q, k_full, v_full), b + "attn1.to_out.0")
-            hs = hs + (att.view(B, Fr, fs, D) * gate[:, :, None]).reshape(B, L, D)
+                att = sdpa(q, torch.cat([kv["k"][:, :cache_start], k], dim=1), torch.cat([kv["v"][:, :cache_start], v], dim=1))
+            hs = self_attn_out(p, i, hs, att, mod)
             # 2. cross-attention to the text (static cache, :331-360)
-            y = layer_norm(hs, cfg.eps, p[b + "norm2.weight"], p[b + "norm2.bias"])
-            q2 = rms_norm(self._lin(y, b + "attn2.to_q"), p[b + "attn2.norm_q.weight"], cfg.eps).view(B, L, cfg.num_heads, -1)
             if self.cross_kv[i] is None or store_kv:
-                k2 = rms_norm(self._lin(ctx, b + "attn2.to_k"), p[b + "attn2.norm_k.weight"], cfg.eps).view(B, -1, cfg.num_heads, cfg.head_dim)
-                v2 = self._lin(ctx, b + "attn2.to_v").view(B, -1, cfg.num_heads, cfg.head_dim)
+                k2, v2 = cross_kv(p, cfg, i, ctx)
                 if store_kv:
                     self.cross_kv[i] = {"k": k2, "v": v2}
             else:
                 k2, v2 = self.cross_kv[i]["k"], self.cross_kv[i]["v"]
-            hs = hs + self._lin(sdpa(q2, k2, v2), b + "attn2.to_out.0")
+            hs = cross_attn(p, cfg, i, hs, k2, v2)[1]
             # 3. feed-forward
-            y = per_frame(layer_norm(hs, cfg.eps), c_scale, c_shift)
-            ff = self._lin(F.gelu(self._lin(y, b + "ffn.net.0.proj"), approximate="tanh"), b + "ffn.net.2")
-            hs = hs + (ff.view(B, Fr, fs, D) * c_gate[:, :, None]).reshape(B, L, D)
+            hs = ffn(p, cfg, i, hs, mod)
             if trace is not None:
                 trace[f"block{i}"] = hs.clone()
-        # output: per-frame modulation (Wan/network.py:226-247), projection, un-patchify
-        so = p["scale_shift_table"].view(1, 1, 2, D) + temb.view(B, Fr, 1, D)
-        y = (layer_norm(hs, cfg.eps).view(B, Fr, fs, D) * (1 + so[:, :, 1, None]) + so[:, :, 0, None]).reshape(B, L, D)
-        o = self._lin(y, "proj_out").view(B, Fr, gh, gw, 1, 2, 2, -1)
-        return o.permute(0, 7, 1, 4, 2, 5, 3, 6).reshape(B, -1, Fr, H, W)
+        return final_layer(p, cfg, hs, temb, Fr, gh, gw)
 
 
 def student_sample_loop(net: CausalWanRef, x: torch.Tensor, t_list: torch.Tensor, text: torch.Tensor, eps_list: Optional[list] = None,

@@ -52,6 +52,28 @@ def test_oracle_cache_append_equals_attention_over_all_frames():
     assert torch.allclose(tr1["block0"][:, :L], tr2["block0"][:, L:], atol=2e-5)
 
 
+def test_fp64_composition_of_the_oracle_pieces_agrees_with_the_fp32_forward():
+    """The oracle's pieces run in the dtype of their inputs (tests/test_gpu_wan_blocks.py runs them in fp64): composed in fp64 they agree
+    with the fp32 forward on TINY - chunk 0, its cache-fill call, chunk 1 over the cache with per-frame timesteps, the block-causal call.
+    Bound 2e-5 (relative L2 and max): fp32 rounding (6e-8) through two blocks of 128- to 512-term sums, and timestep angles of up to
+    1000 rad, whose fp32 rounding (6e-5 rad) is the largest single term; measured 4e-7 ... 5e-6."""
+    cfg = R.TINY
+    sd = R.random_state_dict(cfg, 11)
+    n32, n64 = R.CausalWanRef(sd, cfg), R.CausalWanRef(sd, cfg, dtype=torch.float64)
+    g = torch.Generator().manual_seed(12)
+    x = torch.randn(2, 16, 6, 6, 10, generator=g)
+    text = torch.randn(2, 13, cfg.text_dim, generator=g)
+    t1, tf = torch.rand(2, generator=g, dtype=torch.float64), torch.rand(2, 6, generator=g, dtype=torch.float64)
+    calls = [(x[:, :, :2], t1, 0, False, False), (x[:, :, :2], 0 * t1, 0, True, False), (x[:, :, 2:4], tf[:, 2:4], 2, False, False),
+             (x[:, :, 2:4], t1, 2, True, False), (x, tf, 0, False, True)]
+    for xc, t, start, store, bc in calls:
+        a = n32.forward(xc, t, text, cur_start_frame=start, store_kv=store, block_causal=bc)
+        b = n64.forward(xc, t, text, cur_start_frame=start, store_kv=store, block_causal=bc)
+        assert a.dtype == torch.float32 and b.dtype == torch.float64
+        e = (a.double() - b)
+        assert float(e.norm() / b.norm()) < 2e-5 and float(e.abs().max() / b.abs().max()) < 2e-5, (start, store, bc)
+
+
 def test_module_state_dict_matches_the_restated_key_list():
     from fastgen_amd.networks.Wan.network_causal import CausalWan
 
