@@ -18,6 +18,7 @@ struct ConvArgs {
     const float* temb;  // [B][temb_stride] per-image per-channel additive term (affine(emb)), or nullptr
     int temb_stride;
     const void* resid;   // [B,H,W,Cout] residual (compute dtype) added before `scale`, or nullptr
+    int rshift = 0;      // 1: resid is [B,H/2,W/2,Cout] and output pixel (y, x) adds its pixel (y >> 1, x >> 1) (conv_ws3.hip, RES_NONE only)
     float scale;
     void* out;  // [B,H,W,Cout] in the compute dtype (OUT_NHWC)
     int Cout;
@@ -40,7 +41,8 @@ struct ConvArgs {
 };
 
 enum { PRO_NONE = 0, PRO_GN = 1, PRO_GN_SILU = 2 };
-enum { RES_NONE = 0, RES_DOWN = 1, RES_UP = 2 };
+// RES_SUBPIX: RES_UP of a 3x3 conv evaluated as four 2x2 convs on the low-resolution source (conv_ws3.hip only)
+enum { RES_NONE = 0, RES_DOWN = 1, RES_UP = 2, RES_SUBPIX = 3 };
 enum { OUT_NHWC = 0, OUT_QKV = 1, OUT_TOK = 2, OUT_HEADS = 3 };
 
 // dtype: 0 fp32, 1 bf16 — also the storage type of every activation tensor (src1/src2/resid/out); 2 = split-bf16 arithmetic
@@ -58,9 +60,14 @@ int launch_pack_conv_weights_ws(const float* w_oihw, void* wpack_ws, int cout, i
 // conv_ws3.hip: the wave-specialised kernel of the split-bf16 mode (dtype 2), same dispatch rule
 bool conv_x3ws_supported(int ks, int pro, int res, int outmode, const ConvArgs& a);
 bool conv_x3ws_shape_ok(int cout, int cin, int res);
-int conv_x3ws_stat_slots(int W);
+int conv_x3ws_stat_slots(int W, int res);
 int launch_conv_x3ws(int res, const ConvArgs& a, hipStream_t stream, bool prepare_only, int pro = PRO_GN_SILU);
 int launch_pack_conv_weights_x3ws(const float* w_oihw, void* wpack_ws, int cout, int cin, hipStream_t stream);
+// per-phase merged 2x2 weights of RES_SUBPIX: 16 * cout * cin {hi, lo} bf16 pairs = conv_pack_elems(cout, cin, 4) * 4 bytes
+int launch_pack_conv_weights_x3sub(const float* w_oihw, void* wpack_sub, int cout, int cin, hipStream_t stream);
+// FASTGEN_AMD_CONV_SUBPIX: 0 = up blocks keep the full-resolution launches, "skip" = only the low-resolution 1x1 skip,
+// anything else / unset = sub-pixel conv0 and low-resolution skip; read once
+int conv_subpix_mode();
 // statistics slots per image that launch_conv_fused will write for this call (depends on the kernel the dispatch picks)
 int conv_launch_stat_slots(int dtype, int ks, int pro, int res, int outmode, const ConvArgs& a);
 int launch_conv_ws_debug(const ConvArgs& a, int abl, hipStream_t stream);  // ablation builds of the 32x32 shape

@@ -23,6 +23,7 @@
 #include "common.h"
 #include "conv.h"
 #include <stdlib.h>
+#include <string.h>
 
 #include <type_traits>
 
@@ -671,11 +672,12 @@ int launch_conv_fused(int dtype, int ks, int pro, int res, int outmode, const Co
         return (int)hipErrorInvalidValue;
     if (res == RES_NONE && (a.Hs != a.H || a.Ws != a.W)) return (int)hipErrorInvalidValue;
     if (res == RES_DOWN && (a.Hs != 2 * a.H || a.Ws != 2 * a.W)) return (int)hipErrorInvalidValue;
-    if (res == RES_UP && (2 * a.Hs != a.H || 2 * a.Ws != a.W)) return (int)hipErrorInvalidValue;
+    if ((res == RES_UP || res == RES_SUBPIX) && (2 * a.Hs != a.H || 2 * a.Ws != a.W)) return (int)hipErrorInvalidValue;
     if (pro != PRO_NONE && !a.ab) return (int)hipErrorInvalidValue;
     if (outmode == OUT_QKV && (a.Cout != 768 || a.W > 16)) return (int)hipErrorInvalidValue;
     if (conv_ws_enabled() && conv_ws_supported(dtype, ks, pro, res, outmode, a)) return launch_conv_ws(res, a, stream, false, pro);
     if (dtype == 2 && conv_ws_enabled() && conv_x3ws_supported(ks, pro, res, outmode, a)) return launch_conv_x3ws(res, a, stream, false, pro);
+    if (res == RES_SUBPIX || a.rshift) return (int)hipErrorInvalidValue;  // conv_ws3.hip only: the caller checks conv_x3ws_supported first
     return dispatch_t(dtype, ks, pro, res, outmode, a, stream);
 }
 
@@ -688,8 +690,17 @@ bool conv_ws_enabled() {
     return on;
 }
 
+int conv_subpix_mode() {
+    static const int mode = [] {
+        const char* e = getenv("FASTGEN_AMD_CONV_SUBPIX");
+        if (e && e[0] == '0') return 0;
+        return (e && !strcmp(e, "skip")) ? 1 : 2;
+    }();
+    return mode;
+}
+
 int conv_launch_stat_slots(int dtype, int ks, int pro, int res, int outmode, const ConvArgs& a) {
-    if (dtype == 2 && conv_ws_enabled() && conv_x3ws_supported(ks, pro, res, outmode, a)) return conv_x3ws_stat_slots(a.W);
+    if (dtype == 2 && conv_ws_enabled() && conv_x3ws_supported(ks, pro, res, outmode, a)) return conv_x3ws_stat_slots(a.W, res);
     return conv_stat_slots(a.W);
 }
 
@@ -724,6 +735,11 @@ int conv_prepare_all(int dtype) {
                 if (!rc) rc = launch_conv_x3ws(res, w, nullptr, true, PRO_GN_SILU);
                 if (!rc && res == RES_NONE) rc = launch_conv_x3ws(res, w, nullptr, true, PRO_NONE);
             }
+        for (int ws_ : {16, 8}) {
+            w.Ws = w.Hs = ws_;
+            w.W = w.H = 2 * ws_;
+            if (!rc) rc = launch_conv_x3ws(RES_SUBPIX, w, nullptr, true, PRO_GN_SILU);
+        }
     }
     if (!rc && dtype == 1) {
         ConvArgs w{};

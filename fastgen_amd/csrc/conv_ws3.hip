@@ -40,7 +40,7 @@ constexpr int X3_ABUF = 8 * X3_PLANE;      // 24576
 constexpr int X3_RING = 4;
 constexpr int X3_HOFF = 128 * 512;         // 65536
 constexpr int X3_LDS = X3_HOFF + X3_RING * X3_ABUF;  // 163840 = the CU's whole LDS
-constexpr int X3_STEPB = 9 * 2048;         // bytes of packed weights per step and 16-channel group: [tap][part][lane][8] bf16
+constexpr int X3_TAPB = 2048;              // bytes of packed weights per tap, step and 16-channel group: [part][lane][8] bf16
 
 // 32x32 / 16x16: a tile is an 8x16-pixel window of one image.  8x8: a tile is TWO whole images side by side (image 2t in columns
 // 0-7, image 2t+1 in columns 8-15); their halos share the zero column between them, so a halo row is 1 + 8 + 1 + 8 + 1 = 19
@@ -67,9 +67,22 @@ struct X3Frag {
     bf16x8 hi, lo;
 };
 
+// RES_SUBPIX: the nearest 2x up-sampling in front of the conv, as four 2x2 convs on the LOW-resolution source (LOGW is the
+// source's geometry).  Output pixel (2y + py, 2x + px) reads up-sampled rows 2y + py - 1 .. 2y + py + 1 = source rows
+// {y - 1, y, y} (py = 0) or {y, y, y + 1} (py = 1), columns alike: per phase (py, px) the kernel rows {0}, {1,2} / {0,1}, {2}
+// (and columns) merge into a 2x2 kernel whose tap (ty, tx) reads source pixel (y - 1 + py + ty, x - 1 + px + tx), halo
+// position (ty + py, tx + px) of the window.  The zero border of the up-sampled image is the zero border of the source halo for
+// every phase (a source pixel's 2x2 replicas are all inside or all outside).  A tile is (source tile, phase), t = 4 * source
+// tile + 2 py + px: 16 quarter-taps per step instead of 36, merged weights packed per phase (pack_conv_weights_x3sub_kernel),
+// output stored with stride 2 in both directions.
 template <int RES, int LOGW, int PRO>
 __global__ __launch_bounds__(X3_NTHR) void conv3_x3ws_kernel(const ConvArgs a, const int ntiles) {
     using G = X3Geom<LOGW>;
+    constexpr bool SUB = RES == RES_SUBPIX;
+    constexpr int NTAP = SUB ? 4 : 9;         // taps per step
+    constexpr int RN = SUB ? 4 : 3;           // taps in the weight register ring
+    constexpr int NQ = 4 * NTAP;              // quarter-taps per step
+    constexpr int X3_STEPB = NTAP * X3_TAPB;  // bytes of packed weights per step and 16-channel group
     extern __shared__ __attribute__((aligned(16))) char smem[];
     char* const hbuf = smem;
     char* const ring = smem + X3_HOFF;
@@ -86,30 +99,33 @@ __global__ __launch_bounds__(X3_NTHR) void conv3_x3ws_kernel(const ConvArgs a, c
     const int my_tiles = (ntiles - wg + gstride - 1) / gstride;  // >= 1: grid <= ntiles
     const int S = my_tiles * nchunk;
     const int NSTEP = S + 3;  // group B finishes at global step S + 1, its last half tile is retired during S + 2
-    const int H = a.H;
+    const int H = SUB ? a.Hs : a.H;  // of the tensor the tiles are cut from
 
     if (wave < 8) {
         // ================================================= consumers =================================================
         const int grp = wave >> 2, wl = wave & 3;
         const int col = lane & 15, g4 = lane >> 4;
-        // packed weights [cout/16][step][tap][part][lane][8] (pack_conv_weights_x3ws_kernel); this wave: groups 8 grp + 2 wl, +1
-        const size_t wstride = (size_t)nchunk * 9 * 1024;  // bf16 elements per 16-channel group
+        // packed weights [cout/16][step][tap][part][lane][8] (pack_conv_weights_x3ws_kernel; SUB: one such block of 16 groups per
+        // phase); this wave: groups 8 grp + 2 wl, +1
+        const size_t wstride = (size_t)nchunk * NTAP * 1024;  // bf16 elements per 16-channel group
         const __amdgpu_buffer_rsrc_t wrs = __builtin_amdgcn_make_buffer_rsrc(
             const_cast<__bf16*>(reinterpret_cast<const __bf16*>(a.wpack_ws) + (size_t)(grp * 8 + wl * 2) * wstride), 0, 0x7fffffff,
             0x00020000);
         const int wvoff = lane * 16;
         const int wsb = (int)(wstride * 2);
+        const int wphb = SUB ? 16 * wsb : 0;  // bytes per phase
+        int tcur = wg;                        // this group's tile (SUB: its phase is tcur & 3)
         auto load_w = [&](int byte_off) -> X3Frag {
             X3Frag f;
             f.hi = __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(wrs, wvoff, byte_off, 0));
             f.lo = __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(wrs, wvoff, byte_off + 1024, 0));
             return f;
         };
-        X3Frag wq[3][2];
+        X3Frag wq[RN][2];
 #pragma unroll
-        for (int j = 0; j < 3; ++j)
+        for (int j = 0; j < RN; ++j)
 #pragma unroll
-            for (int nt = 0; nt < 2; ++nt) wq[j][nt] = load_w(nt * wsb + j * 2048);
+            for (int nt = 0; nt < 2; ++nt) wq[j][nt] = load_w((tcur & 3) * wphb + nt * wsb + j * X3_TAPB);
 
         f32x4 acc[8][2];
 #pragma unroll
@@ -127,14 +143,16 @@ __global__ __launch_bounds__(X3_NTHR) void conv3_x3ws_kernel(const ConvArgs a, c
         for (int s = 0; s < NSTEP; ++s) {
             const int ls = s - 2 * grp;  // this group's step
             if (ls >= 0 && ls < S) {
-                const char* abase = ring + (ls & 3) * X3_ABUF + lane_off;
+                // SUB: the phase shifts the window by (py, px) halo pixels and selects the block of merged weights; uniform per tile
+                const char* abase = ring + (ls & 3) * X3_ABUF + lane_off + (SUB ? ((tcur >> 1) & 1) * G::RS + (tcur & 1) * X3_PA : 0);
                 const int cn = (c + 1 == nchunk) ? 0 : c + 1;
-                const int wcur = c * X3_STEPB;
-                const int wnxt = (ls + 1 < S) ? cn * X3_STEPB : wcur;  // the very last refills re-read this step (never used)
+                const int tnext = cn == 0 ? tcur + gstride : tcur;
+                const int wcur = (tcur & 3) * wphb + c * X3_STEPB;
+                const int wnxt = (ls + 1 < S) ? (tnext & 3) * wphb + cn * X3_STEPB : wcur;  // the very last refills re-read this step (never used)
                 // quarter-tap q: tap q >> 2, pixel rows 2 (q & 3), +1
                 auto read_x = [&](int q, X3Frag (&xf)[2]) {
                     const int tap = q >> 2, m0 = 2 * (q & 3);
-                    const int off = (tap / 3 + m0) * G::RS + (tap % 3) * X3_PA;
+                    const int off = ((SUB ? tap >> 1 : tap / 3) + m0) * G::RS + (SUB ? tap & 1 : tap % 3) * X3_PA;
 #pragma unroll
                     for (int m = 0; m < 2; ++m) {
                         xf[m].hi = *reinterpret_cast<const bf16x8*>(abase + off + m * G::RS);
@@ -143,7 +161,7 @@ __global__ __launch_bounds__(X3_NTHR) void conv3_x3ws_kernel(const ConvArgs a, c
                 };
                 auto mma12 = [&](int q, const X3Frag (&xf)[2]) {
                     const int tap = q >> 2, m0 = 2 * (q & 3);
-                    const X3Frag(&wf)[2] = wq[tap % 3];
+                    const X3Frag(&wf)[2] = wq[tap % RN];
                     // small terms first; every accumulator is touched once per group of four MFMAs
 #pragma unroll
                     for (int m = 0; m < 2; ++m)
@@ -161,20 +179,20 @@ __global__ __launch_bounds__(X3_NTHR) void conv3_x3ws_kernel(const ConvArgs a, c
                         for (int nt = 0; nt < 2; ++nt)
                             acc[m0 + m][nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[nt].hi, xf[m].hi, acc[m0 + m][nt], 0, 0, 0);
                     if ((q & 3) != 3) return;
-                    // the tap's fragments are dead: refill their ring slot three taps ahead
-                    const int pn = (tap + 3 < 9) ? wcur + (tap + 3) * 2048 : wnxt + (tap + 3 - 9) * 2048;
+                    // the tap's fragments are dead: refill their ring slot RN taps ahead
+                    const int pn = (tap + RN < NTAP) ? wcur + (tap + RN) * X3_TAPB : wnxt + (tap + RN - NTAP) * X3_TAPB;
 #pragma unroll
-                    for (int nt = 0; nt < 2; ++nt) wq[tap % 3][nt] = load_w(pn + nt * wsb);
+                    for (int nt = 0; nt < 2; ++nt) wq[tap % RN][nt] = load_w(pn + nt * wsb);
                 };
                 X3Frag x0[2], x1[2];
                 read_x(0, x0);
 #pragma unroll
-                for (int q = 0; q < 36; q += 2) {
+                for (int q = 0; q < NQ; q += 2) {
                     read_x(q + 1, x1);
                     __builtin_amdgcn_sched_barrier(0);
                     mma12(q, x0);
                     __builtin_amdgcn_sched_barrier(0);
-                    if (q + 2 < 36) read_x(q + 2, x0);
+                    if (q + 2 < NQ) read_x(q + 2, x0);
                     __builtin_amdgcn_sched_barrier(0);
                     mma12(q + 1, x1);
                     __builtin_amdgcn_sched_barrier(0);
@@ -190,6 +208,7 @@ __global__ __launch_bounds__(X3_NTHR) void conv3_x3ws_kernel(const ConvArgs a, c
                     }
                 }
                 c = cn;
+                tcur = tnext;
             }
             x3_barrier();
         }
@@ -229,6 +248,7 @@ __global__ __launch_bounds__(X3_NTHR) void conv3_x3ws_kernel(const ConvArgs a, c
     }
 
     auto tile_coord = [&](int t, int& n, int& slot, int& row0, int& col0) {
+        if (SUB) t >>= 2;         // the source tile; the phase is t & 3
         n = t * G::IPT / G::TPI;  // 8x8: the first image of the pair
         slot = t - n * G::TPI / G::IPT;
         row0 = (slot / G::TCOLS) * G::TH;
@@ -331,7 +351,14 @@ __global__ __launch_bounds__(X3_NTHR) void conv3_x3ws_kernel(const ConvArgs a, c
             if (a.temb) radd[k] += *reinterpret_cast<const f32x4*>(a.temb + (size_t)nk * a.temb_stride + co);
             radd[k] *= a.scale;  // (acc + add + resid) * scale evaluated as fma(acc, scale, add * scale) [+ fma(resid, scale, .)]
         }
-        const size_t tb = (((size_t)n * H + row0) * G::W + col0) * 256 + co;
+        // SUB: hand-off pixel (r, c) of the tile is output pixel (2 (row0 + r) + py, 2 (col0 + c) + px) of a 2H x 2W image
+        constexpr int OW = SUB ? 2 * G::W : G::W, OST = SUB ? 2 : 1;
+        const int ph = t & 3;
+        const size_t tb = SUB ? (((size_t)n * (2 * H) + 2 * row0 + (ph >> 1)) * OW + 2 * col0 + (ph & 1)) * 256 + co
+                              : (((size_t)n * H + row0) * G::W + col0) * 256 + co;
+        // residual: at the output position, or (a.rshift = 1) at (y >> 1, x >> 1) of a half-resolution tensor
+        const int rs = (SUB || G::IPT == 2) ? 0 : a.rshift;
+        const size_t rtb = (SUB || G::IPT == 2) ? tb : (((size_t)n * (H >> rs) + (row0 >> rs)) * (G::W >> rs) + (col0 >> rs)) * 256 + co;
         float ssum[G::IPT] = {}, ssq[G::IPT] = {};
 #pragma unroll 1
         for (int grp8 = 0; grp8 < 2; ++grp8) {
@@ -340,12 +367,16 @@ __global__ __launch_bounds__(X3_NTHR) void conv3_x3ws_kernel(const ConvArgs a, c
 #pragma unroll
             for (int j = 0; j < 8; ++j) {
                 const int px = pw * 32 + 2 * (grp8 * 8 + j) + psub;
-                if (G::IPT == 2)
-                    go[j] = (unsigned)((((j >> 2) * G::W + (px >> 4)) * G::W + (px & 7)) * 256);
-                else
-                    go[j] = (unsigned)(((px >> 4) * G::W + (px & 15)) * 256);
+                unsigned rgo;
+                if (G::IPT == 2) {
+                    go[j] = (unsigned)((((j >> 2) * OW + OST * (px >> 4)) * OW + OST * (px & 7)) * 256);
+                    rgo = go[j];  // no shifted residual at 8x8 (checked by the launcher)
+                } else {
+                    go[j] = (unsigned)((OST * (px >> 4) * OW + OST * (px & 15)) * 256);
+                    rgo = SUB ? go[j] : (unsigned)((((px >> 4) >> rs) * (G::W >> rs) + ((px & 15) >> rs)) * 256);
+                }
                 rr[j] = f32x4{0.f, 0.f, 0.f, 0.f};
-                if (has_resid && (G::IPT == 1 || (j >> 2) < nimg)) rr[j] = *reinterpret_cast<const f32x4*>(resid + tb + go[j]);
+                if (has_resid && (G::IPT == 1 || (j >> 2) < nimg)) rr[j] = *reinterpret_cast<const f32x4*>(resid + rtb + rgo);
                 dv[j] = *reinterpret_cast<const f32x4*>(hbuf + px * 512 + ((chq ^ (px & 7)) << 4));
             }
 #pragma unroll
@@ -368,9 +399,10 @@ __global__ __launch_bounds__(X3_NTHR) void conv3_x3ws_kernel(const ConvArgs a, c
         for (int k = 0; k < G::IPT; ++k) {
             ssum[k] += __shfl_xor(ssum[k], 32);
             ssq[k] += __shfl_xor(ssq[k], 32);
-            // one statistics slot per (tile, producer wave) and image: [n][TPI * 4][64 quads] (8x8: [n][4][64])
-            if (a.stats && psub == 0 && k < nimg)
-                a.stats[(((size_t)(n + k) * G::TPI + slot) * 4 + pw) * 64 + half * 32 + chq] = make_float2(ssum[k], ssq[k]);
+            // one statistics slot per (tile, producer wave) and image: [n][TPI * 4][64 quads] (8x8: [n][4][64]; SUB: four
+            // phases per source tile)
+            const size_t sl = SUB ? ((size_t)(n + k) * G::TPI + slot) * 4 + ph : (size_t)(n + k) * G::TPI + slot;
+            if (a.stats && psub == 0 && k < nimg) a.stats[(sl * 4 + pw) * 64 + half * 32 + chq] = make_float2(ssum[k], ssq[k]);
         }
     };
 
@@ -427,6 +459,35 @@ __global__ void pack_conv_weights_x3ws_kernel(const float* __restrict__ w, __bf1
     }
 }
 
+// RES_SUBPIX: packed[phase][n16][step][tap4][part][lane][j], the merged 2x2 kernel of phase (py, px) = (phase >> 1, phase & 1):
+// tap (ty, tx) is the fp32 sum, rows then columns in ascending order, of W[..][ky][kx] over ky in R(py, ty), kx in R(px, tx) with
+// R(0,0) = {0}, R(0,1) = {1,2}, R(1,0) = {0,1}, R(1,1) = {2}; the sum is split into hi / lo as above.
+__global__ void pack_conv_weights_x3sub_kernel(const float* __restrict__ w, __bf16* __restrict__ out, int cout, int cin) {
+    const size_t total = (size_t)16 * cout * cin;
+    const int nstep = cin / X3_KC, ng = cout / 16;
+    for (size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (size_t)gridDim.x * blockDim.x) {
+        size_t t = idx;
+        const int j = t % 8; t /= 8;
+        const int lane = t % 64; t /= 64;
+        const int tap = t % 4; t /= 4;
+        const int step = t % nstep; t /= nstep;
+        const int n16 = t % ng; t /= ng;
+        const int py = (int)t >> 1, px = (int)t & 1, ty = tap >> 1, tx = tap & 1;
+        const int co = n16 * 16 + (lane & 15);
+        const int ci = step * X3_KC + 8 * (lane >> 4) + j;
+        const int ky0 = py ? 2 * ty : ty, ky1 = py ? ty + 1 : 2 * ty;  // inclusive range of merged rows
+        const int kx0 = px ? 2 * tx : tx, kx1 = px ? tx + 1 : 2 * tx;
+        const float* wp = w + ((size_t)co * cin + ci) * 9;
+        float v = 0.f;
+        for (int ky = ky0; ky <= ky1; ++ky)
+            for (int kx = kx0; kx <= kx1; ++kx) v += wp[ky * 3 + kx];
+        const __bf16 hi = (__bf16)v;
+        const size_t o = (idx / 512) * 1024 + (idx % 512);
+        out[o] = hi;
+        out[o + 512] = (__bf16)(v - (float)hi);
+    }
+}
+
 int g_x3_cus[16] = {};
 
 template <int RES, int LOGW, int PRO>
@@ -447,7 +508,7 @@ int launch_x3_one(const ConvArgs& a, hipStream_t stream, bool prepare_only) {
         g_x3_cus[dev] = n;
     }
     if (prepare_only) return 0;
-    const int ntiles = (a.B * G::TPI + G::IPT - 1) / G::IPT;
+    const int ntiles = (a.B * G::TPI + G::IPT - 1) / G::IPT * (RES == RES_SUBPIX ? 4 : 1);
     const int grid = ntiles < g_x3_cus[dev] ? ntiles : g_x3_cus[dev];
     hipLaunchKernelGGL(kern, dim3(grid), dim3(X3_NTHR), X3_LDS, stream, a, ntiles);
     return (int)hipGetLastError();
@@ -455,8 +516,12 @@ int launch_x3_one(const ConvArgs& a, hipStream_t stream, bool prepare_only) {
 
 }  // namespace
 
-// statistics slots per image written by this kernel: one per (tile, producer wave)
-int conv_x3ws_stat_slots(int W) { return (W == 32 ? X3Geom<5>::TPI : W == 16 ? X3Geom<4>::TPI : X3Geom<3>::TPI) * 4; }
+// statistics slots per image written by this kernel for an output of width W: one per (tile, producer wave); RES_SUBPIX cuts
+// its tiles from the half-width source, four phases each
+int conv_x3ws_stat_slots(int W, int res) {
+    if (res == RES_SUBPIX) return (W == 32 ? X3Geom<4>::TPI : X3Geom<3>::TPI) * 16;
+    return (W == 32 ? X3Geom<5>::TPI : W == 16 ? X3Geom<4>::TPI : X3Geom<3>::TPI) * 4;
+}
 
 bool conv_x3ws_shape_ok(int cout, int cin, int res) {
     return cout == 256 && (res == 32 || res == 16 || res == 8) && (cin % X3_KC) == 0 && cin / X3_KC >= 4;
@@ -466,13 +531,22 @@ bool conv_x3ws_supported(int ks, int pro, int res, int outmode, const ConvArgs& 
     const int cin = a.C1 + a.C2;
     const size_t src_bytes = (size_t)a.B * a.Hs * a.Ws * (size_t)(a.C1 > a.C2 ? a.C1 : a.C2) * 4;
     if (src_bytes >= (1ull << 32)) return false;  // the staged loads use 32-bit byte offsets into each source tensor
+    if (res == RES_SUBPIX)  // a.wpack_ws: the per-phase merged weights (launch_pack_conv_weights_x3sub)
+        return ks == 3 && outmode == OUT_NHWC && pro == PRO_GN_SILU && a.ab && a.H == a.W && a.Hs == a.Ws && a.H == 2 * a.Hs && (a.Ws == 16 || a.Ws == 8) &&
+               conv_x3ws_shape_ok(a.Cout, cin, a.Ws) && (a.C1 % X3_KC) == 0 && a.wpack_ws && !a.rshift;
     if (ks != 3 || outmode != OUT_NHWC || a.H != a.W || !conv_x3ws_shape_ok(a.Cout, cin, a.W) || (a.C1 % X3_KC) || !a.wpack_ws) return false;
     if (a.W == 8 && res != RES_NONE) return false;
+    // the residual of a half-resolution tensor: conv1 of an up block (16x16 / 32x32 output, no resample of its own)
+    if (a.rshift && (a.rshift != 1 || !a.resid || a.W == 8 || res != RES_NONE)) return false;
     if (pro == PRO_NONE) return res == RES_NONE && a.Hs == a.H && a.Ws == a.W;
     return pro == PRO_GN_SILU && (res == RES_NONE || res == RES_UP) && a.ab != nullptr;
 }
 
 int launch_conv_x3ws(int res, const ConvArgs& a, hipStream_t stream, bool prepare_only, int pro) {
+    if (res == RES_SUBPIX) {
+        if (pro != PRO_GN_SILU || (a.Ws != 16 && a.Ws != 8)) return (int)hipErrorInvalidValue;
+        return a.Ws == 16 ? launch_x3_one<RES_SUBPIX, 4, PRO_GN_SILU>(a, stream, prepare_only) : launch_x3_one<RES_SUBPIX, 3, PRO_GN_SILU>(a, stream, prepare_only);
+    }
     if (pro == PRO_NONE || a.W == 8) {
         if (res != RES_NONE) return (int)hipErrorInvalidValue;
         if (a.W == 8)
@@ -489,5 +563,12 @@ int launch_pack_conv_weights_x3ws(const float* w_oihw, void* wpack_ws, int cout,
     const size_t total = (size_t)cout * cin * 9;
     const int grid = (int)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096);
     hipLaunchKernelGGL(pack_conv_weights_x3ws_kernel, dim3(grid), dim3(256), 0, stream, w_oihw, (__bf16*)wpack_ws, cout, cin);
+    return (int)hipGetLastError();
+}
+
+int launch_pack_conv_weights_x3sub(const float* w_oihw, void* wpack_sub, int cout, int cin, hipStream_t stream) {
+    const size_t total = (size_t)16 * cout * cin;
+    const int grid = (int)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096);
+    hipLaunchKernelGGL(pack_conv_weights_x3sub_kernel, dim3(grid), dim3(256), 0, stream, w_oihw, (__bf16*)wpack_sub, cout, cin);
     return (int)hipGetLastError();
 }

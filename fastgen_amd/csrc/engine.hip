@@ -63,6 +63,7 @@ struct Block {
     // packed weights (owned device memory, compute dtype)
     void *p_conv0 = nullptr, *p_conv1 = nullptr, *p_skip = nullptr, *p_qkv = nullptr, *p_proj = nullptr;
     void *p_conv0_ws = nullptr, *p_conv1_ws = nullptr;  // conv_ws.hip layout, where that kernel applies
+    void* p_conv0_sub = nullptr;  // bf16x3 up blocks: conv0 merged per output phase (conv_ws3.hip, RES_SUBPIX)
     int tap = -1;  // index among the encoder's `block3` outputs (feature taps), or -1
     float* qkv_bias = nullptr;  // [3C] permuted to q|k|v
     void* p_aux = nullptr;      // K_AUX_CONV: weights packed for the MFMA output head
@@ -108,6 +109,7 @@ struct Workspace {
     float2 *ab0, *ab1, *ab2;
     float2 *mr0 = nullptr, *mr1 = nullptr, *mr2 = nullptr;  // {mean, rstd} of norm0 / norm1 / norm2, kept when a backward pass follows
     void* a1d = nullptr;   // kept (training) forward: where the block's conv1 operand (after dropout, if on) goes
+    bool infer = false;    // inference forward (no backward or tangent pass reads its intermediates): up blocks may run at the source resolution
     DropArgs drop;         // ... and its dropout parameters (p == 0: off)
     std::vector<Act> skip;  // encoder outputs
     Act xa, xb, h, xattn;
@@ -794,7 +796,20 @@ int run_block(fg_edm* h, const Block& b, const Act& x1, int c1, const Act& x2, i
     a.ab = w.ab0; a.wpack = b.p_conv0; a.wpack_ws = b.p_conv0_ws; a.bias = h->P(b.conv0_b);
     a.temb = temb + b.temb_off; a.temb_stride = h->temb_total;
     a.resid = nullptr; a.scale = 1.0f; a.out = w.h.p; a.Cout = b.cout; a.stats = w.h.st;
-    if (b.down && !c2) {
+    // bf16x3 inference, up blocks: conv0 as four 2x2 convs on the source (5/9 of the MFMA work of the replicated 3x3 is redundant)
+    // and the 1x1 skip once per source pixel (it commutes with nearest replication); conv1 then reads its residual at (y >> 1, x >> 1)
+    const bool x3_up = b.up && w.infer && !w.a1d && h->cmode == FG_DTYPE_BF16X3 && conv_ws_enabled();
+    bool sub0 = false;
+    if (x3_up && conv_subpix_mode() == 2 && b.p_conv0_sub) {
+        ConvArgs p = a;
+        p.wpack_ws = b.p_conv0_sub;
+        sub0 = conv_x3ws_supported(3, PRO_GN_SILU, RES_SUBPIX, OUT_NHWC, p);
+    }
+    if (sub0) {
+        a.wpack_ws = b.p_conv0_sub;
+        w.h.slots = conv_launch_stat_slots(h->cmode, 3, PRO_GN_SILU, RES_SUBPIX, OUT_NHWC, a);
+        HIP_TRY(conv_launch(h, 3, PRO_GN_SILU, RES_SUBPIX, OUT_NHWC, a, s));
+    } else if (b.down && !c2) {
         // pooled silu(norm0(x)) written once by a small pass (4x less transform work than pooling inside the conv)
         HIP_TRY(launch_gn_silu_pool(h->dtype, x1.p, w.ab0, w.pool, B, b.res_out, b.res_out, c1, s));
         a.src1 = w.pool; a.Hs = a.Ws = b.res_out; a.ab = nullptr;
@@ -804,23 +819,31 @@ int run_block(fg_edm* h, const Block& b, const Act& x1, int c1, const Act& x2, i
         w.h.slots = conv_launch_stat_slots(h->cmode, 3, PRO_GN_SILU, res_mode, OUT_NHWC, a);
         HIP_TRY(conv_launch(h, 3, PRO_GN_SILU, res_mode, OUT_NHWC, a, s));
     }
+    ConvArgs d{};
+    d.src1 = w.h.p; d.C1 = b.cout; d.Hs = d.Ws = d.H = d.W = b.res_out; d.B = B;
+    d.ab = w.ab1; d.wpack = b.p_conv1; d.wpack_ws = b.p_conv1_ws; d.bias = h->P(b.conv1_b);
+    d.scale = kSkipScale; d.Cout = b.cout;
     // skip path
     const void* resid = x1.p;
     if (b.has_skip) {
+        bool low = false;  // conv1 must be on the kernel that knows the shifted residual
+        if (x3_up && conv_subpix_mode() >= 1) {
+            ConvArgs p = d;
+            p.resid = w.sbuf; p.rshift = 1;
+            low = conv_x3ws_supported(3, PRO_GN_SILU, RES_NONE, OUT_NHWC, p);
+        }
         ConvArgs k{};
         k.src1 = x1.p; k.src2 = c2 ? x2.p : nullptr; k.C1 = c1; k.C2 = c2;
-        k.Hs = k.Ws = b.res_in; k.H = k.W = b.res_out; k.B = B;
+        k.Hs = k.Ws = b.res_in; k.H = k.W = low ? b.res_in : b.res_out; k.B = B;
         k.wpack = b.p_skip; k.bias = h->P(b.skip_b); k.scale = 1.0f; k.out = w.sbuf; k.Cout = b.cout;
-        HIP_TRY(conv_launch(h, 1, PRO_NONE, res_mode, OUT_NHWC, k, s));
+        HIP_TRY(conv_launch(h, 1, PRO_NONE, low ? RES_NONE : res_mode, OUT_NHWC, k, s));
         resid = w.sbuf;
+        d.rshift = low ? 1 : 0;
     }
     // x = (conv1(silu(norm1(h))) + skip) * sqrt(.5)
     HIP_TRY(launch_gn_finalize(w.h.st, b.cout, w.h.slots, nullptr, 0, 0, h->P(b.norm1_w), h->P(b.norm1_b), kBlockEps, w.ab1, B, hw, s, w.mr1));
     Act& x_mid = b.attn ? w.xattn : out;
-    ConvArgs d{};
-    d.src1 = w.h.p; d.C1 = b.cout; d.Hs = d.Ws = d.H = d.W = b.res_out; d.B = B;
-    d.ab = w.ab1; d.wpack = b.p_conv1; d.wpack_ws = b.p_conv1_ws; d.bias = h->P(b.conv1_b);
-    d.resid = resid; d.scale = kSkipScale; d.out = x_mid.p; d.Cout = b.cout; d.stats = x_mid.st;
+    d.resid = resid; d.out = x_mid.p; d.stats = x_mid.st;
     if (w.a1d) {
         // kept (training) forward: the operand silu(norm1(h)) [* keep with dropout, EDM/network.py:283-284] is materialised once —
         // the backward's weight gradient contracts with the same tensor — and the conv runs without a prologue
@@ -877,6 +900,7 @@ int run_forward(fg_edm* h, const float* x_t, const double* t, int t_stride, cons
     int rc = run_mapping(h, labels, B, w, s);
     if (rc) return rc;
     w.drop = DropArgs{};
+    w.infer = ts == nullptr;
     if (ts && h->dropout_p > 0.f) w.drop.p = h->dropout_p, w.drop.seed = h->dropout_seed;  // training forwards only
     // encoder
     const Act none;
@@ -959,6 +983,8 @@ int ensure_device_state(fg_edm* h) {
             return rc;
         if ((x3 ? conv_x3ws_shape_ok(b->cout, b->cout, b->res_out) : conv_ws_shape_ok(h->cmode, b->cout, b->cout, b->res_out)) &&
             (rc = h->alloc(&b->p_conv1_ws, conv_pack_elems(b->cout, b->cout, 3) * tsz)))
+            return rc;
+        if (x3 && b->up && conv_x3ws_shape_ok(b->cout, b->cin, b->res_in) && (rc = h->alloc(&b->p_conv0_sub, conv_pack_elems(b->cout, b->cin, 4) * 4)))
             return rc;
         if (b->has_skip && (rc = h->alloc(&b->p_skip, conv_pack_elems(b->cout, b->cin, 1) * tsz))) return rc;
         if (b->attn) {
@@ -1085,6 +1111,7 @@ int fg_edm_pack_weights(fg_edm* h, void* stream) {
         HIP_TRY(launch_pack_conv_weights(h->cmode, h->P(b->conv1_w), b->p_conv1, b->cout, b->cout, 3, 0, s));
         if (h->cmode == FG_DTYPE_BF16X3) {
             if (b->p_conv0_ws) HIP_TRY(launch_pack_conv_weights_x3ws(h->P(b->conv0_w), b->p_conv0_ws, b->cout, b->cin, s));
+            if (b->p_conv0_sub) HIP_TRY(launch_pack_conv_weights_x3sub(h->P(b->conv0_w), b->p_conv0_sub, b->cout, b->cin, s));
             if (b->p_conv1_ws) HIP_TRY(launch_pack_conv_weights_x3ws(h->P(b->conv1_w), b->p_conv1_ws, b->cout, b->cout, s));
         } else {
             if (b->p_conv0_ws) HIP_TRY(launch_pack_conv_weights_ws(h->P(b->conv0_w), b->p_conv0_ws, b->cout, b->cin, s));
@@ -1352,6 +1379,7 @@ int fg_edm_run_block(fg_edm* h, int index, const float* x1, int c1, const float*
         HIP_TRY(launch_to_act(h->dtype, x2, w.cvt2, (int64_t)npix_in * c2, s));
         a2.p = w.cvt2;
     }
+    w.infer = true;
     int rc = run_block(h, b, a1, c1, a2, c2, w.temb, w.xa, batch, w, s);
     if (rc) return rc;
     HIP_TRY(launch_from_act(h->dtype, w.xa.p, out, (int64_t)npix_out * b.cout, s));

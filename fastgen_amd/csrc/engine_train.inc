@@ -127,6 +127,7 @@ int block_backward(fg_edm* h, const Block& b, const Act& a1, int c1, const Act& 
         w.mr0 = q.mr0;
         w.mr1 = q.mr1;
         w.mr2 = q.mr2;
+        w.infer = false;  // the backward below reads this forward's intermediates at the block's own launches
         rc = run_block(h, b, a1, c1, a2, c2, temb, w.xa, B, w, s);
         w.mr0 = w.mr1 = w.mr2 = nullptr;
         if (rc) return rc;
