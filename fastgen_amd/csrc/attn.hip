@@ -331,8 +331,21 @@ constexpr int X3_KP = 272, X3_VP = 136;
 constexpr int X3_PLANE = 64 * X3_KP;  // = 128 * X3_VP
 constexpr int X3_BUF = 2 * X3_PLANE;  // hi + lo
 
+// MRG (inference blocks whose weights were merged at pack time, engine.hip): the keys are the block's normalised input itself,
+// k = a * x_mid + b with the norm2 coefficients `ab` applied on the way into LDS; q is q' = (Wk^T Wq) xn + Wk^T bq and vt is
+// v'^T = ((Wp Wv) xn + Wp bv)^T, so that P v' is already the projected output.  The store then finishes the block,
+// out = (o + bp + x_mid) * scale, and leaves the GroupNorm partial sums of `out` in `stats` [n][8 slots][64 quads], one slot per wave.
+struct AttnMerge {
+    const float2* ab;   // [B][256] norm2 coefficients of x_mid (= k)
+    const float* bp;    // [256] proj bias
+    float2* stats;      // [B][8][64] or nullptr
+    float scale;
+};
+
+template <bool MRG>
 __global__ __launch_bounds__(256, 2) void attention_x3_lds_kernel(const float* __restrict__ q, const float* __restrict__ k,
-                                                                  const float* __restrict__ vt, float* __restrict__ out, int B) {
+                                                                  const float* __restrict__ vt, float* __restrict__ out, int B,
+                                                                  AttnMerge mg) {
     constexpr int Tn = 256, D = 256;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -342,6 +355,12 @@ __global__ __launch_bounds__(256, 2) void attention_x3_lds_kernel(const float* _
 
     auto stage_k = [&](int s, char* buf) {  // step s = 4 * dim half + key tile: 64 keys x 128 dims, 1024 8-element chunks
         const float* src = k + ((size_t)n * Tn + (s & 3) * 64) * D + (s >> 2) * 128;
+        f32x4 cf[4];  // MRG: {a, b} of this thread's 8 channels (its chunk column tid & 15 is the same for every i)
+        if constexpr (MRG) {
+            const f32x4* cp = reinterpret_cast<const f32x4*>(mg.ab + (size_t)n * D + (s >> 2) * 128 + (tid & 15) * 8);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) cf[j] = cp[j];
+        }
 #pragma unroll
         for (int b2 = 0; b2 < 2; ++b2) {
 #pragma unroll
@@ -349,6 +368,10 @@ __global__ __launch_bounds__(256, 2) void attention_x3_lds_kernel(const float* _
                 const int idx = tid + 256 * i, row = idx >> 4, c = idx & 15;
                 float x[8];
                 widen8(load_frag(src + (size_t)row * D + c * 8), x);
+                if constexpr (MRG) {
+#pragma unroll
+                    for (int j = 0; j < 8; ++j) x[j] = fmaf(x[j], cf[j >> 1][2 * (j & 1)], cf[j >> 1][2 * (j & 1) + 1]);
+                }
                 bf16x8 hi, lo;
                 split8(x, hi, lo);
                 *reinterpret_cast<bf16x8*>(buf + row * X3_KP + c * 16) = hi;
@@ -476,15 +499,89 @@ __global__ __launch_bounds__(256, 2) void attention_x3_lds_kernel(const float* _
         __syncthreads();
         __builtin_amdgcn_sched_barrier(0);
         if ((s & 3) == 3) {
+            if constexpr (MRG) {
+                const float* xbase = k + ((size_t)n * Tn + q0) * D + r;  // the residual: this query's row of x_mid
 #pragma unroll
-            for (int d = 0; d < 4; ++d)
+                for (int d = 0; d < 4; ++d) {
+                    const int col = ((s >> 2) * 4 + d) * 32;
+                    const float bias = mg.bp[col + r];
+                    float sv = 0.f, qv = 0.f;
 #pragma unroll
-                for (int i = 0; i < 16; ++i) obase[(size_t)acc_row(i, h) * D + ((s >> 2) * 4 + d) * 32] = o[d][i];
+                    for (int i = 0; i < 16; ++i) {
+                        const size_t off = (size_t)acc_row(i, h) * D + col;
+                        const float v = (o[d][i] + bias + xbase[off]) * mg.scale;
+                        obase[off] = v;
+                        sv += v;
+                        qv += v * v;
+                    }
+                    if (mg.stats) {  // this wave's 32 queries x channel quad (col + r) / 4: the other row half, then the quad's 4 lanes
+                        sv += __shfl_xor(sv, 32), qv += __shfl_xor(qv, 32);
+                        sv += __shfl_xor(sv, 1), qv += __shfl_xor(qv, 1);
+                        sv += __shfl_xor(sv, 2), qv += __shfl_xor(qv, 2);
+                        if (h == 0 && (r & 3) == 0)
+                            mg.stats[((size_t)n * 8 + (blockIdx.x & 1) * 4 + wave) * (D / 4) + ((col + r) >> 2)] = make_float2(sv, qv);
+                    }
+                }
+            } else {
+#pragma unroll
+                for (int d = 0; d < 4; ++d)
+#pragma unroll
+                    for (int i = 0; i < 16; ++i) obase[(size_t)acc_row(i, h) * D + ((s >> 2) * 4 + d) * 32] = o[d][i];
+            }
         }
     }
 }
 
+// Pack-time merge of a single-head block's weights (C = head dim = channels), fp64 accumulation from the bound fp32 parameters,
+// one rounding to fp32.  qkv_w [3C][C] and qkv_b [3C] in the reference's row order c * 3 + plane (q, k, v), proj_w [C][C]:
+//   rows 0..C-1   M'[o][i] = sum_c Wk[c][o] Wq[c][i],  cq[o] = sum_c Wk[c][o] bq[c]   (logits q'_i . xn_j; q_i . bk is constant per row)
+//   rows C..2C-1  Mv[o][i] = sum_c Wp[o][c] Wv[c][i],  cv[o] = sum_c Wp[o][c] bv[c]   (rows of P sum to 1)
+__global__ void attn_merge_weights_kernel(const float* __restrict__ qkv_w, const float* __restrict__ qkv_b, const float* __restrict__ proj_w,
+                                          float* __restrict__ w_out, float* __restrict__ b_out, int C) {
+    const int o = blockIdx.x % C;
+    const bool val = blockIdx.x >= C;  // the value half
+    for (int i = threadIdx.x; i <= C; i += blockDim.x) {  // i == C: the bias column
+        double acc = 0.0;
+        for (int c = 0; c < C; ++c) {
+            const double l = val ? proj_w[(size_t)o * C + c] : qkv_w[(size_t)(3 * c + 1) * C + o];
+            const int row = 3 * c + (val ? 2 : 0);
+            acc += l * (double)(i < C ? qkv_w[(size_t)row * C + i] : qkv_b[row]);
+        }
+        if (i < C)
+            w_out[(size_t)blockIdx.x * C + i] = (float)acc;
+        else
+            b_out[blockIdx.x] = (float)acc;
+    }
+}
+
+// dynamic-LDS cap of one instantiation, once per device (never inside stream capture: the prepare-only calls do it up front)
+template <bool MRG>
+int x3_lds_prepare() {
+    static bool done[16] = {};
+    const int dev = fg_device_slot();
+    if (dev < 0) return (int)hipErrorInvalidDevice;
+    if (!done[dev]) {
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(attention_x3_lds_kernel<MRG>), hipFuncAttributeMaxDynamicSharedMemorySize, 2 * X3_BUF);
+        if (e != hipSuccess) return (int)e;
+        done[dev] = true;
+    }
+    return 0;
+}
+
 }  // namespace
+
+int launch_attn_merge_weights(const float* qkv_w, const float* qkv_b, const float* proj_w, float* w_out, float* b_out, int C, hipStream_t s) {
+    hipLaunchKernelGGL(attn_merge_weights_kernel, dim3(2 * C), dim3(256), 0, s, qkv_w, qkv_b, proj_w, w_out, b_out, C);
+    return (int)hipGetLastError();
+}
+
+int launch_attention_merged(const float* qm, const float* x_mid, const float2* ab, const float* vmt, const float* bp, float scale, float* out,
+                            float2* stats, int B, hipStream_t s) {
+    const int rc = x3_lds_prepare<true>();
+    if (rc || !qm) return rc;  // qm == nullptr: prepare-only call
+    hipLaunchKernelGGL(attention_x3_lds_kernel<true>, dim3(B * 2), dim3(256), 2 * X3_BUF, s, qm, x_mid, vmt, out, B, AttnMerge{ab, bp, stats, scale});
+    return (int)hipGetLastError();
+}
 
 int launch_attention(int dtype, const void* q, const void* k, const void* vt, void* out, int B, int T, hipStream_t s) {
     if (T != 256 && T != 64) return (int)hipErrorInvalidValue;
@@ -510,16 +607,10 @@ int launch_attention(int dtype, const void* q, const void* k, const void* vt, vo
         return !(e && e[0] == '0');
     }();
     if (dtype == 2 && nt == 8 && x3_lds) {
-        static bool x3_attr_dev[16] = {};
-        const int dev = fg_device_slot();
-        if (dev < 0) return (int)hipErrorInvalidDevice;
-        if (!x3_attr_dev[dev]) {
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(attention_x3_lds_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 2 * X3_BUF);
-            if (e != hipSuccess) return (int)e;
-            x3_attr_dev[dev] = true;
-        }
-        if (!q) return 0;
-        hipLaunchKernelGGL(attention_x3_lds_kernel, dim3(B * 2), block, 2 * X3_BUF, s, (const float*)q, (const float*)k, (const float*)vt, (float*)out, B);
+        const int rc = x3_lds_prepare<false>();
+        if (rc || !q) return rc;
+        hipLaunchKernelGGL(attention_x3_lds_kernel<false>, dim3(B * 2), block, 2 * X3_BUF, s, (const float*)q, (const float*)k, (const float*)vt, (float*)out, B,
+                           AttnMerge{});
         return (int)hipGetLastError();
     }
     if (!q) return 0;  // prepare-only call: nothing to set for the direct-from-global kernels

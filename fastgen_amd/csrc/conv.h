@@ -28,6 +28,7 @@ struct ConvArgs {
     float2* stats;
     int dbg;  // ablation flags for scripts/conv_ablate.py (0 in production): 1 no staging, 2 no weight refill, 4 no epilogue, 8 no MFMA
     // OUT_QKV: compute-dtype planes q,k: [B][HW][256]; vt: [B][256][HW]
+    // OUT_QV (Cout = 512, bf16x3, 16x16): channels 0..255 to q_out [B][HW][256], channels 256..511 to vt_out [B][256][HW]
     void* q_out;
     void* k_out;
     void* vt_out;
@@ -43,7 +44,7 @@ struct ConvArgs {
 enum { PRO_NONE = 0, PRO_GN = 1, PRO_GN_SILU = 2 };
 // RES_SUBPIX: RES_UP of a 3x3 conv evaluated as four 2x2 convs on the low-resolution source (conv_ws3.hip only)
 enum { RES_NONE = 0, RES_DOWN = 1, RES_UP = 2, RES_SUBPIX = 3 };
-enum { OUT_NHWC = 0, OUT_QKV = 1, OUT_TOK = 2, OUT_HEADS = 3 };
+enum { OUT_NHWC = 0, OUT_QKV = 1, OUT_TOK = 2, OUT_HEADS = 3, OUT_QV = 4 };
 
 // dtype: 0 fp32, 1 bf16 — also the storage type of every activation tensor (src1/src2/resid/out); 2 = split-bf16 arithmetic
 // (common.h bf16x3) on fp32 tensors.

@@ -145,6 +145,8 @@ __global__ __launch_bounds__(NTHR, 2) void conv_fused_kernel(const ConvArgs a) {
     // Token GEMMs (OUT_TOK / OUT_HEADS) take any Cout % 64 == 0: in the last 256-column tile the waves past Cout re-do the last valid
     // 64 columns (loads stay inside the packed weights) and skip the epilogue.
     constexpr bool TOKM = (OUTMODE == OUT_TOK || OUTMODE == OUT_HEADS);
+    constexpr bool QKM = (OUTMODE == OUT_QKV || OUTMODE == OUT_QV);  // 256-channel planes, the last one transposed
+    constexpr int QPLANES = (OUTMODE == OUT_QKV) ? 2 : 1;            // ... after this many [B][HW][256] planes (q, k | q')
     const int wcol0 = nblk * (128 * NT) + wave * (32 * NT);  // first output column of this wave
     const bool wactive = !TOKM || wcol0 < a.Cout;
     const int wgroup = wactive ? nblk * (4 * NT) + wave * NT : a.Cout / 32 - NT;
@@ -397,8 +399,8 @@ __global__ __launch_bounds__(NTHR, 2) void conv_fused_kernel(const ConvArgs a) {
     if (!wactive) return;  // (no workgroup barrier below this point)
     // which plane of a head-split qkv projection this wave's 64 columns lie in (planes are multiples of 64 wide)
     const int hplane = (OUTMODE == OUT_HEADS) ? wcol0 / (a.heads * a.head_dim) : 0;
-    if (OUTMODE == OUT_NHWC || OUTMODE == OUT_TOK || (OUTMODE == OUT_QKV && nblk < 2) || (OUTMODE == OUT_HEADS && hplane < 2)) {
-        // NHWC tensor, or the q / k plane of a qkv projection ([B][HW][256]; OUT_HEADS: [B][heads][T][head_dim])
+    if (OUTMODE == OUT_NHWC || OUTMODE == OUT_TOK || (QKM && nblk < QPLANES) || (OUTMODE == OUT_HEADS && hplane < 2)) {
+        // NHWC tensor, or the q / k plane of a qkv projection (OUT_QV: the q' plane) ([B][HW][256]; OUT_HEADS: [B][heads][T][head_dim])
         // Transpose each 32-pixel x 64-channel accumulator slab through this wave's private LDS scratch (the A buffers
         // are dead after the last barrier) so that global traffic is row-contiguous: a lane owns one channel QUAD of one
         // pixel (16 B fp32 / 8 B bf16 per access), 16 lanes cover a pixel's 64 channels, 4 pixels per wave instruction.
@@ -411,7 +413,7 @@ __global__ __launch_bounds__(NTHR, 2) void conv_fused_kernel(const ConvArgs a) {
         char* ep = smem + wave * (32 * EP_PITCH);
         const int c4 = lane % QPW, prow = lane / QPW;
         const int co0 = nblk * (128 * NT) + wave * (32 * NT) + c4 * 4;
-        const bool qk = (OUTMODE == OUT_QKV);
+        const bool qk = QKM;
         const bool hd = (OUTMODE == OUT_HEADS);
         ST* out = reinterpret_cast<ST*>(qk ? (nblk == 0 ? a.q_out : a.k_out) : (hd ? (hplane == 0 ? a.q_out : a.k_out) : a.out));
         const ST* resid = (qk || hd) ? nullptr : reinterpret_cast<const ST*>(a.resid);
@@ -505,8 +507,8 @@ __global__ __launch_bounds__(NTHR, 2) void conv_fused_kernel(const ConvArgs a) {
                     a.stats[((size_t)n * G::TPI + slot) * (a.Cout >> 2) + (co0 >> 2)] = make_float2(sv, qv);
             }
         }
-    } else {  // the v^T plane of the qkv projection: [B][256][HW], four consecutive pixels per 8/16-byte store
-        static_assert(OUTMODE != OUT_QKV || NT == 2, "qkv epilogue assumes 64 channels per wave");
+    } else {  // the v^T plane of the qkv (OUT_QV: q' | v') projection: [B][256][HW], four consecutive pixels per 8/16-byte store
+        static_assert(!QKM || NT == 2, "qkv epilogue assumes 64 channels per wave");
         ST* vt = reinterpret_cast<ST*>(a.vt_out);
 #pragma unroll
         for (int nt = 0; nt < NT; ++nt) {
@@ -616,6 +618,12 @@ int launch_t(int ks, int pro, int res, int outmode, const ConvArgs& a, hipStream
         if (ks == 1 && pro == PRO_GN && res == RES_NONE) return launch_w<T, 1, PRO_GN, RES_NONE, OUT_QKV>(a, s);
         return (int)hipErrorInvalidValue;
     }
+    if (outmode == OUT_QV) {  // merged attention weights: the bf16x3 mode's 16x16 blocks only (engine.hip run_block)
+        if constexpr (std::is_same<T, bf16x3>::value) {
+            if (ks == 1 && pro == PRO_GN && res == RES_NONE && a.W == 16) return launch_one<T, 1, PRO_GN, RES_NONE, 4, OUT_QV>(a, s);
+        }
+        return (int)hipErrorInvalidValue;
+    }
     if (outmode == OUT_TOK || outmode == OUT_HEADS) {  // transformer GEMMs: 256 tokens per image as a 16x16 "image", 1x1 "conv"
         if (ks != 1 || pro != PRO_NONE || res != RES_NONE || a.W != 16) return (int)hipErrorInvalidValue;
         return outmode == OUT_TOK ? launch_one<T, 1, PRO_NONE, RES_NONE, 4, OUT_TOK>(a, s) : launch_one<T, 1, PRO_NONE, RES_NONE, 4, OUT_HEADS>(a, s);
@@ -675,6 +683,7 @@ int launch_conv_fused(int dtype, int ks, int pro, int res, int outmode, const Co
     if ((res == RES_UP || res == RES_SUBPIX) && (2 * a.Hs != a.H || 2 * a.Ws != a.W)) return (int)hipErrorInvalidValue;
     if (pro != PRO_NONE && !a.ab) return (int)hipErrorInvalidValue;
     if (outmode == OUT_QKV && (a.Cout != 768 || a.W > 16)) return (int)hipErrorInvalidValue;
+    if (outmode == OUT_QV && (a.Cout != 512 || a.W != 16 || dtype != 2 || !a.q_out || !a.vt_out)) return (int)hipErrorInvalidValue;
     if (conv_ws_enabled() && conv_ws_supported(dtype, ks, pro, res, outmode, a)) return launch_conv_ws(res, a, stream, false, pro);
     if (dtype == 2 && conv_ws_enabled() && conv_x3ws_supported(ks, pro, res, outmode, a)) return launch_conv_x3ws(res, a, stream, false, pro);
     if (res == RES_SUBPIX || a.rshift) return (int)hipErrorInvalidValue;  // conv_ws3.hip only: the caller checks conv_x3ws_supported first
@@ -722,6 +731,7 @@ int conv_prepare_all(int dtype) {
         }
         if (!rc) rc = dispatch_t(dtype, 3, PRO_NONE, RES_NONE, OUT_NHWC, a, nullptr);
         if (!rc && a.W <= 16) rc = dispatch_t(dtype, 1, PRO_GN, RES_NONE, OUT_QKV, a, nullptr);
+        if (!rc && a.W == 16 && dtype == 2) rc = dispatch_t(dtype, 1, PRO_GN, RES_NONE, OUT_QV, a, nullptr);
         if (!rc && a.W == 16) rc = dispatch_t(dtype, 1, PRO_NONE, RES_NONE, OUT_TOK, a, nullptr);
         if (!rc && a.W == 16) rc = dispatch_t(dtype, 1, PRO_NONE, RES_NONE, OUT_HEADS, a, nullptr);
     }

@@ -66,6 +66,9 @@ struct Block {
     void* p_conv0_sub = nullptr;  // bf16x3 up blocks: conv0 merged per output phase (conv_ws3.hip, RES_SUBPIX)
     int tap = -1;  // index among the encoder's `block3` outputs (feature taps), or -1
     float* qkv_bias = nullptr;  // [3C] permuted to q|k|v
+    // bf16x3 blocks with 256 tokens x 256 channels: [Wk^T Wq ; Wp Wv] (512 x 256) merged at pack time, and its bias [Wk^T bq ; Wp bv]
+    void* p_qv = nullptr;
+    float* qv_bias = nullptr;
     void* p_aux = nullptr;      // K_AUX_CONV: weights packed for the MFMA output head
     void* p_stem = nullptr;     // K_STEM: weights packed for the MFMA stem
 };
@@ -501,6 +504,7 @@ struct fg_edm : HandleBase {
     // owned device memory
     float* freqs = nullptr;      // [noise_ch/2]
     float* aff_w = nullptr;      // [temb_total][emb_ch]
+    float* qv_w = nullptr;       // [512][256] fp32 scratch of the attention weight merge (pack time only)
     float* aff_b = nullptr;      // [temb_total]
     SamplerCache sampler;  // fg_sampler_run
     // live timing of the dominant kernel (conv 3x3, no resample, 32x32 output): HIP events on the launch stream
@@ -780,6 +784,16 @@ int block_index(const fg_edm* h, const Block* b) {
     return -1;
 }
 
+// FASTGEN_AMD_ATTN_MERGE=0 keeps the q|k|v conv, attention and proj launches of the 16x16 bf16x3 attention blocks (A/B measurements);
+// read once.
+bool attn_merge_enabled() {
+    static const bool on = [] {
+        const char* e = getenv("FASTGEN_AMD_ATTN_MERGE");
+        return !(e && e[0] == '0');
+    }();
+    return on;
+}
+
 // One UNetBlock (EDM/network.py:274-299) as 5-10 kernel launches.  `out.st` receives the block output's statistics.
 int run_block(fg_edm* h, const Block& b, const Act& x1, int c1, const Act& x2, int c2, const float* temb, Act& out, int B,
               Workspace& w, hipStream_t s) {
@@ -859,6 +873,18 @@ int run_block(fg_edm* h, const Block& b, const Act& x1, int c1, const Act& x2, i
         HIP_TRY(launch_gn_finalize(x_mid.st, b.cout, x_mid.slots, nullptr, 0, 0, h->P(b.norm2_w), h->P(b.norm2_b), kBlockEps, w.ab2, B, hw, s, w.mr2));
         ConvArgs q{};
         q.src1 = x_mid.p; q.C1 = b.cout; q.Hs = q.Ws = q.H = q.W = b.res_out; q.B = B;
+        // bf16x3 inference, one head of 256 over 256 tokens: q' = (Wk^T Wq) xn + Wk^T bq and v' = (Wp Wv) xn + Wp bv from the merged
+        // weights; the keys are xn itself (q . bk is constant along a softmax row) and P v' is the projected output (rows of P sum
+        // to 1), so the attention kernel's store finishes the block: no k plane, no proj launch, no aout round trip
+        if (w.infer && !w.a1d && h->cmode == FG_DTYPE_BF16X3 && hw == 256 && b.cout == 256 && b.p_qv && attn_merge_enabled()) {
+            q.ab = w.ab2; q.wpack = b.p_qv; q.bias = b.qv_bias; q.scale = 1.0f; q.Cout = 2 * b.cout;
+            q.q_out = w.q; q.vt_out = w.vt;
+            HIP_TRY(conv_launch(h, 1, PRO_GN, RES_NONE, OUT_QV, q, s));
+            HIP_TRY(launch_attention_merged((const float*)w.q, (const float*)x_mid.p, w.ab2, (const float*)w.vt, h->P(b.proj_b), kSkipScale,
+                                            (float*)out.p, out.st, B, s));
+            out.slots = 8;  // one per wave of the attention kernel's two workgroups per image
+            return FG_OK;
+        }
         q.ab = w.ab2; q.wpack = b.p_qkv; q.bias = b.qkv_bias; q.scale = 1.0f; q.Cout = 3 * b.cout;
         q.q_out = w.q; q.k_out = w.k; q.vt_out = w.vt;
         HIP_TRY(conv_launch(h, 1, PRO_GN, RES_NONE, OUT_QKV, q, s));
@@ -991,6 +1017,11 @@ int ensure_device_state(fg_edm* h) {
             if ((rc = h->alloc(&b->p_qkv, conv_pack_elems(3 * b->cout, b->cout, 1) * tsz))) return rc;
             if ((rc = h->alloc(&b->p_proj, conv_pack_elems(b->cout, b->cout, 1) * tsz))) return rc;
             if ((rc = h->alloc((void**)&b->qkv_bias, sizeof(float) * 3 * b->cout))) return rc;
+            if (x3 && b->cout == 256 && b->res_out == 16) {
+                if ((rc = h->alloc(&b->p_qv, conv_pack_elems(2 * b->cout, b->cout, 1) * tsz))) return rc;
+                if ((rc = h->alloc((void**)&b->qv_bias, sizeof(float) * 2 * b->cout))) return rc;
+                if (!h->qv_w && (rc = h->alloc((void**)&h->qv_w, sizeof(float) * 2 * b->cout * b->cout))) return rc;
+            }
         }
     }
     for (Block& b : h->enc)
@@ -1009,6 +1040,8 @@ int ensure_device_state(fg_edm* h) {
     HIP_TRY(hipMemcpy(h->freqs, fr.data(), sizeof(float) * half, hipMemcpyHostToDevice));
     if (conv_prepare_all(h->cmode) != 0) return fail(FG_EHIP, "hipFuncSetAttribute(dynamic LDS) failed");
     if (launch_attention(h->cmode, nullptr, nullptr, nullptr, nullptr, 1, 256, nullptr) != 0) return fail(FG_EHIP, "attention prepare failed");
+    if (h->cmode == FG_DTYPE_BF16X3 && launch_attention_merged(nullptr, nullptr, nullptr, nullptr, nullptr, 0.f, nullptr, nullptr, 1, nullptr) != 0)
+        return fail(FG_EHIP, "attention prepare failed");
     h->device_ready = true;
     return FG_OK;
 }
@@ -1125,6 +1158,10 @@ int fg_edm_pack_weights(fg_edm* h, void* stream) {
             for (int plane = 0; plane < 3; ++plane)
                 HIP_TRY(hipMemcpy2DAsync(b->qkv_bias + plane * b->cout, sizeof(float), h->P(b->qkv_b) + plane,
                                          3 * sizeof(float), sizeof(float), b->cout, hipMemcpyDeviceToDevice, s));
+            if (b->p_qv) {  // the scratch is reused block after block: stream order keeps the merge and its packing paired
+                HIP_TRY(launch_attn_merge_weights(h->P(b->qkv_w), h->P(b->qkv_b), h->P(b->proj_w), h->qv_w, b->qv_bias, b->cout, s));
+                HIP_TRY(launch_pack_conv_weights(h->cmode, h->qv_w, b->p_qv, 2 * b->cout, b->cout, 1, 0, s));
+            }
         }
         HIP_TRY(hipMemcpyAsync(h->aff_w + (size_t)b->temb_off * h->emb_ch, h->P(b->aff_w),
                                sizeof(float) * (size_t)b->cout * h->emb_ch, hipMemcpyDeviceToDevice, s));

@@ -109,6 +109,12 @@ int launch_nchw_to_nhwc(const float* in, float* out, int B, int C, int HW, hipSt
 // q,k: [B][T][256], vt: [B][256][T], out [B][T][256]; dtype 0: fp32 tensors, exact fp32 products / 1: bf16 / 2: fp32 tensors,
 // split-bf16 products (FG_DTYPE_BF16X3).
 int launch_attention(int dtype, const void* q, const void* k, const void* vt, void* out, int B, int T, hipStream_t s);
+// bf16x3, T = 256, C = 256, weights merged at pack time: w_out [2C][C] = [Wk^T Wq ; Wp Wv], b_out [2C] = [Wk^T bq ; Wp bv] (fp64 sums)
+int launch_attn_merge_weights(const float* qkv_w, const float* qkv_b, const float* proj_w, float* w_out, float* b_out, int C, hipStream_t s);
+// out = (softmax_j(qm_i . xn_j / 16) vm + bp + x_mid) * scale with xn = ab.x * x_mid + ab.y; qm, x_mid, out [B][256][256] (token-major),
+// vmt [B][256 dims][256 tokens]; stats (nullable): GroupNorm partial sums of out, [B][8 slots][64 quads].  qm == nullptr: prepare only.
+int launch_attention_merged(const float* qm, const float* x_mid, const float2* ab, const float* vmt, const float* bp, float scale, float* out,
+                            float2* stats, int B, hipStream_t s);
 
 // MFMA output head (aux.hip): aux_conv(silu(aux_norm(x))) + EDM output preconditioning, res == 32.
 size_t aux_pack_elems(int C);
