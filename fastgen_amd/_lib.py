@@ -65,6 +65,10 @@ class fg_wan_sampler_config(ctypes.Structure):
     _fields_ = [("t_scale", c_double), ("context_noise", c_double), ("net_pred_flow", c_int), ("schedule", c_int), ("prefill_frames", c_int)]
 
 
+class fg_wan_guided_sampler_config(ctypes.Structure):
+    _fields_ = [("t_scale", c_double), ("context_noise", c_double), ("guidance", c_int)]
+
+
 # name -> (restype, argtypes); every symbol include/fastgen_amd.h declares
 SIGNATURES = {
     "fg_last_error": (c_char_p, []),
@@ -155,6 +159,11 @@ SIGNATURES = {
     "fg_wan_sampler_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int, c_int, c_int]),
     "fg_wan_sampler_run": (c_int, [c_void_p, POINTER(fg_wan_sampler_config), c_void_p, POINTER(c_double), c_int, c_int, POINTER(c_int), c_void_p,
                                    c_uint64, c_int, c_int, c_int, c_int, c_void_p, c_size_t, c_int, c_void_p]),
+    "fg_wan_guided_sampler_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int]),
+    "fg_wan_guided_sampler_run": (c_int, [c_void_p, POINTER(fg_wan_guided_sampler_config), c_void_p, POINTER(c_double), POINTER(c_double), c_int,
+                                          c_void_p, c_uint64, c_int, c_int, c_int, c_int, c_void_p, c_size_t, c_int, c_void_p]),
+    "fg_op_guided_multistep": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int64, c_void_p]),
+    "fg_wan_select_cache_tag": (c_int, [c_void_p, c_int]),
     "fg_wan_create": (c_int, [POINTER(fg_wan_config), POINTER(c_void_p)]),
     "fg_wan_destroy": (None, [c_void_p]),
     "fg_wan_num_params": (c_int, [c_void_p]),

@@ -1531,6 +1531,13 @@ int fg_edm_set_dropout(fg_edm* h, float p, uint64_t seed) {
     h->dropout_seed = seed;
     return FG_OK;
 }
+int fg_op_guided_multistep(const float* v, float* x, float* x2, float* x_last, float* m_prev, const double* tab, int guided, int first,
+                           int64_t total, void* stream) {
+    if (!v || !x || !x_last || !m_prev || !tab || total <= 0) return fail(FG_EINVAL, "fg_op_guided_multistep: bad argument");
+    HIP_TRY(launch_guided_multistep(v, x, x2, x_last, m_prev, tab, guided != 0, first != 0, total, (hipStream_t)stream));
+    return FG_OK;
+}
+
 int fg_op_dropout_mask(float* out, int64_t total, float p, uint32_t block_index, uint64_t seed, void* stream) {
     if (!out || total <= 0 || (total % 8)) return fail(FG_EINVAL, "fg_op_dropout_mask: bad argument");
     DropArgs d;

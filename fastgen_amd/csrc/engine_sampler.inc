@@ -290,3 +290,156 @@ int fg_wan_sampler_run(fg_wan* h, const fg_wan_sampler_config* sc, float* x, con
     // `net.clear_caches()` at the end of the loop (causvid.py:184): the next call starts from empty caches (and sets its text again)
     return fg_wan_clear_caches(h, s);
 }
+
+}  // extern "C" (reopened below)
+
+// ---- causal video DiT: the guided teacher sampler -----------------------------------------------------------------------------------
+namespace {
+
+struct WanGuidedWs {
+    float *xin, *v;          // the network's input [Be, C, f, H, W] (guided: the chunk twice, rows [0, B) and [B, 2 B)) and its flow
+    float *xl, *mp, *eps;    // x_last, m_prev of the multistep solver and the cache call's noise, [B, C, f, H, W]
+    float* te;
+    double* sc;              // [steps + 1 timesteps | steps x 8 solver table | seed, offset as 2 x uint64]
+    void* net;
+    size_t net_bytes;
+};
+
+size_t wan_guided_plan(const fg_wan* h, int B, int stack, int fmax, int H, int W, int steps, Arena& A, WanGuidedWs& w) {
+    const size_t per = (size_t)B * h->cfg.in_channels * fmax * H * W;
+    w.xin = A.get<float>(per * stack);
+    w.v = A.get<float>(per * stack);
+    w.xl = A.get<float>(per);
+    w.mp = A.get<float>(per);
+    w.eps = A.get<float>(per);
+    w.te = A.get<float>((size_t)B * stack * fmax);
+    w.sc = A.get<double>(9 * (size_t)steps + 3);
+    w.net_bytes = fg_wan_workspace_bytes(h, B * stack, fmax, H, W);
+    w.net = A.take(w.net_bytes);
+    return (A.off + 255) & ~(size_t)255;
+}
+
+constexpr int kGuidedMaxSteps = 4096;  // a sanity bound on the table's size, not a property of the loop
+
+}  // namespace
+
+extern "C" {
+
+size_t fg_wan_guided_sampler_workspace_bytes(const fg_wan* h, int batch, int frames, int height, int width, int steps, int guidance) {
+    if (!h || batch <= 0 || frames <= 0 || height <= 0 || width <= 0 || (height & 1) || (width & 1) || steps < 1 || steps > kGuidedMaxSteps) return 0;
+    const int chunk = h->cfg.chunk_size, fmax = frames < chunk ? frames : chunk + frames % chunk;
+    Arena A;
+    A.dry = true;
+    WanGuidedWs w;
+    return wan_guided_plan(h, batch, guidance ? 2 : 1, fmax, height, width, steps, A, w);
+}
+
+int fg_wan_guided_sampler_run(fg_wan* h, const fg_wan_guided_sampler_config* sc, float* x, const double* t_list, const double* table, int steps,
+                              const float* eps, uint64_t seed, int batch, int frames, int height, int width, void* workspace,
+                              size_t workspace_bytes, int use_graph, void* stream) {
+    if (!h || !sc || !x || !t_list || !table) return fail(FG_EINVAL, "null argument");
+    if (steps < 1 || steps > kGuidedMaxSteps) return fail(FG_EINVAL, "steps must be in [1, %d]", kGuidedMaxSteps);
+    if (!(sc->t_scale > 0.0)) return fail(FG_EINVAL, "t_scale must be positive");
+    if (sc->guidance != 0 && sc->guidance != 1) return fail(FG_EINVAL, "guidance must be 0 (batch B) or 1 (stacked batch 2 B)");
+    if (batch <= 0 || frames <= 0 || frames > h->cfg.total_num_frames || height <= 0 || width <= 0 || (height & 1) || (width & 1) || !workspace ||
+        (((uintptr_t)workspace) & 255))
+        return fail(FG_EINVAL, "bad batch / frames (<= total_num_frames = %d) / size / workspace", h->cfg.total_num_frames);
+    const float cn32 = (float)sc->context_noise;  // (t_cache is a tensor of the latents' dtype, network_causal.py:1268)
+    if (!(sc->context_noise >= 0.0) || (double)cn32 > 0.999) return fail(FG_EINVAL, "context_noise outside [0, 0.999]");
+    for (int i = 0; i < steps; ++i)
+        if (!(t_list[i] >= 0.0 && t_list[i] <= 1.0)) return fail(FG_EINVAL, "t_list[%d] = %g outside [0, 1]", i, t_list[i]);
+    for (int i = 0; i < 8 * steps; ++i)
+        if (!std::isfinite(table[i])) return fail(FG_EINVAL, "table[%d][%d] is not finite", i / 8, i % 8);
+    if (h->tag != 0) return fail(FG_EINVAL, "the guided loop runs on cache tag 0 (call fg_wan_select_cache_tag(h, 0))");
+    const int guided = sc->guidance, stack = guided ? 2 : 1, Be = batch * stack;
+    const int chunk = h->cfg.chunk_size, fmax = frames < chunk ? frames : chunk + frames % chunk;
+    std::vector<std::pair<int, int>> chunks;
+    wan_chunks(frames, chunk, chunks);
+    Arena A;
+    A.base = (char*)workspace;
+    WanGuidedWs w;
+    const size_t need = wan_guided_plan(h, batch, stack, fmax, height, width, steps, A, w);
+    if (need > workspace_bytes) return fail(FG_ENOMEM, "workspace too small: need %zu bytes, got %zu", need, workspace_bytes);
+    if (!h->packed) return fail(FG_ENOTREADY, "weights are not packed (call fg_wan_pack_weights)");
+    if (h->text_B != Be)
+        return fail(FG_ENOTREADY, "no text condition for batch %d (call fg_wan_set_text%s)", Be, guided ? " with [cond; neg_cond]" : "");
+    hipStream_t s = (hipStream_t)stream;
+    int rc;
+    // as in fg_wan_sampler_run: `self.clear_caches()` of the loop's first lines (network_causal.py:1216) without a memset, the text stays
+    if ((rc = wan_ensure_caches(h, Be, height, width, s))) return rc;  // (allocation must not fall inside a capture)
+    h->stored_rows = 0;
+    // The step scalars do not fit the scalar ring: they go up from one pinned host copy of 9 steps + 3 doubles, on the caller's stream
+    // before any graph launch; the copy is rewritten only after the event behind its previous upload has completed.
+    const size_t nd = 9 * (size_t)steps + 3;
+    if (!h->pin_ev) HIP_TRY(hipEventCreateWithFlags(&h->pin_ev, hipEventDisableTiming));
+    if (h->pin_used) HIP_TRY(hipEventSynchronize(h->pin_ev));
+    if (h->pin_doubles < nd) {
+        if (h->pin) (void)hipHostFree(h->pin);
+        h->pin = nullptr, h->pin_doubles = 0;
+        HIP_TRY(hipHostMalloc((void**)&h->pin, sizeof(double) * nd));
+        h->pin_doubles = nd;
+    }
+    for (int i = 0; i < steps; ++i) h->pin[i] = t_list[i];
+    h->pin[steps] = 0.0;  // the cache-fill call's t
+    memcpy(h->pin + steps + 1, table, sizeof(double) * 8 * steps);
+    const uint64_t sd[2] = {seed, 0};
+    memcpy(h->pin + 9 * (size_t)steps + 1, sd, sizeof(sd));
+    HIP_TRY(hipMemcpyAsync(w.sc, h->pin, sizeof(double) * nd, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipEventRecord(h->pin_ev, s));
+    h->pin_used = true;
+    const double* tl = w.sc;
+    const double* tab = w.sc + steps + 1;
+    const uint64_t* seed_dev = (const uint64_t*)(w.sc + 9 * (size_t)steps + 1);
+    if (h->guided_graphs.size() < chunks.size()) h->guided_graphs.resize(chunks.size());
+
+    const int C = h->cfg.in_channels;
+    const int64_t hw = (int64_t)height * width, rows = (int64_t)batch * C, vid_pitch = (int64_t)frames * hw;
+    for (size_t ci = 0; ci < chunks.size(); ++ci) {
+        const int f0 = chunks[ci].first, f1 = chunks[ci].second, nf = f1 - f0;
+        const int64_t run = (int64_t)nf * hw, total = rows * run;
+        float* x2 = guided ? w.xin + total : nullptr;  // the unconditional rows of the stacked input
+        auto enqueue = [&](hipStream_t q) -> int {
+            int r;
+            HIP_TRY(launch_copy_rows(x + f0 * hw, vid_pitch, w.xin, run, run, rows, q));
+            if (x2) HIP_TRY(launch_copy_rows(x + f0 * hw, vid_pitch, x2, run, run, rows, q));
+            for (int i = 0; i < steps; ++i) {
+                HIP_TRY(launch_embed_times(tl, i, 0.0, -2, 0.0, sc->t_scale, 0, 0, 0, w.te, nullptr, Be * nf, q));
+                if ((r = wan_forward(h, w.xin, w.te, w.v, Be, nf, height, width, f0, 0, 0, w.net, w.net_bytes, q))) return r;
+                HIP_TRY(launch_guided_multistep(w.v, w.xin, x2, w.xl, w.mp, tab + 8 * (size_t)i, guided, i == 0, total, q));
+            }
+            HIP_TRY(launch_copy_rows(w.xin, run, x + f0 * hw, vid_pitch, run, rows, q));  // x[:, :, start:end] = x_next
+            // the cache-fill call on the finished chunk at t = 0, or re-noised to context_noise (:1263-1289); both halves hold the chunk
+            if (sc->context_noise > 0.0) {
+                if (eps) HIP_TRY(launch_copy_rows(eps + f0 * hw, vid_pitch, w.eps, run, run, rows, q));
+                else HIP_TRY(launch_randn(w.eps, total, 0, (uint64_t)ci, seed_dev, q));
+                HIP_TRY(launch_forward_process(w.xin, w.eps, (double)cn32, nullptr, 0, FG_SCHEDULE_RF, w.xin, total, q));
+                if (x2) HIP_TRY(hipMemcpyAsync(x2, w.xin, sizeof(float) * total, hipMemcpyDeviceToDevice, q));
+                HIP_TRY(launch_embed_times(nullptr, -1, (double)cn32, -2, 0.0, sc->t_scale, 0, 0, 1, w.te, nullptr, Be * nf, q));
+            } else {
+                HIP_TRY(launch_embed_times(tl, steps, 0.0, -2, 0.0, sc->t_scale, 0, 0, 0, w.te, nullptr, Be * nf, q));
+            }
+            return wan_forward(h, w.xin, w.te, w.v, Be, nf, height, width, f0, 1, 0, w.net, w.net_bytes, q);
+        };
+        if (!use_graph) {
+            if ((rc = enqueue(s))) return rc;
+            continue;
+        }
+        // what the chunk's launches bake in (timesteps, table with the guidance scale, and the seed are device memory); the host-side
+        // cache bookkeeping is in the same state at this point of every call
+        int64_t tsb, cnb;
+        memcpy(&tsb, &sc->t_scale, 8);
+        memcpy(&cnb, &sc->context_noise, 8);
+        const std::vector<int64_t> key = {batch, guided, frames, height, width, steps, f0, f1, (int64_t)(uintptr_t)x, (int64_t)(uintptr_t)eps,
+                                          (int64_t)(uintptr_t)workspace, tsb, cnb, (int64_t)h->text_L, (int64_t)(uintptr_t)h->blocks[0].kc,
+                                          (int64_t)(uintptr_t)h->blocks[0].kv2};
+        const int stored_before = h->stored_rows;
+        GraphEntry& ge = h->guided_graphs[ci];
+        const bool hit = ge.exec && ge.key == key;
+        if ((rc = graph_run(ge, key, h->sampler.cap, s, enqueue))) return rc;
+        if (hit) {  // (capture runs the same host bookkeeping as an eager pass; a replay must apply it too)
+            const int end_rows = f1 * (height / 2) * (width / 2);
+            h->stored_rows = end_rows > stored_before ? end_rows : stored_before;
+        }
+    }
+    return fg_wan_clear_caches(h, s);  // `self.clear_caches()` after the last chunk (:1292)
+}

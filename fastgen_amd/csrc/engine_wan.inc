@@ -30,6 +30,21 @@ struct fg_wan : HandleBase {
     std::vector<GraphEntry> chunk_graphs;
     int cache_B = 0, cache_cap = 0, text_B = 0, text_L = 0;
     int stored_rows = 0;  // cache rows [0, stored_rows) hold K / V that a store_kv = 1 call wrote (the reference's per_tag["len"], network_causal.py:385-390)
+    // The reference keeps one cache sub-dict per cache_tag ("pos" / "neg", network_causal.py:331-412).  The fields above and the blocks'
+    // kc / vc / kv2 are the SELECTED tag's set; the other tag's set waits here (fg_wan_select_cache_tag swaps them).  It is empty until
+    // its tag is first selected and used: a handle that stays on tag 0 allocates nothing more.
+    struct CacheSet {
+        std::vector<void*> kc, vc, kv2;  // per block
+        int cache_B = 0, cache_cap = 0, text_B = 0, text_L = 0, stored_rows = 0;
+    };
+    CacheSet other;
+    int tag = 0;
+    // fg_wan_guided_sampler_run (engine_sampler.inc): its per-chunk graphs and the pinned host copy of the step scalars
+    std::vector<GraphEntry> guided_graphs;
+    double* pin = nullptr;
+    size_t pin_doubles = 0;
+    hipEvent_t pin_ev = nullptr;
+    bool pin_used = false;
     // As in fg_dit: the GEMM weights are read from the caller's tensors at pack time only (into the bf16 copies p_qkv ...); every other
     // parameter is copied into `own` then, so that nothing points into the caller's memory between two packs (FSDP2 gathers one block,
     // packs it and frees it again: CausalWan.fully_shard).
@@ -168,7 +183,7 @@ int wan_pack(fg_wan* h, const ParamGroup& in_group, hipStream_t s) {
         hipLaunchKernelGGL(wan_n2mod_kernel, dim3(g1), dim3(256), 0, s, raw(b.n2_w), raw(b.n2_b), b.n2mod, (int)D);
         HIP_TRY(hipGetLastError());
     }
-    h->text_B = 0;  // the text caches were computed with the previous weights
+    h->text_B = h->other.text_B = 0;  // the text caches (of both tags) were computed with the previous weights
     return FG_OK;
 }
 
@@ -242,7 +257,10 @@ int fg_wan_create(const fg_wan_config* cfg, fg_wan** out) {
 void fg_wan_destroy(fg_wan* h) {
     if (!h) return;
     for (GraphEntry& g : h->chunk_graphs) g.drop();
+    for (GraphEntry& g : h->guided_graphs) g.drop();
     h->sampler.release();
+    if (h->pin) (void)hipHostFree(h->pin);
+    if (h->pin_ev) (void)hipEventDestroy(h->pin_ev);
     delete h;
 }
 
@@ -296,6 +314,37 @@ int fg_wan_clear_caches(fg_wan* h, void* stream) {
         }
     h->stored_rows = 0;
     h->text_B = 0;  // `is_init = False` of the cross-attention caches (network_causal.py:1046-1054)
+    // ... and the same for the tag that is not selected (the reference resets every tag's sub-dict)
+    fg_wan::CacheSet& o = h->other;
+    if (o.cache_B > 0)
+        for (size_t i = 0; i < o.kc.size(); ++i) {
+            const size_t bytes = (size_t)o.cache_B * o.cache_cap * h->D * 2;
+            HIP_TRY(hipMemsetAsync(o.kc[i], 0, bytes, (hipStream_t)stream));
+            HIP_TRY(hipMemsetAsync(o.vc[i], 0, bytes, (hipStream_t)stream));
+        }
+    o.stored_rows = 0;
+    o.text_B = 0;
+    return FG_OK;
+}
+
+int fg_wan_select_cache_tag(fg_wan* h, int tag) {
+    if (!h) return fail(FG_EINVAL, "null handle");
+    if (tag != 0 && tag != 1) return fail(FG_EINVAL, "cache tag %d: 0 (\"pos\") and 1 (\"neg\") are implemented", tag);
+    if (tag == h->tag) return FG_OK;
+    fg_wan::CacheSet& o = h->other;
+    const size_t n = h->blocks.size();
+    o.kc.resize(n, nullptr), o.vc.resize(n, nullptr), o.kv2.resize(n, nullptr);
+    for (size_t i = 0; i < n; ++i) {
+        std::swap(h->blocks[i].kc, o.kc[i]);
+        std::swap(h->blocks[i].vc, o.vc[i]);
+        std::swap(h->blocks[i].kv2, o.kv2[i]);
+    }
+    std::swap(h->cache_B, o.cache_B);
+    std::swap(h->cache_cap, o.cache_cap);
+    std::swap(h->text_B, o.text_B);
+    std::swap(h->text_L, o.text_L);
+    std::swap(h->stored_rows, o.stored_rows);
+    h->tag = tag;
     return FG_OK;
 }
 

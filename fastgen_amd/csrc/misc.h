@@ -32,6 +32,9 @@ int launch_embed_times(const double* tp, int ti, double tv, int ri, double rv, d
 int launch_flow_to_x0(const float* xt, const float* v, const double* tp, int ti, float sign, float* out, int64_t total, hipStream_t s);
 int launch_euler_step(const float* x, const float* v, const double* tp, int ti, float g, int cfg, float sign, float* out, float* out2,
                       int64_t total, hipStream_t s);
+// one step of CausalWan.sample's guided linear multistep solver, in place on x (x2 nullable: a second copy of the new x); tab: 8 device doubles
+int launch_guided_multistep(const float* v, float* x, float* x2, float* x_last, float* m_prev, const double* tab, int guided, int first,
+                            int64_t total, hipStream_t s);
 int launch_copy_rows(const float* src, int64_t src_pitch, float* dst, int64_t dst_pitch, int64_t run, int64_t rows, hipStream_t s);
 // out[B,H,W,C] = mean over 2x2 of silu(a*x+b), x [B,2H,2W,C]
 int launch_gn_silu_pool(int dtype, const void* x, const float2* ab, void* out, int B, int H, int W, int C, hipStream_t s);

@@ -579,6 +579,77 @@ __global__ void euler_step_kernel(const float* x, const float* __restrict__ v, c
         if (out2) out2[i] = nx;
     }
 }
+// One step of the guided linear multistep solver of `CausalWan.sample` (Wan/solvers.py holds the coefficients; reference
+// fastgen/networks/Wan/network_causal.py:1236-1259: classifier-free guidance, then `unipc_scheduler.step`), one pass over the chunk:
+//   v = v_u + g * (v_c - v_u)      guided: v holds [v_c | v_u], two batches of `total` elements; else the one flow
+//   m = x - s * v                  the data prediction at the predicted sample x
+//   x_corr = c0 * x_last + c1 * m_prev + c2 * m      first step (no history): x_last := x, m_prev := m
+//   x_next = p0 * x_corr + p1 * m_prev + p2 * m
+// x <- x_next (and x2 <- x_next when x2 != nullptr: the second half of the stacked network input), x_last <- x_corr, m_prev <- m.
+// The eight scalars {s, g, c0, c1, c2, p0, p1, p2} are doubles in device memory (graph replay with another table or guidance scale),
+// each rounded once to fp32; every product and sum is an fp32 operation with its own rounding, in exactly this order (no fused
+// multiply-add), so a torch mirror of the formula agrees bit for bit.  V = 4: 16-byte accesses (total % 4 == 0, aligned pointers).
+struct MsCoef {
+    float s, g, c0, c1, c2, p0, p1, p2;
+};
+__device__ __forceinline__ float multistep_elem(const MsCoef& k, int guided, int first, float vc, float vu, float x, float& xl, float& mp,
+                                                float& m_out) {
+#pragma clang fp contract(off)
+    float v = vc;
+    if (guided) {
+        const float d = vc - vu;
+        const float gd = k.g * d;
+        v = vu + gd;
+    }
+    const float sv = k.s * v;
+    const float m = x - sv;
+    const float xlast = first ? x : xl, mprev = first ? m : mp;
+    float xc = k.c0 * xlast;
+    float t = k.c1 * mprev;
+    xc = xc + t;
+    t = k.c2 * m;
+    xc = xc + t;
+    float xn = k.p0 * xc;
+    t = k.p1 * mprev;
+    xn = xn + t;
+    t = k.p2 * m;
+    xn = xn + t;
+    xl = xc;
+    m_out = m;
+    return xn;
+}
+template <int V>
+__global__ void guided_multistep_kernel(const float* __restrict__ v, float* x, float* x2, float* __restrict__ x_last, float* __restrict__ m_prev,
+                                        const double* __restrict__ tab, int guided, int first, int64_t total) {
+    MsCoef k;
+    k.s = (float)tab[0], k.g = (float)tab[1], k.c0 = (float)tab[2], k.c1 = (float)tab[3], k.c2 = (float)tab[4], k.p0 = (float)tab[5],
+    k.p1 = (float)tab[6], k.p2 = (float)tab[7];
+    const int64_t n = total / V;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+        if constexpr (V == 4) {
+            const float4 vc = ((const float4*)v)[i];
+            const float4 vu = guided ? ((const float4*)(v + total))[i] : vc;
+            const float4 xx = ((const float4*)x)[i];
+            float4 xl = first ? xx : ((const float4*)x_last)[i], mp = first ? xx : ((const float4*)m_prev)[i], m, xn;
+            xn.x = multistep_elem(k, guided, first, vc.x, vu.x, xx.x, xl.x, mp.x, m.x);
+            xn.y = multistep_elem(k, guided, first, vc.y, vu.y, xx.y, xl.y, mp.y, m.y);
+            xn.z = multistep_elem(k, guided, first, vc.z, vu.z, xx.z, xl.z, mp.z, m.z);
+            xn.w = multistep_elem(k, guided, first, vc.w, vu.w, xx.w, xl.w, mp.w, m.w);
+            ((float4*)x)[i] = xn;
+            if (x2) ((float4*)x2)[i] = xn;
+            ((float4*)x_last)[i] = xl;
+            ((float4*)m_prev)[i] = m;
+        } else {
+            const float vc = v[i], vu = guided ? v[total + i] : vc, xx = x[i];
+            float xl = first ? xx : x_last[i], mp = first ? xx : m_prev[i], m;
+            const float xn = multistep_elem(k, guided, first, vc, vu, xx, xl, mp, m);
+            x[i] = xn;
+            if (x2) x2[i] = xn;
+            x_last[i] = xl;
+            m_prev[i] = m;
+        }
+    }
+}
 // rows of `run` contiguous elements between a tensor with row pitch src_pitch and one with dst_pitch (elements): the frame slice
 // x[:, :, f0:f1] of a [B, C, F, H, W] video <-> a contiguous chunk [B, C, f1 - f0, H, W] (rows = B * C, run = (f1 - f0) * H * W)
 __global__ void copy_rows_kernel(const float* __restrict__ src, int64_t src_pitch, float* __restrict__ dst, int64_t dst_pitch, int64_t run,
@@ -726,6 +797,15 @@ int launch_flow_to_x0(const float* xt, const float* v, const double* tp, int ti,
 int launch_euler_step(const float* x, const float* v, const double* tp, int ti, float g, int cfg, float sign, float* out, float* out2,
                       int64_t total, hipStream_t s) {
     hipLaunchKernelGGL(euler_step_kernel, dim3(ew_grid(total)), dim3(256), 0, s, x, v, tp, ti, g, cfg, sign, out, out2, total);
+    RET_LAST();
+}
+int launch_guided_multistep(const float* v, float* x, float* x2, float* x_last, float* m_prev, const double* tab, int guided, int first,
+                            int64_t total, hipStream_t s) {
+    const uintptr_t al = (uintptr_t)v | (uintptr_t)x | (uintptr_t)x2 | (uintptr_t)x_last | (uintptr_t)m_prev;
+    if (total % 4 == 0 && al % 16 == 0)
+        hipLaunchKernelGGL(guided_multistep_kernel<4>, dim3(ew_grid(total / 4)), dim3(256), 0, s, v, x, x2, x_last, m_prev, tab, guided, first, total);
+    else
+        hipLaunchKernelGGL(guided_multistep_kernel<1>, dim3(ew_grid(total)), dim3(256), 0, s, v, x, x2, x_last, m_prev, tab, guided, first, total);
     RET_LAST();
 }
 int launch_copy_rows(const float* src, int64_t src_pitch, float* dst, int64_t dst_pitch, int64_t run, int64_t rows, hipStream_t s) {

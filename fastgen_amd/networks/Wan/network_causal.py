@@ -8,7 +8,9 @@ weights and config, unavailable offline); here the fields of that config are con
 the parameters carry the same state-dict keys (`transformer.` + diffusers' names), so a converted checkpoint loads with
 `load_state_dict`.  PARITY UNPINNED (the arithmetic lives in un-vendored diffusers: oracle/wan_ref.py restates it).
 
-Autoregressive inference (`is_ar=True`, one cache tag), the teacher- / diffusion-forcing forward over all total_num_frames frames
+Autoregressive inference (`is_ar=True`, cache tags "pos" and "neg": one cache set each, the second allocated on first use), the
+guided teacher sampler `sample` (classifier-free guidance over the stacked batch [cond; neg_cond], one library call:
+`fg_wan_guided_sampler_run`; solver coefficients from Wan/solvers.py, unpinned like the rest), the teacher- / diffusion-forcing forward over all total_num_frames frames
 (`is_ar=False`: block-wise causal mask, per-frame timesteps [B, F]), and the whole chunk-by-chunk student loop as one library call
 replayed as per-chunk hipGraphs (`student_sample` -> `fg_wan_sampler_run`; CausVidModel / SelfForcingModel call it).  Raises (never falls back): autograd,
 feature taps, r / image conditioning, `is_ar=False` on fewer frames, any device but a HIP GPU.
@@ -54,7 +56,8 @@ class CausalWan(FastGenNetwork):
         _lib.check(_lib.lib().fg_wan_create(ctypes.byref(cfg), ctypes.byref(h)))
         self._h = h
         self._names, self._bound_sig, self._ws = [], {}, None
-        self._text_key = None
+        self._text_key = None  # of the selected cache tag ("pos" outside a forward(cache_tag="neg") call) ...
+        self._text_key_other, self._tag = None, "pos"  # ... and the other tag's
         L = _lib.lib()
         name, ndim, shape = ctypes.c_char_p(), ctypes.c_int(), (ctypes.c_int64 * 5)()
         g = torch.Generator().manual_seed(0)
@@ -104,7 +107,7 @@ class CausalWan(FastGenNetwork):
             bind=lambda n, q: _lib.check(L.fg_wan_bind_param(self._h, n.encode(), ctypes.c_void_p(q.data_ptr()), q.numel())),
             pack_group=lambda pre, exc: _lib.check(L.fg_wan_pack_group(self._h, pre.encode(), exc.encode() if exc else None, self._stream(dev))))
         if changed:
-            self._text_key = None  # the text caches were computed with the previous weights
+            self._text_key = self._text_key_other = None  # the text caches were computed with the previous weights
 
     def fully_shard(self, **kwargs):
         """FSDP2 with the reference's grouping (Wan/network.py:761-782): one parameter group per transformer block, then the transformer
@@ -144,7 +147,16 @@ class CausalWan(FastGenNetwork):
         """`CausalWan.clear_caches` (network_causal.py:1030-1054)."""
         if torch.cuda.is_available():
             _lib.check(_lib.lib().fg_wan_clear_caches(self._h, self._stream(torch.device("cuda", torch.cuda.current_device()))))
-        self._text_key = None
+        self._text_key = self._text_key_other = None
+
+    CACHE_TAGS = {"pos": 0, "neg": 1}
+
+    def _select_tag(self, tag: str) -> None:
+        """Make `tag`'s cache set (and its text key) the one the library calls and `_set_text` act on."""
+        _lib.check(_lib.lib().fg_wan_select_cache_tag(self._h, self.CACHE_TAGS[tag]))
+        if tag != self._tag:
+            self._text_key, self._text_key_other = self._text_key_other, self._text_key
+            self._tag = tag
 
     def forward(self, x_t: torch.Tensor, t: torch.Tensor, condition: Optional[Any] = None, r: Optional[torch.Tensor] = None,
                 return_features_early: bool = False, feature_indices: Optional[Set[int]] = None, return_logvar: bool = False,
@@ -158,8 +170,8 @@ class CausalWan(FastGenNetwork):
             # (the reference builds its block mask only for a call over all total_num_frames frames, network_causal.py:673-680)
             raise NotImplementedError(f"is_ar=False (block-wise causal mask) takes all total_num_frames = {self.total_num_frames} frames, got "
                                       f"{x_t.shape[2]}; chunks go through the autoregressive call (is_ar=True)")
-        if cache_tag != "pos":
-            raise NotImplementedError("one cache tag ('pos') is implemented")
+        if cache_tag not in self.CACHE_TAGS:
+            raise NotImplementedError(f"cache_tag {cache_tag!r}: the cache tags 'pos' and 'neg' are implemented")
         if fwd_pred_type is None:
             fwd_pred_type = self.net_pred_type
         else:
@@ -178,6 +190,18 @@ class CausalWan(FastGenNetwork):
             raise ValueError(f"x_t must have {self.in_channels} channels, got {C}")
         self._bind(dev)
         ws = self._workspace(dev, B, F, H, W)
+        self._select_tag(cache_tag)  # the tag's own caches and text around the call; "pos" is selected again whatever happens
+        try:
+            out = self._forward_selected(x_t, t, condition, B, F, H, W, dev, ws, is_ar, cur_start_frame, store_kv)
+        finally:
+            self._select_tag("pos")
+        out = out.to(x_t.dtype)
+        t_in = torch.atleast_1d(t.detach()).to(dev)
+        t_conv = t_in[:, None, :, None, None] if t_in.ndim == 2 else t_in
+        return self.noise_scheduler.convert_model_output(x_t, out, t_conv, src_pred_type=self.net_pred_type, target_pred_type=fwd_pred_type)
+
+    def _forward_selected(self, x_t, t, condition, B, F, H, W, dev, ws, is_ar, cur_start_frame, store_kv) -> torch.Tensor:
+        """The network call on the selected cache tag: the raw fp32 output."""
         L = _lib.lib()
         self._set_text(condition, B, dev, ws)
         # per-frame timesteps in the embedder's units (`_compute_timestep_inputs`, :1063-1075: rescale_t, [B] -> [B, F])
@@ -194,9 +218,7 @@ class CausalWan(FastGenNetwork):
             _lib.check(L.fg_wan_forward_block_causal(self._h, ctypes.c_void_p(x32.data_ptr()), ctypes.c_void_p(ts.data_ptr()),
                                                      ctypes.c_void_p(out.data_ptr()), B, F, H, W, ctypes.c_void_p(ws.data_ptr()), ws.numel(),
                                                      self._stream(dev)))
-        out = out.to(x_t.dtype)
-        t_conv = t_in[:, None, :, None, None] if t_in.ndim == 2 else t_in
-        return self.noise_scheduler.convert_model_output(x_t, out, t_conv, src_pred_type=self.net_pred_type, target_pred_type=fwd_pred_type)
+        return out
 
     # ---- the chunk-by-chunk student loop as one library call ------------------------------------------------------------------
     @torch.no_grad()
@@ -263,7 +285,90 @@ class CausalWan(FastGenNetwork):
                 ctypes.c_void_p(eps.data_ptr() if eps is not None and eps.numel() else None), ctypes.c_uint64(seed), B, F, H, W,
                 ctypes.c_void_p(ws.data_ptr()), ws.numel(), 1 if use_graph else 0, self._stream(dev)))
         finally:
-            self._text_key = None  # the loop ends with clear_caches(): the text is forgotten with them
+            self._text_key = self._text_key_other = None  # the loop ends with clear_caches(): the text is forgotten with them
         if x32 is not x:
             x.copy_(x32)
         return x
+
+    # ---- the guided teacher sampler as one library call ---------------------------------------------------------------------
+    @torch.no_grad()
+    def sample(self, noise: torch.Tensor, condition: Any = None, neg_condition: Any = None, guidance_scale: Optional[float] = 5.0,
+               sample_steps: int = 50, shift: float = 5.0, context_noise: float = 0, solver: str = "unipc",
+               eps: Optional[torch.Tensor] = None, seed: Optional[int] = None, use_graph: bool = True, **kwargs) -> torch.Tensor:
+        """`CausalWan.sample` (fastgen/networks/Wan/network_causal.py:1186-1295): autoregressive sampling of the teacher with
+        classifier-free guidance over `fg_wan_guided_sampler_run`.  The latents are `noise` itself [B, C, F, H, W], overwritten chunk by
+        chunk and returned.  Per chunk and solver step the conditional and the unconditional flow come from ONE network call on the
+        stacked batch [x; x] against [condition; neg_condition] (the reference makes two calls under the cache tags "pos" / "neg"; the
+        stacked batch keeps both tags' keys / values as rows [0, B) and [B, 2 B) of the tag-"pos" cache set, which holds 2 B rows
+        meanwhile), then `v = v_uncond + guidance_scale * (v_cond - v_uncond)` and the solver step are one elementwise pass.  Guided only
+        when both guidance_scale and neg_condition are given (the reference would fail on guidance_scale without neg_condition); else
+        the loop runs at batch B.
+
+        PARITY UNPINNED: the reference steps diffusers' UniPCMultistepScheduler; solver "unipc" (the default) restates it from the paper
+        and "euler" is the plain flow-ODE step (Wan/solvers.py says what differs).  The network sees t = floor(1000 sigma_i) / 1000 where
+        diffusers keeps the integer timestep int64(1000 sigma_i) and the reference divides it by 1000 - the same number, unpinned too.
+        context_noise > 0: the cache-fill call sees the chunk re-noised with eps ([B, C, F, H, W], injected) or with device draws of
+        `seed`.  sample_steps is not bound by the student loops' 64."""
+        assert self.schedule_type == "rf", f"{self.schedule_type} is not supported"
+        if kwargs:
+            raise TypeError(f"unexpected sample kwargs: {sorted(kwargs)}")
+        if noise.device.type != "cuda":
+            raise RuntimeError("fastgen_amd runs on a HIP GPU only (no CPU path); got a tensor on " + str(noise.device))
+        if self.net_pred_type != "flow":
+            raise NotImplementedError(f"sample() needs a flow-predicting network, got net_pred_type {self.net_pred_type!r}")
+        if condition is None:
+            raise ValueError("CausalWan needs the text condition [B, L, text_dim]")
+        from fastgen_amd.networks.Wan import solvers
+
+        guided = guidance_scale is not None and neg_condition is not None
+        condition = torch.stack(condition, dim=0) if isinstance(condition, list) else condition
+        B, C, F, H, W = noise.shape
+        dev = noise.device
+        if C != self.in_channels:
+            raise ValueError(f"noise must have {self.in_channels} channels, got {C}")
+        if guided:
+            neg_condition = torch.stack(neg_condition, dim=0) if isinstance(neg_condition, list) else neg_condition
+            if neg_condition.shape != condition.shape:
+                raise ValueError(f"neg_condition {tuple(neg_condition.shape)} must be shaped like condition {tuple(condition.shape)}")
+            text = torch.cat([condition.to(dev), neg_condition.to(dev)], dim=0)
+        else:
+            text = condition
+        steps = int(sample_steps)
+        sigmas = solvers.flow_shift_sigmas(steps, float(shift))
+        table = solvers.multistep_table(sigmas, solver, float(guidance_scale) if guided else 1.0)
+        t_net = torch.floor(sigmas[:-1] * 1000.0) / 1000.0
+        self._bind(dev)
+        L = _lib.lib()
+        need = L.fg_wan_guided_sampler_workspace_bytes(self._h, B, F, H, W, steps, int(guided))
+        if need == 0:
+            raise ValueError(f"bad video shape or step count: batch {B}, frames {F}, {H}x{W} (height and width must be even), {steps} steps")
+        if self._ws is None or self._ws.numel() < need or self._ws.device != dev:
+            self._ws = torch.empty(need, dtype=torch.uint8, device=dev)
+        ws = self._ws
+        self._select_tag("pos")
+        self._text_key = None  # (a fresh `text` tensor: embedded for this call)
+        self._set_text(text, text.shape[0], dev, ws)
+        x32 = noise if (noise.dtype == torch.float32 and noise.is_contiguous()) else noise.to(torch.float32).contiguous()
+        cn = float(context_noise or 0.0)
+        if eps is not None:
+            eps = eps.to(device=dev, dtype=torch.float32).contiguous()
+            if eps.numel() != (x32.numel() if cn > 0 else 0):
+                raise ValueError("eps must hold one noise video shaped like noise (context_noise > 0 only)")
+        if seed is None:
+            seed = int(torch.randint(0, 2**62, (1,)).item())
+        sc = _lib.fg_wan_guided_sampler_config()
+        sc.t_scale = float(self.noise_scheduler.num_steps)
+        sc.context_noise = cn
+        sc.guidance = int(guided)
+        self._keep = (x32, eps)  # what a graph replay reads
+        try:
+            _lib.check(L.fg_wan_guided_sampler_run(
+                self._h, ctypes.byref(sc), ctypes.c_void_p(x32.data_ptr()), (ctypes.c_double * steps)(*t_net.tolist()),
+                (ctypes.c_double * (8 * steps))(*table.reshape(-1).tolist()), steps,
+                ctypes.c_void_p(eps.data_ptr() if eps is not None and eps.numel() else None), ctypes.c_uint64(seed), B, F, H, W,
+                ctypes.c_void_p(ws.data_ptr()), ws.numel(), 1 if use_graph else 0, self._stream(dev)))
+        finally:
+            self._text_key = self._text_key_other = None  # the loop ends with clear_caches(): the text is forgotten with them
+        if x32 is not noise:
+            noise.copy_(x32)
+        return noise

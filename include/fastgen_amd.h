@@ -434,8 +434,16 @@ FG_API int fg_wan_pack_weights(fg_wan* h, void* stream);
 FG_API int fg_wan_pack_group(fg_wan* h, const char* prefix, const char* exclude, void* stream);
 /* Workspace for one forward over a chunk of `frames` latent frames of height x width (also enough for fg_wan_set_text). */
 FG_API size_t fg_wan_workspace_bytes(const fg_wan* h, int batch, int frames, int height, int width);
-/* `CausalWan.clear_caches` (:1030-1054): zero the self-attention caches, forget the text (cross-attention) caches. */
+/* `CausalWan.clear_caches` (:1030-1054): zero the self-attention caches, forget the text (cross-attention) caches - of both cache tags. */
 FG_API int fg_wan_clear_caches(fg_wan* h, void* stream);
+/* The reference's `cache_tag` (:331-412): the handle keeps one cache set per tag - the per-block self-attention K / V caches, the
+ * per-block cross-attention (text) caches, and their bookkeeping (batch, capacity, stored rows, text batch and length).  tag 0 = "pos"
+ * (selected at creation), 1 = "neg"; anything else: FG_EINVAL.  Host-side only.  After a select, fg_wan_set_text, fg_wan_forward,
+ * fg_wan_forward_features and fg_wan_sampler_run act on the selected set (fg_wan_forward_block_causal touches no cache); the overwrite
+ * check of fg_wan_forward is per tag.  fg_wan_clear_caches clears both sets and packing invalidates both text caches.  A set is
+ * allocated when it is first used: a handle that never selects tag 1 holds one set, as before; using it costs a second set of memory.
+ * A graph captured by a sampler loop under one tag is not replayed under the other (its key holds the set's pointers). */
+FG_API int fg_wan_select_cache_tag(fg_wan* h, int tag);
 /* The text condition: text [B, text_len, text_dim] fp32 (the text encoder's output).  Runs condition_embedder.text_embedder and
  * every block's attn2 k / v projections (+ norm_k) once: the reference's static cross-attention cache (:331-360). */
 FG_API int fg_wan_set_text(fg_wan* h, const float* text, int batch, int text_len, void* workspace, size_t workspace_bytes, void* stream);
@@ -497,6 +505,39 @@ FG_API size_t fg_wan_sampler_workspace_bytes(const fg_wan* h, int batch, int fra
 FG_API int fg_wan_sampler_run(fg_wan* h, const fg_wan_sampler_config* cfg, float* x, const double* t_list, int steps, int sample_type,
                               const int* exit_steps, const float* eps, uint64_t seed, int batch, int frames, int height, int width,
                               void* workspace, size_t workspace_bytes, int use_graph, void* stream);
+
+/* The autoregressive teacher sampler with classifier-free guidance as ONE call: `CausalWan.sample` (network_causal.py:1186-1295) with
+ * the scheduler's step restated as a linear multistep update (fastgen_amd/networks/Wan/solvers.py builds the table; PARITY UNPINNED:
+ * the reference steps diffusers' UniPCMultistepScheduler).  x: [B, C, frames, H, W] fp32, the noise, overwritten in place with the
+ * sample.  Chunks as in fg_wan_sampler_run.  Per chunk, for i in 0 .. steps - 1: ONE fg_wan_forward of the stacked batch 2 B
+ * ([x_chunk; x_chunk] against the text [cond; neg_cond], t = t_list[i], cur_start_frame, store_kv = 0), then one elementwise pass
+ * (fg_op_guided_multistep) with table row i; then the chunk goes back into x and the cache-fill call runs on the stacked batch
+ * (store_kv = 1) at t = 0, or at context_noise on the chunk re-noised with eps ([B, C, frames, H, W], one noise video; NULL:
+ * Philox4x32-10 from (seed; chunk)).  guidance == 0: the same loop unstacked at batch B (the table's g is not read).  The caller sets
+ * the text for the batch the loop runs at (2 B: [cond; neg_cond]) with fg_wan_set_text before every run; the loop uses the tag-0 cache
+ * set (FG_EINVAL while tag 1 is selected), which therefore holds 2 B rows, empties it first and clears both sets at the end.
+ * t_list: HOST array of `steps` timesteps in [0, 1] as the schedule counts them (the embedder sees fp32(t_scale * t)); table: HOST
+ * array [steps][8] = {s, g, c0, c1, c2, p0, p1, p2} per step.  steps: 1 .. 4096 (the 64-step limit of the student loops does not
+ * apply).  use_graph != 0: one hipGraph per chunk keyed by shapes, pointers and the step count; timesteps, table (with the guidance
+ * scale) and seed live in device memory, so a replay with other values re-captures nothing.  Bit-identical to the same sequence of
+ * fg_wan_forward calls at batch 2 B and fg_op_guided_multistep / fg_op_forward_process. */
+typedef struct fg_wan_guided_sampler_config {
+    double t_scale;        /* the embedder sees fp32(t_scale * t): noise_scheduler.num_steps (1000) on the RF schedule */
+    double context_noise;  /* 0: the cache-fill call sees the clean chunk at t = 0 (RF schedule: x = (1 - c) x0 + c eps otherwise) */
+    int guidance;          /* 1: stacked batch 2 B, v = v_u + g (v_c - v_u); 0: batch B */
+} fg_wan_guided_sampler_config;
+FG_API size_t fg_wan_guided_sampler_workspace_bytes(const fg_wan* h, int batch, int frames, int height, int width, int steps, int guidance);
+FG_API int fg_wan_guided_sampler_run(fg_wan* h, const fg_wan_guided_sampler_config* cfg, float* x, const double* t_list, const double* table,
+                                     int steps, const float* eps, uint64_t seed, int batch, int frames, int height, int width,
+                                     void* workspace, size_t workspace_bytes, int use_graph, void* stream);
+/* One step of that solver, in place (misc.hip guided_multistep_kernel): with the eight DEVICE doubles tab = {s, g, c0, c1, c2, p0, p1, p2}
+ * each rounded once to fp32, v = guided ? v[total + i] + g (v[i] - v[total + i]) : v[i]; m = x - s v; x_corr = c0 x_last + c1 m_prev +
+ * c2 m (first != 0: x_last := x, m_prev := m, neither buffer is read); x_next = p0 x_corr + p1 m_prev + p2 m; then x <- x_next (and
+ * x2 <- x_next, nullable), x_last <- x_corr, m_prev <- m.  Every product and sum is an fp32 operation of its own, left to right as
+ * written.  v: [2 total] when guided (conditional rows first), else [total].  16-byte accesses when total % 4 == 0 and the pointers
+ * allow, else element by element. */
+FG_API int fg_op_guided_multistep(const float* v, float* x, float* x2, float* x_last, float* m_prev, const double* tab, int guided, int first,
+                                  int64_t total, void* stream);
 
 /* Samples to image bytes, the step after generator_fn in the reference's sample writer
  * (scripts/fid/compute_fid_from_ckpts.py:199): out[n,y,x,c] = uint8(clip(images[n,c,y,x] * 127.5 + 128, 0, 255)),
