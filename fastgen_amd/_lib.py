@@ -8,8 +8,8 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libfastgen_amd.so")
 
 FG_MAX_LEVELS = 8
-FG_DTYPE_F32, FG_DTYPE_BF16, FG_DTYPE_BF16X3 = 0, 1, 2
-DTYPE_NAMES = {"fp32": FG_DTYPE_F32, "bf16": FG_DTYPE_BF16, "bf16x3": FG_DTYPE_BF16X3}
+FG_DTYPE_F32, FG_DTYPE_BF16, FG_DTYPE_BF16X3, FG_DTYPE_FP8 = 0, 1, 2, 3
+DTYPE_NAMES = {"fp32": FG_DTYPE_F32, "bf16": FG_DTYPE_BF16, "bf16x3": FG_DTYPE_BF16X3, "fp8": FG_DTYPE_FP8}
 FG_SAMPLE_SDE, FG_SAMPLE_ODE = 0, 1
 SAMPLE_TYPES = {"sde": FG_SAMPLE_SDE, "ode": FG_SAMPLE_ODE}
 FG_LOOP_X0, FG_LOOP_MEANFLOW, FG_LOOP_EULER = 0, 1, 2
@@ -194,6 +194,10 @@ SIGNATURES = {
     "fg_op_attention_split": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
     "fg_op_gemm_bf16": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_int, c_void_p,
                                 c_int, c_void_p]),
+    "fg_op_quant_rows_fp8": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p]),
+    "fg_op_gemm_fp8": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_int, c_void_p,
+                               c_int, c_void_p, c_void_p, c_void_p]),
+    "fg_op_dit_ln_modulate_fp8": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
     "fg_op_gemm_x3": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_int, c_void_p,
                               c_int, c_void_p]),
 }

@@ -115,6 +115,24 @@ typedef __attribute__((ext_vector_type(4))) unsigned fg_u32x4;
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void* base) {
     return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, 0x7fffffff, 0x00020000);
 }
+// fp8 compute mode (FG_DTYPE_FP8): the row quantiser's arithmetic, in ONE place for its two producers (gemm.hip quant_rows_fp8_kernel,
+// dit.hip ln_modulate_kernel's quantising store) - tests/dit_fp8_ref.py mirrors it bit for bit.  scale = amax / 448, inv = 448 / amax
+// (IEEE fp32 divisions; a zero row: 1 and 1), q = e4m3fn_RNE(clamp(x * inv, -448, 448)) (v_cvt_pk_fp8_f32: OCP e4m3fn on gfx950).
+__device__ __forceinline__ float fp8_wave_max(float v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
+    return v;
+}
+__device__ __forceinline__ float fp8_row_inv(float amax) { return amax == 0.f ? 1.0f : 448.0f / amax; }
+__device__ __forceinline__ float fp8_row_scale(float amax) { return amax == 0.f ? 1.0f : amax / 448.0f; }
+__device__ __forceinline__ unsigned fp8_pack4(f32x4 v, float inv) {
+    float q[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) q[e] = __builtin_amdgcn_fmed3f(v[e] * inv, -448.0f, 448.0f);
+    int r = __builtin_amdgcn_cvt_pk_fp8_f32(q[0], q[1], 0, false);
+    r = __builtin_amdgcn_cvt_pk_fp8_f32(q[2], q[3], r, true);
+    return (unsigned)r;
+}
 // 16-byte-aligned fragment loads (global or LDS; address space is inferred after inlining).
 __device__ __forceinline__ Frag8<__bf16> load_frag(const __bf16* p) {
     Frag8<__bf16> f;

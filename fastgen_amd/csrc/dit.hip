@@ -69,9 +69,12 @@ __device__ __forceinline__ void st4(__bf16* p, f32x4 v) { *reinterpret_cast<bf16
 // the cycle stamps of wgrad.hip and gemm.hip): 4-channel pieces (8 / 16 bytes per lane) instead of pairs, and the modulation
 // vectors - the same for every token of an image or frame - loaded once per wave instead of once per token: 36 -> 12.5 instructions
 // per token at D = 1152 (DiT-XL/2, B = 256: 72 -> 62 us = 4.9 TB/s).
-template <typename ST, int D>
+// Q8 (fp8 compute mode): a quantising store - the wave holds the whole modulated row, so its amax is one wave-max away; y is e4m3fn
+// bytes [ntok][D] (through the ST pointer) + one fp32 scale per token in y_scale, common.h's row scheme applied to the fp32 y.
+template <typename ST, int D, bool Q8 = false>
 __global__ __launch_bounds__(256) void ln_modulate_kernel(const ST* __restrict__ x, const float* __restrict__ mod, int mod_stride,
-                                                          int shift_off, int scale_off, ST* __restrict__ y, int ntok, int tpi) {
+                                                          int shift_off, int scale_off, ST* __restrict__ y, int ntok, int tpi,
+                                                          float* __restrict__ y_scale = nullptr) {
     constexpr int NJ = (D + 255) / 256, TPW = 4;
     const int lane = threadIdx.x & 63;
     const int tok0 = (blockIdx.x * 4 + (threadIdx.x >> 6)) * TPW;
@@ -113,15 +116,35 @@ __global__ __launch_bounds__(256) void ln_modulate_kernel(const ST* __restrict__
                 ss = fmaf(v[j][0], v[j][0], ss), ss = fmaf(v[j][1], v[j][1], ss), ss = fmaf(v[j][2], v[j][2], ss), ss = fmaf(v[j][3], v[j][3], ss);
             }
         const float rstd = 1.0f / sqrtf(wave_sum(ss) * (1.0f / D) + 1e-6f);
-        ST* yrow = y + (size_t)tok * D;
+        if constexpr (Q8) {
+            float amax = 0.f;
 #pragma unroll
-        for (int j = 0; j < NJ; ++j)
-            if (has(j)) {
-                f32x4 o;
+            for (int j = 0; j < NJ; ++j)
+                if (has(j)) {
 #pragma unroll
-                for (int e = 0; e < 4; ++e) o[e] = fmaf(v[j][e] * rstd, sc[j][e], sh[j][e]);
-                st4(yrow + 4 * lane + 256 * j, o);
-            }
+                    for (int e = 0; e < 4; ++e) {
+                        v[j][e] = fmaf(v[j][e] * rstd, sc[j][e], sh[j][e]);
+                        amax = fmaxf(amax, fabsf(v[j][e]));
+                    }
+                }
+            amax = fp8_wave_max(amax);
+            const float inv = fp8_row_inv(amax);
+            if (lane == 0) y_scale[tok] = fp8_row_scale(amax);
+            unsigned* yrow = reinterpret_cast<unsigned*>(reinterpret_cast<unsigned char*>(y) + (size_t)tok * D);
+#pragma unroll
+            for (int j = 0; j < NJ; ++j)
+                if (has(j)) yrow[lane + 64 * j] = fp8_pack4(v[j], inv);
+        } else {
+            ST* yrow = y + (size_t)tok * D;
+#pragma unroll
+            for (int j = 0; j < NJ; ++j)
+                if (has(j)) {
+                    f32x4 o;
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) o[e] = fmaf(v[j][e] * rstd, sc[j][e], sh[j][e]);
+                    st4(yrow + 4 * lane + 256 * j, o);
+                }
+        }
     }
 }
 
@@ -559,6 +582,21 @@ int launch_dit_ln_modulate_split(int D, const float* x, const float* mod, int mo
         default: return (int)hipErrorInvalidValue;
     }
 #undef LNS
+    DIT_RET();
+}
+int launch_dit_ln_modulate_fp8(int D, const void* x, const float* mod, int mod_stride, int shift_off, int scale_off, void* y, float* y_scale,
+                               int ntok, int tokens_per_image, hipStream_t s) {
+    if ((mod_stride % 4) || (shift_off % 4) || (scale_off % 4)) return (int)hipErrorInvalidValue;  // (16-byte loads of the modulation vectors)
+    dim3 g((ntok + 15) / 16), b(256);  // 4 waves x 4 tokens
+#define LN8(DD) hipLaunchKernelGGL((ln_modulate_kernel<__bf16, DD, true>), g, b, 0, s, (const __bf16*)x, mod, mod_stride, shift_off, scale_off, (__bf16*)y, ntok, tokens_per_image, y_scale)
+    switch (D) {
+        case 384: LN8(384); break;
+        case 768: LN8(768); break;
+        case 1024: LN8(1024); break;
+        case 1152: LN8(1152); break;
+        default: return (int)hipErrorInvalidValue;
+    }
+#undef LN8
     DIT_RET();
 }
 // dtype: storage of the token tensors (1 bf16, 0 fp32)

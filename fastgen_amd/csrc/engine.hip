@@ -1685,6 +1685,39 @@ int fg_op_gemm_bf16(const void* a, const void* w, const float* bias, void* out, 
     HIP_TRY(rc);
     return FG_OK;
 }
+int fg_op_quant_rows_fp8(int dtype, const void* x, void* q, float* scale, int64_t m, int k, void* stream) {
+    if ((dtype != 0 && dtype != 1) || !x || !q || !scale || m <= 0 || k <= 0 || (k % 128))
+        return fail(FG_EINVAL, "fg_op_quant_rows_fp8: dtype 0 / 1, m > 0, k %% 128 == 0, non-null pointers (got dtype %d, m %lld, k %d)", dtype, (long long)m, k);
+    if ((((uintptr_t)x) | ((uintptr_t)q)) & 15) return fail(FG_EINVAL, "fg_op_quant_rows_fp8: x / q must be 16-byte aligned");
+    HIP_TRY(launch_quant_rows_fp8(dtype, x, q, scale, m, k, (hipStream_t)stream));
+    return FG_OK;
+}
+int fg_op_gemm_fp8(const void* a, const void* w, const float* bias, void* out, int m, int n, int k, int act, const float* gate,
+                   int gate_stride, int gate_rows, const void* resid, int tile_order, const float* a_scale, const float* w_scale, void* stream) {
+    if (act != 0 && act != 1) return fail(FG_EINVAL, "fg_op_gemm_fp8: act must be 0 (none) or 1 (GELU tanh), got %d", act);
+    if (tile_order < 0 || (tile_order & ~31)) return fail(FG_EINVAL, "fg_op_gemm_fp8: bad tile_order %d", tile_order);
+    GemmArgs g;
+    g.A = a; g.W = w; g.bias = bias; g.out = out; g.M = m; g.N = n; g.K = k; g.act = act;
+    g.gate = gate; g.gate_stride = gate_stride; g.gate_rows = gate_rows > 0 ? gate_rows : 1; g.resid = resid; g.xn = tile_order & 15;
+    g.variant = (tile_order & 16) ? 0 : -1;
+    g.a_scale = a_scale; g.w_scale = w_scale;
+    if (!gemm_fp8_supported(g)) return fail(FG_EINVAL, "fg_op_gemm_fp8: unsupported shape (m >= 1, k %% 128, n %% 16, n k < 2^31, pointers and scales)");
+    if (gate && (gate_stride < n || (gate_stride % 4))) return fail(FG_EINVAL, "fg_op_gemm_fp8: gate_stride %d >= n and a multiple of 4", gate_stride);
+    if ((((uintptr_t)a) | ((uintptr_t)w) | ((uintptr_t)out) | ((uintptr_t)bias) | ((uintptr_t)gate) | ((uintptr_t)resid) | ((uintptr_t)w_scale)) & 15)
+        return fail(FG_EINVAL, "fg_op_gemm_fp8: a / w / out / bias / gate / resid / w_scale must be 16-byte aligned");
+    HIP_TRY(launch_gemm_fp8(g, (hipStream_t)stream, true));
+    HIP_TRY(launch_gemm_fp8(g, (hipStream_t)stream));
+    return FG_OK;
+}
+int fg_op_dit_ln_modulate_fp8(const void* x, const float* mod, int mod_stride, int shift_off, int scale_off, void* y, float* y_scale, int ntok,
+                              int d, int tokens_per_image, void* stream) {
+    if (!x || !mod || !y || !y_scale || ntok <= 0 || tokens_per_image <= 0) return fail(FG_EINVAL, "fg_op_dit_ln_modulate_fp8: bad argument");
+    if (d != 384 && d != 768 && d != 1024 && d != 1152) return fail(FG_EINVAL, "fg_op_dit_ln_modulate_fp8: d %d unsupported (384, 768, 1024, 1152)", d);
+    if ((mod_stride % 4) || (shift_off % 4) || (scale_off % 4) || shift_off < 0 || scale_off < 0)
+        return fail(FG_EINVAL, "fg_op_dit_ln_modulate_fp8: mod_stride / shift_off / scale_off must be multiples of 4");
+    HIP_TRY(launch_dit_ln_modulate_fp8(d, x, mod, mod_stride, shift_off, scale_off, y, y_scale, ntok, tokens_per_image, (hipStream_t)stream));
+    return FG_OK;
+}
 int fg_op_gemm_x3(const float* a, const float* w, const float* bias, void* out, int m, int n, int k, int act, const float* gate,
                   int gate_stride, int gate_rows, const float* resid, int out_mode, void* stream) {
     // the checks of launch_gemm_x3 (and its row cutting: every launch keeps whole 256-row tiles) before anything is allocated or launched

@@ -19,6 +19,9 @@ struct fg_dit : HandleBase {
     float* modb = nullptr;    // ... and their biases [depth * 6 D]: one GEMM per forward instead of one 256-row linear per block
     SamplerCache sampler;  // fg_dit_sampler_run (engine_sampler.inc)
     bool gemm3 = false;  // bf16x3 mode: the four block linears on gemm.hip's split-bf16 flavour ([hi | lo | hi] weights, [hi | lo] activation planes)
+    // fp8 mode (FG_DTYPE_FP8): cmode / dtype / gemm as in the bf16 mode (token tensors, attention, modulation GEMM, final layer), but the
+    // four block linears contract e4m3 operands: p_qkv ... hold [N][K] e4m3fn bytes followed by the N fp32 channel scales
+    bool fp8 = false;
     bool gemm = false;  // bf16 mode: the four block linears on gemm.hip (plain [N][K] bf16 weights) instead of conv.hip's token modes
     // a kernel that met an out-of-range class index raises *err_host (pinned, mapped: err_dev is its device address); the next call on
     // the handle reports it (the reference's nn.Embedding device-asserts; nothing is clamped, the sample's output is NaN)
@@ -45,6 +48,8 @@ struct DitWs {
     float *tf, *th, *temb, *remb, *c, *sc, *mod, *fmod, *mod_all;
     void* scb;
     void *x0, *x1, *y, *q, *k, *vt, *att, *hid, *qkv;
+    void *y8, *hid8;   // fp8 mode: the quantised A operands [ntok][D] / [ntok][Hd] ...
+    float *ys, *hs;    // ... and their per-token scales
 };
 
 size_t dit_plan(const fg_dit* h, int B, Arena& A, DitWs& w) {
@@ -71,6 +76,10 @@ size_t dit_plan(const fg_dit* h, int B, Arena& A, DitWs& w) {
     w.att = A.take(ntok * D * tsz);
     w.hid = A.take(ntok * (size_t)h->Hd * tsz);
     w.qkv = A.take(ntok * 3 * D * tsz);  // token-major q | k | v of the LDS-staged attention (bf16 GEMM path, head dim 72)
+    w.y8 = A.take(h->fp8 ? ntok * D : 0);
+    w.hid8 = A.take(h->fp8 ? ntok * (size_t)h->Hd : 0);
+    w.ys = A.get<float>(h->fp8 ? ntok : 0);
+    w.hs = A.get<float>(h->fp8 ? ntok : 0);
     return (A.off + 255) & ~(size_t)255;
 }
 
@@ -96,6 +105,48 @@ int dit_gemm(fg_dit* h, const void* src, int K, const void* wpack, const float* 
     a.wpack = wpack; a.bias = bias; a.scale = 1.0f; a.out = out; a.Cout = N;
     a.act = act; a.gate = gate; a.gate_stride = gate_stride; a.resid = resid;
     HIP_TRY(launch_conv_fused(h->cmode, 1, PRO_NONE, RES_NONE, OUT_TOK, a, s));
+    return FG_OK;
+}
+
+// the same on e4m3 operands: src [tok][K] bytes + src_scale [tok]; wpack = [N][K] bytes followed by the N channel scales (dit_pack)
+int dit_gemm_fp8(fg_dit* h, const void* src, const float* src_scale, int K, const void* wpack, const float* bias, int N, void* out, int B,
+                 hipStream_t s, int act = 0, const float* gate = nullptr, int gate_stride = 0, const void* resid = nullptr) {
+    GemmArgs g;
+    g.A = src; g.W = wpack; g.bias = bias; g.out = out; g.M = B * h->T; g.N = N; g.K = K;
+    g.a_scale = src_scale; g.w_scale = reinterpret_cast<const float*>(reinterpret_cast<const char*>(wpack) + (size_t)N * K);
+    g.act = act; g.gate = gate; g.gate_stride = gate_stride; g.gate_rows = h->T; g.resid = resid;
+    HIP_TRY(launch_gemm_fp8(g, s));
+    return FG_OK;
+}
+
+// One transformer block in the fp8 mode: LayerNorm-modulate stores e4m3 + scale, the attention output and the GELU'd hidden layer are
+// quantised by a pass of their own (their rows cross the producing kernels' tiles); q / k / v, attention and the residual stream stay bf16.
+int dit_block_fp8(fg_dit* h, const fg_dit::Blk& b, const float* mod, int mstride, void*& x, void*& xn, int B, DitWs& w, hipStream_t s) {
+    const fg_dit_config& c = h->cfg;
+    const int D = h->D, T = h->T, ntok = B * T;
+    int rc;
+    HIP_TRY(launch_dit_ln_modulate_fp8(D, x, mod, mstride, 0, D, w.y8, w.ys, ntok, T, s));
+    if (h->hd == 72) {  // qkv stays token-major; attention on wan.hip's LDS-staged kernel
+        if ((rc = dit_gemm_fp8(h, w.y8, w.ys, D, b.p_qkv, h->P(b.qkv_b), 3 * D, w.qkv, B, s))) return rc;
+        const __bf16* qkv = (const __bf16*)w.qkv;
+        HIP_TRY(launch_fa(72, qkv, 3 * D, (int64_t)T * 3 * D, qkv + D, qkv + 2 * D, 3 * D, (int64_t)T * 3 * D, w.att, D, (int64_t)T * D, B,
+                          c.num_heads, T, T, s));
+    } else {
+        GemmArgs g;
+        g.A = w.y8; g.W = b.p_qkv; g.bias = h->P(b.qkv_b); g.M = ntok; g.N = 3 * D; g.K = D;
+        g.a_scale = w.ys; g.w_scale = reinterpret_cast<const float*>(reinterpret_cast<const char*>(b.p_qkv) + (size_t)3 * D * D);
+        g.heads = c.num_heads; g.head_dim = h->hd; g.T = T; g.q = w.q; g.k = w.k; g.vt = w.vt;
+        HIP_TRY(launch_gemm_fp8(g, s));
+        HIP_TRY(launch_dit_attention(h->cmode, w.q, w.k, w.vt, w.att, B, c.num_heads, h->hd, 0, s));
+    }
+    HIP_TRY(launch_quant_rows_fp8(1, w.att, w.y8, w.ys, ntok, D, s));
+    if ((rc = dit_gemm_fp8(h, w.y8, w.ys, D, b.p_proj, h->P(b.proj_b), D, xn, B, s, 0, mod + 2 * D, mstride, x))) return rc;  // x + gate * attn
+    std::swap(x, xn);
+    HIP_TRY(launch_dit_ln_modulate_fp8(D, x, mod, mstride, 3 * D, 4 * D, w.y8, w.ys, ntok, T, s));
+    if ((rc = dit_gemm_fp8(h, w.y8, w.ys, D, b.p_fc1, h->P(b.fc1_b), h->Hd, w.hid, B, s, 1))) return rc;  // GELU(tanh)
+    HIP_TRY(launch_quant_rows_fp8(1, w.hid, w.hid8, w.hs, ntok, h->Hd, s));
+    if ((rc = dit_gemm_fp8(h, w.hid8, w.hs, h->Hd, b.p_fc2, h->P(b.fc2_b), D, xn, B, s, 0, mod + 5 * D, mstride, x))) return rc;
+    std::swap(x, xn);
     return FG_OK;
 }
 
@@ -136,6 +187,16 @@ int dit_forward(fg_dit* h, const float* x_t, const float* t, const float* r, con
     for (const fg_dit::Blk& b : h->blocks) {
         float* mod = mod_once ? w.mod_all + (size_t)(bi++) * 6 * D : w.mod;
         if (!mod_once) HIP_TRY(launch_linear(w.sc, h->P(b.mod_w), h->P(b.mod_b), w.mod, B, D, 6 * D, 0, s));
+        if (h->fp8) {
+            const int rc8 = dit_block_fp8(h, b, mod, mstride, x, xn, B, w, s);
+            if (rc8) return rc8;
+            if (fi < nfeat && feat_blocks[fi] == blk_idx) {
+                HIP_TRY(launch_from_act(h->dtype, x, feats[fi], (int64_t)ntok * D, s));
+                if (++fi == nfeat && early) return FG_OK;
+            }
+            ++blk_idx;
+            continue;
+        }
         if (h->gemm3) HIP_TRY(launch_dit_ln_modulate_split(D, (const float*)x, mod, mstride, 0, D, w.y, ntok, T, s));
         else HIP_TRY(launch_dit_ln_modulate(h->dtype, D, x, mod, mstride, 0, D, w.y, ntok, T, s));
         const bool fa = h->gemm && h->hd == 72;  // qkv stays token-major; attention on wan.hip's LDS-staged kernel
@@ -200,6 +261,8 @@ int dit_pack(fg_dit* h, const ParamGroup& in_group, hipStream_t s) {
     const size_t D = h->D, Hd = h->Hd;
     int rc;
     if (!h->device_ready) {
+        // (before anything is allocated: a failure here leaves nothing behind for a second attempt to allocate again)
+        if (h->fp8 && launch_gemm_fp8(GemmArgs{}, s, true) != 0) return fail(FG_EHIP, "hipFuncSetAttribute(dynamic LDS) failed");
         for (fg_dit::Blk& b : h->blocks) {
             if ((rc = h->alloc(&b.p_qkv, 3 * D * D * wsz)) || (rc = h->alloc(&b.p_proj, D * D * wsz)) ||
                 (rc = h->alloc(&b.p_fc1, Hd * D * wsz)) || (rc = h->alloc(&b.p_fc2, D * Hd * wsz)))
@@ -212,7 +275,7 @@ int dit_pack(fg_dit* h, const ParamGroup& in_group, hipStream_t s) {
         *h->err_host = 0;
         HIP_TRY(hipHostGetDevicePointer((void**)&h->err_dev, h->err_host, 0));
         const char* e = getenv("FASTGEN_AMD_DIT_GEMM");
-        h->gemm = h->cmode == FG_DTYPE_BF16 && !(e && e[0] == '0') && (D % 64) == 0 && (Hd % 64) == 0;
+        h->gemm = h->cmode == FG_DTYPE_BF16 && (h->fp8 || !(e && e[0] == '0')) && (D % 64) == 0 && (Hd % 64) == 0;  // (fp8: fg_dit_create has refused the switch)
         h->gemm3 = want3;
         if ((h->gemm || h->gemm3) && launch_gemm_bf16(GemmArgs{}, s, true) != 0) return fail(FG_EHIP, "hipFuncSetAttribute(dynamic LDS) failed");
         if (h->gemm && ((rc = h->alloc(&h->p_modw, h->blocks.size() * 6 * D * D * 2)) || (rc = h->alloc((void**)&h->modb, h->blocks.size() * 6 * D * 4))))
@@ -232,10 +295,20 @@ int dit_pack(fg_dit* h, const ParamGroup& in_group, hipStream_t s) {
         } else if (h->gemm) {
             HIP_TRY(launch_cvt_bf16(h->params[b.mod_w].ptr, (__bf16*)h->p_modw + me * 6 * D * D, 6 * D * D, s));
             HIP_TRY(hipMemcpyAsync(h->modb + me * 6 * D, h->params[b.mod_b].ptr, 6 * D * 4, hipMemcpyDeviceToDevice, s));
-            HIP_TRY(launch_cvt_bf16(qkv, b.p_qkv, 3 * D * D, s));
-            HIP_TRY(launch_cvt_bf16(proj, b.p_proj, D * D, s));
-            HIP_TRY(launch_cvt_bf16(fc1, b.p_fc1, Hd * D, s));
-            HIP_TRY(launch_cvt_bf16(fc2, b.p_fc2, D * Hd, s));
+            if (h->fp8) {  // rows of W [N][K] quantised on the device: e4m3 bytes, then one scale per output channel (inside the bf16-sized allocation)
+                auto q8 = [&](const float* wsrc, void* dst, size_t N, size_t K) {
+                    return launch_quant_rows_fp8(0, wsrc, dst, reinterpret_cast<float*>(reinterpret_cast<char*>(dst) + N * K), (int64_t)N, (int)K, s);
+                };
+                HIP_TRY(q8(qkv, b.p_qkv, 3 * D, D));
+                HIP_TRY(q8(proj, b.p_proj, D, D));
+                HIP_TRY(q8(fc1, b.p_fc1, Hd, D));
+                HIP_TRY(q8(fc2, b.p_fc2, D, Hd));
+            } else {
+                HIP_TRY(launch_cvt_bf16(qkv, b.p_qkv, 3 * D * D, s));
+                HIP_TRY(launch_cvt_bf16(proj, b.p_proj, D * D, s));
+                HIP_TRY(launch_cvt_bf16(fc1, b.p_fc1, Hd * D, s));
+                HIP_TRY(launch_cvt_bf16(fc2, b.p_fc2, D * Hd, s));
+            }
         } else {
             HIP_TRY(launch_pack_conv_weights(h->cmode, qkv, b.p_qkv, 3 * h->D, h->D, 1, 0, s));
             HIP_TRY(launch_pack_conv_weights(h->cmode, proj, b.p_proj, h->D, h->D, 1, 0, s));
@@ -252,8 +325,16 @@ extern "C" {
 
 int fg_dit_create(const fg_dit_config* cfg, fg_dit** out) {
     if (!cfg || !out) return fail(FG_EINVAL, "null argument");
-    if (cfg->compute_dtype != FG_DTYPE_F32 && cfg->compute_dtype != FG_DTYPE_BF16 && cfg->compute_dtype != FG_DTYPE_BF16X3)
+    if (cfg->compute_dtype != FG_DTYPE_F32 && cfg->compute_dtype != FG_DTYPE_BF16 && cfg->compute_dtype != FG_DTYPE_BF16X3 &&
+        cfg->compute_dtype != FG_DTYPE_FP8)
         return fail(FG_EINVAL, "bad compute_dtype");
+    if (cfg->compute_dtype == FG_DTYPE_FP8 && (cfg->hidden_size <= 0 || cfg->hidden_size % 128 || cfg->mlp_hidden <= 0 || cfg->mlp_hidden % 128))
+        return fail(FG_EINVAL, "fp8 mode: hidden_size %d and mlp_hidden %d must be multiples of 128 (the K-step of the e4m3 MFMA)", cfg->hidden_size,
+                    cfg->mlp_hidden);
+    if (cfg->compute_dtype == FG_DTYPE_FP8) {
+        const char* e = getenv("FASTGEN_AMD_DIT_GEMM");
+        if (e && e[0] == '0') return fail(FG_EINVAL, "the fp8 mode runs on the token GEMM: FASTGEN_AMD_DIT_GEMM=0 excludes it");
+    }
     const int D = cfg->hidden_size;
     if (D != 384 && D != 768 && D != 1024 && D != 1152) return fail(FG_EINVAL, "hidden_size %d unsupported (384, 768, 1024, 1152)", D);
     if (cfg->num_heads <= 0 || D % cfg->num_heads) return fail(FG_EINVAL, "hidden_size must be a multiple of num_heads");
@@ -266,8 +347,9 @@ int fg_dit_create(const fg_dit_config* cfg, fg_dit** out) {
         return fail(FG_EINVAL, "bad depth / mlp_hidden / in_channels / embedding_rows");
     fg_dit* h = new fg_dit();
     h->cfg = *cfg;
-    h->cmode = cfg->compute_dtype;
-    h->dtype = cfg->compute_dtype == FG_DTYPE_BF16 ? 1 : 0;
+    h->fp8 = cfg->compute_dtype == FG_DTYPE_FP8;
+    h->cmode = h->fp8 ? FG_DTYPE_BF16 : cfg->compute_dtype;  // (everything but the block linears is the bf16 mode's)
+    h->dtype = h->cmode == FG_DTYPE_BF16 ? 1 : 0;
     h->D = D, h->Hd = cfg->mlp_hidden, h->hd = hd, h->grid = 16, h->T = 256;
     const int p = cfg->patch_size, C = cfg->in_channels, PO = p * p * C;
     // module order of the reference's DiT (:233-290); `pos_embed` is its persistent buffer

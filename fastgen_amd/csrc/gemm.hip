@@ -57,11 +57,23 @@ __device__ __forceinline__ float gm_gelu_tanh(float x) {
     return x * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-z));
 }
 
+typedef __attribute__((ext_vector_type(4))) int i32x4;
+typedef __attribute__((ext_vector_type(8))) int i32x8;
+__device__ __forceinline__ i32x8 gm_cat8(i32x4 lo, i32x4 hi) { return __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7); }
+// 16 x 16 x 128 product of e4m3 operands (formats 0 / 0), block scales E8M0 0x7f = 1: lane l holds row l & 15, k bytes 32 (l >> 4) .. + 31
+__device__ __forceinline__ f32x4 gm_mfma_f8(i32x8 a, i32x8 b, f32x4 c) {
+    return __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(a, b, c, 0, 0, 0, 0x7f7f7f7f, 0, 0x7f7f7f7f);
+}
+
 enum { GM_EPI_TOK = 0, GM_EPI_HEADS = 1, GM_EPI_RAW = 2, GM_EPI_TOK32 = 3, GM_EPI_SPLIT = 4, GM_EPI_HEADS32 = 5 };
 
-template <int NT, int EPI>
+// F8 (the fp8 flavour, launch_gemm_fp8): A / W rows are e4m3 bytes, so a 128-deep K-step is the same 128 bytes per row - the same
+// staging and LDS image - and lane group g reads the planes 2 g, 2 g + 1 (k bytes 32 g .. 32 g + 31 of the step) as the 32-byte
+// operands of one v_mfma_scale_f32_16x16x128_f8f6f4 (unit block scales); the row / channel scales multiply the fp32 sums in the epilogue.
+template <int NT, int EPI, bool F8 = false>
 __global__ __launch_bounds__(GM_NTHR) void gemm_bf16_kernel(const GemmArgs a) {
     constexpr int TN = 64 * NT;             // outputs per tile
+    constexpr int EB = F8 ? 1 : 2;          // bytes per operand element
     constexpr int PW = TN * 16 + 16;        // bytes between the octet planes of the W image
     constexpr int STAGE = 8 * (GM_PA + PW);
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -97,7 +109,7 @@ __global__ __launch_bounds__(GM_NTHR) void gemm_bf16_kernel(const GemmArgs a) {
         m0 = (mlo + q) * GM_TM;
         n0 = (nlo + (lt - q * nx)) * TN;
     };
-    const int nk = a.K / GM_KC;
+    const int nk = a.K * EB / (GM_KC * 2);
     const int S = my_tiles * nk;
 
     // ---- staging: thread -> (row tid >> 3 + 64 i, octet tid & 7) of both operand tiles ------------------------------
@@ -111,9 +123,9 @@ __global__ __launch_bounds__(GM_NTHR) void gemm_bf16_kernel(const GemmArgs a) {
         int m0, n0;
         tile_origin(i, m0, n0);
 #pragma unroll
-        for (int j = 0; j < 4; ++j) offA[j] = (unsigned)min(m0 + srow + 64 * j, a.M - 1) * (unsigned)(a.K * 2) + soct * 16;
+        for (int j = 0; j < 4; ++j) offA[j] = (unsigned)min(m0 + srow + 64 * j, a.M - 1) * (unsigned)(a.K * EB) + soct * 16;
 #pragma unroll
-        for (int j = 0; j < NT; ++j) offW[j] = (unsigned)min(n0 + srow + 64 * j, a.N - 1) * (unsigned)(a.K * 2) + soct * 16;
+        for (int j = 0; j < NT; ++j) offW[j] = (unsigned)min(n0 + srow + 64 * j, a.N - 1) * (unsigned)(a.K * EB) + soct * 16;
     };
     auto issue = [&](int kidx) {
         const int so = __builtin_amdgcn_readfirstlane(kidx * (GM_KC * 2));  // (uniform; kept off the vector unit: no waterfall loop per load)
@@ -139,6 +151,25 @@ __global__ __launch_bounds__(GM_NTHR) void gemm_bf16_kernel(const GemmArgs a) {
         for (int nt = 0; nt < NT; ++nt) acc[m][nt] = f32x4{0.f, 0.f, 0.f, 0.f};
 
     auto compute = [&](const char* st) {
+        if constexpr (F8) {
+            i32x8 w8[NT], x8[4];
+#pragma unroll
+            for (int nt = 0; nt < NT; ++nt)
+                w8[nt] = gm_cat8(*reinterpret_cast<const i32x4*>(st + 8 * GM_PA + 2 * g * PW + (wn * 16 * NT + col) * 16 + nt * 256),
+                                 *reinterpret_cast<const i32x4*>(st + 8 * GM_PA + (2 * g + 1) * PW + (wn * 16 * NT + col) * 16 + nt * 256));
+#pragma unroll
+            for (int half = 0; half < 2; ++half) {
+#pragma unroll
+                for (int m = 0; m < 4; ++m)
+                    x8[m] = gm_cat8(*reinterpret_cast<const i32x4*>(st + 2 * g * GM_PA + (wm * 128 + col) * 16 + (half * 4 + m) * 256),
+                                    *reinterpret_cast<const i32x4*>(st + (2 * g + 1) * GM_PA + (wm * 128 + col) * 16 + (half * 4 + m) * 256));
+#pragma unroll
+                for (int m = 0; m < 4; ++m)
+#pragma unroll
+                    for (int nt = 0; nt < NT; ++nt) acc[half * 4 + m][nt] = gm_mfma_f8(w8[nt], x8[m], acc[half * 4 + m][nt]);
+            }
+            return;
+        }
         bf16x8 x0[4], x1[4], w0[NT], w1[NT];
         auto read_x = [&](int j, int half, bf16x8 (&x)[4]) {
 #pragma unroll
@@ -186,10 +217,23 @@ __global__ __launch_bounds__(GM_NTHR) void gemm_bf16_kernel(const GemmArgs a) {
             b4[nt] = f32x4{0.f, 0.f, 0.f, 0.f};
             if (a.bias && c0 + 16 * nt < a.N) b4[nt] = *reinterpret_cast<const f32x4*>(a.bias + c0 + 16 * nt);
         }
+        f32x4 ws4[NT];  // (fp8 flavour) the channel scales of this lane's outputs
+        if constexpr (F8) {
+#pragma unroll
+            for (int nt = 0; nt < NT; ++nt) {
+                ws4[nt] = f32x4{0.f, 0.f, 0.f, 0.f};
+                if (c0 + 16 * nt < a.N) ws4[nt] = *reinterpret_cast<const f32x4*>(a.w_scale + c0 + 16 * nt);
+            }
+        }
 #pragma unroll
         for (int m = 0; m < 8; ++m) {
             const int row = m0 + wm * 128 + m * 16 + col;
             if (row < a.M) {
+                if constexpr (F8) {
+                    const float sa = a.a_scale[row];
+#pragma unroll
+                    for (int nt = 0; nt < NT; ++nt) acc[m][nt] *= ws4[nt] * sa;
+                }
                 if constexpr (EPI == GM_EPI_TOK) {
                     __bf16* orow = reinterpret_cast<__bf16*>(a.out) + (size_t)row * a.N;
                     const __bf16* rrow = reinterpret_cast<const __bf16*>(a.resid) + (size_t)row * a.N;
@@ -290,9 +334,13 @@ __global__ __launch_bounds__(GM_NTHR) void gemm_bf16_kernel(const GemmArgs a) {
 #endif
 #define GM_DSR(dst, addr, off) asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "n"(off))
 
-template <int EPI>
+// F8 (the fp8 flavour): as in gemm_bf16_kernel the 128-byte row of a K-step holds 128 e4m3 values; DMA, ring, swizzle and the phase
+// schedule are byte-identical.  Lane group g reads the k-octets 2 g and 2 g + 1 (the two ds_read_b128 per fragment that the bf16
+// form spends on its two 32-deep sub-steps) and a phase is 8 MFMAs of 16 x 16 x 128 - the cycles of the bf16 form's 16.
+template <int EPI, bool F8 = false>
 __global__ __launch_bounds__(GM_NTHR) void gemm_bf16_pp_kernel(const GemmArgs a) {
     constexpr int TN = 256;
+    constexpr int EB = F8 ? 1 : 2;  // bytes per operand element
     extern __shared__ __attribute__((aligned(16))) char smem[];
     typedef __attribute__((address_space(3))) void* lds_ptr;
 
@@ -339,10 +387,10 @@ __global__ __launch_bounds__(GM_NTHR) void gemm_bf16_pp_kernel(const GemmArgs a)
         mk = (mlo + q) * GM_TM;
         nk_ = (nlo + (lt - q * nx)) * TN;
     };
-    const int nk = (a.K / GM_KC) / ks;  // K-steps per work item
+    const int nk = (a.K * EB / (GM_KC * 2)) / ks;  // K-steps per work item
     const int S = my_tiles * nk;
     // row pitches in bytes (split-bf16 flavour: A rows hold [hi | lo] = 2 K1 elements, W rows [hi | lo | hi] = 3 K1 = K elements)
-    const int KA2 = (a.lda ? a.lda : a.K) * 2, KW2 = (a.ldw ? a.ldw : a.K) * 2;
+    const int KA2 = (a.lda ? a.lda : a.K) * EB, KW2 = (a.ldw ? a.ldw : a.K) * EB;
     // ---- DMA: wave w moves the 8-row groups 2 w, 2 w + 1 of every half-tile; lane -> (row lane >> 3 of the group, LDS octet
     // position lane & 7, which holds k-octet position ^ ((row >> 1) & 7)) ------------------------------------------------
     const __amdgpu_buffer_rsrc_t rsA = make_rsrc(a.A), rsW = make_rsrc(a.W);
@@ -387,7 +435,7 @@ __global__ __launch_bounds__(GM_NTHR) void gemm_bf16_pp_kernel(const GemmArgs a)
     };
 
     // ---- fragments ----------------------------------------------------------------------------------------------------
-    const int lrow0 = col * 128 + ((g ^ ((col >> 1) & 7)) * 16), lrow1 = lrow0 ^ 64;   // k-substep 0 / 1
+    const int lrow0 = col * 128 + (((F8 ? 2 * g : g) ^ ((col >> 1) & 7)) * 16), lrow1 = lrow0 ^ (F8 ? 16 : 64);   // k-substep 0 / 1 (fp8: low / high 16 bytes)
     const int fxa = wr * 16384;                                  // this wave's A half
     const int fwb = 32768 + (wc >> 1) * 16384 + (wc & 1) * 8192;  // this wave's 64 W rows
     bf16x8 X0[4][2], X1[4][2], W0[2][2], W1[2][2];  // [m | nt][k-substep]
@@ -416,6 +464,23 @@ __global__ __launch_bounds__(GM_NTHR) void gemm_bf16_pp_kernel(const GemmArgs a)
         }
     };
     auto mma = [&](int mh, int nh, const bf16x8 (&x)[4][2], const bf16x8 (&w)[2][2]) {
+        if constexpr (F8) {
+#pragma unroll
+            for (int m = 0; m < 4; ++m)
+#pragma unroll
+                for (int nt = 0; nt < 2; ++nt)
+                    acc[mh * 4 + m][nh * 2 + nt] = gm_mfma_f8(gm_cat8(__builtin_bit_cast(i32x4, w[nt][0]), __builtin_bit_cast(i32x4, w[nt][1])),
+                                                              gm_cat8(__builtin_bit_cast(i32x4, x[m][0]), __builtin_bit_cast(i32x4, x[m][1])),
+                                                              acc[mh * 4 + m][nh * 2 + nt]);
+            // (the phase's results pinned in place: with nothing but the next K-step's MFMAs reading them, hipcc sank all 32 of a K-step
+            // behind the cursor update's branch - out of their setprio brackets and past the fragment reads of the next step, which
+            // then needed 32 more registers and spilled)
+#pragma unroll
+            for (int m = 0; m < 4; ++m)
+#pragma unroll
+                for (int nt = 0; nt < 2; ++nt) asm volatile("" : "+v"(acc[mh * 4 + m][nh * 2 + nt]));
+            return;
+        }
 #pragma unroll
         for (int j = 0; j < 2; ++j)
 #pragma unroll
@@ -458,6 +523,28 @@ __global__ __launch_bounds__(GM_NTHR) void gemm_bf16_pp_kernel(const GemmArgs a)
     // (gate periods >= the tile height: a tile then spans at most two gate rows; launch_gemm_bf16 sends shorter ones to gemm_bf16_kernel)
     auto slice = [&](auto MH_, auto NH_, int tile, f32x4 be, f32x4 bo) {
         constexpr int MH = decltype(MH_)::value, NH = decltype(NH_)::value;
+        if constexpr (F8) {
+            // row scale x channel scale on the fp32 sums, in the accumulators' own layout (before the swap): token col of the 16-row
+            // block, outputs 4 g .. 4 g + 3 of the even / odd 16-output group
+            const __amdgpu_buffer_rsrc_t rsAS = make_rsrc(a.a_scale), rsWS = make_rsrc(a.w_scale);
+            const int wso = __builtin_amdgcn_readfirstlane((ep_n0 + wc * 64 + 32 * NH) * 4);
+            const f32x4 wse = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsWS, g * 16, wso, 0));
+            const f32x4 wso4 = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsWS, g * 16, wso + 64, 0));
+            // (the bias with them, not a K-step ahead as in the bf16 form: 16 registers less across the last K-step, and this wait exists anyway)
+            f32x4 be8 = {0.f, 0.f, 0.f, 0.f}, bo8 = be8;
+            if (a.bias) {
+                const __amdgpu_buffer_rsrc_t rsB8 = make_rsrc(a.bias);
+                be8 = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsB8, g * 16, wso, 0));
+                bo8 = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsB8, g * 16, wso + 64, 0));
+            }
+#pragma unroll
+            for (int m = 0; m < 4; ++m) {
+                const int aso = __builtin_amdgcn_readfirstlane((ep_m0 + (MH * 4 + m) * 16) * 4);
+                const float sa = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rsAS, (wr * 128 + col) * 4, aso, 0));
+                acc[MH * 4 + m][NH * 2] = acc[MH * 4 + m][NH * 2] * (wse * sa) + be8;
+                acc[MH * 4 + m][NH * 2 + 1] = acc[MH * 4 + m][NH * 2 + 1] * (wso4 * sa) + bo8;
+            }
+        }
         if constexpr (EPI == GM_EPI_TOK) {
             if (!GM_TIMING(a.act & 8)) {
                 const int m0 = ep_m0, n0 = ep_n0, mk = ep_mk, nk_ = ep_nk;  // (tile_origin / tile_keep_from of `tile`, computed once per tile)
@@ -743,7 +830,7 @@ __global__ __launch_bounds__(GM_NTHR) void gemm_bf16_pp_kernel(const GemmArgs a)
         f32x4 b00 = {0.f, 0.f, 0.f, 0.f}, b01 = b00, b10 = b00, b11 = b00;
         tile_origin(ti, ep_m0, ep_n0);
         tile_keep_from(ti, ep_mk, ep_nk);
-        if (a.bias && EPI != GM_EPI_RAW) {
+        if (a.bias && EPI != GM_EPI_RAW && !F8) {
             // (buffer-resource addressing, one lane-constant register + scalar offsets: as a 64-bit per-lane pointer kept across the tile
             // loop this cost spilled registers in the head-split / fp32-output instantiations, and their reload here - a scratch load,
             // waited for with vmcnt(0) - drained the DMA pipeline once per tile)
@@ -1405,13 +1492,40 @@ __global__ void split_planes_kernel(const float* __restrict__ x, __bf16* __restr
     *reinterpret_cast<bf16x4*>(out + r * 2 * K + K + c) = lo;
 }
 
+// ---- fp8 (e4m3fn) row quantiser: W8A8 with one scale per row -------------------------------------------------------------------
+// scale = amax / 448, q = e4m3fn_RNE(clamp(x * (448 / amax), -448, 448)) (both IEEE fp32 divisions; a zero row: scale 1, q 0).
+// v_cvt_pk_fp8_f32 on gfx950 is the OCP e4m3fn conversion (round to nearest even, subnormals).
+// (the arithmetic itself - fp8_row_inv / fp8_row_scale / fp8_pack4 - is common.h's, shared with dit.hip's quantising LayerNorm-modulate)
+__device__ __forceinline__ f32x4 gm_ld4(const float* p) { return *reinterpret_cast<const f32x4*>(p); }
+__device__ __forceinline__ f32x4 gm_ld4(const __bf16* p) { return load4(p); }
+// One wave per row, 4 elements per lane and pass; the row is read twice (amax, then conversion: the second read hits the cache -
+// a row is at most a few KiB), so K is a run-time value.  K % 128 == 0.
+template <typename ST>
+__global__ __launch_bounds__(256) void quant_rows_fp8_kernel(const ST* __restrict__ x, unsigned char* __restrict__ q, float* __restrict__ scale,
+                                                             int64_t M, int K) {
+    const int lane = threadIdx.x & 63;
+    const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= M) return;
+    const ST* xr = x + row * K;
+    float amax = 0.f;
+    for (int c = 4 * lane; c < K; c += 256) {
+        const f32x4 v = gm_ld4(xr + c);
+        amax = fmaxf(amax, fmaxf(fmaxf(fabsf(v[0]), fabsf(v[1])), fmaxf(fabsf(v[2]), fabsf(v[3]))));
+    }
+    amax = fp8_wave_max(amax);
+    const float inv = fp8_row_inv(amax);
+    if (lane == 0) scale[row] = fp8_row_scale(amax);
+    unsigned* qr = reinterpret_cast<unsigned*>(q + row * K);
+    for (int c = 4 * lane; c < K; c += 256) qr[c >> 2] = fp8_pack4(gm_ld4(xr + c), inv);
+}
+
 int g_gm_cus[16] = {};
 
-template <int NT, int EPI>
+template <int NT, int EPI, bool F8 = false>
 int launch_gm(const GemmArgs& a, hipStream_t s, bool prepare_only) {
     constexpr int TN = 64 * NT;
     constexpr int LDS = 2 * 8 * (GM_PA + TN * 16 + 16);
-    auto kern = gemm_bf16_kernel<NT, EPI>;
+    auto kern = gemm_bf16_kernel<NT, EPI, F8>;
     const int dev = fg_device_slot();
     if (dev < 0) return (int)hipErrorInvalidDevice;
     static bool attr_done[16] = {};
@@ -1447,10 +1561,10 @@ int launch_gm(const GemmArgs& a, hipStream_t s, bool prepare_only) {
     return (int)hipGetLastError();
 }
 
-template <int EPI>
+template <int EPI, bool F8 = false>
 int launch_pp(const GemmArgs& a, hipStream_t s, bool prepare_only) {
     constexpr int LDS = 131072;
-    auto kern = gemm_bf16_pp_kernel<EPI>;
+    auto kern = gemm_bf16_pp_kernel<EPI, F8>;
     const int dev = fg_device_slot();
     if (dev < 0) return (int)hipErrorInvalidDevice;
     static bool attr_done[16] = {};
@@ -1731,5 +1845,61 @@ int launch_split3_weights(const float* w, void* out, int N, int K, hipStream_t s
 int launch_split_planes(const float* x, void* out, int64_t M, int K, hipStream_t s) {
     const int64_t n = M * (K / 4);
     hipLaunchKernelGGL(split_planes_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, x, (__bf16*)out, M, K);
+    return (int)hipGetLastError();
+}
+
+// ---- fp8 (e4m3) flavour of the token GEMM ------------------------------------------------------------------------------------------
+// A [M][K], W [N][K] e4m3fn bytes with a_scale [M], w_scale [N] (launch_quant_rows_fp8); out = epilogue(a_scale[m] w_scale[n] sum_k
+// qa qw + bias[n]) with the bf16 GEMM's token / head-split epilogues.  K % 128 == 0, N % 16 == 0.  The ping-pong kernel where M, N >=
+// 256 and K >= 256 (variant -1: unless FASTGEN_AMD_GEMM_PP=0, as launch_gemm_bf16), else the register-staged one - which has the token
+// epilogue only: a head-split launch that is not ping-pong eligible is refused.  No split-K, no narrow tile.
+bool gemm_fp8_supported(const GemmArgs& a) {
+    if (a.M <= 0 || a.N <= 0 || a.K <= 0 || (a.K % 128) || (a.N % 16)) return false;
+    if ((size_t)a.N * a.K >= (1ull << 31)) return false;
+    if (a.heads > 0 && (a.head_dim % 4 || a.N != 3 * a.heads * a.head_dim || a.T <= 0 || !a.q || !a.k || !a.vt)) return false;
+    if (a.heads > 0 && (a.heads * a.head_dim) % 8) return false;
+    if (a.heads <= 0 && !a.out) return false;
+    if (a.gate && a.gate_rows <= 0) return false;
+    if (a.act != 0 && a.act != 1) return false;
+    return a.A && a.W && a.a_scale && a.w_scale;
+}
+
+int launch_gemm_fp8(const GemmArgs& a, hipStream_t s, bool prepare_only) {
+    if (prepare_only) {
+        int rc;
+        if ((rc = launch_gm<4, GM_EPI_TOK, true>(a, s, true)) || (rc = launch_gm<3, GM_EPI_TOK, true>(a, s, true)) ||
+            (rc = launch_pp<GM_EPI_TOK, true>(a, s, true)) || (rc = launch_pp<GM_EPI_HEADS, true>(a, s, true)))
+            return rc;
+        return 0;
+    }
+    if (!gemm_fp8_supported(a)) return (int)hipErrorInvalidValue;
+    const bool heads = a.heads > 0;
+    const bool n3 = (a.N % 256) != 0 && (a.N % 192) == 0;
+    // rows per launch: byte offsets into A (K per row) and out / resid (2 N per row) stay below the buffer resource's 2 GiB
+    const int rows_max = (int)(((1ull << 31) - 1) / ((size_t)(a.K > 2 * a.N ? a.K : 2 * a.N))) / GM_TM * GM_TM;
+    for (int r0 = 0; r0 < a.M; r0 += rows_max) {
+        GemmArgs b = a;
+        b.row0 = a.row0 + r0;
+        b.M = a.M - r0 < rows_max ? a.M - r0 : rows_max;
+        b.A = reinterpret_cast<const unsigned char*>(a.A) + (size_t)r0 * a.K;
+        b.a_scale = a.a_scale + r0;
+        if (a.out) b.out = reinterpret_cast<__bf16*>(a.out) + (size_t)r0 * a.N;
+        if (a.resid) b.resid = reinterpret_cast<const __bf16*>(a.resid) + (size_t)r0 * a.N;
+        b.ksplit = 1, b.scratch = nullptr, b.lda = b.ldw = b.a_wrap = 0, b.out_f32 = 0;
+        const bool pp = (a.variant < 0 ? gm_variant() : a.variant) != 0 && b.M >= GM_TM && a.N >= 256 && a.K >= 256 && (!a.gate || a.gate_rows >= GM_TM);
+        if (heads && !pp) return (int)hipErrorInvalidValue;
+        const int rc = pp ? (heads ? launch_pp<GM_EPI_HEADS, true>(b, s, false) : launch_pp<GM_EPI_TOK, true>(b, s, false))
+                          : (n3 ? launch_gm<3, GM_EPI_TOK, true>(b, s, false) : launch_gm<4, GM_EPI_TOK, true>(b, s, false));
+        if (rc) return rc;
+    }
+    return 0;
+}
+
+// dtype: 0 fp32 / 1 bf16 rows in; q [M][K] e4m3fn bytes, scale [M] fp32
+int launch_quant_rows_fp8(int dtype, const void* x, void* q, float* scale, int64_t M, int K, hipStream_t s) {
+    if (M <= 0 || K <= 0 || (K % 128) || !x || !q || !scale) return (int)hipErrorInvalidValue;
+    const dim3 g((unsigned)((M + 3) / 4)), b(256);
+    if (dtype) hipLaunchKernelGGL(quant_rows_fp8_kernel<__bf16>, g, b, 0, s, (const __bf16*)x, (unsigned char*)q, scale, M, K);
+    else hipLaunchKernelGGL(quant_rows_fp8_kernel<float>, g, b, 0, s, (const float*)x, (unsigned char*)q, scale, M, K);
     return (int)hipGetLastError();
 }

@@ -139,6 +139,9 @@ int launch_dit_ln_modulate(int dtype, int D, const void* x, const float* mod, in
 // fp32 tokens in, y as [hi | lo] bf16 planes [ntok][2 D] (the split-bf16 token GEMM's A operand)
 int launch_dit_ln_modulate_split(int D, const float* x, const float* mod, int mod_stride, int shift_off, int scale_off, void* y, int ntok,
                                  int tokens_per_image, hipStream_t s);
+// bf16 tokens in, y as e4m3fn bytes [ntok][D] with one scale per token (the fp8 token GEMM's A operand; D % 128 == 0)
+int launch_dit_ln_modulate_fp8(int D, const void* x, const float* mod, int mod_stride, int shift_off, int scale_off, void* y, float* y_scale,
+                               int ntok, int tokens_per_image, hipStream_t s);
 int launch_dit_final(int dtype, int D, const void* x, const float* mod, const float* w, const float* bias, float* out, int ntok, int grid,
                      int p, int C, hipStream_t s);
 int launch_dit_patch_embed(int dtype, const float* x, const float* w, const float* bias, const float* pos, void* out, int B, int C, int grid,
@@ -175,12 +178,19 @@ struct GemmArgs {
     size_t scratch_bytes = 0;
     int ksplit = 1;               // set by the launcher
     int out_f32 = 0;              // 1: out (and resid) fp32 [M][N] instead of bf16 (ping-pong kernel only: M, N >= 256)
-    int variant = -1;  // -1: default (env FASTGEN_AMD_GEMM_PP, 1 unless set to 0); 0 register-staged kernel; 1 LDS-DMA ping-pong kernel; 2 its narrow-tile form
+    const float *a_scale = nullptr, *w_scale = nullptr;  // fp8 flavour (launch_gemm_fp8): per-row scale of A [M], per-channel scale of W [N]
+    int variant = -1;  // -1: default (env FASTGEN_AMD_GEMM_PP, 1 unless set to 0; launch_gemm_fp8 too); 0 register-staged kernel; 1 LDS-DMA ping-pong kernel; 2 its narrow-tile form
     int xn = 1;    // 0: linear tile order; 1: XCD-aware order, split chosen by the launcher; 2 / 4 / 8: that many XCD columns over N
 };
 bool gemm_bf16_supported(const GemmArgs& a);
 int launch_gemm_bf16(const GemmArgs& a, hipStream_t s, bool prepare_only = false);
 int launch_cvt_bf16(const float* in, void* out, size_t n, hipStream_t s);
+// the same kernels on e4m3fn operands (W8A8): A [M][K], W [N][K] bytes + a_scale / w_scale (launch_quant_rows_fp8: scale = amax / 448 per
+// row); out = epilogue(a_scale[m] w_scale[n] sum_k qa qw + bias[n]), bf16 out / resid, token and head-split epilogues as above.
+// K % 128 == 0, N % 16 == 0; variant 0: always the register-staged kernel.
+bool gemm_fp8_supported(const GemmArgs& a);
+int launch_gemm_fp8(const GemmArgs& a, hipStream_t s, bool prepare_only = false);
+int launch_quant_rows_fp8(int dtype, const void* x, void* q, float* scale, int64_t M, int K, hipStream_t s);
 // the same kernel in the split-bf16 (fp32-grade) mode: see gemm.hip.  A = [hi | lo] planes [M][2 K] bf16, W = launch_split3_weights
 // of the fp32 weight ([N][3 K]), fp32 epilogue; out_mode 0: fp32 [M][N] (+ fp32 resid), 1: [hi | lo] planes [M][2 N]; heads > 0: head-split
 // hi / lo planes (q, k, vt + lo_off).  M >= 256, N >= 256, K % 64 == 0.

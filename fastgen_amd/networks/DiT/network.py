@@ -58,8 +58,12 @@ class DiT(FastGenNetwork):
         self.use_sit_convention = use_sit_convention
         self.class_dropout_prob = class_dropout_prob if enable_class_dropout else 0.0  # ConditionalEmbedding.cfg_dropout_rate, :114
         self.compute_dtype = compute_dtype or os.environ.get("FASTGEN_AMD_COMPUTE_DTYPE") or None
-        if self.compute_dtype not in (None, "fp32", "bf16x3", "bf16"):
-            raise ValueError(f"compute_dtype must be 'fp32', 'bf16x3', 'bf16' or None, got {self.compute_dtype!r}")
+        # "fp8": the block linears on e4m3 operands (W8A8, FG_DTYPE_FP8); only ever chosen explicitly, never by autocast
+        if self.compute_dtype not in (None, "fp32", "bf16x3", "bf16", "fp8"):
+            raise ValueError(f"compute_dtype must be 'fp32', 'bf16x3', 'bf16', 'fp8' or None, got {self.compute_dtype!r}")
+        if self.compute_dtype == "fp8" and (hidden_size % 128 or int(hidden_size * mlp_ratio) % 128):
+            raise ValueError(f"compute_dtype='fp8' needs hidden_size and the MLP width to be multiples of 128, got {hidden_size} and "
+                             f"{int(hidden_size * mlp_ratio)}")
         cfg = _lib.fg_dit_config()
         cfg.input_size, cfg.patch_size, cfg.in_channels, cfg.hidden_size = input_size, patch_size, in_channels, hidden_size
         cfg.depth, cfg.num_heads, cfg.mlp_hidden = depth, num_heads, int(hidden_size * mlp_ratio)

@@ -329,6 +329,8 @@ class EDMPrecond(FastGenNetwork):
         self.r_timestep = bool(mk.get("r_timestep", False))
         self.dropout = mk.get("dropout", 0.10)
         self.compute_dtype = compute_dtype or os.environ.get("FASTGEN_AMD_COMPUTE_DTYPE") or None
+        if self.compute_dtype == "fp8":
+            raise ValueError("compute_dtype='fp8' is implemented for the DiT only (EDMPrecond: 'fp32', 'bf16x3', 'bf16' or None)")
         if self.compute_dtype not in (None, "fp32", "bf16x3", "bf16"):
             raise ValueError(f"compute_dtype must be 'fp32', 'bf16x3', 'bf16' or None, got {self.compute_dtype!r}")
 

@@ -79,6 +79,8 @@ class EDM2Precond(FastGenNetwork):
         self.compute_dtype = compute_dtype or os.environ.get("FASTGEN_AMD_COMPUTE_DTYPE") or None
         if self.compute_dtype == "fp32":
             raise NotImplementedError("EDM2 runs in the 'bf16x3' (default) and 'bf16' compute modes, not in exact fp32")
+        if self.compute_dtype == "fp8":
+            raise ValueError("compute_dtype='fp8' is implemented for the DiT only (EDM2Precond: 'bf16x3', 'bf16' or None)")
         if self.compute_dtype not in (None, "bf16x3", "bf16"):
             raise ValueError(f"compute_dtype must be 'bf16x3', 'bf16' or None, got {self.compute_dtype!r}")
         self.img_resolution = img_resolution

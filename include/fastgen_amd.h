@@ -45,6 +45,12 @@ extern "C" {
  * activations, statistics, attention, embedding MLP and preconditioning exactly as FG_DTYPE_F32.  Three bf16 MFMAs per product:
  * roofline 2.5 PFLOP/s / 3, against 157 TFLOP/s for FG_DTYPE_F32. */
 #define FG_DTYPE_BF16X3 2
+/* fp8 (DiT only): the four linears of every transformer block contract OCP e4m3fn operands (W8A8, v_mfma_scale_f32_16x16x128_f8f6f4
+ * with unit block scales, fp32 accumulate): weights quantised per output channel at pack time, activations per token on every call
+ * (scale = amax / 448, q = RNE(clamp(x * (448 / amax), -448, 448))); everything else - token tensors, attention, embeddings, the
+ * modulation GEMM, the final layer - exactly as FG_DTYPE_BF16.  hidden_size and mlp_hidden must be multiples of 128.  Roofline
+ * 5 PFLOP/s.  The EDM / EDM2 / ADM handles refuse it. */
+#define FG_DTYPE_FP8 3
 
 #define FG_SAMPLE_SDE 0  /* student_sample_type='sde'  (methods/model.py:358-359) */
 #define FG_SAMPLE_ODE 1  /* student_sample_type='ode'  (methods/model.py:360-361) */
@@ -567,6 +573,25 @@ FG_API int fg_op_attention_split(const void* q, const void* k, const void* v, vo
  * half the CUs split K (fp32 partial sums + a finishing pass).  Exposed for the parity tests and scripts/gemm_bench.py. */
 FG_API int fg_op_gemm_bf16(const void* a, const void* w, const float* bias, void* out, int m, int n, int k, int act, const float* gate,
                            int gate_stride, int gate_rows, const void* resid, int tile_order, void* stream);
+/* Row quantiser of the fp8 compute mode (gemm.hip): x [m][k] fp32 (dtype 0) or bf16 (dtype 1) -> q [m][k] OCP e4m3fn bytes and
+ * scale [m] fp32.  Per row: amax = max |x|; amax == 0: scale = 1 and q = 0; else scale = amax / 448.0f, q = e4m3fn_RNE(clamp(x *
+ * (448.0f / amax), -448, 448)) (IEEE fp32 divisions and product).  k % 128 == 0; anything else: FG_EINVAL before any launch. */
+FG_API int fg_op_quant_rows_fp8(int dtype, const void* x, void* q, float* scale, int64_t m, int k, void* stream);
+/* The token GEMM on e4m3fn operands (FG_DTYPE_FP8; gemm.hip, v_mfma_scale_f32_16x16x128_f8f6f4 with unit block scales):
+ * out[m][n] = resid[m][n] + gate[(m / gate_rows) * gate_stride + n] * act(a_scale[m] * w_scale[n] * sum_k a[m][k] w[n][k] + bias[n])
+ * with a [m][k], w [n][k] e4m3fn bytes (fg_op_quant_rows_fp8), a_scale [m], w_scale [n], bias, gate fp32, resid / out bf16, fp32
+ * accumulation; act 0 none, 1 GELU(tanh); bias, gate, resid nullable.  m >= 1, n % 16 == 0, k % 128 == 0, n k < 2^31; anything else:
+ * FG_EINVAL before any launch.  tile_order: 0 linear, 1 XCD-aware, 2 / 4 / 8 XCD columns over n; + 16 forces the register-staged
+ * kernel (default: the LDS-DMA ping-pong kernel where m, n, k >= 256).  Exposed for the parity tests and scripts/gemm_bench.py. */
+FG_API int fg_op_gemm_fp8(const void* a, const void* w, const float* bias, void* out, int m, int n, int k, int act, const float* gate,
+                          int gate_stride, int gate_rows, const void* resid, int tile_order, const float* a_scale, const float* w_scale,
+                          void* stream);
+/* LayerNorm (eps 1e-6, no affine) + adaLN modulation with the quantising store of the fp8 mode (dit.hip): y = LN(x[tok]) * (1 +
+ * mod[n][scale_off + c]) + mod[n][shift_off + c], n = tok / tokens_per_image, written as e4m3fn bytes y [ntok][d] + y_scale [ntok]
+ * (the scheme of fg_op_quant_rows_fp8 applied to the fp32 y).  x bf16 [ntok][d]; d in {384, 768, 1024, 1152}; mod_stride and the
+ * offsets multiples of 4. */
+FG_API int fg_op_dit_ln_modulate_fp8(const void* x, const float* mod, int mod_stride, int shift_off, int scale_off, void* y, float* y_scale,
+                                     int ntok, int d, int tokens_per_image, void* stream);
 /* The same token GEMM in the split-bf16 (FG_DTYPE_BF16X3) mode, the DiT's default: a [m][k] and w [n][k] fp32 are split into bf16
  * hi / lo planes (scratch allocated here, freed once the stream has drained: a test entry point, not a hot path) and contracted as
  * a_hi w_hi + a_hi w_lo + a_lo w_hi with fp32 accumulation; out[m][n] = resid[m][n] + gate[(m / gate_rows) * gate_stride + n] *
