@@ -69,6 +69,16 @@ class fg_wan_guided_sampler_config(ctypes.Structure):
     _fields_ = [("t_scale", c_double), ("context_noise", c_double), ("guidance", c_int)]
 
 
+class fg_attention_plan(ctypes.Structure):
+    _fields_ = [("kernel", c_int), ("nsplit", c_int), ("t_cut", c_int), ("sample_major", c_int), ("refusal", c_int), ("grid", c_int64),
+                ("scratch_bytes", c_size_t)]
+
+
+# token attention's kernel forms (fg_attention_plan.kernel, the `path` argument) and refusal codes
+FG_FA_TILE128, FG_FA_TILE128_W3, FG_FA_TILE128_REG, FG_FA_WIDE, FG_FA_WIDE_CUT, FG_FA_SEQ72, FG_FA_TILE72, FG_FA_TILE72_W3 = range(1, 9)
+FG_FA_REFUSE_ARG, FG_FA_REFUSE_OFFSET, FG_FA_REFUSE_PATH = 1, 2, 3
+
+
 # name -> (restype, argtypes); every symbol include/fastgen_amd.h declares
 SIGNATURES = {
     "fg_last_error": (c_char_p, []),
@@ -192,6 +202,9 @@ SIGNATURES = {
     "fg_op_randn": (c_int, [c_void_p, c_int64, c_uint64, c_uint64, c_void_p]),
     "fg_op_attention": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),
     "fg_op_attention_split": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
+    "fg_op_attention_plan": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, POINTER(fg_attention_plan)]),
+    "fg_op_attention_ex": (c_int, [c_void_p, c_int, c_int64, c_void_p, c_void_p, c_int, c_int64, c_void_p, c_int, c_int64, c_int, c_int, c_int,
+                                   c_int, c_int, c_int, c_int, c_int, c_void_p]),
     "fg_op_gemm_bf16": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_int, c_void_p,
                                 c_int, c_void_p]),
     "fg_op_quant_rows_fp8": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p]),

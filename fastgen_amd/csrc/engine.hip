@@ -1608,21 +1608,45 @@ int fg_op_randn(float* out, int64_t total, uint64_t seed, uint64_t offset, void*
     HIP_TRY(launch_randn(out, total, seed, offset, nullptr, (hipStream_t)stream));
     return FG_OK;
 }
-int fg_op_attention_split(const void* q, const void* k, const void* v, void* out, int batch, int heads, int head_dim, int lq, int lkv, int nsplit,
-                          void* stream) {
-    if (!q || !k || !v || !out || batch <= 0 || heads <= 0 || lq <= 0 || lkv <= 0 || (head_dim != 128 && head_dim != 72))
-        return fail(FG_EINVAL, "fg_op_attention: bad argument (head_dim 128 or 72)");
-    if (nsplit < 0 || nsplit > 8) return fail(FG_EINVAL, "fg_op_attention_split: nsplit must be in [0, 8]");
-    const int D = heads * head_dim;
+int fg_op_attention_plan(int head_dim, int batch, int heads, int lq, int lkv, int ldk, int use_scratch, int force_split, int path,
+                         fg_attention_plan* plan) {
+    if (!plan) return fail(FG_EINVAL, "fg_op_attention_plan: null plan");
+    const FaPlan p = fa_plan(head_dim, batch, heads, lq, lkv, ldk, use_scratch != 0, force_split, path);
+    plan->kernel = p.kernel, plan->nsplit = p.nsplit, plan->t_cut = p.t_cut, plan->sample_major = p.sample_major, plan->refusal = p.refusal;
+    plan->grid = (int64_t)p.grid;
+    plan->scratch_bytes = p.refusal ? 0 : fa128_scratch_bytes(batch, heads, lq);
+    return FG_OK;
+}
+int fg_op_attention_ex(const void* q, int ldq, int64_t q_bs, const void* k, const void* v, int ldk, int64_t kv_bs, void* out, int ldo,
+                       int64_t o_bs, int batch, int heads, int head_dim, int lq, int lkv, int use_scratch, int force_split, int path,
+                       void* stream) {
+    if (!q || !k || !v || !out || ldq <= 0 || ldo <= 0 || (ldq % 8) || (ldo % 4) || q_bs < 0 || kv_bs < 0 || o_bs < 0)
+        return fail(FG_EINVAL, "fg_op_attention: bad argument (null pointer, ldq %% 8, ldo %% 4 or a negative stride)");
+    const FaPlan p = fa_plan(head_dim, batch, heads, lq, lkv, ldk, use_scratch != 0, force_split, path);
+    if (p.refusal == FG_FA_REFUSE_OFFSET) return fail(FG_EINVAL, "fg_op_attention: lkv * ldk * 2 bytes exceed the kernels' 32-bit buffer offsets");
+    if (p.refusal == FG_FA_REFUSE_PATH)
+        return fail(FG_EINVAL, "fg_op_attention: kernel form %d cannot serve head_dim %d, batch %d, heads %d, lq %d, lkv %d, scratch %d, force_split %d",
+                    path, head_dim, batch, heads, lq, lkv, use_scratch != 0, force_split);
+    if (p.refusal)
+        return fail(FG_EINVAL, "fg_op_attention: bad argument (head_dim 128 or 72, counts > 0, ldk %% 8, force_split in [0, 8] and > 1 only with scratch)");
     // key-split scratch for short grids (freed after the stream has drained: a test entry point, not a hot path)
     void* scratch = nullptr;
-    HIP_TRY(hipMalloc(&scratch, fa128_scratch_bytes(batch, heads, lq)));
-    const int rc = launch_fa(head_dim, q, D, (int64_t)lq * D, k, v, D, (int64_t)lkv * D, out, D, (int64_t)lq * D, batch, heads, lq, lkv,
-                             (hipStream_t)stream, scratch, nsplit);
+    if (use_scratch) HIP_TRY(hipMalloc(&scratch, fa128_scratch_bytes(batch, heads, lq)));
+    const int rc = launch_fa(head_dim, q, ldq, q_bs, k, v, ldk, kv_bs, out, ldo, o_bs, batch, heads, lq, lkv, (hipStream_t)stream, scratch,
+                             force_split, path);
     (void)hipStreamSynchronize((hipStream_t)stream);
     (void)hipFree(scratch);
     HIP_TRY(rc);
     return FG_OK;
+}
+int fg_op_attention_split(const void* q, const void* k, const void* v, void* out, int batch, int heads, int head_dim, int lq, int lkv, int nsplit,
+                          void* stream) {
+    if (batch <= 0 || heads <= 0 || lq <= 0 || lkv <= 0 || (head_dim != 128 && head_dim != 72))
+        return fail(FG_EINVAL, "fg_op_attention: bad argument (head_dim 128 or 72)");
+    if (nsplit < 0 || nsplit > 8) return fail(FG_EINVAL, "fg_op_attention_split: nsplit must be in [0, 8]");
+    const int D = heads * head_dim;
+    return fg_op_attention_ex(q, D, (int64_t)lq * D, k, v, D, (int64_t)lkv * D, out, D, (int64_t)lq * D, batch, heads, head_dim, lq, lkv, 1, nsplit,
+                              0, stream);
 }
 int fg_op_attention(const void* q, const void* k, const void* v, void* out, int batch, int heads, int head_dim, int lq, int lkv, void* stream) {
     return fg_op_attention_split(q, k, v, out, batch, heads, head_dim, lq, lkv, 0, stream);

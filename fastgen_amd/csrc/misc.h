@@ -214,9 +214,18 @@ int launch_rms_rope(int D, const void* src, int ld_src, const float* w, float ep
 // [B][Lkv] rows of ldk, out [B][Lq] rows of ldo; *_bs = elements between batches
 // scratch: fa128_scratch_bytes(B, heads, Lq) bytes for key-split partials (nullptr: never split)
 size_t fa128_scratch_bytes(int B, int heads, int Lq);
+// What launch_fa decides, as a plain host function (no launch, no GPU): the kernel form (FG_FA_* of include/fastgen_amd.h), the number
+// of key splits, fa2_kernel's uneven cut (0: none), fa_kernel's / fa72_seq_kernel's sample-major workgroup map, the grid of the
+// attention kernel and why the launch is refused (FG_FA_REFUSE_*, 0: it is not).  path 0: the launcher's own choice (the
+// FASTGEN_AMD_FA_* switches, read once per process, included); path = one of FG_FA_*: that form or a refusal, never another form.
+struct FaPlan {
+    int refusal, kernel, nsplit, t_cut, sample_major;
+    unsigned grid;
+};
+FaPlan fa_plan(int hd, int B, int heads, int Lq, int Lkv, int ldk, bool scratch, int force_split, int path);
 // the same kernel for head dim hd = 128 | 72 (DiT-XL/2's 16 x 72)
 int launch_fa(int hd, const void* q, int ldq, int64_t q_bs, const void* k, const void* v, int ldk, int64_t kv_bs, void* out, int ldo, int64_t o_bs,
-              int B, int heads, int Lq, int Lkv, hipStream_t s, void* scratch = nullptr, int force_split = 0);
+              int B, int heads, int Lq, int Lkv, hipStream_t s, void* scratch = nullptr, int force_split = 0, int path = 0);
 int launch_fa128(const void* q, int ldq, int64_t q_bs, const void* k, const void* v, int ldk, int64_t kv_bs, void* out, int ldo, int64_t o_bs,
                  int B, int heads, int Lq, int Lkv, hipStream_t s, void* scratch = nullptr);
 int launch_wan_final(int D, const void* x, const float* mod, const float* w, const float* bias, float* out, int ntok, int Fr, int gh, int gw, int C,

@@ -15,6 +15,7 @@
 #include <type_traits>
 
 #include "common.h"
+#include "../../include/fastgen_amd.h"
 #include "misc.h"
 
 namespace {
@@ -1440,35 +1441,121 @@ int launch_rms_rope(int D, const void* src, int ld_src, const float* w, float ep
 // partial outputs and log-sum-exps: fa128_scratch_bytes(B, heads, Lq).
 constexpr int FA_MAX_SPLIT = 8;
 size_t fa128_scratch_bytes(int B, int heads, int Lq) { return (size_t)FA_MAX_SPLIT * B * Lq * ((size_t)heads * 128 + heads) * 4 + 256; }
-int launch_fa(int hd, const void* q, int ldq, int64_t q_bs, const void* k, const void* v, int ldk, int64_t kv_bs, void* out, int ldo, int64_t o_bs,
-              int B, int heads, int Lq, int Lkv, hipStream_t s, void* scratch, int force_split) {
-    if ((hd != 128 && hd != 72) || Lq <= 0 || Lkv <= 0 || (ldq % 8) || (ldk % 8) || (ldo % 4)) return (int)hipErrorInvalidValue;
-    if (force_split < 0 || force_split > FA_MAX_SPLIT || (force_split > 1 && !scratch)) return (int)hipErrorInvalidValue;
+// The launcher's switches: what the FASTGEN_AMD_FA_* variables set (read once per process), or what a path override stands for.
+struct FaSwitches {
+    int dma;    // head dim 128: LDS-DMA ring (1, default) | two-deep register prefetch (0): FASTGEN_AMD_FA_DMA
+    int minw;   // waves per SIMD the kernel is compiled for (register budget 256 | 168): FASTGEN_AMD_FA_WAVES = 2 (default: room for the tile's fragments) | 3
+    int seq72;  // head dim 72, <= 256 keys: the whole-sequence kernel (1, default) | fa_kernel<72> (0): FASTGEN_AMD_FA_SEQ72
+    int wide;   // FASTGEN_AMD_FA_WIDE = 0 | 1 forces fa_kernel<128> | fa2_kernel for every length (-1, default: fa2_kernel from 1024 keys)
+    int cut;    // FASTGEN_AMD_FA_CUT = 0: even splits by the cost model instead of fa2_kernel's uneven cut (A / B)
+};
+static FaSwitches fa_env_switches() {
+    static const FaSwitches sw = [] {
+        FaSwitches w;
+        const char* e = getenv("FASTGEN_AMD_FA_DMA");
+        w.dma = (e && e[0] == '0') ? 0 : 1;
+        e = getenv("FASTGEN_AMD_FA_WAVES");
+        w.minw = (e && e[0] == '3') ? 3 : 2;
+        e = getenv("FASTGEN_AMD_FA_SEQ72");
+        w.seq72 = (e && e[0] == '0') ? 0 : 1;
+        e = getenv("FASTGEN_AMD_FA_WIDE");
+        w.wide = !e ? -1 : (e[0] == '1' ? 1 : 0);
+        e = getenv("FASTGEN_AMD_FA_CUT");
+        w.cut = (e && e[0] == '0') ? 0 : 1;
+        return w;
+    }();
+    return sw;
+}
+// the switch settings under which the launcher's own rules arrive at kernel form `path` wherever that form can serve the shape
+static bool fa_path_switches(int path, int hd, FaSwitches& w) {
+    w = FaSwitches{1, 2, 1, 0, 1};
+    switch (path) {
+        case FG_FA_TILE128: break;
+        case FG_FA_TILE128_W3: w.minw = 3; break;
+        case FG_FA_TILE128_REG: w.dma = 0; break;
+        case FG_FA_WIDE: w.wide = 1, w.cut = 0; break;
+        case FG_FA_WIDE_CUT: w.wide = 1; break;
+        case FG_FA_SEQ72: break;
+        case FG_FA_TILE72: w.seq72 = 0; break;
+        case FG_FA_TILE72_W3: w.seq72 = 0, w.minw = 3; break;
+        default: return false;
+    }
+    return hd == (path <= FG_FA_WIDE_CUT ? 128 : 72);
+}
+FaPlan fa_plan(int hd, int B, int heads, int Lq, int Lkv, int ldk, bool scratch, int force_split, int path) {
+    const auto refuse = [](int why) { return FaPlan{why, 0, 0, 0, 0, 0u}; };
+    if ((hd != 128 && hd != 72) || B <= 0 || heads <= 0 || Lq <= 0 || Lkv <= 0 || ldk <= 0 || (ldk % 8)) return refuse(FG_FA_REFUSE_ARG);
+    if (force_split < 0 || force_split > FA_MAX_SPLIT || (force_split > 1 && !scratch)) return refuse(FG_FA_REFUSE_ARG);
+    FaSwitches sw = fa_env_switches();
+    if (path != 0 && !fa_path_switches(path, hd, sw)) return refuse(path < 0 || path > FG_FA_TILE72_W3 ? FG_FA_REFUSE_ARG : FG_FA_REFUSE_PATH);
     const int qtiles = (Lq + 127) / 128, ktiles = (Lkv + 31) / 32;
     // key splits: units (sample, head, split) are dealt to the 8 XCDs (fa_kernel's mapping: 32 CUs each, two workgroups resident per CU at
     // half speed each).  Cost in tile iterations (~1.2 us) = workgroups on the fullest CU / 2 x (key tiles per split + ~6 of prologue
     // and epilogue) + the merge pass (fp32 partial outputs read back at ~5 TB/s); every split keeps >= 8 key tiles.
-    int nsplit = 1;
+    FaPlan p{0, 0, 1, 0, 0, 0u};
     if (force_split > 0) {  // (parity tests: the splits of one launch against another's)
-        nsplit = force_split < ktiles ? force_split : ktiles;
+        p.nsplit = force_split < ktiles ? force_split : ktiles;
     } else if (scratch) {
         double best = -1.0;
         for (int c = 1; c <= FA_MAX_SPLIT && (c == 1 || ktiles / c >= 8); ++c) {
             const long long ux = ((long long)B * heads * c + 7) / 8, per_cu = (ux * qtiles + 31) / 32;
             const double cost = 0.5 * (double)per_cu * ((ktiles + c - 1) / c + 6) + (c > 1 ? 3.0 + 6.7e-7 * c * B * (double)Lq * heads * hd : 0.0);
-            if (best < 0.0 || cost < best) best = cost, nsplit = c;
+            if (best < 0.0 || cost < best) best = cost, p.nsplit = c;
         }
     }
+    p.sample_major = (p.nsplit == 1 && B >= 8 && Lq <= 1024) ? 1 : 0;
+    const long long units = p.sample_major ? (long long)((B + 7) / 8) * 8 * heads : (long long)B * heads * p.nsplit;
+    p.grid = (unsigned)(((units + 7) / 8) * 8 * qtiles);
+    // head dim 128: fa2_kernel (64 queries per wave, one wave per SIMD) where it measures ahead - self-attention over >= 1024 keys:
+    // 165 / 596 / 1005 us against fa_kernel's 186 / 608 / 1033 at 4680 queries x 4680 / 18720 / 32760 keys, the 21-frame loop 1.168 s
+    // against 1.180 (profiles/r03_fa2_experiments.txt); the text cross-attention (512 keys) stays with fa_kernel (42 us against 50).
+    const bool use_wide = sw.wide == 1 || (sw.wide == -1 && Lkv >= 1024);
+    if (hd == 128) {
+        if ((size_t)Lkv * ldk * 2 >= ((size_t)1 << 31)) return refuse(FG_FA_REFUSE_OFFSET);  // (buffer-resource offsets are 32-bit)
+        if (use_wide && sw.dma && !p.sample_major) {
+            const int qt2 = (Lq + 255) / 256;
+            // fewer workgroups than CUs (one per CU: 256): the uneven two-way split (fa2_kernel) - the long pieces last f of the keys with
+            // f = P (L + c) / (L CUs), c ~ 6 tiles of prologue / epilogue per piece: then the CUs - P spare CUs get through the P short
+            // pieces while the long ones run
+            const long long P = (long long)B * heads * qt2;
+            p.kernel = FG_FA_WIDE;
+            p.grid = (unsigned)(((units + 7) / 8) * 8 * qt2);
+            if (sw.cut && force_split == 0 && scratch && P <= 248 && ktiles >= 32) {
+                const double f = (double)P * (ktiles + 6) / ((double)ktiles * 256.0);
+                if (f < 0.97) {
+                    p.t_cut = (int)(f * ktiles) + 1;
+                    if (p.t_cut < (ktiles + 1) / 2) p.t_cut = (ktiles + 1) / 2;
+                    // both pieces hold a key tile: f ktiles reaches ktiles - 1 at P = 209, ktiles = 32, and a piece [ktiles, ktiles)
+                    // would start its DMA past the keys and leave 0 * inf in its partial output
+                    if (p.t_cut > ktiles - 1) p.t_cut = ktiles - 1;
+                    p.kernel = FG_FA_WIDE_CUT;
+                    p.nsplit = 2;
+                    p.grid = (unsigned)(2 * 8 * ((P + 7) / 8));
+                }
+            }
+        } else {
+            p.kernel = !sw.dma ? FG_FA_TILE128_REG : (sw.minw == 3 ? FG_FA_TILE128_W3 : FG_FA_TILE128);
+        }
+    } else if (Lkv <= 256 && !force_split && sw.seq72) {
+        // (every split of the cost model keeps >= 8 key tiles: one split here.)  The kernel's own map is the sample-major one.
+        p.kernel = FG_FA_SEQ72;
+        p.sample_major = 1;
+        p.grid = (unsigned)(((B + 7) / 8) * 8 * heads * qtiles);
+    } else {
+        p.kernel = sw.minw == 3 ? FG_FA_TILE72_W3 : FG_FA_TILE72;
+    }
+    if (path != 0 && p.kernel != path) return refuse(FG_FA_REFUSE_PATH);
+    return p;
+}
+int launch_fa(int hd, const void* q, int ldq, int64_t q_bs, const void* k, const void* v, int ldk, int64_t kv_bs, void* out, int ldo, int64_t o_bs,
+              int B, int heads, int Lq, int Lkv, hipStream_t s, void* scratch, int force_split, int path) {
+    if ((ldq % 8) || (ldo % 4)) return (int)hipErrorInvalidValue;
+    const FaPlan p = fa_plan(hd, B, heads, Lq, Lkv, ldk, scratch != nullptr, force_split, path);
+    if (p.refusal) return (int)hipErrorInvalidValue;
+    const int nsplit = p.nsplit, sample_major = p.sample_major;
     float* po = (float*)scratch;
     float* plse = po ? po + (size_t)FA_MAX_SPLIT * B * Lq * heads * hd : nullptr;
-    const int sample_major = (nsplit == 1 && B >= 8 && Lq <= 1024) ? 1 : 0;
-    const long long units = sample_major ? (long long)((B + 7) / 8) * 8 * heads : (long long)B * heads * nsplit;
-    dim3 g((unsigned)(((units + 7) / 8) * 8 * qtiles));
-    static int use_dma = -1;  // head dim 128: LDS-DMA ring (1, default) | two-deep register prefetch (0): FASTGEN_AMD_FA_DMA
-    if (use_dma < 0) {
-        const char* e = getenv("FASTGEN_AMD_FA_DMA");
-        use_dma = (e && e[0] == '0') ? 0 : 1;
-    }
+    const dim3 g(p.grid);
 #ifdef FG_TIMING_BUILD
     static int abl = -1;  // FASTGEN_AMD_FA_ABL bit mask, see fa_kernel's pipelined step (libfastgen_amd_timing.so only)
     if (abl < 0) {
@@ -1476,66 +1563,26 @@ int launch_fa(int hd, const void* q, int ldq, int64_t q_bs, const void* k, const
         abl = e ? atoi(e) : 0;
     }
 #endif
-    static int minw = -1;  // waves per SIMD the kernel is compiled for (register budget 256 | 168): FASTGEN_AMD_FA_WAVES = 2 (default: room for the tile's fragments) | 3
-    if (minw < 0) {
-        const char* e = getenv("FASTGEN_AMD_FA_WAVES");
-        minw = (e && e[0] == '3') ? 3 : 2;
-    }
-    static int seq72 = -1;  // head dim 72, <= 256 keys: the whole-sequence kernel (1, default) | fa_kernel<72> (0): FASTGEN_AMD_FA_SEQ72
-    if (seq72 < 0) {
-        const char* e = getenv("FASTGEN_AMD_FA_SEQ72");
-        seq72 = (e && e[0] == '0') ? 0 : 1;
-    }
     const float sc = 1.44269504088896341f / sqrtf((float)hd);
 #define FA_GO(HD, MW, LDS, DM)                                                                                                              \
     hipLaunchKernelGGL((fa_kernel<HD, MW, DM>), g, dim3(256), LDS, s, (const __bf16*)q, ldq, q_bs, (const __bf16*)k, (const __bf16*)v, ldk, kv_bs, \
                        (__bf16*)out, ldo, o_bs, Lq, Lkv, sc, nsplit, po, plse, heads, B, sample_major FA_ABL_ARG)
-    // head dim 128: fa2_kernel (64 queries per wave, one wave per SIMD) where it measures ahead - self-attention over >= 1024 keys:
-    // 165 / 596 / 1005 us against fa_kernel's 186 / 608 / 1033 at 4680 queries x 4680 / 18720 / 32760 keys, the 21-frame loop 1.168 s
-    // against 1.180 (profiles/r03_fa2_experiments.txt); the text cross-attention (512 keys) stays with fa_kernel (42 us against 50).
-    // FASTGEN_AMD_FA_WIDE = 0 | 1 forces one of them for every length.
-    static int wide = -2;
-    if (wide == -2) {
-        const char* e = getenv("FASTGEN_AMD_FA_WIDE");
-        wide = !e ? -1 : (e[0] == '1' ? 1 : 0);
-    }
-    const bool use_wide = wide == 1 || (wide == -1 && Lkv >= 1024);
-    if (hd == 128) {
-        if ((size_t)Lkv * ldk * 2 >= ((size_t)1 << 31)) return (int)hipErrorInvalidValue;  // (buffer-resource offsets are 32-bit)
-        if (use_wide && use_dma && !sample_major) {
-            const int qt2 = (Lq + 255) / 256;
-            // fewer workgroups than CUs (one per CU: 256): the uneven two-way split (fa2_kernel) - the long pieces last f of the keys with
-            // f = P (L + c) / (L CUs), c ~ 6 tiles of prologue / epilogue per piece: then the CUs - P spare CUs get through the P short
-            // pieces while the long ones run
-            const long long P = (long long)B * heads * qt2;
-            int t_cut = 0;
-            unsigned grid = (unsigned)(((units + 7) / 8) * 8 * qt2);
-            static int cut = -1;  // FASTGEN_AMD_FA_CUT = 0: even splits by the cost model above instead (A / B)
-            if (cut < 0) {
-                const char* e = getenv("FASTGEN_AMD_FA_CUT");
-                cut = (e && e[0] == '0') ? 0 : 1;
-            }
-            if (cut && force_split == 0 && scratch && P <= 248 && ktiles >= 32) {
-                const double f = (double)P * (ktiles + 6) / ((double)ktiles * 256.0);
-                if (f < 0.97) {
-                    t_cut = (int)(f * ktiles) + 1;
-                    if (t_cut < (ktiles + 1) / 2) t_cut = (ktiles + 1) / 2;
-                    nsplit = 2;
-                    grid = (unsigned)(2 * 8 * ((P + 7) / 8));
-                }
-            }
-            hipLaunchKernelGGL(fa2_kernel, dim3(grid), dim3(256), 6 * 16384, s, (const __bf16*)q, ldq, q_bs, (const __bf16*)k, (const __bf16*)v, ldk,
-                               kv_bs, (__bf16*)out, ldo, o_bs, Lq, Lkv, sc, nsplit, po, plse, heads, B, t_cut FA_ABL_ARG);
-        } else if (!use_dma) FA_GO(128, 2, 32768, false);
-        else if (minw == 3) FA_GO(128, 3, 65536, true);
-        else FA_GO(128, 2, 65536, true);
-    } else if (Lkv <= 256 && !force_split && seq72) {
-        const int qt = (Lq + 127) / 128;
-        hipLaunchKernelGGL(fa72_seq_kernel, dim3((unsigned)(((B + 7) / 8) * 8 * heads * qt)), dim3(256), 2 * 256 * 144 + 64, s, (const __bf16*)q, ldq,
-                           q_bs, (const __bf16*)k, (const __bf16*)v, ldk, kv_bs, (__bf16*)out, ldo, o_bs, Lq, Lkv, sc, heads, B);
-    } else {
-        if (minw == 3) FA_GO(72, 3, 2 * (32 * 144 + 32 * 192), false);
-        else FA_GO(72, 2, 2 * (32 * 144 + 32 * 192), false);
+    switch (p.kernel) {
+        case FG_FA_WIDE:
+        case FG_FA_WIDE_CUT:
+            hipLaunchKernelGGL(fa2_kernel, g, dim3(256), 6 * 16384, s, (const __bf16*)q, ldq, q_bs, (const __bf16*)k, (const __bf16*)v, ldk, kv_bs,
+                               (__bf16*)out, ldo, o_bs, Lq, Lkv, sc, nsplit, po, plse, heads, B, p.t_cut FA_ABL_ARG);
+            break;
+        case FG_FA_TILE128_REG: FA_GO(128, 2, 32768, false); break;
+        case FG_FA_TILE128_W3: FA_GO(128, 3, 65536, true); break;
+        case FG_FA_TILE128: FA_GO(128, 2, 65536, true); break;
+        case FG_FA_SEQ72:
+            hipLaunchKernelGGL(fa72_seq_kernel, g, dim3(256), 2 * 256 * 144 + 64, s, (const __bf16*)q, ldq, q_bs, (const __bf16*)k,
+                               (const __bf16*)v, ldk, kv_bs, (__bf16*)out, ldo, o_bs, Lq, Lkv, sc, heads, B);
+            break;
+        case FG_FA_TILE72_W3: FA_GO(72, 3, 2 * (32 * 144 + 32 * 192), false); break;
+        case FG_FA_TILE72: FA_GO(72, 2, 2 * (32 * 144 + 32 * 192), false); break;
+        default: return (int)hipErrorInvalidValue;
     }
 #undef FA_GO
     if (nsplit > 1) {

@@ -563,6 +563,41 @@ FG_API int fg_op_attention(const void* q, const void* k, const void* v, void* ou
  * log-sum-exp.  For the parity tests: the split paths against each other at the video DiT's full sequence lengths. */
 FG_API int fg_op_attention_split(const void* q, const void* k, const void* v, void* out, int batch, int heads, int head_dim, int lq, int lkv,
                                  int nsplit, void* stream);
+/* The kernel forms of token attention (wan.hip): what fg_attention_plan.kernel names and what `path` selects. */
+#define FG_FA_TILE128 1     /* fa_kernel<128, 2, true>: 128-query tiles, LDS-DMA ring (the launcher's choice below 1024 keys) */
+#define FG_FA_TILE128_W3 2  /* fa_kernel<128, 3, true>: the same compiled for three waves per SIMD (FASTGEN_AMD_FA_WAVES=3) */
+#define FG_FA_TILE128_REG 3 /* fa_kernel<128, 2, false>: register prefetch instead of LDS-DMA (FASTGEN_AMD_FA_DMA=0) */
+#define FG_FA_WIDE 4        /* fa2_kernel, 256-query tiles, even key splits (>= 1024 keys; FASTGEN_AMD_FA_WIDE=1, FASTGEN_AMD_FA_CUT=0) */
+#define FG_FA_WIDE_CUT 5    /* fa2_kernel with the uneven two-way cut at key tile t_cut (grids of fewer workgroups than CUs) */
+#define FG_FA_SEQ72 6       /* fa72_seq_kernel: head dim 72, at most 256 keys, all of them in one pass */
+#define FG_FA_TILE72 7      /* fa_kernel<72, 2, false> (FASTGEN_AMD_FA_SEQ72=0, more than 256 keys or a forced split) */
+#define FG_FA_TILE72_W3 8   /* fa_kernel<72, 3, false> (FASTGEN_AMD_FA_WAVES=3) */
+#define FG_FA_REFUSE_ARG 1    /* bad argument (head_dim, a count <= 0, ldk % 8, force_split out of [0, 8] or > 1 without scratch) */
+#define FG_FA_REFUSE_OFFSET 2 /* head dim 128: lkv * ldk * 2 bytes do not fit the kernels' 32-bit buffer offsets */
+#define FG_FA_REFUSE_PATH 3   /* the kernel form `path` names cannot serve this shape (it is never redirected to another) */
+typedef struct fg_attention_plan {
+    int kernel;           /* FG_FA_* */
+    int nsplit;           /* key splits; > 1: partial outputs in scratch + the merge pass */
+    int t_cut;            /* FG_FA_WIDE_CUT: the pieces are key tiles [0, t_cut) and [t_cut, ceil(lkv / 32)); else 0 */
+    int sample_major;     /* workgroup map: all heads of a sample on one XCD (batch >= 8, lq <= 1024, one split; FG_FA_SEQ72 always) */
+    int refusal;          /* 0 or FG_FA_REFUSE_*: the other members are then zero */
+    int64_t grid;         /* workgroups of the attention kernel */
+    size_t scratch_bytes; /* what use_scratch allocates: room for 8 splits' fp32 partial outputs and log-sum-exps */
+} fg_attention_plan;
+/* What token attention would launch for this shape: the launcher's decisions and nothing else (no launch, no GPU needed).  ldk: row
+ * pitch of k / v in elements; use_scratch 0: never split; force_split as fg_op_attention_split's nsplit; path 0: the launcher's own
+ * choice (the FASTGEN_AMD_FA_* switches, read once per process, included), FG_FA_*: that form or refusal FG_FA_REFUSE_PATH.
+ * Returns FG_OK with *plan filled, refusals included. */
+FG_API int fg_op_attention_plan(int head_dim, int batch, int heads, int lq, int lkv, int ldk, int use_scratch, int force_split, int path,
+                                fg_attention_plan* plan);
+/* fg_op_attention on the layouts the engines pass: q / k / v / out rows of ldq / ldk / ldk / ldo elements (head h at column
+ * h * head_dim), q_bs / kv_bs / o_bs elements between samples - packed q|k|v rows (ldq = ldk = 3 D, v = k + D), interleaved k|v
+ * (ldk = 2 D), a KV cache whose kv_bs exceeds lkv * ldk.  ldq % 8 == ldk % 8 == ldo % 4 == 0, 16-byte aligned q / k / v, 8-byte out.
+ * use_scratch, force_split, path as in fg_op_attention_plan; a refused plan is FG_EINVAL with its reason in fg_last_error().
+ * fg_op_attention(_split) is this call with contiguous tensors, scratch and path 0.  For the per-element parity tests. */
+FG_API int fg_op_attention_ex(const void* q, int ldq, int64_t q_bs, const void* k, const void* v, int ldk, int64_t kv_bs, void* out, int ldo,
+                              int64_t o_bs, int batch, int heads, int head_dim, int lq, int lkv, int use_scratch, int force_split, int path,
+                              void* stream);
 /* The transformer blocks' token GEMM in the bf16 compute mode (gemm.hip; reference: the nn.Linear calls of DiTBlock,
  * fastgen/networks/DiT/network.py:168-198, under bf16 autocast): out[m][n] = resid[m][n] + gate[(m / gate_rows) * gate_stride + n] *
  * act(sum_k a[m][k] w[n][k] + bias[n]) with a [m][k], w [n][k], resid / out [m][n] in bf16, fp32 accumulation, bias / gate fp32;
