@@ -18,6 +18,8 @@ FG_SCHEDULE_EDM, FG_SCHEDULE_RF = 0, 1
 FG_DROP_PRECOND_INPUT, FG_DROP_PRECOND_OUTPUT = 1, 2
 FG_BWD_DECODER, FG_BWD_ENCODER, FG_BWD_EMBED = 1, 2, 4
 FG_MODEL_SONGUNET, FG_MODEL_DHARIWAL = 0, 1
+(FG_TRAIN_OP_HEAD_GRAD, FG_TRAIN_OP_STEM_OPERAND, FG_TRAIN_OP_INPUT_GRAD, FG_TRAIN_OP_ADD_NCHW_TO_NHWC, FG_TRAIN_OP_SILU_BWD, FG_TRAIN_OP_JVP_COEF,
+ FG_TRAIN_OP_JVP_EMBED, FG_TRAIN_OP_JVP_INPUT, FG_TRAIN_OP_JVP_OUTPUT) = range(9)  # fg_op_train_elementwise
 
 
 class fg_edm_config(ctypes.Structure):
@@ -195,6 +197,26 @@ SIGNATURES = {
     "fg_edm_jvp": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
                            c_void_p, c_size_t, c_void_p]),
     "fg_edm_set_dropout": (c_int, [c_void_p, c_float, c_uint64]),
+    "fg_op_gn_workspace_bytes": (c_size_t, [c_int, c_int]),
+    "fg_op_gn_act": (c_int, [c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_float, c_void_p, c_int, c_int, c_int,
+                             c_float, ctypes.c_uint32, c_uint64, c_void_p, c_size_t, c_void_p]),
+    "fg_op_gn_backward": (c_int, [c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_float, c_void_p,
+                                  c_void_p, c_void_p, c_int, c_float, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float,
+                                  ctypes.c_uint32, c_uint64, c_void_p, c_size_t, c_void_p]),
+    "fg_op_gn_jvp": (c_int, [c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_int, c_int,
+                             c_float, ctypes.c_uint32, c_uint64, c_void_p, c_size_t, c_void_p]),
+    "fg_op_attention_backward_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "fg_op_attention_backward": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int,
+                                         c_int, c_void_p, c_size_t, c_void_p]),
+    "fg_op_attention_jvp": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
+                                    c_void_p, c_size_t, c_void_p]),
+    "fg_op_colsum": (c_int, [c_int, c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_float, c_int, c_void_p]),
+    "fg_op_batchsum_add": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
+    "fg_op_linear_backward": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_int,
+                                      c_void_p]),
+    "fg_op_dgrad_weights": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
+    "fg_op_train_elementwise": (c_int, [c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
+                                        c_double, c_double, c_int, c_void_p]),
     "fg_op_dropout_mask": (c_int, [c_void_p, c_int64, c_float, ctypes.c_uint32, c_uint64, c_void_p]),
     "fg_edm_set_augment": (c_int, [c_void_p, c_void_p]),
     "fg_edm_set_training": (c_int, [c_void_p, c_int]),

@@ -329,6 +329,70 @@ FG_API int fg_edm_set_augment(fg_edm* h, const float* augment_labels);
 FG_API int fg_edm_set_dropout(fg_edm* h, float p, uint64_t seed);
 FG_API int fg_op_dropout_mask(float* out, int64_t total, float p, uint32_t block_index, uint64_t seed, void* stream);
 
+/* ---- EDM training kernels, one op per call (bwd.hip, attn_bwd.hip): the launchers fg_edm_run_block_backward / fg_edm_backward /
+ * fg_edm_jvp run, without a handle, for per-op parity tests.  Activation tensors are void* NHWC in the storage type `dtype`: 0 fp32
+ * (the bf16x3 mode's storage), 1 bf16.  Every argument is checked before anything is launched; a shape the launcher cannot serve is
+ * FG_EINVAL.  Dropout arguments (p, block index, seed) as fg_op_dropout_mask; p = 0: off.
+ *
+ * GroupNorm ops: x = the virtual concat [x1 (c1) | x2 (c2)], c1 / c2 multiples of 8, groups = min(32, C / 4); the statistics are
+ * computed by the call itself (launch_gn_coeffs).  workspace: fg_op_gn_workspace_bytes(batch, c1 + c2), 16-byte aligned.
+ * fg_op_gn_act: out [batch][res][res][C] = R(act(x)) * keep, act = silu(a x + b) (mode 0), a x + b (mode 1), x (mode 2: gamma, beta and
+ * the workspace unused); R: rm 0 none, 1 mean of 2x2 (x at 2 res), 2 nearest 2x (x at res / 2).
+ * fg_op_gn_backward: dx (+)= d(act(x))/dx applied to R^T(dact) * keep [+ add_scale * R^T(add)], x at `res`, dact (pixel pitch cd >= C)
+ * and add (nullable, pitch ca) at res (rm 0), res / 2 (rm 1) or 2 res (rm 2); mode 0 / 1 as above.  dgamma / dbeta (nullable, [C]) are
+ * accumulated.  dx2 == NULL: dx is [batch][res * res][C]; otherwise dx takes channels [0, c1) and dx2 [c1, C), both dense.
+ * fg_op_gn_jvp: out = the tangent of act(x) along xd (dense [batch][res * res][C]) * keep; mode 0 / 1. */
+FG_API size_t fg_op_gn_workspace_bytes(int batch, int c);
+FG_API int fg_op_gn_act(int dtype, int mode, const void* x1, int c1, const void* x2, int c2, const float* gamma, const float* beta, float eps,
+                        void* out, int batch, int res, int rm, float drop_p, uint32_t drop_block, uint64_t drop_seed, void* workspace,
+                        size_t workspace_bytes, void* stream);
+FG_API int fg_op_gn_backward(int dtype, int mode, const void* x1, int c1, const void* x2, int c2, const void* dact, int cd,
+                             const float* gamma, const float* beta, float eps, float* dgamma, float* dbeta, const void* add, int ca,
+                             float add_scale, void* dx, void* dx2, int accumulate, int batch, int res, int rm, float drop_p,
+                             uint32_t drop_block, uint64_t drop_seed, void* workspace, size_t workspace_bytes, void* stream);
+FG_API int fg_op_gn_jvp(int dtype, int mode, const void* x1, int c1, const void* x2, int c2, const void* xd, const float* gamma,
+                        const float* beta, float eps, void* out, int batch, int res, float drop_p, uint32_t drop_block, uint64_t drop_seed,
+                        void* workspace, size_t workspace_bytes, void* stream);
+/* Single-head self-attention, P = softmax(q k^T / sqrt(c)), o = P v: q, k, d_out, dq, dk, qd, kd, od [batch][t][c]; vt, dvt, vtd
+ * [batch][c][t]; t in {64, 256}, c % 32 == 0.  backward: dq, dk, dvt, and (dqkv nullable) their interleave [batch][t][3 c] with channel
+ * 3 ch + {0 q, 1 k, 2 v}.  jvp: od = Pd v + P vd.  workspace: fg_op_attention_backward_workspace_bytes (0: unsupported), 256-byte
+ * aligned, for both. */
+FG_API size_t fg_op_attention_backward_workspace_bytes(int dtype, int batch, int t, int c);
+FG_API int fg_op_attention_backward(int dtype, const void* q, const void* k, const void* vt, const void* d_out, void* dq, void* dk, void* dvt,
+                                    void* dqkv, int batch, int t, int c, void* workspace, size_t workspace_bytes, void* stream);
+FG_API int fg_op_attention_jvp(int dtype, const void* q, const void* k, const void* vt, const void* qd, const void* kd, const void* vtd,
+                               void* od, int batch, int t, int c, void* workspace, size_t workspace_bytes, void* stream);
+/* out[n * out_stride + ch] = scale * sum_p t[n][p][ch] for ch < c (t has pixel pitch ct >= c; out_stride 0 = c);
+ * out[ch] (and out2[ch], nullable) += sum_n in[n * in_stride + ch] (in_stride 0 = c). */
+FG_API int fg_op_colsum(int dtype, const void* t, int ct, int c, float* out, int batch, int hw, float scale, int out_stride, void* stream);
+FG_API int fg_op_batchsum_add(const float* in, float* out, float* out2, int batch, int c, int in_stride, void* stream);
+/* Linear backward, each of dw / db / dx nullable and accumulated: dw[c][k] += scale * sum_b dy[b][ch] x[b][kk], db[ch] += sum_b dy,
+ * dx[b][kk] += sum_ch dy[b][ch] w[ch][kk]; dy_stride (0 = c) is honoured by dw alone.  affine != 0: the embedding-affine kernels
+ * (no db, scale 1, no stride). */
+FG_API int fg_op_linear_backward(int affine, const float* dy, const float* x, const float* w, float* dw, float* db, float* dx, int batch,
+                                 int c, int k, float scale, int dy_stride, void* stream);
+/* Weights of the data-gradient convolution: wt[ci][co][tap] = w[co][ci][taps - 1 - tap] for ci < cin, 0 for cin <= ci < cin_pad. */
+FG_API int fg_op_dgrad_weights(const float* w, float* wt, int cout, int cin, int cin_pad, int taps, void* stream);
+/* The small elementwise pieces of the whole-network passes, selected by op (operands a .. e, meaning per op):
+ * HEAD_GRAD out[n][p][cp] = c_out[n] dout[n][ch][p] | 0 (a dout NCHW, b c_out);  STEM_OPERAND the same with a = x, b = c_in;
+ * INPUT_GRAD out[n][ch][p] = c_in[n] da[n][p][ch] (+ c_skip[n] dout) (a da with pitch ch_pad, b c_in, c c_skip, d dout nullable);
+ * ADD_NCHW_TO_NHWC out[n][p][ch] += a[n][ch][p];  SILU_BWD out = a silu'(b), batch * ch elements;
+ * JVP_COEF out[8][batch] from a = t, b = r (doubles, r nullable), c = vt, d = vr (nullable), f0 = sigma_data, f1 = sigma_shift,
+ * flag = drop_precond;  JVP_EMBED out[batch][ch] from a = c_noise, b = r_noise, c = dc, d = dr, e = freqs, ch_pad = noise channels;
+ * JVP_INPUT out = c_in vx + dc_in x (a vx, b x, c c_in, d dc_in);  JVP_OUTPUT out = c_out Fd + dc_out F + c_skip vx + dc_skip x
+ * (a Fd with pitch ch_pad, b F, c x, d vx, e the JVP_COEF table). */
+#define FG_TRAIN_OP_HEAD_GRAD 0
+#define FG_TRAIN_OP_STEM_OPERAND 1
+#define FG_TRAIN_OP_INPUT_GRAD 2
+#define FG_TRAIN_OP_ADD_NCHW_TO_NHWC 3
+#define FG_TRAIN_OP_SILU_BWD 4
+#define FG_TRAIN_OP_JVP_COEF 5
+#define FG_TRAIN_OP_JVP_EMBED 6
+#define FG_TRAIN_OP_JVP_INPUT 7
+#define FG_TRAIN_OP_JVP_OUTPUT 8
+FG_API int fg_op_train_elementwise(int op, int dtype, const void* a, const void* b, const void* c, const void* d, const void* e, void* out,
+                                   int batch, int ch, int ch_pad, int hw, double f0, double f1, int flag, void* stream);
+
 /* ---- DiT: the class-conditional diffusion transformer of fastgen/networks/DiT/network.py -------------------------
  * kwargs of DiT(input_size, patch_size, in_channels, hidden_size, depth, num_heads, mlp_ratio, num_classes, class_dropout_prob,
  * r_timestep, ...) (:233-253; configs/net.py:98-127).  Supported: 256 tokens (input_size / patch_size == 16), hidden_size in

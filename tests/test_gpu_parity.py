@@ -637,6 +637,43 @@ BWD_BLOCKS = {"enc_first": "32x32_block0", "enc_plain": "8x8_block1", "dec_cat51
 BWD_TOL = {"bf16": dict(block=2e-2, norm=2e-2, sample=3e-2), "bf16x3": dict(block=1e-4, norm=1e-4, sample=2e-4)}
 
 
+def _block_backward_hip(net, sd, b, bi, key, names, x, emb, dout):
+    """fg_edm_run_block_backward through the C ABI with the block's parameter gradients bound; x, dout NCHW fp32 on the CPU.  Returns
+    {"dx", "demb", <parameter name without the block's key>: gradient} on the CPU."""
+    L = _lib.lib()
+    bs, rin = x.shape[0], x.shape[2]
+    with torch.inference_mode():
+        dt, h = net._engine(dev())
+        c2 = b.skip_from or 0
+        c1 = b.cin - c2
+        x1 = nhwc(x[:, :c1]).to(dev())
+        x2 = nhwc(x[:, c1:]).to(dev()) if c2 else None
+        grads = {k: torch.zeros_like(sd[k], device=dev()) for k in names}
+        for k, g in grads.items():
+            _lib.check(L.fg_edm_bind_grad(h, k.encode(), g.data_ptr(), g.numel()))
+        try:
+            dx1 = torch.full((bs, rin, rin, c1), float("nan"), device=dev())  # overwritten: an element left out shows
+            dx2 = torch.full((bs, rin, rin, max(c2, 1)), float("nan"), device=dev())
+            demb = torch.zeros(bs, 512, device=dev())
+            nbytes = L.fg_edm_block_backward_workspace_bytes(h, bi, bs)
+            assert nbytes > 0
+            ws = torch.empty(nbytes, dtype=torch.uint8, device=dev())
+            # device copies held in names: a temporary's memory returns to the caching allocator as soon as data_ptr() has been
+            # taken, and the next temporary may be carved from the same block (it was: a stale emb pointer read dout's bytes
+            # whenever three networks' worth of small allocations had shaped the free lists that way)
+            emb_d, dout_d = emb.to(dev()), nhwc(dout).to(dev())
+            _lib.check(L.fg_edm_run_block_backward(h, bi, x1.data_ptr(), c1, x2.data_ptr() if c2 else None, c2,
+                                                   emb_d.data_ptr(), dout_d.data_ptr(), dx1.data_ptr(),
+                                                   dx2.data_ptr() if c2 else None, demb.data_ptr(), bs, ws.data_ptr(), nbytes, None))
+            torch.cuda.synchronize()
+        finally:
+            for k in grads:
+                _lib.check(L.fg_edm_bind_grad(h, k.encode(), None, 0))
+    dx = torch.cat([nchw(dx1.cpu()), nchw(dx2.cpu())], 1) if c2 else nchw(dx1.cpu())
+    got = {"dx": dx, "demb": demb.cpu(), **{k[len(key) + 1:]: g.cpu() for k, g in grads.items()}}
+    return got
+
+
 @pytest.mark.parametrize("mode", ["bf16", "bf16x3"])
 @pytest.mark.parametrize("case", ["enc_first", "enc_plain", "dec_cat512", "dec_cat384", "enc_down", "dec_up", "enc_attn", "dec_in0",
                                   "dec_cat_attn"])
@@ -668,35 +705,7 @@ def test_block_backward_against_reference_golden(nets, sd, golden_dir, case, mod
         R.unet_block(sdg, b, xo, eo).backward(dout)
     want = {"dx": xo.grad, "demb": eo.grad, **{k[len(key) + 1:]: sdg[k].grad for k in names}}
     # ---- HIP path through the C ABI --------------------------------------------------------------------------------------
-    with torch.inference_mode():
-        dt, h = net._engine(dev())
-        c2 = b.skip_from or 0
-        c1 = b.cin - c2
-        x1 = nhwc(x[:, :c1]).to(dev())
-        x2 = nhwc(x[:, c1:]).to(dev()) if c2 else None
-        grads = {k: torch.zeros_like(sd[k], device=dev()) for k in names}
-        for k, g in grads.items():
-            _lib.check(L.fg_edm_bind_grad(h, k.encode(), g.data_ptr(), g.numel()))
-        try:
-            dx1 = torch.empty(bs, rin, rin, c1, device=dev())
-            dx2 = torch.empty(bs, rin, rin, max(c2, 1), device=dev())
-            demb = torch.zeros(bs, 512, device=dev())
-            nbytes = L.fg_edm_block_backward_workspace_bytes(h, bi, bs)
-            assert nbytes > 0
-            ws = torch.empty(nbytes, dtype=torch.uint8, device=dev())
-            # device copies held in names: a temporary's memory returns to the caching allocator as soon as data_ptr() has been
-            # taken, and the next temporary may be carved from the same block (it was: a stale emb pointer read dout's bytes
-            # whenever three networks' worth of small allocations had shaped the free lists that way)
-            emb_d, dout_d = emb.to(dev()), nhwc(dout).to(dev())
-            _lib.check(L.fg_edm_run_block_backward(h, bi, x1.data_ptr(), c1, x2.data_ptr() if c2 else None, c2,
-                                                   emb_d.data_ptr(), dout_d.data_ptr(), dx1.data_ptr(),
-                                                   dx2.data_ptr() if c2 else None, demb.data_ptr(), bs, ws.data_ptr(), nbytes, None))
-            torch.cuda.synchronize()
-        finally:
-            for k in grads:
-                _lib.check(L.fg_edm_bind_grad(h, k.encode(), None, 0))
-    dx = torch.cat([nchw(dx1.cpu()), nchw(dx2.cpu())], 1) if c2 else nchw(dx1.cpu())
-    got = {"dx": dx, "demb": demb.cpu(), **{k[len(key) + 1:]: g.cpu() for k, g in grads.items()}}
+    got = _block_backward_hip(net, sd, b, bi, key, names, x, emb, dout)
     assert set(got) == set(want)
     for n in sorted(want):
         rel = float((got[n] - want[n]).norm() / want[n].norm())
@@ -707,6 +716,87 @@ def test_block_backward_against_reference_golden(nets, sd, golden_dir, case, mod
         smp = flat[:: max(1, flat.numel() // 4096)][:4096]
         assert abs(float(flat.double().norm()) / float(gn) - 1) <= tol["norm"], (case, mode, n)
         assert float((smp - gs).norm() / gs.norm()) <= tol["sample"], (case, mode, n)
+
+
+# Batch 5 puts a second image on batch lane 0 of gn_bwd_group_param_kernel / batchsum_add_kernel (the golden cases run at batch 1 or 2);
+# the 32x32 cases run at batch 3 to keep the fp64 oracle to a few seconds.
+SLICE_BATCH = {"enc_plain": 5, "enc_attn": 5, "dec_cat512": 5, "dec_cat_attn": 5, "dec_in0": 5, "enc_down": 5, "enc_first": 3, "dec_cat384": 3,
+               "dec_up": 3}
+_SLICE_ORACLE = {}
+
+
+def _slice_oracle(sd, golden_dir, case):
+    """(block, index, key, names, x, emb, dout, fp64 autograd gradients) of one case, computed once for both modes."""
+    if case not in _SLICE_ORACLE:
+        fx = load(golden_dir, "blocks_backward.pt")
+        enc, dec = R.layout(R.CIFAR10)
+        blocks = [b for b in enc + dec if b.kind == "block"]
+        key = fx[f"{case}/key"]
+        bi = [i for i, b in enumerate(blocks) if b.key == key][0]
+        b = blocks[bi]
+        bs = SLICE_BATCH[case]
+        rin = b.res * 2 if b.down else (b.res // 2 if b.up else b.res)
+        x, emb, dout = seeded((bs, b.cin, rin, rin), 9100 + bi), seeded((bs, 512), 9200 + bi) * 0.5, seeded((bs, b.cout, b.res, b.res), 9300 + bi)
+        names = [k for k in sd if k.startswith(key + ".") and "resample_filter" not in k]
+        sdg = {k: (v.double() if v.is_floating_point() else v) for k, v in sd.items() if k.startswith(key + ".")}
+        for k in names:
+            sdg[k].requires_grad_(True)
+        xo, eo = x.double().requires_grad_(True), emb.double().requires_grad_(True)
+        with torch.enable_grad():
+            R.unet_block(sdg, b, xo, eo).backward(dout.double())
+        want = {"dx": xo.grad, "demb": eo.grad, **{k[len(key) + 1:]: sdg[k].grad for k in names}}
+        _SLICE_ORACLE[case] = (b, bi, key, names, x, emb, dout, want)
+    return _SLICE_ORACLE[case]
+
+
+def _slices(name, t):
+    """{slicing: dims reduced} of one gradient tensor: dx per image, pixel row, pixel column and 8-channel octet; a conv weight per
+    output channel and per tap; demb per image."""
+    if name == "dx":
+        B, C, H, W = t.shape
+        o = t.reshape(B, C // 8, 8, H, W)
+        return {"image": (t, (1, 2, 3)), "row": (t, (0, 1, 3)), "column": (t, (0, 1, 2)), "octet": (o, (0, 2, 3, 4))}
+    if name == "demb":
+        return {"image": (t, (1,))}
+    if t.dim() == 4:
+        return {"cout": (t, (1, 2, 3)), "tap": (t, (0, 1))}
+    return {}
+
+
+@pytest.mark.parametrize("mode", ["bf16", "bf16x3"])
+@pytest.mark.parametrize("case", sorted(SLICE_BATCH))
+def test_block_backward_per_slice_against_fp64_autograd(nets, sd, golden_dir, case, mode):
+    """fg_edm_run_block_backward at batch 5 (3 at 32x32) against fp64 autograd through the oracle's UNetBlock: BWD_TOL's relative L2 per
+    tensor AND per slice of every gradient - a wrong value confined to one image, one border row or column, one octet, one output
+    channel or one tap moves the whole tensor's relative L2 only by the root of its share.  A slice is skipped only if its reference
+    norm is below 1e-3 of the tensor's RMS times the root of the slice size (at most 2 % of a slicing); per-channel vectors are
+    compared per entry against tol * max|want|."""
+    b, bi, key, names, x, emb, dout, want = _slice_oracle(sd, golden_dir, case)
+    tol = BWD_TOL[mode]["block"]
+    got = _block_backward_hip(nets[mode], sd, b, bi, key, names, x, emb, dout)
+    assert set(got) == set(want)
+    worst = {}
+    for n in sorted(want):
+        g, w = got[n].double(), want[n]
+        assert torch.isfinite(g).all(), (case, mode, n)
+        rel = float((g - w).norm() / w.norm())
+        assert rel <= tol, (case, mode, n, rel)
+        if w.dim() == 1:
+            e = float((g - w).abs().max() / w.abs().max())
+            worst["entry"] = max(worst.get("entry", 0.0), e)
+            assert e <= tol, (case, mode, n, "entry", e)
+            continue
+        rms = float(w.pow(2).mean().sqrt())
+        for kind, (wv, dims) in _slices(n, w).items():
+            gv = _slices(n, g)[kind][0]
+            num, den = (gv - wv).pow(2).sum(dims).sqrt(), wv.pow(2).sum(dims).sqrt()
+            size = wv.numel() // den.numel()
+            keep = den >= 1e-3 * rms * size ** 0.5
+            assert int((~keep).sum()) <= 0.02 * den.numel(), (case, mode, n, kind, "slices skipped", int((~keep).sum()), den.numel())
+            r = float((num[keep] / den[keep]).max())
+            worst[kind] = max(worst.get(kind, 0.0), r)
+            assert r <= tol, (case, mode, n, kind, r, int((num / den.clamp_min(1e-300) * keep).argmax()))
+    print(f"SLICES {case} {mode} " + " ".join(f"{k} {v:.3e}" for k, v in sorted(worst.items())))
 
 
 # ---- training step, whole network: EDMPrecond backward (SURVEY 8(f)1) ------------------------------------------------------
