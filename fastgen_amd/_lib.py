@@ -76,9 +76,18 @@ class fg_attention_plan(ctypes.Structure):
                 ("scratch_bytes", c_size_t)]
 
 
+class fg_gemm_plan(ctypes.Structure):
+    _fields_ = [("refusal", c_int), ("kernel", c_int), ("tile_n", c_int), ("epilogue", c_int), ("ksplit", c_int), ("xn", c_int), ("grid", c_int),
+                ("lds_bytes", c_int), ("row0", c_int), ("rows", c_int), ("pieces", c_int)]
+
+
 # token attention's kernel forms (fg_attention_plan.kernel, the `path` argument) and refusal codes
 FG_FA_TILE128, FG_FA_TILE128_W3, FG_FA_TILE128_REG, FG_FA_WIDE, FG_FA_WIDE_CUT, FG_FA_SEQ72, FG_FA_TILE72, FG_FA_TILE72_W3 = range(1, 9)
 FG_FA_REFUSE_ARG, FG_FA_REFUSE_OFFSET, FG_FA_REFUSE_PATH = 1, 2, 3
+# the token GEMM's kernel forms, epilogues and refusal codes (fg_gemm_plan)
+FG_GEMM_REG, FG_GEMM_PP, FG_GEMM_PP_NARROW, FG_GEMM_PP_SPLITK = range(1, 5)
+FG_GEMM_EPI_TOK, FG_GEMM_EPI_HEADS, FG_GEMM_EPI_RAW, FG_GEMM_EPI_TOK32, FG_GEMM_EPI_SPLIT, FG_GEMM_EPI_HEADS32 = range(6)
+FG_GEMM_REFUSE_ARG, FG_GEMM_REFUSE_OFFSET, FG_GEMM_REFUSE_FORM, FG_GEMM_REFUSE_PIECE = 1, 2, 3, 4
 
 
 # name -> (restype, argtypes); every symbol include/fastgen_amd.h declares
@@ -227,6 +236,7 @@ SIGNATURES = {
     "fg_op_attention_plan": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, POINTER(fg_attention_plan)]),
     "fg_op_attention_ex": (c_int, [c_void_p, c_int, c_int64, c_void_p, c_void_p, c_int, c_int64, c_void_p, c_int, c_int64, c_int, c_int, c_int,
                                    c_int, c_int, c_int, c_int, c_int, c_void_p]),
+    "fg_op_gemm_plan": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_size_t, c_int, c_int, c_int, c_int, POINTER(fg_gemm_plan)]),
     "fg_op_gemm_bf16": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_int, c_void_p,
                                 c_int, c_void_p]),
     "fg_op_quant_rows_fp8": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p]),

@@ -1652,23 +1652,52 @@ int fg_op_attention_split(const void* q, const void* k, const void* v, void* out
 int fg_op_attention(const void* q, const void* k, const void* v, void* out, int batch, int heads, int head_dim, int lq, int lkv, void* stream) {
     return fg_op_attention_split(q, k, v, out, batch, heads, head_dim, lq, lkv, 0, stream);
 }
+// tile_order of the token GEMM entry points (flavour 0 bf16, 1 split-bf16: the tile order alone, 2 fp8) -> GemmArgs.xn / .variant;
+// false: bits the flavour does not take
+static bool gemm_tile_order(int flavour, int tile_order, GemmArgs& g) {
+#ifdef FG_TIMING_BUILD
+    const int order_ok = flavour == 0 ? 511 : flavour == 1 ? 15 : 31;  // tile_order 128: cycle stamps (gemm.hip, GM_TIMING)
+#else
+    const int order_ok = flavour == 0 ? 127 | 256 : flavour == 1 ? 15 : 31;
+#endif
+    if (tile_order < 0 || (tile_order & ~order_ok) || ((tile_order >> 4) & 1) + ((tile_order >> 5) & 1) + ((tile_order >> 8) & 1) > 1) return false;
+    g.xn = tile_order & 15;
+    g.variant = (tile_order & 16) ? 0 : (tile_order & 32) ? 1 : (tile_order & 256) ? 2 : -1;
+    return true;
+}
+int fg_op_gemm_plan(int flavour, int m, int n, int k, int heads, int gate_rows, size_t scratch_bytes, int tile_order, int out_mode, int cus,
+                    int piece, fg_gemm_plan* plan) {
+    if (!plan) return fail(FG_EINVAL, "fg_op_gemm_plan: null plan");
+    // (the plan reads no memory: `plan` stands for every pointer the call would pass)
+    GemmArgs g;
+    g.A = g.W = plan; g.a_scale = g.w_scale = (const float*)plan; g.M = m; g.N = n; g.K = k;
+    if (heads > 0) g.q = g.k = g.vt = plan, g.heads = heads, g.head_dim = n / (3 * heads), g.T = 1;
+    else g.out = plan;
+    if (gate_rows > 0) g.gate = (const float*)plan, g.gate_rows = gate_rows;
+    if (flavour == 0 && (tile_order & 64) && scratch_bytes == 0) scratch_bytes = (size_t)4 * m * n * 4;  // (as fg_op_gemm_bf16 allocates)
+    if (scratch_bytes) g.scratch = (float*)plan, g.scratch_bytes = scratch_bytes;
+    g.out_f32 = flavour == 0 && out_mode == 1;
+    GemmPlan p = {};
+    if (!gemm_tile_order(flavour, tile_order, g) || gate_rows < 0 || out_mode < 0 || out_mode > (flavour == 2 ? 0 : 1)) p.refusal = FG_GEMM_REFUSE_ARG;
+    else p = gemm_plan(flavour, g, out_mode, cus, piece);
+    plan->refusal = p.refusal, plan->kernel = p.kernel, plan->tile_n = p.tile_n, plan->epilogue = p.epilogue, plan->ksplit = p.ksplit;
+    plan->xn = p.xn, plan->grid = p.grid, plan->lds_bytes = p.lds_bytes, plan->row0 = p.row0, plan->rows = p.rows, plan->pieces = p.pieces;
+    return FG_OK;
+}
 int fg_op_gemm_bf16(const void* a, const void* w, const float* bias, void* out, int m, int n, int k, int act, const float* gate,
                     int gate_stride, int gate_rows, const void* resid, int tile_order, void* stream) {
 #ifdef FG_TIMING_BUILD
-    const int act_ok = 1 | 4 | 8, order_ok = 1023;  // + act 4 / 8: no stores / no epilogue; tile_order 128: cycle stamps (gemm.hip, GM_TIMING)
+    const int act_ok = 1 | 4 | 8;  // + act 4 / 8: no stores / no epilogue
 #else
-    const int act_ok = 1, order_ok = 127 | 256 | 512;
+    const int act_ok = 1;
 #endif
     if (act < 0 || (act & ~act_ok)) return fail(FG_EINVAL, "fg_op_gemm_bf16: act must be 0 (none) or 1 (GELU tanh), got %d", act);
-    if (tile_order < 0 || (tile_order & ~order_ok)) return fail(FG_EINVAL, "fg_op_gemm_bf16: bad tile_order %d", tile_order);
-    if (((tile_order >> 4) & 1) + ((tile_order >> 5) & 1) + ((tile_order >> 8) & 1) + ((tile_order >> 9) & 1) > 1)
-        return fail(FG_EINVAL, "fg_op_gemm_bf16: tile_order bits 16, 32, 256 and 512 exclude each other");
     GemmArgs g;
     g.A = a; g.W = w; g.bias = bias; g.out = out; g.M = m; g.N = n; g.K = k; g.act = act;
-    g.gate = gate; g.gate_stride = gate_stride; g.gate_rows = gate_rows > 0 ? gate_rows : 1; g.resid = resid; g.xn = tile_order & 15;
-    g.variant = (tile_order & 16) ? 0 : (tile_order & 32) ? 1 : (tile_order & 256) ? 2 : (tile_order & 512) ? 3 : -1;
+    g.gate = gate; g.gate_stride = gate_stride; g.gate_rows = gate_rows > 0 ? gate_rows : 1; g.resid = resid;
+    if (!gemm_tile_order(0, tile_order, g)) return fail(FG_EINVAL, "fg_op_gemm_bf16: bad tile_order %d (bits 16, 32 and 256 exclude each other)", tile_order);
     if (!gemm_bf16_supported(g)) return fail(FG_EINVAL, "fg_op_gemm_bf16: unsupported shape (k %% 64, n %% 16, pointers)");
-    HIP_TRY(launch_gemm_bf16(g, (hipStream_t)stream, true));
+    HIP_TRY(gemm_prepare(1));
     // one scratch allocation, released on every path once the stream has drained (a test entry point, not a hot path)
     void* scratch = nullptr;
     hipError_t herr = hipSuccess;
@@ -1720,17 +1749,16 @@ int fg_op_quant_rows_fp8(int dtype, const void* x, void* q, float* scale, int64_
 int fg_op_gemm_fp8(const void* a, const void* w, const float* bias, void* out, int m, int n, int k, int act, const float* gate,
                    int gate_stride, int gate_rows, const void* resid, int tile_order, const float* a_scale, const float* w_scale, void* stream) {
     if (act != 0 && act != 1) return fail(FG_EINVAL, "fg_op_gemm_fp8: act must be 0 (none) or 1 (GELU tanh), got %d", act);
-    if (tile_order < 0 || (tile_order & ~31)) return fail(FG_EINVAL, "fg_op_gemm_fp8: bad tile_order %d", tile_order);
     GemmArgs g;
     g.A = a; g.W = w; g.bias = bias; g.out = out; g.M = m; g.N = n; g.K = k; g.act = act;
-    g.gate = gate; g.gate_stride = gate_stride; g.gate_rows = gate_rows > 0 ? gate_rows : 1; g.resid = resid; g.xn = tile_order & 15;
-    g.variant = (tile_order & 16) ? 0 : -1;
+    g.gate = gate; g.gate_stride = gate_stride; g.gate_rows = gate_rows > 0 ? gate_rows : 1; g.resid = resid;
     g.a_scale = a_scale; g.w_scale = w_scale;
+    if (!gemm_tile_order(2, tile_order, g)) return fail(FG_EINVAL, "fg_op_gemm_fp8: bad tile_order %d", tile_order);
     if (!gemm_fp8_supported(g)) return fail(FG_EINVAL, "fg_op_gemm_fp8: unsupported shape (m >= 1, k %% 128, n %% 16, n k < 2^31, pointers and scales)");
     if (gate && (gate_stride < n || (gate_stride % 4))) return fail(FG_EINVAL, "fg_op_gemm_fp8: gate_stride %d >= n and a multiple of 4", gate_stride);
     if ((((uintptr_t)a) | ((uintptr_t)w) | ((uintptr_t)out) | ((uintptr_t)bias) | ((uintptr_t)gate) | ((uintptr_t)resid) | ((uintptr_t)w_scale)) & 15)
         return fail(FG_EINVAL, "fg_op_gemm_fp8: a / w / out / bias / gate / resid / w_scale must be 16-byte aligned");
-    HIP_TRY(launch_gemm_fp8(g, (hipStream_t)stream, true));
+    HIP_TRY(gemm_prepare(4));
     HIP_TRY(launch_gemm_fp8(g, (hipStream_t)stream));
     return FG_OK;
 }
@@ -1745,21 +1773,24 @@ int fg_op_dit_ln_modulate_fp8(const void* x, const float* mod, int mod_stride, i
 }
 int fg_op_gemm_x3(const float* a, const float* w, const float* bias, void* out, int m, int n, int k, int act, const float* gate,
                   int gate_stride, int gate_rows, const float* resid, int out_mode, void* stream) {
-    // the checks of launch_gemm_x3 (and its row cutting: every launch keeps whole 256-row tiles) before anything is allocated or launched
-    if (m < 256 || n < 256 || (n % 16) || k <= 0 || (k % 64) || (size_t)n * 3 * k * 2 >= (1ull << 31))
-        return fail(FG_EINVAL, "fg_op_gemm_x3: unsupported shape m %d (>= 256), n %d (>= 256, %% 16), k %d (%% 64), 6 n k < 2^31", m, n, k);
-    const int rows_max = (int)(((1ull << 31) - 1) / ((size_t)k * 4)) / 256 * 256;
-    if (m % rows_max && m % rows_max < 256) return fail(FG_EINVAL, "fg_op_gemm_x3: m %d leaves a last launch of fewer than 256 rows", m);
-    if (act != 0 && act != 1) return fail(FG_EINVAL, "fg_op_gemm_x3: act must be 0 (none) or 1 (GELU tanh), got %d", act);
+    // what launch_gemm_x3 would refuse (its row cutting included: every launch keeps whole 256-row tiles), before anything is allocated
+    GemmArgs g;
+    g.A = a; g.W = w; g.bias = bias; g.out = out; g.M = m; g.N = n; g.K = k; g.act = act;
+    g.gate = gate; g.gate_stride = gate_stride; g.gate_rows = gate_rows; g.resid = resid;
     if (out_mode != 0 && out_mode != 1) return fail(FG_EINVAL, "fg_op_gemm_x3: out_mode must be 0 (fp32) or 1 ([hi | lo] planes), got %d", out_mode);
     if (!a || !w || !out) return fail(FG_EINVAL, "fg_op_gemm_x3: null pointer");
+    const int refusal = gemm_plan(1, g, out_mode, 256, 0).refusal;  // (no refusal depends on the CU count)
+    if (refusal == FG_GEMM_REFUSE_PIECE) return fail(FG_EINVAL, "fg_op_gemm_x3: m %d leaves a last launch of fewer than 256 rows", m);
+    if (refusal)
+        return fail(FG_EINVAL, "fg_op_gemm_x3: unsupported shape m %d (>= 256), n %d (>= 256, %% 16), k %d (%% 64), 6 n k < 2^31", m, n, k);
+    if (act != 0 && act != 1) return fail(FG_EINVAL, "fg_op_gemm_x3: act must be 0 (none) or 1 (GELU tanh), got %d", act);
     if (gate && (gate_rows <= 0 || gate_stride < n || (gate_stride % 4)))
         return fail(FG_EINVAL, "fg_op_gemm_x3: gate_rows %d > 0, gate_stride %d >= n and a multiple of 4", gate_rows, gate_stride);
     if ((((uintptr_t)a) | ((uintptr_t)w) | ((uintptr_t)out) | ((uintptr_t)bias) | ((uintptr_t)gate) | ((uintptr_t)resid)) & 15)
         return fail(FG_EINVAL, "fg_op_gemm_x3: a / w / out / bias / gate / resid must be 16-byte aligned");
     if (resid && out_mode == 1 && (const void*)resid == out) return fail(FG_EINVAL, "fg_op_gemm_x3: out_mode 1 cannot write over resid");
     const hipStream_t s = (hipStream_t)stream;
-    HIP_TRY(launch_gemm_bf16(GemmArgs{}, s, true));
+    HIP_TRY(gemm_prepare(2));
     // A as [hi | lo] planes [m][2 k], W as [hi | lo | hi] [n][3 k] (what the DiT's layers produce and pack)
     void *ap = nullptr, *wp = nullptr;
     hipError_t herr = hipMalloc(&ap, (size_t)m * k * 4);
@@ -1767,12 +1798,8 @@ int fg_op_gemm_x3(const float* a, const float* w, const float* bias, void* out, 
     int rc = (int)herr;
     if (!rc) rc = launch_split_planes(a, ap, (int64_t)m, k, s);
     if (!rc) rc = launch_split3_weights(w, wp, n, k, s);
-    if (!rc) {
-        GemmArgs g;
-        g.A = ap; g.W = wp; g.bias = bias; g.out = out; g.M = m; g.N = n; g.K = k; g.act = act;
-        g.gate = gate; g.gate_stride = gate_stride; g.gate_rows = gate_rows; g.resid = resid;
-        rc = launch_gemm_x3(g, out_mode, s);
-    }
+    g.A = ap, g.W = wp;
+    if (!rc) rc = launch_gemm_x3(g, out_mode, s);
     (void)hipStreamSynchronize(s);
     if (ap) (void)hipFree(ap);
     if (wp) (void)hipFree(wp);

@@ -262,7 +262,7 @@ int dit_pack(fg_dit* h, const ParamGroup& in_group, hipStream_t s) {
     int rc;
     if (!h->device_ready) {
         // (before anything is allocated: a failure here leaves nothing behind for a second attempt to allocate again)
-        if (h->fp8 && launch_gemm_fp8(GemmArgs{}, s, true) != 0) return fail(FG_EHIP, "hipFuncSetAttribute(dynamic LDS) failed");
+        if (h->fp8 && gemm_prepare(4) != 0) return fail(FG_EHIP, "hipFuncSetAttribute(dynamic LDS) failed");
         for (fg_dit::Blk& b : h->blocks) {
             if ((rc = h->alloc(&b.p_qkv, 3 * D * D * wsz)) || (rc = h->alloc(&b.p_proj, D * D * wsz)) ||
                 (rc = h->alloc(&b.p_fc1, Hd * D * wsz)) || (rc = h->alloc(&b.p_fc2, D * Hd * wsz)))
@@ -277,7 +277,7 @@ int dit_pack(fg_dit* h, const ParamGroup& in_group, hipStream_t s) {
         const char* e = getenv("FASTGEN_AMD_DIT_GEMM");
         h->gemm = h->cmode == FG_DTYPE_BF16 && (h->fp8 || !(e && e[0] == '0')) && (D % 64) == 0 && (Hd % 64) == 0;  // (fp8: fg_dit_create has refused the switch)
         h->gemm3 = want3;
-        if ((h->gemm || h->gemm3) && launch_gemm_bf16(GemmArgs{}, s, true) != 0) return fail(FG_EHIP, "hipFuncSetAttribute(dynamic LDS) failed");
+        if ((h->gemm || h->gemm3) && gemm_prepare(3) != 0) return fail(FG_EHIP, "hipFuncSetAttribute(dynamic LDS) failed");
         if (h->gemm && ((rc = h->alloc(&h->p_modw, h->blocks.size() * 6 * D * D * 2)) || (rc = h->alloc((void**)&h->modb, h->blocks.size() * 6 * D * 4))))
             return rc;
         h->device_ready = true;

@@ -155,7 +155,7 @@ int wan_pack(fg_wan* h, const ParamGroup& in_group, hipStream_t s) {
         for (size_t i = 0; i < h->params.size(); ++i)
             if (!h->pack_only[i] && !h->is_logvar((int)i) && (rc = h->alloc((void**)&h->own[i], sizeof(float) * (size_t)h->params[i].numel))) return rc;
         if ((rc = wan_build_rope(h))) return rc;
-        if (launch_gemm_bf16(GemmArgs{}, s, true) != 0) return fail(FG_EHIP, "hipFuncSetAttribute(dynamic LDS) failed");
+        if (gemm_prepare(1) != 0) return fail(FG_EHIP, "hipFuncSetAttribute(dynamic LDS) failed");
         h->device_ready = true;
     }
     auto raw = [&](int idx) { return h->params[idx].ptr; };

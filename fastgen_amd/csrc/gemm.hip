@@ -29,12 +29,9 @@
 
 #include <type_traits>
 
+#include "../../include/fastgen_amd.h"
 #include "common.h"
 #include "misc.h"
-
-#ifndef W4_EXP
-#define W4_EXP 0  // gemm_bf16_w4_kernel timing experiments (wrong results): 1 no LDS-DMA in the K-loop, 2 no fragment reads
-#endif
 
 namespace {
 
@@ -863,304 +860,6 @@ __global__ __launch_bounds__(GM_NTHR) void gemm_bf16_pp_kernel(const GemmArgs a)
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // no DMA may land in an LDS allocation this workgroup has given up
 }
 
-template <int I, int N, typename F>
-__device__ __forceinline__ void static_for(F&& f) {  // compile-time loop (instruction offsets / register indices as constants)
-    if constexpr (I < N) {
-        f(std::integral_constant<int, I>{});
-        static_for<I + 1, N>(f);
-    }
-}
-
-// ---- one wave per SIMD: 4 waves x (128 tokens x 128 outputs) --------------------------------------------------------------------
-// hipBLASLt's kernel for these shapes keeps the matrix pipe 70 % busy where the 8-wave ping-pong above keeps it 51 % busy, with the same
-// instruction mix per MFMA (profiles/r03_gemm_vs_hipblaslt_pmc.txt): its wave owns a 128 x 128 output tile - all 512 registers of a
-// one-wave-per-SIMD kernel, 256 of them accumulators - so a K-step of 64 is 128 MFMAs fed by 32 fragment reads (the 128 x 64 wave
-// tile: 64 MFMAs per 24 reads), and there is no partner wave to be paced against with two barriers per phase.  This is that shape on
-// this file's LDS image and LDS-DMA staging: tile 256 x 256, waves 2 x 2, K-step = two sub-steps of 32 (64 MFMAs each, fragments of
-// the next sub-step read while this one's MFMAs run), ONE barrier per K-step: the DMA of K-step t + 1 is issued at the start of step
-// t into the buffer step t - 1 left, waited for (vmcnt(0)) and handed over before the last 16 MFMAs of step t, behind which the first
-// fragments of step t + 1 are read.  Token epilogue only (GM_EPI_TOK).
-__global__ __launch_bounds__(256, 1) void gemm_bf16_w4_kernel(const GemmArgs a) {
-    constexpr int TN = 256, EPI = GM_EPI_TOK;
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    typedef __attribute__((address_space(3))) void* lds_ptr;
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int wr = wave >> 1, wc = wave & 1;  // token half, output half
-    const int col = lane & 15, g = lane >> 4;
-    // ---- this workgroup's tiles (as gemm_bf16_kernel) ----------------------------------------------------------------
-    const int Mt = (a.M + GM_TM - 1) / GM_TM, Nt = (a.N + TN - 1) / TN;
-    int mlo = 0, nlo = 0, nx = Nt, first, stride, count;
-    if ((gridDim.x & 7) == 0 && a.xn > 0) {
-        const int x = (int)blockIdx.x & 7, xm = 8 / a.xn, xi = x / a.xn, xj = x - xi * a.xn;
-        mlo = (int)((long long)xi * Mt / xm);
-        const int mhi = (int)((long long)(xi + 1) * Mt / xm);
-        nlo = xj * Nt / a.xn;
-        nx = (xj + 1) * Nt / a.xn - nlo;
-        first = (int)blockIdx.x >> 3;
-        stride = (int)gridDim.x >> 3;
-        count = (mhi - mlo) * nx;
-    } else {
-        first = (int)blockIdx.x;
-        stride = (int)gridDim.x;
-        count = Mt * Nt;
-    }
-    // split-K (EPI == GM_EPI_RAW): a work item is (tile, split); the ks splits of a tile are neighbours in the enumeration (same
-    // XCD: they read the same A rows and W rows at different k) and leave fp32 partial sums for gemm_splitk_finish_kernel
-    const int ks = 1;
-    count *= ks;
-    const int my_tiles = first < count ? (count - first + stride - 1) / stride : 0;  // work items of this workgroup
-    if (my_tiles == 0) return;
-    auto tile_origin = [&](int i, int& m0, int& n0) {
-        const int lt = (first + min(i, my_tiles - 1) * stride) / ks;  // (cursors running past the end re-read the last tile)
-        const int q = lt / nx;
-        m0 = min((mlo + q) * GM_TM, a.M - GM_TM);
-        n0 = min((nlo + (lt - q * nx)) * TN, a.N - TN);
-    };
-    auto item_split = [&](int i) { return (first + min(i, my_tiles - 1) * stride) % ks; };
-    // where the tile would start without the shift: rows / columns below are the neighbour tile's and are not stored again
-    auto tile_keep_from = [&](int i, int& mk, int& nk_) {
-        const int lt = (first + min(i, my_tiles - 1) * stride) / ks;
-        const int q = lt / nx;
-        mk = (mlo + q) * GM_TM;
-        nk_ = (nlo + (lt - q * nx)) * TN;
-    };
-    const int nk = (a.K / GM_KC) / ks;  // K-steps per work item
-    const int S = my_tiles * nk;
-    // row pitches in bytes (split-bf16 flavour: A rows hold [hi | lo] = 2 K1 elements, W rows [hi | lo | hi] = 3 K1 = K elements)
-    const int KA2 = (a.lda ? a.lda : a.K) * 2, KW2 = (a.ldw ? a.ldw : a.K) * 2;
-    // ---- DMA: wave w moves the 8-row groups 4 w .. 4 w + 3 of every half-tile; lane -> (row lane >> 3 of the group, LDS octet
-    // position lane & 7, which holds k-octet position ^ ((row >> 1) & 7)) ------------------------------------------------
-    const __amdgpu_buffer_rsrc_t rsA = make_rsrc(a.A), rsW = make_rsrc(a.W);
-    unsigned voffA[4], voffW[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const int row = (wave * 4 + j) * 8 + (lane >> 3);
-        const unsigned sw = (unsigned)(((lane & 7) ^ ((row >> 1) & 7)) * 16);
-        voffA[j] = (unsigned)row * (unsigned)KA2 + sw;
-        voffW[j] = (unsigned)row * (unsigned)KW2 + sw;
-    }
-    // regions of buffer b: A half h at b * 65536 + h * 16384, W half h at b * 65536 + 32768 + h * 16384
-    // (the scalar offset through v_readfirstlane: the cursors are uniform by construction, but hipcc kept the A cursor in a VGPR and
-    // wrapped each of its DMA instructions in a waterfall loop - readfirstlane, compare, exec mask, branch - inside the K-loop)
-    // one piece = one wave instruction = 1 KiB = 8 rows of a half-tile; a half-tile is 16 pieces, 4 per wave
-    auto pieceA = [&](int region, int so, int j) {
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(rsA, (lds_ptr)(smem + region + (wave * 4 + j) * 1024), 16, voffA[j], so, 0, 0);
-    };
-    auto pieceW = [&](int region, int so, int j) {
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(rsW, (lds_ptr)(smem + region + (wave * 4 + j) * 1024), 16, voffW[j], so, 0, 0);
-    };
-    // cursors over the flat K-steps t + 1 and t + 2: scalar byte offsets of their A / W tiles' first row at their k
-    struct Cur {
-        int ti, kk, sa, sw;
-    };
-    auto cur_set = [&](Cur& c) {
-        int m0, n0;
-        tile_origin(c.ti, m0, n0);
-        const int ks_ = item_split(c.ti) * nk + c.kk;                       // K-step of the (virtual) contraction
-        const int ka = (a.a_wrap && ks_ >= a.a_wrap) ? ks_ - a.a_wrap : ks_;  // split-bf16: A' = [hi | hi | lo] read out of [hi | lo]
-        c.sa = __builtin_amdgcn_readfirstlane(m0 * KA2 + ka * (GM_KC * 2));  // (uniform by construction; keeps the cursor arithmetic on the scalar unit)
-        c.sw = __builtin_amdgcn_readfirstlane(n0 * KW2 + ks_ * (GM_KC * 2));
-    };
-    auto cur_next = [&](Cur& c) {
-        if (++c.kk == nk) c.kk = 0, ++c.ti;
-        cur_set(c);
-    };
-
-
-    // ---- fragments (v_mfma_f32_32x32x16_bf16: a 32-cycle MFMA hides ONE memory instruction completely - a 16x16x32 one, 16 cycles, does
-    // not: measured 15-20 cycles of matrix-pipe idle per LDS / VMEM instruction placed behind it).  Fragment (32-row group g, 16-deep
-    // sub-step ks): lane (r = lane & 31, kh = lane >> 5) reads the 16 bytes at row g * 32 + r, k-octet 2 ks + kh of the half-tile. ----------
-    const int r32 = lane & 31, kh = lane >> 5;
-    uint32_t la[4];  // lane address inside a half-tile at 32-row group 0, per sub-step (the octet swizzle depends on the row pair only)
-#pragma unroll
-    for (int ks = 0; ks < 4; ++ks) la[ks] = (uint32_t)(r32 * 128 + (((2 * ks + kh) ^ ((r32 >> 1) & 7)) * 16));
-    const int fxa = wr * 16384, fwb = 32768 + wc * 16384;
-    bf16x8 X[2][4], W[2][4];  // [register set = sub-step parity][32-row group]
-    f32x16 acc[4][4];         // [token group][output group]: D[output][token] of W X^T
-#pragma unroll
-    for (int mg = 0; mg < 4; ++mg)
-#pragma unroll
-        for (int ng = 0; ng < 4; ++ng)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) acc[mg][ng][e] = 0.f;
-    // staging registers: this wave's 16 pieces (16 bytes per lane each) of one K-step, global -> VGPR -> LDS.  (LDS-DMA, which the other
-    // kernels of this file stage with, takes 60-100 cycles of the wave's instruction stream per piece: with one wave per SIMD that is
-    // 36 % of a K-step - measured, profiles/r03_gemm_w4_experiments.txt - where the 8-wave kernel hides it behind the partner wave.)
-    fg_u32x4 G[16];
-    const uint32_t wl = (uint32_t)(uintptr_t)smem + (uint32_t)((wave * 4) * 1024 + lane * 16);  // LDS address of this lane's 16 bytes of piece j = 0
-
-    // ---- epilogue of one 32-token x 32-output accumulator tile (mg, ng).  Lane (token r, half h) holds outputs 8 q + 4 h + (0..3), q = 0..3;
-    // v_permlane32_swap of group 2 P with group 2 P + 1 leaves lane h = 0 with outputs 16 P .. 16 P + 7 and lane h = 1 with 16 P + 8 .. + 15
-    // of its token: one 16-byte store each, bias / GELU / gate / residual on the eight consecutive outputs as in gemm_bf16_pp_kernel. ------
-    int ep_m0 = 0, ep_n0 = 0, ep_mk = 0, ep_nk = 0;
-    const int lane_c8 = wc * 128 + 8 * kh;
-    const int vo_out = ((wr * 128 + r32) * a.N + lane_c8) * 2;
-    const __amdgpu_buffer_rsrc_t rsO = make_rsrc(a.out), rsR = make_rsrc(a.resid), rsG = make_rsrc(a.gate), rsB = make_rsrc(a.bias);
-    auto tile_out = [&](auto MG_, auto NG_) {
-        constexpr int MG = decltype(MG_)::value, NG = decltype(NG_)::value;
-        const int m0 = ep_m0, n0 = ep_n0, mk = ep_mk, nk_ = ep_nk;
-        const bool edge = (mk != m0) || (nk_ != n0);
-        const int row = m0 + wr * 128 + MG * 32 + r32;
-        int bnd = 0x7fffffff, gso = 0;
-        if (a.gate) {
-            const int gi0 = (a.row0 + m0) / a.gate_rows;
-            bnd = (gi0 + 1) * a.gate_rows - a.row0;
-            gso = __builtin_amdgcn_readfirstlane((gi0 * a.gate_stride + n0 + 32 * NG) * 4);
-        }
-        if (W4_EXP & 16) {  // (experiment: no epilogue)
-            asm volatile("" : "+a"(acc[MG][NG]));
-            return;
-        }
-        // (the tile leaves the accumulator file through explicit reads: as plain vector arithmetic on acc[][] hipcc moves ALL sixteen tiles
-        //  into vector registers for the epilogue - 256 of them - and spills the staging registers, in the K-loop as well)
-        float tv[16];
-#pragma unroll
-        for (int e = 0; e < 16; ++e) asm volatile("v_accvgpr_read_b32 %0, %1" : "=v"(tv[e]) : "a"(acc[MG][NG][e]));
-        {
-            f32x16 z;
-#pragma unroll
-            for (int e = 0; e < 16; ++e) z[e] = 0.f;
-            asm volatile("s_nop 0" ::: "memory");
-            acc[MG][NG] = z;
-            asm volatile("" : "+a"(acc[MG][NG]));
-        }
-#pragma unroll
-        for (int P = 0; P < 2; ++P) {
-            float e0 = tv[8 * P], e1 = tv[8 * P + 1], e2 = tv[8 * P + 2], e3 = tv[8 * P + 3];
-            float o0 = tv[8 * P + 4], o1 = tv[8 * P + 5], o2 = tv[8 * P + 6], o3 = tv[8 * P + 7];
-            asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %4\n\tv_permlane32_swap_b32 %1, %5\n\tv_permlane32_swap_b32 %2, %6\n\t"
-                         "v_permlane32_swap_b32 %3, %7\n\ts_nop 1"
-                         : "+v"(e0), "+v"(e1), "+v"(e2), "+v"(e3), "+v"(o0), "+v"(o1), "+v"(o2), "+v"(o3));
-            f32x4 ve = {e0, e1, e2, e3}, vo = {o0, o1, o2, o3};
-            const int c8 = n0 + lane_c8 + 32 * NG + 16 * P;
-            if (a.bias) {
-                const int bo_ = __builtin_amdgcn_readfirstlane((n0 + 32 * NG + 16 * P) * 4);
-                ve += __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsB, lane_c8 * 4, bo_, 0));
-                vo += __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsB, lane_c8 * 4, bo_ + 16, 0));
-            }
-            if (a.act & 1) {
-#pragma unroll
-                for (int e = 0; e < 4; ++e) ve[e] = gm_gelu_tanh(ve[e]), vo[e] = gm_gelu_tanh(vo[e]);
-            }
-            if (edge && !(row >= mk && c8 >= nk_)) continue;
-            if (a.gate) {
-                const int go = gso + 64 * P + (row >= bnd ? a.gate_stride * 4 : 0);
-                ve *= __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsG, lane_c8 * 4 + go - gso, gso, 0));
-                vo *= __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsG, lane_c8 * 4 + go - gso + 16, gso, 0));
-            }
-            const int so = __builtin_amdgcn_readfirstlane(((m0 + MG * 32) * a.N + n0 + 32 * NG + 16 * P) * 2);
-            if (a.resid) {
-                const bf16x8 r8 = __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(rsR, vo_out, so, 0));
-#pragma unroll
-                for (int e = 0; e < 4; ++e) ve[e] += (float)r8[e], vo[e] += (float)r8[4 + e];
-            }
-            bf16x8 o8;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) o8[e] = (__bf16)ve[e], o8[4 + e] = (__bf16)vo[e];
-            __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(fg_u32x4, o8), rsO, vo_out, so, 0);
-        }
-        __builtin_amdgcn_sched_barrier(0);
-    };
-
-    // ---- staging: piece p of a K-step = (region p >> 2: A rows 0-127 | A rows 128-255 | W rows 0-127 | W rows 128-255, 8-row group p & 3) ----
-    Cur c2{0, 0, 0, 0};  // the K-step the next loads fetch
-    cur_set(c2);
-    int g_sa0 = 0, g_sa1 = 0, g_sw0 = 0, g_sw1 = 0;
-    auto g_cur = [&]() {
-        if ((W4_EXP & 4) && g_sa1 != 0) return;  // (experiment: every K-step re-reads the first one's operands - cache-resident)
-        g_sa0 = c2.sa, g_sa1 = __builtin_amdgcn_readfirstlane(c2.sa + 128 * KA2), g_sw0 = c2.sw, g_sw1 = __builtin_amdgcn_readfirstlane(c2.sw + 128 * KW2);
-    };
-    auto g_load = [&](auto P_) {
-        constexpr int P = decltype(P_)::value, R = P >> 2, J = P & 3;
-        if (W4_EXP & 1) return;
-        if constexpr (R == 0) G[P] = __builtin_amdgcn_raw_buffer_load_b128(rsA, voffA[J], g_sa0, 0);
-        else if constexpr (R == 1) G[P] = __builtin_amdgcn_raw_buffer_load_b128(rsA, voffA[J], g_sa1, 0);
-        else if constexpr (R == 2) G[P] = __builtin_amdgcn_raw_buffer_load_b128(rsW, voffW[J], g_sw0, 0);
-        else G[P] = __builtin_amdgcn_raw_buffer_load_b128(rsW, voffW[J], g_sw1, 0);
-    };
-    auto g_store = [&](auto P_, uint32_t base) {  // base = wl + buffer * 65536
-        constexpr int P = decltype(P_)::value;
-        if (W4_EXP & 1) return;
-        const fg_u32x4& gp = G[P];
-        asm volatile("ds_write_b128 %0, %1 offset:%2" ::"v"(base), "v"(gp), "n"((P >> 2) * 16384 + (P & 3) * 1024) : "memory");
-    };
-    auto SBAR = [] { __builtin_amdgcn_sched_barrier(0); };
-    // fragment i of a sub-step: i = 0..3 token groups, 4..7 output groups
-    auto rd_f = [&](int set, auto I_, uint32_t xb, uint32_t wb) {  // xb / wb = buffer + half-tile + la[ks]
-        constexpr int I = decltype(I_)::value;
-        if (W4_EXP & 2) return;
-        if constexpr (I < 4) {
-            bf16x8& f = X[set][I];
-            asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(f) : "v"(xb), "n"(I * 4096));
-        } else {
-            bf16x8& f = W[set][I - 4];
-            asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(f) : "v"(wb), "n"((I - 4) * 4096));
-        }
-    };
-    const uint32_t s0 = (uint32_t)(uintptr_t)smem;
-
-    // ---- prologue: K-step 0 into buffer 0 through the registers, the loads of K-step 1 in flight, first fragments read --------------------
-    g_cur();
-    static_for<0, 16>([&](auto P_) { g_load(P_); });
-    if (S > 1) cur_next(c2);
-    static_for<0, 16>([&](auto P_) { g_store(P_, wl); });  // (the compiler waits for each load in front of its store)
-    g_cur();
-    static_for<0, 16>([&](auto P_) { g_load(P_); });      // K-step 1
-    if (S > 2) cur_next(c2);
-    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-    static_for<0, 8>([&](auto I_) { rd_f(0, I_, s0 + fxa + la[0], s0 + fwb + la[0]); });
-
-    // One K-step of 64 = four sub-steps of 16 MFMAs (4 token groups x 4 output groups), ONE memory instruction behind every MFMA:
-    //   slots 0-7 of sub-step ks: the eight fragments of sub-step ks + 1 (of the NEXT K-step, other buffer, for ks = 3)
-    //   slots 8-15: ks = 0, 1: the staged K-step t + 1 goes into the other LDS buffer (2 x 8 ds_write_b128)
-    //               ks = 2, 3: the loads of K-step t + 2 into the same registers (2 x 8)
-    //   between ks = 2 and 3: this wave's writes are done (lgkmcnt(0)), then the one barrier of the step
-    auto kstep = [&](int t) {
-        const int cb = t & 1, nb = cb ^ 1;
-        const uint32_t xcb = s0 + cb * 65536 + fxa, wcb = s0 + cb * 65536 + fwb, xnb = s0 + nb * 65536 + fxa, wnb_ = s0 + nb * 65536 + fwb;
-        const uint32_t wst = wl + nb * 65536;
-        static_for<0, 4>([&](auto KS_) {
-            constexpr int KS = decltype(KS_)::value, SET = KS & 1;
-            // this sub-step's fragments (read in slots 0-7 of the previous one; behind them at most its 8 LDS writes)
-            if constexpr (KS == 1 || KS == 2) asm volatile("s_waitcnt lgkmcnt(8)" ::: "memory");
-            else asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            if constexpr (KS == 3) {
-                asm volatile("s_barrier" ::: "memory");  // K-step t + 1 is in LDS, in every wave's part
-            }
-#pragma unroll
-            for (int i = 0; i < 4; ++i) asm volatile("" : "+v"(X[SET][i]), "+v"(W[SET][i]));
-            SBAR();
-            if constexpr (KS == 2) g_cur();
-            static_for<0, 16>([&](auto I_) {
-                constexpr int I = decltype(I_)::value, MG = I >> 2, NG = I & 3;
-                acc[MG][NG] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(W[SET][NG], X[SET][MG], acc[MG][NG], 0, 0, 0);
-                if constexpr (I < 8) {
-                    if constexpr (KS < 3) rd_f(SET ^ 1, I_, xcb + la[KS < 3 ? KS + 1 : 0], wcb + la[KS < 3 ? KS + 1 : 0]);
-                    else rd_f(SET ^ 1, I_, xnb + la[0], wnb_ + la[0]);
-                } else {
-                    if constexpr (KS < 2) g_store(std::integral_constant<int, 8 * KS + I - 8>{}, wst);
-                    else g_load(std::integral_constant<int, 8 * (KS - 2) + I - 8>{});
-                }
-                SBAR();
-            });
-        });
-    };
-    int t = 0;
-    for (int ti = 0; ti < my_tiles; ++ti) {
-        for (int kk = 0; kk < nk; ++kk) {  // (ONE copy of the K-step in the kernel: a second, peeled one gets its own accumulator registers
-            kstep(t);                      //  and 240 accumulator-to-accumulator moves to reconcile them)
-            if (t + 3 < S) cur_next(c2);
-            ++t;
-        }
-        tile_origin(ti, ep_m0, ep_n0);
-        tile_keep_from(ti, ep_mk, ep_nk);
-        static_for<0, 16>([&](auto I_) { tile_out(std::integral_constant<int, (decltype(I_)::value >> 2)>{}, std::integral_constant<int, (decltype(I_)::value & 3)>{}); });
-    }
-    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-}
-
 // ---- the narrow tile: 256 tokens x 128 outputs, for SHORT token counts ---------------------------------------------------------
 // One sample of the causal video DiT hands the block linears M = 4 680 tokens (a chunk of 3 latent frames): 19 token tiles.  With
 // 256-wide tiles N = 1 536 gives 114 tiles for 256 CUs; the kernel above then cuts K in two (fp32 partial sums through HBM + a finishing
@@ -1519,162 +1218,74 @@ __global__ __launch_bounds__(256) void quant_rows_fp8_kernel(const ST* __restric
     for (int c = 4 * lane; c < K; c += 256) qr[c >> 2] = fp8_pack4(gm_ld4(xr + c), inv);
 }
 
-int g_gm_cus[16] = {};
+// ---- host side: one plan (gemm_plan: every decision, no HIP call), one table of the instantiations, one launcher ------------------------
+static_assert(GM_EPI_TOK == FG_GEMM_EPI_TOK && GM_EPI_HEADS == FG_GEMM_EPI_HEADS && GM_EPI_RAW == FG_GEMM_EPI_RAW && GM_EPI_TOK32 == FG_GEMM_EPI_TOK32 &&
+                  GM_EPI_SPLIT == FG_GEMM_EPI_SPLIT && GM_EPI_HEADS32 == FG_GEMM_EPI_HEADS32,
+              "fg_gemm_plan.epilogue names the kernels' EPI template argument");
 
-template <int NT, int EPI, bool F8 = false>
-int launch_gm(const GemmArgs& a, hipStream_t s, bool prepare_only) {
-    constexpr int TN = 64 * NT;
-    constexpr int LDS = 2 * 8 * (GM_PA + TN * 16 + 16);
-    auto kern = gemm_bf16_kernel<NT, EPI, F8>;
-    const int dev = fg_device_slot();
-    if (dev < 0) return (int)hipErrorInvalidDevice;
-    static bool attr_done[16] = {};
-    if (!attr_done[dev]) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-        if (e != hipSuccess) return (int)e;
-        attr_done[dev] = true;
-    }
-    if (!g_gm_cus[dev]) {
-        int n = 0;
-        if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) return (int)hipErrorUnknown;
-        g_gm_cus[dev] = n;
-    }
-    if (prepare_only) return 0;
-    const int Mt = (a.M + GM_TM - 1) / GM_TM, Nt = (a.N + TN - 1) / TN;
-    GemmArgs b = a;
-    int grid = g_gm_cus[dev];
-    if ((long long)Mt * Nt < grid) grid = Mt * Nt, b.xn = 0;
-    if (grid & 7) b.xn = 0;
-    if (b.xn > 0) {
-        // XCD grid xm x xn: the widest split of the output tiles that divides them and still leaves every XCD >= 4 token tiles;
-        // an explicit a.xn (tuning) is taken when it divides
-        int xn = 1;
-        for (int c = 8; c >= 1; c >>= 1)
-            if (Nt % c == 0 && Mt / (8 / c) >= 4) {
-                xn = c;
-                break;
-            }
-        if (a.xn <= 8 && (a.xn & (a.xn - 1)) == 0 && Nt % a.xn == 0 && a.xn != 1) xn = a.xn;
-        b.xn = xn;
-    }
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(GM_NTHR), LDS, s, b);
-    return (int)hipGetLastError();
+// dynamic LDS of a kernel form: the register-staged kernel's two stages of 8 + 8 octet planes, the ping-pong kernel's two 64 KiB buffers,
+// the narrow tile's ring of three 48 KiB stages
+constexpr int gm_lds_bytes(int kernel, int tile_n) {
+    return kernel == FG_GEMM_REG ? 2 * 8 * (GM_PA + tile_n * 16 + 16) : kernel == FG_GEMM_PP_NARROW ? 3 * 49152 : 131072;
 }
 
-template <int EPI, bool F8 = false>
-int launch_pp(const GemmArgs& a, hipStream_t s, bool prepare_only) {
-    constexpr int LDS = 131072;
-    auto kern = gemm_bf16_pp_kernel<EPI, F8>;
-    const int dev = fg_device_slot();
-    if (dev < 0) return (int)hipErrorInvalidDevice;
-    static bool attr_done[16] = {};
-    if (!attr_done[dev]) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-        if (e != hipSuccess) return (int)e;
-        attr_done[dev] = true;
-    }
-    if (!g_gm_cus[dev]) {
-        int n = 0;
-        if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) return (int)hipErrorUnknown;
-        g_gm_cus[dev] = n;
-    }
-    if (prepare_only) return 0;
-    const int Mt = (a.M + GM_TM - 1) / GM_TM, Nt = (a.N + 255) / 256;
-    GemmArgs b = a;
-    int grid = g_gm_cus[dev];
-    const long long items = (long long)Mt * Nt * (EPI == GM_EPI_RAW ? a.ksplit : 1);
-    if (items < grid) grid = (int)items, b.xn = 0;
-    if (grid & 7) b.xn = 0;
-    if (b.xn > 0) {
-        int xn = 1;
-        for (int c = 8; c >= 1; c >>= 1)
-            if (Nt % c == 0 && Mt / (8 / c) >= 4) {
-                xn = c;
-                break;
-            }
-        if (a.xn <= 8 && (a.xn & (a.xn - 1)) == 0 && Nt % a.xn == 0 && a.xn != 1) xn = a.xn;
-        b.xn = xn;
-    }
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(GM_NTHR), LDS, s, b);
-    if (EPI == GM_EPI_RAW) {
-        const int64_t n = (int64_t)a.M * (a.N / 8);
-        hipLaunchKernelGGL(gemm_splitk_finish_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, b);
-    }
-    return (int)hipGetLastError();
+// Every instantiation the launcher can reach, keyed by what a plan names (split-K is the wide ping-pong kernel with the RAW epilogue).
+struct GmKernel {
+    bool f8;
+    int kernel, tile_n, epilogue;
+    const void* fn;
+    bool attr_done[16];  // per device: hipFuncSetAttribute(dynamic LDS) has run
+};
+#define GM_FN(...) reinterpret_cast<const void*>(&__VA_ARGS__), {}
+GmKernel g_gm_kernels[] = {
+    {false, FG_GEMM_REG, 256, GM_EPI_TOK, GM_FN(gemm_bf16_kernel<4, GM_EPI_TOK>)},
+    {false, FG_GEMM_REG, 192, GM_EPI_TOK, GM_FN(gemm_bf16_kernel<3, GM_EPI_TOK>)},
+    {false, FG_GEMM_REG, 256, GM_EPI_HEADS, GM_FN(gemm_bf16_kernel<4, GM_EPI_HEADS>)},
+    {false, FG_GEMM_REG, 192, GM_EPI_HEADS, GM_FN(gemm_bf16_kernel<3, GM_EPI_HEADS>)},
+    {false, FG_GEMM_PP, 256, GM_EPI_TOK, GM_FN(gemm_bf16_pp_kernel<GM_EPI_TOK>)},
+    {false, FG_GEMM_PP, 256, GM_EPI_HEADS, GM_FN(gemm_bf16_pp_kernel<GM_EPI_HEADS>)},
+    {false, FG_GEMM_PP_SPLITK, 256, GM_EPI_RAW, GM_FN(gemm_bf16_pp_kernel<GM_EPI_RAW>)},
+    {false, FG_GEMM_PP, 256, GM_EPI_TOK32, GM_FN(gemm_bf16_pp_kernel<GM_EPI_TOK32>)},
+    {false, FG_GEMM_PP, 256, GM_EPI_SPLIT, GM_FN(gemm_bf16_pp_kernel<GM_EPI_SPLIT>)},
+    {false, FG_GEMM_PP, 256, GM_EPI_HEADS32, GM_FN(gemm_bf16_pp_kernel<GM_EPI_HEADS32>)},
+    {false, FG_GEMM_PP_NARROW, 128, GM_EPI_TOK, GM_FN(gemm_bf16_pp2_kernel)},
+    {true, FG_GEMM_REG, 256, GM_EPI_TOK, GM_FN(gemm_bf16_kernel<4, GM_EPI_TOK, true>)},
+    {true, FG_GEMM_REG, 192, GM_EPI_TOK, GM_FN(gemm_bf16_kernel<3, GM_EPI_TOK, true>)},
+    {true, FG_GEMM_PP, 256, GM_EPI_TOK, GM_FN(gemm_bf16_pp_kernel<GM_EPI_TOK, true>)},
+    {true, FG_GEMM_PP, 256, GM_EPI_HEADS, GM_FN(gemm_bf16_pp_kernel<GM_EPI_HEADS, true>)},
+};
+#undef GM_FN
+
+int gm_set_attr(GmKernel& k, int dev) {
+    if (k.attr_done[dev]) return 0;
+    const hipError_t e = hipFuncSetAttribute(k.fn, hipFuncAttributeMaxDynamicSharedMemorySize, gm_lds_bytes(k.kernel, k.tile_n));
+    k.attr_done[dev] = e == hipSuccess;
+    return (int)e;
 }
 
-// the narrow-tile kernel (256 x 128): token epilogue only
-// the one-wave-per-SIMD kernel (256 x 256 tiles, 4 waves): token epilogue only
-int launch_w4(const GemmArgs& a, hipStream_t s, bool prepare_only) {
-    constexpr int LDS = 131072;
-    const int dev = fg_device_slot();
-    if (dev < 0) return (int)hipErrorInvalidDevice;
-    static bool attr_done[16] = {};
-    if (!attr_done[dev]) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_bf16_w4_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-        if (e != hipSuccess) return (int)e;
-        attr_done[dev] = true;
-    }
-    if (!g_gm_cus[dev]) {
-        int n = 0;
-        if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) return (int)hipErrorUnknown;
-        g_gm_cus[dev] = n;
-    }
-    if (prepare_only) return 0;
-    const int Mt = (a.M + GM_TM - 1) / GM_TM, Nt = (a.N + 255) / 256;
-    GemmArgs b = a;
-    int grid = g_gm_cus[dev];
-    const long long items = (long long)Mt * Nt;
-    if (items < grid) grid = (int)items, b.xn = 0;
-    if (grid & 7) b.xn = 0;
-    if (b.xn > 0) {
-        int xn = 1;
-        for (int c = 8; c >= 1; c >>= 1)
-            if (Nt % c == 0 && Mt / (8 / c) >= 4) {
-                xn = c;
-                break;
-            }
-        if (a.xn <= 8 && (a.xn & (a.xn - 1)) == 0 && Nt % a.xn == 0 && a.xn != 1) xn = a.xn;
-        b.xn = xn;
-    }
-    hipLaunchKernelGGL(gemm_bf16_w4_kernel, dim3(grid), dim3(256), LDS, s, b);
-    return (int)hipGetLastError();
+int gm_cus(int dev) {  // (0: the query failed)
+    static int cus[16] = {};
+    if (!cus[dev] && (hipDeviceGetAttribute(&cus[dev], hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus[dev] < 0)) cus[dev] = 0;
+    return cus[dev];
 }
 
-int launch_pp2(const GemmArgs& a, hipStream_t s, bool prepare_only) {
-    constexpr int LDS = 3 * 49152;
-    const int dev = fg_device_slot();
-    if (dev < 0) return (int)hipErrorInvalidDevice;
-    static bool attr_done[16] = {};
-    if (!attr_done[dev]) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_bf16_pp2_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
+// One launch of a plan: `piece` holds the arguments of that row piece; xn and ksplit are the plan's.  Split-K: + the finishing pass over the partial sums.
+int gm_launch(const GemmArgs& piece, const GemmPlan& p, bool f8, int dev, hipStream_t s) {
+    for (GmKernel& k : g_gm_kernels) {
+        if (k.f8 != f8 || k.kernel != p.kernel || k.tile_n != p.tile_n || k.epilogue != p.epilogue) continue;
+        if (const int rc = gm_set_attr(k, dev)) return rc;
+        GemmArgs b = piece;
+        b.xn = p.xn, b.ksplit = p.ksplit;
+        void* args[] = {&b};
+        const hipError_t e = hipLaunchKernel(k.fn, dim3(p.grid), dim3(GM_NTHR), args, p.lds_bytes, s);
         if (e != hipSuccess) return (int)e;
-        attr_done[dev] = true;
+        if (p.epilogue == GM_EPI_RAW) {
+            const int64_t n = (int64_t)b.M * (b.N / 8);
+            hipLaunchKernelGGL(gemm_splitk_finish_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, b);
+        }
+        return (int)hipGetLastError();
     }
-    if (!g_gm_cus[dev]) {
-        int n = 0;
-        if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) return (int)hipErrorUnknown;
-        g_gm_cus[dev] = n;
-    }
-    if (prepare_only) return 0;
-    const int Mt = (a.M + GM_TM - 1) / GM_TM, Nt = (a.N + 127) / 128;
-    GemmArgs b = a;
-    int grid = g_gm_cus[dev];
-    const long long items = (long long)Mt * Nt;
-    if (items < grid) grid = (int)items, b.xn = 0;
-    if (grid & 7) b.xn = 0;
-    if (b.xn > 0) {
-        int xn = 1;
-        for (int c = 8; c >= 1; c >>= 1)
-            if (Nt % c == 0 && Mt / (8 / c) >= 4) {
-                xn = c;
-                break;
-            }
-        if (a.xn <= 8 && (a.xn & (a.xn - 1)) == 0 && Nt % a.xn == 0 && a.xn != 1) xn = a.xn;
-        b.xn = xn;
-    }
-    hipLaunchKernelGGL(gemm_bf16_pp2_kernel, dim3(grid), dim3(GM_NTHR), LDS, s, b);
-    return (int)hipGetLastError();
+    return (int)hipErrorInvalidValue;  // (a plan names no other form: the table above is what gemm_plan can return)
 }
 
 // Which short grids take the narrow tile: the 256-wide tiling would leave CUs idle (fewer than 2.5 tiles per CU) and the 128-wide one
@@ -1702,26 +1313,11 @@ int gm_pick_ksplit(const GemmArgs& a, int cus) {
     return 1;
 }
 
-int gm_env(const char* name, int dflt) {
+// FASTGEN_AMD_GEMM_PP=0: the register-staged kernel wherever the launcher has the choice; FASTGEN_AMD_GEMM_NARROW=0: never the 256 x 128
+// tile (A/B measurements).  Read once per process.
+bool gm_switch(const char* name) {
     const char* e = getenv(name);
-    return e ? atoi(e) : dflt;
-}
-// FASTGEN_AMD_GEMM_NARROW=0: never the 256 x 128 tile (A/B measurements)
-bool gm_narrow_enabled() {
-    static const bool on = [] {
-        const char* e = getenv("FASTGEN_AMD_GEMM_NARROW");
-        return !(e && e[0] == '0');
-    }();
-    return on;
-}
-// 0: gemm_bf16_kernel (register-staged), 1: gemm_bf16_pp_kernel (LDS-DMA, ping-pong) where the shape allows
-int gm_variant() {
-    static int v = -1;
-    if (v < 0) {
-        const char* e = getenv("FASTGEN_AMD_GEMM_PP");
-        v = (e && e[0] == '0') ? 0 : 1;
-    }
-    return v;
+    return !(e && e[0] == '0');
 }
 
 }  // namespace
@@ -1735,123 +1331,10 @@ bool gemm_bf16_supported(const GemmArgs& a) {
     return a.A && a.W;
 }
 
-// xn: 0 = linear tile order, 1 = choose the XCD grid, 2 / 4 / 8 = force that many output-tile columns of XCDs
-int launch_gemm_bf16(const GemmArgs& a, hipStream_t s, bool prepare_only) {
-    if (!prepare_only && !gemm_bf16_supported(a)) return (int)hipErrorInvalidValue;
-    const bool heads = a.heads > 0;
-    const bool n3 = !prepare_only && (a.N % 256) != 0 && (a.N % 192) == 0;
-    if (prepare_only) {
-        int rc;
-        if ((rc = launch_gm<4, GM_EPI_TOK>(a, s, true)) || (rc = launch_gm<3, GM_EPI_TOK>(a, s, true)) ||
-            (rc = launch_gm<4, GM_EPI_HEADS>(a, s, true)) || (rc = launch_gm<3, GM_EPI_HEADS>(a, s, true)) ||
-            (rc = launch_pp<GM_EPI_TOK>(a, s, true)) || (rc = launch_pp<GM_EPI_HEADS>(a, s, true)) || (rc = launch_pp<GM_EPI_RAW>(a, s, true)) ||
-            (rc = launch_pp<GM_EPI_TOK32>(a, s, true)) || (rc = launch_pp<GM_EPI_SPLIT>(a, s, true)) || (rc = launch_pp<GM_EPI_HEADS32>(a, s, true)) ||
-            (rc = launch_pp2(a, s, true)))
-            return rc;
-        return 0;
-    }
-    // rows per launch: staging offsets into A stay below the buffer resource's 2 GiB
-    // (... and the epilogue's offsets into out / resid: N instead of K)
-    const int rows_max = (int)(((1ull << 31) - 1) / ((size_t)(a.K > a.N ? a.K : a.N) * 2)) / GM_TM * GM_TM;
-    for (int r0 = 0; r0 < a.M; r0 += rows_max) {
-        GemmArgs b = a;
-        b.row0 = a.row0 + r0;
-        b.M = a.M - r0 < rows_max ? a.M - r0 : rows_max;
-        b.A = reinterpret_cast<const __bf16*>(a.A) + (size_t)r0 * a.K;
-        if (a.out) b.out = reinterpret_cast<__bf16*>(a.out) + (size_t)r0 * a.N;
-        if (a.resid) b.resid = reinterpret_cast<const __bf16*>(a.resid) + (size_t)r0 * a.N;
-        const bool pp = (a.variant < 0 ? gm_variant() : (a.variant >= 2 ? 1 : a.variant)) == 1 && b.M >= GM_TM && a.N >= 256 && a.K >= 2 * GM_KC &&
-                        (!a.gate || a.gate_rows >= GM_TM);  // (the ping-pong kernel's token epilogue: a tile spans at most two gate rows)
-        if (pp && !heads && !a.out_f32 && rows_max >= a.M) {
-            const int dev = fg_device_slot();
-            const int cus = dev >= 0 && g_gm_cus[dev] ? g_gm_cus[dev] : 256;
-            if (a.variant == 3) {  // (experimental: one wave per SIMD)
-                if (b.M < GM_TM || b.N < 256) return (int)hipErrorInvalidValue;
-                const int rc4 = launch_w4(b, s, false);
-                if (rc4) return rc4;
-                continue;
-            }
-            if (a.variant == 2 || (a.variant < 0 && gm_narrow_enabled() && gm_use_narrow(b, cus))) {
-                const int rc0 = launch_pp2(b, s, false);
-                if (rc0) return rc0;
-                continue;
-            }
-            b.ksplit = gm_pick_ksplit(b, cus);
-            if (b.ksplit > 1) {
-                const int rc2 = launch_pp<GM_EPI_RAW>(b, s, false);
-                if (rc2) return rc2;
-                continue;
-            }
-        }
-        if (a.out_f32) {
-            if (!pp || heads || rows_max < a.M) return (int)hipErrorInvalidValue;
-            const int rc3 = launch_pp<GM_EPI_TOK32>(b, s, false);
-            if (rc3) return rc3;
-            continue;
-        }
-        const int rc = pp ? (heads ? launch_pp<GM_EPI_HEADS>(b, s, false) : launch_pp<GM_EPI_TOK>(b, s, false))
-                          : heads ? (n3 ? launch_gm<3, GM_EPI_HEADS>(b, s, false) : launch_gm<4, GM_EPI_HEADS>(b, s, false))
-                                  : (n3 ? launch_gm<3, GM_EPI_TOK>(b, s, false) : launch_gm<4, GM_EPI_TOK>(b, s, false));
-        if (rc) return rc;
-    }
-    return 0;
-}
-
-int launch_cvt_bf16(const float* in, void* out, size_t n, hipStream_t s) {
-    const size_t blocks = (n + 255) / 256;
-    hipLaunchKernelGGL(cvt_bf16_kernel, dim3((unsigned)(blocks > 8192 ? 8192 : blocks)), dim3(256), 0, s, in, (__bf16*)out, n);
-    return (int)hipGetLastError();
-}
-
-// ---- split-bf16 ("bf16x3", the fp32-grade mode of common.h) on the same kernel -----------------------------------------------
-// sum_k a_k w_k with a = a_hi + a_lo, w = w_hi + w_lo evaluated as a_hi w_hi + a_hi w_lo + a_lo w_hi is ONE bf16 contraction of
-// length 3 K: A' = [a_hi | a_hi | a_lo], W' = [w_hi | w_lo | w_hi].  A is stored as [hi | lo] planes ([M][2 K] bf16, the same bytes
-// as the fp32 tensor; its hi plane is read twice: a_wrap) by the producing kernel (LayerNorm-modulate, the SPLIT epilogue of the
-// previous GEMM, split_planes_kernel), W' once per weight version; fp32 accumulation over all 3 K products, fp32 epilogue.
-// a: M, N, K = the real contraction length; A = planes, W = W'; out: fp32 [M][N] (out_mode 0, + fp32 resid / gate), [hi | lo]
-// planes [M][2 N] (out_mode 1), or head-split hi / lo planes (heads > 0, lo_off).
-int launch_gemm_x3(const GemmArgs& a, int out_mode, hipStream_t s) {
-    if (a.M < GM_TM || a.N < 256 || (a.N % 16) || (a.K % GM_KC) || 3 * a.K < 2 * GM_KC || !a.A || !a.W) return (int)hipErrorInvalidValue;
-    if ((size_t)a.N * 3 * a.K * 2 >= (1ull << 31)) return (int)hipErrorInvalidValue;
-    const int rows_max = (int)(((1ull << 31) - 1) / ((size_t)a.K * 4)) / GM_TM * GM_TM;
-    for (int r0 = 0; r0 < a.M; r0 += rows_max) {
-        GemmArgs b = a;
-        b.row0 = a.row0 + r0;
-        b.M = a.M - r0 < rows_max ? a.M - r0 : rows_max;
-        if (b.M < GM_TM) return (int)hipErrorInvalidValue;  // (a remainder below one tile: not met by the callers' shapes)
-        b.A = reinterpret_cast<const __bf16*>(a.A) + (size_t)r0 * 2 * a.K;
-        b.lda = 2 * a.K, b.ldw = 3 * a.K, b.a_wrap = a.K / GM_KC, b.K = 3 * a.K;
-        b.ksplit = 1, b.scratch = nullptr;
-        if (a.resid) b.resid = reinterpret_cast<const float*>(a.resid) + (size_t)r0 * a.N;
-        int rc;
-        if (a.heads > 0) {
-            rc = launch_pp<GM_EPI_HEADS32>(b, s, false);
-        } else if (out_mode == 1) {
-            b.out = reinterpret_cast<__bf16*>(a.out) + (size_t)r0 * 2 * a.N;
-            rc = launch_pp<GM_EPI_SPLIT>(b, s, false);
-        } else {
-            b.out = reinterpret_cast<float*>(a.out) + (size_t)r0 * a.N;
-            rc = launch_pp<GM_EPI_TOK32>(b, s, false);
-        }
-        if (rc) return rc;
-    }
-    return 0;
-}
-int launch_split3_weights(const float* w, void* out, int N, int K, hipStream_t s) {
-    const int64_t n = (int64_t)N * K;
-    hipLaunchKernelGGL(split3_weights_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, w, (__bf16*)out, N, K);
-    return (int)hipGetLastError();
-}
-int launch_split_planes(const float* x, void* out, int64_t M, int K, hipStream_t s) {
-    const int64_t n = M * (K / 4);
-    hipLaunchKernelGGL(split_planes_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, x, (__bf16*)out, M, K);
-    return (int)hipGetLastError();
-}
-
 // ---- fp8 (e4m3) flavour of the token GEMM ------------------------------------------------------------------------------------------
 // A [M][K], W [N][K] e4m3fn bytes with a_scale [M], w_scale [N] (launch_quant_rows_fp8); out = epilogue(a_scale[m] w_scale[n] sum_k
 // qa qw + bias[n]) with the bf16 GEMM's token / head-split epilogues.  K % 128 == 0, N % 16 == 0.  The ping-pong kernel where M, N >=
-// 256 and K >= 256 (variant -1: unless FASTGEN_AMD_GEMM_PP=0, as launch_gemm_bf16), else the register-staged one - which has the token
+// 256 and K >= 256 (variant -1: unless FASTGEN_AMD_GEMM_PP=0, as the bf16 flavour), else the register-staged one - which has the token
 // epilogue only: a head-split launch that is not ping-pong eligible is refused.  No split-K, no narrow tile.
 bool gemm_fp8_supported(const GemmArgs& a) {
     if (a.M <= 0 || a.N <= 0 || a.K <= 0 || (a.K % 128) || (a.N % 16)) return false;
@@ -1864,35 +1347,150 @@ bool gemm_fp8_supported(const GemmArgs& a) {
     return a.A && a.W && a.a_scale && a.w_scale;
 }
 
-int launch_gemm_fp8(const GemmArgs& a, hipStream_t s, bool prepare_only) {
-    if (prepare_only) {
-        int rc;
-        if ((rc = launch_gm<4, GM_EPI_TOK, true>(a, s, true)) || (rc = launch_gm<3, GM_EPI_TOK, true>(a, s, true)) ||
-            (rc = launch_pp<GM_EPI_TOK, true>(a, s, true)) || (rc = launch_pp<GM_EPI_HEADS, true>(a, s, true)))
-            return rc;
-        return 0;
-    }
-    if (!gemm_fp8_supported(a)) return (int)hipErrorInvalidValue;
-    const bool heads = a.heads > 0;
-    const bool n3 = (a.N % 256) != 0 && (a.N % 192) == 0;
-    // rows per launch: byte offsets into A (K per row) and out / resid (2 N per row) stay below the buffer resource's 2 GiB
-    const int rows_max = (int)(((1ull << 31) - 1) / ((size_t)(a.K > 2 * a.N ? a.K : 2 * a.N))) / GM_TM * GM_TM;
-    for (int r0 = 0; r0 < a.M; r0 += rows_max) {
+GemmPlan gemm_plan(int flavour, const GemmArgs& a, int out_mode, int cus, int piece) {
+    static const bool pp_on = gm_switch("FASTGEN_AMD_GEMM_PP"), narrow_on = gm_switch("FASTGEN_AMD_GEMM_NARROW");
+    const bool x3 = flavour == 1, f8 = flavour == 2, heads = a.heads > 0;
+    GemmPlan p = {};
+    auto refuse = [&](int why) {
+        p = GemmPlan{};
+        p.refusal = why;
+        return p;
+    };
+    if (flavour < 0 || flavour > 2 || cus <= 0 || piece < 0 || a.M <= 0 || a.N <= 0 || a.K <= 0) return refuse(FG_GEMM_REFUSE_ARG);
+    // staging offsets into W stay below the buffer resource's 2 GiB
+    if ((size_t)a.N * a.K * (x3 ? 6 : f8 ? 1 : 2) >= (1ull << 31)) return refuse(FG_GEMM_REFUSE_OFFSET);
+    if (x3 ? (a.M < GM_TM || a.N < 256 || (a.N % 16) || (a.K % GM_KC) || 3 * a.K < 2 * GM_KC || !a.A || !a.W || (out_mode != 0 && out_mode != 1) ||
+              (heads ? (a.head_dim % 8 || a.N != 3 * a.heads * a.head_dim || a.T <= 0 || !a.q || !a.k || !a.vt) : !a.out))
+           : !(f8 ? gemm_fp8_supported(a) : gemm_bf16_supported(a)))
+        return refuse(FG_GEMM_REFUSE_ARG);
+    // rows per launch: byte offsets into A (a row is 2 K / 4 K / K bytes: bf16 / [hi | lo] planes / e4m3) and into out / resid
+    // (2 N / 4 N / 2 N) stay below the buffer resource's 2 GiB
+    const size_t kn = a.K > a.N ? a.K : a.N;
+    const size_t pitch = x3 ? 4 * kn : f8 ? (a.K > 2 * a.N ? a.K : 2 * a.N) : 2 * kn;
+    const int rows_max = (int)(((1ull << 31) - 1) / pitch) / GM_TM * GM_TM;
+    if (rows_max <= 0) return refuse(FG_GEMM_REFUSE_OFFSET);  // (not one 256-row tile below 2 GiB: N > 4 M outputs)
+    p.pieces = (a.M + rows_max - 1) / rows_max;
+    if (piece >= p.pieces) return refuse(FG_GEMM_REFUSE_ARG);
+    p.row0 = piece * rows_max;
+    p.rows = a.M - p.row0 < rows_max ? a.M - p.row0 : rows_max;
+
+    // the kernel form of a piece of `rows` rows (0: refused, *why says so)
+    auto form = [&](int rows, int* why) {
         GemmArgs b = a;
-        b.row0 = a.row0 + r0;
-        b.M = a.M - r0 < rows_max ? a.M - r0 : rows_max;
-        b.A = reinterpret_cast<const unsigned char*>(a.A) + (size_t)r0 * a.K;
-        b.a_scale = a.a_scale + r0;
-        if (a.out) b.out = reinterpret_cast<__bf16*>(a.out) + (size_t)r0 * a.N;
-        if (a.resid) b.resid = reinterpret_cast<const __bf16*>(a.resid) + (size_t)r0 * a.N;
-        b.ksplit = 1, b.scratch = nullptr, b.lda = b.ldw = b.a_wrap = 0, b.out_f32 = 0;
-        const bool pp = (a.variant < 0 ? gm_variant() : a.variant) != 0 && b.M >= GM_TM && a.N >= 256 && a.K >= 256 && (!a.gate || a.gate_rows >= GM_TM);
-        if (heads && !pp) return (int)hipErrorInvalidValue;
-        const int rc = pp ? (heads ? launch_pp<GM_EPI_HEADS, true>(b, s, false) : launch_pp<GM_EPI_TOK, true>(b, s, false))
-                          : (n3 ? launch_gm<3, GM_EPI_TOK, true>(b, s, false) : launch_gm<4, GM_EPI_TOK, true>(b, s, false));
-        if (rc) return rc;
+        b.M = rows;
+        p.kernel = FG_GEMM_PP, p.tile_n = 256, p.ksplit = 1;
+        if (x3) {
+            p.epilogue = heads ? GM_EPI_HEADS32 : out_mode == 1 ? GM_EPI_SPLIT : GM_EPI_TOK32;
+            *why = FG_GEMM_REFUSE_PIECE;  // (a remainder below one tile: not met by the callers' shapes)
+            return rows >= GM_TM;
+        }
+        // (the ping-pong kernel's token epilogue: a tile spans at most two gate rows)
+        const bool pp = (a.variant < 0 ? pp_on : a.variant != 0) && rows >= GM_TM && a.N >= 256 && a.K >= (f8 ? 256 : 2 * GM_KC) &&
+                        (!a.gate || a.gate_rows >= GM_TM);
+        const bool f32 = !f8 && a.out_f32;
+        *why = FG_GEMM_REFUSE_FORM;  // fp32 out and the fp8 head split are the ping-pong kernel's alone
+        if (f32 ? (!pp || heads || p.pieces > 1) : (f8 && heads && !pp)) return false;
+        p.epilogue = f32 ? GM_EPI_TOK32 : heads ? GM_EPI_HEADS : GM_EPI_TOK;
+        if (pp && !f8 && !heads && !f32 && p.pieces == 1) {
+            if (a.variant == 2 || (a.variant < 0 && narrow_on && gm_use_narrow(b, cus))) {
+                p.kernel = FG_GEMM_PP_NARROW, p.tile_n = 128;
+            } else if ((p.ksplit = gm_pick_ksplit(b, cus)) > 1) {
+                p.kernel = FG_GEMM_PP_SPLITK, p.epilogue = GM_EPI_RAW;
+            }
+        }
+        if (!pp) p.kernel = FG_GEMM_REG, p.tile_n = (a.N % 256) != 0 && (a.N % 192) == 0 ? 192 : 256;
+        return true;
+    };
+    // (a call is refused as a whole: its last piece is the only one with another row count)
+    int why = 0;
+    if (!form(a.M - (p.pieces - 1) * rows_max, &why) || !form(p.rows, &why)) return refuse(why);
+
+    // XCD grid xm x xn: the widest split of the output tiles that divides them and still leaves every XCD >= 4 token tiles; an
+    // explicit a.xn (tuning) is taken when it divides
+    const int Mt = (p.rows + GM_TM - 1) / GM_TM, Nt = (a.N + p.tile_n - 1) / p.tile_n;
+    const long long items = (long long)Mt * Nt * p.ksplit;
+    p.grid = cus, p.xn = a.xn > 0 ? a.xn : 0;
+    if (items < p.grid) p.grid = (int)items, p.xn = 0;
+    if (p.grid & 7) p.xn = 0;
+    if (p.xn > 0) {
+        p.xn = 1;
+        for (int c = 8; c > 1; c >>= 1)
+            if (Nt % c == 0 && Mt / (8 / c) >= 4) {
+                p.xn = c;
+                break;
+            }
+        if (a.xn <= 8 && (a.xn & (a.xn - 1)) == 0 && Nt % a.xn == 0 && a.xn != 1) p.xn = a.xn;
+    }
+    p.lds_bytes = gm_lds_bytes(p.kernel, p.tile_n);
+    return p;
+}
+
+int gemm_prepare(int flavours) {
+    const int dev = fg_device_slot();
+    if (dev < 0) return (int)hipErrorInvalidDevice;
+    if (!gm_cus(dev)) return (int)hipErrorUnknown;
+    for (GmKernel& k : g_gm_kernels)
+        if (flavours & (k.f8 ? 4 : 3))
+            if (const int rc = gm_set_attr(k, dev)) return rc;
+    return 0;
+}
+
+namespace {
+
+// every piece of the plan: its rows of A / a_scale / out / resid, and the fields the flavour sets for its kernels
+int gm_run(int flavour, const GemmArgs& a, int out_mode, hipStream_t s) {
+    const int dev = fg_device_slot();
+    if (dev < 0) return (int)hipErrorInvalidDevice;
+    const int cus = gm_cus(dev);
+    if (!cus) return (int)hipErrorUnknown;
+    const bool x3 = flavour == 1, f8 = flavour == 2;
+    const size_t a_row = x3 ? (size_t)4 * a.K : f8 ? (size_t)a.K : (size_t)2 * a.K, o_row = x3 ? (size_t)4 * a.N : (size_t)2 * a.N;
+    for (int i = 0, n = 1; i < n; ++i) {
+        const GemmPlan p = gemm_plan(flavour, a, out_mode, cus, i);
+        if (p.refusal) return (int)hipErrorInvalidValue;
+        n = p.pieces;
+        GemmArgs b = a;
+        b.row0 = a.row0 + p.row0, b.M = p.rows;
+        b.A = static_cast<const char*>(a.A) + p.row0 * a_row;
+        if (a.out) b.out = static_cast<char*>(a.out) + p.row0 * o_row;
+        if (a.resid) b.resid = static_cast<const char*>(a.resid) + p.row0 * o_row;
+        if (x3) b.lda = 2 * a.K, b.ldw = 3 * a.K, b.a_wrap = a.K / GM_KC, b.K = 3 * a.K;
+        if (f8) b.a_scale = a.a_scale + p.row0, b.lda = b.ldw = b.a_wrap = 0, b.out_f32 = 0;
+        if (x3 || f8) b.scratch = nullptr;
+        if (const int rc = gm_launch(b, p, f8, dev, s)) return rc;
     }
     return 0;
+}
+
+}  // namespace
+
+// xn: 0 = linear tile order, 1 = choose the XCD grid, 2 / 4 / 8 = force that many output-tile columns of XCDs
+int launch_gemm_bf16(const GemmArgs& a, hipStream_t s) { return gm_run(0, a, 0, s); }
+
+// ---- split-bf16 ("bf16x3", the fp32-grade mode of common.h) on the same kernel -----------------------------------------------
+// sum_k a_k w_k with a = a_hi + a_lo, w = w_hi + w_lo evaluated as a_hi w_hi + a_hi w_lo + a_lo w_hi is ONE bf16 contraction of
+// length 3 K: A' = [a_hi | a_hi | a_lo], W' = [w_hi | w_lo | w_hi].  A is stored as [hi | lo] planes ([M][2 K] bf16, the same bytes
+// as the fp32 tensor; its hi plane is read twice: a_wrap) by the producing kernel (LayerNorm-modulate, the SPLIT epilogue of the
+// previous GEMM, split_planes_kernel), W' once per weight version; fp32 accumulation over all 3 K products, fp32 epilogue.
+// a: M, N, K = the real contraction length; A = planes, W = W'; out: fp32 [M][N] (out_mode 0, + fp32 resid / gate), [hi | lo]
+// planes [M][2 N] (out_mode 1), or head-split hi / lo planes (heads > 0, lo_off).
+int launch_gemm_x3(const GemmArgs& a, int out_mode, hipStream_t s) { return gm_run(1, a, out_mode, s); }
+int launch_gemm_fp8(const GemmArgs& a, hipStream_t s) { return gm_run(2, a, 0, s); }
+
+int launch_cvt_bf16(const float* in, void* out, size_t n, hipStream_t s) {
+    const size_t blocks = (n + 255) / 256;
+    hipLaunchKernelGGL(cvt_bf16_kernel, dim3((unsigned)(blocks > 8192 ? 8192 : blocks)), dim3(256), 0, s, in, (__bf16*)out, n);
+    return (int)hipGetLastError();
+}
+int launch_split3_weights(const float* w, void* out, int N, int K, hipStream_t s) {
+    const int64_t n = (int64_t)N * K;
+    hipLaunchKernelGGL(split3_weights_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, w, (__bf16*)out, N, K);
+    return (int)hipGetLastError();
+}
+int launch_split_planes(const float* x, void* out, int64_t M, int K, hipStream_t s) {
+    const int64_t n = M * (K / 4);
+    hipLaunchKernelGGL(split_planes_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, x, (__bf16*)out, M, K);
+    return (int)hipGetLastError();
 }
 
 // dtype: 0 fp32 / 1 bf16 rows in; q [M][K] e4m3fn bytes, scale [M] fp32

@@ -182,14 +182,27 @@ struct GemmArgs {
     int variant = -1;  // -1: default (env FASTGEN_AMD_GEMM_PP, 1 unless set to 0; launch_gemm_fp8 too); 0 register-staged kernel; 1 LDS-DMA ping-pong kernel; 2 its narrow-tile form
     int xn = 1;    // 0: linear tile order; 1: XCD-aware order, split chosen by the launcher; 2 / 4 / 8: that many XCD columns over N
 };
+// What the launchers below decide, as a plain host function (no HIP call, no launch): for row piece `piece` of the call (M is cut so that
+// byte offsets into A / out / resid stay below 2 GiB: `pieces` launches of `rows` rows from row `row0`) the kernel form (FG_GEMM_* of
+// include/fastgen_amd.h), its tile width, epilogue (FG_GEMM_EPI_*), split-K factor, XCD columns as the kernel sees them, grid and
+// dynamic LDS - or why the whole call is refused (FG_GEMM_REFUSE_*, 0: it is not).  flavour: 0 bf16, 1 split-bf16 (a.K = the real
+// contraction length; out_mode as launch_gemm_x3), 2 fp8; cus: the device's CU count.  FASTGEN_AMD_GEMM_PP / _NARROW are read once
+// per process.
+struct GemmPlan {
+    int refusal, kernel, tile_n, epilogue, ksplit, xn, grid, lds_bytes, row0, rows, pieces;
+};
+GemmPlan gemm_plan(int flavour, const GemmArgs& a, int out_mode, int cus, int piece);
+// hipFuncSetAttribute(dynamic LDS) of every instantiation the flavours (bit f = flavour f) can launch, once per device: before a
+// stream capture, where the launchers must not do it
+int gemm_prepare(int flavours);
 bool gemm_bf16_supported(const GemmArgs& a);
-int launch_gemm_bf16(const GemmArgs& a, hipStream_t s, bool prepare_only = false);
+int launch_gemm_bf16(const GemmArgs& a, hipStream_t s);
 int launch_cvt_bf16(const float* in, void* out, size_t n, hipStream_t s);
 // the same kernels on e4m3fn operands (W8A8): A [M][K], W [N][K] bytes + a_scale / w_scale (launch_quant_rows_fp8: scale = amax / 448 per
 // row); out = epilogue(a_scale[m] w_scale[n] sum_k qa qw + bias[n]), bf16 out / resid, token and head-split epilogues as above.
 // K % 128 == 0, N % 16 == 0; variant 0: always the register-staged kernel.
 bool gemm_fp8_supported(const GemmArgs& a);
-int launch_gemm_fp8(const GemmArgs& a, hipStream_t s, bool prepare_only = false);
+int launch_gemm_fp8(const GemmArgs& a, hipStream_t s);
 int launch_quant_rows_fp8(int dtype, const void* x, void* q, float* scale, int64_t M, int K, hipStream_t s);
 // the same kernel in the split-bf16 (fp32-grade) mode: see gemm.hip.  A = [hi | lo] planes [M][2 K] bf16, W = launch_split3_weights
 // of the fp32 weight ([N][3 K]), fp32 epilogue; out_mode 0: fp32 [M][N] (+ fp32 resid), 1: [hi | lo] planes [M][2 N]; heads > 0: head-split

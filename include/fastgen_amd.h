@@ -667,11 +667,49 @@ FG_API int fg_op_attention_ex(const void* q, int ldq, int64_t q_bs, const void* 
  * act(sum_k a[m][k] w[n][k] + bias[n]) with a [m][k], w [n][k], resid / out [m][n] in bf16, fp32 accumulation, bias / gate fp32;
  * act 0 none, 1 GELU(tanh) (anything else: FG_EINVAL); bias, gate, resid nullable.  k % 64 == 0, n % 16 == 0.  tile_order: 0 linear, 1 XCD-aware (launcher's
  * choice), 2 / 4 / 8 XCD columns over n; + 16 forces the register-staged kernel, + 32 the LDS-DMA ping-pong kernel (default: the
- * latter where m, n >= 256), + 256 its narrow-tile form (256 x 128: what short token counts - one sample of the video DiT - take), + 512 the experimental
- * one-wave-per-SIMD kernel (token epilogue, m, n >= 256; no engine uses it), + 64 lets grids of fewer tiles than
- * half the CUs split K (fp32 partial sums + a finishing pass).  Exposed for the parity tests and scripts/gemm_bench.py. */
+ * latter where m, n >= 256), + 256 its narrow-tile form (256 x 128: what short token counts - one sample of the video DiT - take),
+ * + 64 lets grids of fewer tiles than half the CUs split K (fp32 partial sums + a finishing pass); bits 16, 32 and 256 exclude each
+ * other.  What a call launches: fg_op_gemm_plan.  Exposed for the parity tests and scripts/gemm_bench.py. */
 FG_API int fg_op_gemm_bf16(const void* a, const void* w, const float* bias, void* out, int m, int n, int k, int act, const float* gate,
                            int gate_stride, int gate_rows, const void* resid, int tile_order, void* stream);
+/* The kernel forms and epilogues of the token GEMM (gemm.hip): what fg_gemm_plan names. */
+#define FG_GEMM_REG 1       /* gemm_bf16_kernel: register-staged, tiles of 256 tokens x 256 | 192 outputs */
+#define FG_GEMM_PP 2        /* gemm_bf16_pp_kernel: LDS-DMA, two ping-pong wave groups, 256 x 256 (m, n >= 256) */
+#define FG_GEMM_PP_NARROW 3 /* gemm_bf16_pp2_kernel: its 256 x 128 form (short grids; tile_order + 256) */
+#define FG_GEMM_PP_SPLITK 4 /* gemm_bf16_pp_kernel over ksplit pieces of k (fp32 partial sums in scratch) + gemm_splitk_finish_kernel */
+#define FG_GEMM_EPI_TOK 0     /* bf16 out [m][n]: bias, act, gate x value + resid */
+#define FG_GEMM_EPI_HEADS 1   /* bf16 q | k | v^T split by head (the qkv linear) */
+#define FG_GEMM_EPI_RAW 2     /* fp32 partial sums (FG_GEMM_PP_SPLITK; the finishing pass applies FG_GEMM_EPI_TOK) */
+#define FG_GEMM_EPI_TOK32 3   /* fp32 out [m][n] */
+#define FG_GEMM_EPI_SPLIT 4   /* [hi | lo] bf16 planes [m][2 n] of the fp32 value (split-bf16, out_mode 1) */
+#define FG_GEMM_EPI_HEADS32 5 /* head-split hi / lo planes (split-bf16 qkv) */
+/* FG_GEMM_REFUSE_ARG, a bad argument: a count <= 0, k % 64 (fp8: 128), n % 16, heads that do not divide n, a tile_order / out_mode the
+ * flavour does not take, split-bf16 below m = 256 or n = 256, piece >= pieces */
+#define FG_GEMM_REFUSE_ARG 1
+#define FG_GEMM_REFUSE_OFFSET 2 /* w, or one 256-row tile of a / out, does not fit the kernels' 32-bit buffer offsets (2 GiB) */
+#define FG_GEMM_REFUSE_FORM 3   /* fp32 out, or the fp8 head split, where the ping-pong kernel cannot run (it alone has those epilogues) */
+#define FG_GEMM_REFUSE_PIECE 4  /* split-bf16: the row cutting leaves a last launch of fewer than 256 rows */
+typedef struct fg_gemm_plan {
+    int refusal;   /* 0 or FG_GEMM_REFUSE_*: the whole call is refused, the other members are zero */
+    int kernel;    /* FG_GEMM_* */
+    int tile_n;    /* outputs per tile: 256, 192 or 128 (tokens per tile: always 256) */
+    int epilogue;  /* FG_GEMM_EPI_* */
+    int ksplit;    /* pieces of k per tile (1 unless FG_GEMM_PP_SPLITK) */
+    int xn;        /* tile order as the kernel sees it: 0 linear, else the 8 XCDs form (8 / xn) x xn over (token, output) tiles */
+    int grid;      /* workgroups, at most cus; each walks the work items (tile, k piece) first, first + stride, ... */
+    int lds_bytes; /* dynamic LDS per workgroup */
+    int row0, rows; /* this piece: rows [row0, row0 + rows) of the call */
+    int pieces;    /* launches the call is cut into so that byte offsets into a / out / resid stay below 2 GiB */
+} fg_gemm_plan;
+/* What the token GEMM would launch for row piece `piece` of a call: the launcher's decisions and nothing else (no launch, no GPU
+ * needed).  flavour 0: fg_op_gemm_bf16 (out_mode 1: fp32 out, an option of the engines), 1: fg_op_gemm_x3 (k its real k; out_mode as
+ * there; tile_order 0 .. 15), 2: fg_op_gemm_fp8 (out_mode 0).  heads > 0: the head-split epilogue of the qkv linear (n = 3 heads
+ * head_dim); gate_rows 0: no gate; scratch_bytes: split-K scratch the caller has (tile_order + 64 counts as the 16 m n bytes
+ * fg_op_gemm_bf16 allocates); tile_order as the flavour's entry point takes it; cus: compute units of the device.  The switches
+ * FASTGEN_AMD_GEMM_PP / FASTGEN_AMD_GEMM_NARROW, read once per process, are part of the plan.  Returns FG_OK with *plan filled,
+ * refusals included. */
+FG_API int fg_op_gemm_plan(int flavour, int m, int n, int k, int heads, int gate_rows, size_t scratch_bytes, int tile_order, int out_mode,
+                           int cus, int piece, fg_gemm_plan* plan);
 /* Row quantiser of the fp8 compute mode (gemm.hip): x [m][k] fp32 (dtype 0) or bf16 (dtype 1) -> q [m][k] OCP e4m3fn bytes and
  * scale [m] fp32.  Per row: amax = max |x|; amax == 0: scale = 1 and q = 0; else scale = amax / 448.0f, q = e4m3fn_RNE(clamp(x *
  * (448.0f / amax), -448, 448)) (IEEE fp32 divisions and product).  k % 128 == 0; anything else: FG_EINVAL before any launch. */
