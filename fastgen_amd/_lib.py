@@ -236,6 +236,7 @@ SIGNATURES = {
     "fg_op_attention_plan": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, POINTER(fg_attention_plan)]),
     "fg_op_attention_ex": (c_int, [c_void_p, c_int, c_int64, c_void_p, c_void_p, c_int, c_int64, c_void_p, c_int, c_int64, c_int, c_int, c_int,
                                    c_int, c_int, c_int, c_int, c_int, c_void_p]),
+    "fg_op_dit_attention": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_size_t, c_int, c_void_p]),
     "fg_op_gemm_plan": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_size_t, c_int, c_int, c_int, c_int, POINTER(fg_gemm_plan)]),
     "fg_op_gemm_bf16": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_int, c_void_p,
                                 c_int, c_void_p]),

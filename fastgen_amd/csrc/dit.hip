@@ -3,6 +3,7 @@
 // workgroup, bias / GELU(tanh) / adaLN gate / residual epilogues, head-split q | k | v^T outputs).  Here:
 //   ln_modulate_kernel     LayerNorm(eps 1e-6, no affine) + apply_adaptive_modulation (:29-41, 187-189, 195-196)
 //   dit_attention_kernel   multi-head self-attention, 256 tokens, head_dim 64 / 72 (timm Attention as DiTBlock uses it, :168, 191)
+//   dit_flash_kernel       the same for any multiple of 256 tokens (1024: the 512 x 512 models), online softmax over 128-key blocks
 //   patch_embed_kernel     PatchEmbed conv(kernel = stride = patch) + bias + pos_embed (:270, 511)
 //   fourier_kernel, cond_kernel   FourierTimeEmbedding features (:67-96), c = t_emb + y_emb + r_emb and silu(c) (:514-533)
 //   final_kernel           OutputProjection (adaLN + Linear to patch pixels, :218-225) + unpatchify (:437-455)
@@ -535,6 +536,125 @@ __global__ __launch_bounds__(256, 2) void dit_attention_kernel(const typename DT
         }
 }
 
+// The same attention for any token count that is a multiple of 256 (1024 tokens: DiT at 512 x 512), as an online softmax over key
+// blocks of 128: q fragments stay in registers, a block's 128 logits per query are 64 registers (the whole-sequence kernel holds
+// all 256 keys' 128), and a running maximum m and row sum l per query live on the query's lane.  O is accumulated transposed,
+// O^T = V^T P^T (the operands of mma16 swapped against dit_attention_kernel), so its query is on the lane as well: the rescale at
+// a change of maximum is one multiplication per register by the lane's own factor, with no exchange between lanes.  Every block
+// is consumed (P V issued) before the next block's maximum is known, so at a change of maximum exactly O and l are at the old
+// maximum, and both are scaled by alpha = exp2(c (m_old - m_new)) - unconditionally: alpha is exactly 1 where the maximum stays,
+// and there is no deferred-rescale threshold.  P is never normalised; O is divided by l once at the end.
+template <typename T, int HD>
+__global__ __launch_bounds__(256, 2) void dit_flash_kernel(const typename DT<T>::WT* __restrict__ q, const typename DT<T>::WT* __restrict__ k,
+                                                        const typename DT<T>::WT* __restrict__ vt, typename DT<T>::ST* __restrict__ out,
+                                                        int BH, int heads, int Tn, size_t lo_off) {
+    typedef typename DT<T>::WT QT;
+    typedef typename DT<T>::ST ST;
+    constexpr bool X3 = std::is_same<T, bf16x3>::value;
+    constexpr int KB = 128, NT = KB / 32;  // keys per block, 32-key tiles of a block
+    constexpr int KS = (HD + 15) / 16;
+    constexpr int DT_ = (HD + 31) / 32;
+    const int lane = threadIdx.x & 63;
+    const int r = lane & 31, h = lane >> 5;
+    const int slabs = Tn / 32;  // a multiple of 8: the four waves of a workgroup share their (image, head)
+    const int gw = blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int bh = gw / slabs, q0 = (gw % slabs) * 32;
+    if (bh >= BH) return;  // wave-uniform
+    const int n = bh / heads, hh = bh - n * heads;
+
+    const QT* qrow = q + ((size_t)bh * Tn + q0 + r) * HD + 8 * h;
+    // Lane r reads key row rk = r with bits 2 and 3 exchanged.  Accumulator row (i & 3) + 8 (i >> 2) + 4 h then holds key
+    // 8 h + (i & 7) + 16 (i >> 3) of the tile: the 8 logits a lane hands to one 16-deep step of P V are 8 CONSECUTIVE keys, and
+    // the matching V^T fragment is one 16-byte load (dit_attention_kernel: two 8-byte loads, keys 4 h .. and 8 + 4 h ..).
+    const int rk = (r & ~12) | ((r & 4) << 1) | ((r & 8) >> 1);
+    const QT* kbase = k + ((size_t)bh * Tn + rk) * HD + 8 * h;
+    const QT* vbase = vt + ((size_t)bh * HD + r) * Tn + 8 * h;
+    Frag8<T> qf[KS];
+#pragma unroll
+    for (int kk = 0; kk < KS; ++kk) {
+        const bool valid = kk * 16 + 8 * h < HD;
+        if constexpr (X3) qf[kk] = dload_planes(qrow + kk * 16, lo_off, valid);
+        else qf[kk] = dload<T>(qrow + kk * 16, valid);
+    }
+    const float c2 = 1.44269504088896341f / sqrtf((float)HD);  // logits to bits
+    float m = -INFINITY, l = 0.f;
+    f32x16 o[DT_];  // o[d][i]: dim d * 32 + acc_row(i, h) of query r
+#pragma unroll
+    for (int d = 0; d < DT_; ++d)
+#pragma unroll
+        for (int i = 0; i < 16; ++i) o[d][i] = 0.f;
+
+    for (int kb = 0; kb < Tn; kb += KB) {
+        f32x16 st[NT];
+#pragma unroll
+        for (int kt = 0; kt < NT; ++kt)
+#pragma unroll
+            for (int i = 0; i < 16; ++i) st[kt][i] = 0.f;
+#pragma unroll
+        for (int kk = 0; kk < KS; ++kk) {
+            const bool valid = kk * 16 + 8 * h < HD;
+#pragma unroll
+            for (int kt = 0; kt < NT; ++kt) {
+                Frag8<T> kf;
+                if constexpr (X3) kf = dload_planes(kbase + (size_t)(kb + kt * 32) * HD + kk * 16, lo_off, valid);
+                else kf = dload<T>(kbase + (size_t)(kb + kt * 32) * HD + kk * 16, valid);
+                mma16(st[kt], kf, qf[kk]);
+            }
+        }
+        float mb = st[0][0];
+#pragma unroll
+        for (int kt = 0; kt < NT; ++kt)
+#pragma unroll
+            for (int i = 0; i < 16; ++i) mb = fmaxf(mb, st[kt][i]);
+        mb = fmaxf(mb, __shfl_xor(mb, 32));
+        const float mn = fmaxf(m, mb);
+        const float alpha = __builtin_amdgcn_exp2f((m - mn) * c2);  // first block: exp2(-inf) = 0 on O = 0, l = 0
+        m = mn;
+        float sum = 0.f;
+#pragma unroll
+        for (int kt = 0; kt < NT; ++kt)
+#pragma unroll
+            for (int i = 0; i < 16; ++i) {
+                const float e = __builtin_amdgcn_exp2f((st[kt][i] - mn) * c2);
+                st[kt][i] = e;
+                sum += e;
+            }
+        sum += __shfl_xor(sum, 32);
+        l = fmaf(l, alpha, sum);
+#pragma unroll
+        for (int d = 0; d < DT_; ++d)
+#pragma unroll
+            for (int i = 0; i < 16; ++i) o[d][i] *= alpha;
+#pragma unroll
+        for (int kt = 0; kt < NT; ++kt)
+#pragma unroll
+            for (int s = 0; s < 2; ++s) {
+                const Frag8<T> pf = DPFrag<T>::make(st[kt], s);
+#pragma unroll
+                for (int d = 0; d < DT_; ++d) {
+                    Frag8<T> vf;
+                    if constexpr (X3) vf = dload_planes(vbase + (size_t)(d * 32) * Tn + kb + kt * 32 + 16 * s, lo_off, true);
+                    else vf = dload<T>(vbase + (size_t)(d * 32) * Tn + kb + kt * 32 + 16 * s, true);
+                    mma16(o[d], vf, pf);
+                }
+            }
+    }
+    const float inv = __builtin_amdgcn_rcpf(l);
+    ST* orow = out + ((size_t)n * Tn + q0 + r) * (heads * HD) + hh * HD + 4 * h;
+#pragma unroll
+    for (int d = 0; d < DT_; ++d)
+#pragma unroll
+        for (int g = 0; g < 4; ++g)
+            if (d * 32 + 8 * g < HD) {  // HD % 8 == 0: a group of 4 dims (and its twin in the other lane half) is inside or outside as a whole
+                const f32x4 v = f32x4{o[d][4 * g] * inv, o[d][4 * g + 1] * inv, o[d][4 * g + 2] * inv, o[d][4 * g + 3] * inv};
+                if constexpr (std::is_same<ST, float>::value) {
+                    *reinterpret_cast<f32x4*>(orow + d * 32 + 8 * g) = v;
+                } else {
+                    *reinterpret_cast<bf16x4*>(orow + d * 32 + 8 * g) = bf16x4{(__bf16)v[0], (__bf16)v[1], (__bf16)v[2], (__bf16)v[3]};
+                }
+            }
+}
+
 #define DIT_RET() return (int)hipGetLastError()
 
 template <typename ST>
@@ -636,24 +756,39 @@ int launch_dit_cond(const float* t_emb, const float* r_emb, const float* table, 
     hipLaunchKernelGGL(cond_kernel, dim3((B * D + 255) / 256), dim3(256), 0, s, t_emb, r_emb, table, cls, c, sc, B, D, rows, err);
     DIT_RET();
 }
-// mode: FG_DTYPE_* (0 exact fp32, 1 bf16, 2 split-bf16 on fp32 tensors).  256 tokens; head_dim 64 or 72.
-int launch_dit_attention(int mode, const void* q, const void* k, const void* vt, void* out, int B, int heads, int head_dim, size_t lo_off,
-                         hipStream_t s) {
+// mode: FG_DTYPE_* (0 exact fp32, 1 bf16, 2 split-bf16 on fp32 tensors); head_dim 64 or 72.  path 0: T == 256 the whole-sequence
+// kernel, any other multiple of 256 the flash form (bf16 and split-bf16 only); 1 / 2: that kernel or nothing.
+int launch_dit_attention(int mode, const void* q, const void* k, const void* vt, void* out, int B, int heads, int head_dim, int T, size_t lo_off,
+                         hipStream_t s, int path) {
     const int BH = B * heads;
-    dim3 g((BH * 8 + 3) / 4), b(256);
+    if (T <= 0 || (T % 256) || (head_dim != 64 && head_dim != 72) || mode < 0 || mode > 2 || path < 0 || path > 2 || BH <= 0 ||
+        (int64_t)BH * (T / 32) > INT32_MAX)
+        return (int)hipErrorInvalidValue;
+    const bool flash = path == 2 || (path == 0 && T != 256);
+    if ((!flash && T != 256) || (flash && mode == 0)) return (int)hipErrorInvalidValue;
+    dim3 g((unsigned)(((int64_t)BH * (T / 32) + 3) / 4)), b(256);
 #define DIT_ATT(TT, HD) hipLaunchKernelGGL((dit_attention_kernel<TT, HD>), g, b, 0, s, (const typename DT<TT>::WT*)q, (const typename DT<TT>::WT*)k, \
                                            (const typename DT<TT>::WT*)vt, (typename DT<TT>::ST*)out, BH, heads, lo_off)
-    if (head_dim == 72) {
+#define DIT_FLASH(TT, HD) hipLaunchKernelGGL((dit_flash_kernel<TT, HD>), g, b, 0, s, (const typename DT<TT>::WT*)q, (const typename DT<TT>::WT*)k, \
+                                             (const typename DT<TT>::WT*)vt, (typename DT<TT>::ST*)out, BH, heads, T, lo_off)
+    if (flash) {
+        if (head_dim == 72) {
+            if (mode == 2) DIT_FLASH(bf16x3, 72);
+            else DIT_FLASH(__bf16, 72);
+        } else {
+            if (mode == 2) DIT_FLASH(bf16x3, 64);
+            else DIT_FLASH(__bf16, 64);
+        }
+    } else if (head_dim == 72) {
         if (mode == 2) DIT_ATT(bf16x3, 72);
         else if (mode == 1) DIT_ATT(__bf16, 72);
         else DIT_ATT(float, 72);
-    } else if (head_dim == 64) {
+    } else {
         if (mode == 2) DIT_ATT(bf16x3, 64);
         else if (mode == 1) DIT_ATT(__bf16, 64);
         else DIT_ATT(float, 64);
-    } else {
-        return (int)hipErrorInvalidValue;
     }
 #undef DIT_ATT
+#undef DIT_FLASH
     DIT_RET();
 }

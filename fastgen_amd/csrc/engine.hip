@@ -1652,6 +1652,22 @@ int fg_op_attention_split(const void* q, const void* k, const void* v, void* out
 int fg_op_attention(const void* q, const void* k, const void* v, void* out, int batch, int heads, int head_dim, int lq, int lkv, void* stream) {
     return fg_op_attention_split(q, k, v, out, batch, heads, head_dim, lq, lkv, 0, stream);
 }
+int fg_op_dit_attention(int mode, const void* q, const void* k, const void* vt, void* out, int batch, int heads, int head_dim, int tokens,
+                        size_t lo_off, int path, void* stream) {
+    if (!q || !k || !vt || !out || ((((uintptr_t)q) | ((uintptr_t)k) | ((uintptr_t)vt) | ((uintptr_t)out)) & 15) || (lo_off % 8))
+        return fail(FG_EINVAL, "fg_op_dit_attention: q / k / vt / out non-null and 16-byte aligned, lo_off a multiple of 8");
+    if ((mode != FG_DTYPE_BF16 && mode != FG_DTYPE_BF16X3) || batch <= 0 || heads <= 0 || (head_dim != 64 && head_dim != 72) || path < 0 || path > 2)
+        return fail(FG_EINVAL, "fg_op_dit_attention: mode bf16 or bf16x3, batch and heads > 0, head_dim 64 or 72, path 0 .. 2 (got mode %d, batch %d, "
+                    "heads %d, head_dim %d, path %d)", mode, batch, heads, head_dim, path);
+    if (tokens <= 0 || (tokens % 256) || (int64_t)batch * heads * (tokens / 32) > INT32_MAX)
+        return fail(FG_EINVAL, "fg_op_dit_attention: tokens must be a multiple of 256 (and batch * heads * tokens / 32 < 2^31), got %d", tokens);
+    if (path == 1 && tokens != 256)
+        return fail(FG_EINVAL, "fg_op_dit_attention: the whole-sequence kernel (path 1) serves 256 tokens only, got %d", tokens);
+    if (mode == FG_DTYPE_BF16X3 && lo_off < (size_t)batch * heads * tokens * head_dim + 32 * (size_t)tokens)
+        return fail(FG_EINVAL, "fg_op_dit_attention: lo_off %zu is inside the hi plane (batch * heads * tokens * head_dim + 32 * tokens elements)", lo_off);
+    HIP_TRY(launch_dit_attention(mode, q, k, vt, out, batch, heads, head_dim, tokens, lo_off, (hipStream_t)stream, path));
+    return FG_OK;
+}
 // tile_order of the token GEMM entry points (flavour 0 bf16, 1 split-bf16: the tile order alone, 2 fp8) -> GemmArgs.xn / .variant;
 // false: bits the flavour does not take
 static bool gemm_tile_order(int flavour, int tile_order, GemmArgs& g) {

@@ -137,7 +137,7 @@ int dit_block_fp8(fg_dit* h, const fg_dit::Blk& b, const float* mod, int mstride
         g.a_scale = w.ys; g.w_scale = reinterpret_cast<const float*>(reinterpret_cast<const char*>(b.p_qkv) + (size_t)3 * D * D);
         g.heads = c.num_heads; g.head_dim = h->hd; g.T = T; g.q = w.q; g.k = w.k; g.vt = w.vt;
         HIP_TRY(launch_gemm_fp8(g, s));
-        HIP_TRY(launch_dit_attention(h->cmode, w.q, w.k, w.vt, w.att, B, c.num_heads, h->hd, 0, s));
+        HIP_TRY(launch_dit_attention(h->cmode, w.q, w.k, w.vt, w.att, B, c.num_heads, h->hd, T, 0, s));
     }
     HIP_TRY(launch_quant_rows_fp8(1, w.att, w.y8, w.ys, ntok, D, s));
     if ((rc = dit_gemm_fp8(h, w.y8, w.ys, D, b.p_proj, h->P(b.proj_b), D, xn, B, s, 0, mod + 2 * D, mstride, x))) return rc;  // x + gate * attn
@@ -226,7 +226,7 @@ int dit_forward(fg_dit* h, const float* x_t, const float* t, const float* r, con
             HIP_TRY(launch_fa(72, qkv, 3 * D, (int64_t)T * 3 * D, qkv + D, qkv + 2 * D, 3 * D, (int64_t)T * 3 * D, w.att, D, (int64_t)T * D, B,
                               c.num_heads, T, T, s));
         } else {
-            HIP_TRY(launch_dit_attention(h->cmode, w.q, w.k, w.vt, w.att, B, c.num_heads, h->hd, lo_off, s));
+            HIP_TRY(launch_dit_attention(h->cmode, w.q, w.k, w.vt, w.att, B, c.num_heads, h->hd, T, lo_off, s));
         }
         const void* att = w.att;
         if (h->gemm3) {  // the attention output (fp32) as planes, in the buffer the qkv projection has consumed
@@ -259,9 +259,14 @@ int dit_pack(fg_dit* h, const ParamGroup& in_group, hipStream_t s) {
     // bytes per packed weight element: bf16 2; bf16x3 two bf16 planes = 4, or [hi | lo | hi] = 6 for the split-bf16 token GEMM
     const size_t wsz = h->cmode == FG_DTYPE_BF16 ? 2 : (want3 ? 6 : 4);
     const size_t D = h->D, Hd = h->Hd;
+    const char* e1 = getenv("FASTGEN_AMD_DIT_GEMM");
+    const bool want1 = h->cmode == FG_DTYPE_BF16 && (h->fp8 || !(e1 && e1[0] == '0')) && (D % 64) == 0 && (Hd % 64) == 0;  // (fp8: fg_dit_create has refused the switch)
     int rc;
     if (!h->device_ready) {
         // (before anything is allocated: a failure here leaves nothing behind for a second attempt to allocate again)
+        if (h->grid != 16 && !want1 && !want3)  // conv.hip's token modes are a 16 x 16 image by construction
+            return fail(FG_EINVAL, "a %d x %d token grid runs on the token GEMM: FASTGEN_AMD_DIT_GEMM%s=0 excludes it", h->grid, h->grid,
+                        h->cmode == FG_DTYPE_BF16X3 ? "3" : "");
         if (h->fp8 && gemm_prepare(4) != 0) return fail(FG_EHIP, "hipFuncSetAttribute(dynamic LDS) failed");
         for (fg_dit::Blk& b : h->blocks) {
             if ((rc = h->alloc(&b.p_qkv, 3 * D * D * wsz)) || (rc = h->alloc(&b.p_proj, D * D * wsz)) ||
@@ -274,8 +279,7 @@ int dit_pack(fg_dit* h, const ParamGroup& in_group, hipStream_t s) {
         HIP_TRY(hipHostMalloc((void**)&h->err_host, sizeof(int), hipHostMallocMapped));
         *h->err_host = 0;
         HIP_TRY(hipHostGetDevicePointer((void**)&h->err_dev, h->err_host, 0));
-        const char* e = getenv("FASTGEN_AMD_DIT_GEMM");
-        h->gemm = h->cmode == FG_DTYPE_BF16 && (h->fp8 || !(e && e[0] == '0')) && (D % 64) == 0 && (Hd % 64) == 0;  // (fp8: fg_dit_create has refused the switch)
+        h->gemm = want1;
         h->gemm3 = want3;
         if ((h->gemm || h->gemm3) && gemm_prepare(3) != 0) return fail(FG_EHIP, "hipFuncSetAttribute(dynamic LDS) failed");
         if (h->gemm && ((rc = h->alloc(&h->p_modw, h->blocks.size() * 6 * D * D * 2)) || (rc = h->alloc((void**)&h->modb, h->blocks.size() * 6 * D * 4))))
@@ -340,8 +344,11 @@ int fg_dit_create(const fg_dit_config* cfg, fg_dit** out) {
     if (cfg->num_heads <= 0 || D % cfg->num_heads) return fail(FG_EINVAL, "hidden_size must be a multiple of num_heads");
     const int hd = D / cfg->num_heads;
     if (hd != 64 && hd != 72) return fail(FG_EINVAL, "head dim %d unsupported (64, 72)", hd);
-    if (cfg->patch_size <= 0 || cfg->input_size % cfg->patch_size || cfg->input_size / cfg->patch_size != 16)
-        return fail(FG_EINVAL, "input_size / patch_size must be 16 (256 tokens), got %d / %d", cfg->input_size, cfg->patch_size);
+    const int grid = cfg->patch_size > 0 && cfg->input_size % cfg->patch_size == 0 ? cfg->input_size / cfg->patch_size : 0;
+    if (grid != 16 && grid != 32)
+        return fail(FG_EINVAL, "input_size / patch_size must be 16 (256 tokens) or 32 (1024 tokens), got %d / %d", cfg->input_size, cfg->patch_size);
+    if (grid != 16 && cfg->compute_dtype == FG_DTYPE_F32)
+        return fail(FG_EINVAL, "the exact fp32 mode runs its linears as 16 x 16 token images: a %d x %d token grid excludes it", grid, grid);
     if (cfg->mlp_hidden <= 0 || cfg->mlp_hidden % 128 || cfg->depth <= 0 || cfg->in_channels <= 0 || cfg->embedding_rows <= 0 ||
         cfg->in_channels * cfg->patch_size * cfg->patch_size > 64)
         return fail(FG_EINVAL, "bad depth / mlp_hidden / in_channels / embedding_rows");
@@ -350,7 +357,7 @@ int fg_dit_create(const fg_dit_config* cfg, fg_dit** out) {
     h->fp8 = cfg->compute_dtype == FG_DTYPE_FP8;
     h->cmode = h->fp8 ? FG_DTYPE_BF16 : cfg->compute_dtype;  // (everything but the block linears is the bf16 mode's)
     h->dtype = h->cmode == FG_DTYPE_BF16 ? 1 : 0;
-    h->D = D, h->Hd = cfg->mlp_hidden, h->hd = hd, h->grid = 16, h->T = 256;
+    h->D = D, h->Hd = cfg->mlp_hidden, h->hd = hd, h->grid = grid, h->T = grid * grid;
     const int p = cfg->patch_size, C = cfg->in_channels, PO = p * p * C;
     // module order of the reference's DiT (:233-290); `pos_embed` is its persistent buffer
     h->pos = h->add("pos_embed", {1, h->T, D});

@@ -149,9 +149,11 @@ int launch_dit_patch_embed(int dtype, const float* x, const float* w, const floa
 int launch_dit_fourier(const float* t, float* f, int B, int dim, hipStream_t s);
 int launch_dit_cond(const float* t_emb, const float* r_emb, const float* table, const int64_t* cls, float* c, float* sc, int B, int D,
                     int rows, int* err, hipStream_t s);
-// mode 2 (bf16x3): q, k, vt are hi / lo bf16 planes, lo_off elements apart (conv.hip OUT_HEADS writes them so); else lo_off unused
-int launch_dit_attention(int mode, const void* q, const void* k, const void* vt, void* out, int B, int heads, int head_dim, size_t lo_off,
-                         hipStream_t s);
+// mode 2 (bf16x3): q, k, vt are hi / lo bf16 planes, lo_off elements apart (conv.hip OUT_HEADS writes them so); else lo_off unused.
+// T tokens per image, a multiple of 256.  path 0: the whole-sequence kernel at T == 256 and the flash form otherwise; 1: the
+// whole-sequence kernel; 2: the flash form.  A combination without a kernel is hipErrorInvalidValue.
+int launch_dit_attention(int mode, const void* q, const void* k, const void* vt, void* out, int B, int heads, int head_dim, int T, size_t lo_off,
+                         hipStream_t s, int path = 0);
 
 // gemm.hip: token GEMM of the transformer blocks in the bf16 compute mode.  out[tok][n] = epilogue(sum_k A[tok][k] W[n][k] + bias[n]),
 // A [M][K] bf16, W [N][K] bf16 (launch_cvt_bf16 of the fp32 parameter), K % 64 == 0, N % 16 == 0.

@@ -9,7 +9,10 @@ embedding / attention / MLP layers are those of the `timm` classes the reference
 
 Inference / sampling: `forward`, and the three sampling loops as single library calls replayed as hipGraphs (`few_step_sample`:
 `FastGenModel` / `MeanFlowModel._student_sample_loop`; `sample()`: the RF Euler sampler with classifier-free guidance) - `fg_dit_sampler_run`.
-Raises (never falls back): autograd through the network, token counts other than 256, and any device but a HIP GPU.
+Token grids: `input_size // patch_size` of 16 (256 tokens, the 256 x 256 models) and 32 (1024 tokens, DiT-XL/2 and SiT-XL/2 at
+512 x 512: `input_size=64`), the latter on the flash form of the attention kernel in every compute mode but exact "fp32".
+Raises (never falls back): autograd through the network, other token grids, `compute_dtype="fp32"` at 1024 tokens
+(NotImplementedError with the library's message), and any device but a HIP GPU.
 """
 from __future__ import annotations
 
@@ -76,7 +79,11 @@ class DiT(FastGenNetwork):
         self._ws: Dict[int, torch.Tensor] = {}
         # module tree with the reference's key paths; names / shapes come from the library's own plan
         self._names: List[str] = []
-        h = self._make_engine(_lib.FG_DTYPE_F32)
+        # (the naming handle in a mode the token grid accepts: exact fp32 is a 16 x 16 grid only)
+        naming = _lib.FG_DTYPE_F32 if input_size // max(patch_size, 1) == 16 else _lib.FG_DTYPE_BF16X3
+        if self.compute_dtype == "fp32" and naming != _lib.FG_DTYPE_F32:
+            self._make_engine(_lib.FG_DTYPE_F32)  # raises NotImplementedError
+        h = self._make_engine(naming)
         L = _lib.lib()
         name, ndim, shape = ctypes.c_char_p(), ctypes.c_int(), (ctypes.c_int64 * 4)()
         for i in range(L.fg_dit_num_params(h)):
@@ -89,10 +96,11 @@ class DiT(FastGenNetwork):
                     node.add_module(p, _edm._Node())
                 node = node._modules[p]
             if full == "pos_embed":
+                self._tokens = int(shp[1])
                 self.register_buffer("pos_embed", sinusoidal_2d_table(hidden_size, input_size // patch_size), persistent=True)
             else:
                 node.register_parameter(parts[-1], nn.Parameter(self._init_value(full, shp)))
-        self._engines[_lib.FG_DTYPE_F32] = h
+        self._engines[naming] = h
 
     @staticmethod
     def _init_value(name: str, shape) -> torch.Tensor:
@@ -109,7 +117,12 @@ class DiT(FastGenNetwork):
         cfg = _lib.fg_dit_config.from_buffer_copy(self._cfg)
         cfg.compute_dtype = dtype
         h = ctypes.c_void_p()
-        _lib.check(_lib.lib().fg_dit_create(ctypes.byref(cfg), ctypes.byref(h)))
+        try:
+            _lib.check(_lib.lib().fg_dit_create(ctypes.byref(cfg), ctypes.byref(h)))
+        except _lib.FastGenAMDError as e:
+            if dtype == _lib.FG_DTYPE_F32 and self._cfg.patch_size > 0 and self._cfg.input_size // self._cfg.patch_size == 32:
+                raise NotImplementedError(str(e)) from None
+            raise
         return h
 
     def __del__(self):
@@ -235,14 +248,14 @@ class DiT(FastGenNetwork):
         ws = self._ws.get(dt)
         if ws is None or ws.numel() < need or ws.device != dev:
             ws = self._ws[dt] = torch.empty(need, dtype=torch.uint8, device=dev)
-        # block-output taps (:536-543): token tensors [B, 256, D] behind the requested blocks; with return_features_early the call
+        # block-output taps (:536-543): token tensors [B, T, D] behind the requested blocks; with return_features_early the call
         # stops at the last of them (no requested index: after the first block, an empty list - as the reference's loop does)
         depth = self._cfg.depth
         taps = sorted(i for i in set(feature_indices) if 0 <= i < depth)
         if return_features_early and len(taps) == len(feature_indices) and not taps:
             return []
         early = return_features_early and len(taps) == len(feature_indices)  # (an index past the last block: the reference never returns early)
-        feats = [torch.empty(B, 256, self.hidden_size, dtype=torch.float32, device=dev) for _ in taps]
+        feats = [torch.empty(B, self._tokens, self.hidden_size, dtype=torch.float32, device=dev) for _ in taps]
         out = None if early else torch.empty_like(x32)
         _lib.check(L.fg_dit_forward_features(
             h, ctypes.c_void_p(x32.data_ptr()), ctypes.c_void_p(t_e.data_ptr()), ctypes.c_void_p(r_e.data_ptr() if r_e is not None else None),

@@ -395,10 +395,12 @@ FG_API int fg_op_train_elementwise(int op, int dtype, const void* a, const void*
 
 /* ---- DiT: the class-conditional diffusion transformer of fastgen/networks/DiT/network.py -------------------------
  * kwargs of DiT(input_size, patch_size, in_channels, hidden_size, depth, num_heads, mlp_ratio, num_classes, class_dropout_prob,
- * r_timestep, ...) (:233-253; configs/net.py:98-127).  Supported: 256 tokens (input_size / patch_size == 16), hidden_size in
- * {384, 768, 1024, 1152} with head dim 64 or 72 (DiT-S/2, B/2, L/2, XL/2), mlp_hidden % 128 == 0. */
+ * r_timestep, ...) (:233-253; configs/net.py:98-127).  Supported: token grids input_size / patch_size of 16 (256
+ * tokens) and 32 (1024 tokens: the 512 x 512 models; every compute mode but FG_DTYPE_F32, and not with FASTGEN_AMD_DIT_GEMM=0 /
+ * FASTGEN_AMD_DIT_GEMM3=0, which fg_dit_pack_weights / fg_dit_pack_group then refuse), hidden_size in {384, 768, 1024, 1152} with head
+ * dim 64 or 72 (DiT-S/2, B/2, L/2, XL/2), mlp_hidden % 128 == 0. */
 typedef struct fg_dit_config {
-    int input_size;      /* 32 (latent resolution) */
+    int input_size;      /* 32 (latent resolution); 64 for the 512 x 512 models */
     int patch_size;      /* 2 */
     int in_channels;     /* 4 */
     int hidden_size;     /* 1152 */
@@ -654,6 +656,14 @@ typedef struct fg_attention_plan {
  * Returns FG_OK with *plan filled, refusals included. */
 FG_API int fg_op_attention_plan(int head_dim, int batch, int heads, int lq, int lkv, int ldk, int use_scratch, int force_split, int path,
                                 fg_attention_plan* plan);
+/* The DiT engine's attention (dit.hip) on its own operand layouts: q, k [batch][heads][tokens][head_dim], vt [batch][heads][head_dim][tokens]
+ * followed by 32 rows (32 * tokens elements) of readable slack, out [batch][tokens][heads * head_dim].  mode FG_DTYPE_BF16: bf16 tensors;
+ * FG_DTYPE_BF16X3: q / k / vt are a hi and a lo bf16 plane each, lo_off elements apart, out fp32.  head_dim 64 or 72; tokens a multiple
+ * of 256.  path 0: what fg_dit_forward launches (256 tokens: the whole-sequence kernel, bit-identical to path 1; otherwise the flash
+ * form), 1: the whole-sequence kernel (256 tokens only), 2: the flash form (online softmax over blocks of 128 keys).  A path that cannot
+ * serve the shape is FG_EINVAL and launches nothing.  For the per-element parity tests and scripts/attn_bench.py. */
+FG_API int fg_op_dit_attention(int mode, const void* q, const void* k, const void* vt, void* out, int batch, int heads, int head_dim,
+                               int tokens, size_t lo_off, int path, void* stream);
 /* fg_op_attention on the layouts the engines pass: q / k / v / out rows of ldq / ldk / ldk / ldo elements (head h at column
  * h * head_dim), q_bs / kv_bs / o_bs elements between samples - packed q|k|v rows (ldq = ldk = 3 D, v = k + D), interleaved k|v
  * (ldk = 2 D), a KV cache whose kv_bs exceeds lkv * ldk.  ldq % 8 == ldk % 8 == ldo % 4 == 0, 16-byte aligned q / k / v, 8-byte out.

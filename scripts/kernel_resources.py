@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Per-kernel register / spill / LDS table of one HIP source (hipcc -Rpass-analysis=kernel-resource-usage), demangled.
-    python scripts/kernel_resources.py fastgen_amd/csrc/conv.hip [substring filter]"""
+    python scripts/kernel_resources.py fastgen_amd/csrc/conv.hip [substring filter]
+    python scripts/kernel_resources.py fastgen_amd/csrc/dit.hip dit_flash_kernel     (must show 0 spill, 0 scratch in all four rows)"""
 import re
 import subprocess
 import sys
