@@ -174,6 +174,14 @@ SIGNATURES = {
     "fg_dit_forward": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_size_t, c_void_p]),
     "fg_dit_forward_features": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, POINTER(c_int), POINTER(c_void_p),
                                         c_int, c_int, c_void_p, c_size_t, c_void_p]),
+    "fg_dit_jvp_workspace_bytes": (c_size_t, [c_void_p, c_int]),
+    "fg_dit_jvp": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p,
+                           c_size_t, c_void_p]),
+    "fg_op_dit_ln_modulate_jvp": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_int,
+                                          c_void_p]),
+    "fg_op_dit_attention_jvp": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
+                                        c_size_t, c_void_p]),
+    "fg_op_dit_gelu_jvp": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p]),
     "fg_dit_sampler_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int]),
     "fg_dit_sampler_run": (c_int, [c_void_p, POINTER(fg_dit_sampler_config), c_void_p, c_void_p, c_void_p, POINTER(c_double), c_int, c_int, c_int,
                                    c_void_p, c_uint64, c_void_p, c_int, c_void_p, c_size_t, c_int, c_void_p]),

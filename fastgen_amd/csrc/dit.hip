@@ -211,6 +211,7 @@ __global__ __launch_bounds__(256) void final_kernel(const ST* __restrict__ x, co
 }
 
 // x0[n][t][d] = bias[d] + pos[t][d] + sum_{c,py,px} W[d][c][py][px] x[n][c][gy p + py][gx p + px]
+// (bias / pos nullable = 0: the tangent stream of dit_jvp.hip is the bare convolution)
 // One thread = output dim d of FOUR neighbouring tokens (one patch row segment): its weight row (K = C p p floats, 16-byte loads,
 // consecutive threads = consecutive rows: coalesced) is read once for the four; the tokens' inputs are wave-uniform (broadcast) loads.
 template <typename ST, int K>
@@ -230,10 +231,10 @@ __global__ __launch_bounds__(256) void patch_embed_kernel(const float* __restric
             const f32x4 q = *reinterpret_cast<const f32x4*>(w + (size_t)d * K + k);
             wr[k] = q[0], wr[k + 1] = q[1], wr[k + 2] = q[2], wr[k + 3] = q[3];
         }
-        const float bd = bias[d];
+        const float bd = bias ? bias[d] : 0.f;
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-            float a = bd + pos[(size_t)(t0 + j) * D + d];
+            float a = pos ? bd + pos[(size_t)(t0 + j) * D + d] : bd;
             int k = 0;
             for (int c = 0; c < C; ++c)
                 for (int py = 0; py < p; ++py)
@@ -272,10 +273,10 @@ __global__ __launch_bounds__(256) void patch_embed_c4p2_kernel(const float* __re
 #pragma unroll
                 for (int e = 0; e < 8; ++e) xs[c][py][e] = row[e];
             }
-        const float bd = bias[d];
+        const float bd = bias ? bias[d] : 0.f;
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-            float a = bd + pos[(size_t)(t0 + j) * D + d];
+            float a = pos ? bd + pos[(size_t)(t0 + j) * D + d] : bd;
 #pragma unroll
             for (int c = 0; c < 4; ++c)
 #pragma unroll
@@ -298,7 +299,7 @@ __global__ __launch_bounds__(256) void patch_embed_any_kernel(const float* __res
         const int64_t tok = i / D;
         const int t = (int)(tok % tpi), n = (int)(tok / tpi);
         const int gy = t / grid, gx = t - gy * grid;
-        float a = bias[d] + pos[(size_t)t * D + d];
+        float a = (bias ? bias[d] : 0.f) + (pos ? pos[(size_t)t * D + d] : 0.f);
         const float* wr = w + (size_t)d * K;
         for (int c = 0; c < C; ++c)
             for (int py = 0; py < p; ++py)

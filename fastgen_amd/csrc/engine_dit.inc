@@ -252,6 +252,119 @@ int dit_forward(fg_dit* h, const float* x_t, const float* t, const float* r, con
     return FG_OK;
 }
 
+// ---- forward-mode derivative (fg_dit_jvp): split-bf16 mode, 256 tokens -------------------------------------------------------------
+// The primal stream x and the tangent stream xd side by side, both fp32 (kernels: dit_jvp.hip; formulas: DESIGN.md "DiT jvp").  Its own
+// workspace plan: the tangent twins of dit_plan's token buffers, the un-gated output h of proj / fc2 and the fc1 pre-activation.
+struct DitJvpWs {
+    float *zero, *tf, *tfd, *pre, *pred, *th, *thd, *temb, *tembd, *remb, *rembd, *c, *sc, *scd, *mod, *modd, *fmod, *fmodd;
+    float *x0, *x1, *xd0, *xd1, *att, *attd, *hid, *hidd;
+    void *y, *yd, *q, *k, *vt, *qd, *kd, *vtd, *a, *ad;
+};
+
+bool dit_has_jvp(const fg_dit* h) { return h->cmode == FG_DTYPE_BF16X3 && !h->fp8 && h->grid == 16; }
+
+size_t dit_jvp_plan(const fg_dit* h, int B, Arena& A, DitJvpWs& w) {
+    const size_t D = h->D, Hd = h->Hd, ntok = (size_t)B * h->T;
+    w.zero = A.get<float>((size_t)B);
+    w.tf = A.get<float>((size_t)B * 256);
+    w.tfd = A.get<float>((size_t)B * 256);
+    float** rows[] = {&w.pre, &w.pred, &w.th, &w.thd, &w.temb, &w.tembd, &w.remb, &w.rembd, &w.c, &w.sc, &w.scd};
+    for (float** r : rows) *r = A.get<float>((size_t)B * D);
+    w.mod = A.get<float>((size_t)B * 6 * D);
+    w.modd = A.get<float>((size_t)B * 6 * D);
+    w.fmod = A.get<float>((size_t)B * 2 * D);
+    w.fmodd = A.get<float>((size_t)B * 2 * D);
+    float** toks[] = {&w.x0, &w.x1, &w.xd0, &w.xd1, &w.att, &w.attd};
+    for (float** t : toks) *t = A.get<float>(ntok * D);
+    w.y = A.take(ntok * D * 4);   // [hi | lo] planes: the bytes of the fp32 tensor
+    w.yd = A.take(ntok * D * 4);
+    void** heads[] = {&w.q, &w.k, &w.vt, &w.qd, &w.kd, &w.vtd};
+    for (void** p : heads) *p = A.take(2 * (ntok * D + 32 * (size_t)h->T) * 2);  // hi and lo planes, 32 rows of slack behind the last head each
+    w.hid = A.get<float>(ntok * Hd);
+    w.hidd = A.get<float>(ntok * Hd);
+    w.a = A.take(ntok * Hd * 4);
+    w.ad = A.take(ntok * Hd * 4);
+    return (A.off + 255) & ~(size_t)255;
+}
+
+// FourierTimeEmbedding with tangent: emb = W2 silu(W0 f(t) + b0) + b2, embd = W2 (silu'(.) o (W0 fd))
+int dit_jvp_embed(fg_dit* h, const float* t, const float* td, int w0, int b0, int w2, int b2, float* emb, float* embd, int B, DitJvpWs& w,
+                  hipStream_t s) {
+    const int D = h->D;
+    HIP_TRY(launch_dit_fourier_jvp(t, td, w.tf, w.tfd, B, 256, s));
+    HIP_TRY(launch_linear(w.tf, h->P(w0), h->P(b0), w.pre, B, 256, D, 0, s));
+    HIP_TRY(launch_linear(w.tfd, h->P(w0), nullptr, w.pred, B, 256, D, 0, s));
+    HIP_TRY(launch_dit_silu_jvp(w.pre, w.pred, nullptr, w.th, w.thd, B * D, s));
+    HIP_TRY(launch_linear(w.th, h->P(w2), h->P(b2), emb, B, D, D, 0, s));
+    HIP_TRY(launch_linear(w.thd, h->P(w2), nullptr, embd, B, D, D, 0, s));
+    return FG_OK;
+}
+
+int dit_jvp(fg_dit* h, const float* x_t, const float* t, const float* r, const int64_t* cls, const float* vx, const float* vt, const float* vr,
+            float* out, float* jvp, int B, DitJvpWs& w, hipStream_t s) {
+    const fg_dit_config& c = h->cfg;
+    const int D = h->D, Hd = h->Hd, T = h->T, ntok = B * T;
+    const size_t lo_off = (size_t)ntok * D + 32 * (size_t)T;
+    int rc;
+    HIP_TRY(hipMemsetAsync(w.zero, 0, sizeof(float) * (size_t)B, s));
+    // conditioning: c = t_emb + y + r_emb, cd = t_embd + r_embd; the blocks read silu(c) and its tangent silu'(c) o cd
+    if ((rc = dit_jvp_embed(h, t, vt ? vt : w.zero, h->tw0, h->tb0, h->tw2, h->tb2, w.temb, w.tembd, B, w, s))) return rc;
+    const bool has_r = c.r_timestep && r;
+    if (has_r && (rc = dit_jvp_embed(h, r, vr ? vr : w.zero, h->rw0, h->rb0, h->rw2, h->rb2, w.remb, w.rembd, B, w, s))) return rc;
+    HIP_TRY(launch_dit_cond(w.temb, has_r ? w.remb : nullptr, h->P(h->ytab), cls, w.c, w.sc, B, D, c.embedding_rows, h->err_dev, s));
+    HIP_TRY(launch_dit_silu_jvp(w.c, w.tembd, has_r ? w.rembd : nullptr, nullptr, w.scd, B * D, s));
+    // tokens: the patch embedding is linear - the tangent stream is the bare convolution of vx
+    HIP_TRY(launch_dit_patch_embed(0, x_t, h->P(h->xw), h->P(h->xb), h->P(h->pos), w.x0, B, c.in_channels, h->grid, c.patch_size, D, s));
+    HIP_TRY(launch_dit_patch_embed(0, vx, h->P(h->xw), nullptr, nullptr, w.xd0, B, c.in_channels, h->grid, c.patch_size, D, s));
+    float *x = w.x0, *xn = w.x1, *xd = w.xd0, *xdn = w.xd1;
+    const int ms = 6 * D;
+    auto gemm = [&](const void* A, int K, const void* W, const float* bias, int N, void* o, const float* gate, const void* resid) {
+        GemmArgs g;
+        g.A = A; g.W = W; g.bias = bias; g.out = o; g.M = ntok; g.N = N; g.K = K;
+        g.gate = gate; g.gate_stride = ms; g.gate_rows = T; g.resid = resid;
+        return launch_gemm_x3(g, 0, s);
+    };
+    auto qkv = [&](const void* A, const fg_dit::Blk& b, const float* bias, void* q, void* k, void* v) {
+        GemmArgs g;
+        g.A = A; g.W = b.p_qkv; g.bias = bias; g.M = ntok; g.N = 3 * D; g.K = D;
+        g.heads = c.num_heads; g.head_dim = h->hd; g.T = T; g.q = q; g.k = k; g.vt = v; g.lo_off = lo_off;
+        return launch_gemm_x3(g, 0, s);
+    };
+    for (const fg_dit::Blk& b : h->blocks) {
+        // {shift, scale, gate} x {attention, feed-forward} and their tangents: modd = W_mod (silu'(c) o cd), no bias
+        HIP_TRY(launch_linear(w.sc, h->P(b.mod_w), h->P(b.mod_b), w.mod, B, D, 6 * D, 0, s));
+        HIP_TRY(launch_linear(w.scd, h->P(b.mod_w), nullptr, w.modd, B, D, 6 * D, 0, s));
+        // attention branch
+        HIP_TRY(launch_dit_ln_modulate_jvp(D, x, xd, w.mod, w.modd, ms, 0, D, w.y, w.yd, ntok, T, s));
+        HIP_TRY(qkv(w.y, b, h->P(b.qkv_b), w.q, w.k, w.vt));
+        HIP_TRY(qkv(w.yd, b, nullptr, w.qd, w.kd, w.vtd));
+        HIP_TRY(launch_dit_attention_jvp(w.q, w.k, w.vt, w.qd, w.kd, w.vtd, w.att, w.attd, B, c.num_heads, h->hd, T, lo_off, s));
+        HIP_TRY(launch_split_planes(w.att, w.y, (int64_t)ntok, D, s));
+        HIP_TRY(launch_split_planes(w.attd, w.yd, (int64_t)ntok, D, s));
+        // x' = x + g o h, xd' = xd + g o (W od) + gd o h with h = W o + b: h un-gated (in att's space, consumed above), the middle term
+        // on the GEMM's gate + residual epilogue, the outer ones in one elementwise pass
+        HIP_TRY(gemm(w.y, D, b.p_proj, h->P(b.proj_b), D, w.att, nullptr, nullptr));
+        HIP_TRY(gemm(w.yd, D, b.p_proj, nullptr, D, xdn, w.mod + 2 * D, xd));
+        HIP_TRY(launch_dit_gate_update(w.att, w.mod + 2 * D, w.modd + 2 * D, ms, T, x, xn, xdn, (int64_t)ntok, D, s));
+        std::swap(x, xn);
+        std::swap(xd, xdn);
+        // feed-forward branch: fc1 keeps its pre-activation, GELU and its derivative in one pass of their own
+        HIP_TRY(launch_dit_ln_modulate_jvp(D, x, xd, w.mod, w.modd, ms, 3 * D, 4 * D, w.y, w.yd, ntok, T, s));
+        HIP_TRY(gemm(w.y, D, b.p_fc1, h->P(b.fc1_b), Hd, w.hid, nullptr, nullptr));
+        HIP_TRY(gemm(w.yd, D, b.p_fc1, nullptr, Hd, w.hidd, nullptr, nullptr));
+        HIP_TRY(launch_dit_gelu_jvp(w.hid, w.hidd, w.a, w.ad, (int64_t)ntok, Hd, s));
+        HIP_TRY(gemm(w.a, Hd, b.p_fc2, h->P(b.fc2_b), D, w.att, nullptr, nullptr));
+        HIP_TRY(gemm(w.ad, Hd, b.p_fc2, nullptr, D, xdn, w.mod + 5 * D, xd));
+        HIP_TRY(launch_dit_gate_update(w.att, w.mod + 5 * D, w.modd + 5 * D, ms, T, x, xn, xdn, (int64_t)ntok, D, s));
+        std::swap(x, xn);
+        std::swap(xd, xdn);
+    }
+    HIP_TRY(launch_linear(w.sc, h->P(h->fmw), h->P(h->fmb), w.fmod, B, D, 2 * D, 0, s));
+    HIP_TRY(launch_linear(w.scd, h->P(h->fmw), nullptr, w.fmodd, B, D, 2 * D, 0, s));
+    HIP_TRY(launch_dit_final_jvp(D, x, xd, w.fmod, w.fmodd, h->P(h->fw), h->P(h->fb), out, jvp, ntok, h->grid, c.patch_size, c.in_channels, s));
+    return FG_OK;
+}
+
 // fg_dit_pack_group's part: device storage on the first call, then the GEMM weights of the group's blocks
 int dit_pack(fg_dit* h, const ParamGroup& in_group, hipStream_t s) {
     const char* e3 = getenv("FASTGEN_AMD_DIT_GEMM3");
@@ -465,4 +578,89 @@ int fg_dit_forward_features(fg_dit* h, const float* x_t, const float* t, const f
     const size_t need = dit_plan(h, batch, A, w);
     if (need > workspace_bytes) return fail(FG_ENOMEM, "workspace too small: need %zu bytes for batch %d, got %zu", need, batch, workspace_bytes);
     return dit_forward(h, x_t, t, r, class_ids, out, cond_out, batch, w, (hipStream_t)stream, feature_blocks, features, num_features, out == nullptr);
+}
+
+size_t fg_dit_jvp_workspace_bytes(const fg_dit* h, int batch) {
+    if (!h || batch <= 0 || !dit_has_jvp(h)) return 0;
+    Arena A;
+    A.dry = true;
+    DitJvpWs w;
+    return dit_jvp_plan(h, batch, A, w);
+}
+
+int fg_dit_jvp(fg_dit* h, const float* x_t, const float* t, const float* r, const int64_t* class_ids, const float* vx, const float* vt,
+               const float* vr, float* out, float* jvp, int batch, void* workspace, size_t workspace_bytes, void* stream) {
+    if (!h || !x_t || !t || !class_ids || !vx || !out || !jvp) return fail(FG_EINVAL, "fg_dit_jvp: null argument");
+    if (!dit_has_jvp(h))
+        return fail(FG_EINVAL, "fg_dit_jvp: the jvp runs in the bf16x3 compute mode on a 16 x 16 token grid (this handle: compute_dtype %d, %d x %d)",
+                    h->cfg.compute_dtype, h->grid, h->grid);
+    if (batch <= 0 || (size_t)batch * h->T > (size_t)INT32_MAX) return fail(FG_EINVAL, "fg_dit_jvp: bad batch %d", batch);
+    if (!workspace || (((uintptr_t)workspace) & 255)) return fail(FG_EINVAL, "fg_dit_jvp: the workspace must be non-null and 256-byte aligned");
+    const size_t img = sizeof(float) * (size_t)batch * h->cfg.in_channels * h->cfg.input_size * h->cfg.input_size;
+    auto overlap = [](const void* a, size_t na, const void* b, size_t nb) {
+        const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+        return b && x < y + nb && y < x + na;
+    };
+    const size_t vec = sizeof(float) * (size_t)batch;
+    for (float* o : {out, jvp})
+        if (overlap(o, img, x_t, img) || overlap(o, img, vx, img) || overlap(o, img, t, vec) || overlap(o, img, r, vec) ||
+            overlap(o, img, vt, vec) || overlap(o, img, vr, vec) || overlap(o, img, class_ids, sizeof(int64_t) * (size_t)batch) ||
+            overlap(o, img, workspace, workspace_bytes))
+            return fail(FG_EINVAL, "fg_dit_jvp: out / jvp must not alias an input or the workspace");
+    if (overlap(out, img, jvp, img)) return fail(FG_EINVAL, "fg_dit_jvp: out and jvp must not alias each other");
+    if (!h->packed) return fail(FG_ENOTREADY, "weights are not packed (call fg_dit_pack_weights)");
+    if (!h->gemm3) return fail(FG_EINVAL, "fg_dit_jvp: the jvp runs on the split-bf16 token GEMM: FASTGEN_AMD_DIT_GEMM3=0 excludes it");
+    if (h->take_error())
+        return fail(FG_EINVAL, "an earlier call on this handle met a class index outside the %d rows of y_embedder.class_embeddings (its output is NaN)",
+                    h->cfg.embedding_rows);
+    Arena A;
+    A.base = (char*)workspace;
+    DitJvpWs w;
+    const size_t need = dit_jvp_plan(h, batch, A, w);
+    if (need > workspace_bytes) return fail(FG_ENOMEM, "fg_dit_jvp: workspace too small: need %zu bytes for batch %d, got %zu", need, batch, workspace_bytes);
+    return dit_jvp(h, x_t, t, r, class_ids, vx, vt, vr, out, jvp, batch, w, (hipStream_t)stream);
+}
+
+// The three new kernels of the jvp on their own (per-op parity tests): every argument is checked before anything is launched.
+int fg_op_dit_ln_modulate_jvp(const float* x, const float* xd, const float* mod, const float* modd, int mod_stride, int shift_off, int scale_off,
+                              void* y, void* yd, int ntok, int d, int tokens_per_image, void* stream) {
+    if (!x || !xd || !mod || !modd || !y || !yd) return fail(FG_EINVAL, "fg_op_dit_ln_modulate_jvp: null pointer");
+    if ((((uintptr_t)x) | ((uintptr_t)xd) | ((uintptr_t)mod) | ((uintptr_t)modd) | ((uintptr_t)y) | ((uintptr_t)yd)) & 15)
+        return fail(FG_EINVAL, "fg_op_dit_ln_modulate_jvp: tensors must be 16-byte aligned");
+    if (ntok <= 0 || tokens_per_image <= 0) return fail(FG_EINVAL, "fg_op_dit_ln_modulate_jvp: ntok %d and tokens_per_image %d must be positive", ntok, tokens_per_image);
+    if (d != 384 && d != 768 && d != 1024 && d != 1152) return fail(FG_EINVAL, "fg_op_dit_ln_modulate_jvp: d %d unsupported (384, 768, 1024, 1152)", d);
+    if (shift_off < 0 || scale_off < 0 || (mod_stride % 2) || (shift_off % 2) || (scale_off % 2) || mod_stride < shift_off + d || mod_stride < scale_off + d)
+        return fail(FG_EINVAL, "fg_op_dit_ln_modulate_jvp: mod_stride / shift_off / scale_off must be even, the offsets + d inside the stride");
+    if (y == yd || (const void*)x == y || (const void*)xd == y || (const void*)x == yd || (const void*)xd == yd)
+        return fail(FG_EINVAL, "fg_op_dit_ln_modulate_jvp: y / yd must not alias each other or an input");
+    HIP_TRY(launch_dit_ln_modulate_jvp(d, x, xd, mod, modd, mod_stride, shift_off, scale_off, y, yd, ntok, tokens_per_image, (hipStream_t)stream));
+    return FG_OK;
+}
+
+int fg_op_dit_attention_jvp(const void* q, const void* k, const void* vt, const void* qd, const void* kd, const void* vtd, float* out, float* outd,
+                            int batch, int heads, int head_dim, int tokens, size_t lo_off, void* stream) {
+    if (!q || !k || !vt || !qd || !kd || !vtd || !out || !outd) return fail(FG_EINVAL, "fg_op_dit_attention_jvp: null pointer");
+    if (((((uintptr_t)q) | ((uintptr_t)k) | ((uintptr_t)vt) | ((uintptr_t)qd) | ((uintptr_t)kd) | ((uintptr_t)vtd) | ((uintptr_t)out) | ((uintptr_t)outd)) & 15) ||
+        (lo_off % 8))
+        return fail(FG_EINVAL, "fg_op_dit_attention_jvp: tensors must be 16-byte aligned, lo_off a multiple of 8");
+    if (batch <= 0 || heads <= 0 || (head_dim != 64 && head_dim != 72) || (int64_t)batch * heads * 8 > INT32_MAX)
+        return fail(FG_EINVAL, "fg_op_dit_attention_jvp: batch and heads > 0 (batch * heads * 8 < 2^31), head_dim 64 or 72 (got %d, %d, %d)", batch, heads,
+                    head_dim);
+    if (tokens != 256) return fail(FG_EINVAL, "fg_op_dit_attention_jvp: 256 tokens only, got %d", tokens);
+    if (lo_off < (size_t)batch * heads * tokens * head_dim + 32 * (size_t)tokens)
+        return fail(FG_EINVAL, "fg_op_dit_attention_jvp: lo_off %zu is inside the hi plane (batch * heads * tokens * head_dim + 32 * tokens elements)", lo_off);
+    if (out == outd) return fail(FG_EINVAL, "fg_op_dit_attention_jvp: out and outd must not alias");
+    HIP_TRY(launch_dit_attention_jvp(q, k, vt, qd, kd, vtd, out, outd, batch, heads, head_dim, tokens, lo_off, (hipStream_t)stream));
+    return FG_OK;
+}
+
+int fg_op_dit_gelu_jvp(const float* h, const float* hd, void* a, void* ad, int64_t m, int k, void* stream) {
+    if (!h || !hd || !a || !ad) return fail(FG_EINVAL, "fg_op_dit_gelu_jvp: null pointer");
+    if ((((uintptr_t)h) | ((uintptr_t)hd) | ((uintptr_t)a) | ((uintptr_t)ad)) & 15) return fail(FG_EINVAL, "fg_op_dit_gelu_jvp: tensors must be 16-byte aligned");
+    if (m <= 0 || k <= 0 || (k % 4) || m > INT32_MAX || (m * (k / 4) + 255) / 256 > INT32_MAX)
+        return fail(FG_EINVAL, "fg_op_dit_gelu_jvp: m %lld > 0, k %d > 0 and a multiple of 4, m k / 1024 < 2^31", (long long)m, k);
+    if (a == ad || (const void*)h == a || (const void*)hd == a || (const void*)h == ad || (const void*)hd == ad)
+        return fail(FG_EINVAL, "fg_op_dit_gelu_jvp: a / ad must not alias each other or an input");
+    HIP_TRY(launch_dit_gelu_jvp(h, hd, a, ad, m, k, (hipStream_t)stream));
+    return FG_OK;
 }

@@ -144,6 +144,7 @@ int launch_dit_ln_modulate_fp8(int D, const void* x, const float* mod, int mod_s
                                int ntok, int tokens_per_image, hipStream_t s);
 int launch_dit_final(int dtype, int D, const void* x, const float* mod, const float* w, const float* bias, float* out, int ntok, int grid,
                      int p, int C, hipStream_t s);
+// bias / pos nullable = 0 (the tangent stream of the jvp is the bare convolution)
 int launch_dit_patch_embed(int dtype, const float* x, const float* w, const float* bias, const float* pos, void* out, int B, int C, int grid,
                            int p, int D, hipStream_t s);
 int launch_dit_fourier(const float* t, float* f, int B, int dim, hipStream_t s);
@@ -154,6 +155,24 @@ int launch_dit_cond(const float* t_emb, const float* r_emb, const float* table, 
 // whole-sequence kernel; 2: the flash form.  A combination without a kernel is hipErrorInvalidValue.
 int launch_dit_attention(int mode, const void* q, const void* k, const void* vt, void* out, int B, int heads, int head_dim, int T, size_t lo_off,
                          hipStream_t s, int path = 0);
+// dit_jvp.hip: the non-GEMM pieces of the DiT forward-mode derivative (split-bf16 mode, 256 tokens): a primal and a tangent stream, fp32
+int launch_dit_fourier_jvp(const float* t, const float* td, float* f, float* fd, int B, int dim, hipStream_t s);
+// sout (nullable) = silu(v), sd = silu'(v) (da + db); db nullable
+int launch_dit_silu_jvp(const float* v, const float* da, const float* db, float* sout, float* sd, int n, hipStream_t s);
+// launch_dit_ln_modulate_split with tangent: xd [ntok][D], modd laid out as mod; y, yd [hi | lo] planes [ntok][2 D]; even stride / offsets
+int launch_dit_ln_modulate_jvp(int D, const float* x, const float* xd, const float* mod, const float* modd, int mod_stride, int shift_off,
+                               int scale_off, void* y, void* yd, int ntok, int tokens_per_image, hipStream_t s);
+// launch_dit_attention(mode 2, T == 256) with tangent: qd / kd / vtd in the layouts of q / k / vt (planes lo_off apart, 32 rows of
+// slack), out / outd fp32 [B][T][heads * head_dim]
+int launch_dit_attention_jvp(const void* q, const void* k, const void* vt, const void* qd, const void* kd, const void* vtd, float* out, float* outd,
+                             int B, int heads, int head_dim, int T, size_t lo_off, hipStream_t s);
+// a = gelu_tanh(h), ad = gelu_tanh'(h) hd: h, hd fp32 [M][K]; a, ad [hi | lo] planes [M][2 K]; K % 4 == 0
+int launch_dit_gelu_jvp(const float* h, const float* hd, void* a, void* ad, int64_t M, int K, hipStream_t s);
+// xo = x + g h; xdo += gd h with g, gd = rows [row / gate_rows] of stride gate_stride; all fp32 [M][N], N % 4 == 0
+int launch_dit_gate_update(const float* h, const float* g, const float* gd, int gate_stride, int gate_rows, const float* x, float* xo, float* xdo,
+                           int64_t M, int N, hipStream_t s);
+int launch_dit_final_jvp(int D, const float* x, const float* xd, const float* mod, const float* modd, const float* w, const float* bias, float* out,
+                         float* outd, int ntok, int grid, int p, int C, hipStream_t s);
 
 // gemm.hip: token GEMM of the transformer blocks in the bf16 compute mode.  out[tok][n] = epilogue(sum_k A[tok][k] W[n][k] + bias[n]),
 // A [M][K] bf16, W [N][K] bf16 (launch_cvt_bf16 of the fp32 parameter), K % 64 == 0, N % 16 == 0.

@@ -9,6 +9,8 @@ embedding / attention / MLP layers are those of the `timm` classes the reference
 
 Inference / sampling: `forward`, and the three sampling loops as single library calls replayed as hipGraphs (`few_step_sample`:
 `FastGenModel` / `MeanFlowModel._student_sample_loop`; `sample()`: the RF Euler sampler with classifier-free guidance) - `fg_dit_sampler_run`.
+`jvp`: the forward-mode derivative MeanFlow training needs (`MeanFlowModel.network_jvp`), one `fg_dit_jvp` call - compute mode "bf16x3",
+256 tokens, forward-only (no graph is built).
 Token grids: `input_size // patch_size` of 16 (256 tokens, the 256 x 256 models) and 32 (1024 tokens, DiT-XL/2 and SiT-XL/2 at
 512 x 512: `input_size=64`), the latter on the flash form of the attention kernel in every compute mode but exact "fp32".
 Raises (never falls back): autograd through the network, other token grids, `compute_dtype="fp32"` at 1024 tokens
@@ -274,6 +276,70 @@ class DiT(FastGenNetwork):
         if return_logvar:
             return out, self._logvar(t_e)
         return out
+
+    @torch.no_grad()
+    def jvp(self, x_t: torch.Tensor, t: torch.Tensor, v_x: torch.Tensor, v_t: Optional[torch.Tensor] = None,
+            condition: Optional[torch.Tensor] = None, r: Optional[torch.Tensor] = None, v_r: Optional[torch.Tensor] = None,
+            fwd_pred_type: Optional[str] = None):
+        """(output, directional derivative) of `forward(x_t, t, condition=condition, r=r)` along (v_x, v_t, v_r) - what
+        `torch.func.jvp(net_wrapper, (x_t, t, r), tangents)` returns in MeanFlowModel._jvp (mean_flow.py:240-250), as one library call
+        (`fg_dit_jvp`: compute mode "bf16x3", 256 tokens; anything else raises NotImplementedError).  Forward-only: no graph is built
+        (the reference detaches the result too).  `forward()`'s preparation of (t, r) - scale_t, the SiT flip, the 'diff' difference -
+        is applied here, and its chain rule to (v_t, v_r)."""
+        if fwd_pred_type is not None and fwd_pred_type != self.net_pred_type:
+            raise NotImplementedError("jvp is provided for the network's own prediction type")
+        if r is None and self.r_timestep:
+            raise ValueError("this network was built with r_timestep=True: jvp() needs r")
+        if self.input_size // max(self.patch_size, 1) != 16:
+            raise NotImplementedError("fastgen_amd.DiT.jvp runs on the 16 x 16 token grid (256 tokens) only, got "
+                                      f"{self.input_size // max(self.patch_size, 1)} patches per side")
+        if self._select_dtype() != _lib.FG_DTYPE_BF16X3:
+            raise NotImplementedError("fastgen_amd.DiT.jvp runs in the 'bf16x3' compute mode only (the reference evaluates this JVP in float32)")
+        if x_t.device.type != "cuda":
+            raise RuntimeError("fastgen_amd runs on a HIP GPU only (no CPU path); got a tensor on " + str(x_t.device))
+        B, dev = x_t.shape[0], x_t.device
+        if tuple(x_t.shape[1:]) != (self.in_channels, self.input_size, self.input_size) or v_x.shape != x_t.shape:
+            raise ValueError(f"x_t and v_x must be [B,{self.in_channels},{self.input_size},{self.input_size}], got {tuple(x_t.shape)} "
+                             f"and {tuple(v_x.shape)}")
+        cls = self._class_ids(condition, B, dev)
+        x32 = x_t.detach().to(torch.float32).contiguous()
+        vx = v_x.detach().to(device=dev, dtype=torch.float32).contiguous()
+
+        def rows(a):
+            a = torch.atleast_1d(a.detach()).to(dev)
+            return a.expand(B) if a.numel() == 1 and B > 1 else a
+
+        def tangent(v):  # the derivative of prepare_t, a multiplication by num_steps or 1
+            v = rows(v).to(torch.float32)
+            return self.noise_scheduler._rescale(v) if self.scale_t else v
+
+        use_r = self.r_timestep and r is not None
+        t_e = self.prepare_t(rows(t), torch.float32)
+        vt_e = tangent(v_t) if v_t is not None else torch.zeros(B, dtype=torch.float32, device=dev)
+        r_e = self.prepare_t(rows(r), torch.float32) if use_r else None
+        vr_e = (tangent(v_r) if v_r is not None else torch.zeros(B, dtype=torch.float32, device=dev)) if use_r else None
+        if self.use_sit_convention:
+            t_e, vt_e = 1 - t_e, -vt_e  # :503-504
+        if use_r and self.time_cond_type == "diff":
+            r_e, vr_e = t_e - r_e, vt_e - vr_e  # :520-521
+        p = lambda a: ctypes.c_void_p(a.data_ptr() if a is not None else None)  # noqa: E731
+        t_e, vt_e = t_e.contiguous(), vt_e.contiguous()
+        r_e, vr_e = (r_e.contiguous(), vr_e.contiguous()) if use_r else (None, None)
+        dt, h = self._engine(dev)
+        L = _lib.lib()
+        need = L.fg_dit_jvp_workspace_bytes(h, B)
+        if need == 0:
+            raise NotImplementedError("fastgen_amd.DiT.jvp: this compute mode / token grid has no jvp (bf16x3, 256 tokens)")
+        ws = self._ws.get(dt)
+        if ws is None or ws.numel() < need or ws.device != dev:
+            ws = self._ws[dt] = torch.empty(need, dtype=torch.uint8, device=dev)
+        out, jv = torch.empty_like(x32), torch.empty_like(x32)
+        _lib.check(L.fg_dit_jvp(h, p(x32), p(t_e), p(r_e), p(cls), p(vx), p(vt_e), p(vr_e), p(out), p(jv), B, ctypes.c_void_p(ws.data_ptr()),
+                                ws.numel(), ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+        out, jv = out.to(x_t.dtype), jv.to(x_t.dtype)
+        if self.use_sit_convention and self.net_pred_type == "flow":
+            out, jv = -out, -jv  # :555-558
+        return out, jv
 
     def _logvar(self, t_e: torch.Tensor) -> torch.Tensor:
         """logvar_linear(t_embedder(t)) (:568-570) - a [B, D] x [D, 1] product on the module's own parameters, evaluated with torch."""

@@ -446,6 +446,37 @@ FG_API int fg_dit_forward_features(fg_dit* h, const float* x_t, const float* t, 
                                    float* cond_out, const int* feature_blocks, float* const* features, int num_features, int batch,
                                    void* workspace, size_t workspace_bytes, void* stream);
 
+/* Forward-mode derivative of fg_dit_forward (the tangent of the MeanFlow objective, fastgen/methods/consistency_model/mean_flow.py:220-252:
+ * torch.func.jvp(net_wrapper, (x_t, t, r), (dxt_dt, 1, 0))).  Forward-only and stateless: no activations are kept, nothing is built for
+ * a backward pass.  Served by FG_DTYPE_BF16X3 handles on a 16 x 16 token grid (every hidden size, head dims 64 and 72, r_timestep on
+ * or off); any other handle has no jvp.
+ * fg_dit_jvp_workspace_bytes: 0 where this handle's compute mode / token grid has no jvp. */
+FG_API size_t fg_dit_jvp_workspace_bytes(const fg_dit* h, int batch);
+/* out = the raw network output of fg_dit_forward(x_t, t, r, class_ids) (same arithmetic, not the same bits: the pass keeps
+ * pre-activations the forward fuses away); jvp = its directional derivative along (vx [B,C,H,W], vt [B], vr [B]).  t, r, vt, vr are
+ * fp32 and refer to the values AS THE EMBEDDERS SEE THEM (after scale_t / 1 - t / t - r, exactly like fg_dit_forward's t and r: the
+ * caller applies the chain rule of that preparation to vt, vr).  vt / vr nullable = 0.  r / vr ignored without r_timestep; r NULL = no
+ * r embedding.  FG_EINVAL before anything is launched: a null pointer, batch <= 0, a workspace that is not 256-byte aligned, out / jvp
+ * overlapping an input, the workspace or each other, a handle without a jvp; FG_ENOTREADY: unpacked weights; FG_ENOMEM: workspace too
+ * small.  An out-of-range class id is reported as in fg_dit_forward. */
+FG_API int fg_dit_jvp(fg_dit* h, const float* x_t, const float* t, const float* r, const int64_t* class_ids, const float* vx, const float* vt,
+                      const float* vr, float* out, float* jvp, int batch, void* workspace, size_t workspace_bytes, void* stream);
+/* The three kernels fg_dit_jvp adds (dit_jvp.hip), handle-free, for the per-op parity tests (fp64 mirror: tests/dit_jvp_ref.py).
+ * Every argument is checked before anything is launched (FG_EINVAL); pointers 16-byte aligned.
+ * fg_op_dit_ln_modulate_jvp: LayerNorm (eps 1e-6, no affine) + adaLN modulation with tangent.  x, xd fp32 [ntok][d]; mod, modd
+ * [ntok / tokens_per_image][mod_stride] with shift at shift_off and scale at scale_off (even numbers); y, yd: [hi | lo] bf16 planes
+ * [ntok][2 d] of y = n (1 + scale) + shift and yd = nd (1 + scale) + n scaled + shiftd, n = LN(x),
+ * nd = (xd - mean(xd) - n mean(n xd)) / sigma.  d in {384, 768, 1024, 1152}. */
+FG_API int fg_op_dit_ln_modulate_jvp(const float* x, const float* xd, const float* mod, const float* modd, int mod_stride, int shift_off,
+                                     int scale_off, void* y, void* yd, int ntok, int d, int tokens_per_image, void* stream);
+/* fg_op_dit_attention (FG_DTYPE_BF16X3 layouts: hi / lo bf16 planes lo_off elements apart, 32 rows of slack behind vt / vtd) with
+ * tangent: out = softmax(q k^T / sqrt(head_dim)) v, outd = (P o (Sd - delta)) v + P vd with Sd = (qd k^T + q kd^T) / sqrt(head_dim),
+ * delta_i = sum_j P_ij Sd_ij; out, outd fp32 [batch][tokens][heads * head_dim].  tokens == 256, head_dim 64 or 72. */
+FG_API int fg_op_dit_attention_jvp(const void* q, const void* k, const void* vt, const void* qd, const void* kd, const void* vtd, float* out,
+                                   float* outd, int batch, int heads, int head_dim, int tokens, size_t lo_off, void* stream);
+/* a = GELU_tanh(h), ad = GELU_tanh'(h) hd: h, hd fp32 [m][k]; a, ad [hi | lo] bf16 planes [m][2 k]; k % 4 == 0. */
+FG_API int fg_op_dit_gelu_jvp(const float* h, const float* hd, void* a, void* ad, int64_t m, int k, void* stream);
+
 /* The sampling loops around fg_dit_forward as ONE call (replayed as one hipGraph per (batch, steps, pointers) when use_graph != 0):
  *   FG_LOOP_X0        FastGenModel.generator_fn + _student_sample_loop (methods/model.py:315-420): x = noise * sigma(t_0); per step
  *                     x0 = convert(forward(x, t_i)) [flow -> x0: x - t v, fp64]; if t_{i+1} > 0: x = alpha(t_{i+1}) x0 + sigma(t_{i+1}) eps_i
