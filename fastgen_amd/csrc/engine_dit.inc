@@ -1,28 +1,42 @@
 // DiT engine (SURVEY §8(f)2): parameter plan with the reference's state-dict names, packed GEMM weights, workspace plan, forward
 // orchestration and the C ABI of include/fastgen_amd.h (fg_dit_*).  Textually included by engine.hip inside its `extern "C"` region
 // (the handle is a HandleBase; pack_group is engine.hip's).  Reference: fastgen/networks/DiT/network.py:153-201 (DiTBlock),
-// :204-225 (OutputProjection), :464-574 (DiT.forward); kernels: dit.hip + conv.hip's token GEMM modes.
+// :204-225 (OutputProjection), :464-574 (DiT.forward); kernels: dit.hip, gemm.hip + conv.hip's token GEMM modes.
+// The four linears of a block (qkv, proj, fc1, fc2) run in one of four flavours (DitFlavour, derived once by dit_flavour).  Everything
+// that depends on the flavour is in one place each: dit_linear launches a linear (the only GemmArgs / ConvArgs of a block linear),
+// dit_modulate / dit_stage put a token tensor into the flavour's operand form, dit_pack_linear packs a weight; dit_block is the one
+// block schedule (dit_forward: modulation vector, dit_block, feature tap), dit_jvp its two-stream twin on the same dit_linear.
 }  // extern "C" (reopened below: the structures and helpers are C++)
+
+// How the four block linears run.  The rest of the network follows cmode: the token tensors, attention, patch embedding, final layer.
+enum DitFlavour {
+    DIT_CONV,  // conv.hip's 16 x 16 token modes in cmode's arithmetic: the exact fp32 mode; bf16 / bf16x3 with their switch at 0
+    DIT_BF16,  // gemm.hip on plain [N][K] bf16 weights
+    DIT_X3,    // gemm.hip's split-bf16 flavour: [hi | lo | hi] weights, [hi | lo] activation planes
+    DIT_FP8,   // gemm.hip on e4m3 operands, the weight as [N][K] e4m3fn bytes followed by the N fp32 channel scales; cmode bf16
+};
+enum { DIT_QKV, DIT_PROJ, DIT_FC1, DIT_FC2, DIT_NLIN };  // the block linears, in the reference's module order
 
 struct fg_dit : HandleBase {
     fg_dit_config cfg;
     int dtype = 0, cmode = 0;  // as fg_edm: storage of the token tensors (0 fp32 / 1 bf16), arithmetic of the GEMMs (FG_DTYPE_*)
+    DitFlavour flavour = DIT_CONV;
     int D = 0, Hd = 0, hd = 0, T = 0, grid = 0;  // hidden size, MLP hidden size, head dim, tokens per image, patches per side
+    struct Lin {  // one block linear: parameter indices of weight [N][K] and bias [N], the weight packed for the flavour (owned)
+        int w = -1, b = -1, N = 0, K = 0;
+        void* p = nullptr;
+    };
     struct Blk {
-        int qkv_w, qkv_b, proj_w, proj_b, fc1_w, fc1_b, fc2_w, fc2_b, mod_w, mod_b;
-        void *p_qkv = nullptr, *p_proj = nullptr, *p_fc1 = nullptr, *p_fc2 = nullptr;  // packed (owned)
+        Lin lin[DIT_NLIN];
+        int mod_w, mod_b;
     };
     std::vector<Blk> blocks;
     int pos = -1, xw = -1, xb = -1, tw0 = -1, tb0 = -1, tw2 = -1, tb2 = -1, rw0 = -1, rb0 = -1, rw2 = -1, rb2 = -1, ytab = -1, fw = -1, fb = -1,
         fmw = -1, fmb = -1;
-    void* p_modw = nullptr;   // bf16 GEMM path: all blocks' conditioning_net weights stacked [depth * 6 D][D] bf16 ...
+    void* p_modw = nullptr;   // DIT_BF16 / DIT_FP8: all blocks' conditioning_net weights stacked [depth * 6 D][D] bf16 ...
     float* modb = nullptr;    // ... and their biases [depth * 6 D]: one GEMM per forward instead of one 256-row linear per block
+    bool bf16_gemm() const { return flavour == DIT_BF16 || flavour == DIT_FP8; }  // (what the two share: p_modw, token-major qkv at head dim 72)
     SamplerCache sampler;  // fg_dit_sampler_run (engine_sampler.inc)
-    bool gemm3 = false;  // bf16x3 mode: the four block linears on gemm.hip's split-bf16 flavour ([hi | lo | hi] weights, [hi | lo] activation planes)
-    // fp8 mode (FG_DTYPE_FP8): cmode / dtype / gemm as in the bf16 mode (token tensors, attention, modulation GEMM, final layer), but the
-    // four block linears contract e4m3 operands: p_qkv ... hold [N][K] e4m3fn bytes followed by the N fp32 channel scales
-    bool fp8 = false;
-    bool gemm = false;  // bf16 mode: the four block linears on gemm.hip (plain [N][K] bf16 weights) instead of conv.hip's token modes
     // a kernel that met an out-of-range class index raises *err_host (pinned, mapped: err_dev is its device address); the next call on
     // the handle reports it (the reference's nn.Embedding device-asserts; nothing is clamped, the sample's output is NaN)
     int *err_host = nullptr, *err_dev = nullptr;
@@ -32,7 +46,7 @@ struct fg_dit : HandleBase {
         return 1;
     }
     // Parameters as the kernels read them.  The four block linears are read from the caller's tensors at PACK time only (into the
-    // GEMM layouts of p_qkv ...); every other parameter is copied into `own` at pack time, so that between two packs nothing points into
+    // flavour's layout, Lin::p); every other parameter is copied into `own` at pack time, so that between two packs nothing points into
     // the caller's memory: FSDP2 gathers a group's parameters, packs that group and frees them again (DiT.fully_shard), and a captured
     // sampler graph never holds a pointer to a tensor the caller may reallocate.
     std::vector<float*> own;       // [params]: engine-owned fp32 copy, or nullptr (pack-only parameters, logvar_linear)
@@ -48,13 +62,14 @@ struct DitWs {
     float *tf, *th, *temb, *remb, *c, *sc, *mod, *fmod, *mod_all;
     void* scb;
     void *x0, *x1, *y, *q, *k, *vt, *att, *hid, *qkv;
-    void *y8, *hid8;   // fp8 mode: the quantised A operands [ntok][D] / [ntok][Hd] ...
+    void *y8, *hid8;   // DIT_FP8: the quantised A operands [ntok][D] / [ntok][Hd] ...
     float *ys, *hs;    // ... and their per-token scales
 };
 
 size_t dit_plan(const fg_dit* h, int B, Arena& A, DitWs& w) {
     const size_t tsz = h->dtype ? 2 : 4;
     const size_t D = h->D, ntok = (size_t)B * h->T;
+    const bool fp8 = h->flavour == DIT_FP8;
     w.tf = A.get<float>((size_t)B * 256);
     w.th = A.get<float>((size_t)B * D);
     w.temb = A.get<float>((size_t)B * D);
@@ -62,8 +77,8 @@ size_t dit_plan(const fg_dit* h, int B, Arena& A, DitWs& w) {
     w.c = A.get<float>((size_t)B * D);
     w.sc = A.get<float>((size_t)B * D);
     w.mod = A.get<float>((size_t)B * 6 * D);
-    w.mod_all = A.get<float>(h->p_modw && B >= 256 ? (size_t)B * h->blocks.size() * 6 * D : 0);
-    w.scb = A.take(h->p_modw && B >= 256 ? (size_t)B * D * 2 : 0);
+    w.mod_all = A.get<float>(h->bf16_gemm() && B >= 256 ? (size_t)B * h->blocks.size() * 6 * D : 0);
+    w.scb = A.take(h->bf16_gemm() && B >= 256 ? (size_t)B * D * 2 : 0);
     w.fmod = A.get<float>((size_t)B * 2 * D);
     w.x0 = A.take(ntok * D * tsz);
     w.x1 = A.take(ntok * D * tsz);
@@ -75,77 +90,126 @@ size_t dit_plan(const fg_dit* h, int B, Arena& A, DitWs& w) {
     w.vt = A.take(2 * (ntok * D + 32 * (size_t)h->T) * (tsz / 2));
     w.att = A.take(ntok * D * tsz);
     w.hid = A.take(ntok * (size_t)h->Hd * tsz);
-    w.qkv = A.take(ntok * 3 * D * tsz);  // token-major q | k | v of the LDS-staged attention (bf16 GEMM path, head dim 72)
-    w.y8 = A.take(h->fp8 ? ntok * D : 0);
-    w.hid8 = A.take(h->fp8 ? ntok * (size_t)h->Hd : 0);
-    w.ys = A.get<float>(h->fp8 ? ntok : 0);
-    w.hs = A.get<float>(h->fp8 ? ntok : 0);
+    w.qkv = A.take(ntok * 3 * D * tsz);  // token-major q | k | v of the LDS-staged attention (DIT_BF16 / DIT_FP8, head dim 72)
+    w.y8 = A.take(fp8 ? ntok * D : 0);
+    w.hid8 = A.take(fp8 ? ntok * (size_t)h->Hd : 0);
+    w.ys = A.get<float>(fp8 ? ntok : 0);
+    w.hs = A.get<float>(fp8 ? ntok : 0);
     return (A.off + 255) & ~(size_t)255;
 }
 
-// one token GEMM: out[tok][n] = epilogue(sum_k src[tok][k] W[n][k] + bias[n])
-int dit_gemm(fg_dit* h, const void* src, int K, const void* wpack, const float* bias, int N, void* out, int B, hipStream_t s, int act = 0,
-             const float* gate = nullptr, int gate_stride = 0, const void* resid = nullptr) {
-    if (h->gemm3) {  // src: [hi | lo] planes; out: fp32 (act == 0) or [hi | lo] planes of the GELU'd hidden layer (act == 1)
-        GemmArgs g;
-        g.A = src; g.W = wpack; g.bias = bias; g.out = out; g.M = B * h->T; g.N = N; g.K = K;
-        g.act = act; g.gate = gate; g.gate_stride = gate_stride; g.gate_rows = h->T; g.resid = resid;
-        HIP_TRY(launch_gemm_x3(g, act ? 1 : 0, s));
-        return FG_OK;
-    }
-    if (h->gemm) {
-        GemmArgs g;
-        g.A = src; g.W = wpack; g.bias = bias; g.out = out; g.M = B * h->T; g.N = N; g.K = K;
-        g.act = act; g.gate = gate; g.gate_stride = gate_stride; g.gate_rows = h->T; g.resid = resid;
-        HIP_TRY(launch_gemm_bf16(g, s));
-        return FG_OK;
-    }
-    ConvArgs a{};
-    a.src1 = src; a.C1 = K; a.Hs = a.Ws = a.H = a.W = 16; a.B = B;
-    a.wpack = wpack; a.bias = bias; a.scale = 1.0f; a.out = out; a.Cout = N;
-    a.act = act; a.gate = gate; a.gate_stride = gate_stride; a.resid = resid;
-    HIP_TRY(launch_conv_fused(h->cmode, 1, PRO_NONE, RES_NONE, OUT_TOK, a, s));
-    return FG_OK;
+// A block linear's input in the handle's flavour: a token tensor in cmode's storage (DIT_CONV, DIT_BF16), [hi | lo] planes (DIT_X3),
+// or e4m3 bytes with their per-token scales (DIT_FP8)
+struct DitOperand {
+    const void* p = nullptr;
+    const float* scale = nullptr;
+};
+
+// ... and where its result goes: the token epilogue out[tok][n] = resid + gate * act(acc + bias) (dit_tok), or the head-split one
+// q | k [B][H][T][hd], v^T [B][H][hd][T], the lo planes of the bf16x3 mode lo_off elements behind (dit_heads)
+struct DitEpilogue {
+    void* out = nullptr;
+    int act = 0;
+    const float* gate = nullptr;
+    int gate_stride = 0;
+    const void* resid = nullptr;
+    void *q = nullptr, *k = nullptr, *vt = nullptr;
+    size_t lo_off = 0;
+};
+DitEpilogue dit_tok(void* out, int act = 0, const float* gate = nullptr, int gate_stride = 0, const void* resid = nullptr) {
+    DitEpilogue e;
+    e.out = out, e.act = act, e.gate = gate, e.gate_stride = gate_stride, e.resid = resid;
+    return e;
+}
+DitEpilogue dit_heads(void* q, void* k, void* vt, size_t lo_off) {
+    DitEpilogue e;
+    e.q = q, e.k = k, e.vt = vt, e.lo_off = lo_off;
+    return e;
 }
 
-// the same on e4m3 operands: src [tok][K] bytes + src_scale [tok]; wpack = [N][K] bytes followed by the N channel scales (dit_pack)
-int dit_gemm_fp8(fg_dit* h, const void* src, const float* src_scale, int K, const void* wpack, const float* bias, int N, void* out, int B,
-                 hipStream_t s, int act = 0, const float* gate = nullptr, int gate_stride = 0, const void* resid = nullptr) {
+// One block linear in the handle's flavour: epilogue(sum_k a[tok][k] W[n][k] + bias[n]) over B * T tokens (bias nullable: the tangent
+// stream of dit_jvp)
+int dit_linear(const fg_dit* h, DitOperand a, const fg_dit::Lin& l, const float* bias, const DitEpilogue& e, int B, hipStream_t s) {
+    if (h->flavour == DIT_CONV) {
+        ConvArgs c{};
+        c.src1 = a.p; c.C1 = l.K; c.Hs = c.Ws = c.H = c.W = 16; c.B = B;
+        c.wpack = l.p; c.bias = bias; c.scale = 1.0f; c.Cout = l.N;
+        c.out = e.out; c.act = e.act; c.gate = e.gate; c.gate_stride = e.gate_stride; c.resid = e.resid;
+        if (e.q) c.heads = h->cfg.num_heads, c.head_dim = h->hd, c.q_out = e.q, c.k_out = e.k, c.vt_out = e.vt, c.heads_lo_off = e.lo_off;
+        HIP_TRY(launch_conv_fused(h->cmode, 1, PRO_NONE, RES_NONE, e.q ? OUT_HEADS : OUT_TOK, c, s));
+        return FG_OK;
+    }
     GemmArgs g;
-    g.A = src; g.W = wpack; g.bias = bias; g.out = out; g.M = B * h->T; g.N = N; g.K = K;
-    g.a_scale = src_scale; g.w_scale = reinterpret_cast<const float*>(reinterpret_cast<const char*>(wpack) + (size_t)N * K);
-    g.act = act; g.gate = gate; g.gate_stride = gate_stride; g.gate_rows = h->T; g.resid = resid;
-    HIP_TRY(launch_gemm_fp8(g, s));
+    g.A = a.p; g.W = l.p; g.bias = bias; g.M = B * h->T; g.N = l.N; g.K = l.K;
+    if (e.q) g.heads = h->cfg.num_heads, g.head_dim = h->hd, g.T = h->T, g.q = e.q, g.k = e.k, g.vt = e.vt;
+    else g.out = e.out, g.act = e.act, g.gate = e.gate, g.gate_stride = e.gate_stride, g.gate_rows = h->T, g.resid = e.resid;
+    if (h->flavour == DIT_X3) {  // a GELU'd output (fc1) is written as the [hi | lo] planes fc2 reads, every other one as fp32
+        g.lo_off = e.lo_off;
+        HIP_TRY(launch_gemm_x3(g, e.act ? 1 : 0, s));
+    } else if (h->flavour == DIT_FP8) {  // (the channel scales lie behind the packed bytes: dit_pack_linear)
+        g.a_scale = a.scale;
+        g.w_scale = reinterpret_cast<const float*>(reinterpret_cast<const char*>(l.p) + (size_t)l.N * l.K);
+        HIP_TRY(launch_gemm_fp8(g, s));
+    } else {
+        HIP_TRY(launch_gemm_bf16(g, s));
+    }
     return FG_OK;
 }
 
-// One transformer block in the fp8 mode: LayerNorm-modulate stores e4m3 + scale, the attention output and the GELU'd hidden layer are
-// quantised by a pass of their own (their rows cross the producing kernels' tiles); q / k / v, attention and the residual stream stay bf16.
-int dit_block_fp8(fg_dit* h, const fg_dit::Blk& b, const float* mod, int mstride, void*& x, void*& xn, int B, DitWs& w, hipStream_t s) {
-    const fg_dit_config& c = h->cfg;
-    const int D = h->D, T = h->T, ntok = B * T;
-    int rc;
-    HIP_TRY(launch_dit_ln_modulate_fp8(D, x, mod, mstride, 0, D, w.y8, w.ys, ntok, T, s));
-    if (h->hd == 72) {  // qkv stays token-major; attention on wan.hip's LDS-staged kernel
-        if ((rc = dit_gemm_fp8(h, w.y8, w.ys, D, b.p_qkv, h->P(b.qkv_b), 3 * D, w.qkv, B, s))) return rc;
-        const __bf16* qkv = (const __bf16*)w.qkv;
-        HIP_TRY(launch_fa(72, qkv, 3 * D, (int64_t)T * 3 * D, qkv + D, qkv + 2 * D, 3 * D, (int64_t)T * 3 * D, w.att, D, (int64_t)T * D, B,
-                          c.num_heads, T, T, s));
+// LayerNorm-modulate of the stream x as the flavour's operand: y = LN(x) (1 + mod[scale_off ...]) + mod[shift_off ...]
+int dit_modulate(const fg_dit* h, const void* x, const float* mod, int mstride, int shift_off, int scale_off, int ntok, DitWs& w, hipStream_t s,
+                 DitOperand& y) {
+    y = DitOperand{w.y, nullptr};
+    if (h->flavour == DIT_FP8) {
+        y = DitOperand{w.y8, w.ys};
+        HIP_TRY(launch_dit_ln_modulate_fp8(h->D, x, mod, mstride, shift_off, scale_off, w.y8, w.ys, ntok, h->T, s));
+    } else if (h->flavour == DIT_X3) {
+        HIP_TRY(launch_dit_ln_modulate_split(h->D, (const float*)x, mod, mstride, shift_off, scale_off, w.y, ntok, h->T, s));
     } else {
-        GemmArgs g;
-        g.A = w.y8; g.W = b.p_qkv; g.bias = h->P(b.qkv_b); g.M = ntok; g.N = 3 * D; g.K = D;
-        g.a_scale = w.ys; g.w_scale = reinterpret_cast<const float*>(reinterpret_cast<const char*>(b.p_qkv) + (size_t)3 * D * D);
-        g.heads = c.num_heads; g.head_dim = h->hd; g.T = T; g.q = w.q; g.k = w.k; g.vt = w.vt;
-        HIP_TRY(launch_gemm_fp8(g, s));
-        HIP_TRY(launch_dit_attention(h->cmode, w.q, w.k, w.vt, w.att, B, c.num_heads, h->hd, T, 0, s));
+        HIP_TRY(launch_dit_ln_modulate(h->dtype, h->D, x, mod, mstride, shift_off, scale_off, w.y, ntok, h->T, s));
     }
-    HIP_TRY(launch_quant_rows_fp8(1, w.att, w.y8, w.ys, ntok, D, s));
-    if ((rc = dit_gemm_fp8(h, w.y8, w.ys, D, b.p_proj, h->P(b.proj_b), D, xn, B, s, 0, mod + 2 * D, mstride, x))) return rc;  // x + gate * attn
+    return FG_OK;
+}
+
+// A token tensor [ntok][K] that a kernel left in cmode's storage (the attention output, the hidden layer) as the flavour's operand:
+// as it is, as planes in `planes` (nullptr: src holds planes already), or quantised into q8 / scale.  The rows of both tensors cross
+// their producing kernels' tiles, so the quantiser is a pass of its own.
+int dit_stage(const fg_dit* h, const void* src, int K, void* planes, void* q8, float* scale, int ntok, hipStream_t s, DitOperand& a) {
+    a = DitOperand{src, nullptr};
+    if (h->flavour == DIT_X3 && planes) {
+        HIP_TRY(launch_split_planes((const float*)src, planes, (int64_t)ntok, K, s));
+        a.p = planes;
+    } else if (h->flavour == DIT_FP8) {
+        HIP_TRY(launch_quant_rows_fp8(1, src, q8, scale, ntok, K, s));
+        a = DitOperand{q8, scale};
+    }
+    return FG_OK;
+}
+
+// One transformer block (DiTBlock.forward, :186-199) on the stream x (xn: its other buffer; swapped so that x is the output); mod:
+// {shift, scale, gate} x {attention, feed-forward} of stride mstride per sample.  q / k / v, attention and the stream are cmode's.
+int dit_block(const fg_dit* h, const fg_dit::Blk& b, const float* mod, int mstride, void*& x, void*& xn, int B, DitWs& w, hipStream_t s) {
+    const int D = h->D, T = h->T, ntok = B * T, heads = h->cfg.num_heads;
+    DitOperand a;  // the operand the next linear reads
+    const auto linear = [&](int l, const DitEpilogue& e) { return dit_linear(h, a, b.lin[l], h->P(b.lin[l].b), e, B, s); };
+    int rc;
+    if ((rc = dit_modulate(h, x, mod, mstride, 0, D, ntok, w, s, a))) return rc;
+    if (h->bf16_gemm() && h->hd == 72) {  // qkv stays token-major; attention on wan.hip's LDS-staged kernel
+        if ((rc = linear(DIT_QKV, dit_tok(w.qkv)))) return rc;
+        const __bf16* qkv = (const __bf16*)w.qkv;
+        HIP_TRY(launch_fa(72, qkv, 3 * D, (int64_t)T * 3 * D, qkv + D, qkv + 2 * D, 3 * D, (int64_t)T * 3 * D, w.att, D, (int64_t)T * D, B, heads, T,
+                          T, s));
+    } else {  // head-split q | k | v^T; lo_off: elements between their hi and lo planes (only the bf16x3 kernels read it)
+        const size_t lo_off = h->flavour == DIT_FP8 ? 0 : (size_t)ntok * D + 32 * (size_t)T;
+        if ((rc = linear(DIT_QKV, dit_heads(w.q, w.k, w.vt, lo_off)))) return rc;
+        HIP_TRY(launch_dit_attention(h->cmode, w.q, w.k, w.vt, w.att, B, heads, h->hd, T, lo_off, s));
+    }
+    // x + gate * proj(attention) (:192); bf16x3: its planes go into the buffer the qkv projection has consumed
+    if ((rc = dit_stage(h, w.att, D, w.y, w.y8, w.ys, ntok, s, a)) || (rc = linear(DIT_PROJ, dit_tok(xn, 0, mod + 2 * D, mstride, x)))) return rc;
     std::swap(x, xn);
-    HIP_TRY(launch_dit_ln_modulate_fp8(D, x, mod, mstride, 3 * D, 4 * D, w.y8, w.ys, ntok, T, s));
-    if ((rc = dit_gemm_fp8(h, w.y8, w.ys, D, b.p_fc1, h->P(b.fc1_b), h->Hd, w.hid, B, s, 1))) return rc;  // GELU(tanh)
-    HIP_TRY(launch_quant_rows_fp8(1, w.hid, w.hid8, w.hs, ntok, h->Hd, s));
-    if ((rc = dit_gemm_fp8(h, w.hid8, w.hs, h->Hd, b.p_fc2, h->P(b.fc2_b), D, xn, B, s, 0, mod + 5 * D, mstride, x))) return rc;
+    // x + gate * fc2(GELU(tanh)(fc1(.))) (:198); bf16x3: fc1 writes the hidden layer as planes itself
+    if ((rc = dit_modulate(h, x, mod, mstride, 3 * D, 4 * D, ntok, w, s, a)) || (rc = linear(DIT_FC1, dit_tok(w.hid, 1)))) return rc;
+    if ((rc = dit_stage(h, w.hid, h->Hd, nullptr, w.hid8, w.hs, ntok, s, a)) || (rc = linear(DIT_FC2, dit_tok(xn, 0, mod + 5 * D, mstride, x)))) return rc;
     std::swap(x, xn);
     return FG_OK;
 }
@@ -155,8 +219,7 @@ int dit_block_fp8(fg_dit* h, const fg_dit::Blk& b, const float* mod, int mstride
 int dit_forward(fg_dit* h, const float* x_t, const float* t, const float* r, const int64_t* cls, float* out, float* cond_out, int B, DitWs& w,
                 hipStream_t s, const int* feat_blocks = nullptr, float* const* feats = nullptr, int nfeat = 0, bool early = false) {
     const fg_dit_config& c = h->cfg;
-    const int D = h->D, T = h->T, ntok = B * T;
-    const size_t lo_off = (size_t)ntok * D + 32 * (size_t)T;  // bf16x3: elements between the hi and lo planes of q / k / v^T
+    const int D = h->D, ntok = B * h->T;
     // conditioning vector c = t_emb + y_emb + r_emb (:514-533)
     HIP_TRY(launch_dit_fourier(t, w.tf, B, 256, s));
     HIP_TRY(launch_linear(w.tf, h->P(h->tw0), h->P(h->tb0), w.th, B, 256, D, 1, s));
@@ -173,9 +236,9 @@ int dit_forward(fg_dit* h, const float* x_t, const float* t, const float* r, con
     // tokens
     HIP_TRY(launch_dit_patch_embed(h->dtype, x_t, h->P(h->xw), h->P(h->xb), h->P(h->pos), w.x0, B, c.in_channels, h->grid, c.patch_size, D, s));
     void *x = w.x0, *xn = w.x1;
-    // {shift, scale, gate} x {attention, feed-forward} = conditioning_net(c).chunk(6) (:186-187).  bf16 mode at B >= 256: the 28 blocks'
+    // {shift, scale, gate} x {attention, feed-forward} = conditioning_net(c).chunk(6) (:186-187).  DIT_BF16 / DIT_FP8 at B >= 256: the 28 blocks'
     // Linear(D, 6 D) of silu(c) as ONE token GEMM over the stacked weights (bf16 operands as under the reference's autocast, fp32 out)
-    const bool mod_once = h->p_modw && B >= 256;
+    const bool mod_once = h->bf16_gemm() && B >= 256;
     const int mstride = mod_once ? (int)h->blocks.size() * 6 * D : 6 * D;
     if (mod_once) {
         HIP_TRY(launch_cvt_rows_bf16(w.sc, w.scb, (int64_t)B * D, s));
@@ -183,69 +246,17 @@ int dit_forward(fg_dit* h, const float* x_t, const float* t, const float* r, con
         g.A = w.scb; g.W = h->p_modw; g.bias = h->modb; g.out = w.mod_all; g.M = B; g.N = mstride; g.K = D; g.out_f32 = 1;
         HIP_TRY(launch_gemm_bf16(g, s));
     }
-    int bi = 0, blk_idx = 0, fi = 0;
+    int bi = 0, fi = 0;
     for (const fg_dit::Blk& b : h->blocks) {
-        float* mod = mod_once ? w.mod_all + (size_t)(bi++) * 6 * D : w.mod;
+        float* mod = mod_once ? w.mod_all + (size_t)bi * 6 * D : w.mod;
         if (!mod_once) HIP_TRY(launch_linear(w.sc, h->P(b.mod_w), h->P(b.mod_b), w.mod, B, D, 6 * D, 0, s));
-        if (h->fp8) {
-            const int rc8 = dit_block_fp8(h, b, mod, mstride, x, xn, B, w, s);
-            if (rc8) return rc8;
-            if (fi < nfeat && feat_blocks[fi] == blk_idx) {
-                HIP_TRY(launch_from_act(h->dtype, x, feats[fi], (int64_t)ntok * D, s));
-                if (++fi == nfeat && early) return FG_OK;
-            }
-            ++blk_idx;
-            continue;
-        }
-        if (h->gemm3) HIP_TRY(launch_dit_ln_modulate_split(D, (const float*)x, mod, mstride, 0, D, w.y, ntok, T, s));
-        else HIP_TRY(launch_dit_ln_modulate(h->dtype, D, x, mod, mstride, 0, D, w.y, ntok, T, s));
-        const bool fa = h->gemm && h->hd == 72;  // qkv stays token-major; attention on wan.hip's LDS-staged kernel
-        if (fa) {
-            int rc = dit_gemm(h, w.y, D, b.p_qkv, h->P(b.qkv_b), 3 * D, w.qkv, B, s);
-            if (rc) return rc;
-        } else if (h->gemm3) {
-            GemmArgs g;
-            g.A = w.y; g.W = b.p_qkv; g.bias = h->P(b.qkv_b); g.M = ntok; g.N = 3 * D; g.K = D;
-            g.heads = c.num_heads; g.head_dim = h->hd; g.T = T; g.q = w.q; g.k = w.k; g.vt = w.vt; g.lo_off = lo_off;
-            HIP_TRY(launch_gemm_x3(g, 0, s));
-        } else if (h->gemm) {
-            GemmArgs g;
-            g.A = w.y; g.W = b.p_qkv; g.bias = h->P(b.qkv_b); g.M = ntok; g.N = 3 * D; g.K = D;
-            g.heads = c.num_heads; g.head_dim = h->hd; g.T = T; g.q = w.q; g.k = w.k; g.vt = w.vt;
-            HIP_TRY(launch_gemm_bf16(g, s));
-        } else {   // qkv projection, written head-split: q | k [B][H][T][hd], v^T [B][H][hd][T]
-            ConvArgs a{};
-            a.src1 = w.y; a.C1 = D; a.Hs = a.Ws = a.H = a.W = 16; a.B = B;
-            a.wpack = b.p_qkv; a.bias = h->P(b.qkv_b); a.scale = 1.0f; a.Cout = 3 * D;
-            a.heads = c.num_heads; a.head_dim = h->hd; a.q_out = w.q; a.k_out = w.k; a.vt_out = w.vt;
-            a.heads_lo_off = lo_off;
-            HIP_TRY(launch_conv_fused(h->cmode, 1, PRO_NONE, RES_NONE, OUT_HEADS, a, s));
-        }
-        if (fa) {
-            const __bf16* qkv = (const __bf16*)w.qkv;
-            HIP_TRY(launch_fa(72, qkv, 3 * D, (int64_t)T * 3 * D, qkv + D, qkv + 2 * D, 3 * D, (int64_t)T * 3 * D, w.att, D, (int64_t)T * D, B,
-                              c.num_heads, T, T, s));
-        } else {
-            HIP_TRY(launch_dit_attention(h->cmode, w.q, w.k, w.vt, w.att, B, c.num_heads, h->hd, T, lo_off, s));
-        }
-        const void* att = w.att;
-        if (h->gemm3) {  // the attention output (fp32) as planes, in the buffer the qkv projection has consumed
-            HIP_TRY(launch_split_planes((const float*)w.att, w.y, (int64_t)ntok, D, s));
-            att = w.y;
-        }
-        int rc = dit_gemm(h, att, D, b.p_proj, h->P(b.proj_b), D, xn, B, s, 0, mod + 2 * D, mstride, x);  // x + gate * attn (:192)
+        const int rc = dit_block(h, b, mod, mstride, x, xn, B, w, s);
         if (rc) return rc;
-        std::swap(x, xn);
-        if (h->gemm3) HIP_TRY(launch_dit_ln_modulate_split(D, (const float*)x, mod, mstride, 3 * D, 4 * D, w.y, ntok, T, s));
-        else HIP_TRY(launch_dit_ln_modulate(h->dtype, D, x, mod, mstride, 3 * D, 4 * D, w.y, ntok, T, s));
-        if ((rc = dit_gemm(h, w.y, D, b.p_fc1, h->P(b.fc1_b), h->Hd, w.hid, B, s, 1))) return rc;  // GELU(tanh)
-        if ((rc = dit_gemm(h, w.hid, h->Hd, b.p_fc2, h->P(b.fc2_b), D, xn, B, s, 0, mod + 5 * D, mstride, x))) return rc;  // :198
-        std::swap(x, xn);
-        if (fi < nfeat && feat_blocks[fi] == blk_idx) {
+        if (fi < nfeat && feat_blocks[fi] == bi) {
             HIP_TRY(launch_from_act(h->dtype, x, feats[fi], (int64_t)ntok * D, s));
             if (++fi == nfeat && early) return FG_OK;
         }
-        ++blk_idx;
+        ++bi;
     }
     HIP_TRY(launch_linear(w.sc, h->P(h->fmw), h->P(h->fmb), w.fmod, B, D, 2 * D, 0, s));
     HIP_TRY(launch_dit_final(h->dtype, D, x, w.fmod, h->P(h->fw), h->P(h->fb), out, ntok, h->grid, c.patch_size, c.in_channels, s));
@@ -261,7 +272,8 @@ struct DitJvpWs {
     void *y, *yd, *q, *k, *vt, *qd, *kd, *vtd, *a, *ad;
 };
 
-bool dit_has_jvp(const fg_dit* h) { return h->cmode == FG_DTYPE_BF16X3 && !h->fp8 && h->grid == 16; }
+// (the bf16x3 mode is DIT_X3, or DIT_CONV by its switch: that handle has a jvp plan too, and fg_dit_jvp refuses it by the switch's name)
+bool dit_has_jvp(const fg_dit* h) { return h->cmode == FG_DTYPE_BF16X3 && h->grid == 16; }
 
 size_t dit_jvp_plan(const fg_dit* h, int B, Arena& A, DitJvpWs& w) {
     const size_t D = h->D, Hd = h->Hd, ntok = (size_t)B * h->T;
@@ -318,43 +330,32 @@ int dit_jvp(fg_dit* h, const float* x_t, const float* t, const float* r, const i
     HIP_TRY(launch_dit_patch_embed(0, vx, h->P(h->xw), nullptr, nullptr, w.xd0, B, c.in_channels, h->grid, c.patch_size, D, s));
     float *x = w.x0, *xn = w.x1, *xd = w.xd0, *xdn = w.xd1;
     const int ms = 6 * D;
-    auto gemm = [&](const void* A, int K, const void* W, const float* bias, int N, void* o, const float* gate, const void* resid) {
-        GemmArgs g;
-        g.A = A; g.W = W; g.bias = bias; g.out = o; g.M = ntok; g.N = N; g.K = K;
-        g.gate = gate; g.gate_stride = ms; g.gate_rows = T; g.resid = resid;
-        return launch_gemm_x3(g, 0, s);
-    };
-    auto qkv = [&](const void* A, const fg_dit::Blk& b, const float* bias, void* q, void* k, void* v) {
-        GemmArgs g;
-        g.A = A; g.W = b.p_qkv; g.bias = bias; g.M = ntok; g.N = 3 * D; g.K = D;
-        g.heads = c.num_heads; g.head_dim = h->hd; g.T = T; g.q = q; g.k = k; g.vt = v; g.lo_off = lo_off;
-        return launch_gemm_x3(g, 0, s);
+    // a block linear on one stream's operand planes; the tangent stream's has no bias
+    auto lin = [&](const void* a, const fg_dit::Lin& l, bool bias, const DitEpilogue& e) {
+        return dit_linear(h, DitOperand{a, nullptr}, l, bias ? h->P(l.b) : nullptr, e, B, s);
     };
     for (const fg_dit::Blk& b : h->blocks) {
+        const fg_dit::Lin &qkv = b.lin[DIT_QKV], &proj = b.lin[DIT_PROJ], &fc1 = b.lin[DIT_FC1], &fc2 = b.lin[DIT_FC2];
         // {shift, scale, gate} x {attention, feed-forward} and their tangents: modd = W_mod (silu'(c) o cd), no bias
         HIP_TRY(launch_linear(w.sc, h->P(b.mod_w), h->P(b.mod_b), w.mod, B, D, 6 * D, 0, s));
         HIP_TRY(launch_linear(w.scd, h->P(b.mod_w), nullptr, w.modd, B, D, 6 * D, 0, s));
         // attention branch
         HIP_TRY(launch_dit_ln_modulate_jvp(D, x, xd, w.mod, w.modd, ms, 0, D, w.y, w.yd, ntok, T, s));
-        HIP_TRY(qkv(w.y, b, h->P(b.qkv_b), w.q, w.k, w.vt));
-        HIP_TRY(qkv(w.yd, b, nullptr, w.qd, w.kd, w.vtd));
+        if ((rc = lin(w.y, qkv, true, dit_heads(w.q, w.k, w.vt, lo_off))) || (rc = lin(w.yd, qkv, false, dit_heads(w.qd, w.kd, w.vtd, lo_off)))) return rc;
         HIP_TRY(launch_dit_attention_jvp(w.q, w.k, w.vt, w.qd, w.kd, w.vtd, w.att, w.attd, B, c.num_heads, h->hd, T, lo_off, s));
         HIP_TRY(launch_split_planes(w.att, w.y, (int64_t)ntok, D, s));
         HIP_TRY(launch_split_planes(w.attd, w.yd, (int64_t)ntok, D, s));
         // x' = x + g o h, xd' = xd + g o (W od) + gd o h with h = W o + b: h un-gated (in att's space, consumed above), the middle term
         // on the GEMM's gate + residual epilogue, the outer ones in one elementwise pass
-        HIP_TRY(gemm(w.y, D, b.p_proj, h->P(b.proj_b), D, w.att, nullptr, nullptr));
-        HIP_TRY(gemm(w.yd, D, b.p_proj, nullptr, D, xdn, w.mod + 2 * D, xd));
+        if ((rc = lin(w.y, proj, true, dit_tok(w.att, 0, nullptr, ms))) || (rc = lin(w.yd, proj, false, dit_tok(xdn, 0, w.mod + 2 * D, ms, xd)))) return rc;
         HIP_TRY(launch_dit_gate_update(w.att, w.mod + 2 * D, w.modd + 2 * D, ms, T, x, xn, xdn, (int64_t)ntok, D, s));
         std::swap(x, xn);
         std::swap(xd, xdn);
         // feed-forward branch: fc1 keeps its pre-activation, GELU and its derivative in one pass of their own
         HIP_TRY(launch_dit_ln_modulate_jvp(D, x, xd, w.mod, w.modd, ms, 3 * D, 4 * D, w.y, w.yd, ntok, T, s));
-        HIP_TRY(gemm(w.y, D, b.p_fc1, h->P(b.fc1_b), Hd, w.hid, nullptr, nullptr));
-        HIP_TRY(gemm(w.yd, D, b.p_fc1, nullptr, Hd, w.hidd, nullptr, nullptr));
+        if ((rc = lin(w.y, fc1, true, dit_tok(w.hid, 0, nullptr, ms))) || (rc = lin(w.yd, fc1, false, dit_tok(w.hidd, 0, nullptr, ms)))) return rc;
         HIP_TRY(launch_dit_gelu_jvp(w.hid, w.hidd, w.a, w.ad, (int64_t)ntok, Hd, s));
-        HIP_TRY(gemm(w.a, Hd, b.p_fc2, h->P(b.fc2_b), D, w.att, nullptr, nullptr));
-        HIP_TRY(gemm(w.ad, Hd, b.p_fc2, nullptr, D, xdn, w.mod + 5 * D, xd));
+        if ((rc = lin(w.a, fc2, true, dit_tok(w.att, 0, nullptr, ms))) || (rc = lin(w.ad, fc2, false, dit_tok(xdn, 0, w.mod + 5 * D, ms, xd)))) return rc;
         HIP_TRY(launch_dit_gate_update(w.att, w.mod + 5 * D, w.modd + 5 * D, ms, T, x, xn, xdn, (int64_t)ntok, D, s));
         std::swap(x, xn);
         std::swap(xd, xdn);
@@ -365,73 +366,66 @@ int dit_jvp(fg_dit* h, const float* x_t, const float* t, const float* r, const i
     return FG_OK;
 }
 
+// The flavour of a configuration: the compute mode, moved onto conv.hip's token modes by its switch at 0.  (fg_dit_create's checks of
+// hidden_size and mlp_hidden leave nothing for the token GEMMs to refuse, and it refuses the fp8 mode with the switch itself.)
+DitFlavour dit_flavour(int compute_dtype) {
+    const auto off = [](const char* name) {
+        const char* e = getenv(name);
+        return e && e[0] == '0';
+    };
+    if (compute_dtype == FG_DTYPE_FP8) return DIT_FP8;
+    if (compute_dtype == FG_DTYPE_BF16 && !off("FASTGEN_AMD_DIT_GEMM")) return DIT_BF16;
+    if (compute_dtype == FG_DTYPE_BF16X3 && !off("FASTGEN_AMD_DIT_GEMM3")) return DIT_X3;
+    return DIT_CONV;
+}
+
+// One block linear's fp32 weight [N][K] into the flavour's layout
+int dit_pack_linear(const fg_dit* h, const fg_dit::Lin& l, hipStream_t s) {
+    const float* src = h->params[l.w].ptr;
+    const size_t n = (size_t)l.N * l.K;
+    if (h->flavour == DIT_X3) HIP_TRY(launch_split3_weights(src, l.p, l.N, l.K, s));
+    else if (h->flavour == DIT_BF16) HIP_TRY(launch_cvt_bf16(src, l.p, n, s));
+    else if (h->flavour == DIT_FP8)  // rows quantised on the device: e4m3 bytes, then one scale per output channel (inside the bf16-sized allocation)
+        HIP_TRY(launch_quant_rows_fp8(0, src, l.p, reinterpret_cast<float*>(reinterpret_cast<char*>(l.p) + n), (int64_t)l.N, l.K, s));
+    else HIP_TRY(launch_pack_conv_weights(h->cmode, src, l.p, l.N, l.K, 1, 0, s));
+    return FG_OK;
+}
+
 // fg_dit_pack_group's part: device storage on the first call, then the GEMM weights of the group's blocks
 int dit_pack(fg_dit* h, const ParamGroup& in_group, hipStream_t s) {
-    const char* e3 = getenv("FASTGEN_AMD_DIT_GEMM3");
-    const bool want3 = h->cmode == FG_DTYPE_BF16X3 && !(e3 && e3[0] == '0') && (h->D % 64) == 0 && (h->Hd % 64) == 0 && h->D >= 256;
-    // bytes per packed weight element: bf16 2; bf16x3 two bf16 planes = 4, or [hi | lo | hi] = 6 for the split-bf16 token GEMM
-    const size_t wsz = h->cmode == FG_DTYPE_BF16 ? 2 : (want3 ? 6 : 4);
-    const size_t D = h->D, Hd = h->Hd;
-    const char* e1 = getenv("FASTGEN_AMD_DIT_GEMM");
-    const bool want1 = h->cmode == FG_DTYPE_BF16 && (h->fp8 || !(e1 && e1[0] == '0')) && (D % 64) == 0 && (Hd % 64) == 0;  // (fp8: fg_dit_create has refused the switch)
+    const size_t D = h->D, depth = h->blocks.size();
     int rc;
     if (!h->device_ready) {
         // (before anything is allocated: a failure here leaves nothing behind for a second attempt to allocate again)
-        if (h->grid != 16 && !want1 && !want3)  // conv.hip's token modes are a 16 x 16 image by construction
+        if (h->grid != 16 && h->flavour == DIT_CONV)  // conv.hip's token modes are a 16 x 16 image by construction
             return fail(FG_EINVAL, "a %d x %d token grid runs on the token GEMM: FASTGEN_AMD_DIT_GEMM%s=0 excludes it", h->grid, h->grid,
                         h->cmode == FG_DTYPE_BF16X3 ? "3" : "");
-        if (h->fp8 && gemm_prepare(4) != 0) return fail(FG_EHIP, "hipFuncSetAttribute(dynamic LDS) failed");
-        for (fg_dit::Blk& b : h->blocks) {
-            if ((rc = h->alloc(&b.p_qkv, 3 * D * D * wsz)) || (rc = h->alloc(&b.p_proj, D * D * wsz)) ||
-                (rc = h->alloc(&b.p_fc1, Hd * D * wsz)) || (rc = h->alloc(&b.p_fc2, D * Hd * wsz)))
-                return rc;
-        }
+        if (h->flavour == DIT_FP8 && gemm_prepare(4) != 0) return fail(FG_EHIP, "hipFuncSetAttribute(dynamic LDS) failed");
+        // bytes per packed weight element: bf16 2 (the e4m3 bytes and their scales fit inside); bf16x3 two bf16 planes = 4, or
+        // [hi | lo | hi] = 6 for the split-bf16 token GEMM
+        const size_t wsz = h->cmode == FG_DTYPE_BF16 ? 2 : (h->flavour == DIT_X3 ? 6 : 4);
+        for (fg_dit::Blk& b : h->blocks)
+            for (fg_dit::Lin& l : b.lin)
+                if ((rc = h->alloc(&l.p, (size_t)l.N * l.K * wsz))) return rc;
         for (size_t i = 0; i < h->params.size(); ++i)
             if (!h->pack_only[i] && !h->is_logvar((int)i) && (rc = h->alloc((void**)&h->own[i], sizeof(float) * (size_t)h->params[i].numel))) return rc;
         if (conv_prepare_all(h->cmode) != 0) return fail(FG_EHIP, "hipFuncSetAttribute(dynamic LDS) failed");
         HIP_TRY(hipHostMalloc((void**)&h->err_host, sizeof(int), hipHostMallocMapped));
         *h->err_host = 0;
         HIP_TRY(hipHostGetDevicePointer((void**)&h->err_dev, h->err_host, 0));
-        h->gemm = want1;
-        h->gemm3 = want3;
-        if ((h->gemm || h->gemm3) && gemm_prepare(3) != 0) return fail(FG_EHIP, "hipFuncSetAttribute(dynamic LDS) failed");
-        if (h->gemm && ((rc = h->alloc(&h->p_modw, h->blocks.size() * 6 * D * D * 2)) || (rc = h->alloc((void**)&h->modb, h->blocks.size() * 6 * D * 4))))
-            return rc;
+        if (h->flavour != DIT_CONV && gemm_prepare(3) != 0) return fail(FG_EHIP, "hipFuncSetAttribute(dynamic LDS) failed");
+        if (h->bf16_gemm() && ((rc = h->alloc(&h->p_modw, depth * 6 * D * D * 2)) || (rc = h->alloc((void**)&h->modb, depth * 6 * D * 4)))) return rc;
         h->device_ready = true;
     }
-    size_t bi = 0;
-    for (fg_dit::Blk& b : h->blocks) {
-        const size_t me = bi++;
-        if (!in_group(h->params[b.qkv_w].name)) continue;  // (a block's parameters share their prefix: all of them in the group or none)
-        const float *qkv = h->params[b.qkv_w].ptr, *proj = h->params[b.proj_w].ptr, *fc1 = h->params[b.fc1_w].ptr, *fc2 = h->params[b.fc2_w].ptr;
-        if (h->gemm3) {
-            HIP_TRY(launch_split3_weights(qkv, b.p_qkv, (int)(3 * D), (int)D, s));
-            HIP_TRY(launch_split3_weights(proj, b.p_proj, (int)D, (int)D, s));
-            HIP_TRY(launch_split3_weights(fc1, b.p_fc1, (int)Hd, (int)D, s));
-            HIP_TRY(launch_split3_weights(fc2, b.p_fc2, (int)D, (int)Hd, s));
-        } else if (h->gemm) {
+    for (size_t me = 0; me < depth; ++me) {
+        const fg_dit::Blk& b = h->blocks[me];
+        if (!in_group(h->params[b.lin[DIT_QKV].w].name)) continue;  // (a block's parameters share their prefix: all of them in the group or none)
+        if (h->bf16_gemm()) {
             HIP_TRY(launch_cvt_bf16(h->params[b.mod_w].ptr, (__bf16*)h->p_modw + me * 6 * D * D, 6 * D * D, s));
             HIP_TRY(hipMemcpyAsync(h->modb + me * 6 * D, h->params[b.mod_b].ptr, 6 * D * 4, hipMemcpyDeviceToDevice, s));
-            if (h->fp8) {  // rows of W [N][K] quantised on the device: e4m3 bytes, then one scale per output channel (inside the bf16-sized allocation)
-                auto q8 = [&](const float* wsrc, void* dst, size_t N, size_t K) {
-                    return launch_quant_rows_fp8(0, wsrc, dst, reinterpret_cast<float*>(reinterpret_cast<char*>(dst) + N * K), (int64_t)N, (int)K, s);
-                };
-                HIP_TRY(q8(qkv, b.p_qkv, 3 * D, D));
-                HIP_TRY(q8(proj, b.p_proj, D, D));
-                HIP_TRY(q8(fc1, b.p_fc1, Hd, D));
-                HIP_TRY(q8(fc2, b.p_fc2, D, Hd));
-            } else {
-                HIP_TRY(launch_cvt_bf16(qkv, b.p_qkv, 3 * D * D, s));
-                HIP_TRY(launch_cvt_bf16(proj, b.p_proj, D * D, s));
-                HIP_TRY(launch_cvt_bf16(fc1, b.p_fc1, Hd * D, s));
-                HIP_TRY(launch_cvt_bf16(fc2, b.p_fc2, D * Hd, s));
-            }
-        } else {
-            HIP_TRY(launch_pack_conv_weights(h->cmode, qkv, b.p_qkv, 3 * h->D, h->D, 1, 0, s));
-            HIP_TRY(launch_pack_conv_weights(h->cmode, proj, b.p_proj, h->D, h->D, 1, 0, s));
-            HIP_TRY(launch_pack_conv_weights(h->cmode, fc1, b.p_fc1, h->Hd, h->D, 1, 0, s));
-            HIP_TRY(launch_pack_conv_weights(h->cmode, fc2, b.p_fc2, h->D, h->Hd, 1, 0, s));
         }
+        for (const fg_dit::Lin& l : b.lin)
+            if ((rc = dit_pack_linear(h, l, s))) return rc;
     }
     return FG_OK;
 }
@@ -467,8 +461,8 @@ int fg_dit_create(const fg_dit_config* cfg, fg_dit** out) {
         return fail(FG_EINVAL, "bad depth / mlp_hidden / in_channels / embedding_rows");
     fg_dit* h = new fg_dit();
     h->cfg = *cfg;
-    h->fp8 = cfg->compute_dtype == FG_DTYPE_FP8;
-    h->cmode = h->fp8 ? FG_DTYPE_BF16 : cfg->compute_dtype;  // (everything but the block linears is the bf16 mode's)
+    h->flavour = dit_flavour(cfg->compute_dtype);
+    h->cmode = h->flavour == DIT_FP8 ? FG_DTYPE_BF16 : cfg->compute_dtype;  // (everything but the block linears is the bf16 mode's)
     h->dtype = h->cmode == FG_DTYPE_BF16 ? 1 : 0;
     h->D = D, h->Hd = cfg->mlp_hidden, h->hd = hd, h->grid = grid, h->T = grid * grid;
     const int p = cfg->patch_size, C = cfg->in_channels, PO = p * p * C;
@@ -487,17 +481,19 @@ int fg_dit_create(const fg_dit_config* cfg, fg_dit** out) {
         h->rb2 = h->add("r_embedder.proj_net.2.bias", {D});
     }
     h->ytab = h->add("y_embedder.class_embeddings.weight", {cfg->embedding_rows, D});
+    const struct {
+        const char* name;
+        int N, K;
+    } lins[DIT_NLIN] = {{"attention.qkv", 3 * D, D}, {"attention.proj", D, D}, {"feed_forward.fc1", h->Hd, D}, {"feed_forward.fc2", D, h->Hd}};
     for (int i = 0; i < cfg->depth; ++i) {
         const std::string b = "blocks." + std::to_string(i) + ".";
         fg_dit::Blk k;
-        k.qkv_w = h->add(b + "attention.qkv.weight", {3 * D, D});
-        k.qkv_b = h->add(b + "attention.qkv.bias", {3 * D});
-        k.proj_w = h->add(b + "attention.proj.weight", {D, D});
-        k.proj_b = h->add(b + "attention.proj.bias", {D});
-        k.fc1_w = h->add(b + "feed_forward.fc1.weight", {h->Hd, D});
-        k.fc1_b = h->add(b + "feed_forward.fc1.bias", {h->Hd});
-        k.fc2_w = h->add(b + "feed_forward.fc2.weight", {D, h->Hd});
-        k.fc2_b = h->add(b + "feed_forward.fc2.bias", {D});
+        for (int l = 0; l < DIT_NLIN; ++l) {
+            fg_dit::Lin& n = k.lin[l];
+            n.N = lins[l].N, n.K = lins[l].K;
+            n.w = h->add(b + lins[l].name + ".weight", {n.N, n.K});
+            n.b = h->add(b + lins[l].name + ".bias", {n.N});
+        }
         k.mod_w = h->add(b + "conditioning_net.1.weight", {6 * D, D});
         k.mod_b = h->add(b + "conditioning_net.1.bias", {6 * D});
         h->blocks.push_back(k);
@@ -511,7 +507,8 @@ int fg_dit_create(const fg_dit_config* cfg, fg_dit** out) {
     h->own.assign(h->params.size(), nullptr);
     h->pack_only.assign(h->params.size(), 0);
     h->dirty.assign(h->params.size(), 1);
-    for (const fg_dit::Blk& k : h->blocks) h->pack_only[k.qkv_w] = h->pack_only[k.proj_w] = h->pack_only[k.fc1_w] = h->pack_only[k.fc2_w] = 1;
+    for (const fg_dit::Blk& k : h->blocks)
+        for (const fg_dit::Lin& l : k.lin) h->pack_only[l.w] = 1;
     *out = h;
     return FG_OK;
 }
@@ -572,11 +569,9 @@ int fg_dit_forward_features(fg_dit* h, const float* x_t, const float* t, const f
     if (h->take_error())
         return fail(FG_EINVAL, "an earlier call on this handle met a class index outside the %d rows of y_embedder.class_embeddings (its output is NaN)",
                     h->cfg.embedding_rows);
-    Arena A;
-    A.base = (char*)workspace;
     DitWs w;
-    const size_t need = dit_plan(h, batch, A, w);
-    if (need > workspace_bytes) return fail(FG_ENOMEM, "workspace too small: need %zu bytes for batch %d, got %zu", need, batch, workspace_bytes);
+    const int rc = setup_ws(dit_plan, h, batch, workspace, workspace_bytes, w);  // (its own argument checks have passed above; FG_ENOMEM is left)
+    if (rc) return rc;
     return dit_forward(h, x_t, t, r, class_ids, out, cond_out, batch, w, (hipStream_t)stream, feature_blocks, features, num_features, out == nullptr);
 }
 
@@ -609,15 +604,13 @@ int fg_dit_jvp(fg_dit* h, const float* x_t, const float* t, const float* r, cons
             return fail(FG_EINVAL, "fg_dit_jvp: out / jvp must not alias an input or the workspace");
     if (overlap(out, img, jvp, img)) return fail(FG_EINVAL, "fg_dit_jvp: out and jvp must not alias each other");
     if (!h->packed) return fail(FG_ENOTREADY, "weights are not packed (call fg_dit_pack_weights)");
-    if (!h->gemm3) return fail(FG_EINVAL, "fg_dit_jvp: the jvp runs on the split-bf16 token GEMM: FASTGEN_AMD_DIT_GEMM3=0 excludes it");
+    if (h->flavour != DIT_X3) return fail(FG_EINVAL, "fg_dit_jvp: the jvp runs on the split-bf16 token GEMM: FASTGEN_AMD_DIT_GEMM3=0 excludes it");
     if (h->take_error())
         return fail(FG_EINVAL, "an earlier call on this handle met a class index outside the %d rows of y_embedder.class_embeddings (its output is NaN)",
                     h->cfg.embedding_rows);
-    Arena A;
-    A.base = (char*)workspace;
     DitJvpWs w;
-    const size_t need = dit_jvp_plan(h, batch, A, w);
-    if (need > workspace_bytes) return fail(FG_ENOMEM, "fg_dit_jvp: workspace too small: need %zu bytes for batch %d, got %zu", need, batch, workspace_bytes);
+    const int rc = setup_ws(dit_jvp_plan, h, batch, workspace, workspace_bytes, w);  // (as in fg_dit_forward_features)
+    if (rc) return rc;
     return dit_jvp(h, x_t, t, r, class_ids, vx, vt, vr, out, jvp, batch, w, (hipStream_t)stream);
 }
 

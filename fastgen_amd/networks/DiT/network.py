@@ -168,6 +168,13 @@ class DiT(FastGenNetwork):
             pack_group=lambda pre, exc: _lib.check(L.fg_dit_pack_group(h, pre.encode(), exc.encode() if exc else None, stream)))
         return dt, h
 
+    def _workspace(self, dt: int, need: int, device) -> torch.Tensor:
+        """The cached workspace of compute mode `dt`, grown to `need` bytes (forward, jvp and the fused loops share it)."""
+        ws = self._ws.get(dt)
+        if ws is None or ws.numel() < need or ws.device != device:
+            ws = self._ws[dt] = torch.empty(need, dtype=torch.uint8, device=device)
+        return ws
+
     def fully_shard(self, **kwargs):
         """FSDP2 with the reference's grouping (DiT/network.py:402-420): one parameter group per transformer block, one each for the
         patch / time / class (/ r) embedders and the output layer; `pos_embed` and `logvar_linear` stay whole on the root, as there.
@@ -246,10 +253,7 @@ class DiT(FastGenNetwork):
         r_e = r_e.contiguous() if r_e is not None else None
         dt, h = self._engine(dev)
         L = _lib.lib()
-        need = L.fg_dit_workspace_bytes(h, B)
-        ws = self._ws.get(dt)
-        if ws is None or ws.numel() < need or ws.device != dev:
-            ws = self._ws[dt] = torch.empty(need, dtype=torch.uint8, device=dev)
+        ws = self._workspace(dt, L.fg_dit_workspace_bytes(h, B), dev)
         # block-output taps (:536-543): token tensors [B, T, D] behind the requested blocks; with return_features_early the call
         # stops at the last of them (no requested index: after the first block, an empty list - as the reference's loop does)
         depth = self._cfg.depth
@@ -330,9 +334,7 @@ class DiT(FastGenNetwork):
         need = L.fg_dit_jvp_workspace_bytes(h, B)
         if need == 0:
             raise NotImplementedError("fastgen_amd.DiT.jvp: this compute mode / token grid has no jvp (bf16x3, 256 tokens)")
-        ws = self._ws.get(dt)
-        if ws is None or ws.numel() < need or ws.device != dev:
-            ws = self._ws[dt] = torch.empty(need, dtype=torch.uint8, device=dev)
+        ws = self._workspace(dt, need, dev)
         out, jv = torch.empty_like(x32), torch.empty_like(x32)
         _lib.check(L.fg_dit_jvp(h, p(x32), p(t_e), p(r_e), p(cls), p(vx), p(vt_e), p(vr_e), p(out), p(jv), B, ctypes.c_void_p(ws.data_ptr()),
                                 ws.numel(), ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
@@ -391,10 +393,7 @@ class DiT(FastGenNetwork):
         sc.schedule = _lib.FG_SCHEDULE_RF if rf else _lib.FG_SCHEDULE_EDM
         dt, h = self._engine(dev)
         L = _lib.lib()
-        need = L.fg_dit_sampler_workspace_bytes(h, B, int(neg is not None))
-        ws = self._ws.get(dt)
-        if ws is None or ws.numel() < need or ws.device != dev:
-            ws = self._ws[dt] = torch.empty(need, dtype=torch.uint8, device=dev)
+        ws = self._workspace(dt, L.fg_dit_sampler_workspace_bytes(h, B, int(neg is not None)), dev)
         out = torch.empty_like(n32)
         self._keep = (n32, cls, neg, eps, out)  # graph replays read these buffers; keep them alive
         p = lambda a: ctypes.c_void_p(a.data_ptr() if a is not None and a.numel() else None)  # noqa: E731
