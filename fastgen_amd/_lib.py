@@ -51,7 +51,7 @@ class fg_dit_config(ctypes.Structure):
 class fg_wan_config(ctypes.Structure):
     _fields_ = [("num_heads", c_int), ("head_dim", c_int), ("in_channels", c_int), ("out_channels", c_int), ("text_dim", c_int),
                 ("freq_dim", c_int), ("ffn_dim", c_int), ("num_layers", c_int), ("rope_max_seq_len", c_int), ("chunk_size", c_int),
-                ("total_num_frames", c_int), ("eps", c_float)]
+                ("total_num_frames", c_int), ("eps", c_float), ("compute_dtype", c_int)]
 
 
 class fg_wan_block_taps(ctypes.Structure):

@@ -715,6 +715,11 @@ int launch_dit_ln_modulate_fp8(int D, const void* x, const float* mod, int mod_s
         case 768: LN8(768); break;
         case 1024: LN8(1024); break;
         case 1152: LN8(1152); break;
+        // the causal video DiT's widths (engine_wan.inc)
+        case 256: LN8(256); break;
+        case 1536: LN8(1536); break;
+        case 2048: LN8(2048); break;
+        case 5120: LN8(5120); break;
         default: return (int)hipErrorInvalidValue;
     }
 #undef LN8

@@ -1781,7 +1781,8 @@ int fg_op_gemm_fp8(const void* a, const void* w, const float* bias, void* out, i
 int fg_op_dit_ln_modulate_fp8(const void* x, const float* mod, int mod_stride, int shift_off, int scale_off, void* y, float* y_scale, int ntok,
                               int d, int tokens_per_image, void* stream) {
     if (!x || !mod || !y || !y_scale || ntok <= 0 || tokens_per_image <= 0) return fail(FG_EINVAL, "fg_op_dit_ln_modulate_fp8: bad argument");
-    if (d != 384 && d != 768 && d != 1024 && d != 1152) return fail(FG_EINVAL, "fg_op_dit_ln_modulate_fp8: d %d unsupported (384, 768, 1024, 1152)", d);
+    if (d != 384 && d != 768 && d != 1024 && d != 1152 && d != 256 && d != 1536 && d != 2048 && d != 5120)
+        return fail(FG_EINVAL, "fg_op_dit_ln_modulate_fp8: d %d unsupported (384, 768, 1024, 1152; the video DiT's 256, 1536, 2048, 5120)", d);
     if ((mod_stride % 4) || (shift_off % 4) || (scale_off % 4) || shift_off < 0 || scale_off < 0)
         return fail(FG_EINVAL, "fg_op_dit_ln_modulate_fp8: mod_stride / shift_off / scale_off must be multiples of 4");
     HIP_TRY(launch_dit_ln_modulate_fp8(d, x, mod, mod_stride, shift_off, scale_off, y, y_scale, ntok, tokens_per_image, (hipStream_t)stream));

@@ -1,5 +1,5 @@
 // Causal video DiT engine (SURVEY 8(f)3 / CausVid row of 8(a)): parameter plan with the state-dict names of the reference's
-// CausalWan (`transformer.` + diffusers' WanTransformer3DModel keys), bf16 weight copies, per-handle KV caches, forward
+// CausalWan (`transformer.` + diffusers' WanTransformer3DModel keys), bf16 (fp8 mode: e4m3) weight copies, per-handle KV caches, forward
 // orchestration and the C ABI of include/fastgen_amd.h (fg_wan_*).  Textually included by engine.hip inside its `extern "C"` region
 // (the handle is a HandleBase; pack_group is engine.hip's).
 // Reference: fastgen/networks/Wan/network_causal.py:467-550 (block), :568-705 (prepare), :815-913 (block loop, cache positions),
@@ -9,11 +9,15 @@
 struct fg_wan : HandleBase {
     fg_wan_config cfg;
     int D = 0, Fd = 0, H = 0;
+    // FG_DTYPE_FP8: the six linears of a block that read the video tokens (p_qkv, p_o, p_q2, p_o2, p_f0, p_f2) hold [N][K] e4m3fn bytes
+    // followed by the N fp32 channel scales instead of bf16 (inside the same allocation), and their A operands are quantised per
+    // token (wan_modulate / wan_stage); wan_gemm is the one place that launches either.  The text side (p_x1, p_x2, p_kv2) stays bf16.
+    bool fp8 = false;
     struct Blk {
         int sst, q_w, q_b, k_w, k_b, v_w, v_b, o_w, o_b, nq, nk;          // attn1
         int q2_w, q2_b, k2_w, k2_b, v2_w, v2_b, o2_w, o2_b, nq2, nk2;      // attn2
         int n2_w, n2_b, f0_w, f0_b, f2_w, f2_b;
-        void *p_qkv = nullptr, *p_o = nullptr, *p_q2 = nullptr, *p_kv2 = nullptr, *p_o2 = nullptr, *p_f0 = nullptr, *p_f2 = nullptr;  // bf16 [N][K]
+        void *p_qkv = nullptr, *p_o = nullptr, *p_q2 = nullptr, *p_kv2 = nullptr, *p_o2 = nullptr, *p_f0 = nullptr, *p_f2 = nullptr;  // bf16 [N][K] (fp8: above)
         float *b_qkv = nullptr, *b_kv2 = nullptr, *n2mod = nullptr;  // fused biases; norm2 as {shift = bias, scale = weight - 1}
         void *kc = nullptr, *vc = nullptr;   // self-attention cache [B][cap][D] bf16
         void* kv2 = nullptr;                 // cross-attention cache [B][Lt][2 D] bf16 (k normalised | v)
@@ -63,6 +67,8 @@ struct WanWs {
     void *kf, *vf;  // K / V of all frames in the block-causal (teacher-forcing) call: they stay out of the caches
     float* gs;  // split-K scratch of the token GEMMs (short grids: one sample's chunk)
     size_t gs_bytes;
+    void *y8, *hid8;  // fp8 mode: the quantised A operands [M][D] (LayerNorm-modulate and attention outputs) / [M][ffn] (GELU hidden) ...
+    float *ys, *hs;   // ... and their per-token scales [M]
 };
 
 size_t wan_plan(const fg_wan* h, int B, int Fr, int gh, int gw, Arena& A, WanWs& w) {
@@ -90,17 +96,74 @@ size_t wan_plan(const fg_wan* h, int B, int Fr, int gh, int gw, Arena& A, WanWs&
         w.kf = A.take(M * D * 2);
         w.vf = A.take(M * D * 2);
     }
+    // (behind everything else, and nothing in the bf16 mode: that mode's plan and its size are what they were)
+    w.y8 = A.take(h->fp8 ? M * D : 0);
+    w.hid8 = A.take(h->fp8 ? M * (size_t)h->Fd : 0);
+    w.ys = A.get<float>(h->fp8 ? M : 0);
+    w.hs = A.get<float>(h->fp8 ? M : 0);
     return (A.off + 255) & ~(size_t)255;
 }
 
-int wan_gemm(const void* a, const void* w, const float* bias, void* out, int M, int N, int K, hipStream_t s, int act = 0, const float* gate = nullptr,
+// A block linear's input: bf16 tokens (scale == nullptr), or e4m3 bytes with their per-token scales (fp8 mode)
+struct WanOperand {
+    const void* p = nullptr;
+    const float* scale = nullptr;
+};
+
+// The one linear dispatch: out = resid + gate * act(a W^T + bias).  An operand that carries scales runs on the e4m3 flavour of the
+// token GEMM, W then being [N][K] e4m3fn bytes with the N channel scales behind them (wan_pack_linear); any other on the bf16 one.
+int wan_gemm(WanOperand a, const void* w, const float* bias, void* out, int M, int N, int K, hipStream_t s, int act = 0, const float* gate = nullptr,
              int gate_stride = 0, int gate_rows = 1, const void* resid = nullptr, float* scratch = nullptr, size_t scratch_bytes = 0) {
     GemmArgs g;
     g.scratch = scratch; g.scratch_bytes = scratch_bytes;
-    g.A = a; g.W = w; g.bias = bias; g.out = out; g.M = M; g.N = N; g.K = K; g.act = act;
+    g.A = a.p; g.W = w; g.bias = bias; g.out = out; g.M = M; g.N = N; g.K = K; g.act = act;
     g.gate = gate; g.gate_stride = gate_stride; g.gate_rows = gate_rows; g.resid = resid;
+    if (a.scale) {  // (no split-K in this flavour: the scratch goes unused)
+        g.a_scale = a.scale;
+        g.w_scale = reinterpret_cast<const float*>(static_cast<const char*>(w) + (size_t)N * K);
+        if (!gemm_fp8_supported(g)) return fail(FG_EINVAL, "fp8 token GEMM %d x %d x %d unsupported (k %% 128, n %% 16)", M, N, K);
+        HIP_TRY(launch_gemm_fp8(g, s));
+        return FG_OK;
+    }
     if (!gemm_bf16_supported(g)) return fail(FG_EINVAL, "token GEMM %d x %d x %d unsupported (k %% 64, n %% 16)", M, N, K);
     HIP_TRY(launch_gemm_bf16(g, s));
+    return FG_OK;
+}
+
+// LayerNorm-modulate of the stream x as the mode's operand: y = LN(x) (1 + mod[scale_off ...]) + mod[shift_off ...], one modulation
+// row per tpi tokens
+int wan_modulate(const fg_wan* h, const void* x, const float* mod, int mstride, int shift_off, int scale_off, int M, int tpi, WanWs& w,
+                 hipStream_t s, WanOperand& y) {
+    if (h->fp8) {
+        y = WanOperand{w.y8, w.ys};
+        HIP_TRY(launch_dit_ln_modulate_fp8(h->D, x, mod, mstride, shift_off, scale_off, w.y8, w.ys, M, tpi, s));
+    } else {
+        y = WanOperand{w.y, nullptr};
+        HIP_TRY(launch_dit_ln_modulate(1, h->D, x, mod, mstride, shift_off, scale_off, w.y, M, tpi, s));
+    }
+    return FG_OK;
+}
+
+// A bf16 token tensor [M][K] that a kernel left behind (an attention output, the GELU hidden) as the mode's operand: as it is, or
+// quantised into q8 / scale (its rows cross the producing kernel's tiles, so the quantiser is a pass of its own, as in the DiT)
+int wan_stage(const fg_wan* h, const void* src, int K, void* q8, float* scale, int M, hipStream_t s, WanOperand& a) {
+    a = WanOperand{src, nullptr};
+    if (h->fp8) {
+        HIP_TRY(launch_quant_rows_fp8(1, src, q8, scale, M, K, s));
+        a = WanOperand{q8, scale};
+    }
+    return FG_OK;
+}
+
+// A block linear's fp32 weight src [N][K] into rows [row0, row0 + N) of the packed [Ntot][K] matrix dst (the fused qkv weight takes
+// three) in the mode's layout.  fp8: rows quantised on the device, the Ntot channel scales behind the Ntot K bytes.
+int wan_pack_linear(const fg_wan* h, const float* src, void* dst, size_t row0, size_t Ntot, size_t N, size_t K, hipStream_t s) {
+    if (h->fp8) {
+        char* q = static_cast<char*>(dst);
+        HIP_TRY(launch_quant_rows_fp8(0, src, q + row0 * K, reinterpret_cast<float*>(q + Ntot * K) + row0, (int64_t)N, (int)K, s));
+    } else {
+        HIP_TRY(launch_cvt_bf16(src, static_cast<__bf16*>(dst) + row0 * K, N * K, s));
+    }
     return FG_OK;
 }
 
@@ -155,7 +218,8 @@ int wan_pack(fg_wan* h, const ParamGroup& in_group, hipStream_t s) {
         for (size_t i = 0; i < h->params.size(); ++i)
             if (!h->pack_only[i] && !h->is_logvar((int)i) && (rc = h->alloc((void**)&h->own[i], sizeof(float) * (size_t)h->params[i].numel))) return rc;
         if ((rc = wan_build_rope(h))) return rc;
-        if (gemm_prepare(1) != 0) return fail(FG_EHIP, "hipFuncSetAttribute(dynamic LDS) failed");
+        // (here, at pack time: never inside a sampler's graph capture; the text side runs the bf16 kernels in every mode)
+        if (gemm_prepare(h->fp8 ? 1 | 4 : 1) != 0) return fail(FG_EHIP, "hipFuncSetAttribute(dynamic LDS) failed");
         h->device_ready = true;
     }
     auto raw = [&](int idx) { return h->params[idx].ptr; };
@@ -166,18 +230,16 @@ int wan_pack(fg_wan* h, const ParamGroup& in_group, hipStream_t s) {
     const int g1 = (int)((D + 255) / 256);
     for (fg_wan::Blk& b : h->blocks) {
         if (!in_group(h->params[b.q_w].name)) continue;  // (a block's parameters share their prefix: all of them in the group or none)
-        __bf16* qkv = (__bf16*)b.p_qkv;
-        HIP_TRY(launch_cvt_bf16(raw(b.q_w), qkv, D * D, s));
-        HIP_TRY(launch_cvt_bf16(raw(b.k_w), qkv + D * D, D * D, s));
-        HIP_TRY(launch_cvt_bf16(raw(b.v_w), qkv + 2 * D * D, D * D, s));
-        HIP_TRY(launch_cvt_bf16(raw(b.o_w), b.p_o, D * D, s));
-        HIP_TRY(launch_cvt_bf16(raw(b.q2_w), b.p_q2, D * D, s));
-        __bf16* kv2 = (__bf16*)b.p_kv2;
+        const auto lin = [&](int idx, void* dst, size_t row0, size_t Ntot, size_t N, size_t K) {
+            return wan_pack_linear(h, raw(idx), dst, row0, Ntot, N, K, s);
+        };
+        if ((rc = lin(b.q_w, b.p_qkv, 0, 3 * D, D, D)) || (rc = lin(b.k_w, b.p_qkv, D, 3 * D, D, D)) || (rc = lin(b.v_w, b.p_qkv, 2 * D, 3 * D, D, D)) ||
+            (rc = lin(b.o_w, b.p_o, 0, D, D, D)) || (rc = lin(b.q2_w, b.p_q2, 0, D, D, D)) || (rc = lin(b.o2_w, b.p_o2, 0, D, D, D)) ||
+            (rc = lin(b.f0_w, b.p_f0, 0, Fd, Fd, D)) || (rc = lin(b.f2_w, b.p_f2, 0, D, D, Fd)))
+            return rc;
+        __bf16* kv2 = (__bf16*)b.p_kv2;  // the text side: bf16 in every mode
         HIP_TRY(launch_cvt_bf16(raw(b.k2_w), kv2, D * D, s));
         HIP_TRY(launch_cvt_bf16(raw(b.v2_w), kv2 + D * D, D * D, s));
-        HIP_TRY(launch_cvt_bf16(raw(b.o2_w), b.p_o2, D * D, s));
-        HIP_TRY(launch_cvt_bf16(raw(b.f0_w), b.p_f0, Fd * D, s));
-        HIP_TRY(launch_cvt_bf16(raw(b.f2_w), b.p_f2, D * Fd, s));
         hipLaunchKernelGGL(wan_cat_kernel, dim3(g1), dim3(256), 0, s, raw(b.q_b), raw(b.k_b), raw(b.v_b), b.b_qkv, (int)D);
         hipLaunchKernelGGL(wan_cat_kernel, dim3(g1), dim3(256), 0, s, raw(b.k2_b), raw(b.v2_b), (const float*)nullptr, b.b_kv2, (int)D);
         hipLaunchKernelGGL(wan_n2mod_kernel, dim3(g1), dim3(256), 0, s, raw(b.n2_w), raw(b.n2_b), b.n2mod, (int)D);
@@ -200,7 +262,13 @@ int fg_wan_create(const fg_wan_config* cfg, fg_wan** out) {
         (cfg->ffn_dim % 64) || (cfg->text_dim % 64) || cfg->freq_dim != 256 || cfg->rope_max_seq_len <= 0 || cfg->chunk_size <= 0 ||
         cfg->total_num_frames <= 0)
         return fail(FG_EINVAL, "bad channels / depth / ffn_dim / text_dim / freq_dim");
+    if (cfg->compute_dtype != 0 && cfg->compute_dtype != FG_DTYPE_BF16 && cfg->compute_dtype != FG_DTYPE_FP8)
+        return fail(FG_EINVAL, "compute_dtype %d unsupported (0 / FG_DTYPE_BF16, FG_DTYPE_FP8)", cfg->compute_dtype);
+    const bool fp8 = cfg->compute_dtype == FG_DTYPE_FP8;
+    if (fp8 && (cfg->ffn_dim % 128))  // (every supported inner dim is a multiple already)
+        return fail(FG_EINVAL, "fp8 mode: ffn_dim %d must be a multiple of 128 (the K-step of the e4m3 MFMA)", cfg->ffn_dim);
     fg_wan* h = new fg_wan();
+    h->fp8 = fp8;
     h->name_prefix = "transformer.";
     h->cfg = *cfg;
     h->D = D, h->Fd = cfg->ffn_dim, h->H = cfg->num_heads;
@@ -371,10 +439,11 @@ int fg_wan_set_text(fg_wan* h, const float* text, int batch, int text_len, void*
     // text_embedder: Linear - GELU(tanh) - Linear (PixArtAlphaTextProjection); then per block k = norm_k(to_k(ctx)), v = to_v(ctx)
     HIP_TRY(launch_cvt_rows_bf16(text, tb, (int64_t)(M * Td), s));
     int rc;
-    if ((rc = wan_gemm(tb, h->p_x1, h->P(h->x1_b), e1, (int)M, (int)D, (int)Td, s, 1))) return rc;
-    if ((rc = wan_gemm(e1, h->p_x2, h->P(h->x2_b), e2, (int)M, (int)D, (int)D, s))) return rc;
+    // (bf16 operands in every mode: this runs once per text)
+    if ((rc = wan_gemm(WanOperand{tb}, h->p_x1, h->P(h->x1_b), e1, (int)M, (int)D, (int)Td, s, 1))) return rc;
+    if ((rc = wan_gemm(WanOperand{e1}, h->p_x2, h->P(h->x2_b), e2, (int)M, (int)D, (int)D, s))) return rc;
     for (fg_wan::Blk& b : h->blocks) {
-        if ((rc = wan_gemm(e2, b.p_kv2, b.b_kv2, b.kv2, (int)M, (int)(2 * D), (int)D, s))) return rc;
+        if ((rc = wan_gemm(WanOperand{e2}, b.p_kv2, b.b_kv2, b.kv2, (int)M, (int)(2 * D), (int)D, s))) return rc;
         HIP_TRY(launch_rms_rope((int)D, b.kv2, (int)(2 * D), h->P(b.nk2), h->cfg.eps, nullptr, b.kv2, (int64_t)text_len * 2 * D, 0, (int)(2 * D),
                                 (int)M, text_len, s));
     }
@@ -467,8 +536,8 @@ int wan_forward(fg_wan* h, const float* x_t, const float* t_frames, float* out, 
         HIP_TRY(launch_wan_mod(h->P(b.sst), w.tproj, w.mod, BF, 6, D, s));
         // 1. self-attention over the cached frames and this chunk.  K / V of the chunk go to their cache rows in every call (a call
         // with store_kv = 0 leaves rows that the chunk's store_kv = 1 call rewrites; the reference's cache length only moves there)
-        HIP_TRY(launch_dit_ln_modulate(1, D, x, w.mod, 6 * D, 0, D, w.y, M, fs, s));
-        if ((rc = wan_gemm(w.y, b.p_qkv, b.b_qkv, w.qkv, M, 3 * D, D, s))) return rc;
+        WanOperand a;  // the operand the next linear reads
+        if ((rc = wan_modulate(h, x, w.mod, 6 * D, 0, D, M, fs, w, s, a)) || (rc = wan_gemm(a, b.p_qkv, b.b_qkv, w.qkv, M, 3 * D, D, s))) return rc;
         const __bf16* qkv = (const __bf16*)w.qkv;
         HIP_TRY(launch_rms_rope(D, qkv, 3 * D, h->P(b.nq), c.eps, w.cs, w.qn, (int64_t)L * D, 0, D, M, L, s));
         if (block_causal) {
@@ -491,24 +560,31 @@ int wan_forward(fg_wan* h, const float* x_t, const float* t_frames, float* out, 
             HIP_TRY(launch_fa128(w.qn, D, (int64_t)L * D, b.kc, b.vc, D, cbs, w.att, D, (int64_t)L * D, batch, h->H, L, cache_start + L, s, w.fa));
         }
         if (bt && bt->attn1) HIP_TRY(launch_from_act(1, w.att, bt->attn1, MD, s));
-        if ((rc = wan_gemm(w.att, b.p_o, h->P(b.o_b), xn, M, D, D, s, 0, w.mod + 2 * D, 6 * D, fs, x, w.gs, w.gs_bytes))) return rc;
+        if ((rc = wan_stage(h, w.att, D, w.y8, w.ys, M, s, a)) ||
+            (rc = wan_gemm(a, b.p_o, h->P(b.o_b), xn, M, D, D, s, 0, w.mod + 2 * D, 6 * D, fs, x, w.gs, w.gs_bytes)))
+            return rc;
         std::swap(x, xn);
         if (bt && bt->x_attn1) HIP_TRY(launch_from_act(1, x, bt->x_attn1, MD, s));
         // 2. cross-attention to the text
-        HIP_TRY(launch_dit_ln_modulate(1, D, x, b.n2mod, 0, 0, D, w.y, M, M, s));
-        if ((rc = wan_gemm(w.y, b.p_q2, h->P(b.q2_b), w.qkv, M, D, D, s, 0, nullptr, 0, 1, nullptr, w.gs, w.gs_bytes))) return rc;
+        if ((rc = wan_modulate(h, x, b.n2mod, 0, 0, D, M, M, w, s, a)) ||
+            (rc = wan_gemm(a, b.p_q2, h->P(b.q2_b), w.qkv, M, D, D, s, 0, nullptr, 0, 1, nullptr, w.gs, w.gs_bytes)))
+            return rc;
         HIP_TRY(launch_rms_rope(D, w.qkv, D, h->P(b.nq2), c.eps, nullptr, w.qn, (int64_t)L * D, 0, D, M, L, s));
         const int64_t tbs = (int64_t)h->text_L * 2 * D;
         HIP_TRY(launch_fa128(w.qn, D, (int64_t)L * D, b.kv2, (const __bf16*)b.kv2 + D, 2 * D, tbs, w.att, D, (int64_t)L * D, batch, h->H, L,
                              h->text_L, s, w.fa));
         if (bt && bt->attn2) HIP_TRY(launch_from_act(1, w.att, bt->attn2, MD, s));
-        if ((rc = wan_gemm(w.att, b.p_o2, h->P(b.o2_b), xn, M, D, D, s, 0, nullptr, 0, 1, x, w.gs, w.gs_bytes))) return rc;
+        if ((rc = wan_stage(h, w.att, D, w.y8, w.ys, M, s, a)) ||
+            (rc = wan_gemm(a, b.p_o2, h->P(b.o2_b), xn, M, D, D, s, 0, nullptr, 0, 1, x, w.gs, w.gs_bytes)))
+            return rc;
         std::swap(x, xn);
         if (bt && bt->x_attn2) HIP_TRY(launch_from_act(1, x, bt->x_attn2, MD, s));
         // 3. feed-forward
-        HIP_TRY(launch_dit_ln_modulate(1, D, x, w.mod, 6 * D, 3 * D, 4 * D, w.y, M, fs, s));
-        if ((rc = wan_gemm(w.y, b.p_f0, h->P(b.f0_b), w.hid, M, h->Fd, D, s, 1))) return rc;
-        if ((rc = wan_gemm(w.hid, b.p_f2, h->P(b.f2_b), xn, M, D, h->Fd, s, 0, w.mod + 5 * D, 6 * D, fs, x, w.gs, w.gs_bytes))) return rc;
+        if ((rc = wan_modulate(h, x, w.mod, 6 * D, 3 * D, 4 * D, M, fs, w, s, a)) || (rc = wan_gemm(a, b.p_f0, h->P(b.f0_b), w.hid, M, h->Fd, D, s, 1)))
+            return rc;
+        if ((rc = wan_stage(h, w.hid, h->Fd, w.hid8, w.hs, M, s, a)) ||
+            (rc = wan_gemm(a, b.p_f2, h->P(b.f2_b), xn, M, D, h->Fd, s, 0, w.mod + 5 * D, 6 * D, fs, x, w.gs, w.gs_bytes)))
+            return rc;
         std::swap(x, xn);
         if (bt && bt->x_ffn) HIP_TRY(launch_from_act(1, x, bt->x_ffn, MD, s));
     }

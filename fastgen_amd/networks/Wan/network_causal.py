@@ -14,6 +14,10 @@ guided teacher sampler `sample` (classifier-free guidance over the stacked batch
 (`is_ar=False`: block-wise causal mask, per-frame timesteps [B, F]), and the whole chunk-by-chunk student loop as one library call
 replayed as per-chunk hipGraphs (`student_sample` -> `fg_wan_sampler_run`; CausVidModel / SelfForcingModel call it).  Raises (never falls back): autograd,
 feature taps, r / image conditioning, `is_ar=False` on fewer frames, any device but a HIP GPU.
+
+`compute_dtype="fp8"` (keyword only; default None = "bf16"): the six linears of every block that read the video tokens contract e4m3fn
+operands - weights quantised per output channel at every pack, activations per token - through every call above; the text side, the
+embedders, attention and the caches stay bf16.  What it costs and buys: DESIGN.md, section 10.
 """
 from __future__ import annotations
 
@@ -35,7 +39,14 @@ class CausalWan(FastGenNetwork):
     def __init__(self, num_attention_heads: int = 12, attention_head_dim: int = 128, in_channels: int = 16, out_channels: int = 16,
                  text_dim: int = 4096, freq_dim: int = 256, ffn_dim: int = 8960, num_layers: int = 30, eps: float = 1e-6,
                  rope_max_seq_len: int = 1024, r_timestep: bool = False, net_pred_type: str = "flow", schedule_type: str = "rf",
-                 chunk_size: int = 3, total_num_frames: int = 21, enable_logvar_linear: bool = True, **model_kwargs):
+                 chunk_size: int = 3, total_num_frames: int = 21, enable_logvar_linear: bool = True, *,
+                 compute_dtype: Optional[str] = None, **model_kwargs):
+        # compute_dtype: None / "bf16" - every GEMM on bf16 operands; "fp8" - the six linears of a block that read the video tokens on
+        # e4m3fn operands (include/fastgen_amd.h, fg_wan_config).  Fixed at construction; the state dict (fp32 masters) is the same.
+        if compute_dtype not in (None, "bf16", "fp8"):
+            raise ValueError(f"compute_dtype must be None, 'bf16' or 'fp8' for the causal video DiT, got {compute_dtype!r}")
+        if compute_dtype == "fp8" and ffn_dim % 128:
+            raise ValueError(f"compute_dtype='fp8' needs ffn_dim to be a multiple of 128 (the K-step of the e4m3 MFMA), got {ffn_dim}")
         for k in ("model_id_or_local_path", "load_pretrained", "disable_efficient_attn", "disable_grad_ckpt", "use_fsdp_checkpoint",
                   "r_embedder_init", "time_cond_type", "norm_temb", "encoder_depth", "delete_cache_on_clear"):
             v = model_kwargs.pop(k, None)  # reference knobs without meaning here (hub ids, autograd plumbing) ...
@@ -46,8 +57,9 @@ class CausalWan(FastGenNetwork):
         super().__init__(net_pred_type=net_pred_type, schedule_type=schedule_type, **model_kwargs)
         if r_timestep:
             raise NotImplementedError("r_timestep=True (a second time embedder) is not implemented for the causal video DiT path")
-        self.chunk_size, self.total_num_frames = chunk_size, total_num_frames
+        self.chunk_size, self.total_num_frames, self.compute_dtype = chunk_size, total_num_frames, compute_dtype
         cfg = _lib.fg_wan_config()
+        cfg.compute_dtype = _lib.DTYPE_NAMES[compute_dtype or "bf16"]
         cfg.num_heads, cfg.head_dim, cfg.in_channels, cfg.out_channels = num_attention_heads, attention_head_dim, in_channels, out_channels
         cfg.text_dim, cfg.freq_dim, cfg.ffn_dim, cfg.num_layers = text_dim, freq_dim, ffn_dim, num_layers
         cfg.rope_max_seq_len, cfg.chunk_size, cfg.total_num_frames, cfg.eps = rope_max_seq_len, chunk_size, total_num_frames, eps

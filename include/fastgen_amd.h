@@ -45,11 +45,11 @@ extern "C" {
  * activations, statistics, attention, embedding MLP and preconditioning exactly as FG_DTYPE_F32.  Three bf16 MFMAs per product:
  * roofline 2.5 PFLOP/s / 3, against 157 TFLOP/s for FG_DTYPE_F32. */
 #define FG_DTYPE_BF16X3 2
-/* fp8 (DiT only): the four linears of every transformer block contract OCP e4m3fn operands (W8A8, v_mfma_scale_f32_16x16x128_f8f6f4
- * with unit block scales, fp32 accumulate): weights quantised per output channel at pack time, activations per token on every call
- * (scale = amax / 448, q = RNE(clamp(x * (448 / amax), -448, 448))); everything else - token tensors, attention, embeddings, the
- * modulation GEMM, the final layer - exactly as FG_DTYPE_BF16.  hidden_size and mlp_hidden must be multiples of 128.  Roofline
- * 5 PFLOP/s.  The EDM / EDM2 / ADM handles refuse it. */
+/* fp8 (the DiT and the causal video DiT): the linears of every transformer block - the DiT's four, the video DiT's six (fg_wan_config)
+ * - contract OCP e4m3fn operands (W8A8, v_mfma_scale_f32_16x16x128_f8f6f4 with unit block scales, fp32 accumulate): weights quantised
+ * per output channel at pack time, activations per token on every call (scale = amax / 448, q = RNE(clamp(x * (448 / amax), -448,
+ * 448))); everything else - token tensors, attention, embeddings, the modulation GEMM, the final layer - exactly as FG_DTYPE_BF16.
+ * hidden_size and mlp_hidden (ffn_dim) must be multiples of 128.  Roofline 5 PFLOP/s.  The EDM / EDM2 / ADM handles refuse it. */
 #define FG_DTYPE_FP8 3
 
 #define FG_SAMPLE_SDE 0  /* student_sample_type='sde'  (methods/model.py:358-359) */
@@ -507,7 +507,13 @@ FG_API int fg_dit_sampler_run(fg_dit* h, const fg_dit_sampler_config* cfg, const
  * restatement in oracle/wan_ref.py - PARITY UNPINNED.  bf16 token tensors and GEMM operands with fp32 accumulation,
  * fp32 norms / softmax / modulation: the reference runs this network in bf16 (configs/experiments/WanT2V/config_sf.py:19).
  * fg_wan_config = the fields of the transformer's config the path reads.  Supported: head_dim 128, inner dim (heads x 128) in
- * {256, 384, 1536 (1.3B), 2048, 5120 (14B)}, patch (1,2,2), ffn_dim / text_dim % 64 == 0, freq_dim 256, cross_attn_norm. */
+ * {256, 384, 1536 (1.3B), 2048, 5120 (14B)}, patch (1,2,2), ffn_dim / text_dim % 64 == 0, freq_dim 256, cross_attn_norm.
+ * compute_dtype FG_DTYPE_FP8: the six linears of a block that read the video tokens - attn1 to_q | to_k | to_v (one fused GEMM),
+ * attn1.to_out.0, attn2.to_q, attn2.to_out.0, ffn.net.0.proj, ffn.net.2 - run on e4m3fn operands (FG_DTYPE_FP8 above: weights
+ * re-quantised per output channel on every pack, the LayerNorm-modulate outputs, the two attention outputs and the GELU hidden
+ * quantised per token); the text side (text_embedder, attn2.to_k / to_v: once per text in fg_wan_set_text), time embedder, patch
+ * embedding, proj_out, attention, RMSNorm + RoPE and the caches are the bf16 mode's.  ffn_dim % 128 == 0 then.  Through every entry
+ * point below, the two samplers included; fg_wan_workspace_bytes grows by the quantised operands (m x (inner dim + ffn_dim + 8) bytes). */
 typedef struct fg_wan_config {
     int num_heads;         /* 12 */
     int head_dim;          /* 128 */
@@ -521,6 +527,7 @@ typedef struct fg_wan_config {
     int chunk_size;        /* CausalFastGenNetwork.chunk_size, 3 (frames per autoregressive chunk; the sampler's business) */
     int total_num_frames;  /* 21: capacity of the self-attention KV caches, in frames */
     float eps;             /* 1e-6 */
+    int compute_dtype;     /* 0 (unset) or FG_DTYPE_BF16: bf16 linears; FG_DTYPE_FP8; anything else: FG_EINVAL */
 } fg_wan_config;
 typedef struct fg_wan fg_wan; /* opaque */
 
@@ -766,8 +773,8 @@ FG_API int fg_op_gemm_fp8(const void* a, const void* w, const float* bias, void*
                           void* stream);
 /* LayerNorm (eps 1e-6, no affine) + adaLN modulation with the quantising store of the fp8 mode (dit.hip): y = LN(x[tok]) * (1 +
  * mod[n][scale_off + c]) + mod[n][shift_off + c], n = tok / tokens_per_image, written as e4m3fn bytes y [ntok][d] + y_scale [ntok]
- * (the scheme of fg_op_quant_rows_fp8 applied to the fp32 y).  x bf16 [ntok][d]; d in {384, 768, 1024, 1152}; mod_stride and the
- * offsets multiples of 4. */
+ * (the scheme of fg_op_quant_rows_fp8 applied to the fp32 y).  x bf16 [ntok][d]; d in {384, 768, 1024, 1152} (DiT) or {256, 1536,
+ * 2048, 5120} (the causal video DiT, tokens_per_image = tokens per frame); mod_stride and the offsets multiples of 4. */
 FG_API int fg_op_dit_ln_modulate_fp8(const void* x, const float* mod, int mod_stride, int shift_off, int scale_off, void* y, float* y_scale,
                                      int ntok, int d, int tokens_per_image, void* stream);
 /* The same token GEMM in the split-bf16 (FG_DTYPE_BF16X3) mode, the DiT's default: a [m][k] and w [n][k] fp32 are split into bf16

@@ -2,7 +2,16 @@
 Wan2.1-T2V-1.3B, latents [16, 21, 60, 104] = 480p, chunk of 3 frames, t_list of 4 steps): one network call of the student loop on
 chunk k (4680 query tokens over (3 k + 3) * 1560 cached + own keys), and the whole 21-frame 4-step loop (7 chunks x (4 + 1) calls).
 Random-init weights of the 1.3B architecture, synthetic latents and text embeddings.
-    python scripts/wan_bench.py [--layers=30] [--loop]"""
+    python scripts/wan_bench.py [--layers=30] [--loop] [--compute-dtype=bf16[,fp8]] [--case=chunks|bc|guided] [--chunks=0,6]
+                                [--widths=1.3b|14b] [--trace=CALLS]
+--compute-dtype: the arms (default bf16).  Several arms are built on the same seed and timed SIDE BY SIDE in this one run: per shape
+  three rounds of windows, the arms alternating inside a round, the median window per arm reported (and their ratio).
+--case: chunks (default) - one call per listed chunk (default all 7) over the cache the earlier chunks' calls left; bc - the all-frames
+  block-causal call (32 760 tokens); guided - the chunk calls at the stacked batch 2 of the guided teacher sampler ([cond; neg]).
+--widths=14b: inner dim 5120, ffn 13 824 (Wan2.1-T2V-14B's; --layers defaults to 2 then: the weights of 40 layers are 56 GB of fp32).
+--trace=CALLS: for `rocprofv3 --kernel-trace`: ONE arm, the listed chunks, one warm-up + CALLS calls each, nothing else (scripts/
+  wan_linear_trace.py reads the per-linear times out of the trace)."""
+import statistics
 import sys
 import time
 
@@ -11,31 +20,87 @@ import torch
 from fastgen_amd.methods.distribution_matching.causvid import CausVidModel
 from fastgen_amd.networks.Wan.network_causal import CausalWan
 
-LAYERS = next((int(a.split("=")[1]) for a in sys.argv[1:] if a.startswith("--layers=")), 30)
-net = CausalWan(num_layers=LAYERS).cuda().eval()
-D, Fd, H, fs, Lt = 1536, 8960, 12, 1560, 512
-x = torch.randn(1, 16, 21, 60, 104, device="cuda")
-text = torch.randn(1, Lt, 4096, device="cuda")
-t = torch.tensor([0.7], dtype=torch.float64, device="cuda")
+
+def _opt(name, default):
+    return next((a.split("=", 1)[1] for a in sys.argv[1:] if a.startswith(f"--{name}=")), default)
+
+
+WIDTHS = _opt("widths", "1.3b")
+LAYERS = int(_opt("layers", "30" if WIDTHS == "1.3b" else "2"))
+ARMS = _opt("compute-dtype", "bf16").split(",")
+CASE = _opt("case", "chunks")
+CHUNKS = [int(c) for c in _opt("chunks", "0,1,2,3,4,5,6").split(",")]
+TRACE = int(_opt("trace", "0"))
+assert WIDTHS in ("1.3b", "14b") and CASE in ("chunks", "bc", "guided") and all(a in ("bf16", "fp8") for a in ARMS) and (not TRACE or len(ARMS) == 1)
+H, Fd = (12, 8960) if WIDTHS == "1.3b" else (40, 13824)
+D, fs, Lt = H * 128, 1560, 512
+B = 2 if CASE == "guided" else 1
+
+nets = {}
+for arm in ARMS:
+    torch.manual_seed(0)  # the same weights in every arm
+    nets[arm] = CausalWan(num_attention_heads=H, ffn_dim=Fd, num_layers=LAYERS, compute_dtype=arm).cuda().eval()
+x = torch.randn(B, 16, 21, 60, 104, device="cuda")
+text = torch.randn(B, Lt, 4096, device="cuda")
+t = torch.tensor([0.7] * B, dtype=torch.float64, device="cuda")
+
+
+def gflop(L, Lkv):
+    return B * LAYERS * (2 * L * D * (4 * D + 2 * Fd + 2 * D) + 4 * L * Lkv * D + 4 * L * Lt * D) / 1e9
+
+
+def window(fn, n):
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(n):
+        fn()
+    torch.cuda.synchronize()
+    return (time.perf_counter() - t0) / n
+
+
+def side_by_side(label, fns, n, gf=None, rounds=3):
+    """fns: {arm: callable}; every arm warmed, then `rounds` rounds of one n-call window per arm, alternating."""
+    for fn in fns.values():
+        fn()
+    times = {a: [] for a in fns}
+    for _ in range(rounds):
+        for a, fn in fns.items():
+            times[a].append(window(fn, n))
+    med = {a: statistics.median(v) for a, v in times.items()}
+    parts = [f"{a} {med[a] * 1e3:8.2f} ms (min {min(times[a]) * 1e3:.2f}, max {max(times[a]) * 1e3:.2f})" +
+             (f" {gf / med[a] / 1e3:6.1f} TFLOP/s" if gf else "") for a in fns]
+    ratio = f"   bf16 / fp8 = {med['bf16'] / med['fp8']:.3f}" if "bf16" in med and "fp8" in med else ""
+    print(f"{label}: " + "   ".join(parts) + ratio, flush=True)
+    return med
+
+
 with torch.inference_mode():
-    for k in range(7):  # fill the cache chunk by chunk, timing the call on each chunk
-        xs = x[:, :, 3 * k: 3 * k + 3]
-        net(xs, t, condition=text, cur_start_frame=3 * k, store_kv=True, is_ar=True)
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        n = 3
-        for _ in range(n):
-            net(xs, t, condition=text, cur_start_frame=3 * k, store_kv=True, is_ar=True)
-        torch.cuda.synchronize()
-        dt = (time.perf_counter() - t0) / n
-        L, Lkv = 3 * fs, (3 * k + 3) * fs
-        gf = LAYERS * (2 * L * D * (4 * D + 2 * Fd + 2 * D) + 4 * L * Lkv * D + 4 * L * Lt * D) / 1e9
-        print(f"chunk {k}: {dt * 1e3:8.2f} ms / call  ({gf:7.1f} GFLOP: {gf / dt / 1e3:6.1f} TFLOP/s)", flush=True)
-    if "--loop" in sys.argv:
+    if CASE == "bc":
+        tf = torch.full((B, 21), 0.7, dtype=torch.float64, device="cuda")
+        call = lambda net: net(x, tf, condition=text, fwd_pred_type="flow", is_ar=False)  # noqa: E731
+        if TRACE:
+            window(lambda: call(nets[ARMS[0]]), 1 + TRACE)
+        else:
+            L = 21 * fs
+            # (keys per query under the block mask: on average 4 of the 7 chunks)
+            side_by_side(f"block-causal call, {L} tokens, {LAYERS} layers", {a: (lambda n=n: call(n)) for a, n in nets.items()}, 2,
+                         gflop(L, L * 4 // 7))
+    else:
+        for k in range(max(CHUNKS) + 1):  # fill the caches chunk by chunk, timing the call on the listed chunks
+            xs = x[:, :, 3 * k: 3 * k + 3]
+            call = lambda net: net(xs, t, condition=text, cur_start_frame=3 * k, store_kv=True, is_ar=True)  # noqa: E731
+            if k not in CHUNKS:
+                for net in nets.values():
+                    call(net)
+            elif TRACE:
+                window(lambda: call(nets[ARMS[0]]), 1 + TRACE)
+            else:
+                side_by_side(f"chunk {k} (batch {B}, {LAYERS} layers, {WIDTHS})", {a: (lambda n=n: call(n)) for a, n in nets.items()}, 3,
+                             gflop(3 * fs, (3 * k + 3) * fs))
+    if "--loop" in sys.argv and not TRACE:
         noise = torch.randn(1, 16, 21, 60, 104, device="cuda")
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        CausVidModel.generator_fn(net, noise, student_sample_steps=4, t_list=[0.999, 0.937, 0.833, 0.624, 0.0], condition=text)
-        torch.cuda.synchronize()
-        dt = time.perf_counter() - t0
-        print(f"21-frame 4-step CausVid loop (35 network calls): {dt:.3f} s = {21 / dt:.2f} latent frames / s")
+        text1 = text[:1]
+        loop = lambda net: CausVidModel.generator_fn(net, noise.clone(), student_sample_steps=4, t_list=[0.999, 0.937, 0.833, 0.624, 0.0],  # noqa: E731
+                                                     condition=text1)
+        med = side_by_side("21-frame 4-step CausVid loop (35 network calls)", {a: (lambda n=n: loop(n)) for a, n in nets.items()}, 1)
+        print("   " + "   ".join(f"{a}: {21 / v:.2f} latent frames / s" for a, v in med.items()))
