@@ -21,14 +21,15 @@ from __future__ import annotations
 import ctypes
 import math
 import os
-from typing import Any, Dict, List, Optional, Set
+from typing import Optional, Set
 
 import numpy as np
 import torch
 import torch.nn as nn
 
 from fastgen_amd import _lib
-from fastgen_amd.networks import _weights
+from fastgen_amd.networks import _engine
+from fastgen_amd.networks._engine import ptr, ptr_nonempty, stream
 from fastgen_amd.networks.EDM import network as _edm
 from fastgen_amd.networks.network import FastGenNetwork, _fused_sample_args
 from fastgen_amd.networks.noise_schedule import NET_PRED_TYPES
@@ -76,33 +77,21 @@ class DiT(FastGenNetwork):
         cfg.r_timestep = int(self.r_timestep)
         self._cfg = cfg
         self.hidden_size = hidden_size
-        self._engines: Dict[int, ctypes.c_void_p] = {}
-        self._bound_sig: Dict[int, Dict[str, tuple]] = {}
-        self._ws: Dict[int, torch.Tensor] = {}
+        self._eng = _engine.Handles("dit", cfg)
         # module tree with the reference's key paths; names / shapes come from the library's own plan
-        self._names: List[str] = []
         # (the naming handle in a mode the token grid accepts: exact fp32 is a 16 x 16 grid only)
         naming = _lib.FG_DTYPE_F32 if input_size // max(patch_size, 1) == 16 else _lib.FG_DTYPE_BF16X3
         if self.compute_dtype == "fp32" and naming != _lib.FG_DTYPE_F32:
             self._make_engine(_lib.FG_DTYPE_F32)  # raises NotImplementedError
-        h = self._make_engine(naming)
-        L = _lib.lib()
-        name, ndim, shape = ctypes.c_char_p(), ctypes.c_int(), (ctypes.c_int64 * 4)()
-        for i in range(L.fg_dit_num_params(h)):
-            _lib.check(L.fg_dit_param_info(h, i, ctypes.byref(name), ctypes.byref(ndim), shape))
-            full, shp = name.value.decode(), tuple(shape[j] for j in range(ndim.value))
-            self._names.append(full)
-            node, parts = self, full.split(".")
-            for p in parts[:-1]:
-                if p not in node._modules:
-                    node.add_module(p, _edm._Node())
-                node = node._modules[p]
+
+        def register(node, leaf, full, shp):
             if full == "pos_embed":
                 self._tokens = int(shp[1])
                 self.register_buffer("pos_embed", sinusoidal_2d_table(hidden_size, input_size // patch_size), persistent=True)
             else:
-                node.register_parameter(parts[-1], nn.Parameter(self._init_value(full, shp)))
-        self._engines[naming] = h
+                node.register_parameter(leaf, nn.Parameter(self._init_value(full, shp)))
+
+        self._names, _ = _engine.build_tree(self, "dit", self._eng.get(naming, self._make_engine), register)
 
     @staticmethod
     def _init_value(name: str, shape) -> torch.Tensor:
@@ -116,23 +105,12 @@ class DiT(FastGenNetwork):
         return math.sqrt(6 / (fan_in + fan_out)) * (torch.rand(*shape) * 2 - 1)
 
     def _make_engine(self, dtype: int):
-        cfg = _lib.fg_dit_config.from_buffer_copy(self._cfg)
-        cfg.compute_dtype = dtype
-        h = ctypes.c_void_p()
         try:
-            _lib.check(_lib.lib().fg_dit_create(ctypes.byref(cfg), ctypes.byref(h)))
+            return self._eng.create(dtype)
         except _lib.FastGenAMDError as e:
             if dtype == _lib.FG_DTYPE_F32 and self._cfg.patch_size > 0 and self._cfg.input_size // self._cfg.patch_size == 32:
                 raise NotImplementedError(str(e)) from None
             raise
-        return h
-
-    def __del__(self):
-        try:
-            for h in getattr(self, "_engines", {}).values():
-                _lib.lib().fg_dit_destroy(h)
-        except Exception:
-            pass
 
     def reset_parameters(self):
         with torch.no_grad():
@@ -144,36 +122,17 @@ class DiT(FastGenNetwork):
         super().reset_parameters()
 
     def _select_dtype(self) -> int:
-        if self.compute_dtype is not None:
-            return _lib.DTYPE_NAMES[self.compute_dtype]
-        if torch.is_autocast_enabled():
-            ad = torch.get_autocast_gpu_dtype()
-            if ad == torch.bfloat16:
-                return _lib.FG_DTYPE_BF16
-            if ad != torch.float32:
-                raise NotImplementedError(f"autocast dtype {ad} is not implemented (bf16 or fp32)")
-        return _lib.DTYPE_NAMES[_edm.DEFAULT_FP32_MODE]
+        return _lib.DTYPE_NAMES[_engine.compute_mode(self.compute_dtype, _edm.DEFAULT_FP32_MODE)]
 
     def _engine(self, device: torch.device):
         dt = self._select_dtype()
-        if dt not in self._engines:
-            self._engines[dt] = self._make_engine(dt)
-        h = self._engines[dt]
-        L = _lib.lib()
-        stream = ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
-        _weights.sync_weights(
-            self, self._names, self._bound_sig.setdefault(dt, {}),
-            tensors=lambda: {**dict(self.named_parameters()), "pos_embed": self.pos_embed},
-            bind=lambda n, q: _lib.check(L.fg_dit_bind_param(h, n.encode(), ctypes.c_void_p(q.data_ptr()), q.numel())),
-            pack_group=lambda pre, exc: _lib.check(L.fg_dit_pack_group(h, pre.encode(), exc.encode() if exc else None, stream)))
+        h = self._eng.get(dt, self._make_engine)
+        self._eng.sync_copies(self, dt, self._names, lambda: {**dict(self.named_parameters()), "pos_embed": self.pos_embed}, device)
         return dt, h
 
     def _workspace(self, dt: int, need: int, device) -> torch.Tensor:
         """The cached workspace of compute mode `dt`, grown to `need` bytes (forward, jvp and the fused loops share it)."""
-        ws = self._ws.get(dt)
-        if ws is None or ws.numel() < need or ws.device != device:
-            ws = self._ws[dt] = torch.empty(need, dtype=torch.uint8, device=device)
-        return ws
+        return self._eng.workspace(dt, need, device)
 
     def fully_shard(self, **kwargs):
         """FSDP2 with the reference's grouping (DiT/network.py:402-420): one parameter group per transformer block, one each for the
@@ -228,23 +187,17 @@ class DiT(FastGenNetwork):
         if torch.is_grad_enabled() and (x_t.requires_grad or any(p.requires_grad for p in self.parameters())):
             raise NotImplementedError("fastgen_amd.DiT: the backward pass is not implemented; call under torch.no_grad() / "
                                       "torch.inference_mode() (sampling)")
-        if x_t.device.type != "cuda":
-            raise RuntimeError("fastgen_amd runs on a HIP GPU only (no CPU path); got a tensor on " + str(x_t.device))
+        _engine.require_gpu(x_t)
         B, dev = x_t.shape[0], x_t.device
         if tuple(x_t.shape[1:]) != (self.in_channels, self.input_size, self.input_size):
             raise ValueError(f"x_t must be [B,{self.in_channels},{self.input_size},{self.input_size}], got {tuple(x_t.shape)}")
         cls = self._class_ids(condition, B, dev)
         x32 = x_t.detach().to(torch.float32).contiguous()
-        t_in = torch.atleast_1d(t.detach()).to(dev)
-        if t_in.numel() == 1 and B > 1:
-            t_in = t_in.expand(B)
+        t_in = _engine.per_sample("t", t, B, dev)
         t_e = self.prepare_t(t_in, torch.float32)
         r_e = None
         if self.r_timestep and r is not None:
-            r_in = torch.atleast_1d(r.detach()).to(dev)
-            if r_in.numel() == 1 and B > 1:
-                r_in = r_in.expand(B)
-            r_e = self.prepare_t(r_in, torch.float32)
+            r_e = self.prepare_t(_engine.per_sample("r", r, B, dev), torch.float32)
         if self.use_sit_convention:
             t_e = 1 - t_e  # :503-504
         if r_e is not None and self.time_cond_type == "diff":
@@ -264,10 +217,9 @@ class DiT(FastGenNetwork):
         feats = [torch.empty(B, self._tokens, self.hidden_size, dtype=torch.float32, device=dev) for _ in taps]
         out = None if early else torch.empty_like(x32)
         _lib.check(L.fg_dit_forward_features(
-            h, ctypes.c_void_p(x32.data_ptr()), ctypes.c_void_p(t_e.data_ptr()), ctypes.c_void_p(r_e.data_ptr() if r_e is not None else None),
-            ctypes.c_void_p(cls.data_ptr()), ctypes.c_void_p(out.data_ptr() if out is not None else None), None,
+            h, ptr(x32), ptr(t_e), ptr(r_e), ptr(cls), ptr(out), None,
             (ctypes.c_int * len(taps))(*taps) if taps else None, (ctypes.c_void_p * len(taps))(*[f.data_ptr() for f in feats]) if taps else None,
-            len(taps), B, ctypes.c_void_p(ws.data_ptr()), ws.numel(), ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+            len(taps), B, ptr(ws), ws.numel(), stream(dev)))
         feats = [f.to(x_t.dtype) for f in feats]
         if early:
             return feats
@@ -299,8 +251,7 @@ class DiT(FastGenNetwork):
                                       f"{self.input_size // max(self.patch_size, 1)} patches per side")
         if self._select_dtype() != _lib.FG_DTYPE_BF16X3:
             raise NotImplementedError("fastgen_amd.DiT.jvp runs in the 'bf16x3' compute mode only (the reference evaluates this JVP in float32)")
-        if x_t.device.type != "cuda":
-            raise RuntimeError("fastgen_amd runs on a HIP GPU only (no CPU path); got a tensor on " + str(x_t.device))
+        _engine.require_gpu(x_t)
         B, dev = x_t.shape[0], x_t.device
         if tuple(x_t.shape[1:]) != (self.in_channels, self.input_size, self.input_size) or v_x.shape != x_t.shape:
             raise ValueError(f"x_t and v_x must be [B,{self.in_channels},{self.input_size},{self.input_size}], got {tuple(x_t.shape)} "
@@ -309,24 +260,19 @@ class DiT(FastGenNetwork):
         x32 = x_t.detach().to(torch.float32).contiguous()
         vx = v_x.detach().to(device=dev, dtype=torch.float32).contiguous()
 
-        def rows(a):
-            a = torch.atleast_1d(a.detach()).to(dev)
-            return a.expand(B) if a.numel() == 1 and B > 1 else a
-
-        def tangent(v):  # the derivative of prepare_t, a multiplication by num_steps or 1
-            v = rows(v).to(torch.float32)
+        def tangent(name, v):  # the derivative of prepare_t, a multiplication by num_steps or 1
+            v = _engine.per_sample(name, v, B, dev).to(torch.float32)
             return self.noise_scheduler._rescale(v) if self.scale_t else v
 
         use_r = self.r_timestep and r is not None
-        t_e = self.prepare_t(rows(t), torch.float32)
-        vt_e = tangent(v_t) if v_t is not None else torch.zeros(B, dtype=torch.float32, device=dev)
-        r_e = self.prepare_t(rows(r), torch.float32) if use_r else None
-        vr_e = (tangent(v_r) if v_r is not None else torch.zeros(B, dtype=torch.float32, device=dev)) if use_r else None
+        t_e = self.prepare_t(_engine.per_sample("t", t, B, dev), torch.float32)
+        vt_e = tangent("v_t", v_t) if v_t is not None else torch.zeros(B, dtype=torch.float32, device=dev)
+        r_e = self.prepare_t(_engine.per_sample("r", r, B, dev), torch.float32) if use_r else None
+        vr_e = (tangent("v_r", v_r) if v_r is not None else torch.zeros(B, dtype=torch.float32, device=dev)) if use_r else None
         if self.use_sit_convention:
             t_e, vt_e = 1 - t_e, -vt_e  # :503-504
         if use_r and self.time_cond_type == "diff":
             r_e, vr_e = t_e - r_e, vt_e - vr_e  # :520-521
-        p = lambda a: ctypes.c_void_p(a.data_ptr() if a is not None else None)  # noqa: E731
         t_e, vt_e = t_e.contiguous(), vt_e.contiguous()
         r_e, vr_e = (r_e.contiguous(), vr_e.contiguous()) if use_r else (None, None)
         dt, h = self._engine(dev)
@@ -336,8 +282,8 @@ class DiT(FastGenNetwork):
             raise NotImplementedError("fastgen_amd.DiT.jvp: this compute mode / token grid has no jvp (bf16x3, 256 tokens)")
         ws = self._workspace(dt, need, dev)
         out, jv = torch.empty_like(x32), torch.empty_like(x32)
-        _lib.check(L.fg_dit_jvp(h, p(x32), p(t_e), p(r_e), p(cls), p(vx), p(vt_e), p(vr_e), p(out), p(jv), B, ctypes.c_void_p(ws.data_ptr()),
-                                ws.numel(), ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+        _lib.check(L.fg_dit_jvp(h, ptr(x32), ptr(t_e), ptr(r_e), ptr(cls), ptr(vx), ptr(vt_e), ptr(vr_e), ptr(out), ptr(jv), B, ptr(ws),
+                                ws.numel(), stream(dev)))
         out, jv = out.to(x_t.dtype), jv.to(x_t.dtype)
         if self.use_sit_convention and self.net_pred_type == "flow":
             out, jv = -out, -jv  # :555-558
@@ -396,11 +342,11 @@ class DiT(FastGenNetwork):
         ws = self._workspace(dt, L.fg_dit_sampler_workspace_bytes(h, B, int(neg is not None)), dev)
         out = torch.empty_like(n32)
         self._keep = (n32, cls, neg, eps, out)  # graph replays read these buffers; keep them alive
-        p = lambda a: ctypes.c_void_p(a.data_ptr() if a is not None and a.numel() else None)  # noqa: E731
+        # (this call has always passed null for a tensor without elements, not only for `eps`)
         _lib.check(L.fg_dit_sampler_run(
-            h, ctypes.byref(sc), p(n32), p(cls), p(neg), tl_arr, steps, _lib.SAMPLE_TYPES[sample_type], _lib.LOOP_KINDS[loop], p(eps),
-            ctypes.c_uint64(seed), p(out), B,
-            ctypes.c_void_p(ws.data_ptr()), ws.numel(), 1 if use_graph else 0, ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+            h, ctypes.byref(sc), ptr_nonempty(n32), ptr_nonempty(cls), ptr_nonempty(neg), tl_arr, steps, _lib.SAMPLE_TYPES[sample_type],
+            _lib.LOOP_KINDS[loop], ptr_nonempty(eps), ctypes.c_uint64(seed), ptr_nonempty(out), B, ptr(ws), ws.numel(),
+            1 if use_graph else 0, stream(dev)))
         return out.to(noise.dtype)
 
     @torch.no_grad()

@@ -40,6 +40,8 @@ import torch
 import torch.nn as nn
 
 from fastgen_amd import _lib
+from fastgen_amd.networks import _engine
+from fastgen_amd.networks._engine import _Node, ptr, stream  # (`_Node`: DiT and CausalWan name it through this module too)
 from fastgen_amd.networks.network import FastGenNetwork, _edm_euler_sample, _fused_sample_args
 from fastgen_amd.networks.noise_schedule import NET_PRED_TYPES
 
@@ -49,10 +51,6 @@ from fastgen_amd.networks.noise_schedule import NET_PRED_TYPES
 # "bf16x3": fp32 tensors, convolutions as three bf16 MFMAs per product (hi/lo split, ~2^-17 per product: 64x tighter than TF32,
 # 833 TFLOP/s roof; held to the SAME parity tolerance as "fp32" in tests/test_gpu_parity.py).  Overridable per module (compute_dtype=...) or per process (FASTGEN_AMD_COMPUTE_DTYPE).
 DEFAULT_FP32_MODE = "bf16x3"
-
-
-class _Node(nn.Module):
-    """Bare container: the parameter tree only has to reproduce the reference's state-dict key paths."""
 
 
 class _UNet(_Node):
@@ -146,17 +144,15 @@ class _TrainCall:
         self.ws_ptr_bwd = ws.data_ptr()
         if self.drop is not None:
             _lib.check(L.fg_edm_set_dropout(h, self.drop[0], self.drop[1]))
-        p_ = lambda a: ctypes.c_void_p(a.data_ptr() if a is not None else None)  # noqa: E731
         try:
             for (n, _), g in zip(named, grads):
                 if g is not None:
-                    _lib.check(L.fg_edm_bind_grad(h, n.encode(), ctypes.c_void_p(g.data_ptr()), g.numel()))
+                    _lib.check(L.fg_edm_bind_grad(h, n.encode(), ptr(g), g.numel()))
             if self.aug is not None:
-                _lib.check(L.fg_edm_set_augment(h, ctypes.c_void_p(self.aug.data_ptr())))
+                _lib.check(L.fg_edm_set_augment(h, ptr(self.aug)))
             _lib.check(L.fg_edm_backward_part(
-                h, p_(x32), p_(t64), p_(r64), p_(labels), p_(self.d32), self.dptrs if (self.any_feat or self.early) else None,
-                p_(self.scratch_out), p_(self.dx), self.have_forward, part, B, ctypes.c_void_p(ws.data_ptr()), ws.numel(),
-                net._stream(dev)))
+                h, ptr(x32), ptr(t64), ptr(r64), ptr(labels), ptr(self.d32), self.dptrs if (self.any_feat or self.early) else None,
+                ptr(self.scratch_out), ptr(self.dx), self.have_forward, part, B, ptr(ws), ws.numel(), net._stream(dev)))
         finally:
             if self.drop is not None:
                 _lib.check(L.fg_edm_set_dropout(h, 0.0, 0))
@@ -209,11 +205,7 @@ class _EDMForwardFn(torch.autograd.Function):
             feats.append(f)
         with net._AugmentScope(h, call.aug):
             _lib.check(L.fg_edm_forward_train(
-                h, ctypes.c_void_p(x32.data_ptr()), ctypes.c_void_p(t64.data_ptr()),
-                ctypes.c_void_p(r64.data_ptr() if r64 is not None else None),
-                ctypes.c_void_p(labels.data_ptr() if labels is not None else None),
-                ctypes.c_void_p(out.data_ptr() if out is not None else None), ptrs if taps else None,
-                B, ctypes.c_void_p(ws.data_ptr()), ws.numel(), net._stream(dev)))
+                h, ptr(x32), ptr(t64), ptr(r64), ptr(labels), ptr(out), ptrs if taps else None, B, ptr(ws), ws.numel(), net._stream(dev)))
         if drop is not None:
             _lib.check(L.fg_edm_set_dropout(h, 0.0, 0))
         # the training workspace now holds this call's state; any later training forward of the module replaces the token, and
@@ -359,34 +351,23 @@ class EDMPrecond(FastGenNetwork):
         cfg.schedule = self.noise_scheduler.schedule_id
         cfg.model_type = _lib.FG_MODEL_DHARIWAL if self.is_adm else _lib.FG_MODEL_SONGUNET
         self._cfg = cfg
-        self._engines: Dict[int, ctypes.c_void_p] = {}
-        self._bound_sig: Dict[int, Any] = {}
-        self._pack_refs: Dict[int, list] = {}
-        self._ws: Dict[int, torch.Tensor] = {}
+        self._eng = _engine.Handles("edm", cfg)
         self._noise_channels = cfg.model_channels * (1 if self.is_adm else cfg.channel_mult_noise)
 
         # parameter tree with the reference's key paths; names/shapes come from the library's own plan
         self.model = _UNet()
-        self._param_names: List[str] = []
+
+        def register(node, leaf, full, shp):
+            node.register_parameter(leaf, nn.Parameter(_init_value(full, shp)))
+            # the reference keeps the constant 2x2 resampling kernel as a persistent buffer (EDM/network.py:89-91)
+            parts = full.split(".")
+            if leaf == "weight" and parts[-2] in ("conv0", "skip") and (parts[-3].endswith("_down") or parts[-3].endswith("_up")):
+                node.register_buffer("resample_filter", torch.full((1, 1, 2, 2), 0.25))
+
         # (DhariwalUNet has no exact-fp32 engine: its parameter plan is read from a split-bf16 one)
         plan_dt = _lib.FG_DTYPE_BF16X3 if self.is_adm else _lib.FG_DTYPE_F32
-        h = self._make_engine(plan_dt)
-        L = _lib.lib()
-        name, ndim, shape = ctypes.c_char_p(), ctypes.c_int(), (ctypes.c_int64 * 4)()
-        for i in range(L.fg_edm_num_params(h)):
-            _lib.check(L.fg_edm_param_info(h, i, ctypes.byref(name), ctypes.byref(ndim), shape))
-            full = name.value.decode()
-            shp = tuple(shape[j] for j in range(ndim.value))
-            self._param_names.append(full)
-            node, parts = self, full.split(".")
-            for p in parts[:-1]:
-                if p not in node._modules:
-                    node.add_module(p, _Node())
-                node = node._modules[p]
-            node.register_parameter(parts[-1], nn.Parameter(_init_value(full, shp)))
-            # the reference keeps the constant 2x2 resampling kernel as a persistent buffer (EDM/network.py:89-91)
-            if parts[-1] == "weight" and parts[-2] in ("conv0", "skip") and (parts[-3].endswith("_down") or parts[-3].endswith("_up")):
-                node.register_buffer("resample_filter", torch.full((1, 1, 2, 2), 0.25))
+        # `_leafs`: (leaf module, parameter name) of every engine parameter, in engine order (see _engine)
+        self._param_names, self._leafs = _engine.build_tree(self, "edm", self._eng.get(plan_dt), register)
         if self.is_adm:
             # DhariwalUNet's up / down blocks keep their width: their skip is a weightless resampling Conv2d (kernel 0) whose only
             # state is the filter buffer (EDM/network.py:249-259)
@@ -396,14 +377,6 @@ class EDMPrecond(FastGenNetwork):
                         skip = _Node()
                         skip.register_buffer("resample_filter", torch.full((1, 1, 2, 2), 0.25))
                         block.add_module("skip", skip)
-        self._engines[plan_dt] = h
-        # (leaf module, parameter name) of every engine parameter, in engine order (see _engine)
-        self._leafs = []
-        for full in self._param_names:
-            node, parts = self, full.split(".")
-            for p_ in parts[:-1]:
-                node = node._modules[p_]
-            self._leafs.append((node, parts[-1]))
 
     @property
     def is_adm(self) -> bool:
@@ -430,18 +403,7 @@ class EDMPrecond(FastGenNetwork):
 
     # ------------------------------------------------------------------------------------------------
     def _make_engine(self, dtype: int):
-        cfg = _lib.fg_edm_config.from_buffer_copy(self._cfg)
-        cfg.compute_dtype = dtype
-        h = ctypes.c_void_p()
-        _lib.check(_lib.lib().fg_edm_create(ctypes.byref(cfg), ctypes.byref(h)))
-        return h
-
-    def __del__(self):
-        try:
-            for h in getattr(self, "_engines", {}).values():
-                _lib.lib().fg_edm_destroy(h)
-        except Exception:
-            pass
+        return self._eng.create(dtype)
 
     def _named_weights(self, names=None):
         sd = dict(self.named_parameters())
@@ -458,71 +420,32 @@ class EDMPrecond(FastGenNetwork):
     def _select_dtype(self) -> int:
         if self.is_adm and (self.compute_dtype or (None if torch.is_autocast_enabled() else DEFAULT_FP32_MODE)) == "fp32":
             raise NotImplementedError("DhariwalUNet runs in the 'bf16x3' and 'bf16' compute modes, not in exact fp32")
-        if self.compute_dtype is not None:
-            return _lib.DTYPE_NAMES[self.compute_dtype]
-        if torch.is_autocast_enabled():
-            ad = torch.get_autocast_gpu_dtype()
-            if ad == torch.bfloat16:
-                return _lib.FG_DTYPE_BF16
-            if ad != torch.float32:
-                raise NotImplementedError(f"autocast dtype {ad} is not implemented (bf16 or fp32)")
-        return _lib.DTYPE_NAMES[DEFAULT_FP32_MODE]
+        return _lib.DTYPE_NAMES[_engine.compute_mode(self.compute_dtype, DEFAULT_FP32_MODE)]
 
     def _engine(self, device: torch.device, dt: Optional[int] = None):
         """Engine for the active (or the given) compute dtype with up-to-date weights bound and packed."""
         if dt is None:
             dt = self._select_dtype()
-        if dt not in self._engines:
-            self._engines[dt] = self._make_engine(dt)
-        h = self._engines[dt]
-        # Is what the engine bound still what the module holds?  One pass over the 421 parameters (storage pointer, in-place
-        # version counter, dtype: any optimizer step, load_state_dict, .to() or FSDP2 all-gather changes one of them), read straight
-        # from the leaf modules' parameter dicts - no named_parameters() generator, no per-call name -> tensor dict.
+        h = self._eng.get(dt)
+        # the 421 parameters in engine order, straight from the leaf modules' dicts (`Handles.bind_in_place` says why)
         ps = [leaf._parameters[nm] for leaf, nm in self._leafs]
         for n, p in zip(self._param_names, ps):
             if hasattr(p, "_local_tensor"):
                 raise RuntimeError(
                     f"parameter {n} is a sharded DTensor: the engine reads whole parameters.  Call the network through "
                     "forward() / jvp() / few_step_sample() / generator_fn(), which all-gather FSDP2 groups around the call")
-        sig = tuple((p.data_ptr(), p._version, p.dtype) for p in ps)
-        if self._bound_sig.get(dt) != sig:
-            weights = list(zip(self._param_names, ps))
-            L = _lib.lib()
-            refs = []
-            for n, p in weights:
-                if p.device.type != "cuda":
-                    raise RuntimeError(f"parameter {n} is on {p.device}; fastgen_amd runs on a HIP GPU only (no CPU path)")
-                q = p.detach()
-                if q.dtype != torch.float32 or not q.is_contiguous():
-                    q = q.to(torch.float32).contiguous()
-                refs.append(q)
-                _lib.check(L.fg_edm_bind_param(h, n.encode(), ctypes.c_void_p(q.data_ptr()), q.numel()))
-            _lib.check(L.fg_edm_pack_weights(h, ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)))
-            self._pack_refs[dt] = refs
-            self._bound_sig[dt] = sig
+        self._eng.bind_in_place(dt, self._param_names, ps, device)
         # train() / eval() as far as the arithmetic sees it: sigma_shift applies in eval mode only (EDM/network.py:956)
         _lib.check(_lib.lib().fg_edm_set_training(h, int(self.training)))
         return dt, h
 
     def _workspace(self, dt: int, h, batch: int, device) -> torch.Tensor:
-        need = _lib.lib().fg_edm_workspace_bytes(h, batch)
-        ws = self._ws.get(dt)
-        if ws is None or ws.numel() < need or ws.device != device:
-            ws = torch.empty(need, dtype=torch.uint8, device=device)
-            self._ws[dt] = ws
-        return ws
+        return self._eng.workspace(dt, _lib.lib().fg_edm_workspace_bytes(h, batch), device)
 
     def _train_workspace(self, h, batch: int, device) -> torch.Tensor:
-        need = _lib.lib().fg_edm_backward_workspace_bytes(h, batch)
-        ws = self._ws.get("bwd")
-        if ws is None or ws.numel() < need or ws.device != device:
-            ws = torch.empty(need, dtype=torch.uint8, device=device)
-            self._ws["bwd"] = ws
-        return ws
+        return self._eng.workspace("bwd", _lib.lib().fg_edm_backward_workspace_bytes(h, batch), device)
 
-    @staticmethod
-    def _stream(device) -> ctypes.c_void_p:
-        return ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+    _stream = staticmethod(stream)
 
     def _needs_grad(self, x_t: Optional[torch.Tensor] = None) -> bool:
         return torch.is_grad_enabled() and (any(p.requires_grad for p in self.parameters())
@@ -544,18 +467,12 @@ class EDMPrecond(FastGenNetwork):
     def _labels(self, condition, batch: int, device) -> Optional[torch.Tensor]:
         if isinstance(condition, dict) and "aug_condition" in condition:
             condition = condition.get("orig_condition")  # the augmentation part is taken by _augment()
-        if self.label_dim == 0 or condition is None:
-            return None  # the library broadcasts map_label(zeros) as the reference does (EDM/network.py:919-925)
-        c = condition.reshape(-1, self.label_dim).to(device=device, dtype=torch.float32)
-        if c.shape[0] == 1 and batch > 1:
-            c = c.expand(batch, -1)
-        if c.shape[0] != batch:
-            raise ValueError(f"condition has {c.shape[0]} rows, expected {batch}")
-        if self.training and self.label_dropout:
+        c = _engine.class_labels(condition, self.label_dim, batch, device)
+        if c is not None and self.training and self.label_dropout:
             # whole label rows are zeroed with probability label_dropout (classifier-free-guidance training), same draw as the
             # reference: torch.rand([B, 1]) on the input's device (EDM/network.py:515-516)
             c = c * (torch.rand([batch, 1], device=device) >= self.label_dropout).to(c.dtype)
-        return c.contiguous()
+        return c
 
     def _augment(self, condition, batch: int, device) -> Optional[torch.Tensor]:
         """Augmentation labels of a {"aug_condition", "orig_condition"} condition (EDM/network.py:903-915): [B, augment_dim] fp32,
@@ -578,7 +495,7 @@ class EDMPrecond(FastGenNetwork):
 
         def __enter__(self):
             if self.aug is not None:
-                _lib.check(_lib.lib().fg_edm_set_augment(self.h, ctypes.c_void_p(self.aug.data_ptr())))
+                _lib.check(_lib.lib().fg_edm_set_augment(self.h, ptr(self.aug)))
 
         def __exit__(self, *exc):
             if self.aug is not None:
@@ -705,26 +622,13 @@ class EDMPrecond(FastGenNetwork):
             self._check_trainable_call(return_logvar)
         if self.is_adm:
             self._select_dtype()  # refuses the exact-fp32 mode before anything else
-        if x_t.device.type != "cuda":
-            raise RuntimeError("fastgen_amd runs on a HIP GPU only (no CPU path); got a tensor on " + str(x_t.device))
+        _engine.require_gpu(x_t)
         if x_t.dim() != 4 or x_t.shape[1] != self.img_channels or x_t.shape[2] != self.img_resolution or x_t.shape[3] != self.img_resolution:
             raise ValueError(f"x_t must be [B,{self.img_channels},{self.img_resolution},{self.img_resolution}], got {tuple(x_t.shape)}")
         B, dev = x_t.shape[0], x_t.device
         x32 = (x_t if needs_grad and x_t.requires_grad else x_t.detach()).to(torch.float32).contiguous()
-        t64 = torch.atleast_1d(t.detach()).to(device=dev, dtype=torch.float64)
-        if t64.numel() == 1 and B > 1:
-            t64 = t64.expand(B)
-        t64 = t64.contiguous()
-        if t64.numel() != B:
-            raise ValueError(f"t has {t64.numel()} entries, expected {B}")
-        r64 = None
-        if r is not None:
-            r64 = torch.atleast_1d(r.detach()).to(device=dev, dtype=torch.float64)
-            if r64.numel() == 1 and B > 1:
-                r64 = r64.expand(B)
-            r64 = r64.contiguous()
-            if r64.numel() != B:
-                raise ValueError(f"r has {r64.numel()} entries, expected {B}")
+        t64 = _engine.per_sample("t", t, B, dev, torch.float64)
+        r64 = None if r is None else _engine.per_sample("r", r, B, dev, torch.float64)
         labels = self._labels(condition, B, dev)
         aug = self._augment(condition, B, dev)
 
@@ -766,11 +670,7 @@ class EDMPrecond(FastGenNetwork):
                 out = None if return_features_early else torch.empty_like(x32)
                 with self._AugmentScope(h, aug):
                     _lib.check(L.fg_edm_forward_features(
-                    h, ctypes.c_void_p(x32.data_ptr()), ctypes.c_void_p(t64.data_ptr()),
-                    ctypes.c_void_p(r64.data_ptr() if r64 is not None else None),
-                    ctypes.c_void_p(labels.data_ptr() if labels is not None else None),
-                    ctypes.c_void_p(out.data_ptr() if out is not None else None), ptrs, B, ctypes.c_void_p(ws.data_ptr()),
-                    ws.numel(), self._stream(dev)))
+                        h, ptr(x32), ptr(t64), ptr(r64), ptr(labels), ptr(out), ptrs, B, ptr(ws), ws.numel(), self._stream(dev)))
                 features = [f.to(x_t.dtype) for f in features]
                 if return_features_early:
                     return None, features
@@ -778,10 +678,7 @@ class EDMPrecond(FastGenNetwork):
                 out = torch.empty_like(x32)
                 with self._AugmentScope(h, aug):
                     _lib.check(L.fg_edm_forward(
-                        h, ctypes.c_void_p(x32.data_ptr()), ctypes.c_void_p(t64.data_ptr()),
-                        ctypes.c_void_p(r64.data_ptr() if r64 is not None else None),
-                        ctypes.c_void_p(labels.data_ptr() if labels is not None else None), ctypes.c_void_p(out.data_ptr()), None,
-                        B, ctypes.c_void_p(ws.data_ptr()), ws.numel(), self._stream(dev)))
+                        h, ptr(x32), ptr(t64), ptr(r64), ptr(labels), ptr(out), None, B, ptr(ws), ws.numel(), self._stream(dev)))
             return out, features
 
         out, features = self._fsdp_call(engine_call)
@@ -815,11 +712,11 @@ class EDMPrecond(FastGenNetwork):
         dt, h = self._engine(dev)
         if dt == _lib.FG_DTYPE_F32:
             raise NotImplementedError("fastgen_amd.EDMPrecond.jvp runs in the 'bf16x3' and 'bf16' compute modes, not in exact fp32")
-        f32 = lambda a: None if a is None else torch.atleast_1d(a.detach()).to(device=dev, dtype=torch.float32).expand(B).contiguous()
-        f64 = lambda a: None if a is None else torch.atleast_1d(a.detach()).to(device=dev, dtype=torch.float64).expand(B).contiguous()
+        rows = lambda name, a, dtype: None if a is None else _engine.per_sample(name, a, B, dev, dtype)  # noqa: E731
         x32 = x_t.detach().to(torch.float32).contiguous()
         vx = v_x.detach().to(torch.float32).contiguous()
-        t64, r64, vt, vr = f64(t), f64(r), f32(v_t), f32(v_r)
+        t64, r64 = rows("t", t, torch.float64), rows("r", r, torch.float64)
+        vt, vr = rows("v_t", v_t, torch.float32), rows("v_r", v_r, torch.float32)
         labels = self._labels(condition, B, dev)
         aug = self._augment(condition, B, dev)
         L = _lib.lib()
@@ -831,10 +728,9 @@ class EDMPrecond(FastGenNetwork):
             self._train_token = object()  # the kept state of an earlier training forward is overwritten
             self._bwd_owner = None
             out, jv = torch.empty_like(x32), torch.empty_like(x32)
-            p = lambda a: ctypes.c_void_p(a.data_ptr() if a is not None else None)
             with self._AugmentScope(h, aug):
-                _lib.check(L.fg_edm_jvp(h, p(x32), p(t64), p(r64), p(labels), p(vx), p(vt), p(vr), p(out), p(jv), B,
-                                        ctypes.c_void_p(ws.data_ptr()), ws.numel(), self._stream(dev)))
+                _lib.check(L.fg_edm_jvp(h, ptr(x32), ptr(t64), ptr(r64), ptr(labels), ptr(vx), ptr(vt), ptr(vr), ptr(out), ptr(jv), B,
+                                        ptr(ws), ws.numel(), self._stream(dev)))
         finally:
             if drop:
                 _lib.check(L.fg_edm_set_dropout(h, 0.0, 0))
@@ -901,12 +797,7 @@ class EDMPrecond(FastGenNetwork):
     def _sampler_call(self, n32, labels, tl_arr, steps, sample_type, loop, eps, seed, out, B, dev, use_graph):
         dt, h = self._engine(dev)
         ws = self._workspace(dt, h, B, dev)
-        _lib.check(_lib.lib().fg_sampler_run(
-            h, ctypes.c_void_p(n32.data_ptr()), ctypes.c_void_p(labels.data_ptr() if labels is not None else None),
-            tl_arr, steps, _lib.SAMPLE_TYPES[sample_type], _lib.LOOP_KINDS[loop],
-            ctypes.c_void_p(eps.data_ptr() if eps is not None and eps.numel() else None), ctypes.c_uint64(seed),
-            ctypes.c_void_p(out.data_ptr()), B, ctypes.c_void_p(ws.data_ptr()), ws.numel(), 1 if use_graph else 0,
-            self._stream(dev)))
+        _engine.run_x0_sampler(_lib.lib().fg_sampler_run, h, n32, labels, tl_arr, steps, sample_type, loop, eps, seed, out, B, ws, use_graph, dev)
         return out
 
     # ------------------------------------------------------------------------------------------------

@@ -17,24 +17,21 @@ and resample_filter != [1, 1] raise NotImplementedError.  There is no CPU path.
 """
 from __future__ import annotations
 
-import ctypes
 import math
 import os
-from typing import Dict, List, Optional, Set
+from typing import Optional, Set
 
 import numpy as np
 import torch
 import torch.nn as nn
 
 from fastgen_amd import _lib
+from fastgen_amd.networks import _engine
+from fastgen_amd.networks._engine import _Node, ptr, stream
 from fastgen_amd.networks.network import FastGenNetwork, _edm_euler_sample, _fused_sample_args
 from fastgen_amd.networks.noise_schedule import NET_PRED_TYPES
 
 DEFAULT_FP32_MODE = "bf16x3"  # as fastgen_amd.networks.EDM.network
-
-
-class _Node(nn.Module):
-    """Bare container: the parameter tree only has to reproduce the reference's state-dict key paths."""
 
 
 def _mp_weight(w: torch.Tensor, gain=1.0) -> torch.Tensor:
@@ -119,30 +116,12 @@ class EDM2Precond(FastGenNetwork):
         cfg.drop_precond = {None: 0, "input": _lib.FG_DROP_PRECOND_INPUT, "output": _lib.FG_DROP_PRECOND_OUTPUT,
                             "both": _lib.FG_DROP_PRECOND_INPUT | _lib.FG_DROP_PRECOND_OUTPUT}[drop_precond]
         self._cfg = cfg
-        self._engines: Dict[int, ctypes.c_void_p] = {}
-        self._bound_sig: Dict[int, tuple] = {}
-        self._pack_refs: Dict[int, list] = {}
-        self._ws: Dict[int, torch.Tensor] = {}
+        self._eng = _engine.Handles("edm2", cfg)
 
         # the tree of the reference's key paths; names / shapes / order from the library's plan (its state_dict() order)
         self.unet = _Node()
-        self._names: List[str] = []
-        h = self._make_engine(_lib.FG_DTYPE_BF16X3)
-        self._engines[_lib.FG_DTYPE_BF16X3] = h
-        L = _lib.lib()
-        name, ndim, shape = ctypes.c_char_p(), ctypes.c_int(), (ctypes.c_int64 * 4)()
-        self._leafs = []
-        for i in range(L.fg_edm2_num_params(h)):
-            _lib.check(L.fg_edm2_param_info(h, i, ctypes.byref(name), ctypes.byref(ndim), shape))
-            full = name.value.decode()
-            shp = tuple(shape[j] for j in range(ndim.value))
-            self._names.append(full)
-            node, parts = self, full.split(".")
-            for p in parts[:-1]:
-                if p not in node._modules:
-                    node.add_module(p, _Node())
-                node = node._modules[p]
-            leaf = parts[-1]
+
+        def register(node, leaf, full, shp):
             if leaf == "freqs":
                 node.register_buffer(leaf, 2 * np.pi * torch.randn(shp) * bandwidth)
             elif leaf == "phases":
@@ -151,7 +130,8 @@ class EDM2Precond(FastGenNetwork):
                 node.register_parameter(leaf, nn.Parameter(torch.zeros(shp)))
             else:
                 node.register_parameter(leaf, nn.Parameter(torch.randn(shp)))
-            self._leafs.append((node, leaf))
+
+        self._names, self._leafs = _engine.build_tree(self, "edm2", self._eng.get(_lib.FG_DTYPE_BF16X3), register)
         # the logvar head: host-side torch (MPFourier(logvar_channels) + MPConv(logvar_channels, 1))
         self.logvar_fourier = _Node()
         self.logvar_fourier.register_buffer("freqs", 2 * np.pi * torch.randn(logvar_channels) * bandwidth)
@@ -161,28 +141,10 @@ class EDM2Precond(FastGenNetwork):
 
     # ------------------------------------------------------------------------------------------------
     def _make_engine(self, dtype: int):
-        cfg = _lib.fg_edm2_config.from_buffer_copy(self._cfg)
-        cfg.compute_dtype = dtype
-        h = ctypes.c_void_p()
-        _lib.check(_lib.lib().fg_edm2_create(ctypes.byref(cfg), ctypes.byref(h)))
-        return h
-
-    def __del__(self):
-        try:
-            for h in getattr(self, "_engines", {}).values():
-                _lib.lib().fg_edm2_destroy(h)
-        except Exception:
-            pass
+        return self._eng.create(dtype)
 
     def _select_dtype(self) -> int:
-        mode = self.compute_dtype
-        if mode is None and torch.is_autocast_enabled():
-            ad = torch.get_autocast_gpu_dtype()
-            if ad == torch.bfloat16:
-                mode = "bf16"
-            elif ad != torch.float32:
-                raise NotImplementedError(f"autocast dtype {ad} is not implemented (bf16 or fp32)")
-        mode = mode or DEFAULT_FP32_MODE
+        mode = _engine.compute_mode(self.compute_dtype, DEFAULT_FP32_MODE)
         if mode == "fp32":
             raise NotImplementedError("EDM2 runs in the 'bf16x3' and 'bf16' compute modes, not in exact fp32")
         return _lib.DTYPE_NAMES[mode]
@@ -190,39 +152,17 @@ class EDM2Precond(FastGenNetwork):
     def _engine(self, device: torch.device):
         """Engine of the active compute mode with the module's current weights bound and packed."""
         dt = self._select_dtype()
-        if dt not in self._engines:
-            self._engines[dt] = self._make_engine(dt)
-        h = self._engines[dt]
+        h = self._eng.get(dt)
+        # the parameters and the Fourier buffers in engine order, straight from the leaf modules' dicts
         ts = [leaf._parameters[n] if n in leaf._parameters else leaf._buffers[n] for leaf, n in self._leafs]
-        sig = tuple((p.data_ptr(), p._version, p.dtype) for p in ts)
-        if self._bound_sig.get(dt) != sig:
-            L = _lib.lib()
-            refs = []
-            for n, p in zip(self._names, ts):
-                if p.device.type != "cuda":
-                    raise RuntimeError(f"{n} is on {p.device}; fastgen_amd runs on a HIP GPU only (no CPU path)")
-                q = p.detach()
-                if q.dtype != torch.float32 or not q.is_contiguous():
-                    q = q.to(torch.float32).contiguous()
-                refs.append(q)
-                _lib.check(L.fg_edm2_bind_param(h, n.encode(), ctypes.c_void_p(q.data_ptr()), q.numel()))
-            _lib.check(L.fg_edm2_pack_weights(h, self._stream(device)))
-            self._pack_refs[dt] = refs
-            self._bound_sig[dt] = sig
+        self._eng.bind_in_place(dt, self._names, ts, device)
         _lib.check(_lib.lib().fg_edm2_set_training(h, int(self.training)))
         return dt, h
 
     def _workspace(self, dt: int, h, batch: int, device) -> torch.Tensor:
-        need = _lib.lib().fg_edm2_workspace_bytes(h, batch)
-        ws = self._ws.get(dt)
-        if ws is None or ws.numel() < need or ws.device != device:
-            ws = torch.empty(need, dtype=torch.uint8, device=device)
-            self._ws[dt] = ws
-        return ws
+        return self._eng.workspace(dt, _lib.lib().fg_edm2_workspace_bytes(h, batch), device)
 
-    @staticmethod
-    def _stream(device) -> ctypes.c_void_p:
-        return ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+    _stream = staticmethod(stream)
 
     def _refuse_training(self, x_t: Optional[torch.Tensor] = None):
         if torch.is_grad_enabled() and (any(p.requires_grad for p in self.parameters()) or (x_t is not None and x_t.requires_grad)):
@@ -232,14 +172,7 @@ class EDM2Precond(FastGenNetwork):
             raise NotImplementedError("train() mode with dropout > 0 is not implemented for EDM2 by the fused MI355X path")
 
     def _labels(self, condition, batch: int, device) -> Optional[torch.Tensor]:
-        if self.label_dim == 0 or condition is None:
-            return None  # the library takes emb_label(zeros) = 0, as the reference's zero labels give
-        c = condition.reshape(-1, self.label_dim).to(device=device, dtype=torch.float32)
-        if c.shape[0] == 1 and batch > 1:
-            c = c.expand(batch, -1)
-        if c.shape[0] != batch:
-            raise ValueError(f"condition has {c.shape[0]} rows, expected {batch}")
-        return c.contiguous()
+        return _engine.class_labels(condition, self.label_dim, batch, device)  # (None: emb_label(zeros) = 0, as the reference's zero labels give)
 
     # ------------------------------------------------------------------------------------------------
     @torch.no_grad()
@@ -300,27 +233,18 @@ class EDM2Precond(FastGenNetwork):
             raise TypeError(f"unexpected forward kwargs: {sorted(fwd_kwargs)}")
         self._refuse_training(x_t)
         self._select_dtype()
-        if x_t.device.type != "cuda":
-            raise RuntimeError("fastgen_amd runs on a HIP GPU only (no CPU path); got a tensor on " + str(x_t.device))
+        _engine.require_gpu(x_t)
         R, C = self.img_resolution, self.img_channels
         if x_t.dim() != 4 or tuple(x_t.shape[1:]) != (C, R, R):
             raise ValueError(f"x_t must be [B,{C},{R},{R}], got {tuple(x_t.shape)}")
         B, dev = x_t.shape[0], x_t.device
         x32 = x_t.detach().to(torch.float32).contiguous()
-        t64 = torch.atleast_1d(t.detach()).to(device=dev, dtype=torch.float64)
-        if t64.numel() == 1 and B > 1:
-            t64 = t64.expand(B)
-        t64 = t64.contiguous()
-        if t64.numel() != B:
-            raise ValueError(f"t has {t64.numel()} entries, expected {B}")
+        t64 = _engine.per_sample("t", t, B, dev, torch.float64)
         labels = self._labels(condition, B, dev)
         dt, h = self._engine(dev)
         ws = self._workspace(dt, h, B, dev)
         out = torch.empty_like(x32)
-        _lib.check(_lib.lib().fg_edm2_forward(
-            h, ctypes.c_void_p(x32.data_ptr()), ctypes.c_void_p(t64.data_ptr()),
-            ctypes.c_void_p(labels.data_ptr() if labels is not None else None), ctypes.c_void_p(out.data_ptr()), None, B,
-            ctypes.c_void_p(ws.data_ptr()), ws.numel(), self._stream(dev)))
+        _lib.check(_lib.lib().fg_edm2_forward(h, ptr(x32), ptr(t64), ptr(labels), ptr(out), None, B, ptr(ws), ws.numel(), self._stream(dev)))
         out = out.to(x_t.dtype)
         out = self.noise_scheduler.convert_model_output(x_t, out, t64, src_pred_type=self.net_pred_type, target_pred_type=fwd_pred_type)
         if return_logvar:
@@ -351,11 +275,7 @@ class EDM2Precond(FastGenNetwork):
         self._keep = (n32, labels, eps)  # graph replays read these buffers; keep them alive
         dt, h = self._engine(dev)
         ws = self._workspace(dt, h, B, dev)
-        _lib.check(_lib.lib().fg_edm2_sampler_run(
-            h, ctypes.c_void_p(n32.data_ptr()), ctypes.c_void_p(labels.data_ptr() if labels is not None else None), tl_arr, steps,
-            _lib.SAMPLE_TYPES[sample_type], _lib.LOOP_KINDS[loop],
-            ctypes.c_void_p(eps.data_ptr() if eps is not None and eps.numel() else None), ctypes.c_uint64(seed),
-            ctypes.c_void_p(out.data_ptr()), B, ctypes.c_void_p(ws.data_ptr()), ws.numel(), 1 if use_graph else 0, self._stream(dev)))
+        _engine.run_x0_sampler(_lib.lib().fg_edm2_sampler_run, h, n32, labels, tl_arr, steps, sample_type, loop, eps, seed, out, B, ws, use_graph, dev)
         return out
 
     def sample(self, noise: torch.Tensor, condition: Optional[torch.Tensor] = None, neg_condition: Optional[torch.Tensor] = None,

@@ -23,14 +23,14 @@ from __future__ import annotations
 
 import ctypes
 import weakref
-from typing import Any, Dict, Optional, Set
+from typing import Any, Optional, Set
 
 import torch
 import torch.nn as nn
 
 from fastgen_amd import _lib
-from fastgen_amd.networks import _weights
-from fastgen_amd.networks.EDM import network as _edm
+from fastgen_amd.networks import _engine
+from fastgen_amd.networks._engine import ptr, ptr_nonempty, stream
 from fastgen_amd.networks.network import FastGenNetwork
 from fastgen_amd.networks.noise_schedule import NET_PRED_TYPES
 
@@ -64,27 +64,18 @@ class CausalWan(FastGenNetwork):
         cfg.text_dim, cfg.freq_dim, cfg.ffn_dim, cfg.num_layers = text_dim, freq_dim, ffn_dim, num_layers
         cfg.rope_max_seq_len, cfg.chunk_size, cfg.total_num_frames, cfg.eps = rope_max_seq_len, chunk_size, total_num_frames, eps
         self._cfg, self.in_channels = cfg, in_channels
-        h = ctypes.c_void_p()
-        _lib.check(_lib.lib().fg_wan_create(ctypes.byref(cfg), ctypes.byref(h)))
-        self._h = h
-        self._names, self._bound_sig, self._ws = [], {}, None
+        self._eng = _engine.Handles("wan", cfg)  # one handle: the mode is fixed at construction
+        self._h = self._eng.get(cfg.compute_dtype)
         self._text_key = None  # of the selected cache tag ("pos" outside a forward(cache_tag="neg") call) ...
         self._text_key_other, self._tag = None, "pos"  # ... and the other tag's
-        L = _lib.lib()
-        name, ndim, shape = ctypes.c_char_p(), ctypes.c_int(), (ctypes.c_int64 * 5)()
         g = torch.Generator().manual_seed(0)
-        for i in range(L.fg_wan_num_params(h)):
-            _lib.check(L.fg_wan_param_info(h, i, ctypes.byref(name), ctypes.byref(ndim), shape))
-            full, shp = name.value.decode(), tuple(shape[j] for j in range(ndim.value))
+
+        def register(node, leaf, full, shp):
             if "logvar_linear" in full and not enable_logvar_linear:
-                continue
-            self._names.append(full)
-            node, parts = self, full.split(".")
-            for p in parts[:-1]:
-                if p not in node._modules:
-                    node.add_module(p, _edm._Node())
-                node = node._modules[p]
-            node.register_parameter(parts[-1], nn.Parameter(self._init_value(full, shp, g)))
+                return False
+            node.register_parameter(leaf, nn.Parameter(self._init_value(full, shp, g)))
+
+        self._names, _ = _engine.build_tree(self, "wan", self._h, register)
 
     @staticmethod
     def _init_value(name: str, shape, g) -> torch.Tensor:
@@ -101,24 +92,12 @@ class CausalWan(FastGenNetwork):
             fan_in *= s_
         return (torch.rand(shape, generator=g) * 2 - 1) * fan_in ** -0.5
 
-    def __del__(self):
-        try:
-            _lib.lib().fg_wan_destroy(self._h)
-        except Exception:
-            pass
-
     # ---- library plumbing -------------------------------------------------------------------------------------------------
-    def _stream(self, dev):
-        return ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    _stream = staticmethod(stream)
 
     def _bind(self, dev: torch.device):
-        L = _lib.lib()
         names = [n for n in self._names if "logvar_linear" not in n]
-        changed = _weights.sync_weights(
-            self, names, self._bound_sig, tensors=lambda: dict(self.named_parameters()),
-            bind=lambda n, q: _lib.check(L.fg_wan_bind_param(self._h, n.encode(), ctypes.c_void_p(q.data_ptr()), q.numel())),
-            pack_group=lambda pre, exc: _lib.check(L.fg_wan_pack_group(self._h, pre.encode(), exc.encode() if exc else None, self._stream(dev))))
-        if changed:
+        if self._eng.sync_copies(self, self._cfg.compute_dtype, names, lambda: dict(self.named_parameters()), dev):
             self._text_key = self._text_key_other = None  # the text caches were computed with the previous weights
 
     def fully_shard(self, **kwargs):
@@ -137,9 +116,7 @@ class CausalWan(FastGenNetwork):
         need = _lib.lib().fg_wan_workspace_bytes(self._h, B, F, H, W)
         if need == 0:
             raise ValueError(f"bad chunk shape: batch {B}, frames {F}, {H}x{W} (height and width must be even)")
-        if self._ws is None or self._ws.numel() < need or self._ws.device != dev:
-            self._ws = torch.empty(need, dtype=torch.uint8, device=dev)
-        return self._ws
+        return self._eng.workspace(self._cfg.compute_dtype, need, dev)
 
     def _set_text(self, condition: torch.Tensor, B: int, dev, ws: torch.Tensor) -> None:
         """The text condition: embedded (and its cross-attention k / v cached) once per tensor, as the reference's static cache
@@ -151,8 +128,7 @@ class CausalWan(FastGenNetwork):
         c32 = condition.detach().to(device=dev, dtype=torch.float32).contiguous()
         if c32.shape[0] != B:
             raise ValueError(f"condition batch {c32.shape[0]} != {B}")
-        _lib.check(_lib.lib().fg_wan_set_text(self._h, ctypes.c_void_p(c32.data_ptr()), B, c32.shape[1], ctypes.c_void_p(ws.data_ptr()), ws.numel(),
-                                              self._stream(dev)))
+        _lib.check(_lib.lib().fg_wan_set_text(self._h, ptr(c32), B, c32.shape[1], ptr(ws), ws.numel(), self._stream(dev)))
         self._text_key = (weakref.ref(condition), ver, tuple(condition.shape))
 
     def clear_caches(self) -> None:
@@ -191,8 +167,7 @@ class CausalWan(FastGenNetwork):
         if torch.is_grad_enabled() and (x_t.requires_grad or any(p.requires_grad for p in self.parameters())):
             raise NotImplementedError("fastgen_amd.CausalWan: the backward pass is not implemented; call under torch.no_grad() / "
                                       "torch.inference_mode() (sampling)")
-        if x_t.device.type != "cuda":
-            raise RuntimeError("fastgen_amd runs on a HIP GPU only (no CPU path); got a tensor on " + str(x_t.device))
+        _engine.require_gpu(x_t)
         if condition is None:
             raise ValueError("CausalWan.forward needs the text condition [B, L, text_dim]")
         condition = torch.stack(condition, dim=0) if isinstance(condition, list) else condition
@@ -223,13 +198,10 @@ class CausalWan(FastGenNetwork):
         x32 = x_t.detach().to(torch.float32).contiguous()
         out = torch.empty_like(x32)
         if is_ar:
-            _lib.check(L.fg_wan_forward(self._h, ctypes.c_void_p(x32.data_ptr()), ctypes.c_void_p(ts.data_ptr()), ctypes.c_void_p(out.data_ptr()),
-                                        B, F, H, W, int(cur_start_frame), int(bool(store_kv)), ctypes.c_void_p(ws.data_ptr()), ws.numel(),
-                                        self._stream(dev)))
+            _lib.check(L.fg_wan_forward(self._h, ptr(x32), ptr(ts), ptr(out), B, F, H, W, int(cur_start_frame), int(bool(store_kv)), ptr(ws),
+                                        ws.numel(), self._stream(dev)))
         else:  # teacher / diffusion forcing: all frames under the block-wise causal mask, caches untouched
-            _lib.check(L.fg_wan_forward_block_causal(self._h, ctypes.c_void_p(x32.data_ptr()), ctypes.c_void_p(ts.data_ptr()),
-                                                     ctypes.c_void_p(out.data_ptr()), B, F, H, W, ctypes.c_void_p(ws.data_ptr()), ws.numel(),
-                                                     self._stream(dev)))
+            _lib.check(L.fg_wan_forward_block_causal(self._h, ptr(x32), ptr(ts), ptr(out), B, F, H, W, ptr(ws), ws.numel(), self._stream(dev)))
         return out
 
     # ---- the chunk-by-chunk student loop as one library call ------------------------------------------------------------------
@@ -243,8 +215,7 @@ class CausalWan(FastGenNetwork):
         the head that only fill the caches (`generator_fn_extrapolation`'s bridged segment head); exit_steps: one exit index per chunk
         (`SelfForcingModel.rollout_with_gradient`).  eps: noise videos to inject instead of device draws, [steps - 1 (+ 1 if context_noise
         > 0), B, C, F, H, W].  The caches are empty afterwards, as after the reference's loop."""
-        if x.device.type != "cuda":
-            raise RuntimeError("fastgen_amd runs on a HIP GPU only (no CPU path); got a tensor on " + str(x.device))
+        _engine.require_gpu(x)
         if sample_type not in _lib.SAMPLE_TYPES:
             raise NotImplementedError(f"student_sample_type must be one of 'sde', 'ode' but got {sample_type}")
         if self.net_pred_type not in ("flow", "x0"):
@@ -264,9 +235,7 @@ class CausalWan(FastGenNetwork):
         need = L.fg_wan_sampler_workspace_bytes(self._h, B, F, H, W)
         if need == 0:
             raise ValueError(f"bad video shape: batch {B}, frames {F}, {H}x{W} (height and width must be even)")
-        if self._ws is None or self._ws.numel() < need or self._ws.device != dev:
-            self._ws = torch.empty(need, dtype=torch.uint8, device=dev)
-        ws = self._ws
+        ws = self._eng.workspace(self._cfg.compute_dtype, need, dev)
         self._set_text(condition, B, dev, ws)
         x32 = x if (x.dtype == torch.float32 and x.is_contiguous()) else x.to(torch.float32).contiguous()
         n_eps = max(steps - 1, 0) + (1 if context_noise and context_noise > 0 else 0)
@@ -292,10 +261,8 @@ class CausalWan(FastGenNetwork):
         self._keep = (x32, eps)
         try:
             _lib.check(L.fg_wan_sampler_run(
-                self._h, ctypes.byref(sc), ctypes.c_void_p(x32.data_ptr()), (ctypes.c_double * (steps + 1))(*tl), steps,
-                _lib.SAMPLE_TYPES[sample_type], ex,
-                ctypes.c_void_p(eps.data_ptr() if eps is not None and eps.numel() else None), ctypes.c_uint64(seed), B, F, H, W,
-                ctypes.c_void_p(ws.data_ptr()), ws.numel(), 1 if use_graph else 0, self._stream(dev)))
+                self._h, ctypes.byref(sc), ptr(x32), (ctypes.c_double * (steps + 1))(*tl), steps, _lib.SAMPLE_TYPES[sample_type], ex,
+                ptr_nonempty(eps), ctypes.c_uint64(seed), B, F, H, W, ptr(ws), ws.numel(), 1 if use_graph else 0, self._stream(dev)))
         finally:
             self._text_key = self._text_key_other = None  # the loop ends with clear_caches(): the text is forgotten with them
         if x32 is not x:
@@ -324,8 +291,7 @@ class CausalWan(FastGenNetwork):
         assert self.schedule_type == "rf", f"{self.schedule_type} is not supported"
         if kwargs:
             raise TypeError(f"unexpected sample kwargs: {sorted(kwargs)}")
-        if noise.device.type != "cuda":
-            raise RuntimeError("fastgen_amd runs on a HIP GPU only (no CPU path); got a tensor on " + str(noise.device))
+        _engine.require_gpu(noise)
         if self.net_pred_type != "flow":
             raise NotImplementedError(f"sample() needs a flow-predicting network, got net_pred_type {self.net_pred_type!r}")
         if condition is None:
@@ -354,9 +320,7 @@ class CausalWan(FastGenNetwork):
         need = L.fg_wan_guided_sampler_workspace_bytes(self._h, B, F, H, W, steps, int(guided))
         if need == 0:
             raise ValueError(f"bad video shape or step count: batch {B}, frames {F}, {H}x{W} (height and width must be even), {steps} steps")
-        if self._ws is None or self._ws.numel() < need or self._ws.device != dev:
-            self._ws = torch.empty(need, dtype=torch.uint8, device=dev)
-        ws = self._ws
+        ws = self._eng.workspace(self._cfg.compute_dtype, need, dev)
         self._select_tag("pos")
         self._text_key = None  # (a fresh `text` tensor: embedded for this call)
         self._set_text(text, text.shape[0], dev, ws)
@@ -375,10 +339,9 @@ class CausalWan(FastGenNetwork):
         self._keep = (x32, eps)  # what a graph replay reads
         try:
             _lib.check(L.fg_wan_guided_sampler_run(
-                self._h, ctypes.byref(sc), ctypes.c_void_p(x32.data_ptr()), (ctypes.c_double * steps)(*t_net.tolist()),
-                (ctypes.c_double * (8 * steps))(*table.reshape(-1).tolist()), steps,
-                ctypes.c_void_p(eps.data_ptr() if eps is not None and eps.numel() else None), ctypes.c_uint64(seed), B, F, H, W,
-                ctypes.c_void_p(ws.data_ptr()), ws.numel(), 1 if use_graph else 0, self._stream(dev)))
+                self._h, ctypes.byref(sc), ptr(x32), (ctypes.c_double * steps)(*t_net.tolist()),
+                (ctypes.c_double * (8 * steps))(*table.reshape(-1).tolist()), steps, ptr_nonempty(eps), ctypes.c_uint64(seed), B, F, H, W,
+                ptr(ws), ws.numel(), 1 if use_graph else 0, self._stream(dev)))
         finally:
             self._text_key = self._text_key_other = None  # the loop ends with clear_caches(): the text is forgotten with them
         if x32 is not noise:

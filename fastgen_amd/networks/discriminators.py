@@ -13,6 +13,7 @@ import torch
 from torch import nn
 
 from .. import _lib
+from ._engine import ptr, stream
 
 
 class _HeadFn(torch.autograd.Function):
@@ -26,8 +27,7 @@ class _HeadFn(torch.autograd.Function):
         need = L.fg_disc_edm_workspace_bytes(res, B)
         ws = torch.empty(need, dtype=torch.uint8, device=dev)
         logits = torch.empty(B, dtype=torch.float32, device=dev)
-        _lib.check(L.fg_disc_edm_run(ctypes.c_void_p(f32.data_ptr()), res, arr, ctypes.c_void_p(logits.data_ptr()), None, None, None, B,
-                                     ctypes.c_void_p(ws.data_ptr()), need, ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+        _lib.check(L.fg_disc_edm_run(ptr(f32), res, arr, ptr(logits), None, None, None, B, ptr(ws), need, stream(dev)))
         ctx.res = res
         ctx.save_for_backward(f32, *ps)
         return logits.reshape(B, 1)
@@ -45,10 +45,7 @@ class _HeadFn(torch.autograd.Function):
         ws = torch.empty(need, dtype=torch.uint8, device=dev)
         logits = torch.empty(B, dtype=torch.float32, device=dev)
         dl = dlogits.detach().to(torch.float32).reshape(B).contiguous()
-        _lib.check(L.fg_disc_edm_run(ctypes.c_void_p(f32.data_ptr()), res, arr, ctypes.c_void_p(logits.data_ptr()),
-                                     ctypes.c_void_p(dl.data_ptr()), ctypes.c_void_p(dfeat.data_ptr() if dfeat is not None else None),
-                                     garr, B, ctypes.c_void_p(ws.data_ptr()), need,
-                                     ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+        _lib.check(L.fg_disc_edm_run(ptr(f32), res, arr, ptr(logits), ptr(dl), ptr(dfeat), garr, B, ptr(ws), need, stream(dev)))
         return (dfeat, None, *grads)
 
 
