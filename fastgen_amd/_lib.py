@@ -94,6 +94,7 @@ FG_GEMM_REFUSE_ARG, FG_GEMM_REFUSE_OFFSET, FG_GEMM_REFUSE_FORM, FG_GEMM_REFUSE_P
 SIGNATURES = {
     "fg_last_error": (c_char_p, []),
     "fg_version": (c_char_p, []),
+    "fg_graph_stats": (None, [POINTER(c_uint64), POINTER(c_uint64)]),
     "fg_edm_create": (c_int, [POINTER(fg_edm_config), POINTER(c_void_p)]),
     "fg_edm_destroy": (None, [c_void_p]),
     "fg_edm_num_params": (c_int, [c_void_p]),
@@ -274,6 +275,14 @@ def lib():
             fn.argtypes = args
         _lib = L
     return _lib
+
+
+def graph_stats():
+    """(captures, launches) of `fg_graph_stats`: the hipGraphs the sampler entry points have instantiated and launched in this process.
+    A call replayed its cached graph(s) if `captures` did not move across it."""
+    c, n = c_uint64(), c_uint64()
+    lib().fg_graph_stats(ctypes.byref(c), ctypes.byref(n))
+    return c.value, n.value
 
 
 class FastGenAMDError(RuntimeError):

@@ -2,6 +2,7 @@
 // replay, and the C ABI declared in include/fastgen_amd.h.  Host-side C++ only; every kernel lives in conv/attn/misc.hip.
 #include <hip/hip_runtime.h>
 
+#include <atomic>
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
@@ -274,6 +275,9 @@ struct GraphEntry {
     }
 };
 
+// Process-wide counts of graph_run's work (fg_graph_stats): graphs instantiated, graphs launched.  launches - captures = replays.
+std::atomic<uint64_t> g_graph_captures{0}, g_graph_launches{0};
+
 // Capture `enqueue(capture_stream)` into `e` unless its key matches, then launch it on s.  The capture stream only records (the legacy
 // default stream cannot be captured); the graph runs on the caller's stream.
 template <typename F>
@@ -292,9 +296,11 @@ int graph_run(GraphEntry& e, const std::vector<int64_t>& key, hipStream_t& cap, 
         if (err != hipSuccess) return fail(FG_EHIP, "hipStreamEndCapture failed: %s", hipGetErrorString(err));
         e.graph = g;
         HIP_TRY(hipGraphInstantiate(&e.exec, e.graph, nullptr, nullptr, 0));
+        g_graph_captures.fetch_add(1, std::memory_order_relaxed);
         e.key = key;
     }
     HIP_TRY(hipGraphLaunch(e.exec, s));
+    g_graph_launches.fetch_add(1, std::memory_order_relaxed);
     return FG_OK;
 }
 
@@ -1055,6 +1061,10 @@ extern "C" {
 
 const char* fg_last_error(void) { return g_err.c_str(); }
 const char* fg_version(void) { return "fastgen_amd 0.1 gfx950"; }
+void fg_graph_stats(uint64_t* captures, uint64_t* launches) {
+    if (captures) *captures = g_graph_captures.load(std::memory_order_relaxed);
+    if (launches) *launches = g_graph_launches.load(std::memory_order_relaxed);
+}
 
 int fg_edm_create(const fg_edm_config* cfg, fg_edm** out) {
     if (!cfg || !out) return fail(FG_EINVAL, "null argument");

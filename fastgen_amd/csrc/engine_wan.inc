@@ -33,6 +33,7 @@ struct fg_wan : HandleBase {
     SamplerCache sampler;
     std::vector<GraphEntry> chunk_graphs;
     int cache_B = 0, cache_cap = 0, text_B = 0, text_L = 0;
+    size_t kv2_rows = 0;  // text rows (batch * text_len) the blocks' kv2 are allocated for; outlives clear_caches, which only zeroes text_B
     int stored_rows = 0;  // cache rows [0, stored_rows) hold K / V that a store_kv = 1 call wrote (the reference's per_tag["len"], network_causal.py:385-390)
     // The reference keeps one cache sub-dict per cache_tag ("pos" / "neg", network_causal.py:331-412).  The fields above and the blocks'
     // kc / vc / kv2 are the SELECTED tag's set; the other tag's set waits here (fg_wan_select_cache_tag swaps them).  It is empty until
@@ -40,6 +41,7 @@ struct fg_wan : HandleBase {
     struct CacheSet {
         std::vector<void*> kc, vc, kv2;  // per block
         int cache_B = 0, cache_cap = 0, text_B = 0, text_L = 0, stored_rows = 0;
+        size_t kv2_rows = 0;
     };
     CacheSet other;
     int tag = 0;
@@ -56,6 +58,12 @@ struct fg_wan : HandleBase {
     std::vector<char> pack_only, dirty;
     const float* P(int idx) const { return idx < 0 ? nullptr : (own[idx] ? own[idx] : params[idx].ptr); }
     bool is_logvar(int idx) const { return params[idx].name.find("logvar_linear") != std::string::npos; }
+    // Before a cache buffer is freed: the chunk graphs name every block's kc / vc / kv2 and their keys hold block 0's addresses only,
+    // which the allocator may hand out again - no graph outlives a buffer it was captured on.
+    void drop_graphs() {
+        for (GraphEntry& g : chunk_graphs) g.drop();
+        for (GraphEntry& g : guided_graphs) g.drop();
+    }
 };
 
 namespace {
@@ -411,6 +419,7 @@ int fg_wan_select_cache_tag(fg_wan* h, int tag) {
     std::swap(h->cache_cap, o.cache_cap);
     std::swap(h->text_B, o.text_B);
     std::swap(h->text_L, o.text_L);
+    std::swap(h->kv2_rows, o.kv2_rows);
     std::swap(h->stored_rows, o.stored_rows);
     h->tag = tag;
     return FG_OK;
@@ -428,13 +437,18 @@ int fg_wan_set_text(fg_wan* h, const float* text, int batch, int text_len, void*
     void* tb = ws;
     void* e1 = ws + ((M * Td * 2 + 255) & ~(size_t)255);
     void* e2 = (char*)e1 + ((M * D * 2 + 255) & ~(size_t)255);
-    if (h->text_B != batch || h->text_L != text_len) {
+    // (the sampler loops end with clear_caches, so every call sets its text again: the buffers stay where they are while their size
+    // does, and the chunk graphs that name them stay valid)
+    if (h->kv2_rows != M) {
+        h->drop_graphs();
+        h->kv2_rows = 0;
         for (fg_wan::Blk& b : h->blocks) {
             h->free(b.kv2);
             b.kv2 = nullptr;
             int rc = h->alloc(&b.kv2, M * 2 * D * 2);
             if (rc) return rc;
         }
+        h->kv2_rows = M;
     }
     // text_embedder: Linear - GELU(tanh) - Linear (PixArtAlphaTextProjection); then per block k = norm_k(to_k(ctx)), v = to_v(ctx)
     HIP_TRY(launch_cvt_rows_bf16(text, tb, (int64_t)(M * Td), s));
@@ -457,6 +471,8 @@ namespace {
 int wan_ensure_caches(fg_wan* h, int batch, int height, int width, hipStream_t s) {
     const int cap = h->cfg.total_num_frames * (height / 2) * (width / 2), D = h->D;
     if (h->cache_B == batch && h->cache_cap == cap) return FG_OK;
+    h->drop_graphs();
+    h->cache_B = h->cache_cap = 0;  // (nothing valid until every block has its new buffers)
     for (fg_wan::Blk& b : h->blocks) {
         h->free(b.kc);
         h->free(b.vc);

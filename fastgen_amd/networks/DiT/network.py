@@ -29,7 +29,7 @@ import torch.nn as nn
 
 from fastgen_amd import _lib
 from fastgen_amd.networks import _engine
-from fastgen_amd.networks._engine import ptr, ptr_nonempty, stream
+from fastgen_amd.networks._engine import ptr, stream
 from fastgen_amd.networks.EDM import network as _edm
 from fastgen_amd.networks.network import FastGenNetwork, _fused_sample_args
 from fastgen_amd.networks.noise_schedule import NET_PRED_TYPES
@@ -340,14 +340,17 @@ class DiT(FastGenNetwork):
         dt, h = self._engine(dev)
         L = _lib.lib()
         ws = self._workspace(dt, L.fg_dit_sampler_workspace_bytes(h, B, int(neg is not None)), dev)
-        out = torch.empty_like(n32)
-        self._keep = (n32, cls, neg, eps, out)  # graph replays read these buffers; keep them alive
-        # (this call has always passed null for a tensor without elements, not only for `eps`)
+        # every device pointer of the call is in the graph's key: the call runs on the handle's staging tensors, so that a second call
+        # with the same shapes replays the graph whatever tensors the caller passes
+        st = self._eng.staged
+        n32, cls, neg, eps = st(dt, "noise", n32), st(dt, "labels", cls), st(dt, "neg", neg), st(dt, "eps", eps)
+        out = st(dt, "out", like=n32)
+        # (a tensor without elements has no staging tensor: the call passes null for it, an `eps` of a one-step loop for one)
         _lib.check(L.fg_dit_sampler_run(
-            h, ctypes.byref(sc), ptr_nonempty(n32), ptr_nonempty(cls), ptr_nonempty(neg), tl_arr, steps, _lib.SAMPLE_TYPES[sample_type],
-            _lib.LOOP_KINDS[loop], ptr_nonempty(eps), ctypes.c_uint64(seed), ptr_nonempty(out), B, ptr(ws), ws.numel(),
+            h, ctypes.byref(sc), ptr(n32), ptr(cls), ptr(neg), tl_arr, steps, _lib.SAMPLE_TYPES[sample_type],
+            _lib.LOOP_KINDS[loop], ptr(eps), ctypes.c_uint64(seed), ptr(out), B, ptr(ws), ws.numel(),
             1 if use_graph else 0, stream(dev)))
-        return out.to(noise.dtype)
+        return out.to(noise.dtype, copy=True)  # the caller's own tensor
 
     @torch.no_grad()
     def sample(self, noise: torch.Tensor, condition: Optional[torch.Tensor] = None, neg_condition: Optional[torch.Tensor] = None,

@@ -788,17 +788,13 @@ class EDMPrecond(FastGenNetwork):
         n32, steps, tl_arr, eps, seed = _fused_sample_args(noise, t_list, sample_type, eps, seed)
         B, dev = noise.shape[0], noise.device
         labels = self._labels(condition, B, dev)
-        if out is None:
-            out = torch.empty_like(n32)
-        self._keep = (n32, labels, eps)  # graph replays read these buffers; keep them alive
-        self._fsdp_call(lambda: self._sampler_call(n32, labels, tl_arr, steps, sample_type, loop, eps, seed, out, B, dev, use_graph))
-        return out
+        return self._fsdp_call(lambda: self._sampler_call(n32, labels, tl_arr, steps, sample_type, loop, eps, seed, out, B, dev, use_graph))
 
     def _sampler_call(self, n32, labels, tl_arr, steps, sample_type, loop, eps, seed, out, B, dev, use_graph):
         dt, h = self._engine(dev)
         ws = self._workspace(dt, h, B, dev)
-        _engine.run_x0_sampler(_lib.lib().fg_sampler_run, h, n32, labels, tl_arr, steps, sample_type, loop, eps, seed, out, B, ws, use_graph, dev)
-        return out
+        return _engine.run_x0_sampler(_lib.lib().fg_sampler_run, self._eng, dt, h, n32, labels, tl_arr, steps, sample_type, loop, eps, seed, out,
+                                      B, ws, use_graph, dev)
 
     # ------------------------------------------------------------------------------------------------
     def sample(self, noise: torch.Tensor, condition: Optional[torch.Tensor] = None,

@@ -270,13 +270,10 @@ class EDM2Precond(FastGenNetwork):
         n32, steps, tl_arr, eps, seed = _fused_sample_args(noise, t_list, sample_type, eps, seed)
         B, dev = noise.shape[0], noise.device
         labels = self._labels(condition, B, dev)
-        if out is None:
-            out = torch.empty_like(n32)
-        self._keep = (n32, labels, eps)  # graph replays read these buffers; keep them alive
         dt, h = self._engine(dev)
         ws = self._workspace(dt, h, B, dev)
-        _engine.run_x0_sampler(_lib.lib().fg_edm2_sampler_run, h, n32, labels, tl_arr, steps, sample_type, loop, eps, seed, out, B, ws, use_graph, dev)
-        return out
+        return _engine.run_x0_sampler(_lib.lib().fg_edm2_sampler_run, self._eng, dt, h, n32, labels, tl_arr, steps, sample_type, loop, eps, seed,
+                                      out, B, ws, use_graph, dev)
 
     def sample(self, noise: torch.Tensor, condition: Optional[torch.Tensor] = None, neg_condition: Optional[torch.Tensor] = None,
                guidance_scale: Optional[float] = 5.0, num_steps: int = 50, **kwargs) -> torch.Tensor:

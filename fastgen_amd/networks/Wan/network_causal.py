@@ -30,7 +30,7 @@ import torch.nn as nn
 
 from fastgen_amd import _lib
 from fastgen_amd.networks import _engine
-from fastgen_amd.networks._engine import ptr, ptr_nonempty, stream
+from fastgen_amd.networks._engine import ptr, stream
 from fastgen_amd.networks.network import FastGenNetwork
 from fastgen_amd.networks.noise_schedule import NET_PRED_TYPES
 
@@ -258,15 +258,17 @@ class CausalWan(FastGenNetwork):
             n_chunks = max(1, F // self.chunk_size)
             if len(exit_steps) < n_chunks:
                 raise ValueError(f"exit_steps must hold one index per chunk ({n_chunks})")
-        self._keep = (x32, eps)
+        # the latents and the injected noise are in the chunk graphs' keys by address: the loop runs on the handle's staging tensors,
+        # so that a second call with the same shapes replays the graphs whatever tensors the caller passes
+        dt = self._cfg.compute_dtype
+        xs, eps = self._eng.staged(dt, "x", x32), self._eng.staged(dt, "eps", eps)
         try:
             _lib.check(L.fg_wan_sampler_run(
-                self._h, ctypes.byref(sc), ptr(x32), (ctypes.c_double * (steps + 1))(*tl), steps, _lib.SAMPLE_TYPES[sample_type], ex,
-                ptr_nonempty(eps), ctypes.c_uint64(seed), B, F, H, W, ptr(ws), ws.numel(), 1 if use_graph else 0, self._stream(dev)))
+                self._h, ctypes.byref(sc), ptr(xs), (ctypes.c_double * (steps + 1))(*tl), steps, _lib.SAMPLE_TYPES[sample_type], ex,
+                ptr(eps), ctypes.c_uint64(seed), B, F, H, W, ptr(ws), ws.numel(), 1 if use_graph else 0, self._stream(dev)))
         finally:
             self._text_key = self._text_key_other = None  # the loop ends with clear_caches(): the text is forgotten with them
-        if x32 is not x:
-            x.copy_(x32)
+        x.copy_(xs)
         return x
 
     # ---- the guided teacher sampler as one library call ---------------------------------------------------------------------
@@ -336,14 +338,14 @@ class CausalWan(FastGenNetwork):
         sc.t_scale = float(self.noise_scheduler.num_steps)
         sc.context_noise = cn
         sc.guidance = int(guided)
-        self._keep = (x32, eps)  # what a graph replay reads
+        dt = self._cfg.compute_dtype  # (staging tensors as in student_sample)
+        xs, eps = self._eng.staged(dt, "x", x32), self._eng.staged(dt, "eps", eps)
         try:
             _lib.check(L.fg_wan_guided_sampler_run(
-                self._h, ctypes.byref(sc), ptr(x32), (ctypes.c_double * steps)(*t_net.tolist()),
-                (ctypes.c_double * (8 * steps))(*table.reshape(-1).tolist()), steps, ptr_nonempty(eps), ctypes.c_uint64(seed), B, F, H, W,
+                self._h, ctypes.byref(sc), ptr(xs), (ctypes.c_double * steps)(*t_net.tolist()),
+                (ctypes.c_double * (8 * steps))(*table.reshape(-1).tolist()), steps, ptr(eps), ctypes.c_uint64(seed), B, F, H, W,
                 ptr(ws), ws.numel(), 1 if use_graph else 0, self._stream(dev)))
         finally:
             self._text_key = self._text_key_other = None  # the loop ends with clear_caches(): the text is forgotten with them
-        if x32 is not noise:
-            noise.copy_(x32)
+        noise.copy_(xs)
         return noise

@@ -20,11 +20,6 @@ def ptr(a: Optional[torch.Tensor]) -> ctypes.c_void_p:
     return ctypes.c_void_p(a.data_ptr() if a is not None else None)
 
 
-def ptr_nonempty(a: Optional[torch.Tensor]) -> ctypes.c_void_p:
-    """As `ptr`, and a tensor without elements -> null too (an injected `eps` of a one-step loop)."""
-    return ctypes.c_void_p(a.data_ptr() if a is not None and a.numel() else None)
-
-
 def stream(device) -> ctypes.c_void_p:
     return ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
 
@@ -59,10 +54,17 @@ def class_labels(condition: Optional[torch.Tensor], label_dim: int, batch: int, 
     return c.contiguous()
 
 
-def run_x0_sampler(run, h, n32, labels, tl_arr, steps: int, sample_type: str, loop: str, eps, seed: int, out, B: int, ws, use_graph, device):
-    """One call of `fg_sampler_run` / `fg_edm2_sampler_run` (`run`: one signature, the fused few-step loop of the two U-Nets)."""
-    _lib.check(run(h, ptr(n32), ptr(labels), tl_arr, steps, _lib.SAMPLE_TYPES[sample_type], _lib.LOOP_KINDS[loop], ptr_nonempty(eps),
-                   ctypes.c_uint64(seed), ptr(out), B, ptr(ws), ws.numel(), 1 if use_graph else 0, stream(device)))
+def run_x0_sampler(run, eng: "Handles", dt: int, h, n32, labels, tl_arr, steps: int, sample_type: str, loop: str, eps, seed: int, out, B: int, ws,
+                   use_graph, device) -> torch.Tensor:
+    """One call of `fg_sampler_run` / `fg_edm2_sampler_run` (`run`: one signature, the fused few-step loop of the two U-Nets) on the
+    staging tensors of handle `dt` (`Handles.staged`): noise, labels and injected eps are copied in, and without a caller's `out` the
+    result is copied out of the staged output into a tensor of the caller's.  A caller's `out` is written in place: its address is
+    the caller's to keep stable."""
+    n32, labels, eps = eng.staged(dt, "noise", n32), eng.staged(dt, "labels", labels), eng.staged(dt, "eps", eps)
+    dst = out if out is not None else eng.staged(dt, "out", like=n32)
+    _lib.check(run(h, ptr(n32), ptr(labels), tl_arr, steps, _lib.SAMPLE_TYPES[sample_type], _lib.LOOP_KINDS[loop], ptr(eps),
+                   ctypes.c_uint64(seed), ptr(dst), B, ptr(ws), ws.numel(), 1 if use_graph else 0, stream(device)))
+    return out if out is not None else dst.clone()
 
 
 # ---- compute mode ---------------------------------------------------------------------------------------------------------------
@@ -116,7 +118,8 @@ def build_tree(root: nn.Module, family: str, h, register: Callable) -> Tuple[Lis
 # ---- the handles of one module ----------------------------------------------------------------------------------------------------
 class Handles:
     """The library handles of one network module, by compute mode, with what belongs to each: the signature of the weights it has
-    bound, the tensors kept alive for it, and the cached workspaces (by mode, or "bwd").  Destroyed with the module."""
+    bound, the tensors kept alive for it, the cached workspaces (by mode, or "bwd") and the staging tensors of the fused sampler
+    loops.  Destroyed with the module."""
 
     def __init__(self, family: str, cfg):
         self.family, self.cfg = family, cfg
@@ -124,6 +127,7 @@ class Handles:
         self.bound_sig: Dict[int, object] = {}
         self.pack_refs: Dict[int, list] = {}
         self.ws: Dict[object, torch.Tensor] = {}
+        self.staging: Dict[tuple, torch.Tensor] = {}
 
     def _fn(self, what: str):
         return getattr(_lib.lib(), f"fg_{self.family}_{what}")
@@ -158,6 +162,24 @@ class Handles:
         if ws is None or ws.numel() < need or ws.device != device:
             ws = self.ws[key] = torch.empty(need, dtype=torch.uint8, device=device)
         return ws
+
+    def staged(self, dt: int, role: str, src: Optional[torch.Tensor] = None, like: Optional[torch.Tensor] = None) -> Optional[torch.Tensor]:
+        """The persistent device tensor of handle `dt` for argument `role` ("noise", "labels", "neg", "eps", "out", "x") of a fused
+        sampler call, one per shape: the library keys its cached hipGraph on the ADDRESS of every such argument, so a call replays the
+        graph only if it passes the buffers the capture saw - the callers' own tensors are new ones on every call.  `src`: copied in
+        on the current stream (None, or no elements -> None: the call passes null); `like`: an output, returned as it is - the caller
+        copies out of it.  Stream order on the caller's stream keeps one call's copies and launches apart from the next call's."""
+        t = src if src is not None else like
+        if t is None or t.numel() == 0:
+            return None
+        key = (dt, role, tuple(t.shape), t.dtype, t.device)
+        buf = self.staging.get(key)
+        if buf is None:
+            with torch.inference_mode(False):  # (an inference tensor could not be written by a later call under no_grad)
+                buf = self.staging[key] = torch.empty(t.shape, dtype=t.dtype, device=t.device)
+        if src is not None:
+            buf.copy_(src)
+        return buf
 
     def bind_in_place(self, dt: int, names: List[str], ts: List[torch.Tensor], device) -> None:
         """For the engines that borrow the parameters' device pointers (EDM, EDM2).  Is what handle `dt` bound still what the module

@@ -109,6 +109,10 @@ typedef struct fg_edm fg_edm; /* opaque */
 FG_API const char* fg_last_error(void);
 /* "fastgen_amd <version> gfx950" */
 FG_API const char* fg_version(void);
+/* Process-wide, read-only counts of the sampler entry points' hipGraph work (either pointer may be null): `captures` graphs
+ * instantiated (a use_graph call whose cached graph did not match its arguments), `launches` graphs launched.  A replay is a launch
+ * without a capture: launches - captures.  Read the two before and after a call and take the differences. */
+FG_API void fg_graph_stats(uint64_t* captures, uint64_t* launches);
 
 /* ---- network object: replaces EDMPrecond.__init__ / state-dict ownership (EDM/network.py:808-839) ---- */
 FG_API int fg_edm_create(const fg_edm_config* cfg, fg_edm** out);
@@ -555,7 +559,9 @@ FG_API int fg_wan_clear_caches(fg_wan* h, void* stream);
  * A graph captured by a sampler loop under one tag is not replayed under the other (its key holds the set's pointers). */
 FG_API int fg_wan_select_cache_tag(fg_wan* h, int tag);
 /* The text condition: text [B, text_len, text_dim] fp32 (the text encoder's output).  Runs condition_embedder.text_embedder and
- * every block's attn2 k / v projections (+ norm_k) once: the reference's static cross-attention cache (:331-360). */
+ * every block's attn2 k / v projections (+ norm_k) once: the reference's static cross-attention cache (:331-360).  The caches are
+ * rewritten in place while batch x text_len stays the same (the sampler loops' cached graphs name them); a change of that size
+ * reallocates them and drops those graphs. */
 FG_API int fg_wan_set_text(fg_wan* h, const float* text, int batch, int text_len, void* workspace, size_t workspace_bytes, void* stream);
 /* One network call of the autoregressive sampler: `CausalWan.forward(x_t, t, cache_tag="pos", cur_start_frame, store_kv, is_ar=True)`
  * up to the raw network output (:1077-1160; the flow -> x0 conversion stays with the caller).  x_t, out: [B, C, frames, H, W] fp32;

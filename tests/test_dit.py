@@ -230,9 +230,15 @@ def test_fused_sampler_loops_equal_the_per_step_loops(tag, mode, B, monkeypatch)
         got = gf(net, noise, student_sample_steps=4, condition=cond, student_sample_type=kind, eps=eps)
         assert torch.isfinite(got).all() and torch.equal(got, want), kind
         assert torch.equal(gf(net, noise, student_sample_steps=4, condition=cond, student_sample_type=kind, eps=eps, use_graph=False), want)
-    # the cached graph replayed with another timestep list (same steps / zero pattern), then 1 step
+    # the cached graph replayed with another timestep list (same steps / zero pattern; the same arguments otherwise, `eps` among them:
+    # its address is in the graph's key), then 1 step
+    from fastgen_amd import _lib
+
     tl2 = [0.9, 0.61, 0.33, 0.12, 0.0]
-    assert torch.equal(gf(net, noise, student_sample_steps=4, t_list=tl2, condition=cond, student_sample_type="ode"), per_step(FastGenModel, 4, "ode", tl2))
+    captures = _lib.graph_stats()[0]
+    got = gf(net, noise, student_sample_steps=4, t_list=tl2, condition=cond, student_sample_type="ode", eps=eps)
+    assert _lib.graph_stats()[0] == captures, "the call with another timestep list captured a new graph"
+    assert torch.equal(got, per_step(FastGenModel, 4, "ode", tl2))
     assert torch.equal(gf(net, noise, student_sample_steps=1, condition=cond), per_step(FastGenModel, 1, "sde"))
     # device RNG: seed control
     a = gf(net, noise, student_sample_steps=3, condition=cond, seed=5)
@@ -255,8 +261,6 @@ def test_fused_sampler_loops_equal_the_per_step_loops(tag, mode, B, monkeypatch)
         want = _euler_per_step(net, noise, cond, None, 1.0, 3)
         assert torch.equal(net.sample(noise, condition=cond, guidance_scale=None, num_steps=3), want)
     # refused, not approximated
-    from fastgen_amd import _lib
-
     with pytest.raises(_lib.FastGenAMDError):
         gf(net, noise, student_sample_steps=1, t_list=[1.5, 0.0], condition=cond)
     if not CFGS[tag].r_timestep:

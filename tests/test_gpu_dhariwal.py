@@ -5,6 +5,7 @@ import os
 import pytest
 import torch
 
+from fastgen_amd import _lib
 from fastgen_amd.methods.model import FastGenModel
 from fastgen_amd.networks.EDM.network import EDMPrecond
 
@@ -91,7 +92,9 @@ def test_graph_replay_bit_equal_to_eager(narrow, mode):
     tl = net.noise_scheduler.get_t_list(4, device="cpu")
     eager = net.few_step_sample(noise, cond, tl, sample_type="sde", seed=7, use_graph=False).clone()
     g1 = net.few_step_sample(noise, cond, tl, sample_type="sde", seed=7, use_graph=True).clone()
-    g2 = net.few_step_sample(noise, cond, tl, sample_type="sde", seed=7, use_graph=True).clone()  # a replay
+    captures, launches = _lib.graph_stats()
+    g2 = net.few_step_sample(noise, cond, tl, sample_type="sde", seed=7, use_graph=True).clone()
+    assert _lib.graph_stats() == (captures, launches + 1)  # a replay
     assert torch.equal(eager, g1) and torch.equal(g1, g2)
     # the per-step loop through forward() and the noise schedule, with the same device noise
     eps = torch.randn(3, 3, 3, 64, 64, generator=torch.Generator().manual_seed(5)).cuda()

@@ -149,11 +149,14 @@ def test_graph_replay_bit_equal_to_eager(narrow, mode):
     tl = net.noise_scheduler.get_t_list(4, device="cpu")
     eager = net.few_step_sample(noise, cond, tl, sample_type="sde", seed=7, use_graph=False).clone()
     g1 = net.few_step_sample(noise, cond, tl, sample_type="sde", seed=7, use_graph=True).clone()
+    captures, launches = _lib.graph_stats()
     g2 = net.few_step_sample(noise, cond, tl, sample_type="sde", seed=7, use_graph=True).clone()
+    assert _lib.graph_stats() == (captures, launches + 1)
     assert torch.equal(eager, g1) and torch.equal(g1, g2)
     # the same graph replayed with a new t_list (same zero pattern) and seed equals an eager run with those
     tl2 = torch.tensor([60.0, 9.0, 2.0, 0.3, 0.0], dtype=torch.float64)
     g3 = net.few_step_sample(noise, cond, tl2, sample_type="sde", seed=11, use_graph=True).clone()
+    assert _lib.graph_stats() == (captures, launches + 2)
     e3 = net.few_step_sample(noise, cond, tl2, sample_type="sde", seed=11, use_graph=False).clone()
     assert torch.equal(g3, e3) and not torch.equal(g3, g1)
     # the per-step loop through forward() and the noise schedule, with the same injected noise

@@ -256,8 +256,13 @@ def test_sampler_against_reference_golden(nets, golden_dir, mode):
     check(gf(net, noise, condition=cond, student_sample_steps=2, t_list=[40.0, 1.5, 0.0], student_sample_type="ode"),
           fx["out_tlist"], mode, "custom t_list")
     # graph replay with NEW timesteps reuses the captured graph (timesteps live in device memory)
+    captures = _lib.graph_stats()[0]
     check(gf(net, noise, condition=cond, student_sample_steps=2, t_list=[40.0, 1.5, 0.0], student_sample_type="ode"),
           fx["out_tlist"], mode, "custom t_list replay")
+    other = gf(net, noise, condition=cond, student_sample_steps=2, t_list=[30.0, 0.7, 0.0], student_sample_type="ode")
+    assert _lib.graph_stats()[0] == captures, "a call with the same or with new timesteps captured a new graph"
+    assert torch.equal(other, gf(net, noise, condition=cond, student_sample_steps=2, t_list=[30.0, 0.7, 0.0], student_sample_type="ode",
+                                 use_graph=False))
     # per-step x0 predictions of the sde trace through the module's forward (generic loop == fused loop)
     with torch.inference_mode():
         tl = net.noise_scheduler.get_t_list(4).to(dev())

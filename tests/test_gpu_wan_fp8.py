@@ -21,6 +21,8 @@ import ctypes
 import pytest
 import torch
 
+from fastgen_amd import _lib
+
 import test_wan as TW
 import wan_fp8_ref as W
 from oracle import wan_ref as R
@@ -124,7 +126,9 @@ def test_student_loop_graph_eager_and_per_call_agree_bit_for_bit():
         want = TW._per_call_loop(net, lat.clone(), tl, text, "ode")
         got = net.student_sample(lat.clone(), tl, text, sample_type="ode")
         assert torch.isfinite(got).all() and torch.equal(got, want)
+        captures, launches = _lib.graph_stats()
         assert torch.equal(net.student_sample(lat.clone(), tl, text, sample_type="ode"), want)  # replay of the cached chunk graphs
+        assert _lib.graph_stats() == (captures, launches + 2)
         assert torch.equal(net.student_sample(lat.clone(), tl, text, sample_type="ode", use_graph=False), want)
         # ... and it is the fp8 arithmetic that ran: the bf16 module on the same weights gives another video
         assert not torch.equal(net16.student_sample(lat.clone(), tl, text, sample_type="ode"), want)
@@ -137,7 +141,9 @@ def test_guided_sampler_graph_and_eager_agree_bit_for_bit():
     with torch.inference_mode():
         a = net.sample(noise.clone(), **kw)
         assert torch.isfinite(a).all()
+        captures, launches = _lib.graph_stats()
         assert torch.equal(net.sample(noise.clone(), **kw), a)  # the cached graphs
+        assert _lib.graph_stats() == (captures, launches + 2)
         assert torch.equal(net.sample(noise.clone(), use_graph=False, **kw), a)
         assert not torch.equal(net16.sample(noise.clone(), **kw), a)
 

@@ -531,3 +531,34 @@ def test_sampler_entry_points_share_their_argument_checks():
         assert rc == 2 and b"not packed" in L.fg_last_error(), L.fg_last_error()
     finally:
         L.fg_edm_destroy(h_edm), L.fg_edm_destroy(h_mf), L.fg_edm2_destroy(h_edm2), L.fg_dit_destroy(h_dit)
+
+
+def test_staging_tensors_keep_their_addresses_across_calls():
+    """`Handles.staged` (the wrappers' side of a graph replay: the library keys a cached graph on its arguments' addresses): one
+    persistent tensor per (handle, role, shape), the argument copied in; nothing for an absent or empty argument; a tensor first made
+    under inference_mode takes the copy of a later call under no_grad."""
+    from fastgen_amd.networks._engine import Handles
+
+    eng = Handles("dit", _lib.fg_dit_config())
+    a, b = torch.randn(2, 3), torch.randn(2, 3)
+    with torch.inference_mode():
+        s1 = eng.staged(0, "noise", a)
+    assert torch.equal(s1, a) and s1.data_ptr() != a.data_ptr()
+    with torch.no_grad():
+        s2 = eng.staged(0, "noise", b)
+    assert s2 is s1 and torch.equal(s1, b)
+    assert eng.staged(0, "noise", torch.randn(3, 3)) is not s1 and eng.staged(1, "noise", a) is not s1 and eng.staged(0, "eps", a) is not s1
+    assert eng.staged(0, "eps", None) is None and eng.staged(0, "eps", torch.empty(0, 2, 3)) is None
+    out = eng.staged(0, "out", like=a)
+    assert out.shape == a.shape and eng.staged(0, "out", like=b) is out
+    ids = torch.tensor([1, 2])
+    assert eng.staged(0, "labels", ids).dtype == torch.int64
+
+
+def test_graph_stats_is_read_only_and_takes_null_pointers():
+    c, n = _lib.graph_stats()
+    assert n >= c >= 0
+    _lib.lib().fg_graph_stats(None, None)
+    one = ctypes.c_uint64(123)
+    _lib.lib().fg_graph_stats(None, ctypes.byref(one))
+    assert one.value == n and _lib.graph_stats() == (c, n)

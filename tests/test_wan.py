@@ -366,10 +366,16 @@ def test_fused_student_loop_equals_the_per_call_loop():
         want = _per_call_loop(net, lat.clone(), tl, text, "ode")
         got = net.student_sample(lat.clone(), tl, text, sample_type="ode")
         assert torch.isfinite(got).all() and torch.equal(got, want)
+        from fastgen_amd import _lib
+
+        captures, launches = _lib.graph_stats()
         assert torch.equal(net.student_sample(lat.clone(), tl, text, sample_type="ode"), want)  # replay of the cached chunk graphs
+        assert _lib.graph_stats() == (captures, launches + 2)
         assert torch.equal(net.student_sample(lat.clone(), tl, text, sample_type="ode", use_graph=False), want)
         tl2 = torch.tensor([0.95, 0.6, 0.2, 0.0], dtype=torch.float64, device="cuda")
-        assert torch.equal(net.student_sample(lat.clone(), tl2, text, sample_type="ode"), _per_call_loop(net, lat.clone(), tl2, text, "ode"))
+        want2 = _per_call_loop(net, lat.clone(), tl2, text, "ode")
+        assert torch.equal(net.student_sample(lat.clone(), tl2, text, sample_type="ode"), want2)  # ... replayed with other timesteps
+        assert _lib.graph_stats() == (captures, launches + 4)
         want = _per_call_loop(net, lat.clone(), tl, text, "sde", context_noise=0.1, eps=eps)
         got = net.student_sample(lat.clone(), tl, text, sample_type="sde", context_noise=0.1, eps=eps)
         assert torch.equal(got, want)

@@ -14,6 +14,7 @@ import math
 import pytest
 import torch
 
+from fastgen_amd import _lib
 from fastgen_amd.networks.Wan import solvers
 from oracle import wan_ref as R
 import wan_guided_ref as G
@@ -274,12 +275,15 @@ def test_fused_guided_loop_equals_the_per_call_loop(solver):
         want = _per_call_guided_loop(net, noise.clone(), cond, neg, 5.0, 3, 5.0, solver)
         got = net.sample(noise.clone(), cond, neg, **kw)
         assert torch.isfinite(got).all() and torch.equal(got, want)
+        captures, launches = _lib.graph_stats()
         assert torch.equal(net.sample(noise.clone(), cond, neg, **kw), want)  # replay of the cached chunk graphs
+        assert _lib.graph_stats() == (captures, launches + 2)
         assert torch.equal(net.sample(noise.clone(), cond, neg, use_graph=False, **kw), want)
         # the same graphs with another table and guidance scale: device memory, nothing baked in
         want2 = _per_call_guided_loop(net, noise.clone(), cond, neg, 2.5, 3, 3.0, solver)
         assert not torch.equal(want2, want)
         assert torch.equal(net.sample(noise.clone(), cond, neg, guidance_scale=2.5, shift=3.0, **kw), want2)
+        assert _lib.graph_stats() == (captures, launches + 4)
         # the cache-fill call on the re-noised chunk, injected noise
         want = _per_call_guided_loop(net, noise.clone(), cond, neg, 5.0, 3, 5.0, solver, context_noise=0.1, eps=eps)
         assert torch.equal(net.sample(noise.clone(), cond, neg, context_noise=0.1, eps=eps, **kw), want)
