@@ -54,6 +54,10 @@ class fg_wan_config(ctypes.Structure):
                 ("total_num_frames", c_int), ("eps", c_float), ("compute_dtype", c_int)]
 
 
+class fg_wan_ext_config(ctypes.Structure):
+    _fields_ = [("r_timestep", c_int), ("time_cond_diff", c_int)]
+
+
 class fg_wan_block_taps(ctypes.Structure):
     _fields_ = [("attn1", c_void_p), ("x_attn1", c_void_p), ("attn2", c_void_p), ("x_attn2", c_void_p), ("x_ffn", c_void_p)]
 
@@ -209,6 +213,16 @@ SIGNATURES = {
     "fg_wan_forward_block_causal": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p]),
     "fg_wan_forward_features": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, POINTER(c_int),
                                         POINTER(fg_wan_block_taps), c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "fg_wan_create_ex": (c_int, [POINTER(fg_wan_config), POINTER(fg_wan_ext_config), POINTER(c_void_p)]),
+    "fg_wan_full_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int, c_int, c_int]),
+    "fg_wan_forward_full": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, POINTER(c_int), c_int, c_void_p,
+                                    c_size_t, c_void_p]),
+    "fg_wan_full_sampler_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int, c_int, c_int]),
+    "fg_wan_full_sampler_run": (c_int, [c_void_p, POINTER(fg_wan_sampler_config), c_void_p, POINTER(c_double), c_int, c_int, c_int, c_void_p,
+                                        c_uint64, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_size_t, c_int, c_void_p]),
+    "fg_wan_full_guided_sampler_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int]),
+    "fg_wan_full_guided_sampler_run": (c_int, [c_void_p, POINTER(fg_wan_guided_sampler_config), c_void_p, POINTER(c_double), POINTER(c_double),
+                                               c_int, c_int, c_int, c_int, c_int, c_void_p, c_size_t, c_int, c_void_p]),
     "fg_disc_edm_num_params": (c_int, [c_int]),
     "fg_disc_edm_workspace_bytes": (c_size_t, [c_int, c_int]),
     "fg_disc_edm_run": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_size_t, c_void_p]),

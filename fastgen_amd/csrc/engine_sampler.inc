@@ -5,6 +5,8 @@
 //   fg_wan_sampler_run   CausVidModel._student_sample_loop (distribution_matching/causvid.py:87-185), the segment loop of
 //                        generator_fn_extrapolation (:188-397) and SelfForcingModel.rollout_with_gradient's no-grad form
 //                        (self_forcing.py:92-241) around fg_wan_forward: per chunk N x {x0 prediction; re-noise}, then the cache-fill call
+//   fg_wan_full_sampler_run / fg_wan_full_guided_sampler_run   the bidirectional video DiT's student loops and guided teacher loop
+//                        over the whole video (at the end of this file)
 // Textually included by engine.hip behind engine_dit.inc / engine_wan.inc; the argument check, scalar ring, graph cache and the
 // student loops (x0_loop, meanflow_loop, renoise_x0) are engine.hip's.  The reference's host syncs (`t_next > 0` on a device tensor,
 // `assert is_t_valid(t)` in every schedule call, `rescale_t`) are hoisted to host scalars checked once per call; timesteps and the RNG
@@ -321,6 +323,30 @@ size_t wan_guided_plan(const fg_wan* h, int B, int stack, int fmax, int H, int W
 
 constexpr int kGuidedMaxSteps = 4096;  // a sanity bound on the table's size, not a property of the loop
 
+// The guided loops' step scalars [steps + 1 timesteps (the last 0: the cache-fill call's) | steps x 8 solver table | seed, offset] do
+// not fit the scalar ring: they go up from one pinned host copy of 9 steps + 3 doubles, on the caller's stream before any graph
+// launch; the copy is rewritten only after the event behind its previous upload has completed.
+int wan_upload_step_scalars(fg_wan* h, const double* t_list, const double* table, int steps, uint64_t seed, double* dev, hipStream_t s) {
+    const size_t nd = 9 * (size_t)steps + 3;
+    if (!h->pin_ev) HIP_TRY(hipEventCreateWithFlags(&h->pin_ev, hipEventDisableTiming));
+    if (h->pin_used) HIP_TRY(hipEventSynchronize(h->pin_ev));
+    if (h->pin_doubles < nd) {
+        if (h->pin) (void)hipHostFree(h->pin);
+        h->pin = nullptr, h->pin_doubles = 0;
+        HIP_TRY(hipHostMalloc((void**)&h->pin, sizeof(double) * nd));
+        h->pin_doubles = nd;
+    }
+    for (int i = 0; i < steps; ++i) h->pin[i] = t_list[i];
+    h->pin[steps] = 0.0;
+    memcpy(h->pin + steps + 1, table, sizeof(double) * 8 * steps);
+    const uint64_t sd[2] = {seed, 0};
+    memcpy(h->pin + 9 * (size_t)steps + 1, sd, sizeof(sd));
+    HIP_TRY(hipMemcpyAsync(dev, h->pin, sizeof(double) * nd, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipEventRecord(h->pin_ev, s));
+    h->pin_used = true;
+    return FG_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -368,25 +394,7 @@ int fg_wan_guided_sampler_run(fg_wan* h, const fg_wan_guided_sampler_config* sc,
     // as in fg_wan_sampler_run: `self.clear_caches()` of the loop's first lines (network_causal.py:1216) without a memset, the text stays
     if ((rc = wan_ensure_caches(h, Be, height, width, s))) return rc;  // (allocation must not fall inside a capture)
     h->stored_rows = 0;
-    // The step scalars do not fit the scalar ring: they go up from one pinned host copy of 9 steps + 3 doubles, on the caller's stream
-    // before any graph launch; the copy is rewritten only after the event behind its previous upload has completed.
-    const size_t nd = 9 * (size_t)steps + 3;
-    if (!h->pin_ev) HIP_TRY(hipEventCreateWithFlags(&h->pin_ev, hipEventDisableTiming));
-    if (h->pin_used) HIP_TRY(hipEventSynchronize(h->pin_ev));
-    if (h->pin_doubles < nd) {
-        if (h->pin) (void)hipHostFree(h->pin);
-        h->pin = nullptr, h->pin_doubles = 0;
-        HIP_TRY(hipHostMalloc((void**)&h->pin, sizeof(double) * nd));
-        h->pin_doubles = nd;
-    }
-    for (int i = 0; i < steps; ++i) h->pin[i] = t_list[i];
-    h->pin[steps] = 0.0;  // the cache-fill call's t
-    memcpy(h->pin + steps + 1, table, sizeof(double) * 8 * steps);
-    const uint64_t sd[2] = {seed, 0};
-    memcpy(h->pin + 9 * (size_t)steps + 1, sd, sizeof(sd));
-    HIP_TRY(hipMemcpyAsync(w.sc, h->pin, sizeof(double) * nd, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipEventRecord(h->pin_ev, s));
-    h->pin_used = true;
+    if ((rc = wan_upload_step_scalars(h, t_list, table, steps, seed, w.sc, s))) return rc;
     const double* tl = w.sc;
     const double* tab = w.sc + steps + 1;
     const uint64_t* seed_dev = (const uint64_t*)(w.sc + 9 * (size_t)steps + 1);
@@ -442,4 +450,183 @@ int fg_wan_guided_sampler_run(fg_wan* h, const fg_wan_guided_sampler_config* sc,
         }
     }
     return fg_wan_clear_caches(h, s);  // `self.clear_caches()` after the last chunk (:1292)
+}
+
+}  // extern "C" (reopened below)
+
+// ---- bidirectional video DiT: the whole-video loops around fg_wan_forward_full ------------------------------------------------------
+//   fg_wan_full_sampler_run         FastGenModel._student_sample_loop (methods/model.py:315-372) and MeanFlowModel._student_sample_loop
+//                                   (consistency_model/mean_flow.py:336-381): dit_enqueue_sampler's structure with per-frame embedder rows
+//   fg_wan_full_guided_sampler_run  Wan.sample (Wan/network.py:919-988): the guided multistep loop over the whole video
+// No self-attention cache is allocated, read or moved; the text is the selected tag's (fg_wan_set_text).
+namespace {
+
+struct WanFullLoopWs {
+    float *x, *v, *pred, *eps, *te, *re;
+    double* tl;
+    uint64_t* seed;
+    void* net;
+    size_t net_bytes;
+};
+
+size_t wan_full_sampler_plan(const fg_wan* h, int B, int Fr, int H, int W, Arena& A, WanFullLoopWs& w) {
+    const size_t per = (size_t)B * h->cfg.in_channels * Fr * H * W;
+    w.x = A.get<float>(per);
+    w.v = A.get<float>(per);
+    w.pred = A.get<float>(per);
+    w.eps = A.get<float>(per);
+    w.te = A.get<float>((size_t)B * Fr);
+    w.re = A.get<float>((size_t)B * Fr);
+    w.tl = A.get<double>(ScalarRing::kDoubles);
+    w.seed = A.get<uint64_t>(2);
+    w.net_bytes = fg_wan_full_workspace_bytes(h, B, Fr, H, W);
+    w.net = A.take(w.net_bytes);
+    return (A.off + 255) & ~(size_t)255;
+}
+
+struct WanFullGuidedWs {
+    float *xin, *v, *xl, *mp, *te;  // as WanGuidedWs, over the whole video
+    double* sc;
+    void* net;
+    size_t net_bytes;
+};
+
+size_t wan_full_guided_plan(const fg_wan* h, int B, int stack, int Fr, int H, int W, int steps, Arena& A, WanFullGuidedWs& w) {
+    const size_t per = (size_t)B * h->cfg.in_channels * Fr * H * W;
+    w.xin = A.get<float>(per * stack);
+    w.v = A.get<float>(per * stack);
+    w.xl = A.get<float>(per);
+    w.mp = A.get<float>(per);
+    w.te = A.get<float>((size_t)B * stack * Fr);
+    w.sc = A.get<double>(9 * (size_t)steps + 3);
+    w.net_bytes = fg_wan_full_workspace_bytes(h, B * stack, Fr, H, W);
+    w.net = A.take(w.net_bytes);
+    return (A.off + 255) & ~(size_t)255;
+}
+
+bool wan_full_shape_ok(const fg_wan* h, int batch, int frames, int height, int width) {
+    return h && batch > 0 && frames > 0 && frames <= h->cfg.rope_max_seq_len && height > 0 && width > 0 && !(height & 1) && !(width & 1);
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t fg_wan_full_sampler_workspace_bytes(const fg_wan* h, int batch, int frames, int height, int width) {
+    if (!wan_full_shape_ok(h, batch, frames, height, width)) return 0;
+    Arena A;
+    A.dry = true;
+    WanFullLoopWs w;
+    return wan_full_sampler_plan(h, batch, frames, height, width, A, w);
+}
+
+int fg_wan_full_sampler_run(fg_wan* h, const fg_wan_sampler_config* sc, const float* noise, const double* t_list, int steps, int sample_type,
+                            int loop_kind, const float* eps, uint64_t seed, float* out, int batch, int frames, int height, int width,
+                            void* workspace, size_t workspace_bytes, int use_graph, void* stream) {
+    if (!h || !sc || !noise || !t_list || !out) return fail(FG_EINVAL, "null argument");
+    int rc = check_sampler_args(t_list, steps, sample_type, loop_kind, sc->schedule);
+    if (rc) return rc;
+    if (loop_kind == FG_LOOP_EULER) return fail(FG_EINVAL, "FG_LOOP_EULER is not a loop of this network (fg_wan_full_guided_sampler_run)");
+    if (loop_kind == FG_LOOP_MEANFLOW && (!h->ext.r_timestep || !sc->net_pred_flow))
+        return fail(FG_EINVAL, "FG_LOOP_MEANFLOW needs a flow-predicting network with the r_embedder (fg_wan_create_ex, r_timestep = 1)");
+    if (!(sc->t_scale > 0.0)) return fail(FG_EINVAL, "t_scale must be positive");
+    if (sc->context_noise != 0.0 || sc->prefill_frames != 0) return fail(FG_EINVAL, "context_noise and prefill_frames must be 0: there is no cache to fill");
+    if (!wan_full_shape_ok(h, batch, frames, height, width) || !workspace || (((uintptr_t)workspace) & 255))
+        return fail(FG_EINVAL, "bad batch / frames (<= rope_max_seq_len = %d) / size / workspace", h->cfg.rope_max_seq_len);
+    Arena A;
+    A.base = (char*)workspace;
+    WanFullLoopWs w;
+    const size_t need = wan_full_sampler_plan(h, batch, frames, height, width, A, w);
+    if (need > workspace_bytes) return fail(FG_ENOMEM, "workspace too small: need %zu bytes, got %zu", need, workspace_bytes);
+    if (!h->packed) return fail(FG_ENOTREADY, "weights are not packed (call fg_wan_pack_weights)");
+    if (h->text_B != batch) return fail(FG_ENOTREADY, "no text condition for batch %d (call fg_wan_set_text)", batch);
+    const int rows = batch * frames;
+    const int64_t total = (int64_t)batch * h->cfg.in_channels * frames * height * width;
+    auto enqueue = [&](hipStream_t q) -> int {
+        // the network on w.x at t_i into v; ri: MeanFlow's r (-1: 0, else t_list[ri]), -2: none.  The rows carry r itself: the call
+        // forms t - r for time_cond_diff
+        auto net = [&](int i, int ri, float* v) -> int {
+            HIP_TRY(launch_embed_times(w.tl, i, 0.0, ri, 0.0, sc->t_scale, 0, 0, 0, w.te, w.re, rows, q));
+            const WanFull full{ri == -2 ? nullptr : w.re, nullptr, 0};
+            return wan_forward(h, w.x, w.te, v, batch, frames, height, width, 0, 0, 2, w.net, w.net_bytes, q, nullptr, &full);
+        };
+        const StudentLoop L{noise, t_list, steps, sample_type, sc->schedule, total, w.x, w.eps, eps, w.tl, w.seed, out, q};
+        if (loop_kind == FG_LOOP_X0)
+            return x0_loop(L, w.pred, [&](int i, float* pred) -> int {
+                const int r = net(i, -2, w.v);
+                if (r) return r;
+                if (sc->net_pred_flow) HIP_TRY(launch_flow_to_x0(w.x, w.v, w.tl, i, 1.0f, pred, total, q));
+                else HIP_TRY(hipMemcpyAsync(pred, w.v, sizeof(float) * total, hipMemcpyDeviceToDevice, q));
+                return FG_OK;
+            });
+        return meanflow_loop(L, w.v, [&](int i, float* u) { return net(i, sample_type == FG_SAMPLE_SDE ? -1 : i + 1, u); });
+    };
+    int64_t tsb;
+    memcpy(&tsb, &sc->t_scale, 8);
+    // everything the capture bakes in: shapes, buffers, the text's length and k / v buffer, compute mode, what the r rows mean
+    return sampler_launch(h->sampler, batch, t_list, steps, sample_type, loop_kind, seed, w.tl, w.seed, use_graph,
+                          {frames, height, width, (int64_t)(uintptr_t)noise, (int64_t)(uintptr_t)eps, (int64_t)(uintptr_t)out,
+                           (int64_t)(uintptr_t)workspace, tsb, sc->net_pred_flow, sc->schedule, (int64_t)h->text_L,
+                           (int64_t)(uintptr_t)h->blocks[0].kv2, (int64_t)h->fp8, h->ext.time_cond_diff},
+                          (hipStream_t)stream, enqueue);
+}
+
+size_t fg_wan_full_guided_sampler_workspace_bytes(const fg_wan* h, int batch, int frames, int height, int width, int steps, int guidance) {
+    if (!wan_full_shape_ok(h, batch, frames, height, width) || steps < 1 || steps > kGuidedMaxSteps) return 0;
+    Arena A;
+    A.dry = true;
+    WanFullGuidedWs w;
+    return wan_full_guided_plan(h, batch, guidance ? 2 : 1, frames, height, width, steps, A, w);
+}
+
+int fg_wan_full_guided_sampler_run(fg_wan* h, const fg_wan_guided_sampler_config* sc, float* x, const double* t_list, const double* table,
+                                   int steps, int batch, int frames, int height, int width, void* workspace, size_t workspace_bytes,
+                                   int use_graph, void* stream) {
+    if (!h || !sc || !x || !t_list || !table) return fail(FG_EINVAL, "null argument");
+    if (steps < 1 || steps > kGuidedMaxSteps) return fail(FG_EINVAL, "steps must be in [1, %d]", kGuidedMaxSteps);
+    if (!(sc->t_scale > 0.0)) return fail(FG_EINVAL, "t_scale must be positive");
+    if (sc->guidance != 0 && sc->guidance != 1) return fail(FG_EINVAL, "guidance must be 0 (batch B) or 1 (stacked batch 2 B)");
+    if (sc->context_noise != 0.0) return fail(FG_EINVAL, "context_noise must be 0: there is no cache to fill");
+    if (!wan_full_shape_ok(h, batch, frames, height, width) || !workspace || (((uintptr_t)workspace) & 255))
+        return fail(FG_EINVAL, "bad batch / frames (<= rope_max_seq_len = %d) / size / workspace", h->cfg.rope_max_seq_len);
+    for (int i = 0; i < steps; ++i)
+        if (!(t_list[i] >= 0.0 && t_list[i] <= 1.0)) return fail(FG_EINVAL, "t_list[%d] = %g outside [0, 1]", i, t_list[i]);
+    for (int i = 0; i < 8 * steps; ++i)
+        if (!std::isfinite(table[i])) return fail(FG_EINVAL, "table[%d][%d] is not finite", i / 8, i % 8);
+    const int guided = sc->guidance, stack = guided ? 2 : 1, Be = batch * stack;
+    Arena A;
+    A.base = (char*)workspace;
+    WanFullGuidedWs w;
+    const size_t need = wan_full_guided_plan(h, batch, stack, frames, height, width, steps, A, w);
+    if (need > workspace_bytes) return fail(FG_ENOMEM, "workspace too small: need %zu bytes, got %zu", need, workspace_bytes);
+    if (!h->packed) return fail(FG_ENOTREADY, "weights are not packed (call fg_wan_pack_weights)");
+    if (h->text_B != Be)
+        return fail(FG_ENOTREADY, "no text condition for batch %d (call fg_wan_set_text%s)", Be, guided ? " with [cond; neg_cond]" : "");
+    hipStream_t s = (hipStream_t)stream;
+    int rc;
+    if ((rc = wan_upload_step_scalars(h, t_list, table, steps, 0, w.sc, s))) return rc;  // (no draw in this loop: the seed slot goes unread)
+    const double* tl = w.sc;
+    const double* tab = w.sc + steps + 1;
+    const int64_t total = (int64_t)batch * h->cfg.in_channels * frames * height * width;
+    float* x2 = guided ? w.xin + total : nullptr;  // the unconditional rows of the stacked input
+    auto enqueue = [&](hipStream_t q) -> int {
+        HIP_TRY(hipMemcpyAsync(w.xin, x, sizeof(float) * total, hipMemcpyDeviceToDevice, q));
+        if (x2) HIP_TRY(hipMemcpyAsync(x2, x, sizeof(float) * total, hipMemcpyDeviceToDevice, q));
+        const WanFull full{nullptr, nullptr, 0};
+        for (int i = 0; i < steps; ++i) {
+            HIP_TRY(launch_embed_times(tl, i, 0.0, -2, 0.0, sc->t_scale, 0, 0, 0, w.te, nullptr, Be * frames, q));
+            const int r = wan_forward(h, w.xin, w.te, w.v, Be, frames, height, width, 0, 0, 2, w.net, w.net_bytes, q, nullptr, &full);
+            if (r) return r;
+            HIP_TRY(launch_guided_multistep(w.v, w.xin, x2, w.xl, w.mp, tab + 8 * (size_t)i, guided, i == 0, total, q));
+        }
+        HIP_TRY(hipMemcpyAsync(x, w.xin, sizeof(float) * total, hipMemcpyDeviceToDevice, q));
+        return FG_OK;
+    };
+    if (!use_graph) return enqueue(s);
+    // what the launches bake in (timesteps and the table with the guidance scale are device memory)
+    int64_t tsb;
+    memcpy(&tsb, &sc->t_scale, 8);
+    const std::vector<int64_t> key = {batch, guided, frames, height, width, steps, (int64_t)(uintptr_t)x, (int64_t)(uintptr_t)workspace, tsb,
+                                      (int64_t)h->text_L, (int64_t)(uintptr_t)h->blocks[0].kv2, (int64_t)h->fp8, h->ext.time_cond_diff};
+    return graph_run(h->full_guided_graph, key, h->sampler.cap, s, enqueue);
 }

@@ -1,6 +1,7 @@
 // Causal video DiT engine (SURVEY 8(f)3 / CausVid row of 8(a)): parameter plan with the state-dict names of the reference's
 // CausalWan (`transformer.` + diffusers' WanTransformer3DModel keys), bf16 (fp8 mode: e4m3) weight copies, per-handle KV caches, forward
-// orchestration and the C ABI of include/fastgen_amd.h (fg_wan_*).  Textually included by engine.hip inside its `extern "C"` region
+// orchestration and the C ABI of include/fastgen_amd.h (fg_wan_*); the bidirectional network `Wan` (Wan/network.py: fg_wan_create_ex,
+// fg_wan_forward_full) is a mode of the same forward.  Textually included by engine.hip inside its `extern "C"` region
 // (the handle is a HandleBase; pack_group is engine.hip's).
 // Reference: fastgen/networks/Wan/network_causal.py:467-550 (block), :568-705 (prepare), :815-913 (block loop, cache positions),
 // fastgen/networks/Wan/network.py:156-279 (classify_forward); kernels: wan.hip + gemm.hip + dit.hip's LayerNorm-modulate.
@@ -26,6 +27,10 @@ struct fg_wan : HandleBase {
     int sst = -1, pe_w = -1, pe_b = -1, t1_w = -1, t1_b = -1, t2_w = -1, t2_b = -1, tp_w = -1, tp_b = -1, x1_w = -1, x1_b = -1, x2_w = -1,
         x2_b = -1, po_w = -1, po_b = -1;
     void *p_x1 = nullptr, *p_x2 = nullptr;  // text embedder weights, bf16
+    // fg_wan_create_ex: the second time embedder `r_embedder` (Wan/network.py:615-619, 799-834) and what it is given
+    // (time_cond_type "diff": t - r).  Both zero on a fg_wan_create handle.
+    fg_wan_ext_config ext{0, 0};
+    int r1_w = -1, r1_b = -1, r2_w = -1, r2_b = -1, rp_w = -1, rp_b = -1;
     float2 *tab_t = nullptr, *tab_h = nullptr, *tab_w = nullptr;  // RoPE axis tables
     int npt = 0, nph = 0, npw = 0;
     // fg_wan_sampler_run (engine_sampler.inc): the scalar ring and capture stream, and one graph per chunk of the loop (the chunk's
@@ -47,6 +52,7 @@ struct fg_wan : HandleBase {
     int tag = 0;
     // fg_wan_guided_sampler_run (engine_sampler.inc): its per-chunk graphs and the pinned host copy of the step scalars
     std::vector<GraphEntry> guided_graphs;
+    GraphEntry full_guided_graph;  // fg_wan_full_guided_sampler_run: one graph for the video (fg_wan_full_sampler_run's is sampler.graph)
     double* pin = nullptr;
     size_t pin_doubles = 0;
     hipEvent_t pin_ev = nullptr;
@@ -63,6 +69,8 @@ struct fg_wan : HandleBase {
     void drop_graphs() {
         for (GraphEntry& g : chunk_graphs) g.drop();
         for (GraphEntry& g : guided_graphs) g.drop();
+        full_guided_graph.drop();
+        sampler.graph.drop();
     }
 };
 
@@ -79,7 +87,7 @@ struct WanWs {
     float *ys, *hs;   // ... and their per-token scales [M]
 };
 
-size_t wan_plan(const fg_wan* h, int B, int Fr, int gh, int gw, Arena& A, WanWs& w) {
+size_t wan_plan(const fg_wan* h, int B, int Fr, int gh, int gw, Arena& A, WanWs& w, bool all_frames_kv = false) {
     const size_t D = h->D, BF = (size_t)B * Fr, M = BF * gh * gw, L = (size_t)Fr * gh * gw;
     w.tf = A.get<float>(BF * h->cfg.freq_dim);
     w.th = A.get<float>(BF * D);
@@ -100,7 +108,7 @@ size_t wan_plan(const fg_wan* h, int B, int Fr, int gh, int gw, Arena& A, WanWs&
     w.gs_bytes = 4 * M * D * 4;  // up to 4 splits of an [M][D] output
     w.gs = (float*)A.take(w.gs_bytes);
     w.kf = w.vf = nullptr;
-    if (Fr == h->cfg.total_num_frames) {
+    if (Fr == h->cfg.total_num_frames || all_frames_kv) {  // (all_frames_kv: the bidirectional call, any frame count)
         w.kf = A.take(M * D * 2);
         w.vf = A.take(M * D * 2);
     }
@@ -261,8 +269,12 @@ int wan_pack(fg_wan* h, const ParamGroup& in_group, hipStream_t s) {
 
 extern "C" {
 
-int fg_wan_create(const fg_wan_config* cfg, fg_wan** out) {
+int fg_wan_create(const fg_wan_config* cfg, fg_wan** out) { return fg_wan_create_ex(cfg, nullptr, out); }
+
+int fg_wan_create_ex(const fg_wan_config* cfg, const fg_wan_ext_config* ext, fg_wan** out) {
     if (!cfg || !out) return fail(FG_EINVAL, "null argument");
+    if (ext && ((ext->r_timestep != 0 && ext->r_timestep != 1) || (ext->time_cond_diff != 0 && ext->time_cond_diff != 1)))
+        return fail(FG_EINVAL, "r_timestep and time_cond_diff must be 0 or 1");
     if (cfg->head_dim != 128) return fail(FG_EINVAL, "head_dim %d unsupported (128)", cfg->head_dim);
     const int D = cfg->num_heads * cfg->head_dim;
     if (D != 256 && D != 384 && D != 1536 && D != 2048 && D != 5120) return fail(FG_EINVAL, "inner dim %d unsupported (256, 384, 1536, 2048, 5120)", D);
@@ -320,6 +332,17 @@ int fg_wan_create(const fg_wan_config* cfg, fg_wan** out) {
     h->po_b = h->add("proj_out.bias", {cfg->out_channels * 4});
     h->add("logvar_linear.weight", {1, D});
     h->add("logvar_linear.bias", {1});
+    if (ext) h->ext = *ext;
+    if (h->ext.r_timestep) {
+        // `init_embedder` (Wan/network.py:799-834): a deep copy of condition_embedder without its text_embedder, attached to the
+        // transformer after logvar_linear.  (timesteps_proj and act_fn hold no parameters.)  Read from the code, not from a recorded list.
+        h->r1_w = h->add("r_embedder.time_embedder.linear_1.weight", {D, cfg->freq_dim});
+        h->r1_b = h->add("r_embedder.time_embedder.linear_1.bias", {D});
+        h->r2_w = h->add("r_embedder.time_embedder.linear_2.weight", {D, D});
+        h->r2_b = h->add("r_embedder.time_embedder.linear_2.bias", {D});
+        h->rp_w = h->add("r_embedder.time_proj.weight", {6 * D, D});
+        h->rp_b = h->add("r_embedder.time_proj.bias", {6 * D});
+    }
     h->own.assign(h->params.size(), nullptr);
     h->pack_only.assign(h->params.size(), 0);
     h->dirty.assign(h->params.size(), 1);
@@ -332,8 +355,7 @@ int fg_wan_create(const fg_wan_config* cfg, fg_wan** out) {
 
 void fg_wan_destroy(fg_wan* h) {
     if (!h) return;
-    for (GraphEntry& g : h->chunk_graphs) g.drop();
-    for (GraphEntry& g : h->guided_graphs) g.drop();
+    h->drop_graphs();
     h->sampler.release();
     if (h->pin) (void)hipHostFree(h->pin);
     if (h->pin_ev) (void)hipEventDestroy(h->pin_ev);
@@ -496,10 +518,27 @@ struct WanTaps {
     float *tokens, *temb;
 };
 
+// The bidirectional call's additions (fg_wan_forward_full): the second embedder's rows and the blocks the call passes over
+struct WanFull {
+    const float* r_frames;
+    const int* skip;
+    int num_skip;
+};
+
+// block_causal: 0 - the autoregressive call on the caches; 1 - all total_num_frames frames under the block-wise causal mask; 2 - `full`
+// given: all frames under full self-attention, the block-causal path with ONE chunk of `frames` frames (the same launches when
+// chunk_size >= frames == total_num_frames), bounded by the RoPE table instead of total_num_frames
 int wan_forward(fg_wan* h, const float* x_t, const float* t_frames, float* out, int batch, int frames, int height, int width,
                 int cur_start_frame, int store_kv, int block_causal, void* workspace, size_t workspace_bytes, void* stream,
-                const WanTaps* tp = nullptr) {
+                const WanTaps* tp = nullptr, const WanFull* full = nullptr) {
     if (!h || !x_t || !t_frames || !out) return fail(FG_EINVAL, "null argument");
+    if (full) {  // (what the arguments alone decide comes first, as in fg_wan_forward_features)
+        if (full->r_frames && !h->ext.r_timestep) return fail(FG_EINVAL, "r_frames given, but the handle has no r_embedder (fg_wan_create_ex, r_timestep = 1)");
+        if (full->num_skip < 0 || (full->num_skip > 0 && !full->skip)) return fail(FG_EINVAL, "bad skip_layers arguments");
+        for (int i = 0; i < full->num_skip; ++i)
+            if (full->skip[i] < 0 || full->skip[i] >= (int)h->blocks.size() || (i > 0 && full->skip[i] <= full->skip[i - 1]))
+                return fail(FG_EINVAL, "skip_layers must be ascending block indices in [0, %d)", (int)h->blocks.size());
+    }
     if (!h->packed) return fail(FG_ENOTREADY, "weights are not packed (call fg_wan_pack_weights)");
     if (batch <= 0 || frames <= 0 || height <= 0 || width <= 0 || (height & 1) || (width & 1) || !workspace || (((uintptr_t)workspace) & 255))
         return fail(FG_EINVAL, "bad batch / frames / size / workspace");
@@ -509,15 +548,18 @@ int wan_forward(fg_wan* h, const float* x_t, const float* t_frames, float* out, 
     const fg_wan_config& c = h->cfg;
     const int D = h->D, gh = height / 2, gw = width / 2, fs = gh * gw, BF = batch * frames, L = frames * fs, M = batch * L;
     const int cap = c.total_num_frames * fs;
-    if (cur_start_frame < 0 || (cur_start_frame + frames) * fs > cap)
+    if (full) {
+        if (frames > c.rope_max_seq_len) return fail(FG_EINVAL, "%d frames exceed the RoPE table (rope_max_seq_len = %d)", frames, c.rope_max_seq_len);
+        if ((int64_t)batch * frames * fs > INT32_MAX / 2) return fail(FG_EINVAL, "batch x tokens exceeds the kernels' 32-bit row index");
+    } else if (cur_start_frame < 0 || (cur_start_frame + frames) * fs > cap)
         return fail(FG_EINVAL, "frames [%d, %d) exceed the cache of total_num_frames = %d", cur_start_frame, cur_start_frame + frames, c.total_num_frames);
     if (fs > c.rope_max_seq_len * c.rope_max_seq_len || gh > c.rope_max_seq_len || gw > c.rope_max_seq_len) return fail(FG_EINVAL, "grid exceeds the RoPE table");
     Arena A;
     A.base = (char*)workspace;
     WanWs w;
-    const size_t need = wan_plan(h, batch, frames, gh, gw, A, w);
+    const size_t need = wan_plan(h, batch, frames, gh, gw, A, w, full != nullptr);
     if (need > workspace_bytes) return fail(FG_ENOMEM, "workspace too small: need %zu bytes, got %zu", need, workspace_bytes);
-    if (block_causal && frames != c.total_num_frames)
+    if (block_causal && !full && frames != c.total_num_frames)
         return fail(FG_EINVAL, "the block-causal call takes all total_num_frames = %d frames, got %d", c.total_num_frames, frames);
     if (!block_causal) {
         int rc0 = wan_ensure_caches(h, batch, height, width, s);
@@ -537,6 +579,18 @@ int wan_forward(fg_wan* h, const float* x_t, const float* t_frames, float* out, 
     HIP_TRY(launch_linear(w.th, h->P(h->t2_w), h->P(h->t2_b), w.temb, BF, D, D, 0, s));
     HIP_TRY(launch_silu(w.temb, w.st, (int64_t)BF * D, s));
     HIP_TRY(launch_linear(w.st, h->P(h->tp_w), h->P(h->tp_b), w.tproj, BF, D, 6 * D, 0, s));
+    if (full && full->r_frames) {
+        // r_embedder on r (or t - r), the `encoder_depth is None` branch (Wan/network.py:330-351): temb += remb, timestep_proj +=
+        // r_timestep_proj.  Its scratch is the blocks' and the output layer's modulation rows, which nothing has written yet.
+        float *rrow = w.mod, *remb = w.omod, *rproj = w.mod;
+        HIP_TRY(launch_wan_r_rows(t_frames, full->r_frames, h->ext.time_cond_diff, rrow, BF, s));
+        HIP_TRY(launch_dit_fourier(rrow, w.tf, BF, c.freq_dim, s));
+        HIP_TRY(launch_linear(w.tf, h->P(h->r1_w), h->P(h->r1_b), w.th, BF, c.freq_dim, D, 1, s));
+        HIP_TRY(launch_linear(w.th, h->P(h->r2_w), h->P(h->r2_b), remb, BF, D, D, 0, s));
+        HIP_TRY(launch_silu(remb, w.st, (int64_t)BF * D, s));
+        HIP_TRY(launch_linear(w.st, h->P(h->rp_w), h->P(h->rp_b), rproj, BF, D, 6 * D, 0, s));
+        HIP_TRY(launch_wan_add_r(w.temb, remb, (int64_t)BF * D, w.tproj, rproj, (int64_t)BF * 6 * D, s));
+    }
     HIP_TRY(launch_wan_rope_table(h->tab_t, h->tab_h, h->tab_w, w.cs, L, fs, gw, cur_start_frame, c.rope_max_seq_len, h->npt, h->nph, h->npw, s));
     HIP_TRY(launch_wan_patch_embed(x_t, h->P(h->pe_w), h->P(h->pe_b), w.x0, batch, c.in_channels, frames, height, width, D, s));
     void *x = w.x0, *xn = w.x1;
@@ -545,10 +599,15 @@ int wan_forward(fg_wan* h, const float* x_t, const float* t_frames, float* out, 
     const int64_t MD = (int64_t)M * D;
     if (tp && tp->temb) HIP_TRY(hipMemcpyAsync(tp->temb, w.temb, sizeof(float) * (size_t)BF * D, hipMemcpyDeviceToDevice, s));
     if (tp && tp->tokens) HIP_TRY(launch_from_act(1, x, tp->tokens, MD, s));
-    int ti = 0, blk_idx = 0;
+    int ti = 0, blk_idx = 0, si = 0;
     for (fg_wan::Blk& b : h->blocks) {
         const fg_wan_block_taps* bt = (tp && ti < tp->n && tp->blocks[ti] == blk_idx) ? &tp->taps[ti++] : nullptr;
+        const bool skip = full && si < full->num_skip && full->skip[si] == blk_idx;
         ++blk_idx;
+        if (skip) {  // `if skip_layers is not None and idx in skip_layers: continue` (Wan/network.py:408)
+            ++si;
+            continue;
+        }
         HIP_TRY(launch_wan_mod(h->P(b.sst), w.tproj, w.mod, BF, 6, D, s));
         // 1. self-attention over the cached frames and this chunk.  K / V of the chunk go to their cache rows in every call (a call
         // with store_kv = 0 leaves rows that the chunk's store_kv = 1 call rewrites; the reference's cache length only moves there)
@@ -562,9 +621,10 @@ int wan_forward(fg_wan* h, const float* x_t, const float* t_frames, float* out, 
             // growing prefix of this call's K / V (the caches are the autoregressive calls' and stay untouched).
             HIP_TRY(launch_rms_rope(D, qkv + D, 3 * D, h->P(b.nk), c.eps, w.cs, w.kf, (int64_t)L * D, 0, D, M, L, s));
             HIP_TRY(launch_rms_rope(D, qkv + 2 * D, 3 * D, nullptr, c.eps, nullptr, w.vf, (int64_t)L * D, 0, D, M, L, s));
-            const int nch = frames / c.chunk_size, rem = frames % c.chunk_size;
+            const int chunk = full ? frames : c.chunk_size;  // (full attention: the one chunk sees every key)
+            const int nch = frames / chunk, rem = frames % chunk;
             for (int ci = 0, f0 = 0; ci < (nch > 0 ? nch : 1); ++ci) {
-                const int nf = nch == 0 ? rem : c.chunk_size + (ci == 0 ? rem : 0);
+                const int nf = nch == 0 ? rem : chunk + (ci == 0 ? rem : 0);
                 const size_t q_off = (size_t)f0 * fs * D;
                 HIP_TRY(launch_fa128((const __bf16*)w.qn + q_off, D, (int64_t)L * D, w.kf, w.vf, D, (int64_t)L * D, (__bf16*)w.att + q_off, D, (int64_t)L * D,
                                      batch, h->H, nf * fs, (f0 + nf) * fs, s, w.fa));
@@ -633,4 +693,20 @@ int fg_wan_forward_features(fg_wan* h, const float* x_t, const float* t_frames, 
     const WanTaps tp{tap_blocks, taps, num_taps, tokens_out, temb_out};
     return wan_forward(h, x_t, t_frames, out, batch, frames, height, width, cur_start_frame, store_kv, block_causal ? 1 : 0, workspace,
                        workspace_bytes, stream, &tp);
+}
+
+size_t fg_wan_full_workspace_bytes(const fg_wan* h, int batch, int frames, int height, int width) {
+    if (!h || batch <= 0 || frames <= 0 || height <= 0 || width <= 0 || (height & 1) || (width & 1)) return 0;
+    Arena A;
+    A.dry = true;
+    WanWs w;
+    const size_t net = wan_plan(h, batch, frames, height / 2, width / 2, A, w, true);
+    const size_t text = fg_wan_workspace_bytes(h, batch, 1, 2, 2);  // (at least fg_wan_set_text's scratch)
+    return net > text ? net : text;
+}
+
+int fg_wan_forward_full(fg_wan* h, const float* x_t, const float* t_frames, const float* r_frames, float* out, int batch, int frames, int height,
+                        int width, const int* skip_layers, int num_skip, void* workspace, size_t workspace_bytes, void* stream) {
+    const WanFull full{r_frames, skip_layers, num_skip};
+    return wan_forward(h, x_t, t_frames, out, batch, frames, height, width, 0, 0, 2, workspace, workspace_bytes, stream, nullptr, &full);
 }

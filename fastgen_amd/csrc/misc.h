@@ -237,6 +237,9 @@ int launch_wan_patch_embed(const float* x, const float* w, const float* bias, vo
 int launch_wan_mod(const float* table, const float* tproj, float* mod, int rows, int J, int D, hipStream_t s);
 int launch_wan_outmod(const float* table, const float* temb, float* mod, int rows, int D, hipStream_t s);
 int launch_silu(const float* x, float* y, int64_t n, hipStream_t s);
+// the second time embedder's rows (r, or t - r when diff) and the sums temb += remb [n_e], tproj += rproj [n_p]
+int launch_wan_r_rows(const float* t, const float* r, int diff, float* out, int n, hipStream_t s);
+int launch_wan_add_r(float* temb, const float* remb, int64_t n_e, float* tproj, const float* rproj, int64_t n_p, hipStream_t s);
 int launch_cvt_rows_bf16(const float* x, void* y, int64_t n, hipStream_t s);
 int launch_wan_rope_table(const float2* tab_t, const float2* tab_h, const float2* tab_w, float2* cs, int L, int fs, int gw, int start, int S,
                           int nt, int nh, int nw, hipStream_t s);

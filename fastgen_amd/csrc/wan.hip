@@ -113,6 +113,20 @@ __global__ void cvt_rows_bf16_kernel(const float* __restrict__ x, __bf16* __rest
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) y[i] = (__bf16)x[i];
 }
+// The second time embedder of the bidirectional network (`classify_forward_prepare`, Wan/network.py:330-351).  What it sees, per
+// embedder row: r, or t - r for time_cond_type "diff" (fp32, as the reference subtracts the rescaled fp32 timesteps) ...
+__global__ void wan_r_rows_kernel(const float* __restrict__ t, const float* __restrict__ r, int diff, float* __restrict__ out, int n) {
+#pragma clang fp contract(off)
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) out[i] = diff ? t[i] - r[i] : r[i];
+}
+// ... and its two results joining the first embedder's: temb += remb (n_e elements), timestep_proj += r_timestep_proj (n_p elements)
+__global__ void wan_add_r_kernel(float* __restrict__ temb, const float* __restrict__ remb, int64_t n_e, float* __restrict__ tproj,
+                                 const float* __restrict__ rproj, int64_t n_p) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n_e) temb[i] += remb[i];
+    if (i < n_p) tproj[i] += rproj[i];
+}
 
 // cs[l][i] = {cos, sin} of pair i (0 .. hd / 2) of chunk token l = (f, gy, gx): pairs [0, nt) take the frame axis at min(start + f, S - 1),
 // [nt, nt + nh) the row axis, the rest the column axis; tab: per axis [S][pairs of the axis] {cos, sin} (fp32 of float64 angles, host-built)
@@ -1408,6 +1422,15 @@ int launch_wan_outmod(const float* table, const float* temb, float* mod, int row
 }
 int launch_silu(const float* x, float* y, int64_t n, hipStream_t s) {
     hipLaunchKernelGGL(silu_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, x, y, n);
+    WAN_RET();
+}
+int launch_wan_r_rows(const float* t, const float* r, int diff, float* out, int n, hipStream_t s) {
+    hipLaunchKernelGGL(wan_r_rows_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, t, r, diff, out, n);
+    WAN_RET();
+}
+int launch_wan_add_r(float* temb, const float* remb, int64_t n_e, float* tproj, const float* rproj, int64_t n_p, hipStream_t s) {
+    const int64_t n = n_e > n_p ? n_e : n_p;
+    hipLaunchKernelGGL(wan_add_r_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, temb, remb, n_e, tproj, rproj, n_p);
     WAN_RET();
 }
 int launch_cvt_rows_bf16(const float* x, void* y, int64_t n, hipStream_t s) {

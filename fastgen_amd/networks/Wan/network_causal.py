@@ -22,20 +22,18 @@ embedders, attention and the caches stay bf16.  What it costs and buys: DESIGN.m
 from __future__ import annotations
 
 import ctypes
-import weakref
 from typing import Any, Optional, Set
 
 import torch
-import torch.nn as nn
 
 from fastgen_amd import _lib
 from fastgen_amd.networks import _engine
-from fastgen_amd.networks._engine import ptr, stream
-from fastgen_amd.networks.network import FastGenNetwork
+from fastgen_amd.networks._engine import ptr
+from fastgen_amd.networks.Wan._shared import WanEngineNetwork
 from fastgen_amd.networks.noise_schedule import NET_PRED_TYPES
 
 
-class CausalWan(FastGenNetwork):
+class CausalWan(WanEngineNetwork):
     def __init__(self, num_attention_heads: int = 12, attention_head_dim: int = 128, in_channels: int = 16, out_channels: int = 16,
                  text_dim: int = 4096, freq_dim: int = 256, ffn_dim: int = 8960, num_layers: int = 30, eps: float = 1e-6,
                  rope_max_seq_len: int = 1024, r_timestep: bool = False, net_pred_type: str = "flow", schedule_type: str = "rf",
@@ -43,93 +41,28 @@ class CausalWan(FastGenNetwork):
                  compute_dtype: Optional[str] = None, **model_kwargs):
         # compute_dtype: None / "bf16" - every GEMM on bf16 operands; "fp8" - the six linears of a block that read the video tokens on
         # e4m3fn operands (include/fastgen_amd.h, fg_wan_config).  Fixed at construction; the state dict (fp32 masters) is the same.
-        if compute_dtype not in (None, "bf16", "fp8"):
-            raise ValueError(f"compute_dtype must be None, 'bf16' or 'fp8' for the causal video DiT, got {compute_dtype!r}")
-        if compute_dtype == "fp8" and ffn_dim % 128:
-            raise ValueError(f"compute_dtype='fp8' needs ffn_dim to be a multiple of 128 (the K-step of the e4m3 MFMA), got {ffn_dim}")
-        for k in ("model_id_or_local_path", "load_pretrained", "disable_efficient_attn", "disable_grad_ckpt", "use_fsdp_checkpoint",
-                  "r_embedder_init", "time_cond_type", "norm_temb", "encoder_depth", "delete_cache_on_clear"):
-            v = model_kwargs.pop(k, None)  # reference knobs without meaning here (hub ids, autograd plumbing) ...
-            if k in ("norm_temb",) and v:  # ... except those that change the arithmetic
-                raise NotImplementedError(f"{k}={v!r} is not implemented")
-            if k == "encoder_depth" and v is not None:
-                raise NotImplementedError("encoder_depth is not implemented")
+        self._check_compute_dtype(compute_dtype, ffn_dim, "causal video DiT")
+        self._pop_reference_knobs(model_kwargs)
         super().__init__(net_pred_type=net_pred_type, schedule_type=schedule_type, **model_kwargs)
         if r_timestep:
             raise NotImplementedError("r_timestep=True (a second time embedder) is not implemented for the causal video DiT path")
-        self.chunk_size, self.total_num_frames, self.compute_dtype = chunk_size, total_num_frames, compute_dtype
-        cfg = _lib.fg_wan_config()
-        cfg.compute_dtype = _lib.DTYPE_NAMES[compute_dtype or "bf16"]
-        cfg.num_heads, cfg.head_dim, cfg.in_channels, cfg.out_channels = num_attention_heads, attention_head_dim, in_channels, out_channels
-        cfg.text_dim, cfg.freq_dim, cfg.ffn_dim, cfg.num_layers = text_dim, freq_dim, ffn_dim, num_layers
-        cfg.rope_max_seq_len, cfg.chunk_size, cfg.total_num_frames, cfg.eps = rope_max_seq_len, chunk_size, total_num_frames, eps
-        self._cfg, self.in_channels = cfg, in_channels
-        self._eng = _engine.Handles("wan", cfg)  # one handle: the mode is fixed at construction
-        self._h = self._eng.get(cfg.compute_dtype)
-        self._text_key = None  # of the selected cache tag ("pos" outside a forward(cache_tag="neg") call) ...
-        self._text_key_other, self._tag = None, "pos"  # ... and the other tag's
-        g = torch.Generator().manual_seed(0)
+        self.chunk_size, self.total_num_frames = chunk_size, total_num_frames
+        self._build_engine(num_attention_heads=num_attention_heads, attention_head_dim=attention_head_dim, in_channels=in_channels,
+                           out_channels=out_channels, text_dim=text_dim, freq_dim=freq_dim, ffn_dim=ffn_dim, num_layers=num_layers, eps=eps,
+                           rope_max_seq_len=rope_max_seq_len, chunk_size=chunk_size, total_num_frames=total_num_frames,
+                           compute_dtype=compute_dtype, enable_logvar_linear=enable_logvar_linear)
+        # _text_key: of the selected cache tag ("pos" outside a forward(cache_tag="neg") call); the other tag's:
+        self._text_key_other, self._tag = None, "pos"
 
-        def register(node, leaf, full, shp):
-            if "logvar_linear" in full and not enable_logvar_linear:
-                return False
-            node.register_parameter(leaf, nn.Parameter(self._init_value(full, shp, g)))
-
-        self._names, _ = _engine.build_tree(self, "wan", self._h, register)
-
-    @staticmethod
-    def _init_value(name: str, shape, g) -> torch.Tensor:
-        """torch defaults of the modules diffusers builds (Linear / Conv3d: uniform(+-1/sqrt(fan_in)); RMSNorm / LayerNorm weights 1,
-        biases of norms 0; scale_shift_table randn / sqrt(dim))."""
-        if name.endswith("scale_shift_table"):
-            return torch.randn(shape, generator=g) / shape[-1] ** 0.5
-        if name.endswith(("norm_q.weight", "norm_k.weight", "norm2.weight")):
-            return torch.ones(shape)
-        if name.endswith("norm2.bias"):
-            return torch.zeros(shape)
-        fan_in = 1
-        for s_ in (shape[1:] if len(shape) > 1 else shape):
-            fan_in *= s_
-        return (torch.rand(shape, generator=g) * 2 - 1) * fan_in ** -0.5
-
-    # ---- library plumbing -------------------------------------------------------------------------------------------------
-    _stream = staticmethod(stream)
-
-    def _bind(self, dev: torch.device):
-        names = [n for n in self._names if "logvar_linear" not in n]
-        if self._eng.sync_copies(self, self._cfg.compute_dtype, names, lambda: dict(self.named_parameters()), dev):
-            self._text_key = self._text_key_other = None  # the text caches were computed with the previous weights
-
-    def fully_shard(self, **kwargs):
-        """FSDP2 with the reference's grouping (Wan/network.py:761-782): one parameter group per transformer block, then the transformer
-        itself (embedders, output layer, `logvar_linear`) as the root group.  The engine keeps its own packed bf16 copy of the weights
-        (fastgen_amd/networks/_weights.py): a group whose parameters changed is all-gathered, packed and resharded - ONE block's fp32
-        parameters whole at a time, which is what carries to the 14B network (40 blocks of 350M parameters)."""
-        from torch.distributed.fsdp import fully_shard
-
-        tr = self._modules["transformer"]
-        for block in tr._modules["blocks"]._modules.values():
-            fully_shard(block, **kwargs)
-        fully_shard(tr, **kwargs)
+    # ---- library plumbing (the rest: WanEngineNetwork) -----------------------------------------------------------------------
+    def _forget_text(self) -> None:
+        self._text_key = self._text_key_other = None
 
     def _workspace(self, dev, B, F, H, W) -> torch.Tensor:
         need = _lib.lib().fg_wan_workspace_bytes(self._h, B, F, H, W)
         if need == 0:
             raise ValueError(f"bad chunk shape: batch {B}, frames {F}, {H}x{W} (height and width must be even)")
         return self._eng.workspace(self._cfg.compute_dtype, need, dev)
-
-    def _set_text(self, condition: torch.Tensor, B: int, dev, ws: torch.Tensor) -> None:
-        """The text condition: embedded (and its cross-attention k / v cached) once per tensor, as the reference's static cache
-        (the same tensor OBJECT at the same in-place version; a new object with recycled storage is embedded again)."""
-        ver = 0 if condition.is_inference() else condition._version
-        same = self._text_key is not None and self._text_key[0]() is condition and self._text_key[1:] == (ver, tuple(condition.shape))
-        if same:
-            return
-        c32 = condition.detach().to(device=dev, dtype=torch.float32).contiguous()
-        if c32.shape[0] != B:
-            raise ValueError(f"condition batch {c32.shape[0]} != {B}")
-        _lib.check(_lib.lib().fg_wan_set_text(self._h, ptr(c32), B, c32.shape[1], ptr(ws), ws.numel(), self._stream(dev)))
-        self._text_key = (weakref.ref(condition), ver, tuple(condition.shape))
 
     def clear_caches(self) -> None:
         """`CausalWan.clear_caches` (network_causal.py:1030-1054)."""

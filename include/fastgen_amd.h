@@ -646,6 +646,52 @@ FG_API size_t fg_wan_guided_sampler_workspace_bytes(const fg_wan* h, int batch, 
 FG_API int fg_wan_guided_sampler_run(fg_wan* h, const fg_wan_guided_sampler_config* cfg, float* x, const double* t_list, const double* table,
                                      int steps, const float* eps, uint64_t seed, int batch, int frames, int height, int width,
                                      void* workspace, size_t workspace_bytes, int use_graph, void* stream);
+/* ---- Bidirectional video DiT (reference fastgen/networks/Wan/network.py `Wan`: the network of the DMD2 / f-distill / LADD / MeanFlow
+ * WanT2V students and the teacher of all of them) on the same handle: every frame attends to every frame, no self-attention cache.
+ * PARITY UNPINNED like the rest of fg_wan_*.
+ * fg_wan_create_ex(cfg, NULL or an all-zero ext, ...) is fg_wan_create: the same parameter table in the same order.  r_timestep = 1
+ * adds the second time embedder `r_embedder` (`init_embedder`, Wan/network.py:799-834: a deep copy of condition_embedder without its
+ * text_embedder, attached after logvar_linear), six parameters behind `transformer.logvar_linear.*`:
+ * transformer.r_embedder.time_embedder.linear_1.{weight,bias}, ...linear_2.{weight,bias}, transformer.r_embedder.time_proj.{weight,bias}.
+ * These names and their order are read from the reference's code, not recorded from a run of it (diffusers is un-vendored). */
+typedef struct fg_wan_ext_config {
+    int r_timestep;      /* 1: the handle has the r_embedder */
+    int time_cond_diff;  /* time_cond_type: 1 = "diff" (the r_embedder sees t - r), 0 = "abs" (r) */
+} fg_wan_ext_config;
+FG_API int fg_wan_create_ex(const fg_wan_config* cfg, const fg_wan_ext_config* ext, fg_wan** out);
+/* `Wan.forward` up to the raw network output: all `frames` frames under full self-attention - fg_wan_forward_block_causal's path with one
+ * chunk, ONE attention launch per block over this call's own K / V (the same launches as that call when chunk_size >= frames ==
+ * total_num_frames).  No self-attention cache is allocated, read or written, and the caches' bookkeeping and the chunk graphs stay as
+ * they are.  frames <= rope_max_seq_len (not total_num_frames).  t_frames [B * frames] as for fg_wan_forward.  r_frames (nullable)
+ * [B * frames], in the embedder's units too: the r_embedder runs on fp32(t_frames - r_frames) when time_cond_diff, else on r_frames;
+ * its embedding is added to temb and its projection to timestep_proj (`classify_forward_prepare`, Wan/network.py:330-351, the
+ * `encoder_depth is None` branch).  r_frames on a handle without the r_embedder: FG_EINVAL; NULL on a handle with it: no r term.
+ * skip_layers (nullable): HOST array of num_skip ascending block indices the call passes over (`classify_forward_block_forward`,
+ * :408); out of range or unsorted: FG_EINVAL.  The text is the selected tag's (fg_wan_set_text).  Workspace:
+ * fg_wan_full_workspace_bytes (also enough for fg_wan_set_text). */
+FG_API size_t fg_wan_full_workspace_bytes(const fg_wan* h, int batch, int frames, int height, int width);
+FG_API int fg_wan_forward_full(fg_wan* h, const float* x_t, const float* t_frames, const float* r_frames, float* out, int batch, int frames,
+                               int height, int width, const int* skip_layers, int num_skip, void* workspace, size_t workspace_bytes, void* stream);
+/* The few-step student loops over the whole video as ONE call and one hipGraph, as fg_dit_sampler_run: loop_kind FG_LOOP_X0
+ * (`FastGenModel._student_sample_loop`, methods/model.py:315-372) or FG_LOOP_MEANFLOW (`MeanFlowModel._student_sample_loop`,
+ * consistency_model/mean_flow.py:336-381: r = 0 for 'sde', t_{i+1} for 'ode'; needs the r_embedder and net_pred_flow, else FG_EINVAL).
+ * noise, out: [B, C, frames, H, W] fp32; latents = noise * sigma(t_0); every frame's embedder row is fp32(t_scale * t_i).  eps
+ * (nullable): steps - 1 noise videos to inject; NULL: Philox4x32-10 from (seed; step).  cfg: context_noise and prefill_frames must be 0
+ * (FG_EINVAL).  The graph's key holds the shapes, every buffer address, the text's length and k / v buffer, the compute mode and
+ * time_cond_diff.  Bit-identical to the same sequence of fg_wan_forward_full + fg_op_* calls. */
+FG_API size_t fg_wan_full_sampler_workspace_bytes(const fg_wan* h, int batch, int frames, int height, int width);
+FG_API int fg_wan_full_sampler_run(fg_wan* h, const fg_wan_sampler_config* cfg, const float* noise, const double* t_list, int steps,
+                                   int sample_type, int loop_kind, const float* eps, uint64_t seed, float* out, int batch, int frames,
+                                   int height, int width, void* workspace, size_t workspace_bytes, int use_graph, void* stream);
+/* The teacher's `Wan.sample` (Wan/network.py:919-988) as ONE call and one hipGraph for the video: fg_wan_guided_sampler_run without
+ * chunks, caches, the cache-fill call and its noise (cfg->context_noise must be 0).  x: the latents (noise * sigma(t_0), the caller's
+ * business), overwritten with the sample.  Per step: one fg_wan_forward_full on the stacked batch [x; x] against [cond; neg_cond]
+ * (guidance == 0: batch B), then fg_op_guided_multistep with table row i.  t_list, table, steps as there; they go up through the same
+ * pinned host copy.  The caller sets the text for the batch the loop runs at before the run; it is still set afterwards. */
+FG_API size_t fg_wan_full_guided_sampler_workspace_bytes(const fg_wan* h, int batch, int frames, int height, int width, int steps, int guidance);
+FG_API int fg_wan_full_guided_sampler_run(fg_wan* h, const fg_wan_guided_sampler_config* cfg, float* x, const double* t_list,
+                                          const double* table, int steps, int batch, int frames, int height, int width, void* workspace,
+                                          size_t workspace_bytes, int use_graph, void* stream);
 /* One step of that solver, in place (misc.hip guided_multistep_kernel): with the eight DEVICE doubles tab = {s, g, c0, c1, c2, p0, p1, p2}
  * each rounded once to fp32, v = guided ? v[total + i] + g (v[i] - v[total + i]) : v[i]; m = x - s v; x_corr = c0 x_last + c1 m_prev +
  * c2 m (first != 0: x_last := x, m_prev := m, neither buffer is read); x_next = p0 x_corr + p1 m_prev + p2 m; then x <- x_next (and

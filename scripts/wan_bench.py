@@ -3,7 +3,10 @@ Wan2.1-T2V-1.3B, latents [16, 21, 60, 104] = 480p, chunk of 3 frames, t_list of 
 chunk k (4680 query tokens over (3 k + 3) * 1560 cached + own keys), and the whole 21-frame 4-step loop (7 chunks x (4 + 1) calls).
 Random-init weights of the 1.3B architecture, synthetic latents and text embeddings.
     python scripts/wan_bench.py [--layers=30] [--loop] [--compute-dtype=bf16[,fp8]] [--case=chunks|bc|guided] [--chunks=0,6]
-                                [--widths=1.3b|14b] [--trace=CALLS]
+                                [--widths=1.3b|14b] [--trace=CALLS] [--bidirectional]
+--bidirectional: the bidirectional network `Wan` (fastgen_amd/networks/Wan/network.py) instead, per arm next to the block-causal call of
+  a `CausalWan` of the same weights in the same run: one call at [1,16,21,60,104] (full attention: 7 / 4 of the block mask's key
+  pairs), the 4-step x0 student loop (FastGenModel.generator_fn, one hipGraph) and one guided step (the call at the stacked batch 2).
 --compute-dtype: the arms (default bf16).  Several arms are built on the same seed and timed SIDE BY SIDE in this one run: per shape
   three rounds of windows, the arms alternating inside a round, the median window per arm reported (and their ratio).
 --case: chunks (default) - one call per listed chunk (default all 7) over the cache the earlier chunks' calls left; bc - the all-frames
@@ -73,6 +76,34 @@ def side_by_side(label, fns, n, gf=None, rounds=3):
     print(f"{label}: " + "   ".join(parts) + ratio, flush=True)
     return med
 
+
+if "--bidirectional" in sys.argv:
+    from fastgen_amd.methods.model import FastGenModel
+    from fastgen_amd.networks.Wan.network import Wan
+
+    full = {}
+    for arm in ARMS:
+        torch.manual_seed(0)
+        full[arm] = Wan(num_attention_heads=H, ffn_dim=Fd, num_layers=LAYERS, compute_dtype=arm).cuda().eval()
+    x1, text1, t1, L = x[:1], text[:1], t[:1], 21 * fs
+    x2, text2, t2 = x1.repeat(2, 1, 1, 1, 1), torch.cat([text1, -text1]), t1.repeat(2)
+    tf = torch.full((1, 21), 0.7, dtype=torch.float64, device="cuda")
+    B = 1
+    with torch.inference_mode():
+        fns = {}
+        for a in ARMS:
+            fns[f"{a} full"] = lambda n=full[a]: n(x1, t1, condition=text1, fwd_pred_type="flow")
+            fns[f"{a} block-causal"] = lambda n=nets[a]: n(x1, tf, condition=text1, fwd_pred_type="flow", is_ar=False)
+        med = side_by_side(f"one call, {L} tokens, {LAYERS} layers", fns, 2)
+        print("   " + "   ".join(f"{a}: full / block-causal = {med[f'{a} full'] / med[f'{a} block-causal']:.3f}" for a in ARMS) +
+              f"   (attention key pairs 7 / 4; GEMM + other work equal; full call {gflop(L, L):.0f} GFLOP, block-causal {gflop(L, L * 4 // 7):.0f})")
+        loop = lambda net: FastGenModel.generator_fn(net, x1, student_sample_steps=4, t_list=[0.999, 0.937, 0.833, 0.624, 0.0],  # noqa: E731
+                                                     condition=text1, student_sample_type="sde", seed=1)
+        side_by_side("4-step x0 student loop (4 network calls, one graph)", {a: (lambda n=n: loop(n)) for a, n in full.items()}, 1)
+        B = 2
+        side_by_side("guided step: one call at the stacked batch 2", {a: (lambda n=n: n(x2, t2, condition=text2, fwd_pred_type="flow"))
+                                                                       for a, n in full.items()}, 2, gflop(L, L))
+    sys.exit(0)
 
 with torch.inference_mode():
     if CASE == "bc":
