@@ -217,6 +217,9 @@ SIGNATURES = {
     "fg_wan_full_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int, c_int, c_int]),
     "fg_wan_forward_full": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, POINTER(c_int), c_int, c_void_p,
                                     c_size_t, c_void_p]),
+    "fg_wan_forward_full_features": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, POINTER(c_int), c_int,
+                                             POINTER(c_int), POINTER(fg_wan_block_taps), c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t,
+                                             c_void_p]),
     "fg_wan_full_sampler_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int, c_int, c_int]),
     "fg_wan_full_sampler_run": (c_int, [c_void_p, POINTER(fg_wan_sampler_config), c_void_p, POINTER(c_double), c_int, c_int, c_int, c_void_p,
                                         c_uint64, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_size_t, c_int, c_void_p]),

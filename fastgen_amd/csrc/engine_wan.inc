@@ -516,6 +516,7 @@ struct WanTaps {
     const fg_wan_block_taps* taps;
     int n;
     float *tokens, *temb;
+    float* tproj = nullptr;  // fg_wan_forward_full_features: timestep_proj [B * F][6 D] as the blocks read it (the r term added)
 };
 
 // The bidirectional call's additions (fg_wan_forward_full): the second embedder's rows and the blocks the call passes over
@@ -538,6 +539,8 @@ int wan_forward(fg_wan* h, const float* x_t, const float* t_frames, float* out, 
         for (int i = 0; i < full->num_skip; ++i)
             if (full->skip[i] < 0 || full->skip[i] >= (int)h->blocks.size() || (i > 0 && full->skip[i] <= full->skip[i - 1]))
                 return fail(FG_EINVAL, "skip_layers must be ascending block indices in [0, %d)", (int)h->blocks.size());
+        if (frames > h->cfg.rope_max_seq_len)
+            return fail(FG_EINVAL, "%d frames exceed the RoPE table (rope_max_seq_len = %d)", frames, h->cfg.rope_max_seq_len);
     }
     if (!h->packed) return fail(FG_ENOTREADY, "weights are not packed (call fg_wan_pack_weights)");
     if (batch <= 0 || frames <= 0 || height <= 0 || width <= 0 || (height & 1) || (width & 1) || !workspace || (((uintptr_t)workspace) & 255))
@@ -549,7 +552,6 @@ int wan_forward(fg_wan* h, const float* x_t, const float* t_frames, float* out, 
     const int D = h->D, gh = height / 2, gw = width / 2, fs = gh * gw, BF = batch * frames, L = frames * fs, M = batch * L;
     const int cap = c.total_num_frames * fs;
     if (full) {
-        if (frames > c.rope_max_seq_len) return fail(FG_EINVAL, "%d frames exceed the RoPE table (rope_max_seq_len = %d)", frames, c.rope_max_seq_len);
         if ((int64_t)batch * frames * fs > INT32_MAX / 2) return fail(FG_EINVAL, "batch x tokens exceeds the kernels' 32-bit row index");
     } else if (cur_start_frame < 0 || (cur_start_frame + frames) * fs > cap)
         return fail(FG_EINVAL, "frames [%d, %d) exceed the cache of total_num_frames = %d", cur_start_frame, cur_start_frame + frames, c.total_num_frames);
@@ -598,6 +600,8 @@ int wan_forward(fg_wan* h, const float* x_t, const float* t_frames, float* out, 
     const int64_t cbs = (int64_t)cap * D;
     const int64_t MD = (int64_t)M * D;
     if (tp && tp->temb) HIP_TRY(hipMemcpyAsync(tp->temb, w.temb, sizeof(float) * (size_t)BF * D, hipMemcpyDeviceToDevice, s));
+    // (before the block loop: the r_embedder's scratch was w.mod, which the first launch_wan_mod rewrites from this very buffer)
+    if (tp && tp->tproj) HIP_TRY(hipMemcpyAsync(tp->tproj, w.tproj, sizeof(float) * (size_t)BF * 6 * D, hipMemcpyDeviceToDevice, s));
     if (tp && tp->tokens) HIP_TRY(launch_from_act(1, x, tp->tokens, MD, s));
     int ti = 0, blk_idx = 0, si = 0;
     for (fg_wan::Blk& b : h->blocks) {
@@ -681,14 +685,21 @@ int fg_wan_forward_block_causal(fg_wan* h, const float* x_t, const float* t_fram
     return wan_forward(h, x_t, t_frames, out, batch, frames, height, width, 0, 0, 1, workspace, workspace_bytes, stream);
 }
 
-int fg_wan_forward_features(fg_wan* h, const float* x_t, const float* t_frames, float* out, int batch, int frames, int height, int width,
-                            int cur_start_frame, int store_kv, int block_causal, const int* tap_blocks, const fg_wan_block_taps* taps,
-                            int num_taps, float* tokens_out, float* temb_out, void* workspace, size_t workspace_bytes, void* stream) {
+namespace {
+int wan_check_taps(const fg_wan* h, const int* tap_blocks, const fg_wan_block_taps* taps, int num_taps) {
     if (!h) return fail(FG_EINVAL, "null argument");
     if (num_taps < 0 || (num_taps > 0 && (!tap_blocks || !taps))) return fail(FG_EINVAL, "bad tap arguments");
     for (int i = 0; i < num_taps; ++i)
         if (tap_blocks[i] < 0 || tap_blocks[i] >= (int)h->blocks.size() || (i > 0 && tap_blocks[i] <= tap_blocks[i - 1]))
             return fail(FG_EINVAL, "tap_blocks must be ascending block indices in [0, %d)", (int)h->blocks.size());
+    return FG_OK;
+}
+}  // namespace
+
+int fg_wan_forward_features(fg_wan* h, const float* x_t, const float* t_frames, float* out, int batch, int frames, int height, int width,
+                            int cur_start_frame, int store_kv, int block_causal, const int* tap_blocks, const fg_wan_block_taps* taps,
+                            int num_taps, float* tokens_out, float* temb_out, void* workspace, size_t workspace_bytes, void* stream) {
+    if (int rc = wan_check_taps(h, tap_blocks, taps, num_taps)) return rc;
     if (block_causal && (cur_start_frame != 0 || store_kv)) return fail(FG_EINVAL, "the block-causal call starts at frame 0 and stores nothing");
     const WanTaps tp{tap_blocks, taps, num_taps, tokens_out, temb_out};
     return wan_forward(h, x_t, t_frames, out, batch, frames, height, width, cur_start_frame, store_kv, block_causal ? 1 : 0, workspace,
@@ -709,4 +720,20 @@ int fg_wan_forward_full(fg_wan* h, const float* x_t, const float* t_frames, cons
                         int width, const int* skip_layers, int num_skip, void* workspace, size_t workspace_bytes, void* stream) {
     const WanFull full{r_frames, skip_layers, num_skip};
     return wan_forward(h, x_t, t_frames, out, batch, frames, height, width, 0, 0, 2, workspace, workspace_bytes, stream, nullptr, &full);
+}
+
+int fg_wan_forward_full_features(fg_wan* h, const float* x_t, const float* t_frames, const float* r_frames, float* out, int batch, int frames,
+                                 int height, int width, const int* skip_layers, int num_skip, const int* tap_blocks,
+                                 const fg_wan_block_taps* taps, int num_taps, float* tokens_out, float* temb_out, float* tproj_out,
+                                 void* workspace, size_t workspace_bytes, void* stream) {
+    if (int rc = wan_check_taps(h, tap_blocks, taps, num_taps)) return rc;
+    // a skipped block runs no kernel: it has nothing to tap (wan_forward checks the skip list itself)
+    if (num_skip > 0 && skip_layers)
+        for (int i = 0; i < num_taps; ++i)
+            for (int j = 0; j < num_skip; ++j)
+                if (tap_blocks[i] == skip_layers[j]) return fail(FG_EINVAL, "block %d is both tapped and in skip_layers", tap_blocks[i]);
+    WanTaps tp{tap_blocks, taps, num_taps, tokens_out, temb_out};
+    tp.tproj = tproj_out;
+    const WanFull full{r_frames, skip_layers, num_skip};
+    return wan_forward(h, x_t, t_frames, out, batch, frames, height, width, 0, 0, 2, workspace, workspace_bytes, stream, &tp, &full);
 }

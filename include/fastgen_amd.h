@@ -672,6 +672,15 @@ FG_API int fg_wan_create_ex(const fg_wan_config* cfg, const fg_wan_ext_config* e
 FG_API size_t fg_wan_full_workspace_bytes(const fg_wan* h, int batch, int frames, int height, int width);
 FG_API int fg_wan_forward_full(fg_wan* h, const float* x_t, const float* t_frames, const float* r_frames, float* out, int batch, int frames,
                                int height, int width, const int* skip_layers, int num_skip, void* workspace, size_t workspace_bytes, void* stream);
+/* Exposed for the parity tests (tests/test_gpu_wan_full_blocks.py): fg_wan_forward_full with the taps of fg_wan_forward_features -
+ * the same forward, the same launches, fp32 copies behind the kernels that wrote the buffers; `out` is what the untapped call leaves.
+ * tap_blocks / taps / num_taps / tokens_out as there.  temb_out (nullable) [B * frames, D]: temb with the r_embedder's embedding added
+ * (when r_frames is given).  tproj_out (nullable) [B * frames, 6 D]: timestep_proj with the r_embedder's projection added - the rows
+ * every block's modulation is formed from.  A block that is both tapped and in skip_layers: FG_EINVAL (it runs nothing). */
+FG_API int fg_wan_forward_full_features(fg_wan* h, const float* x_t, const float* t_frames, const float* r_frames, float* out, int batch,
+                                        int frames, int height, int width, const int* skip_layers, int num_skip, const int* tap_blocks,
+                                        const fg_wan_block_taps* taps, int num_taps, float* tokens_out, float* temb_out, float* tproj_out,
+                                        void* workspace, size_t workspace_bytes, void* stream);
 /* The few-step student loops over the whole video as ONE call and one hipGraph, as fg_dit_sampler_run: loop_kind FG_LOOP_X0
  * (`FastGenModel._student_sample_loop`, methods/model.py:315-372) or FG_LOOP_MEANFLOW (`MeanFlowModel._student_sample_loop`,
  * consistency_model/mean_flow.py:336-381: r = 0 for 'sde', t_{i+1} for 'ode'; needs the r_embedder and net_pred_flow, else FG_EINVAL).

@@ -22,8 +22,13 @@ start_frame off by one (calls over a cache: RoPE is relative, without cached key
 swapped in attn1, (e) the last 17 keys dropped, (f) the text K / V of the neighbouring sample, (g) cache_start off by one frame.
 
 The tapped call changes nothing: its `out` is torch.equal to fg_wan_forward's (fg_wan_forward_block_causal's) on the same inputs and cache
-state, and a second tapped call reports the same x_ffn."""
+state, and a second tapped call reports the same x_ffn.
+
+The machinery below also serves tests/test_gpu_wan_full_blocks.py, the same pin of the bidirectional call: a call of kind "full"
+(`fg_wan_forward_full` / `fg_wan_forward_full_features`) is ("full", 0, frames, 0, with_r, skip_layers) - no cache, no mask, start frame
+0, every frame its own r beside its own t - and brings its own checks and mutants (m) - (q); that file describes them."""
 import ctypes
+import dataclasses
 from dataclasses import dataclass
 
 import pytest
@@ -52,6 +57,11 @@ class Case:
     rope_max: int = 5
     calls: tuple = STD
     seed: int = 0
+    # what only the bidirectional matrix sets (tests/test_gpu_wan_full_blocks.py)
+    layers: int = 2
+    r: str = ""             # "diff" / "abs": a `Wan` handle with a full-scale r_embedder of that time_cond_type (fg_wan_create_ex)
+    dtype: str = ""         # "fp8": only the tapped call's `out` is compared, with the untapped call's
+    device_oracle: bool = False  # the oracle's pieces run in fp64 on the GPU (thousands of tokens)
 
 
 CASES = {
@@ -92,37 +102,49 @@ def _checked(B):
 
 
 def _cfg(c: Case) -> R.WanConfig:
-    return R.WanConfig(num_heads=c.heads, head_dim=128, in_channels=c.chans, out_channels=c.chans, text_dim=64, ffn_dim=c.ffn, num_layers=2,
+    return R.WanConfig(num_heads=c.heads, head_dim=128, in_channels=c.chans, out_channels=c.chans, text_dim=64, ffn_dim=c.ffn, num_layers=c.layers,
                        rope_max_seq_len=c.rope_max, chunk_size=c.chunk, total_num_frames=c.total)
 
 
 def _inputs(c: Case, cfg, call, ci, seed):
-    """x [B, C, F, H, W] and the embedder's per-frame timesteps [B, F] (fp32, 1000 t with t spread over [0.05, 0.95], no two alike)."""
+    """x [B, C, F, H, W] and the embedder's per-frame timesteps [B, F] (fp32, 1000 t with t spread over [0.05, 0.95], no two alike);
+    third, for a "full" call, the second embedder's rows r [B, F] (else None): t and r are 2 B F distinct points of the same grid,
+    paired at random, the larger of a pair being t - no two of the 2 B F values coincide and t - r > 0 in every frame."""
     g = torch.Generator().manual_seed(1000 * seed + ci)
     Fr = call[2]
     x = torch.randn((c.B, c.chans, Fr) + tuple(c.lat), generator=g)
     n = c.B * Fr
+    if call[0] == "full":
+        v = (0.05 + 0.9 * (torch.randperm(2 * n, generator=g).double() + 0.5) / (2 * n)).view(n, 2)
+        t, r = v.amax(1).view(c.B, Fr), v.amin(1).view(c.B, Fr)
+        return x, (1000.0 * t).float(), (1000.0 * r).float()
     t = (0.05 + 0.9 * (torch.randperm(n, generator=g).double() + 0.5) / n).view(c.B, Fr)
-    return x, (1000.0 * t).float()
+    return x, (1000.0 * t).float(), None
 
 
 class Gpu:
     """The engine behind the drop-in module, called through the C ABI directly."""
 
     def __init__(self, c: Case, cfg, sd):
+        from fastgen_amd.networks.Wan.network import Wan
         from fastgen_amd.networks.Wan.network_causal import CausalWan
 
         self.dev = torch.device("cuda:0")
-        net = CausalWan(num_attention_heads=cfg.num_heads, attention_head_dim=128, in_channels=cfg.in_channels, out_channels=cfg.out_channels,
-                        text_dim=cfg.text_dim, ffn_dim=cfg.ffn_dim, num_layers=cfg.num_layers, rope_max_seq_len=cfg.rope_max_seq_len,
-                        chunk_size=cfg.chunk_size, total_num_frames=cfg.total_num_frames)
+        kw = dict(num_attention_heads=cfg.num_heads, attention_head_dim=128, in_channels=cfg.in_channels, out_channels=cfg.out_channels,
+                  text_dim=cfg.text_dim, ffn_dim=cfg.ffn_dim, num_layers=cfg.num_layers, rope_max_seq_len=cfg.rope_max_seq_len,
+                  compute_dtype=c.dtype or None)
+        if c.r:  # (the r_embedder is the bidirectional module's; its handle's chunk_size and total_num_frames are 1)
+            net = Wan(r_timestep=True, time_cond_type=c.r, **kw)
+        else:
+            net = CausalWan(chunk_size=cfg.chunk_size, total_num_frames=cfg.total_num_frames, **kw)
         net.load_state_dict(sd, strict=True)
         self.net = net.to(self.dev).eval()
         self.net._bind(self.dev)
         self.cfg, self.B, self.lat = cfg, c.B, c.lat
         self.L = _lib.lib()
         self.stream = ctypes.c_void_p(torch.cuda.current_stream(self.dev).cuda_stream)
-        need = max(self.L.fg_wan_workspace_bytes(self.net._h, c.B, max(k[2] for k in c.calls), c.lat[0], c.lat[1]), 1)
+        need = max([1] + [(self.L.fg_wan_full_workspace_bytes if k[0] == "full" else self.L.fg_wan_workspace_bytes)(
+            self.net._h, c.B, k[2], c.lat[0], c.lat[1]) for k in c.calls])
         self.ws = torch.empty(need, dtype=torch.uint8, device=self.dev)
 
     def set_text(self, text):
@@ -130,13 +152,23 @@ class Gpu:
         _lib.check(self.L.fg_wan_set_text(self.net._h, ctypes.c_void_p(self.text.data_ptr()), self.B, text.shape[1],
                                           ctypes.c_void_p(self.ws.data_ptr()), self.ws.numel(), self.stream))
 
-    def plain(self, call, x, tf):
-        """fg_wan_forward / fg_wan_forward_block_causal: out [B, C, F, H, W] on the device."""
-        kind, start, Fr, store = call
+    def _full_args(self, call, rf):
+        """r_frames (device tensor or None) and skip_layers / num_skip of a "full" call."""
+        self.rd = rf.to(self.dev).contiguous() if call[4] else None
+        skip = tuple(call[5])
+        return ctypes.c_void_p(self.rd.data_ptr()) if call[4] else None, (ctypes.c_int * len(skip))(*skip) if skip else None, len(skip)
+
+    def plain(self, call, x, tf, rf=None):
+        """fg_wan_forward / fg_wan_forward_block_causal / fg_wan_forward_full: out [B, C, F, H, W] on the device."""
+        kind, start, Fr, store = call[:4]
         self.xd, self.td = x.to(self.dev).contiguous(), tf.to(self.dev).contiguous()
         out = torch.full_like(self.xd, float("nan"))
         p = lambda v: ctypes.c_void_p(v.data_ptr())  # noqa: E731
-        if kind == "bc":
+        if kind == "full":
+            r_ptr, skip, nskip = self._full_args(call, rf)
+            _lib.check(self.L.fg_wan_forward_full(self.net._h, p(self.xd), p(self.td), r_ptr, p(out), self.B, Fr, self.lat[0], self.lat[1], skip,
+                                                  nskip, p(self.ws), self.ws.numel(), self.stream))
+        elif kind == "bc":
             _lib.check(self.L.fg_wan_forward_block_causal(self.net._h, p(self.xd), p(self.td), p(out), self.B, Fr, self.lat[0], self.lat[1],
                                                           p(self.ws), self.ws.numel(), self.stream))
         else:
@@ -144,20 +176,33 @@ class Gpu:
                                              p(self.ws), self.ws.numel(), self.stream))
         return out
 
-    def tapped(self, call, x, tf):
-        """fg_wan_forward_features with everything tapped: dict of device tensors."""
-        kind, start, Fr, store = call
+    def tapped(self, call, x, tf, rf=None):
+        """fg_wan_forward_features (fg_wan_forward_full_features) with everything tapped: dict of device tensors; a skipped block: None."""
+        kind, start, Fr, store = call[:4]
         cfg, B = self.cfg, self.B
         Ltok, D, depth = Fr * (self.lat[0] // 2) * (self.lat[1] // 2), cfg.dim, cfg.num_layers
         self.xd, self.td = x.to(self.dev).contiguous(), tf.to(self.dev).contiguous()
         new = lambda *s: torch.full(s, float("nan"), device=self.dev)  # noqa: E731
         r = dict(out=torch.full_like(self.xd, float("nan")), tokens=new(B, Ltok, D), temb=new(B * Fr, D),
                  blocks=[{k: new(B, Ltok, D) for k in ("attn1", "x_attn1", "attn2", "x_attn2", "x_ffn")} for _ in range(depth)])
+        p = lambda v: ctypes.c_void_p(v.data_ptr())  # noqa: E731
+        if kind == "full":
+            r_ptr, skip, nskip = self._full_args(call, rf)
+            r["blocks"] = [None if i in call[5] else b for i, b in enumerate(r["blocks"])]
+            r["tproj"] = new(B * Fr, 6 * D)
+            live = [i for i in range(depth) if i not in call[5]]
+            taps = (_lib.fg_wan_block_taps * len(live))()
+            for j, i in enumerate(live):
+                for k, v in r["blocks"][i].items():
+                    setattr(taps[j], k, v.data_ptr())
+            _lib.check(self.L.fg_wan_forward_full_features(self.net._h, p(self.xd), p(self.td), r_ptr, p(r["out"]), B, Fr, self.lat[0], self.lat[1],
+                                                           skip, nskip, (ctypes.c_int * len(live))(*live), taps, len(live), p(r["tokens"]),
+                                                           p(r["temb"]), p(r["tproj"]), p(self.ws), self.ws.numel(), self.stream))
+            return r
         taps = (_lib.fg_wan_block_taps * depth)()
         for i, b in enumerate(r["blocks"]):
             for k, v in b.items():
                 setattr(taps[i], k, v.data_ptr())
-        p = lambda v: ctypes.c_void_p(v.data_ptr())  # noqa: E731
         _lib.check(self.L.fg_wan_forward_features(self.net._h, p(self.xd), p(self.td), p(r["out"]), B, Fr, self.lat[0], self.lat[1], start, store,
                                                   1 if kind == "bc" else 0, (ctypes.c_int * depth)(*range(depth)), taps, depth, p(r["tokens"]),
                                                   p(r["temb"]), p(self.ws), self.ws.numel(), self.stream))
@@ -169,13 +214,16 @@ class Gpu:
         torch.cuda.empty_cache()
 
 
-def _fetch(r, rows, Fr):
-    """The checked samples of a tapped call's results, fp64 on the CPU."""
+def _fetch(r, rows, Fr, odev="cpu"):
+    """The checked samples of a tapped call's results, fp64 where the oracle runs (the CPU, or the GPU for the largest cases)."""
     idx = torch.tensor(rows, device=r["out"].device)
     D = r["temb"].shape[1]
-    get = lambda v: v[idx].double().cpu()  # noqa: E731
-    return dict(out=get(r["out"]), tokens=get(r["tokens"]), temb=get(r["temb"].view(-1, Fr, D)).reshape(-1, D),
-                blocks=[{k: get(v) for k, v in b.items()} for b in r["blocks"]])
+    get = lambda v: v[idx].double().to(odev)  # noqa: E731
+    g = dict(out=get(r["out"]), tokens=get(r["tokens"]), temb=get(r["temb"].view(-1, Fr, D)).reshape(-1, D),
+             blocks=[b and {k: get(v) for k, v in b.items()} for b in r["blocks"]])
+    if "tproj" in r:
+        g["tproj"] = get(r["tproj"].view(-1, Fr, 6 * D)).reshape(-1, 6 * D)
+    return g
 
 
 def _err(e, d, dims):
@@ -226,16 +274,44 @@ def _tile(x, L):
     return x[:, 128 * ((L - 1) // 128):]
 
 
+def _rope_clamped(cfg, Fr, gh, gw, last):
+    """Mutant (n): RoPE from frame 0 with the TEMPORAL rows of frame f taken at min(f, last) (the first t_dim columns of a row)."""
+    t_dim = cfg.head_dim - 4 * (cfg.head_dim // 6)
+    idx = torch.clamp(torch.arange(Fr), max=last)
+    out = []
+    for v in R.rope_for_chunk(cfg, Fr, gh, gw, 0, torch.float64):
+        v = v.view(Fr, gh * gw, cfg.head_dim).clone()
+        v[:, :, :t_dim] = v[idx][:, :, :t_dim]
+        out.append(v.view(Fr * gh * gw, cfg.head_dim))
+    return out
+
+
+def _block(p, cfg, i, x, mod, cos, sin, kv2):
+    """Block i of the oracle under full self-attention: the stream behind it (mutant (q) runs the blocks a call passes over)."""
+    q, k, v = R.self_attn_qkv(p, cfg, i, x, mod, cos, sin)
+    x1 = R.self_attn_out(p, i, x, R.sdpa(q, k, v), mod)
+    return R.ffn(p, cfg, i, R.cross_attn(p, cfg, i, x1, *kv2)[1], mod)
+
+
 def run_case(c: Case, make_gpu, tol=TOL):
     """One case of the matrix: every call of its sequence, every block, every check.  make_gpu(c, cfg, sd) -> Gpu."""
     cfg = _cfg(c)
     seed = 4000 + c.seed + 7 * c.heads + c.B
-    sd = R.random_state_dict(cfg, seed=seed)
+    if c.r:  # the same draws, and behind them a second embedder at the first one's scale
+        import wan_full_ref
+
+        sd = wan_full_ref.random_state_dict(cfg, seed=seed, r_timestep=True)
+    else:
+        sd = R.random_state_dict(cfg, seed=seed)
     for k in sd:  # sharper self-attention than the fan-in scaled draw gives (score spread ~ Q_GAIN): positions and single keys matter
         if k.endswith("attn1.norm_q.weight"):
             sd[k] = sd[k] * Q_GAIN
     gpu = make_gpu(c, cfg, sd)
-    p = {k[len("transformer."):]: v.double() for k, v in sd.items()}
+    # pe: the weights on the CPU (the embedders and the patch embedding always run there); p: where the oracle's blocks run
+    odev = torch.device("cuda:0" if c.device_oracle else "cpu")
+    pe = {k[len("transformer."):]: v.double() for k, v in sd.items()}
+    p = {k: v.to(odev) for k, v in pe.items()} if c.device_oracle else pe
+    pr = {k.replace("r_embedder.", "condition_embedder."): v for k, v in pe.items() if k.startswith("r_embedder.")}
     del sd
     rows = _checked(c.B)
     Bc, D, H = len(rows), cfg.dim, cfg.num_heads
@@ -246,47 +322,84 @@ def run_case(c: Case, make_gpu, tol=TOL):
     text = torch.randn(c.B, c.text_len, cfg.text_dim, generator=torch.Generator().manual_seed(seed + 1))
     with torch.no_grad():
         gpu.set_text(text)
-        ctx = R.text_embedding(p, text[rows].double())
+        ctx = R.text_embedding(p, text[rows].double().to(odev))
         kv2 = [R.cross_kv(p, cfg, i, ctx) for i in range(cfg.num_layers)]
-        Kc = [torch.zeros(Bc, cap, H, 128, dtype=torch.float64) for _ in range(cfg.num_layers)]
-        Vc = [torch.zeros(Bc, cap, H, 128, dtype=torch.float64) for _ in range(cfg.num_layers)]
+        cached = any(k[0] == "ar" for k in c.calls)
+        Kc = [torch.zeros(Bc, cap, H, 128, dtype=torch.float64) for _ in range(cfg.num_layers if cached else 0)]
+        Vc = [torch.zeros(Bc, cap, H, 128, dtype=torch.float64) for _ in range(cfg.num_layers if cached else 0)]
         for ci, call in enumerate(c.calls):
-            kind, start, Fr, store = call
+            kind, start, Fr, store = call[:4]
+            full = kind == "full"
+            use_r, skipped = (bool(call[4]), tuple(call[5])) if full else (False, ())
             L, cs = Fr * fs, start * fs
-            x, tf = _inputs(c, cfg, call, ci, seed)
+            x, tf, rf = _inputs(c, cfg, call, ci, seed)
             # the untapped path is unchanged: same `out`, and a second tapped call reports the same taps
-            out_plain = gpu.plain(call, x, tf)
-            r1 = gpu.tapped(call, x, tf)
-            r2 = gpu.tapped(call, x, tf)
+            out_plain = gpu.plain(call, x, tf, rf)
+            r1 = gpu.tapped(call, x, tf, rf)
+            r2 = gpu.tapped(call, x, tf, rf)
             if not torch.equal(out_plain, r1["out"]):
                 rep.bad.append(("tapped out != fg_wan_forward's", ci))
             for i in range(cfg.num_layers):
-                if not torch.equal(r1["blocks"][i]["x_ffn"], r2["blocks"][i]["x_ffn"]):
+                if i not in skipped and not torch.equal(r1["blocks"][i]["x_ffn"], r2["blocks"][i]["x_ffn"]):
                     rep.bad.append(("x_ffn tap differs between two calls", ci, i))
-            g = _fetch(r1, rows, Fr)
+            if c.dtype == "fp8":  # (per-block bounds of that mode: not this matrix's)
+                del out_plain, r1, r2
+                continue
+            g = _fetch(r1, rows, Fr, odev)
             del out_plain, r1, r2
             sf = _views(Bc, Fr, L, D)
             sfh = _views(Bc, Fr, L, D, H)
             tile = [("sample,last tile", (Bc, -1), (1,))]
             row = [("sample,query,head", (Bc, L, H, 128), (3,))]
-            zero = torch.zeros(())
+            zero = torch.zeros((), dtype=torch.float64, device=odev)
+            per_row = lambda n: [("sample,frame", (Bc * Fr, n), (1,))]  # noqa: E731
             # temb: fourier features and the embedder linears in fp32, on the timesteps the kernels read
-            rep.check("temb", (ci,), g["temb"], R.time_embedding(p, cfg, tf[rows].double().reshape(-1)), zero, [("sample,frame", (Bc * Fr, D), (1,))])
+            temb_ref = R.time_embedding(pe, cfg, tf[rows].double().reshape(-1))
+            mut_tproj = {}
+            if full:
+                # ... and with r_frames the second embedder's rows on fp32(t - r) ("diff"; wan_r_rows_kernel) or r: temb + remb, and
+                # timestep_proj + r_timestep_proj (the `tproj` tap: what every block's modulation is formed from)
+                tproj_ref = R.time_projection(pe, temb_ref)
+                if use_r:
+                    def r_term(r_rows, diff):
+                        remb = R.time_embedding(pr, cfg, ((tf[rows] - r_rows) if diff else r_rows).double().reshape(-1))
+                        return remb, R.time_projection(pr, remb)
+
+                    temb_t, tproj_t, diff = temb_ref, tproj_ref, c.r == "diff"
+                    remb, rproj = r_term(rf[rows], diff)
+                    temb_ref, tproj_ref = temb_t + remb, tproj_t + rproj
+                    # (o) r taken per sample: every frame is given its neighbour's r.  (p) the wrong r term: none; the other
+                    # time_cond_type; r_timestep_proj added but remb not (wan_full_ref.WanFullRef's mutants)
+                    mo, mp = r_term(rf[rows].roll(1, 1), diff), r_term(rf[rows], not diff)
+                    muts = {"o": (temb_t + mo[0], tproj_t + mo[1]), "p:ignore_r": (temb_t, tproj_t), "p:swap_cond": (temb_t + mp[0], tproj_t + mp[1]),
+                            "p:proj_only": (temb_t, None)}
+                    for name, (me_, mp_) in muts.items():
+                        rep.mutant(name + ":temb", "temb", (ci,), g["temb"], me_.to(odev), zero, per_row(D), every=True)
+                        if mp_ is not None:
+                            rep.mutant(name + ":tproj", "tproj", (ci,), g["tproj"], mp_.to(odev), zero, per_row(6 * D), every=True)
+                    mut_tproj = {k: muts[k][1].to(odev) for k in ("p:ignore_r", "p:swap_cond")}
+                rep.check("tproj", (ci,), g["tproj"], tproj_ref.to(odev), zero, per_row(6 * D))
+            rep.check("temb", (ci,), g["temb"], temb_ref.to(odev), zero, per_row(D))
             # tokens_out: fp32 patch embedding stored as bf16, element by element
-            tok = R.patch_embed(p, x[rows].double())
+            tok = R.patch_embed(pe, x[rows].double()).to(odev)
             q_ = ((g["tokens"] - tok).abs() / (TOK_ULP * tok.abs() + TOK_ABS * tok.abs().max())).max()
             rep.worst["tok/derived"] = (max(rep.worst.get("tok/derived", (0.0, 0.0))[0], float(q_)), 0.0)
             if not q_ <= 1.0:
                 rep.bad.append(("tokens_out", ci, float(q_)))
-            tproj = R.time_projection(p, g["temb"])
-            cos, sin = R.rope_for_chunk(cfg, Fr, gh, gw, start, torch.float64)
+            # the rows the blocks read: the GPU's own (the full call taps them; else they are one fp32 linear behind the temb tap)
+            tproj = g["tproj"] if full else R.time_projection(p, g["temb"])
+            cos, sin = (v.to(odev) for v in R.rope_for_chunk(cfg, Fr, gh, gw, start, torch.float64))
             mask = R.blockwise_causal_mask(Fr, fs, cfg.chunk_size) if kind == "bc" else None
             x_in = g["tokens"]
+            pending = []  # the blocks the call passed over since the last one it ran
             for i, tap in enumerate(g["blocks"]):
+                if tap is None:  # skipped: the next block's input is still x_in
+                    pending.append(i)
+                    continue
                 w = (ci, i)
                 mod = R.modulation(p, i, tproj, Bc, Fr)
                 q, k, v = R.self_attn_qkv(p, cfg, i, x_in, mod, cos, sin)
-                kf, vf = (k, v) if kind == "bc" else (torch.cat([Kc[i][:, :cs], k], 1), torch.cat([Vc[i][:, :cs], v], 1))
+                kf, vf = (k, v) if kind != "ar" else (torch.cat([Kc[i][:, :cs], k], 1), torch.cat([Vc[i][:, :cs], v], 1))
                 att1 = R.sdpa(q, kf, vf, mask)
                 x1 = R.self_attn_out(p, i, x_in, att1, mod)
                 att2, x2 = R.cross_attn(p, cfg, i, x1, *kv2[i])
@@ -328,11 +441,38 @@ def run_case(c: Case, make_gpu, tol=TOL):
                 # (e) the last 17 keys dropped (block-causal: only the last chunk's queries see them)
                 me = R.sdpa(q, kf[:, :-17], vf[:, :-17], None if mask is None else mask[:, :-17])
                 rep.mutant("e:attn1", "attn1/row", w, tap["attn1"], me, zero, row)
+                if full and Fr > cfg.chunk_size:  # (m) the block-causal mask of the config's chunk_size in place of full attention
+                    mm = R.blockwise_causal_mask(Fr, fs, cfg.chunk_size).to(odev)
+                    rep.mutant("m:attn1", "attn1", w, tap["attn1"], R.sdpa(q, k, v, mm), zero, sfh)
+                    del mm
+                if full and Fr > cfg.total_num_frames:  # (n) the temporal RoPE index clamped at total_num_frames - 1
+                    c2, n2 = (t_.to(odev) for t_ in _rope_clamped(cfg, Fr, gh, gw, cfg.total_num_frames - 1))
+                    qm, km, _ = R.self_attn_qkv(p, cfg, i, x_in, mod, c2, n2)
+                    rep.mutant("n:attn1", "attn1", w, tap["attn1"], R.sdpa(qm, km, v), zero, sfh)
+                for name, tp_m in mut_tproj.items():  # (p) again, through the rows the wrong r term hands the blocks
+                    ms = R.modulation(p, i, tp_m, Bc, Fr)
+                    rep.mutant(name + ":inc1", "inc1", w, g1, R.self_attn_out(p, i, x_in, att1, ms) - x_in, zero, sf)
+                    rep.mutant(name + ":ffn", "ffn", w, g3, R.ffn(p, cfg, i, x2, ms) - x2, zero, sf)
+                if pending:  # (q) skip ignored: the reference runs the blocks the call passed over, and this block behind them
+                    xm = x_in
+                    for j in pending:
+                        xm = _block(p, cfg, j, xm, R.modulation(p, j, tproj, Bc, Fr), cos, sin, kv2[j])
+                    qm, km, vm = R.self_attn_qkv(p, cfg, i, xm, mod, cos, sin)
+                    rep.mutant("q:inc1", "inc1", w, g1, R.self_attn_out(p, i, xm, R.sdpa(qm, km, vm), mod) - x_in, zero, sf, every=True)
+                    pending = []
                 if kind == "ar" and store:
                     Kc[i][:, cs:cs + L], Vc[i][:, cs:cs + L] = k, v
                 x_in = tap["x_ffn"]
-            rep.check("out", (ci,), g["out"], R.final_layer(p, cfg, x_in, g["temb"], Fr, gh, gw), zero,
-                      [("sample,frame", (Bc, cfg.out_channels, Fr, -1), (1, 3))])
+            out_views = [("sample,frame", (Bc, cfg.out_channels, Fr, -1), (1, 3))]
+            rep.check("out", (ci,), g["out"], R.final_layer(p, cfg, x_in, g["temb"], Fr, gh, gw), zero, out_views)
+            if pending:  # (q) at the network's end: the output layer behind the blocks the call passed over
+                xm = x_in
+                for j in pending:
+                    xm = _block(p, cfg, j, xm, R.modulation(p, j, tproj, Bc, Fr), cos, sin, kv2[j])
+                rep.mutant("q:out", "out", (ci,), g["out"], R.final_layer(p, cfg, xm, g["temb"], Fr, gh, gw), zero, out_views, every=True)
+            if use_r:  # (p) "proj only" changes temb alone, which the output layer's modulation reads
+                rep.mutant("p:proj_only:out", "out", (ci,), g["out"], R.final_layer(p, cfg, x_in, temb_t.to(odev), Fr, gh, gw), zero, out_views,
+                           every=True)
     gpu.close()
     return rep
 

@@ -95,7 +95,7 @@ def test_forward_with_r_against_oracle_and_its_mutants(cond):
     for m in W.MUTANTS:
         dm = _rel(got, W.WanFullRef(sd, R.TINY, time_cond_type=cond, mutant=m).forward(x, t, text, r=r))
         print("  mutant", m, dm)
-        assert dm > d, (m, dm, d)
+        assert dm > d and dm > 5 * TOL, (m, dm, d)  # (the CPU test measures 0.38 ... 0.54 between each mutant and the oracle)
 
 
 # ---- 3. a zero r_embedder ----------------------------------------------------------------------------------------------------------

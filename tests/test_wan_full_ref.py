@@ -1,7 +1,9 @@
 """The bidirectional video DiT `Wan` (fastgen_amd/networks/Wan/network.py; fg_wan_create_ex, fg_wan_forward_full), what a machine
 without a GPU can hold: the oracle tests/wan_full_ref.py against the causal oracle it is composed from, its r term (zero embedder,
 "diff" against "abs"), that its mutants - the mistakes the GPU comparison has to catch - stand far enough from it, the module's state
-dict and r_embedder inits, the C ABI's parameter table and host-side refusals, and the module's refusals.  PARITY UNPINNED."""
+dict and r_embedder inits, the C ABI's parameter table and host-side refusals, and the module's refusals; for the per-block pin
+tests/test_gpu_wan_full_blocks.py: the launch plan of every case, the distance of its mutants (m) - (q) from the oracle, and the
+refusals of fg_wan_forward_full_features.  PARITY UNPINNED."""
 import ctypes
 import functools
 
@@ -227,6 +229,30 @@ def test_abi_create_ex_and_forward_full_refusals():
         # well-formed arguments on a handle whose weights were never packed
         assert full(hr, fake, sk(0, 1), 2) == FG_ENOTREADY and b"not packed" in L.fg_last_error()
         assert full(h0, None, None, 0) == FG_ENOTREADY
+
+        # fg_wan_forward_full_features: fg_wan_forward_features' tap checks, fg_wan_forward_full's, and a block in both lists
+        taps2 = (_lib.fg_wan_block_taps * 2)()
+
+        def feat(h, r=None, skip=None, n=0, blocks=sk(0, 1), taps=taps2, nt=2, frames=2):
+            return L.fg_wan_forward_full_features(h, fake, fake, r, ctypes.c_void_p(8192), 1, frames, 16, 16, skip, n, blocks, taps, nt, None, None,
+                                                  None, fake, 1 << 30, None)
+
+        assert feat(hr, skip=sk(1), n=1) == FG_EINVAL and b"both tapped and in skip_layers" in L.fg_last_error()
+        assert feat(hr, skip=sk(0, 1), n=2, blocks=sk(1), nt=1) == FG_EINVAL and b"both tapped" in L.fg_last_error()
+        assert feat(h0, r=fake) == FG_EINVAL and b"r_embedder" in L.fg_last_error()
+        for blocks in (sk(1, 0), sk(0, 0), sk(0, 2), sk(-1, 0)):
+            assert feat(hr, blocks=blocks) == FG_EINVAL and b"tap_blocks" in L.fg_last_error(), list(blocks)
+        assert feat(hr, blocks=None) == FG_EINVAL and feat(hr, taps=None) == FG_EINVAL and feat(hr, nt=-1) == FG_EINVAL
+        assert feat(hr, skip=sk(1, 1), n=2, blocks=sk(0), nt=1) == FG_EINVAL and b"skip_layers must be ascending" in L.fg_last_error()
+        # frames beyond the RoPE table (rope_max_seq_len = 1024): refused by both full calls from the arguments alone
+        assert feat(hr, frames=1025) == FG_EINVAL and b"RoPE table" in L.fg_last_error() and feat(hr, frames=1024) == FG_ENOTREADY
+        assert L.fg_wan_forward_full(hr, fake, fake, None, ctypes.c_void_p(8192), 1, 1025, 16, 16, None, 0, fake, 1 << 30, None) == FG_EINVAL
+        assert b"RoPE table" in L.fg_last_error()
+        assert L.fg_wan_forward_full_features(None, fake, fake, None, fake, 1, 2, 16, 16, None, 0, None, None, 0, None, None, None, fake, 1 << 30,
+                                              None) == FG_EINVAL
+        # well-formed (one block skipped, the other tapped; no taps at all) on handles that were never packed
+        assert feat(hr, r=fake, skip=sk(0), n=1, blocks=sk(1), nt=1) == FG_ENOTREADY and b"not packed" in L.fg_last_error()
+        assert feat(h0, blocks=None, taps=None, nt=0) == FG_ENOTREADY
         # workspace sizes: any frame count (the cap of total_num_frames = 6 is the causal calls'), 0 for a bad shape
         assert L.fg_wan_full_workspace_bytes(hr, 1, 12, 16, 24) > L.fg_wan_full_workspace_bytes(hr, 1, 5, 16, 24) > 0
         assert L.fg_wan_full_workspace_bytes(hr, 1, 5, 15, 24) == 0
@@ -301,3 +327,108 @@ def test_module_refusals():
         CausalWan(r_timestep=True, **KW)
     with torch.no_grad(), pytest.raises(NotImplementedError, match="skip_layers / r"):
         CausalWan(**KW)(x, t, condition=text, r=r)
+
+
+# ---- 8. the per-block pin of the bidirectional call (tests/test_gpu_wan_full_blocks.py), what holds without a GPU --------------------
+def _full_cases():
+    import test_gpu_wan_full_blocks as FB
+
+    return FB
+
+
+@pytest.mark.parametrize("name", list(_full_cases().CASES))
+def test_full_cases_reach_the_planned_kernels(name):
+    """The matrix of tests/test_gpu_wan_full_blocks.py covers the kernel forms it names: the launcher's own plan (fg_op_attention_plan,
+    scratch given as the engine gives it) for every case's self-attention (Lq == Lkv, ldk = D) and cross-attention (37 keys, ldk = 2 D)."""
+    from fastgen_amd import _lib
+
+    FB = _full_cases()
+    c = FB.CASES[name]
+    assert set(FB.PLANS) == set(FB.CASES)
+    D, Ltok = 128 * c.heads, c.calls[0][2] * (c.lat[0] // 2) * (c.lat[1] // 2)
+    got = []
+    for Lkv, ldk in ((Ltok, D), (c.text_len, 2 * D)):
+        p = _lib.fg_attention_plan()
+        assert _lib.lib().fg_op_attention_plan(128, c.B, c.heads, Ltok, Lkv, ldk, 1, 0, 0, ctypes.byref(p)) == 0 and p.refusal == 0
+        got.append((p.kernel, p.nsplit, p.t_cut, p.sample_major))
+    assert tuple(got) == FB.PLANS[name], (name, got)
+    # the last frame on the RoPE table's last row, unless the grid's rows / columns need a longer table
+    assert all(k[0] == "full" and c.rope_max == max(k[2], c.lat[0] // 2, c.lat[1] // 2) for k in c.calls)
+
+
+def test_full_matrix_names_every_kernel_form():
+    from fastgen_amd._lib import FG_FA_TILE128, FG_FA_WIDE, FG_FA_WIDE_CUT
+
+    FB = _full_cases()
+    selfs = {v[0] for v in FB.PLANS.values()}
+    assert {(FG_FA_TILE128, 1, 0, 0), (FG_FA_TILE128, 2, 0, 0), (FG_FA_TILE128, 1, 0, 1), (FG_FA_WIDE, 1, 0, 0), (FG_FA_WIDE, 3, 0, 0)} <= selfs
+    cuts = {(n, FB.CASES[n].B) for n, v in FB.PLANS.items() if v[0][0] == FG_FA_WIDE_CUT}
+    assert {b for _, b in cuts} == {2, 9}  # the cut at a batch > 1, and at B >= 8 past the sample-major limit ...
+    assert FB.PLANS["F1056-B9"][1] == (FG_FA_TILE128, 1, 0, 0)  # ... where the cross-attention (Lq > 1024) leaves that map too
+
+
+class OracleAsGpu:
+    """`test_gpu_wan_blocks.Gpu`'s interface answered by the fp64 oracle itself - its own composition of the pieces, apart from
+    run_case's: run_case then measures how far each mutant stands from the unmutated oracle (and that the two compositions agree:
+    r term, skipped blocks, taps).  Calls of kind "full" only."""
+
+    def __init__(self, c, cfg, sd):
+        self.c, self.cfg = c, cfg
+        self.p = {k[len("transformer."):]: v.double() for k, v in sd.items()}
+        self.pr = {k.replace("r_embedder.", "condition_embedder."): v for k, v in self.p.items() if k.startswith("r_embedder.")}
+
+    def set_text(self, text):
+        self.ctx = R.text_embedding(self.p, text.double())
+
+    def tapped(self, call, x, tf, rf=None):
+        cfg, p = self.cfg, self.p
+        kind, _, Fr, _, use_r, skip = call
+        assert kind == "full"
+        B, gh, gw = x.shape[0], x.shape[3] // 2, x.shape[4] // 2
+        temb = R.time_embedding(p, cfg, tf.double().reshape(-1))
+        tproj = R.time_projection(p, temb)
+        if use_r:
+            remb = R.time_embedding(self.pr, cfg, ((tf - rf) if self.c.r == "diff" else rf).double().reshape(-1))
+            temb, tproj = temb + remb, tproj + R.time_projection(self.pr, remb)
+        cos, sin = R.rope_for_chunk(cfg, Fr, gh, gw, 0, torch.float64)
+        hs = R.patch_embed(p, x.double())
+        r = dict(tokens=hs, temb=temb, tproj=tproj, blocks=[])
+        for i in range(cfg.num_layers):
+            if i in skip:
+                r["blocks"].append(None)
+                continue
+            mod = R.modulation(p, i, tproj, B, Fr)
+            q, k, v = R.self_attn_qkv(p, cfg, i, hs, mod, cos, sin)
+            att1 = R.sdpa(q, k, v)
+            x1 = R.self_attn_out(p, i, hs, att1, mod)
+            att2, x2 = R.cross_attn(p, cfg, i, x1, *R.cross_kv(p, cfg, i, self.ctx))
+            hs = R.ffn(p, cfg, i, x2, mod)
+            r["blocks"].append(dict(attn1=att1, x_attn1=x1, attn2=att2, x_attn2=x2, x_ffn=hs))
+        r["out"] = R.final_layer(p, cfg, hs, temb, Fr, gh, gw)
+        return r
+
+    def plain(self, call, x, tf, rf=None):
+        return self.tapped(call, x, tf, rf)["out"]
+
+    def close(self):
+        pass
+
+
+# the cases that carry a mutant of their own, and the small ones of the others ((m) - (q) are asserted on the GPU for every case)
+@pytest.mark.parametrize("name", ["F105", "F555", "F105-C8", "R-diff", "R-abs", "SKIP"])
+def test_full_block_mutants_stand_apart(name):
+    """Every mutant of the per-block pin - the causal file's and (m) block-causal mask, (n) clamped RoPE, (o) per-sample r, (p) wrong r
+    term, (q) skip ignored - differs from the unmutated fp64 oracle by at least MUTANT_FACTOR x the bound of the quantity it is checked
+    on, in the granule used, at the seeds the GPU test runs: the inputs are adequate.  (`rep.bad` also holds any disagreement of
+    run_case's composition with OracleAsGpu's.)"""
+    FB = _full_cases()
+    rep = FB.run_case(FB.CASES[name], OracleAsGpu, FB.TOL_FULL)
+    FB.report(name, rep)
+    assert not rep.bad, rep.bad
+    want = {"F105": {"m:attn1", "n:attn1"}, "F555": {"m:attn1", "n:attn1"}, "F105-C8": {"m:attn1", "n:attn1", "a:inc1", "f:attn2"},
+            "SKIP": {"q:inc1", "q:out", "m:attn1"},
+            "R-diff": {f"{m}:{q}" for m in ("o", "p:ignore_r", "p:swap_cond") for q in ("temb", "tproj")}
+            | {f"p:{m}:{q}" for m in ("ignore_r", "swap_cond") for q in ("inc1", "ffn")} | {"p:proj_only:temb", "p:proj_only:out"}}
+    want["R-abs"] = want["R-diff"]
+    assert want[name] | {"b:inc1", "b:ffn", "d:attn1", "e:attn1"} <= set(rep.mut), sorted(rep.mut)
+    assert all(v >= FB.MUTANT_FACTOR for v in rep.mut.values()), rep.mut
