@@ -16,6 +16,10 @@
 //              per element, then the hi / lo split — and retire finished half tiles: fp32 accumulators from the LDS hand-off,
 //              bias / temb / residual / scale, store, GroupNorm partial sums.
 // Consumers do nothing but ds_read_b128 (activations) -> v_mfma <- weights streamed from L2 through a 3-tap register ring.
+// The nine taps are walked as three row sweeps, one per column shift tx: each of the ten halo rows is read from LDS once per
+// sweep and multiplied with the taps (ty, tx), ty = 0,1,2, into output rows h - ty (a third of the LDS reads of a tap-by-tap
+// walk: profiles/r06_x3_*), and the halo rows that lie wholly outside the image (row 0 of a top tile, row 9 of a bottom tile)
+// are skipped.  RES_SUBPIX keeps the tap-by-tap walk over its four merged taps.
 // The MFMA runs transposed (A = weights [16 ch x 32 k], B = activations [32 k x 16 px]): a lane then holds 4 CONSECUTIVE channels
 // of one pixel, so the hand-off is 16 ds_write_b128 per lane and tile instead of 64 ds_write_b32.
 //
@@ -125,7 +129,7 @@ __global__ __launch_bounds__(X3_NTHR) void conv3_x3ws_kernel(const ConvArgs a, c
 #pragma unroll
         for (int j = 0; j < RN; ++j)
 #pragma unroll
-            for (int nt = 0; nt < 2; ++nt) wq[j][nt] = load_w((tcur & 3) * wphb + nt * wsb + j * X3_TAPB);
+            for (int nt = 0; nt < 2; ++nt) wq[j][nt] = load_w((tcur & 3) * wphb + nt * wsb + (SUB ? j : 3 * j) * X3_TAPB);  // 9 taps: slot ty holds tap (ty, 0)
 
         f32x4 acc[8][2];
 #pragma unroll
@@ -149,53 +153,102 @@ __global__ __launch_bounds__(X3_NTHR) void conv3_x3ws_kernel(const ConvArgs a, c
                 const int tnext = cn == 0 ? tcur + gstride : tcur;
                 const int wcur = (tcur & 3) * wphb + c * X3_STEPB;
                 const int wnxt = (ls + 1 < S) ? (tnext & 3) * wphb + cn * X3_STEPB : wcur;  // the very last refills re-read this step (never used)
-                // quarter-tap q: tap q >> 2, pixel rows 2 (q & 3), +1
-                auto read_x = [&](int q, X3Frag (&xf)[2]) {
-                    const int tap = q >> 2, m0 = 2 * (q & 3);
-                    const int off = ((SUB ? tap >> 1 : tap / 3) + m0) * G::RS + (SUB ? tap & 1 : tap % 3) * X3_PA;
+                if constexpr (!SUB) {
+                    // Row sweep: one pass over the ten halo rows per column shift tx.  Halo row h, read ONCE (one row ahead of its
+                    // MFMAs), feeds tap rows ty = 0,1,2 for output rows m = h - ty; ring slot ty holds tap (ty, tx).  Halo row 0 of
+                    // a tile at the top edge of the image and row 9 of one at the bottom edge are all zero: no read, no MFMAs
+                    // (wave-uniform; at 8x8 both, always, so there the test folds away).
+                    const int trow = (tcur % G::TPI) / G::TCOLS;
+                    const bool top = G::IPT == 2 || trow == 0;
+                    const bool bot = G::IPT == 2 || trow == G::W / G::TH - 1;
+                    auto read_row = [&](int i, X3Frag& xf) {
+                        const int tx = i / G::HH_, h = i % G::HH_;
+                        if ((h == 0 && top) || (h == G::HH_ - 1 && bot)) return;
+                        xf.hi = *reinterpret_cast<const bf16x8*>(abase + h * G::RS + tx * X3_PA);
+                        xf.lo = *reinterpret_cast<const bf16x8*>(abase + h * G::RS + tx * X3_PA + 4 * X3_PLANE);
+                    };
+                    auto mma_row = [&](int i, const X3Frag& xf) {
+                        const int tx = i / G::HH_, h = i % G::HH_;
+                        const bool live = !((h == 0 && top) || (h == G::HH_ - 1 && bot));
+                        // tap row by tap row: an output row gets one tap per halo row (small terms first), so the order of the
+                        // tap rows changes no sum, and a tap's slot is refilled right after its last MFMA (output row 7), ahead
+                        // of the row's other MFMAs, with (ty, tx + 1) or (ty, 0) of the next step / tile
 #pragma unroll
-                    for (int m = 0; m < 2; ++m) {
-                        xf[m].hi = *reinterpret_cast<const bf16x8*>(abase + off + m * G::RS);
-                        xf[m].lo = *reinterpret_cast<const bf16x8*>(abase + off + m * G::RS + 4 * X3_PLANE);
+                        for (int ty = 0; ty < 3; ++ty) {
+                            const int m = h - ty;
+                            if (m < 0 || m >= G::TH) continue;
+                            if (live) {
+#pragma unroll
+                                for (int term = 0; term < 3; ++term)
+#pragma unroll
+                                    for (int nt = 0; nt < 2; ++nt)
+                                        acc[m][nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(term == 1 ? wq[ty][nt].lo : wq[ty][nt].hi,
+                                                                                             term == 0 ? xf.lo : xf.hi, acc[m][nt], 0, 0, 0);
+                            }
+                            if (m != G::TH - 1) continue;
+                            const int pn = (tx < 2 ? wcur + (3 * ty + tx + 1) * X3_TAPB : wnxt + 3 * ty * X3_TAPB);
+#pragma unroll
+                            for (int nt = 0; nt < 2; ++nt) wq[ty][nt] = load_w(pn + nt * wsb);
+                        }
+                    };
+                    X3Frag xr[2];
+                    read_row(0, xr[0]);
+#pragma unroll
+                    for (int i = 0; i < 3 * G::HH_; ++i) {
+                        if (i + 1 < 3 * G::HH_) read_row(i + 1, xr[(i + 1) & 1]);
+                        __builtin_amdgcn_sched_barrier(0);
+                        mma_row(i, xr[i & 1]);
+                        __builtin_amdgcn_sched_barrier(0);
                     }
-                };
-                auto mma12 = [&](int q, const X3Frag (&xf)[2]) {
-                    const int tap = q >> 2, m0 = 2 * (q & 3);
-                    const X3Frag(&wf)[2] = wq[tap % RN];
-                    // small terms first; every accumulator is touched once per group of four MFMAs
+                } else {
+                    // RES_SUBPIX, 2x2 taps: quarter-tap q is tap q >> 2 = 2 ty + tx, pixel rows 2 (q & 3), +1
+                    auto read_x = [&](int q, X3Frag (&xf)[2]) {
+                        const int tap = q >> 2, m0 = 2 * (q & 3);
+                        const int off = ((tap >> 1) + m0) * G::RS + (tap & 1) * X3_PA;
 #pragma unroll
-                    for (int m = 0; m < 2; ++m)
+                        for (int m = 0; m < 2; ++m) {
+                            xf[m].hi = *reinterpret_cast<const bf16x8*>(abase + off + m * G::RS);
+                            xf[m].lo = *reinterpret_cast<const bf16x8*>(abase + off + m * G::RS + 4 * X3_PLANE);
+                        }
+                    };
+                    auto mma12 = [&](int q, const X3Frag (&xf)[2]) {
+                        const int tap = q >> 2, m0 = 2 * (q & 3);
+                        const X3Frag(&wf)[2] = wq[tap % RN];
+                        // small terms first; every accumulator is touched once per group of four MFMAs
 #pragma unroll
-                        for (int nt = 0; nt < 2; ++nt)
-                            acc[m0 + m][nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[nt].hi, xf[m].lo, acc[m0 + m][nt], 0, 0, 0);
+                        for (int m = 0; m < 2; ++m)
 #pragma unroll
-                    for (int m = 0; m < 2; ++m)
+                            for (int nt = 0; nt < 2; ++nt)
+                                acc[m0 + m][nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[nt].hi, xf[m].lo, acc[m0 + m][nt], 0, 0, 0);
 #pragma unroll
-                        for (int nt = 0; nt < 2; ++nt)
-                            acc[m0 + m][nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[nt].lo, xf[m].hi, acc[m0 + m][nt], 0, 0, 0);
+                        for (int m = 0; m < 2; ++m)
 #pragma unroll
-                    for (int m = 0; m < 2; ++m)
+                            for (int nt = 0; nt < 2; ++nt)
+                                acc[m0 + m][nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[nt].lo, xf[m].hi, acc[m0 + m][nt], 0, 0, 0);
 #pragma unroll
-                        for (int nt = 0; nt < 2; ++nt)
-                            acc[m0 + m][nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[nt].hi, xf[m].hi, acc[m0 + m][nt], 0, 0, 0);
-                    if ((q & 3) != 3) return;
-                    // the tap's fragments are dead: refill their ring slot RN taps ahead
-                    const int pn = (tap + RN < NTAP) ? wcur + (tap + RN) * X3_TAPB : wnxt + (tap + RN - NTAP) * X3_TAPB;
+                        for (int m = 0; m < 2; ++m)
 #pragma unroll
-                    for (int nt = 0; nt < 2; ++nt) wq[tap % RN][nt] = load_w(pn + nt * wsb);
-                };
-                X3Frag x0[2], x1[2];
-                read_x(0, x0);
+                            for (int nt = 0; nt < 2; ++nt)
+                                acc[m0 + m][nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[nt].hi, xf[m].hi, acc[m0 + m][nt], 0, 0, 0);
+                        if ((q & 3) != 3) return;
+                        // the tap's fragments are dead: refill their ring slot RN taps ahead
+                        const int pn = (tap + RN < NTAP) ? wcur + (tap + RN) * X3_TAPB : wnxt + (tap + RN - NTAP) * X3_TAPB;
 #pragma unroll
-                for (int q = 0; q < NQ; q += 2) {
-                    read_x(q + 1, x1);
-                    __builtin_amdgcn_sched_barrier(0);
-                    mma12(q, x0);
-                    __builtin_amdgcn_sched_barrier(0);
-                    if (q + 2 < NQ) read_x(q + 2, x0);
-                    __builtin_amdgcn_sched_barrier(0);
-                    mma12(q + 1, x1);
-                    __builtin_amdgcn_sched_barrier(0);
+                        for (int nt = 0; nt < 2; ++nt) wq[tap % RN][nt] = load_w(pn + nt * wsb);
+                    };
+                    X3Frag x0[2], x1[2];
+                    read_x(0, x0);
+#pragma unroll
+                    for (int q = 0; q < NQ; q += 2) {
+                        read_x(q + 1, x1);
+                        __builtin_amdgcn_sched_barrier(0);
+                        mma12(q, x0);
+                        __builtin_amdgcn_sched_barrier(0);
+                        if (q + 2 < NQ) read_x(q + 2, x0);
+                        __builtin_amdgcn_sched_barrier(0);
+                        mma12(q + 1, x1);
+                        __builtin_amdgcn_sched_barrier(0);
+                    }
                 }
                 if (c + 1 == nchunk) {
                     // tile finished: hand this group's half of the fp32 accumulators to the producers, restart from zero
