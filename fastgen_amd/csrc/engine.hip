@@ -1650,6 +1650,21 @@ int fg_op_attention_ex(const void* q, int ldq, int64_t q_bs, const void* k, cons
     HIP_TRY(rc);
     return FG_OK;
 }
+int fg_op_wan_dual_cross_attention(const void* q, int ldq, int64_t q_bs, const void* k_txt, const void* v_txt, int ldk_txt, int64_t kv_bs_txt,
+                                   int l_txt, const void* k_img, const void* v_img, int ldk_img, int64_t kv_bs_img, int l_img, void* out, int ldo,
+                                   int64_t o_bs, int batch, int heads, int lq, void* stream) {
+    if (!q || !k_txt || !v_txt || !out || ldq <= 0 || ldo <= 0 || (ldq % 8) || (ldo % 4) || ldk_txt <= 0 || (ldk_txt % 8) || q_bs < 0 ||
+        kv_bs_txt < 0 || o_bs < 0 || batch <= 0 || heads <= 0 || lq <= 0 || l_txt <= 0 || l_img < 0)
+        return fail(FG_EINVAL, "fg_op_wan_dual_cross_attention: bad argument (null pointer, ldq %% 8, ldk %% 8, ldo %% 4, a negative stride or count)");
+    if (l_img > 0 && (!k_img || !v_img || ldk_img <= 0 || (ldk_img % 8) || kv_bs_img < 0))
+        return fail(FG_EINVAL, "fg_op_wan_dual_cross_attention: bad image context (null pointer, ldk_img %% 8 or a negative stride)");
+    if (l_img == 0)  // the text attention alone: the launch a block without an image context makes
+        HIP_TRY(launch_fa128(q, ldq, q_bs, k_txt, v_txt, ldk_txt, kv_bs_txt, out, ldo, o_bs, batch, heads, lq, l_txt, (hipStream_t)stream, nullptr));
+    else
+        HIP_TRY(launch_wan_dual_xattn(q, ldq, q_bs, k_txt, v_txt, ldk_txt, kv_bs_txt, l_txt, k_img, v_img, ldk_img, kv_bs_img, l_img, out, ldo, o_bs,
+                                      batch, heads, lq, (hipStream_t)stream));
+    return FG_OK;
+}
 int fg_op_attention_split(const void* q, const void* k, const void* v, void* out, int batch, int heads, int head_dim, int lq, int lkv, int nsplit,
                           void* stream) {
     if (batch <= 0 || heads <= 0 || lq <= 0 || lkv <= 0 || (head_dim != 128 && head_dim != 72))

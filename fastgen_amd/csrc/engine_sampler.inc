@@ -183,6 +183,7 @@ int fg_wan_sampler_run(fg_wan* h, const fg_wan_sampler_config* sc, float* x, con
                        const float* eps, uint64_t seed, int batch, int frames, int height, int width, void* workspace, size_t workspace_bytes,
                        int use_graph, void* stream) {
     if (!h || !sc || !x || !t_list) return fail(FG_EINVAL, "null argument");
+    if (h->is_i2v) return fail(FG_EINVAL, "the chunked / causal loops are not implemented for an image-to-video handle");
     int rc = check_sampler_args(t_list, steps, sample_type, FG_LOOP_X0, sc->schedule);
     if (rc) return rc;
     if (!(sc->t_scale > 0.0)) return fail(FG_EINVAL, "t_scale must be positive");
@@ -364,6 +365,7 @@ int fg_wan_guided_sampler_run(fg_wan* h, const fg_wan_guided_sampler_config* sc,
                               const float* eps, uint64_t seed, int batch, int frames, int height, int width, void* workspace,
                               size_t workspace_bytes, int use_graph, void* stream) {
     if (!h || !sc || !x || !t_list || !table) return fail(FG_EINVAL, "null argument");
+    if (h->is_i2v) return fail(FG_EINVAL, "the chunked / causal loops are not implemented for an image-to-video handle");
     if (steps < 1 || steps > kGuidedMaxSteps) return fail(FG_EINVAL, "steps must be in [1, %d]", kGuidedMaxSteps);
     if (!(sc->t_scale > 0.0)) return fail(FG_EINVAL, "t_scale must be positive");
     if (sc->guidance != 0 && sc->guidance != 1) return fail(FG_EINVAL, "guidance must be 0 (batch B) or 1 (stacked batch 2 B)");
@@ -470,7 +472,7 @@ struct WanFullLoopWs {
 };
 
 size_t wan_full_sampler_plan(const fg_wan* h, int B, int Fr, int H, int W, Arena& A, WanFullLoopWs& w) {
-    const size_t per = (size_t)B * h->cfg.in_channels * Fr * H * W;
+    const size_t per = (size_t)B * h->vch() * Fr * H * W;  // (the video's channels: the latents alone on an image-to-video handle)
     w.x = A.get<float>(per);
     w.v = A.get<float>(per);
     w.pred = A.get<float>(per);
@@ -492,7 +494,7 @@ struct WanFullGuidedWs {
 };
 
 size_t wan_full_guided_plan(const fg_wan* h, int B, int stack, int Fr, int H, int W, int steps, Arena& A, WanFullGuidedWs& w) {
-    const size_t per = (size_t)B * h->cfg.in_channels * Fr * H * W;
+    const size_t per = (size_t)B * h->vch() * Fr * H * W;  // (the video's channels: the latents alone on an image-to-video handle)
     w.xin = A.get<float>(per * stack);
     w.v = A.get<float>(per * stack);
     w.xl = A.get<float>(per);
@@ -540,8 +542,10 @@ int fg_wan_full_sampler_run(fg_wan* h, const fg_wan_sampler_config* sc, const fl
     if (need > workspace_bytes) return fail(FG_ENOMEM, "workspace too small: need %zu bytes, got %zu", need, workspace_bytes);
     if (!h->packed) return fail(FG_ENOTREADY, "weights are not packed (call fg_wan_pack_weights)");
     if (h->text_B != batch) return fail(FG_ENOTREADY, "no text condition for batch %d (call fg_wan_set_text)", batch);
+    if (h->is_i2v && (h->ff_B != batch || h->ff_F != frames || h->ff_H != height || h->ff_W != width))
+        return fail(FG_ENOTREADY, "no image-to-video condition for batch %d, %d frames of %d x %d (call fg_wan_set_i2v_cond)", batch, frames, height, width);
     const int rows = batch * frames;
-    const int64_t total = (int64_t)batch * h->cfg.in_channels * frames * height * width;
+    const int64_t total = (int64_t)batch * h->vch() * frames * height * width;
     auto enqueue = [&](hipStream_t q) -> int {
         // the network on w.x at t_i into v; ri: MeanFlow's r (-1: 0, else t_list[ri]), -2: none.  The rows carry r itself: the call
         // forms t - r for time_cond_diff
@@ -567,7 +571,8 @@ int fg_wan_full_sampler_run(fg_wan* h, const fg_wan_sampler_config* sc, const fl
     return sampler_launch(h->sampler, batch, t_list, steps, sample_type, loop_kind, seed, w.tl, w.seed, use_graph,
                           {frames, height, width, (int64_t)(uintptr_t)noise, (int64_t)(uintptr_t)eps, (int64_t)(uintptr_t)out,
                            (int64_t)(uintptr_t)workspace, tsb, sc->net_pred_flow, sc->schedule, (int64_t)h->text_L,
-                           (int64_t)(uintptr_t)h->blocks[0].kv2, (int64_t)h->fp8, h->ext.time_cond_diff},
+                           (int64_t)(uintptr_t)h->blocks[0].kv2, (int64_t)h->fp8, h->ext.time_cond_diff,
+                           (int64_t)(uintptr_t)h->ff, (int64_t)(uintptr_t)h->blocks[0].kvi, (int64_t)h->img_L},
                           (hipStream_t)stream, enqueue);
 }
 
@@ -602,12 +607,14 @@ int fg_wan_full_guided_sampler_run(fg_wan* h, const fg_wan_guided_sampler_config
     if (!h->packed) return fail(FG_ENOTREADY, "weights are not packed (call fg_wan_pack_weights)");
     if (h->text_B != Be)
         return fail(FG_ENOTREADY, "no text condition for batch %d (call fg_wan_set_text%s)", Be, guided ? " with [cond; neg_cond]" : "");
+    if (h->is_i2v && (h->ff_B != Be || h->ff_F != frames || h->ff_H != height || h->ff_W != width))
+        return fail(FG_ENOTREADY, "no image-to-video condition for batch %d, %d frames of %d x %d (call fg_wan_set_i2v_cond)", Be, frames, height, width);
     hipStream_t s = (hipStream_t)stream;
     int rc;
     if ((rc = wan_upload_step_scalars(h, t_list, table, steps, 0, w.sc, s))) return rc;  // (no draw in this loop: the seed slot goes unread)
     const double* tl = w.sc;
     const double* tab = w.sc + steps + 1;
-    const int64_t total = (int64_t)batch * h->cfg.in_channels * frames * height * width;
+    const int64_t total = (int64_t)batch * h->vch() * frames * height * width;
     float* x2 = guided ? w.xin + total : nullptr;  // the unconditional rows of the stacked input
     auto enqueue = [&](hipStream_t q) -> int {
         HIP_TRY(hipMemcpyAsync(w.xin, x, sizeof(float) * total, hipMemcpyDeviceToDevice, q));
@@ -627,6 +634,7 @@ int fg_wan_full_guided_sampler_run(fg_wan* h, const fg_wan_guided_sampler_config
     int64_t tsb;
     memcpy(&tsb, &sc->t_scale, 8);
     const std::vector<int64_t> key = {batch, guided, frames, height, width, steps, (int64_t)(uintptr_t)x, (int64_t)(uintptr_t)workspace, tsb,
-                                      (int64_t)h->text_L, (int64_t)(uintptr_t)h->blocks[0].kv2, (int64_t)h->fp8, h->ext.time_cond_diff};
+                                      (int64_t)h->text_L, (int64_t)(uintptr_t)h->blocks[0].kv2, (int64_t)h->fp8, h->ext.time_cond_diff,
+                                      (int64_t)(uintptr_t)h->ff, (int64_t)(uintptr_t)h->blocks[0].kvi, (int64_t)h->img_L};
     return graph_run(h->full_guided_graph, key, h->sampler.cap, s, enqueue);
 }

@@ -18,10 +18,14 @@ struct fg_wan : HandleBase {
         int sst, q_w, q_b, k_w, k_b, v_w, v_b, o_w, o_b, nq, nk;          // attn1
         int q2_w, q2_b, k2_w, k2_b, v2_w, v2_b, o2_w, o2_b, nq2, nk2;      // attn2
         int n2_w, n2_b, f0_w, f0_b, f2_w, f2_b;
+        int ak_w = -1, ak_b = -1, av_w = -1, av_b = -1, nak = -1;  // attn2.add_k_proj / add_v_proj / norm_added_k (fg_wan_create_i2v, image_dim > 0)
         void *p_qkv = nullptr, *p_o = nullptr, *p_q2 = nullptr, *p_kv2 = nullptr, *p_o2 = nullptr, *p_f0 = nullptr, *p_f2 = nullptr;  // bf16 [N][K] (fp8: above)
         float *b_qkv = nullptr, *b_kv2 = nullptr, *n2mod = nullptr;  // fused biases; norm2 as {shift = bias, scale = weight - 1}
         void *kc = nullptr, *vc = nullptr;   // self-attention cache [B][cap][D] bf16
         void* kv2 = nullptr;                 // cross-attention cache [B][Lt][2 D] bf16 (k normalised | v)
+        void* p_akv = nullptr;               // add_k_proj | add_v_proj, bf16 [2 D][D] in every mode (as p_kv2)
+        float* b_akv = nullptr;
+        void* kvi = nullptr;                 // image cross-attention cache [B][ceil32(Li)][2 D] bf16 (k normalised | v), zero-filled
     };
     std::vector<Blk> blocks;
     int sst = -1, pe_w = -1, pe_b = -1, t1_w = -1, t1_b = -1, t2_w = -1, t2_b = -1, tp_w = -1, tp_b = -1, x1_w = -1, x1_b = -1, x2_w = -1,
@@ -30,6 +34,21 @@ struct fg_wan : HandleBase {
     // fg_wan_create_ex: the second time embedder `r_embedder` (Wan/network.py:615-619, 799-834) and what it is given
     // (time_cond_type "diff": t - r).  Both zero on a fg_wan_create handle.
     fg_wan_ext_config ext{0, 0};
+    // fg_wan_create_i2v: the image-to-video network (WanI2V/network.py, Wan2.1-I2V convention).  The video (x_t, out, the samplers'
+    // frames) then has i2v.latent_channels channels while the patch embedding reads cfg.in_channels = 2 latent + 4: vch() is the
+    // video's count on every handle.  The condition (fg_wan_set_i2v_cond): the first-frame latents `ff` [B][latent][F][H][W] fp32, the
+    // embedded image tokens `img_tok` [B * Li][D] bf16 and the blocks' kvi, all owned here and rewritten in place while their shapes
+    // stay (the loops' graphs name them).
+    bool is_i2v = false;
+    fg_wan_i2v_config i2v{0, 0, 0};
+    int vch() const { return is_i2v ? i2v.latent_channels : cfg.in_channels; }
+    int in1_w = -1, in1_b = -1, if0_w = -1, if0_b = -1, if2_w = -1, if2_b = -1, in2_w = -1, in2_b = -1;  // condition_embedder.image_embedder
+    void *p_if0 = nullptr, *p_if2 = nullptr;  // its two linears, bf16
+    float* ff = nullptr;
+    void* img_tok = nullptr;
+    int ff_B = 0, ff_F = 0, ff_H = 0, ff_W = 0;  // ff_B == 0: no condition set
+    int img_L = 0;                               // image tokens per sample of the condition (0: no image context)
+    size_t ff_elems = 0, img_rows = 0;           // what ff / img_tok + kvi are allocated for
     int r1_w = -1, r1_b = -1, r2_w = -1, r2_b = -1, rp_w = -1, rp_b = -1;
     float2 *tab_t = nullptr, *tab_h = nullptr, *tab_w = nullptr;  // RoPE axis tables
     int npt = 0, nph = 0, npw = 0;
@@ -230,6 +249,11 @@ int wan_pack(fg_wan* h, const ParamGroup& in_group, hipStream_t s) {
                 (rc = h->alloc(&b.p_f2, D * Fd * 2)) || (rc = h->alloc((void**)&b.b_qkv, 3 * D * 4)) ||
                 (rc = h->alloc((void**)&b.b_kv2, 2 * D * 4)) || (rc = h->alloc((void**)&b.n2mod, 2 * D * 4)))
                 return rc;
+            if (h->i2v.image_dim > 0 && ((rc = h->alloc(&b.p_akv, 2 * D * D * 2)) || (rc = h->alloc((void**)&b.b_akv, 2 * D * 4)))) return rc;
+        }
+        if (h->i2v.image_dim > 0) {
+            const size_t Di = h->i2v.image_dim;
+            if ((rc = h->alloc(&h->p_if0, Di * Di * 2)) || (rc = h->alloc(&h->p_if2, D * Di * 2))) return rc;
         }
         for (size_t i = 0; i < h->params.size(); ++i)
             if (!h->pack_only[i] && !h->is_logvar((int)i) && (rc = h->alloc((void**)&h->own[i], sizeof(float) * (size_t)h->params[i].numel))) return rc;
@@ -242,6 +266,11 @@ int wan_pack(fg_wan* h, const ParamGroup& in_group, hipStream_t s) {
     if (in_group(h->params[h->x1_w].name)) {
         HIP_TRY(launch_cvt_bf16(raw(h->x1_w), h->p_x1, D * Td, s));
         HIP_TRY(launch_cvt_bf16(raw(h->x2_w), h->p_x2, D * D, s));
+        if (h->i2v.image_dim > 0) {  // (the image embedder shares the text embedder's prefix: the same group)
+            const size_t Di = h->i2v.image_dim;
+            HIP_TRY(launch_cvt_bf16(raw(h->if0_w), h->p_if0, Di * Di, s));
+            HIP_TRY(launch_cvt_bf16(raw(h->if2_w), h->p_if2, D * Di, s));
+        }
     }
     const int g1 = (int)((D + 255) / 256);
     for (fg_wan::Blk& b : h->blocks) {
@@ -259,9 +288,16 @@ int wan_pack(fg_wan* h, const ParamGroup& in_group, hipStream_t s) {
         hipLaunchKernelGGL(wan_cat_kernel, dim3(g1), dim3(256), 0, s, raw(b.q_b), raw(b.k_b), raw(b.v_b), b.b_qkv, (int)D);
         hipLaunchKernelGGL(wan_cat_kernel, dim3(g1), dim3(256), 0, s, raw(b.k2_b), raw(b.v2_b), (const float*)nullptr, b.b_kv2, (int)D);
         hipLaunchKernelGGL(wan_n2mod_kernel, dim3(g1), dim3(256), 0, s, raw(b.n2_w), raw(b.n2_b), b.n2mod, (int)D);
+        if (b.p_akv) {  // the image side: bf16 in every mode, like the text side
+            __bf16* akv = (__bf16*)b.p_akv;
+            HIP_TRY(launch_cvt_bf16(raw(b.ak_w), akv, D * D, s));
+            HIP_TRY(launch_cvt_bf16(raw(b.av_w), akv + D * D, D * D, s));
+            hipLaunchKernelGGL(wan_cat_kernel, dim3(g1), dim3(256), 0, s, raw(b.ak_b), raw(b.av_b), (const float*)nullptr, b.b_akv, (int)D);
+        }
         HIP_TRY(hipGetLastError());
     }
     h->text_B = h->other.text_B = 0;  // the text caches (of both tags) were computed with the previous weights
+    h->ff_B = 0;                      // ... and so was the image-to-video condition
     return FG_OK;
 }
 
@@ -269,10 +305,22 @@ int wan_pack(fg_wan* h, const ParamGroup& in_group, hipStream_t s) {
 
 extern "C" {
 
-int fg_wan_create(const fg_wan_config* cfg, fg_wan** out) { return fg_wan_create_ex(cfg, nullptr, out); }
+}  // extern "C" (reopened below)
 
-int fg_wan_create_ex(const fg_wan_config* cfg, const fg_wan_ext_config* ext, fg_wan** out) {
+namespace {
+// fg_wan_create_ex and fg_wan_create_i2v: one table builder.  i2v == nullptr: the plain network.
+int wan_create(const fg_wan_config* cfg, const fg_wan_ext_config* ext, const fg_wan_i2v_config* i2v, fg_wan** out) {
     if (!cfg || !out) return fail(FG_EINVAL, "null argument");
+    if (i2v) {
+        if (i2v->mask_channels != 4) return fail(FG_EINVAL, "mask_channels %d unsupported (4 = scale_factor_temporal)", i2v->mask_channels);
+        if (i2v->latent_channels <= 0 || cfg->in_channels != 2 * i2v->latent_channels + i2v->mask_channels)
+            return fail(FG_EINVAL, "in_channels %d must be 2 * latent_channels + mask_channels = %d", cfg->in_channels,
+                        2 * i2v->latent_channels + i2v->mask_channels);
+        if (cfg->out_channels != i2v->latent_channels)
+            return fail(FG_EINVAL, "out_channels %d must equal latent_channels %d", cfg->out_channels, i2v->latent_channels);
+        if (i2v->image_dim < 0 || (i2v->image_dim % 64)) return fail(FG_EINVAL, "image_dim %d must be 0 or a multiple of 64", i2v->image_dim);
+    }
+    const int Di = i2v ? i2v->image_dim : 0;
     if (ext && ((ext->r_timestep != 0 && ext->r_timestep != 1) || (ext->time_cond_diff != 0 && ext->time_cond_diff != 1)))
         return fail(FG_EINVAL, "r_timestep and time_cond_diff must be 0 or 1");
     if (cfg->head_dim != 128) return fail(FG_EINVAL, "head_dim %d unsupported (128)", cfg->head_dim);
@@ -309,6 +357,15 @@ int fg_wan_create_ex(const fg_wan_config* cfg, const fg_wan_ext_config* ext, fg_
     h->x1_b = h->add("condition_embedder.text_embedder.linear_1.bias", {D});
     h->x2_w = h->add("condition_embedder.text_embedder.linear_2.weight", {D, D});
     h->x2_b = h->add("condition_embedder.text_embedder.linear_2.bias", {D});
+    if (Di > 0) {
+        // WanImageEmbedding (diffusers' WanTimeTextImageEmbedding.image_embedder, without pos_embed): norm1, ff, norm2.  UNPINNED: read
+        // from the reference's key map (Wan/network.py:1029-1049) and diffusers' module order, not recorded from a run.
+        const std::string ie = "condition_embedder.image_embedder.";
+        h->in1_w = h->add(ie + "norm1.weight", {Di}); h->in1_b = h->add(ie + "norm1.bias", {Di});
+        h->if0_w = h->add(ie + "ff.net.0.proj.weight", {Di, Di}); h->if0_b = h->add(ie + "ff.net.0.proj.bias", {Di});
+        h->if2_w = h->add(ie + "ff.net.2.weight", {D, Di}); h->if2_b = h->add(ie + "ff.net.2.bias", {D});
+        h->in2_w = h->add(ie + "norm2.weight", {D}); h->in2_b = h->add(ie + "norm2.bias", {D});
+    }
     for (int i = 0; i < cfg->num_layers; ++i) {
         const std::string b = "blocks." + std::to_string(i) + ".";
         fg_wan::Blk k;
@@ -323,6 +380,11 @@ int fg_wan_create_ex(const fg_wan_config* cfg, const fg_wan_ext_config* ext, fg_
         k.v2_w = h->add(b + "attn2.to_v.weight", {D, D}); k.v2_b = h->add(b + "attn2.to_v.bias", {D});
         k.o2_w = h->add(b + "attn2.to_out.0.weight", {D, D}); k.o2_b = h->add(b + "attn2.to_out.0.bias", {D});
         k.nq2 = h->add(b + "attn2.norm_q.weight", {D}); k.nk2 = h->add(b + "attn2.norm_k.weight", {D});
+        if (Di > 0) {  // (UNPINNED, as the image embedder's keys above)
+            k.ak_w = h->add(b + "attn2.add_k_proj.weight", {D, D}); k.ak_b = h->add(b + "attn2.add_k_proj.bias", {D});
+            k.av_w = h->add(b + "attn2.add_v_proj.weight", {D, D}); k.av_b = h->add(b + "attn2.add_v_proj.bias", {D});
+            k.nak = h->add(b + "attn2.norm_added_k.weight", {D});
+        }
         k.n2_w = h->add(b + "norm2.weight", {D}); k.n2_b = h->add(b + "norm2.bias", {D});
         k.f0_w = h->add(b + "ffn.net.0.proj.weight", {Fd, D}); k.f0_b = h->add(b + "ffn.net.0.proj.bias", {Fd});
         k.f2_w = h->add(b + "ffn.net.2.weight", {D, Fd}); k.f2_b = h->add(b + "ffn.net.2.bias", {D});
@@ -348,9 +410,22 @@ int fg_wan_create_ex(const fg_wan_config* cfg, const fg_wan_ext_config* ext, fg_
     h->dirty.assign(h->params.size(), 1);
     h->pack_only[h->x1_w] = h->pack_only[h->x2_w] = 1;
     for (const fg_wan::Blk& k : h->blocks)
-        for (int idx : {k.q_w, k.k_w, k.v_w, k.o_w, k.q2_w, k.k2_w, k.v2_w, k.o2_w, k.f0_w, k.f2_w}) h->pack_only[idx] = 1;
+        for (int idx : {k.q_w, k.k_w, k.v_w, k.o_w, k.q2_w, k.k2_w, k.v2_w, k.o2_w, k.f0_w, k.f2_w, k.ak_w, k.av_w})
+            if (idx >= 0) h->pack_only[idx] = 1;
+    if (Di > 0) h->pack_only[h->if0_w] = h->pack_only[h->if2_w] = 1;
+    if (i2v) h->is_i2v = true, h->i2v = *i2v;
     *out = h;
     return FG_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int fg_wan_create(const fg_wan_config* cfg, fg_wan** out) { return wan_create(cfg, nullptr, nullptr, out); }
+int fg_wan_create_ex(const fg_wan_config* cfg, const fg_wan_ext_config* ext, fg_wan** out) { return wan_create(cfg, ext, nullptr, out); }
+int fg_wan_create_i2v(const fg_wan_config* cfg, const fg_wan_ext_config* ext, const fg_wan_i2v_config* i2v, fg_wan** out) {
+    if (!i2v) return fail(FG_EINVAL, "null argument");
+    return wan_create(cfg, ext, i2v, out);
 }
 
 void fg_wan_destroy(fg_wan* h) {
@@ -487,6 +562,114 @@ int fg_wan_set_text(fg_wan* h, const float* text, int batch, int text_len, void*
     return FG_OK;
 }
 
+// fg_wan_set_i2v_cond's scratch for M = batch * image_len rows: LayerNorm'd image bf16 [M][Di], the hidden [M][Di], the embedder's
+// output before norm2 [M][D], add_k | add_v [M][2 D]
+size_t fg_wan_i2v_cond_workspace_bytes(const fg_wan* h, int batch, int image_len) {
+    if (!h || !h->is_i2v || batch <= 0 || image_len < 0 || image_len > 1024) return 0;
+    const size_t M = (size_t)batch * image_len, D = h->D, Di = h->i2v.image_dim;
+    return ((M * (2 * Di + 3 * D) * 2 + 4 * 256) + 255) & ~(size_t)255;
+}
+
+int fg_wan_set_i2v_cond(fg_wan* h, const float* first_frame_cond, const float* image, int batch, int frames, int height, int width, int image_len,
+                        void* workspace, size_t workspace_bytes, void* stream) {
+    if (!h || !first_frame_cond) return fail(FG_EINVAL, "null argument");
+    if (!h->is_i2v) return fail(FG_EINVAL, "not an image-to-video handle (fg_wan_create_i2v)");
+    if (batch <= 0 || frames <= 0 || height <= 0 || width <= 0 || (height & 1) || (width & 1)) return fail(FG_EINVAL, "bad batch / frames / size");
+    if (image_len < 0 || image_len > 1024) return fail(FG_EINVAL, "image_len %d outside [0, 1024]", image_len);
+    if (!h->packed) return fail(FG_ENOTREADY, "weights are not packed (call fg_wan_pack_weights)");
+    hipStream_t s = (hipStream_t)stream;
+    const size_t D = h->D, Di = h->i2v.image_dim;
+    // image == NULL, image_len == 0 or no image parameters: the reference's empty image context (network_causal.py:297-302)
+    const int Li = (image && Di > 0) ? image_len : 0, Lp = (Li + 31) & ~31;
+    const size_t M = (size_t)batch * Li, rows = (size_t)batch * Lp;
+    if (Li > 0) {
+        const size_t need = fg_wan_i2v_cond_workspace_bytes(h, batch, Li);
+        if (!workspace || (((uintptr_t)workspace) & 255)) return fail(FG_EINVAL, "bad workspace");
+        if (need > workspace_bytes) return fail(FG_ENOMEM, "workspace too small: need %zu bytes, got %zu", need, workspace_bytes);
+    }
+    const size_t elems = (size_t)batch * h->i2v.latent_channels * frames * height * width;
+    int rc;
+    h->ff_B = 0;  // (nothing valid until everything below is in place)
+    if (elems != h->ff_elems) {
+        h->drop_graphs();
+        h->free(h->ff);
+        h->ff = nullptr, h->ff_elems = 0;
+        if ((rc = h->alloc((void**)&h->ff, elems * sizeof(float)))) return rc;
+        h->ff_elems = elems;
+    }
+    if (rows != h->img_rows) {
+        h->drop_graphs();
+        h->img_rows = 0;
+        h->free(h->img_tok);
+        h->img_tok = nullptr;
+        for (fg_wan::Blk& b : h->blocks) {
+            h->free(b.kvi);
+            b.kvi = nullptr;
+        }
+        if (rows > 0) {
+            if ((rc = h->alloc(&h->img_tok, rows * D * 2))) return rc;
+            for (fg_wan::Blk& b : h->blocks) {  // whole 32-key tiles per sample, zero-filled: the padding rows stay zero
+                if ((rc = h->alloc(&b.kvi, rows * 2 * D * 2))) return rc;
+                HIP_TRY(hipMemsetAsync(b.kvi, 0, rows * 2 * D * 2, s));
+            }
+        }
+        h->img_rows = rows;
+    }
+    HIP_TRY(hipMemcpyAsync(h->ff, first_frame_cond, elems * sizeof(float), hipMemcpyDeviceToDevice, s));
+    if (Li > 0) {
+        auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
+        char* ws = (char*)workspace;
+        void* a0 = ws;
+        void* a1 = (char*)a0 + up(M * Di * 2);
+        void* a2 = (char*)a1 + up(M * Di * 2);
+        void* a3 = (char*)a2 + up(M * D * 2);
+        // WanImageEmbedding: FP32LayerNorm - Linear - GELU (erf) - Linear - FP32LayerNorm, eps 1e-5 (bf16 operands in every mode: once
+        // per condition, like the text side)
+        HIP_TRY(launch_wan_ln_rows(0, image, h->P(h->in1_w), h->P(h->in1_b), a0, (int)M, (int)Di, 1e-5f, s));
+        if ((rc = wan_gemm(WanOperand{a0}, h->p_if0, h->P(h->if0_b), a1, (int)M, (int)Di, (int)Di, s))) return rc;
+        HIP_TRY(launch_wan_gelu_erf(a1, (int64_t)(M * Di), s));
+        if ((rc = wan_gemm(WanOperand{a1}, h->p_if2, h->P(h->if2_b), a2, (int)M, (int)D, (int)Di, s))) return rc;
+        HIP_TRY(launch_wan_ln_rows(1, a2, h->P(h->in2_w), h->P(h->in2_b), h->img_tok, (int)M, (int)D, 1e-5f, s));
+        // per block: k_img = norm_added_k(add_k_proj(img)), v_img = add_v_proj(img), scattered to the sample's padded rows
+        for (fg_wan::Blk& b : h->blocks) {
+            if ((rc = wan_gemm(WanOperand{h->img_tok}, b.p_akv, b.b_akv, a3, (int)M, (int)(2 * D), (int)D, s))) return rc;
+            HIP_TRY(launch_rms_rope((int)D, a3, (int)(2 * D), h->P(b.nak), h->cfg.eps, nullptr, b.kvi, (int64_t)Lp * 2 * D, 0, (int)(2 * D), (int)M, Li, s));
+            HIP_TRY(launch_rms_rope((int)D, (const __bf16*)a3 + D, (int)(2 * D), nullptr, h->cfg.eps, nullptr, (__bf16*)b.kvi + D, (int64_t)Lp * 2 * D, 0,
+                                    (int)(2 * D), (int)M, Li, s));
+        }
+    }
+    h->ff_B = batch, h->ff_F = frames, h->ff_H = height, h->ff_W = width, h->img_L = Li;
+    return FG_OK;
+}
+
+int fg_wan_i2v_cond_read(fg_wan* h, int block, float* img_tokens, float* k_img, float* v_img, void* stream) {
+    if (!h || !h->is_i2v) return fail(FG_EINVAL, "not an image-to-video handle (fg_wan_create_i2v)");
+    if (block < 0 || block >= (int)h->blocks.size()) return fail(FG_EINVAL, "block %d outside [0, %d)", block, (int)h->blocks.size());
+    if (h->ff_B == 0 || h->img_L == 0) return fail(FG_ENOTREADY, "no image context is set (call fg_wan_set_i2v_cond with image tokens)");
+    hipStream_t s = (hipStream_t)stream;
+    const int B = h->ff_B, Li = h->img_L, Lp = (Li + 31) & ~31, D = h->D;
+    if (img_tokens) HIP_TRY(launch_from_act(1, h->img_tok, img_tokens, (int64_t)B * Li * D, s));
+    if (!k_img && !v_img) return FG_OK;
+    // the cache rows are strided [B][Lp][2 D]: a half (k or v) of the valid rows is gathered into a temporary contiguous bf16 tensor
+    // (freed after the stream has drained: a test entry point, not a hot path)
+    void* tmp = nullptr;
+    HIP_TRY(hipMalloc(&tmp, (size_t)B * Li * D * 2));
+    int rc = 0;
+    for (int half = 0; half < 2 && !rc; ++half) {
+        float* dst = half ? v_img : k_img;
+        if (!dst) continue;
+        for (int b = 0; b < B && !rc; ++b)
+            rc = (int)hipMemcpy2DAsync((__bf16*)tmp + (size_t)b * Li * D, (size_t)D * 2,
+                                       (const __bf16*)h->blocks[block].kvi + (size_t)b * Lp * 2 * D + half * D, (size_t)2 * D * 2, (size_t)D * 2,
+                                       (size_t)Li, hipMemcpyDeviceToDevice, s);
+        if (!rc) rc = launch_from_act(1, tmp, dst, (int64_t)B * Li * D, s);
+    }
+    (void)hipStreamSynchronize(s);
+    (void)hipFree(tmp);
+    HIP_TRY((hipError_t)rc);
+    return FG_OK;
+}
+
 namespace {
 // self-attention caches: [B][total_num_frames * frame_seqlen][D] per block, (re)allocated and zeroed when batch or frame size change
 // (`_create_external_caches`, network_causal.py:708-812)
@@ -542,10 +725,13 @@ int wan_forward(fg_wan* h, const float* x_t, const float* t_frames, float* out, 
         if (frames > h->cfg.rope_max_seq_len)
             return fail(FG_EINVAL, "%d frames exceed the RoPE table (rope_max_seq_len = %d)", frames, h->cfg.rope_max_seq_len);
     }
+    if (h->is_i2v && !full) return fail(FG_EINVAL, "the chunked / causal calls are not implemented for an image-to-video handle");
     if (!h->packed) return fail(FG_ENOTREADY, "weights are not packed (call fg_wan_pack_weights)");
     if (batch <= 0 || frames <= 0 || height <= 0 || width <= 0 || (height & 1) || (width & 1) || !workspace || (((uintptr_t)workspace) & 255))
         return fail(FG_EINVAL, "bad batch / frames / size / workspace");
     if (h->text_B != batch) return fail(FG_ENOTREADY, "no text condition for batch %d (call fg_wan_set_text)", batch);
+    if (h->is_i2v && (h->ff_B != batch || h->ff_F != frames || h->ff_H != height || h->ff_W != width))
+        return fail(FG_ENOTREADY, "no image-to-video condition for batch %d, %d frames of %d x %d (call fg_wan_set_i2v_cond)", batch, frames, height, width);
     if (out == x_t) return fail(FG_EINVAL, "out must not alias x_t");
     hipStream_t s = (hipStream_t)stream;
     const fg_wan_config& c = h->cfg;
@@ -594,7 +780,10 @@ int wan_forward(fg_wan* h, const float* x_t, const float* t_frames, float* out, 
         HIP_TRY(launch_wan_add_r(w.temb, remb, (int64_t)BF * D, w.tproj, rproj, (int64_t)BF * 6 * D, s));
     }
     HIP_TRY(launch_wan_rope_table(h->tab_t, h->tab_h, h->tab_w, w.cs, L, fs, gw, cur_start_frame, c.rope_max_seq_len, h->npt, h->nph, h->npw, s));
-    HIP_TRY(launch_wan_patch_embed(x_t, h->P(h->pe_w), h->P(h->pe_b), w.x0, batch, c.in_channels, frames, height, width, D, s));
+    if (h->is_i2v)  // the virtual concat [x_t | mask | first_frame_cond] (WanI2V/network.py:310-327)
+        HIP_TRY(launch_wan_i2v_patch_embed(x_t, h->ff, h->P(h->pe_w), h->P(h->pe_b), w.x0, batch, h->i2v.latent_channels, frames, height, width, D, s));
+    else
+        HIP_TRY(launch_wan_patch_embed(x_t, h->P(h->pe_w), h->P(h->pe_b), w.x0, batch, c.in_channels, frames, height, width, D, s));
     void *x = w.x0, *xn = w.x1;
     int rc;
     const int64_t cbs = (int64_t)cap * D;
@@ -651,8 +840,15 @@ int wan_forward(fg_wan* h, const float* x_t, const float* t_frames, float* out, 
             return rc;
         HIP_TRY(launch_rms_rope(D, w.qkv, D, h->P(b.nq2), c.eps, nullptr, w.qn, (int64_t)L * D, 0, D, M, L, s));
         const int64_t tbs = (int64_t)h->text_L * 2 * D;
-        HIP_TRY(launch_fa128(w.qn, D, (int64_t)L * D, b.kv2, (const __bf16*)b.kv2 + D, 2 * D, tbs, w.att, D, (int64_t)L * D, batch, h->H, L,
-                             h->text_L, s, w.fa));
+        if (h->is_i2v && h->img_L > 0) {
+            // ... and, separately normalised, to the image tokens; the two outputs summed (network_causal.py:294-358)
+            const int64_t ibs = (int64_t)((h->img_L + 31) & ~31) * 2 * D;
+            HIP_TRY(launch_wan_dual_xattn(w.qn, D, (int64_t)L * D, b.kv2, (const __bf16*)b.kv2 + D, 2 * D, tbs, h->text_L, b.kvi, (const __bf16*)b.kvi + D,
+                                          2 * D, ibs, h->img_L, w.att, D, (int64_t)L * D, batch, h->H, L, s));
+        } else {
+            HIP_TRY(launch_fa128(w.qn, D, (int64_t)L * D, b.kv2, (const __bf16*)b.kv2 + D, 2 * D, tbs, w.att, D, (int64_t)L * D, batch, h->H, L,
+                                 h->text_L, s, w.fa));
+        }
         if (bt && bt->attn2) HIP_TRY(launch_from_act(1, w.att, bt->attn2, MD, s));
         if ((rc = wan_stage(h, w.att, D, w.y8, w.ys, M, s, a)) ||
             (rc = wan_gemm(a, b.p_o2, h->P(b.o2_b), xn, M, D, D, s, 0, nullptr, 0, 1, x, w.gs, w.gs_bytes)))

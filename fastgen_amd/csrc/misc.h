@@ -267,3 +267,15 @@ int launch_fa128(const void* q, int ldq, int64_t q_bs, const void* k, const void
                  int B, int heads, int Lq, int Lkv, hipStream_t s, void* scratch = nullptr);
 int launch_wan_final(int D, const void* x, const float* mod, const float* w, const float* bias, float* out, int ntok, int Fr, int gh, int gw, int C,
                      float eps, hipStream_t s);
+// wan_i2v.hip: what the image-to-video network adds (reference fastgen/networks/WanI2V/network.py, the Wan2.1-I2V convention)
+// softmax(q k_txt^T / sqrt(128)) v_txt + softmax(q k_img^T / sqrt(128)) v_img, head dim 128, operands as launch_fa128's; l_img == 0:
+// the text term alone.  Nothing is read past key l_txt - 1 / l_img - 1.
+int launch_wan_dual_xattn(const void* q, int ldq, int64_t q_bs, const void* k_txt, const void* v_txt, int ldk_txt, int64_t kv_bs_txt, int l_txt,
+                          const void* k_img, const void* v_img, int ldk_img, int64_t kv_bs_img, int l_img, void* out, int ldo, int64_t o_bs, int B,
+                          int heads, int Lq, hipStream_t s);
+// launch_wan_patch_embed on the virtual [x (C) | mask (4: ones on frame 0) | ff (C)] input; w [D][2 C + 4][4]
+int launch_wan_i2v_patch_embed(const float* x, const float* ff, const float* w, const float* bias, void* out, int B, int C, int Fr, int H, int W, int D,
+                               hipStream_t s);
+// fp32 LayerNorm (affine) of rows [rows][n] (fp32, or bf16 when in_bf16) into bf16; exact (erf) GELU in place on n bf16 values
+int launch_wan_ln_rows(int in_bf16, const void* x, const float* w, const float* b, void* y, int rows, int n, float eps, hipStream_t s);
+int launch_wan_gelu_erf(void* x, int64_t n, hipStream_t s);

@@ -82,7 +82,8 @@ class FastGenModel:
                 t_list = torch.tensor(t_list, dtype=net.noise_scheduler.t_precision)
             assert t_list[-1].item() == 0, "t_list[-1] must be zero"
             fused = (getattr(net, "supports_fused_loop", lambda k: False)(cls._fused_loop) and data is None
-                     and not hasattr(net, "preserve_conditioning") and cls._student_sample_loop.__func__ in _FUSED_LOOPS)
+                     and (not hasattr(net, "preserve_conditioning") or getattr(net, "preserve_conditioning_is_identity", False))
+                     and cls._student_sample_loop.__func__ in _FUSED_LOOPS)
             if fused:
                 kw = dict(kwargs)
                 out = net.few_step_sample(noise, kw.pop("condition", None), t_list,

@@ -42,8 +42,9 @@ class WanEngineNetwork(FastGenNetwork):
                 raise NotImplementedError("encoder_depth is not implemented")
 
     def _build_engine(self, *, num_attention_heads, attention_head_dim, in_channels, out_channels, text_dim, freq_dim, ffn_dim, num_layers, eps,
-                      rope_max_seq_len, chunk_size, total_num_frames, compute_dtype, enable_logvar_linear, ext=None, init_value=None) -> None:
-        """The handle (`ext`: an `fg_wan_ext_config` for fg_wan_create_ex, None: fg_wan_create) and the parameters under their
+                      rope_max_seq_len, chunk_size, total_num_frames, compute_dtype, enable_logvar_linear, ext=None, init_value=None, i2v=None) -> None:
+        """The handle (`ext`: an `fg_wan_ext_config` for fg_wan_create_ex, None: fg_wan_create; `i2v`: an `fg_wan_i2v_config` for
+        fg_wan_create_i2v, with `ext` or without) and the parameters under their
         state-dict paths, initial values drawn in plan order from one seeded generator (`init_value(name, shape, g)`, default
         `_init_value`)."""
         self.compute_dtype = compute_dtype
@@ -55,12 +56,16 @@ class WanEngineNetwork(FastGenNetwork):
         self._cfg, self.in_channels = cfg, in_channels
         self._eng = _engine.Handles("wan", cfg)  # one handle: the mode is fixed at construction
         create = None
-        if ext is not None:
+        if ext is not None or i2v is not None:
             def create(dt):
                 c = type(cfg).from_buffer_copy(cfg)
                 c.compute_dtype = dt
                 h = ctypes.c_void_p()
-                _lib.check(_lib.lib().fg_wan_create_ex(ctypes.byref(c), ctypes.byref(ext), ctypes.byref(h)))
+                e = ctypes.byref(ext) if ext is not None else None
+                if i2v is not None:
+                    _lib.check(_lib.lib().fg_wan_create_i2v(ctypes.byref(c), e, ctypes.byref(i2v), ctypes.byref(h)))
+                else:
+                    _lib.check(_lib.lib().fg_wan_create_ex(ctypes.byref(c), e, ctypes.byref(h)))
                 return h
         self._h = self._eng.get(cfg.compute_dtype, create)
         self._text_key = None
@@ -80,9 +85,9 @@ class WanEngineNetwork(FastGenNetwork):
         biases of norms 0; scale_shift_table randn / sqrt(dim))."""
         if name.endswith("scale_shift_table"):
             return torch.randn(shape, generator=g) / shape[-1] ** 0.5
-        if name.endswith(("norm_q.weight", "norm_k.weight", "norm2.weight")):
+        if name.endswith(("norm_q.weight", "norm_k.weight", "norm_added_k.weight", "norm1.weight", "norm2.weight")):
             return torch.ones(shape)
-        if name.endswith("norm2.bias"):
+        if name.endswith(("norm1.bias", "norm2.bias")):
             return torch.zeros(shape)
         fan_in = 1
         for s_ in (shape[1:] if len(shape) > 1 else shape):

@@ -11,7 +11,8 @@ their order behind `transformer.logvar_linear.*` are read from `init_embedder` (
 solver of `sample` restates diffusers' UniPC (Wan/solvers.py).
 
 Raises (never falls back): autograd, feature taps, logvar, `norm_temb`, `encoder_depth`, per-token timesteps (Wan2.2 TI2V), image
-conditioning, skip-layer guidance inside `sample()` (`forward(skip_layers=...)` serves it), any device but a HIP GPU.
+conditioning (a condition dict: that is `fastgen_amd.networks.WanI2V.network.WanI2V`), skip-layer guidance inside `sample()`
+(`forward(skip_layers=...)` serves it), any device but a HIP GPU.
 `compute_dtype`: as on `CausalWan` (None / "bf16" / "fp8")."""
 from __future__ import annotations
 

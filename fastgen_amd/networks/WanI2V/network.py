@@ -1,0 +1,157 @@
+"""`WanI2V` drop-in for the reference's `fastgen.networks.WanI2V.network.WanI2V` in the Wan2.1-I2V convention (`concat_mask=True`,
+`use_image_encoder=True`): the bidirectional video DiT (`fastgen_amd.networks.Wan.network.Wan`) on the 36-channel input
+[x_t | 4 mask channels | first_frame_cond] with the CLIP image tokens' embedder and a second, separately normalised cross-attention
+softmax over the image keys in every block - backed by `fg_wan_create_i2v`, `fg_wan_set_i2v_cond` and `Wan`'s entry points on that
+handle.  The network of configs/experiments/WanI2V/config_dmd2_14b.py / config_sft_14b.py and the teacher of the I2V students.
+
+The condition is a dict: `text_embeds` [B, L, text_dim], `first_frame_cond` [B, 16, F, H, W] and, optionally,
+`encoder_hidden_states_image` [B, 257, image_dim] (absent, or `image_dim=0`: no image context - the blocks run the text attention alone).
+It is handed to the engine once per (tensor objects, versions, shapes), like the text.
+
+PARITY UNPINNED like `Wan`; in addition the thirteen image keys (`transformer.condition_embedder.image_embedder.*`, per block
+`attn2.add_k_proj.*`, `attn2.add_v_proj.*`, `attn2.norm_added_k.weight`) and their order are read from the reference's key map
+(Wan/network.py:1029-1049) and diffusers' module order, not recorded from a run.
+
+Raises (never falls back): everything `Wan` raises, the Wan2.2-TI2V convention (`concat_mask=False`, `expand_timesteps=True`), the image
+embedder's `pos_embed` (FLF2V)."""
+from __future__ import annotations
+
+import weakref
+from typing import Any, Dict, List, Optional
+
+import torch
+
+from fastgen_amd import _lib
+from fastgen_amd.networks import _engine
+from fastgen_amd.networks._engine import ptr
+from fastgen_amd.networks.Wan.network import Wan
+
+_MASK_CHANNELS = 4  # scale_factor_temporal of the Wan VAE (WanI2V/network.py:312)
+
+
+class WanI2V(Wan):
+    is_i2v = True
+    # the reference's hook returns x unchanged under concat_mask (the first frame is part of the network's input, not of the latents):
+    # FastGenModel.generator_fn may keep the fused loop
+    preserve_conditioning_is_identity = True
+
+    def __init__(self, num_attention_heads: int = 40, attention_head_dim: int = 128, in_channels: int = 36, out_channels: int = 16,
+                 text_dim: int = 4096, freq_dim: int = 256, ffn_dim: int = 13824, num_layers: int = 40, image_dim: Optional[int] = 1280,
+                 concat_mask: bool = True, use_image_encoder: bool = True, expand_timesteps: bool = False, pos_embed_seq_len: Optional[int] = None,
+                 **kwargs):
+        if not concat_mask or expand_timesteps:
+            raise NotImplementedError("the Wan2.2 TI2V convention (concat_mask=False, expand_timesteps=True: first-frame replacement and "
+                                      "per-token timesteps) is not implemented; WanI2V serves Wan2.1 I2V (concat_mask=True)")
+        if pos_embed_seq_len is not None:
+            raise NotImplementedError("pos_embed of the image embedder (pos_embed_seq_len, FLF2V) is not implemented")
+        i2v = _lib.fg_wan_i2v_config()
+        i2v.latent_channels, i2v.mask_channels, i2v.image_dim = out_channels, _MASK_CHANNELS, int(image_dim or 0)
+        self._i2v_cfg, self._i2v_key = i2v, None
+        self.concat_mask, self.use_image_encoder, self.image_dim = True, bool(use_image_encoder), int(image_dim or 0)
+        self.latent_channels = out_channels
+        super().__init__(num_attention_heads=num_attention_heads, attention_head_dim=attention_head_dim, in_channels=in_channels,
+                         out_channels=out_channels, text_dim=text_dim, freq_dim=freq_dim, ffn_dim=ffn_dim, num_layers=num_layers, **kwargs)
+
+    def _build_engine(self, **kw) -> None:
+        super()._build_engine(i2v=self._i2v_cfg, **kw)
+
+    # ---- the reference's surface -------------------------------------------------------------------------------------------
+    def preserve_conditioning(self, x: torch.Tensor, condition: Any) -> torch.Tensor:
+        """`WanI2V.preserve_conditioning` under concat_mask: the latents carry no conditioning frame, x is returned as it is."""
+        return x
+
+    # ---- the condition -----------------------------------------------------------------------------------------------------
+    def _check_video(self, x: torch.Tensor, what: str):
+        if x.ndim != 5 or x.shape[1] != self.latent_channels:
+            raise ValueError(f"{what} must be [B, {self.latent_channels}, F, H, W], got {tuple(x.shape)}")
+        return x.shape[0], x.shape[2], x.shape[3], x.shape[4]
+
+    @staticmethod
+    def _unpack(condition: Any, what: str = "condition"):
+        assert isinstance(condition, dict), f"{what} must be a dict"
+        assert "text_embeds" in condition, f"{what} must contain 'text_embeds'"
+        assert "first_frame_cond" in condition, f"{what} must contain 'first_frame_cond'"
+        text = condition["text_embeds"]
+        text = torch.stack(text, dim=0) if isinstance(text, list) else text
+        return text, condition["first_frame_cond"], condition.get("encoder_hidden_states_image")
+
+    def _forget_text(self) -> None:
+        super()._forget_text()
+        self._i2v_key = None  # packing invalidates the image-to-video condition together with the text
+
+    def _set_i2v(self, ff: torch.Tensor, image: Optional[torch.Tensor], B: int, F: int, H: int, W: int, dev) -> None:
+        """First-frame latents and image tokens into the handle, once per (tensor objects, versions, shapes) as `_set_text`."""
+        if self.image_dim == 0 or not self.use_image_encoder:
+            image = None
+        if tuple(ff.shape) != (B, self.latent_channels, F, H, W):
+            raise ValueError(f"first_frame_cond must be {(B, self.latent_channels, F, H, W)} (zero-padded to the video's frames), got {tuple(ff.shape)}")
+        if image is not None and (image.ndim != 3 or image.shape[0] != B or image.shape[2] != self.image_dim or not 1 <= image.shape[1] <= 1024):
+            raise ValueError(f"encoder_hidden_states_image must be [{B}, 1 .. 1024, {self.image_dim}], got {tuple(image.shape)}")
+
+        def ident(t):
+            return None if t is None else (weakref.ref(t), 0 if t.is_inference() else t._version, tuple(t.shape))
+
+        def same(a, b):
+            return (a is None and b is None) or (a is not None and b is not None and a[0]() is b[0]() and a[1:] == b[1:])
+
+        key = (ident(ff), ident(image))
+        if self._i2v_key is not None and same(self._i2v_key[0], key[0]) and same(self._i2v_key[1], key[1]):
+            return
+        ff32 = ff.detach().to(device=dev, dtype=torch.float32).contiguous()
+        im32 = None if image is None else image.detach().to(device=dev, dtype=torch.float32).contiguous()
+        L = _lib.lib()
+        Li = 0 if im32 is None else im32.shape[1]
+        ws = None
+        if Li:
+            ws = self._eng.workspace(("i2v", self._cfg.compute_dtype), L.fg_wan_i2v_cond_workspace_bytes(self._h, B, Li), dev)
+        _lib.check(L.fg_wan_set_i2v_cond(self._h, ptr(ff32), ptr(im32), B, F, H, W, Li, ptr(ws), ws.numel() if ws is not None else 0,
+                                         self._stream(dev)))
+        self._i2v_key = key
+
+    def _prepare(self, x: torch.Tensor, what: str, ff: torch.Tensor, image: Optional[torch.Tensor], stack: int = 1) -> None:
+        _engine.require_gpu(x)
+        B, F, H, W = self._check_video(x, what)
+        self._bind(x.device)  # (first: packing would invalidate what is set below)
+        self._set_i2v(ff, image, B * stack, F, H, W, x.device)
+
+    # ---- calls -------------------------------------------------------------------------------------------------------------
+    def forward(self, x_t: torch.Tensor, t: torch.Tensor, condition: Optional[Dict[str, torch.Tensor]] = None, r: Optional[torch.Tensor] = None,
+                **kwargs):
+        text, ff, image = self._unpack(condition)  # (the reference's asserts, WanI2V/network.py:457-459)
+        if kwargs.get("feature_indices") or kwargs.get("return_features_early") or kwargs.get("return_logvar"):
+            raise NotImplementedError("feature taps / logvar are not implemented for the bidirectional video DiT path")
+        self._no_autograd(x_t)
+        self._prepare(x_t, "x_t", ff, image)
+        return super().forward(x_t, t, condition=text, r=r, **kwargs)
+
+    def few_step_sample(self, noise: torch.Tensor, condition: Any, t_list, **kwargs) -> torch.Tensor:
+        """`Wan.few_step_sample` under the image-to-video condition: one `fg_wan_full_sampler_run` / one hipGraph replay.  New
+        first-frame contents or image tokens at the same shapes replay the same graph (the handle's buffers are rewritten in place)."""
+        text, ff, image = self._unpack(condition)
+        self._no_autograd()
+        self._prepare(noise, "noise", ff, image)
+        return super().few_step_sample(noise, text, t_list, **kwargs)
+
+    @torch.no_grad()
+    def sample(self, noise: torch.Tensor, condition: Optional[Dict[str, torch.Tensor]] = None,
+               neg_condition: Optional[Dict[str, torch.Tensor]] = None, guidance_scale: Optional[float] = 5.0, num_steps: int = 40,
+               shift: float = 3.0, skip_layers: Optional[List[int]] = None, skip_layers_start_percent: float = 0.0, **kwargs) -> torch.Tensor:
+        """`WanI2V.sample` (WanI2V/network.py:344-419, concat_mask: no first-frame replacement) over `Wan.sample`'s one call: when
+        guided, the stacked batch [x; x] runs against the text, first frame and image tokens of [condition; neg_condition]."""
+        text, ff, image = self._unpack(condition)
+        guided = guidance_scale is not None and neg_condition is not None
+        neg_text = None
+        if guided:
+            neg_text, nff, nimage = self._unpack(neg_condition, "neg_condition")
+            if (image is None) != (nimage is None):
+                raise ValueError("condition and neg_condition must both carry encoder_hidden_states_image, or neither")
+            dev = noise.device
+            ff = torch.cat([ff.to(dev), nff.to(dev)], dim=0)
+            image = None if image is None else torch.cat([image.to(dev), nimage.to(dev)], dim=0)
+        self._prepare(noise, "noise", ff, image, stack=2 if guided else 1)
+        try:
+            return super().sample(noise, condition=text, neg_condition=neg_text, guidance_scale=guidance_scale, num_steps=num_steps, shift=shift,
+                                  skip_layers=skip_layers, skip_layers_start_percent=skip_layers_start_percent, **kwargs)
+        finally:
+            if guided:
+                self._i2v_key = None  # the handle holds the stacked condition: the next call sets its own

@@ -701,6 +701,44 @@ FG_API size_t fg_wan_full_guided_sampler_workspace_bytes(const fg_wan* h, int ba
 FG_API int fg_wan_full_guided_sampler_run(fg_wan* h, const fg_wan_guided_sampler_config* cfg, float* x, const double* t_list,
                                           const double* table, int steps, int batch, int frames, int height, int width, void* workspace,
                                           size_t workspace_bytes, int use_graph, void* stream);
+/* Image-to-video on the bidirectional network (reference fastgen/networks/WanI2V/network.py `WanI2V`, the Wan2.1-I2V convention:
+ * concat_mask = True, use_image_encoder = True).  PARITY UNPINNED like the rest of fg_wan_*.  The patch embedding reads the virtual
+ * cfg->in_channels = 2 latent_channels + 4 channel tensor [x_t | mask | first_frame_cond] (mask: ones on latent frame 0, on all four
+ * channels), cfg->out_channels == latent_channels, and every cross-attention adds a second, separately normalised softmax over the
+ * embedded CLIP image tokens.  Parameter table: fg_wan_create_ex's with, when image_dim > 0, the eight
+ * `condition_embedder.image_embedder.{norm1.weight, norm1.bias, ff.net.0.proj.weight, ff.net.0.proj.bias, ff.net.2.weight,
+ * ff.net.2.bias, norm2.weight, norm2.bias}` behind `condition_embedder.text_embedder.linear_2.bias` and, in every block, the five
+ * `attn2.{add_k_proj.weight, add_k_proj.bias, add_v_proj.weight, add_v_proj.bias, norm_added_k.weight}` behind `attn2.norm_k.weight`
+ * (unpinned: read from the key map at Wan/network.py:1029-1049 and diffusers' module order, not recorded from a run); image_dim == 0:
+ * exactly fg_wan_create_ex's table.  FG_EINVAL (the message names the field): mask_channels != 4, in_channels != 2 latent_channels +
+ * mask_channels, out_channels != latent_channels, image_dim < 0 or not a multiple of 64.
+ * On such a handle fg_wan_forward_full, fg_wan_forward_full_features, fg_wan_full_sampler_run and fg_wan_full_guided_sampler_run
+ * take x_t / noise / x with latent_channels channels and need the condition set for the batch and (frames, height, width) of the
+ * call (FG_ENOTREADY otherwise; the guided loop runs at 2 B: set text and condition for [cond; neg_cond]); the chunked and causal
+ * entry points (fg_wan_forward, fg_wan_forward_block_causal, fg_wan_forward_features in those modes, fg_wan_sampler_run,
+ * fg_wan_guided_sampler_run) return FG_EINVAL "not implemented for an image-to-video handle".  Not implemented: the Wan2.2-TI2V
+ * convention (concat_mask = False, expanded timesteps), the image embedder's pos_embed (FLF2V). */
+typedef struct fg_wan_i2v_config {
+    int latent_channels;   /* 16: channels of x_t and of first_frame_cond */
+    int mask_channels;     /* 4 (scale_factor_temporal): anything else FG_EINVAL */
+    int image_dim;         /* 1280 (CLIP); 0: no image branch, no image parameters; else % 64 == 0 */
+} fg_wan_i2v_config;
+FG_API int fg_wan_create_i2v(const fg_wan_config* cfg, const fg_wan_ext_config* ext /* nullable */, const fg_wan_i2v_config* i2v, fg_wan** out);
+/* The image-to-video condition, the counterpart of fg_wan_set_text: first_frame_cond [B, latent_channels, F, H, W] is copied into a
+ * buffer of the handle; image [B, image_len, image_dim] (nullable; image_len 1 .. 1024, 257 for CLIP ViT-H) goes through the image
+ * embedder (fp32 LayerNorm eps 1e-5 - Linear - erf GELU - Linear - fp32 LayerNorm eps 1e-5) and, per block, k_img =
+ * norm_added_k(add_k_proj(tokens)) (RMSNorm over the inner dimension, like norm_k) and v_img = add_v_proj(tokens) into a bf16 cache
+ * of whole 32-key tiles per sample, zero-filled.  bf16 operands in every compute mode.  image == NULL, image_len == 0 or a handle
+ * with image_dim == 0: no image context (the reference's empty image context, network_causal.py:297-302) - the blocks then run the
+ * text attention alone.  The buffers are rewritten in place while the shapes stay (a captured loop stays valid across new contents)
+ * and reallocated otherwise.  Packing weights invalidates the condition; FG_ENOTREADY before packing.  The workspace (256-byte
+ * aligned, fg_wan_i2v_cond_workspace_bytes; 0 bytes and NULL without image tokens) is scratch of this call only. */
+FG_API size_t fg_wan_i2v_cond_workspace_bytes(const fg_wan* h, int batch, int image_len);
+FG_API int fg_wan_set_i2v_cond(fg_wan* h, const float* first_frame_cond, const float* image, int batch, int frames, int height, int width,
+                               int image_len, void* workspace, size_t workspace_bytes, void* stream);
+/* Exposed for the parity tests: fp32 copies of the condition's embedded image tokens [B, image_len, D] and of block `block`'s k_img /
+ * v_img [B, image_len, D] each (all nullable).  FG_ENOTREADY without an image context.  Synchronises the stream. */
+FG_API int fg_wan_i2v_cond_read(fg_wan* h, int block, float* img_tokens, float* k_img, float* v_img, void* stream);
 /* One step of that solver, in place (misc.hip guided_multistep_kernel): with the eight DEVICE doubles tab = {s, g, c0, c1, c2, p0, p1, p2}
  * each rounded once to fp32, v = guided ? v[total + i] + g (v[i] - v[total + i]) : v[i]; m = x - s v; x_corr = c0 x_last + c1 m_prev +
  * c2 m (first != 0: x_last := x, m_prev := m, neither buffer is read); x_next = p0 x_corr + p1 m_prev + p2 m; then x <- x_next (and
@@ -771,6 +809,14 @@ FG_API int fg_op_dit_attention(int mode, const void* q, const void* k, const voi
 FG_API int fg_op_attention_ex(const void* q, int ldq, int64_t q_bs, const void* k, const void* v, int ldk, int64_t kv_bs, void* out, int ldo,
                               int64_t o_bs, int batch, int heads, int head_dim, int lq, int lkv, int use_scratch, int force_split, int path,
                               void* stream);
+/* The cross-attention of an image-to-video block (wan_i2v.hip wan_dual_xattn_kernel), head dim 128, on the layouts of
+ * fg_op_attention_ex: out = softmax(q k_txt^T / sqrt(128)) v_txt + softmax(q k_img^T / sqrt(128)) v_img - two independent softmaxes,
+ * each output rounded to bf16, their fp32 sum rounded to bf16.  Either key count may be ragged; nothing is read past key l_txt - 1 /
+ * l_img - 1.  l_img == 0 (k_img / v_img then unread): the text attention alone, bit-identical to fg_op_attention_ex without scratch.
+ * For the per-element parity test and scripts/attn_bench.py. */
+FG_API int fg_op_wan_dual_cross_attention(const void* q, int ldq, int64_t q_bs, const void* k_txt, const void* v_txt, int ldk_txt,
+                                          int64_t kv_bs_txt, int l_txt, const void* k_img, const void* v_img, int ldk_img, int64_t kv_bs_img,
+                                          int l_img, void* out, int ldo, int64_t o_bs, int batch, int heads, int lq, void* stream);
 /* The transformer blocks' token GEMM in the bf16 compute mode (gemm.hip; reference: the nn.Linear calls of DiTBlock,
  * fastgen/networks/DiT/network.py:168-198, under bf16 autocast): out[m][n] = resid[m][n] + gate[(m / gate_rows) * gate_stride + n] *
  * act(sum_k a[m][k] w[n][k] + bias[n]) with a [m][k], w [n][k], resid / out [m][n] in bf16, fp32 accumulation, bias / gate fp32;

@@ -3,7 +3,11 @@ Wan2.1-T2V-1.3B, latents [16, 21, 60, 104] = 480p, chunk of 3 frames, t_list of 
 chunk k (4680 query tokens over (3 k + 3) * 1560 cached + own keys), and the whole 21-frame 4-step loop (7 chunks x (4 + 1) calls).
 Random-init weights of the 1.3B architecture, synthetic latents and text embeddings.
     python scripts/wan_bench.py [--layers=30] [--loop] [--compute-dtype=bf16[,fp8]] [--case=chunks|bc|guided] [--chunks=0,6]
-                                [--widths=1.3b|14b] [--trace=CALLS] [--bidirectional]
+                                [--widths=1.3b|14b] [--trace=CALLS] [--bidirectional] [--i2v]
+--i2v (with --bidirectional): the image-to-video network `WanI2V` (fastgen_amd/networks/WanI2V/network.py: 36 input channels, 257 CLIP
+  image tokens of width 1280) next to `Wan` of the same widths and depth in the same run, one call at [1,16,21,60,104] each: the cost of
+  the image branch (the dual cross-attention, the two-source patch embedding) is the difference of the two numbers.  Also the call
+  without image tokens, and the condition's own cost (fg_wan_set_i2v_cond, once per condition).
 --bidirectional: the bidirectional network `Wan` (fastgen_amd/networks/Wan/network.py) instead, per arm next to the block-causal call of
   a `CausalWan` of the same weights in the same run: one call at [1,16,21,60,104] (full attention: 7 / 4 of the block mask's key
   pairs), the 4-step x0 student loop (FastGenModel.generator_fn, one hipGraph) and one guided step (the call at the stacked batch 2).
@@ -40,7 +44,7 @@ D, fs, Lt = H * 128, 1560, 512
 B = 2 if CASE == "guided" else 1
 
 nets = {}
-for arm in ARMS:
+for arm in ([] if "--i2v" in sys.argv else ARMS):
     torch.manual_seed(0)  # the same weights in every arm
     nets[arm] = CausalWan(num_attention_heads=H, ffn_dim=Fd, num_layers=LAYERS, compute_dtype=arm).cuda().eval()
 x = torch.randn(B, 16, 21, 60, 104, device="cuda")
@@ -76,6 +80,34 @@ def side_by_side(label, fns, n, gf=None, rounds=3):
     print(f"{label}: " + "   ".join(parts) + ratio, flush=True)
     return med
 
+
+if "--bidirectional" in sys.argv and "--i2v" in sys.argv:
+    from fastgen_amd.networks.Wan.network import Wan
+    from fastgen_amd.networks.WanI2V.network import WanI2V
+
+    x1, text1, t1, L = x[:1], text[:1], t[:1], 21 * fs
+    ff = torch.randn(1, 16, 21, 60, 104, device="cuda")
+    img = torch.randn(1, 257, 1280, device="cuda")
+    cond, cond_noimg = ({"text_embeds": text1, "first_frame_cond": ff, "encoder_hidden_states_image": img},
+                        {"text_embeds": text1, "first_frame_cond": ff})
+    for arm in ARMS:
+        torch.manual_seed(0)
+        plain = Wan(num_attention_heads=H, ffn_dim=Fd, num_layers=LAYERS, compute_dtype=arm).cuda().eval()
+        i2v = WanI2V(num_attention_heads=H, ffn_dim=Fd, num_layers=LAYERS, image_dim=1280, compute_dtype=arm).cuda().eval()
+        with torch.inference_mode():
+            med = side_by_side(f"{arm}: one call, {L} tokens, {LAYERS} layers, {WIDTHS}",
+                               {"Wan": lambda: plain(x1, t1, condition=text1, fwd_pred_type="flow"),
+                                "WanI2V": lambda: i2v(x1, t1, condition=cond, fwd_pred_type="flow"),
+                                "WanI2V, no image tokens": lambda: i2v(x1, t1, condition=cond_noimg, fwd_pred_type="flow")}, 2)
+            print(f"   image branch: {(med['WanI2V'] - med['Wan']) * 1e3:.2f} ms per call = {(med['WanI2V'] - med['Wan']) / LAYERS * 1e6:.0f} us per "
+                  f"layer ({(med['WanI2V'] / med['Wan'] - 1) * 100:.1f} %); without image tokens {(med['WanI2V, no image tokens'] - med['Wan']) * 1e3:+.2f} ms")
+
+            def set_cond():  # a fresh condition every time: embed the image, project it per block
+                i2v._i2v_key = None
+                i2v._prepare(x1, "x_t", ff, img)
+            side_by_side(f"{arm}: fg_wan_set_i2v_cond (257 image tokens, {LAYERS} layers)", {"set": set_cond}, 3)
+            del plain, i2v
+    sys.exit(0)
 
 if "--bidirectional" in sys.argv:
     from fastgen_amd.methods.model import FastGenModel
