@@ -132,10 +132,16 @@ SIGNATURES = {
     "fg_op_adm_conv_pack": (c_int, [c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
     "fg_op_adm_conv": (c_int, [c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p,
                                c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p]),
+    "fg_op_adm_conv_ex": (c_int, [c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int, c_int, c_void_p,
+                                  c_void_p, c_void_p, c_int, c_float, c_float, c_void_p, c_int, c_void_p]),
     "fg_op_adm_gn_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
     "fg_op_adm_gn_coeffs": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_float, c_void_p, c_int, c_void_p, c_int,
                                     c_int, c_void_p, c_size_t, c_void_p]),
     "fg_op_adm_attention": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
+    "fg_op_edm2_attention": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
+    "fg_op_edm2_prep_weight": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_float, c_float, c_int, c_void_p]),
+    "fg_op_edm2_pixel_norm": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
+    "fg_op_linear": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
     "fg_op_adm_map_in": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p]),
     "fg_op_latents": (c_int, [c_void_p, c_double, c_void_p, c_int64, c_void_p]),
     "fg_op_forward_process": (c_int, [c_void_p, c_void_p, c_double, c_int, c_void_p, c_int64, c_void_p]),
@@ -164,6 +170,9 @@ SIGNATURES = {
     "fg_edm2_pack_weights": (c_int, [c_void_p, c_void_p]),
     "fg_edm2_workspace_bytes": (c_size_t, [c_void_p, c_int]),
     "fg_edm2_forward": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_size_t, c_void_p]),
+    "fg_edm2_num_taps": (c_int, [c_void_p]),
+    "fg_edm2_forward_taps": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, POINTER(c_void_p), c_int, c_int, c_void_p,
+                                     c_size_t, c_void_p]),
     "fg_edm2_set_training": (c_int, [c_void_p, c_int]),
     "fg_edm2_sampler_run": (c_int, [c_void_p, c_void_p, c_void_p, POINTER(c_double), c_int, c_int, c_int, c_void_p, c_uint64,
                                     c_void_p, c_int, c_void_p, c_size_t, c_int, c_void_p]),

@@ -1459,9 +1459,9 @@ int fg_op_adm_conv_pack(int mode, const float* w_oihw, void* packed, int cout, i
     HIP_TRY(adm_pack_conv_weights(mode, w_oihw, packed, cout, cin, ks, (hipStream_t)stream));
     return FG_OK;
 }
-int fg_op_adm_conv(int mode, int ks, const float* src1, int c1, const float* src2, int c2, int batch, int hs, int h, int res_mode,
-                   const float* ab, int silu, const void* packed, const float* bias, const float* resid, int resid_mode, float* out,
-                   int cout, void* stream) {
+int fg_op_adm_conv_ex(int mode, int ks, const float* src1, int c1, const float* src2, int c2, int batch, int hs, int h, int res_mode,
+                      const float* ab, int ab_stride, int silu, const void* packed, const float* bias, const float* resid, int resid_mode,
+                      float resid_scale, float clip, float* out, int cout, void* stream) {
     if ((mode != FG_DTYPE_BF16 && mode != FG_DTYPE_BF16X3) || (ks != 1 && ks != 3))
         return fail(FG_EINVAL, "fg_op_adm_conv: mode %d (1 bf16, 2 bf16x3), ks %d (1, 3)", mode, ks);
     if (c1 <= 0 || c1 % 32 || c2 < 0 || c2 % 32 || cout <= 0 || batch <= 0 || batch > 65535)
@@ -1471,6 +1471,11 @@ int fg_op_adm_conv(int mode, int ks, const float* src1, int c1, const float* src
     if (h <= 0 || h > 4096 || !res_ok) return fail(FG_EINVAL, "fg_op_adm_conv: res_mode %d with hs %d, h %d", res_mode, hs, h);
     if (resid && (resid_mode < 0 || resid_mode > 2 || (resid_mode == 2 && h % 2)))
         return fail(FG_EINVAL, "fg_op_adm_conv: resid_mode %d (0, 1, 2 with h even) at h %d", resid_mode, h);
+    if (ab_stride != -1 && ab_stride != 0 && ab_stride < c1 + c2)
+        return fail(FG_EINVAL, "fg_op_adm_conv_ex: ab_stride %d (-1, 0 or >= c1 + c2 = %d)", ab_stride, c1 + c2);
+    if (!std::isfinite(resid_scale) || !(clip >= 0.0f) || !std::isfinite(clip))
+        return fail(FG_EINVAL, "fg_op_adm_conv_ex: resid_scale %g must be finite, clip %g finite and >= 0 (0: no clamp)", (double)resid_scale,
+                    (double)clip);
     if (!src1 || (c2 && !src2) || !packed || !out) return fail(FG_EINVAL, "fg_op_adm_conv: null pointer");
     if (((uintptr_t)src1 | (uintptr_t)(c2 ? src2 : nullptr) | (uintptr_t)packed) & 15 || (uintptr_t)ab & 7)
         return fail(FG_EINVAL, "fg_op_adm_conv: src1 / src2 / packed must be 16-byte aligned, ab 8-byte aligned");
@@ -1478,8 +1483,15 @@ int fg_op_adm_conv(int mode, int ks, const float* src1, int c1, const float* src
     a.src1 = src1, a.src2 = c2 ? src2 : nullptr, a.C1 = c1, a.C2 = c2, a.Hs = hs, a.H = h, a.B = batch, a.res_mode = res_mode;
     a.ab = (const float2*)ab, a.silu = silu ? 1 : 0, a.w = packed, a.bias = bias, a.resid = resid, a.resid_mode = resid ? resid_mode : 0;
     a.out = out, a.Cout = cout;
+    a.ab_stride = ab_stride, a.resid_scale = resid_scale, a.clip = clip;
     HIP_TRY(adm_launch_conv(mode, ks, a, (hipStream_t)stream));
     return FG_OK;
+}
+int fg_op_adm_conv(int mode, int ks, const float* src1, int c1, const float* src2, int c2, int batch, int hs, int h, int res_mode,
+                   const float* ab, int silu, const void* packed, const float* bias, const float* resid, int resid_mode, float* out,
+                   int cout, void* stream) {
+    return fg_op_adm_conv_ex(mode, ks, src1, c1, src2, c2, batch, hs, h, res_mode, ab, -1, silu, packed, bias, resid, resid_mode, 1.0f, 0.0f,
+                             out, cout, stream);
 }
 size_t fg_op_adm_gn_workspace_bytes(int batch, int hw, int c) {
     if (batch <= 0 || hw <= 0 || c <= 0) return 0;
@@ -1512,6 +1524,43 @@ int fg_op_adm_attention(const float* qkv, float* out, int batch, int t, int head
         return fail(FG_EINVAL, "fg_op_adm_attention: t %d (a positive multiple of 64), heads %d, batch %d (1 .. 65535)", t, heads, batch);
     if (!qkv || !out) return fail(FG_EINVAL, "fg_op_adm_attention: null pointer");
     HIP_TRY(adm_launch_attention(qkv, out, batch, t, heads, (hipStream_t)stream));
+    return FG_OK;
+}
+int fg_op_edm2_attention(const float* qkv, float* out, int batch, int t, int heads, void* stream) {
+    if (t <= 0 || t % 64 || heads <= 0 || heads > 65535 || batch <= 0 || batch > 65535)
+        return fail(FG_EINVAL, "fg_op_edm2_attention: t %d (a positive multiple of 64), heads %d, batch %d (1 .. 65535)", t, heads, batch);
+    if (!qkv || !out) return fail(FG_EINVAL, "fg_op_edm2_attention: null pointer");
+    HIP_TRY(adm_launch_attention_mp(qkv, out, batch, t, heads, (hipStream_t)stream));
+    return FG_OK;
+}
+int fg_op_edm2_prep_weight(const float* w, float* out, int cout, int cin, int cin_pad, int taps, const float* gain, float extra0, float extra1,
+                           int c_split, void* stream) {
+    if (cout <= 0 || cin <= 0 || cin_pad < cin || taps <= 0 || c_split < 0 || (int64_t)cin_pad * taps > (1 << 24))
+        return fail(FG_EINVAL, "fg_op_edm2_prep_weight: cout %d > 0, cin %d > 0, cin_pad %d >= cin, taps %d > 0, c_split %d >= 0, cin_pad * taps <= 2^24",
+                    cout, cin, cin_pad, taps, c_split);
+    if (!std::isfinite(extra0) || !std::isfinite(extra1)) return fail(FG_EINVAL, "fg_op_edm2_prep_weight: extra0 / extra1 must be finite");
+    if (!w || !out || w == out) return fail(FG_EINVAL, "fg_op_edm2_prep_weight: null pointer, or out aliases w");
+    HIP_TRY(edm2_launch_prep_weight(w, out, cout, cin, cin_pad, taps, gain, extra0, extra1, c_split, (hipStream_t)stream));
+    return FG_OK;
+}
+int fg_op_edm2_pixel_norm(const float* x, float* out, int batch, int h, int c, int down, void* stream) {
+    if (batch <= 0 || batch > 65535 || h <= 0 || h > 4096 || c <= 0 || c > (1 << 16) || (down != 0 && down != 1))
+        return fail(FG_EINVAL, "fg_op_edm2_pixel_norm: batch %d (1 .. 65535), h %d (1 .. 4096), c %d (1 .. 65536), down %d (0, 1)", batch, h, c,
+                    down);
+    if ((int64_t)batch * h * h > ((int64_t)1 << 31)) return fail(FG_EINVAL, "fg_op_edm2_pixel_norm: more than 2^31 pixels");
+    if (!x || !out) return fail(FG_EINVAL, "fg_op_edm2_pixel_norm: null pointer");
+    if (down && out == x) return fail(FG_EINVAL, "fg_op_edm2_pixel_norm: in place only with down == 0");
+    HIP_TRY(edm2_launch_pixel_norm(x, out, batch, h, c, down, (hipStream_t)stream));
+    return FG_OK;
+}
+int fg_op_linear(const float* x, const float* w, const float* bias, float* y, int batch, int in, int out, int act_silu, void* stream) {
+    if (batch <= 0 || batch > (1 << 20) || in <= 0 || out <= 0 || (int64_t)out * in > ((int64_t)1 << 31))
+        return fail(FG_EINVAL, "fg_op_linear: batch %d (1 .. 2^20), in %d > 0, out %d > 0, in * out <= 2^31", batch, in, out);
+    if (!x || !w || !y || y == x) return fail(FG_EINVAL, "fg_op_linear: null pointer, or y aliases x");
+    if (linear_on_matrix_pipe(in, out) && (((uintptr_t)x | (uintptr_t)w) & 15))
+        return fail(FG_EINVAL, "fg_op_linear: in %d (a multiple of 16) and out %d (a multiple of 32) run on the matrix pipe, whose 16-byte "
+                    "loads need x and w 16-byte aligned", in, out);
+    HIP_TRY(launch_linear(x, w, bias, y, batch, in, out, act_silu ? 1 : 0, (hipStream_t)stream));
     return FG_OK;
 }
 int fg_op_adm_map_in(const float* c_noise, const float* freqs, const float* aug, const float* wa, int aug_dim, float* out, int batch,

@@ -330,8 +330,18 @@ int e2_modulation(fg_edm2* h, const float* emb, int B, E2Ws& w, hipStream_t s) {
 }
 
 // EDM2Precond.forward (eval, x0) around EMD2UNet.forward
-int e2_forward(fg_edm2* h, const float* x_t, const double* t, int t_stride, const float* labels, float* out, int B, E2Ws& w, hipStream_t s) {
+// taps (nullable): 2 + num_blocks nullable fp32 NHWC device buffers - the stem output, every block output in fg_edm2_block_info order,
+// the raw U-Net output F - each copied on s behind the kernel that wrote it (fg_edm2_forward_taps).
+int e2_forward(fg_edm2* h, const float* x_t, const double* t, int t_stride, const float* labels, float* out, int B, E2Ws& w, hipStream_t s,
+               float* const* taps = nullptr) {
     const fg_edm2_config& c = h->cfg;
+    int tap_i = 0;
+    auto tap = [&](const float* src, int res, int ch) -> int {
+        float* dst = taps ? taps[tap_i] : nullptr;
+        ++tap_i;
+        if (dst) HIP_TRY(hipMemcpyAsync(dst, src, sizeof(float) * (size_t)B * res * res * ch, hipMemcpyDeviceToDevice, s));
+        return FG_OK;
+    };
     HIP_TRY(launch_precond_coef(t, t_stride, nullptr, 0, c.sigma_data, h->shift(), 1e-6, c.drop_precond, w.coef, B, s));
     // embedding: mp_silu(mp_sum(emb_noise(fourier(c_noise)), emb_label(labels sqrt(L)), label_balance)), the balance folded in
     HIP_TRY(edm2_launch_fourier(w.coef + B, h->P(h->freqs), h->P(h->phases), w.four, B, h->cnoise, s));
@@ -347,11 +357,13 @@ int e2_forward(fg_edm2* h, const float* x_t, const double* t, int t_stride, cons
     AdmConvArgs st;
     st.src1 = w.stem_in, st.C1 = kE2StemPad, st.Hs = st.H = R, st.B = B, st.w = h->p_stem, st.out = w.skip[0], st.Cout = h->stem_c;
     HIP_TRY(adm_launch_conv(h->cmode, 3, st, s));
+    if ((rc = tap(w.skip[0], R, h->stem_c))) return rc;
     const float* x = w.skip[0];
     int xc = h->stem_c;
     for (size_t i = 0; i < h->enc.size(); ++i) {
         const E2Block& b = h->enc[i];
         if ((rc = e2_block(h, b, x, xc, nullptr, 0, w.skip[i + 1], B, w, s))) return rc;
+        if ((rc = tap(w.skip[i + 1], b.res_out, b.cout))) return rc;
         x = w.skip[i + 1], xc = b.cout;
     }
     int sp = (int)w.skip.size();
@@ -360,12 +372,14 @@ int e2_forward(fg_edm2* h, const float* x_t, const double* t, int t_stride, cons
     for (const E2Block& b : h->dec) {
         const float* x2 = b.skip_c ? w.skip[--sp] : nullptr;
         if ((rc = e2_block(h, b, x, xc, x2, b.skip_c, pong[cur], B, w, s))) return rc;
+        if ((rc = tap(pong[cur], b.res_out, b.cout))) return rc;
         x = pong[cur], xc = b.cout;
         cur ^= 1;
     }
     AdmConvArgs o;
     o.src1 = x, o.C1 = h->out_cin, o.Hs = o.H = R, o.B = B, o.w = h->p_out, o.out = w.F, o.Cout = c.img_channels;
     HIP_TRY(adm_launch_conv(h->cmode, 3, o, s));
+    if ((rc = tap(w.F, R, c.img_channels))) return rc;
     HIP_TRY(edm2_launch_precond_out(w.F, x_t, w.coef + 2 * (size_t)B, w.coef + 3 * (size_t)B, out, B, c.img_channels, R, s));
     return FG_OK;
 }
@@ -444,18 +458,30 @@ int fg_edm2_set_training(fg_edm2* h, int training) {
     return FG_OK;
 }
 
-int fg_edm2_forward(fg_edm2* h, const float* x_t, const double* t, const float* class_labels, float* out, float* emb_out, int batch,
-                    void* workspace, size_t workspace_bytes, void* stream) {
+int fg_edm2_num_taps(const fg_edm2* h) { return h ? 2 + (int)(h->enc.size() + h->dec.size()) : 0; }
+
+int fg_edm2_forward_taps(fg_edm2* h, const float* x_t, const double* t, const float* class_labels, float* out, float* emb_out,
+                         float* const* taps, int num_taps, int batch, void* workspace, size_t workspace_bytes, void* stream) {
     if (!h || !x_t || !t || !out) return fail(FG_EINVAL, "null argument");
+    if (taps && num_taps != fg_edm2_num_taps(h))
+        return fail(FG_EINVAL, "fg_edm2_forward_taps: num_taps %d, the handle has %d (fg_edm2_num_taps)", num_taps, fg_edm2_num_taps(h));
     if (!h->packed) return fail(FG_ENOTREADY, "weights are not packed (call fg_edm2_pack_weights)");
     if (out == x_t) return fail(FG_EINVAL, "out must not alias x_t");
+    for (int i = 0; taps && i < num_taps; ++i)
+        if (taps[i] && (taps[i] == out || taps[i] == x_t || taps[i] == emb_out))
+            return fail(FG_EINVAL, "fg_edm2_forward_taps: tap %d aliases x_t, out or emb_out", i);
     E2Ws w;
     int rc = setup_ws(e2_plan, h, batch, workspace, workspace_bytes, w);
     if (rc) return rc;
     hipStream_t s = (hipStream_t)stream;
-    if ((rc = e2_forward(h, x_t, t, 1, class_labels, out, batch, w, s))) return rc;
+    if ((rc = e2_forward(h, x_t, t, 1, class_labels, out, batch, w, s, taps))) return rc;
     if (emb_out) HIP_TRY(hipMemcpyAsync(emb_out, w.emb, sizeof(float) * (size_t)batch * h->cemb, hipMemcpyDeviceToDevice, s));
     return FG_OK;
+}
+
+int fg_edm2_forward(fg_edm2* h, const float* x_t, const double* t, const float* class_labels, float* out, float* emb_out, int batch,
+                    void* workspace, size_t workspace_bytes, void* stream) {
+    return fg_edm2_forward_taps(h, x_t, t, class_labels, out, emb_out, nullptr, 0, batch, workspace, workspace_bytes, stream);
 }
 
 int fg_edm2_sampler_run(fg_edm2* h, const float* noise, const float* class_labels, const double* t_list, int steps, int sample_type,

@@ -12,6 +12,9 @@ int launch_precond_coef(const double* t, int t_stride, const double* r, int r_st
                         double sigma_shift, double clamp_min, int drop, float* coef, int B, hipStream_t s);
 int launch_mapping_in(const float* c_noise, const float* r_noise, const float* freqs, const float* labels, int label_dim,
                       const float* wl, const float* bl, float* out, int B, int N, int noise_ch, hipStream_t s, const float* aug = nullptr, const float* wa = nullptr, int aug_dim = 0);
+// y[B, O] = act(x[B, I] W[O, I]^T + bias).  Shapes with linear_on_matrix_pipe run the fp32 MFMA kernels, whose 16-byte loads need x and w
+// 16-byte aligned; every other shape runs the FMA kernel, which has no alignment requirement.
+inline bool linear_on_matrix_pipe(int I, int O) { return I % 16 == 0 && O % 32 == 0; }
 int launch_linear(const float* x, const float* w, const float* bias, float* y, int B, int I, int O, int act_silu,
                   hipStream_t s);
 int launch_conv_in(int dtype, const float* x, const float* c_in, const float* w, const float* bias, void* out, int B,

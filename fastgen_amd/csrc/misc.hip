@@ -713,7 +713,7 @@ int launch_mapping_in(const float* c_noise, const float* r_noise, const float* f
 
 int launch_linear(const float* x, const float* w, const float* bias, float* y, int B, int I, int O, int act_silu,
                   hipStream_t s) {
-    if (I % 16 == 0 && O % 32 == 0) {
+    if (linear_on_matrix_pipe(I, O)) {
         // wide outputs (the stacked affines): two row tiles per wave halve the weight traffic; otherwise keep the wave count up
         const bool pair = I % 64 == 0 && B > 32 && O >= 2048;
         dim3 g(O / 32, pair ? (B + 63) / 64 : (B + 31) / 32);

@@ -214,6 +214,14 @@ FG_API int fg_op_adm_conv_pack(int mode, const float* w_oihw, void* packed, int 
 FG_API int fg_op_adm_conv(int mode, int ks, const float* src1, int c1, const float* src2, int c2, int batch, int hs, int h,
                           int res_mode, const float* ab, int silu, const void* packed, const float* bias, const float* resid,
                           int resid_mode, float* out, int cout, void* stream);
+/* fg_op_adm_conv with the three EDM2 fields of the kernel.  ab_stride: the per-image stride of ab in {a, b} pairs: -1 = c1 + c2 (dense
+ * rows, fg_op_adm_conv), 0 = one row [c1 + c2] for every image, >= c1 + c2 = rows inside a wider matrix (ab points at the first image's
+ * first channel); anything else is FG_EINVAL.  resid_scale (finite): the residual enters as resid_scale * resid (one fp32 product, then
+ * the sum).  clip (finite, >= 0): > 0 clamps the output to [-clip, clip] AFTER the residual; 0 = no clamp.
+ * fg_op_adm_conv is this call with (-1, 1.0f, 0.0f). */
+FG_API int fg_op_adm_conv_ex(int mode, int ks, const float* src1, int c1, const float* src2, int c2, int batch, int hs, int h,
+                             int res_mode, const float* ab, int ab_stride, int silu, const void* packed, const float* bias,
+                             const float* resid, int resid_mode, float resid_scale, float clip, float* out, int cout, void* stream);
 /* GroupNorm (groups = min(32, C / 4), C = c1 + c2 even-sized groups, c1 / c2 even) of the concat [x1 | x2], NHWC [batch][hw][C]:
  * ab_out[b][c] = {a, b} with norm(x) = a x + b; temb (nullable, row stride temb_stride >= 2C) folds the adaptive scale / shift:
  * a (1 + temb[c]), b (1 + temb[c]) + temb[C + c].  workspace: fg_op_adm_gn_workspace_bytes (0: unsupported). */
@@ -224,6 +232,24 @@ FG_API int fg_op_adm_gn_coeffs(const float* x1, int c1, const float* x2, int c2,
 /* Self-attention with head dim 64: qkv [batch][t][heads * 192], channel h * 192 + 3 c + j (j = q, k, v); out [batch][t][heads * 64]
  * = softmax_k(q . k / 8) v.  t % 64 == 0. */
 FG_API int fg_op_adm_attention(const float* qkv, float* out, int batch, int t, int heads, void* stream);
+/* ---- EDM2 single-op entry points and the shared linear (used by the parity tests: the kernels fg_edm2_forward runs).  Arguments are
+ * checked before anything is launched: a bad shape or pointer is FG_EINVAL. */
+/* EDM2's cosine attention: fg_op_adm_attention's layout and checks; each of q, k, v is divided by 1e-4 + |.| / 8 over its 64 channels
+ * before softmax_k(q . k / 8) v. */
+FG_API int fg_op_edm2_attention(const float* qkv, float* out, int batch, int t, int heads, void* stream);
+/* MPConv's forward weight with the folds of fg_edm2_pack_weights: w [cout][cin][taps] -> out [cout][cin_pad][taps] (cin_pad >= cin, the
+ * padding columns zero), out[o][ci][tap] = w[o][ci][tap] * g * (ci < c_split ? extra0 : extra1) / sqrt(fan) / (1e-4 + |w_o| / sqrt(fan)),
+ * fan = cin * taps, g = *gain (a device scalar) or 1 when gain is NULL.  out must not alias w. */
+FG_API int fg_op_edm2_prep_weight(const float* w, float* out, int cout, int cin, int cin_pad, int taps, const float* gain, float extra0,
+                                  float extra1, int c_split, void* stream);
+/* Pixel norm x / (1e-4 + |x| / sqrt(c)) over the channels of every pixel, NHWC: down == 0: x, out [batch][h][h][c], out == x allowed;
+ * down == 1: x [batch][2h][2h][c] is averaged over 2x2 first (out must not alias x). */
+FG_API int fg_op_edm2_pixel_norm(const float* x, float* out, int batch, int h, int c, int down, void* stream);
+/* y [batch][out] = act(x [batch][in] w[out][in]^T + bias): the linear layer of all four engines (embeddings, modulations).  bias nullable;
+ * act_silu != 0: SiLU after the bias.  Shapes with in % 16 == 0 and out % 32 == 0 run on the fp32 matrix pipe with 16-byte loads: there
+ * x and w must be 16-byte aligned (FG_EINVAL otherwise; the engines' buffers always are).  Every other shape runs the FMA kernel, which
+ * has no alignment requirement.  y must not alias x. */
+FG_API int fg_op_linear(const float* x, const float* w, const float* bias, float* y, int batch, int in, int out, int act_silu, void* stream);
 /* Mapping-network input: out[b] = [cos | sin](c_noise[b] * freqs) (+ wa aug[b] when aug != nullptr), freqs [n / 2], wa [n][aug_dim],
  * out [batch][n], n even. */
 FG_API int fg_op_adm_map_in(const float* c_noise, const float* freqs, const float* aug, const float* wa, int aug_dim, float* out,
@@ -942,6 +968,15 @@ FG_API size_t fg_edm2_workspace_bytes(const fg_edm2* h, int batch);
  * [B, label_dim] or NULL (= zeros).  emb_out (nullable): the embedding mp_silu(...) [B, emb_channels]. */
 FG_API int fg_edm2_forward(fg_edm2* h, const float* x_t, const double* t, const float* class_labels, float* out, float* emb_out,
                            int batch, void* workspace, size_t workspace_bytes, void* stream);
+/* Exposed for the parity tests (tests/test_gpu_edm2_ops.py): fg_edm2_forward with taps - the same forward, the same launches, fp32 copies
+ * on `stream` behind the kernels that wrote the buffers; `out` and `emb_out` are what the untapped call leaves, bit for bit.  taps: HOST
+ * array of num_taps = fg_edm2_num_taps(h) = 2 + fg_edm2_num_blocks(h) device buffers, each nullable, fp32 NHWC: taps[0] the stem conv's
+ * output [B, R, R, width of level 0]; taps[1 + i] the output of block i in fg_edm2_block_info order [B, res_out, res_out, cout];
+ * taps[num_taps - 1] the raw U-Net output F [B, R, R, img_channels] (before precond_output).  taps NULL: fg_edm2_forward.  Another
+ * num_taps, or a tap that aliases x_t / out / emb_out: FG_EINVAL. */
+FG_API int fg_edm2_num_taps(const fg_edm2* h);
+FG_API int fg_edm2_forward_taps(fg_edm2* h, const float* x_t, const double* t, const float* class_labels, float* out, float* emb_out,
+                                float* const* taps, int num_taps, int batch, void* workspace, size_t workspace_bytes, void* stream);
 /* train() / eval(): sigma_shift applies in eval mode only (training != 0 disables it). */
 FG_API int fg_edm2_set_training(fg_edm2* h, int training);
 /* The FG_LOOP_X0 student loop of fg_sampler_run (same arguments, checks and semantics, EDM schedule) around fg_edm2_forward;

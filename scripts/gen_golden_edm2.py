@@ -1,6 +1,7 @@
 """Record the EDM2 fixtures under tests/golden/ from the reference itself (read through oracle/_ref_import.py, CPU, fp32).
 
-    python scripts/gen_golden_edm2.py
+    python scripts/gen_golden_edm2.py                  every fixture
+    python scripts/gen_golden_edm2.py drop_precond     only edm2_narrow_drop_precond_b2.pt (the others stay as they are)
 
 Writes
   edm2_in64_s_state_dict_keys.txt  "name shape" per state_dict() entry of EDM2Precond(**EDM2_IN64_S_Config) (203 lines)
@@ -9,6 +10,8 @@ Writes
                                    generator_fn (1 / 2 / 4 steps 'sde' with injected noise, 2 steps 'ode', a custom 2-step t_list) and
                                    one 4-step sample() with classifier-free guidance
   edm2_in64_s_b2.pt                the full EDM2-S network at B = 2, weights random_state_dict(seed 4321): forward output
+  edm2_narrow_drop_precond_b2.pt   NARROW, the same weights and inputs, EDM2Precond(drop_precond = 'input' / 'output' / 'both'): the
+                                   forward output of each, subsampled
 Weights are not stored: tests/edm2_ref.py regenerates them from the seed."""
 import importlib
 import os
@@ -50,9 +53,26 @@ def inputs(cfg, B, seed):
     return x, t, cond
 
 
+def record_drop_precond(mod):
+    cfg = D.NARROW
+    sd = D.random_state_dict(cfg, seed=1234)
+    x, t, cond = inputs(cfg, 2, 11)
+    fx = {"t": t, "cond": cond}
+    for drop in ("input", "output", "both"):
+        net = mod.EDM2Precond(**cfg.kwargs(), drop_precond=drop)
+        net.load_state_dict(sd, strict=True)
+        with torch.inference_mode():
+            fx[drop] = sub(net.eval()(x, t, condition=cond))
+    torch.save(fx, os.path.join(OUT, "edm2_narrow_drop_precond_b2.pt"))
+
+
 def main():
     _, _, model = import_reference()
     mod = importlib.import_module("fastgen.networks.EDM2.network")
+    record_drop_precond(mod)
+    if sys.argv[1:] == ["drop_precond"]:
+        print("wrote", os.path.join(OUT, "edm2_narrow_drop_precond_b2.pt"))
+        return
     torch.manual_seed(0)
     with torch.no_grad():
         full = mod.EDM2Precond(**D.IN64_S.kwargs())

@@ -239,6 +239,8 @@ def unet(sd, cfg: EDM2Config, x: Tensor, c_noise: Tensor, labels: Optional[Tenso
     r = cfg.img_resolution
     x = mp_conv(torch.cat([x, torch.ones_like(x[:, :1])], 1), sd[f"unet.enc.{r}x{r}_conv.weight"])
     skips = [x]
+    if trace is not None:
+        trace["stem"] = x
     for b in enc:
         x = block(sd, b, cfg, x, emb)
         skips.append(x)
@@ -250,17 +252,27 @@ def unet(sd, cfg: EDM2Config, x: Tensor, c_noise: Tensor, labels: Optional[Tenso
         x = block(sd, b, cfg, x, emb)
         if trace is not None:
             trace[b.key] = x
-    return mp_conv(x, sd["unet.out_conv.weight"], gain=sd["unet.out_gain"].to(x.dtype))
+    x = mp_conv(x, sd["unet.out_conv.weight"], gain=sd["unet.out_gain"].to(x.dtype))
+    if trace is not None:
+        trace["F"] = x
+    return x
 
 
 def precond_forward(sd, cfg: EDM2Config, x_t: Tensor, t: Tensor, condition: Optional[Tensor], sigma_shift: float = 0.0,
-                    trace: Optional[dict] = None) -> Tensor:
-    """EDM2Precond.forward in eval mode, x0 prediction; t float64 [B]."""
+                    trace: Optional[dict] = None, drop_precond: Optional[str] = None) -> Tensor:
+    """EDM2Precond.forward in eval mode, x0 prediction; t float64 [B].  drop_precond None / "input" / "output" / "both": "input" skips
+    precond_input (the U-Net sees x_t and t as they are), "output" skips precond_output (the result is the U-Net's own output)."""
+    assert drop_precond in (None, "input", "output", "both")
     t = t.to(torch.float64)
     sd2 = cfg.sigma_data ** 2
-    c_in = (1 / (sd2 + t ** 2).sqrt()).to(x_t.dtype)
-    c_noise = (t.clamp(min=1e-6).log() / 4).to(x_t.dtype)
-    F_x = unet(sd, cfg, x_t * c_in[:, None, None, None], c_noise, condition, trace)
+    if drop_precond in ("input", "both"):
+        F_x = unet(sd, cfg, x_t, t.to(x_t.dtype), condition, trace)
+    else:
+        c_in = (1 / (sd2 + t ** 2).sqrt()).to(x_t.dtype)
+        c_noise = (t.clamp(min=1e-6).log() / 4).to(x_t.dtype)
+        F_x = unet(sd, cfg, x_t * c_in[:, None, None, None], c_noise, condition, trace)
+    if drop_precond in ("output", "both"):
+        return F_x
     ts = t - sigma_shift
     c_skip = (sd2 / (ts ** 2 + sd2)).to(x_t.dtype)
     c_out = (ts * cfg.sigma_data / (ts ** 2 + sd2).sqrt()).to(x_t.dtype)
