@@ -84,6 +84,16 @@ class fg_attention_plan(ctypes.Structure):
                 ("scratch_bytes", c_size_t)]
 
 
+class fg_edm_conv_plan(ctypes.Structure):
+    _fields_ = [("kernel", c_int), ("stat_slots", c_int)]
+
+
+# fg_op_edm_conv_pack layouts, fg_edm_conv_plan.kernel, fg_op_edm_head_pack_bytes
+FG_EDM_PACK_GENERIC, FG_EDM_PACK_WS, FG_EDM_PACK_X3WS, FG_EDM_PACK_X3SUB = range(4)
+FG_EDM_CONV_GENERIC, FG_EDM_CONV_WS, FG_EDM_CONV_X3WS = 1, 2, 3
+FG_EDM_PACK_STEM, FG_EDM_PACK_AUX = 0, 1
+
+
 class fg_gemm_plan(ctypes.Structure):
     _fields_ = [("refusal", c_int), ("kernel", c_int), ("tile_n", c_int), ("epilogue", c_int), ("ksplit", c_int), ("xn", c_int), ("grid", c_int),
                 ("lds_bytes", c_int), ("row0", c_int), ("rows", c_int), ("pieces", c_int)]
@@ -271,6 +281,26 @@ SIGNATURES = {
     "fg_op_dgrad_weights": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
     "fg_op_train_elementwise": (c_int, [c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
                                         c_double, c_double, c_int, c_void_p]),
+    "fg_op_edm_conv_pack_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
+    "fg_op_edm_conv_pack": (c_int, [c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
+    "fg_op_edm_conv_plan": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
+                                    POINTER(fg_edm_conv_plan)]),
+    "fg_op_edm_conv": (c_int, [c_int, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p,
+                               c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_float, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
+                               c_void_p, c_void_p]),
+    "fg_op_edm_gn_finalize": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_int,
+                                      c_int, c_void_p]),
+    "fg_op_edm_gn_silu_pool": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
+    "fg_op_edm_attention": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p]),
+    "fg_op_edm_attn_merge_weights": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
+    "fg_op_edm_attention_merged": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_int, c_void_p]),
+    "fg_op_edm_head_pack_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "fg_op_edm_stem": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
+    "fg_op_edm_conv_in": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
+    "fg_op_edm_aux_head": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
+                                   c_void_p]),
+    "fg_op_edm_aux_out": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
+                                  c_void_p]),
     "fg_op_dropout_mask": (c_int, [c_void_p, c_int64, c_float, ctypes.c_uint32, c_uint64, c_void_p]),
     "fg_edm_set_augment": (c_int, [c_void_p, c_void_p]),
     "fg_edm_set_training": (c_int, [c_void_p, c_int]),

@@ -178,8 +178,9 @@ __global__ __launch_bounds__(256) void stem_kernel(const float* __restrict__ x, 
         float sv = 0.f, qv = 0.f;
 #pragma unroll
         for (int i = 0; i < 16; ++i) {
-            const float v = acc[nt][i] + bv;
-            obase[(size_t)acc_row(i, h) * 128 + nt * 32 + r] = (T)v;
+            const T vs = (T)(acc[nt][i] + bv);
+            obase[(size_t)acc_row(i, h) * 128 + nt * 32 + r] = vs;
+            const float v = (float)vs;  // the statistics are of the values as stored, as the conv epilogues'
             sv += v;
             qv = fmaf(v, v, qv);
         }

@@ -613,7 +613,8 @@ int launch_w(const ConvArgs& a, hipStream_t s) {
 
 template <typename T>
 int launch_t(int ks, int pro, int res, int outmode, const ConvArgs& a, hipStream_t s) {
-    // the instantiations the EDM U-Net needs (EDM/network.py:237-272)
+    // the instantiations the EDM U-Net needs (EDM/network.py:237-272); edm_conv_generic_form (engine_edm_ops.inc) restates this list for
+    // the argument check of fg_op_edm_conv / fg_op_edm_conv_plan: keep the two in step
     if (outmode == OUT_QKV) {
         if (ks == 1 && pro == PRO_GN && res == RES_NONE) return launch_w<T, 1, PRO_GN, RES_NONE, OUT_QKV>(a, s);
         return (int)hipErrorInvalidValue;

@@ -328,9 +328,9 @@ __global__ __launch_bounds__(WS_NTHR) void conv3_ws_kernel(const ConvArgs a, con
 #pragma unroll
                 for (int e = 0; e < 4; ++e) v[e] = fmaf(rw[e], a.scale, v[e]);
             }
-            if (!(ABL & 32)) store4(ob + (loff + (unsigned)(((j >> 2) * G::W + (j & 3) * 4) * 256)), v);
-            // GroupNorm partial sums from the fp32 values: the bf16 rounding of the stored tensor is zero-mean noise of 2^-9
-            // relative size per element, far below the statistics' own resolution over >= 8192 elements per group
+            // GroupNorm partial sums of the values AS STORED (store4 returns them widened back), as conv_fused_kernel's: the next
+            // norm normalises the bf16 tensor the next conv reads, whichever kernel wrote it
+            if (!(ABL & 32)) v = store4(ob + (loff + (unsigned)(((j >> 2) * G::W + (j & 3) * 4) * 256)), v);
             ssum += (v[0] + v[1]) + (v[2] + v[3]);
             ssq += (v[0] * v[0] + v[1] * v[1]) + (v[2] * v[2] + v[3] * v[3]);
         }

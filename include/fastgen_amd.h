@@ -423,6 +423,73 @@ FG_API int fg_op_dgrad_weights(const float* w, float* wt, int cout, int cin, int
 FG_API int fg_op_train_elementwise(int op, int dtype, const void* a, const void* b, const void* c, const void* d, const void* e, void* out,
                                    int batch, int ch, int ch_pad, int hw, double f0, double f1, int flag, void* stream);
 
+/* ---- EDM (SongUNet) inference kernels, one op per call (conv.hip, conv_ws.hip, conv_ws3.hip, misc.hip, aux.hip, attn.hip): the
+ * launchers fg_edm_forward runs, without a handle, for per-op parity tests.  dtype is a compute mode FG_DTYPE_F32 / _BF16 / _BF16X3;
+ * activation tensors are void* NHWC in its storage type (bf16 in FG_DTYPE_BF16, else fp32).  Every argument is checked before anything
+ * is launched: a shape, alignment (tensors, weights, ab, bias, temb 16 bytes; stats 8), null pointer or combination the launcher cannot
+ * serve is FG_EINVAL with the reason in fg_last_error().
+ *
+ * fg_op_edm_conv_pack: OIHW fp32 weights into one of the four packings (bytes: fg_op_edm_conv_pack_bytes, 0 = no such packing):
+ * GENERIC conv_fused_kernel's (any dtype, ks 1 | 3; qkv_perm: the q | k | v de-interleave of the 1x1 qkv weights), WS / X3WS the
+ * wave-specialised 3x3 kernels' (bf16 / bf16x3, cout 256, cin >= 128), X3SUB the per-phase merged 2x2 weights of the sub-pixel form.
+ * fg_op_edm_conv: out = (conv(R(P(a x + b))) + bias + temb[n] + resid) * scale on the virtual concat x = [src1 (c1) | src2 (c2)];
+ * pro 0 none, 1 a x + b, 2 silu(a x + b); res 0 none, 1 2x2 mean (hs = 2 h), 2 nearest 2x (h = 2 hs), 3 the same as four 2x2 convs on
+ * the source (wpack_ws = the X3SUB packing); outmode 0 NHWC (out [batch][h][h][cout]), 1 planes q_out, k_out [batch][h h][256] and
+ * vt_out [batch][256][h h] (cout 768), 4 planes q_out, vt_out (cout 512, bf16x3, 16x16).  temb [batch][temb_stride] and resid nullable;
+ * rshift 1: resid is [batch][h/2][h/2][cout] and pixel (y, x) adds its pixel (y >> 1, x >> 1).  stats (nullable) [batch][slots][cout / 4]
+ * {sum, sum of squares} of the stored values per tile and channel quad.  wpack_ws NULL keeps the call on conv_fused_kernel.
+ * fg_op_edm_conv_plan launches nothing and needs no GPU: the kernel launch_conv_fused will take for these arguments and the number of
+ * statistics slots per image it writes, from the launcher's own predicates (FASTGEN_AMD_CONV_WS, read once per process, included). */
+#define FG_EDM_PACK_GENERIC 0
+#define FG_EDM_PACK_WS 1
+#define FG_EDM_PACK_X3WS 2
+#define FG_EDM_PACK_X3SUB 3
+#define FG_EDM_CONV_GENERIC 1 /* conv_fused_kernel */
+#define FG_EDM_CONV_WS 2      /* conv3_ws_kernel */
+#define FG_EDM_CONV_X3WS 3    /* conv3_x3ws_kernel */
+typedef struct fg_edm_conv_plan {
+    int kernel;     /* FG_EDM_CONV_* */
+    int stat_slots; /* statistics slots per image */
+} fg_edm_conv_plan;
+FG_API size_t fg_op_edm_conv_pack_bytes(int dtype, int layout, int cout, int cin, int ks);
+FG_API int fg_op_edm_conv_pack(int dtype, int layout, const float* w_oihw, void* packed, int cout, int cin, int ks, int qkv_perm, void* stream);
+FG_API int fg_op_edm_conv_plan(int dtype, int ks, int pro, int res, int outmode, int c1, int c2, int batch, int hs, int h, int cout,
+                               int has_wpack_ws, int rshift, fg_edm_conv_plan* plan);
+FG_API int fg_op_edm_conv(int dtype, int ks, int pro, int res, int outmode, const void* src1, int c1, const void* src2, int c2, int batch, int hs,
+                          int h, const float* ab, const void* wpack, const void* wpack_ws, const float* bias, const float* temb, int temb_stride,
+                          const void* resid, int rshift, float scale, void* out, int cout, float* stats, void* q_out, void* k_out, void* vt_out,
+                          void* stream);
+/* GroupNorm coefficients ab [batch][c1 + c2] {a, b} (and mr [batch][groups] {mean, rstd}, nullable) from the producers' partial
+ * statistics st1 [batch][s1][c1 / 4], st2 [batch][s2][c2 / 4] (launch_gn_finalize); 16 <= c1 + c2 <= 512.
+ * fg_op_edm_gn_silu_pool: out [batch][res_out][res_out][c] = mean of 2x2 of silu(a x + b), x at 2 res_out. */
+FG_API int fg_op_edm_gn_finalize(const float* st1, int c1, int s1, const float* st2, int c2, int s2, const float* gamma, const float* beta,
+                                 float eps, float* ab, float* mr, int batch, int hw, void* stream);
+FG_API int fg_op_edm_gn_silu_pool(int dtype, const void* x, const float* ab, void* out, int batch, int res_out, int c, void* stream);
+/* One head of dim 256 over t in {64, 256} tokens: out [batch][t][256] = softmax(q k^T / 16) v, q, k [batch][t][256], vt [batch][256][t].
+ * merge_weights: w_out [2 c][c] = [Wk^T Wq ; Wp Wv], b_out [2 c] = [Wk^T bq ; Wp bv] from the reference's qkv_w [3 c][c] (row 3 ch + plane).
+ * attention_merged (bf16x3, 256 tokens): out = (softmax(qm xn^T / 16) vm + bp + x_mid) * scale, xn = a x_mid + b; stats (nullable)
+ * [batch][8][64] of out, slot = 32 tokens. */
+FG_API int fg_op_edm_attention(int dtype, const void* q, const void* k, const void* vt, void* out, int batch, int t, void* stream);
+FG_API int fg_op_edm_attn_merge_weights(const float* qkv_w, const float* qkv_b, const float* proj_w, float* w_out, float* b_out, int c,
+                                        void* stream);
+FG_API int fg_op_edm_attention_merged(const float* qm, const float* x_mid, const float* ab, const float* vmt, const float* bp, float scale,
+                                      float* out, float* stats, int batch, void* stream);
+/* Stem and output head.  coef [5][batch] = c_in, c_noise, c_skip, c_out, r_noise (an input here).  stem (MFMA, 128 channels out;
+ * stats [batch][res res / 32][32]) and conv_in (the plain form): out NHWC = conv3x3(c_in[n] x) + bias, x NCHW fp32.  aux_head (MFMA,
+ * 32x32) and aux_out (the plain form, cout <= 4): out NCHW fp32 = c_skip[n] x_t + c_out[n] (conv3x3(silu(a x + b)) + bias).  `packed`:
+ * scratch for the packed weights, fg_op_edm_head_pack_bytes(FG_EDM_PACK_STEM | FG_EDM_PACK_AUX, dtype, c) bytes (0: unsupported). */
+#define FG_EDM_PACK_STEM 0
+#define FG_EDM_PACK_AUX 1
+FG_API size_t fg_op_edm_head_pack_bytes(int which, int dtype, int c);
+FG_API int fg_op_edm_stem(int dtype, const float* x, const float* coef, const float* w_oihw, void* packed, const float* bias, void* out,
+                          float* stats, int batch, int res, int cin, void* stream);
+FG_API int fg_op_edm_conv_in(int dtype, const float* x, const float* coef, const float* w_oihw, const float* bias, void* out, int batch, int res,
+                             int cin, int cout, void* stream);
+FG_API int fg_op_edm_aux_head(int dtype, const void* x, const float* ab, const float* w_oihw, void* packed, const float* bias, const float* x_t,
+                              const float* coef, float* out, int batch, int c, int cout, void* stream);
+FG_API int fg_op_edm_aux_out(int dtype, const void* x, const float* ab, const float* w_oihw, const float* bias, const float* x_t,
+                             const float* coef, float* out, int batch, int res, int c, int cout, void* stream);
+
 /* ---- DiT: the class-conditional diffusion transformer of fastgen/networks/DiT/network.py -------------------------
  * kwargs of DiT(input_size, patch_size, in_channels, hidden_size, depth, num_heads, mlp_ratio, num_classes, class_dropout_prob,
  * r_timestep, ...) (:233-253; configs/net.py:98-127).  Supported: token grids input_size / patch_size of 16 (256
