@@ -62,6 +62,10 @@ class fg_wan_i2v_config(ctypes.Structure):
     _fields_ = [("latent_channels", c_int), ("mask_channels", c_int), ("image_dim", c_int)]
 
 
+class fg_wan_ti2v_config(ctypes.Structure):
+    _fields_ = [("latent_channels", c_int)]
+
+
 class fg_wan_block_taps(ctypes.Structure):
     _fields_ = [("attn1", c_void_p), ("x_attn1", c_void_p), ("attn2", c_void_p), ("x_attn2", c_void_p), ("x_ffn", c_void_p)]
 
@@ -253,6 +257,12 @@ SIGNATURES = {
     "fg_wan_i2v_cond_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int]),
     "fg_wan_set_i2v_cond": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p]),
     "fg_wan_i2v_cond_read": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "fg_wan_create_ti2v": (c_int, [POINTER(fg_wan_config), POINTER(fg_wan_ext_config), POINTER(fg_wan_ti2v_config), POINTER(c_void_p)]),
+    "fg_wan_set_first_frame": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
+    "fg_wan_first_frame_read": (c_int, [c_void_p, c_void_p, c_void_p]),
+    "fg_op_wan_patch_embed": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
+    "fg_op_wan_final": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_int,
+                                c_void_p]),
     "fg_op_wan_dual_cross_attention": (c_int, [c_void_p, c_int, c_int64, c_void_p, c_void_p, c_int, c_int64, c_int, c_void_p, c_void_p, c_int,
                                                c_int64, c_int, c_void_p, c_int, c_int64, c_int, c_int, c_int, c_void_p]),
     "fg_disc_edm_num_params": (c_int, [c_int]),

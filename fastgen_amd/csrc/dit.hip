@@ -671,6 +671,7 @@ int ln_mod_d(int D, const void* x, const float* mod, int ms, int so, int co, voi
         case 256: hipLaunchKernelGGL((ln_modulate_kernel<ST, 256>), g, b, 0, s, (const ST*)x, mod, ms, so, co, (ST*)y, ntok, tpi); break;
         case 1536: hipLaunchKernelGGL((ln_modulate_kernel<ST, 1536>), g, b, 0, s, (const ST*)x, mod, ms, so, co, (ST*)y, ntok, tpi); break;
         case 2048: hipLaunchKernelGGL((ln_modulate_kernel<ST, 2048>), g, b, 0, s, (const ST*)x, mod, ms, so, co, (ST*)y, ntok, tpi); break;
+        case 3072: hipLaunchKernelGGL((ln_modulate_kernel<ST, 3072>), g, b, 0, s, (const ST*)x, mod, ms, so, co, (ST*)y, ntok, tpi); break;
         case 5120: hipLaunchKernelGGL((ln_modulate_kernel<ST, 5120>), g, b, 0, s, (const ST*)x, mod, ms, so, co, (ST*)y, ntok, tpi); break;
         default: return (int)hipErrorInvalidValue;
     }
@@ -719,6 +720,7 @@ int launch_dit_ln_modulate_fp8(int D, const void* x, const float* mod, int mod_s
         case 256: LN8(256); break;
         case 1536: LN8(1536); break;
         case 2048: LN8(2048); break;
+        case 3072: LN8(3072); break;
         case 5120: LN8(5120); break;
         default: return (int)hipErrorInvalidValue;
     }

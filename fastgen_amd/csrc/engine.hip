@@ -1715,6 +1715,31 @@ int fg_op_wan_dual_cross_attention(const void* q, int ldq, int64_t q_bs, const v
                                       batch, heads, lq, (hipStream_t)stream));
     return FG_OK;
 }
+int fg_op_wan_patch_embed(const float* x, const float* first_frame, const float* w, const float* bias, void* out, int batch, int channels, int frames,
+                          int height, int width, int d, int path, void* stream) {
+    if (!x || !w || !bias || !out || batch <= 0 || channels <= 0 || channels > 64 || frames <= 0 || height <= 0 || width <= 0 || (height & 1) ||
+        (width & 1) || d <= 0 || (d % 2) || path < 0 || path > 2)
+        return fail(FG_EINVAL, "fg_op_wan_patch_embed: bad argument (null pointer, channels outside [1, 64], odd height / width / d, path outside [0, 2])");
+    if ((int64_t)batch * frames * (height / 2) * (width / 2) > INT32_MAX / 2) return fail(FG_EINVAL, "fg_op_wan_patch_embed: too many tokens");
+    if (path == 2 && channels != 48) return fail(FG_EINVAL, "fg_op_wan_patch_embed: the tiled kernel serves 48 channels, got %d", channels);
+    HIP_TRY(launch_wan_ti2v_patch_embed(x, first_frame, w, bias, out, batch, channels, frames, height, width, d, path, (hipStream_t)stream));
+    return FG_OK;
+}
+int fg_op_wan_final(const void* tokens, const float* mod, const float* w, const float* bias, const float* first_frame, float* out, int batch,
+                    int channels, int frames, int gh, int gw, int d, float eps, int path, void* stream) {
+    if (!tokens || !mod || !w || !bias || !out || batch <= 0 || channels <= 0 || channels > 64 || frames <= 0 || gh <= 0 || gw <= 0 || path < 0 ||
+        path > 2)
+        return fail(FG_EINVAL, "fg_op_wan_final: bad argument (null pointer, channels outside [1, 64], a count <= 0, path outside [0, 2])");
+    if ((int64_t)batch * frames * gh * gw > INT32_MAX / 2) return fail(FG_EINVAL, "fg_op_wan_final: too many tokens");
+    const bool tiled = channels == 48 && (d % 32) == 0 && path != 1;
+    if (path == 2 && !tiled) return fail(FG_EINVAL, "fg_op_wan_final: the tiled kernel serves 48 channels and d %% 32 == 0, got %d, %d", channels, d);
+    if (!tiled && d != 256 && d != 384 && d != 1536 && d != 2048 && d != 3072 && d != 5120)
+        return fail(FG_EINVAL, "fg_op_wan_final: d %d unsupported by the wave-per-token head (256, 384, 1536, 2048, 3072, 5120)", d);
+    if (tiled && d <= 0) return fail(FG_EINVAL, "fg_op_wan_final: bad d");
+    HIP_TRY(launch_wan_ti2v_final(d, tokens, mod, w, bias, first_frame, out, batch * frames * gh * gw, frames, gh, gw, channels, eps, path,
+                                  (hipStream_t)stream));
+    return FG_OK;
+}
 int fg_op_attention_split(const void* q, const void* k, const void* v, void* out, int batch, int heads, int head_dim, int lq, int lkv, int nsplit,
                           void* stream) {
     if (batch <= 0 || heads <= 0 || lq <= 0 || lkv <= 0 || (head_dim != 128 && head_dim != 72))

@@ -183,7 +183,7 @@ int fg_wan_sampler_run(fg_wan* h, const fg_wan_sampler_config* sc, float* x, con
                        const float* eps, uint64_t seed, int batch, int frames, int height, int width, void* workspace, size_t workspace_bytes,
                        int use_graph, void* stream) {
     if (!h || !sc || !x || !t_list) return fail(FG_EINVAL, "null argument");
-    if (h->is_i2v) return fail(FG_EINVAL, "the chunked / causal loops are not implemented for an image-to-video handle");
+    if (h->is_i2v || h->is_ti2v) return fail(FG_EINVAL, "the chunked / causal loops are not implemented for an image-to-video handle");
     int rc = check_sampler_args(t_list, steps, sample_type, FG_LOOP_X0, sc->schedule);
     if (rc) return rc;
     if (!(sc->t_scale > 0.0)) return fail(FG_EINVAL, "t_scale must be positive");
@@ -365,7 +365,7 @@ int fg_wan_guided_sampler_run(fg_wan* h, const fg_wan_guided_sampler_config* sc,
                               const float* eps, uint64_t seed, int batch, int frames, int height, int width, void* workspace,
                               size_t workspace_bytes, int use_graph, void* stream) {
     if (!h || !sc || !x || !t_list || !table) return fail(FG_EINVAL, "null argument");
-    if (h->is_i2v) return fail(FG_EINVAL, "the chunked / causal loops are not implemented for an image-to-video handle");
+    if (h->is_i2v || h->is_ti2v) return fail(FG_EINVAL, "the chunked / causal loops are not implemented for an image-to-video handle");
     if (steps < 1 || steps > kGuidedMaxSteps) return fail(FG_EINVAL, "steps must be in [1, %d]", kGuidedMaxSteps);
     if (!(sc->t_scale > 0.0)) return fail(FG_EINVAL, "t_scale must be positive");
     if (sc->guidance != 0 && sc->guidance != 1) return fail(FG_EINVAL, "guidance must be 0 (batch B) or 1 (stacked batch 2 B)");
@@ -531,6 +531,9 @@ int fg_wan_full_sampler_run(fg_wan* h, const fg_wan_sampler_config* sc, const fl
     if (loop_kind == FG_LOOP_EULER) return fail(FG_EINVAL, "FG_LOOP_EULER is not a loop of this network (fg_wan_full_guided_sampler_run)");
     if (loop_kind == FG_LOOP_MEANFLOW && (!h->ext.r_timestep || !sc->net_pred_flow))
         return fail(FG_EINVAL, "FG_LOOP_MEANFLOW needs a flow-predicting network with the r_embedder (fg_wan_create_ex, r_timestep = 1)");
+    if (loop_kind == FG_LOOP_MEANFLOW && h->is_ti2v)
+        return fail(FG_EINVAL, "FG_LOOP_MEANFLOW is not implemented for a first-frame-replacement handle (the reference writes the first-frame "
+                    "latents into the velocity there)");
     if (!(sc->t_scale > 0.0)) return fail(FG_EINVAL, "t_scale must be positive");
     if (sc->context_noise != 0.0 || sc->prefill_frames != 0) return fail(FG_EINVAL, "context_noise and prefill_frames must be 0: there is no cache to fill");
     if (!wan_full_shape_ok(h, batch, frames, height, width) || !workspace || (((uintptr_t)workspace) & 255))
@@ -544,8 +547,10 @@ int fg_wan_full_sampler_run(fg_wan* h, const fg_wan_sampler_config* sc, const fl
     if (h->text_B != batch) return fail(FG_ENOTREADY, "no text condition for batch %d (call fg_wan_set_text)", batch);
     if (h->is_i2v && (h->ff_B != batch || h->ff_F != frames || h->ff_H != height || h->ff_W != width))
         return fail(FG_ENOTREADY, "no image-to-video condition for batch %d, %d frames of %d x %d (call fg_wan_set_i2v_cond)", batch, frames, height, width);
+    if (h->is_ti2v && !h->has_first_frame(batch, height, width))
+        return fail(FG_ENOTREADY, "no first frame for batch %d of %d x %d (call fg_wan_set_first_frame)", batch, height, width);
     const int rows = batch * frames;
-    const int64_t total = (int64_t)batch * h->vch() * frames * height * width;
+    const int64_t total = (int64_t)batch * h->vch() * frames * height * width, hw1 = (int64_t)height * width;
     auto enqueue = [&](hipStream_t q) -> int {
         // the network on w.x at t_i into v; ri: MeanFlow's r (-1: 0, else t_list[ri]), -2: none.  The rows carry r itself: the call
         // forms t - r for time_cond_diff
@@ -561,6 +566,10 @@ int fg_wan_full_sampler_run(fg_wan* h, const fg_wan_sampler_config* sc, const fl
                 if (r) return r;
                 if (sc->net_pred_flow) HIP_TRY(launch_flow_to_x0(w.x, w.v, w.tl, i, 1.0f, pred, total, q));
                 else HIP_TRY(hipMemcpyAsync(pred, w.v, sizeof(float) * total, hipMemcpyDeviceToDevice, q));
+                // first-frame replacement: the conversion ran on the loop's own (unreplaced) state, as the reference converts on the
+                // caller's x_t; the condition lands last (WanI2V/network.py:506-510).  The state's frame 0 is never restored between
+                // steps (`preserve_conditioning`): the network reads the condition in its place and every prediction carries it.
+                if (h->is_ti2v) HIP_TRY(launch_copy_rows(h->ff0, hw1, pred, (int64_t)frames * hw1, hw1, (int64_t)batch * h->vch(), q));
                 return FG_OK;
             });
         return meanflow_loop(L, w.v, [&](int i, float* u) { return net(i, sample_type == FG_SAMPLE_SDE ? -1 : i + 1, u); });
@@ -572,7 +581,7 @@ int fg_wan_full_sampler_run(fg_wan* h, const fg_wan_sampler_config* sc, const fl
                           {frames, height, width, (int64_t)(uintptr_t)noise, (int64_t)(uintptr_t)eps, (int64_t)(uintptr_t)out,
                            (int64_t)(uintptr_t)workspace, tsb, sc->net_pred_flow, sc->schedule, (int64_t)h->text_L,
                            (int64_t)(uintptr_t)h->blocks[0].kv2, (int64_t)h->fp8, h->ext.time_cond_diff,
-                           (int64_t)(uintptr_t)h->ff, (int64_t)(uintptr_t)h->blocks[0].kvi, (int64_t)h->img_L},
+                           (int64_t)(uintptr_t)h->ff, (int64_t)(uintptr_t)h->blocks[0].kvi, (int64_t)h->img_L, (int64_t)(uintptr_t)h->ff0},
                           (hipStream_t)stream, enqueue);
 }
 
@@ -609,6 +618,9 @@ int fg_wan_full_guided_sampler_run(fg_wan* h, const fg_wan_guided_sampler_config
         return fail(FG_ENOTREADY, "no text condition for batch %d (call fg_wan_set_text%s)", Be, guided ? " with [cond; neg_cond]" : "");
     if (h->is_i2v && (h->ff_B != Be || h->ff_F != frames || h->ff_H != height || h->ff_W != width))
         return fail(FG_ENOTREADY, "no image-to-video condition for batch %d, %d frames of %d x %d (call fg_wan_set_i2v_cond)", Be, frames, height, width);
+    if (h->is_ti2v && !h->has_first_frame(Be, height, width))
+        return fail(FG_ENOTREADY, "no first frame for batch %d of %d x %d (call fg_wan_set_first_frame%s)", Be, height, width,
+                    guided ? " with [cond; neg_cond]" : "");
     hipStream_t s = (hipStream_t)stream;
     int rc;
     if ((rc = wan_upload_step_scalars(h, t_list, table, steps, 0, w.sc, s))) return rc;  // (no draw in this loop: the seed slot goes unread)
@@ -625,6 +637,16 @@ int fg_wan_full_guided_sampler_run(fg_wan* h, const fg_wan_guided_sampler_config
             const int r = wan_forward(h, w.xin, w.te, w.v, Be, frames, height, width, 0, 0, 2, w.net, w.net_bytes, q, nullptr, &full);
             if (r) return r;
             HIP_TRY(launch_guided_multistep(w.v, w.xin, x2, w.xl, w.mp, tab + 8 * (size_t)i, guided, i == 0, total, q));
+            if (h->is_ti2v) {
+                // `latents[:, :, 0] = first_frame_cond[:, :, 0]` after every solver step (WanI2V/network.py:414-417): the conditional
+                // rows' first frame into x and into the stacked copy, as the reference restores the one latent tensor both calls read.
+                // Its zeroing of the guided flow on frame 0 (:406-410) is unobservable here: the solver step is elementwise, so frame 0
+                // of the flow reaches frame 0 of x, x_last and m_prev only, x's is overwritten right here, and the other two are read
+                // for frame 0 of later steps alone.
+                const int64_t hw1 = (int64_t)height * width, planes = (int64_t)batch * h->vch();
+                HIP_TRY(launch_copy_rows(h->ff0, hw1, w.xin, (int64_t)frames * hw1, hw1, planes, q));
+                if (x2) HIP_TRY(launch_copy_rows(h->ff0, hw1, x2, (int64_t)frames * hw1, hw1, planes, q));
+            }
         }
         HIP_TRY(hipMemcpyAsync(x, w.xin, sizeof(float) * total, hipMemcpyDeviceToDevice, q));
         return FG_OK;
@@ -635,6 +657,7 @@ int fg_wan_full_guided_sampler_run(fg_wan* h, const fg_wan_guided_sampler_config
     memcpy(&tsb, &sc->t_scale, 8);
     const std::vector<int64_t> key = {batch, guided, frames, height, width, steps, (int64_t)(uintptr_t)x, (int64_t)(uintptr_t)workspace, tsb,
                                       (int64_t)h->text_L, (int64_t)(uintptr_t)h->blocks[0].kv2, (int64_t)h->fp8, h->ext.time_cond_diff,
-                                      (int64_t)(uintptr_t)h->ff, (int64_t)(uintptr_t)h->blocks[0].kvi, (int64_t)h->img_L};
+                                      (int64_t)(uintptr_t)h->ff, (int64_t)(uintptr_t)h->blocks[0].kvi, (int64_t)h->img_L,
+                                      (int64_t)(uintptr_t)h->ff0};
     return graph_run(h->full_guided_graph, key, h->sampler.cap, s, enqueue);
 }

@@ -49,6 +49,16 @@ struct fg_wan : HandleBase {
     int ff_B = 0, ff_F = 0, ff_H = 0, ff_W = 0;  // ff_B == 0: no condition set
     int img_L = 0;                               // image tokens per sample of the condition (0: no image context)
     size_t ff_elems = 0, img_rows = 0;           // what ff / img_tok + kvi are allocated for
+    // fg_wan_create_ti2v: the Wan2.2-TI2V convention (WanI2V/network.py, concat_mask = False, expand_timesteps = True).  No extra
+    // channels and no image keys; the condition (fg_wan_set_first_frame) is frame 0 of the first-frame latents, `ff0`
+    // [B][latent][1][H][W] fp32, owned here and rewritten in place while its shape stays (the loops' graphs name it).  It feeds
+    // frame 0's tokens, frame 0's embedder rows are zero and frame 0 of every result is its copy.
+    bool is_ti2v = false;
+    fg_wan_ti2v_config ti2v{0};
+    float* ff0 = nullptr;
+    int ff0_B = 0, ff0_H = 0, ff0_W = 0;  // ff0_B == 0: no condition set
+    size_t ff0_elems = 0;
+    bool has_first_frame(int batch, int height, int width) const { return ff0_B == batch && ff0_H == height && ff0_W == width; }
     int r1_w = -1, r1_b = -1, r2_w = -1, r2_b = -1, rp_w = -1, rp_b = -1;
     float2 *tab_t = nullptr, *tab_h = nullptr, *tab_w = nullptr;  // RoPE axis tables
     int npt = 0, nph = 0, npw = 0;
@@ -308,9 +318,14 @@ extern "C" {
 }  // extern "C" (reopened below)
 
 namespace {
-// fg_wan_create_ex and fg_wan_create_i2v: one table builder.  i2v == nullptr: the plain network.
-int wan_create(const fg_wan_config* cfg, const fg_wan_ext_config* ext, const fg_wan_i2v_config* i2v, fg_wan** out) {
+// fg_wan_create_ex, fg_wan_create_i2v and fg_wan_create_ti2v: one table builder.  i2v == nullptr: the plain network's table (ti2v
+// adds no parameter).
+int wan_create(const fg_wan_config* cfg, const fg_wan_ext_config* ext, const fg_wan_i2v_config* i2v, fg_wan** out,
+               const fg_wan_ti2v_config* ti2v = nullptr) {
     if (!cfg || !out) return fail(FG_EINVAL, "null argument");
+    if (ti2v && (ti2v->latent_channels <= 0 || cfg->in_channels != ti2v->latent_channels || cfg->out_channels != ti2v->latent_channels))
+        return fail(FG_EINVAL, "in_channels %d and out_channels %d must both equal latent_channels %d", cfg->in_channels, cfg->out_channels,
+                    ti2v->latent_channels);
     if (i2v) {
         if (i2v->mask_channels != 4) return fail(FG_EINVAL, "mask_channels %d unsupported (4 = scale_factor_temporal)", i2v->mask_channels);
         if (i2v->latent_channels <= 0 || cfg->in_channels != 2 * i2v->latent_channels + i2v->mask_channels)
@@ -325,7 +340,8 @@ int wan_create(const fg_wan_config* cfg, const fg_wan_ext_config* ext, const fg_
         return fail(FG_EINVAL, "r_timestep and time_cond_diff must be 0 or 1");
     if (cfg->head_dim != 128) return fail(FG_EINVAL, "head_dim %d unsupported (128)", cfg->head_dim);
     const int D = cfg->num_heads * cfg->head_dim;
-    if (D != 256 && D != 384 && D != 1536 && D != 2048 && D != 5120) return fail(FG_EINVAL, "inner dim %d unsupported (256, 384, 1536, 2048, 5120)", D);
+    if (D != 256 && D != 384 && D != 1536 && D != 2048 && D != 3072 && D != 5120)
+        return fail(FG_EINVAL, "inner dim %d unsupported (256, 384, 1536, 2048, 3072, 5120)", D);
     if (cfg->in_channels <= 0 || cfg->in_channels > 64 || cfg->out_channels <= 0 || cfg->out_channels > 64 || cfg->num_layers <= 0 ||
         (cfg->ffn_dim % 64) || (cfg->text_dim % 64) || cfg->freq_dim != 256 || cfg->rope_max_seq_len <= 0 || cfg->chunk_size <= 0 ||
         cfg->total_num_frames <= 0)
@@ -414,6 +430,7 @@ int wan_create(const fg_wan_config* cfg, const fg_wan_ext_config* ext, const fg_
             if (idx >= 0) h->pack_only[idx] = 1;
     if (Di > 0) h->pack_only[h->if0_w] = h->pack_only[h->if2_w] = 1;
     if (i2v) h->is_i2v = true, h->i2v = *i2v;
+    if (ti2v) h->is_ti2v = true, h->ti2v = *ti2v;
     *out = h;
     return FG_OK;
 }
@@ -426,6 +443,37 @@ int fg_wan_create_ex(const fg_wan_config* cfg, const fg_wan_ext_config* ext, fg_
 int fg_wan_create_i2v(const fg_wan_config* cfg, const fg_wan_ext_config* ext, const fg_wan_i2v_config* i2v, fg_wan** out) {
     if (!i2v) return fail(FG_EINVAL, "null argument");
     return wan_create(cfg, ext, i2v, out);
+}
+
+int fg_wan_create_ti2v(const fg_wan_config* cfg, const fg_wan_ext_config* ext, const fg_wan_ti2v_config* ti2v, fg_wan** out) {
+    if (!ti2v) return fail(FG_EINVAL, "null argument");
+    return wan_create(cfg, ext, nullptr, out, ti2v);
+}
+
+int fg_wan_set_first_frame(fg_wan* h, const float* first_frame, int batch, int height, int width, void* stream) {
+    if (!h || !first_frame) return fail(FG_EINVAL, "null argument");
+    if (!h->is_ti2v) return fail(FG_EINVAL, "not a first-frame-replacement handle (fg_wan_create_ti2v)");
+    if (batch <= 0 || height <= 0 || width <= 0 || (height & 1) || (width & 1)) return fail(FG_EINVAL, "bad batch / size");
+    const size_t elems = (size_t)batch * h->ti2v.latent_channels * height * width;
+    h->ff0_B = 0;  // (nothing valid until the copy is enqueued)
+    if (elems != h->ff0_elems) {
+        h->drop_graphs();
+        h->free(h->ff0);
+        h->ff0 = nullptr, h->ff0_elems = 0;
+        if (int rc = h->alloc((void**)&h->ff0, elems * sizeof(float))) return rc;
+        h->ff0_elems = elems;
+    }
+    HIP_TRY(hipMemcpyAsync(h->ff0, first_frame, elems * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    h->ff0_B = batch, h->ff0_H = height, h->ff0_W = width;
+    return FG_OK;
+}
+
+int fg_wan_first_frame_read(fg_wan* h, float* out, void* stream) {
+    if (!h || !out) return fail(FG_EINVAL, "null argument");
+    if (!h->is_ti2v) return fail(FG_EINVAL, "not a first-frame-replacement handle (fg_wan_create_ti2v)");
+    if (h->ff0_B == 0) return fail(FG_ENOTREADY, "no first frame is set (call fg_wan_set_first_frame)");
+    HIP_TRY(hipMemcpyAsync(out, h->ff0, h->ff0_elems * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    return FG_OK;
 }
 
 void fg_wan_destroy(fg_wan* h) {
@@ -725,13 +773,15 @@ int wan_forward(fg_wan* h, const float* x_t, const float* t_frames, float* out, 
         if (frames > h->cfg.rope_max_seq_len)
             return fail(FG_EINVAL, "%d frames exceed the RoPE table (rope_max_seq_len = %d)", frames, h->cfg.rope_max_seq_len);
     }
-    if (h->is_i2v && !full) return fail(FG_EINVAL, "the chunked / causal calls are not implemented for an image-to-video handle");
+    if ((h->is_i2v || h->is_ti2v) && !full) return fail(FG_EINVAL, "the chunked / causal calls are not implemented for an image-to-video handle");
     if (!h->packed) return fail(FG_ENOTREADY, "weights are not packed (call fg_wan_pack_weights)");
     if (batch <= 0 || frames <= 0 || height <= 0 || width <= 0 || (height & 1) || (width & 1) || !workspace || (((uintptr_t)workspace) & 255))
         return fail(FG_EINVAL, "bad batch / frames / size / workspace");
     if (h->text_B != batch) return fail(FG_ENOTREADY, "no text condition for batch %d (call fg_wan_set_text)", batch);
     if (h->is_i2v && (h->ff_B != batch || h->ff_F != frames || h->ff_H != height || h->ff_W != width))
         return fail(FG_ENOTREADY, "no image-to-video condition for batch %d, %d frames of %d x %d (call fg_wan_set_i2v_cond)", batch, frames, height, width);
+    if (h->is_ti2v && !h->has_first_frame(batch, height, width))
+        return fail(FG_ENOTREADY, "no first frame for batch %d of %d x %d (call fg_wan_set_first_frame)", batch, height, width);
     if (out == x_t) return fail(FG_EINVAL, "out must not alias x_t");
     hipStream_t s = (hipStream_t)stream;
     const fg_wan_config& c = h->cfg;
@@ -762,6 +812,13 @@ int wan_forward(fg_wan* h, const float* x_t, const float* t_frames, float* out, 
         return fail(FG_EINVAL, "store_kv = 0 at frame %d would overwrite cached keys / values (frames [0, %d) are stored): re-evaluating a stored "
                     "chunk without storing it is not implemented", cur_start_frame, h->stored_rows / fs);
     // condition embedder, per frame (:586-590): Timesteps(256) -> Linear - SiLU - Linear; time_proj(silu(temb))
+    const float* t_rows_in = t_frames;  // the caller's rows
+    if (h->is_ti2v) {
+        // expand_timesteps: the embedder sees mask * t per token (Wan/network.py:904-917) with the mask zero on latent frame 0 and
+        // constant within a frame - the per-frame rows with frame 0's at zero (w.st: scratch until the SiLU below writes it)
+        HIP_TRY(launch_wan_ti2v_zero_frame0(t_frames, w.st, BF, frames, s));
+        t_frames = w.st;
+    }
     HIP_TRY(launch_dit_fourier(t_frames, w.tf, BF, c.freq_dim, s));
     HIP_TRY(launch_linear(w.tf, h->P(h->t1_w), h->P(h->t1_b), w.th, BF, c.freq_dim, D, 1, s));
     HIP_TRY(launch_linear(w.th, h->P(h->t2_w), h->P(h->t2_b), w.temb, BF, D, D, 0, s));
@@ -771,7 +828,10 @@ int wan_forward(fg_wan* h, const float* x_t, const float* t_frames, float* out, 
         // r_embedder on r (or t - r), the `encoder_depth is None` branch (Wan/network.py:330-351): temb += remb, timestep_proj +=
         // r_timestep_proj.  Its scratch is the blocks' and the output layer's modulation rows, which nothing has written yet.
         float *rrow = w.mod, *remb = w.omod, *rproj = w.mod;
-        HIP_TRY(launch_wan_r_rows(t_frames, full->r_frames, h->ext.time_cond_diff, rrow, BF, s));
+        // (first-frame replacement: the SiLU has rewritten the zeroed copy of t; the r rows are formed from the caller's values and their
+        // frame 0 zeroed behind them - both masked rows are zero there, and so is their difference)
+        HIP_TRY(launch_wan_r_rows(t_rows_in, full->r_frames, h->ext.time_cond_diff, rrow, BF, s));
+        if (h->is_ti2v) HIP_TRY(launch_wan_ti2v_zero_frame0(rrow, rrow, BF, frames, s));
         HIP_TRY(launch_dit_fourier(rrow, w.tf, BF, c.freq_dim, s));
         HIP_TRY(launch_linear(w.tf, h->P(h->r1_w), h->P(h->r1_b), w.th, BF, c.freq_dim, D, 1, s));
         HIP_TRY(launch_linear(w.th, h->P(h->r2_w), h->P(h->r2_b), remb, BF, D, D, 0, s));
@@ -782,8 +842,9 @@ int wan_forward(fg_wan* h, const float* x_t, const float* t_frames, float* out, 
     HIP_TRY(launch_wan_rope_table(h->tab_t, h->tab_h, h->tab_w, w.cs, L, fs, gw, cur_start_frame, c.rope_max_seq_len, h->npt, h->nph, h->npw, s));
     if (h->is_i2v)  // the virtual concat [x_t | mask | first_frame_cond] (WanI2V/network.py:310-327)
         HIP_TRY(launch_wan_i2v_patch_embed(x_t, h->ff, h->P(h->pe_w), h->P(h->pe_b), w.x0, batch, h->i2v.latent_channels, frames, height, width, D, s));
-    else
-        HIP_TRY(launch_wan_patch_embed(x_t, h->P(h->pe_w), h->P(h->pe_b), w.x0, batch, c.in_channels, frames, height, width, D, s));
+    else  // (first-frame replacement: frame 0's tokens from the condition, `_replace_first_frame` WanI2V/network.py:254-277)
+        HIP_TRY(launch_wan_ti2v_patch_embed(x_t, h->is_ti2v ? h->ff0 : nullptr, h->P(h->pe_w), h->P(h->pe_b), w.x0, batch, c.in_channels, frames,
+                                            height, width, D, 0, s));
     void *x = w.x0, *xn = w.x1;
     int rc;
     const int64_t cbs = (int64_t)cap * D;
@@ -866,7 +927,8 @@ int wan_forward(fg_wan* h, const float* x_t, const float* t_frames, float* out, 
     }
     if (!block_causal && store_kv && cache_start + L > h->stored_rows) h->stored_rows = cache_start + L;
     HIP_TRY(launch_wan_outmod(h->P(h->sst), w.temb, w.omod, BF, D, s));
-    HIP_TRY(launch_wan_final(D, x, w.omod, h->P(h->po_w), h->P(h->po_b), out, M, frames, gh, gw, c.out_channels, c.eps, s));
+    HIP_TRY(launch_wan_ti2v_final(D, x, w.omod, h->P(h->po_w), h->P(h->po_b), h->is_ti2v ? h->ff0 : nullptr, out, M, frames, gh, gw, c.out_channels,
+                                  c.eps, 0, s));
     return FG_OK;
 }
 }  // namespace

@@ -282,3 +282,14 @@ int launch_wan_i2v_patch_embed(const float* x, const float* ff, const float* w, 
 // fp32 LayerNorm (affine) of rows [rows][n] (fp32, or bf16 when in_bf16) into bf16; exact (erf) GELU in place on n bf16 values
 int launch_wan_ln_rows(int in_bf16, const void* x, const float* w, const float* b, void* y, int rows, int n, float eps, hipStream_t s);
 int launch_wan_gelu_erf(void* x, int64_t n, hipStream_t s);
+// wan_ti2v.hip: the two ends of the network at 48 latent channels (Wan2.2 TI2V-5B) and the first-frame replacement of that model's
+// image-to-video convention (reference fastgen/networks/WanI2V/network.py, concat_mask = False).  ff0 (nullable) [B][C][1][H][W]: the
+// source of frame 0's tokens / of frame 0 of the head's result.  path 0: the launcher's choice - the tiled kernels at C == 48, else
+// the kernels of wan.hip (launch_wan_patch_embed / launch_wan_final; with ff0 the per-output embedding with the second source, and a
+// copy of ff0 behind the head); 1: never the tiled kernels; 2: the tiled kernels or hipErrorInvalidValue.
+int launch_wan_ti2v_patch_embed(const float* x, const float* ff0, const float* w, const float* bias, void* out, int B, int C, int Fr, int H, int W,
+                                int D, int path, hipStream_t s);
+int launch_wan_ti2v_final(int D, const void* x, const float* mod, const float* w, const float* bias, const float* ff0, float* out, int ntok, int Fr,
+                          int gh, int gw, int C, float eps, int path, hipStream_t s);
+// dst[i] = i % Fr == 0 ? 0 : src[i] over n = rows of (sample, frame): the embedder rows under the first-frame mask (in place allowed)
+int launch_wan_ti2v_zero_frame0(const float* src, float* dst, int n, int Fr, hipStream_t s);

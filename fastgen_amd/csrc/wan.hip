@@ -1443,7 +1443,7 @@ int launch_wan_rope_table(const float2* tab_t, const float2* tab_h, const float2
     hipLaunchKernelGGL(wan_rope_table_kernel, dim3((n + 255) / 256), dim3(256), 0, s, tab_t, tab_h, tab_w, cs, L, fs, gw, start, S, nt, nh, nw);
     WAN_RET();
 }
-// D = 128 NP with NP in {2, 3, 12, 16, 40} (256, 384, 1536 = the 1.3B network, 2048, 5120 = the 14B network)
+// D = 128 NP with NP in {2, 3, 12, 16, 24, 40} (256, 384, 1536 = the 1.3B network, 2048, 3072 = the 5B network, 5120 = the 14B network)
 int launch_rms_rope(int D, const void* src, int ld_src, const float* w, float eps, const float2* cs, void* dst, int64_t dst_bs, int dst_row0,
                     int ld_dst, int rows, int L, hipStream_t s) {
     dim3 g((rows + 3) / 4), b(256);
@@ -1453,6 +1453,7 @@ int launch_rms_rope(int D, const void* src, int ld_src, const float* w, float ep
         case 384: RR(3); break;
         case 1536: RR(12); break;
         case 2048: RR(16); break;
+        case 3072: RR(24); break;
         case 5120: RR(40); break;
         default: return (int)hipErrorInvalidValue;
     }
@@ -1628,6 +1629,7 @@ int launch_wan_final(int D, const void* x, const float* mod, const float* w, con
         case 384: WF(3); break;
         case 1536: WF(12); break;
         case 2048: WF(16); break;
+        case 3072: WF(24); break;
         case 5120: WF(40); break;
         default: return (int)hipErrorInvalidValue;
     }

@@ -82,7 +82,9 @@ class FastGenModel:
                 t_list = torch.tensor(t_list, dtype=net.noise_scheduler.t_precision)
             assert t_list[-1].item() == 0, "t_list[-1] must be zero"
             fused = (getattr(net, "supports_fused_loop", lambda k: False)(cls._fused_loop) and data is None
-                     and (not hasattr(net, "preserve_conditioning") or getattr(net, "preserve_conditioning_is_identity", False))
+                     # (a hook the fused loop has no call for: absent, the identity, or restated by the network's own fused loop)
+                     and (not hasattr(net, "preserve_conditioning") or getattr(net, "preserve_conditioning_is_identity", False)
+                          or getattr(net, "fused_loop_preserves_conditioning", False))
                      and cls._student_sample_loop.__func__ in _FUSED_LOOPS)
             if fused:
                 kw = dict(kwargs)

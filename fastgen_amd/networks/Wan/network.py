@@ -10,7 +10,11 @@ restates it, tests/wan_full_ref.py composes this network from it); the six `tran
 their order behind `transformer.logvar_linear.*` are read from `init_embedder` (Wan/network.py:799-834), not recorded from a run; the
 solver of `sample` restates diffusers' UniPC (Wan/solvers.py).
 
-Raises (never falls back): autograd, feature taps, logvar, `norm_temb`, `encoder_depth`, per-token timesteps (Wan2.2 TI2V), image
+`expand_timesteps=True` (Wan2.2 TI2V-5B as a text-to-video network: 24 heads, 48 channels, ffn 14336) is accepted and changes nothing:
+the reference then hands the embedder one timestep per token, `mask * t` with a mask of ones (Wan/network.py:904-917) - every token of
+a sample sees t, which is what the engine's per-frame rows hold already.
+
+Raises (never falls back): autograd, feature taps, logvar, `norm_temb`, `encoder_depth`, timesteps given per token by the caller, image
 conditioning (a condition dict: that is `fastgen_amd.networks.WanI2V.network.WanI2V`), skip-layer guidance inside `sample()`
 (`forward(skip_layers=...)` serves it), any device but a HIP GPU.
 `compute_dtype`: as on `CausalWan` (None / "bf16" / "fp8")."""
@@ -36,8 +40,9 @@ class Wan(WanEngineNetwork):
                  text_dim: int = 4096, freq_dim: int = 256, ffn_dim: int = 8960, num_layers: int = 30, eps: float = 1e-6,
                  rope_max_seq_len: int = 1024, r_timestep: bool = False, time_cond_type: str = "diff", r_embedder_init: str = "pretrained",
                  net_pred_type: str = "flow", schedule_type: str = "rf", enable_logvar_linear: bool = True, *,
-                 compute_dtype: Optional[str] = None, **model_kwargs):
+                 compute_dtype: Optional[str] = None, expand_timesteps: bool = False, **model_kwargs):
         self._check_compute_dtype(compute_dtype, ffn_dim, "bidirectional video DiT")
+        self.expand_timesteps = bool(expand_timesteps)  # (see the module docstring: the rows are per frame and the mask is ones)
         self._pop_reference_knobs(model_kwargs, keep=("r_embedder_init", "time_cond_type"))
         if model_kwargs.pop("use_wan_official_sinusoidal", False):
             raise NotImplementedError("use_wan_official_sinusoidal=True is not implemented")
@@ -121,14 +126,15 @@ class Wan(WanEngineNetwork):
             fwd_pred_type = self.net_pred_type
         else:
             assert fwd_pred_type in NET_PRED_TYPES, f"{fwd_pred_type} is not supported as fwd_pred_type"
+        dev = x_t.device
+        t_in = torch.atleast_1d(t.detach()).to(dev)
+        if t_in.ndim != 1:
+            raise NotImplementedError(f"t must be [B] (timesteps given per token, [B, seq_len], are not implemented: expand_timesteps "
+                                      f"expands a [B] t inside the network), got {tuple(t_in.shape)}")
         self._no_autograd(x_t)
         _engine.require_gpu(x_t)
         condition = self._text(condition)
         B, F, H, W = self._check_video(x_t, "x_t")
-        dev = x_t.device
-        t_in = torch.atleast_1d(t.detach()).to(dev)
-        if t_in.ndim != 1:
-            raise NotImplementedError(f"t must be [B] (per-token timesteps, Wan2.2 TI2V, are not implemented), got {tuple(t_in.shape)}")
         skip = sorted(set(int(i) for i in skip_layers)) if skip_layers else []
         if skip and (skip[0] < 0 or skip[-1] >= self.num_layers):
             raise ValueError(f"skip_layers must be block indices in [0, {self.num_layers}), got {list(skip_layers)}")

@@ -12,8 +12,15 @@ PARITY UNPINNED like `Wan`; in addition the thirteen image keys (`transformer.co
 `attn2.add_k_proj.*`, `attn2.add_v_proj.*`, `attn2.norm_added_k.weight`) and their order are read from the reference's key map
 (Wan/network.py:1029-1049) and diffusers' module order, not recorded from a run.
 
-Raises (never falls back): everything `Wan` raises, the Wan2.2-TI2V convention (`concat_mask=False`, `expand_timesteps=True`), the image
-embedder's `pos_embed` (FLF2V)."""
+The Wan2.2-TI2V convention (`concat_mask=False, use_image_encoder=False, expand_timesteps=True`: Wan2.2-TI2V-5B, the network of
+configs/experiments/WanI2V/config_{dmd2,sft}_wan22_5b.py) runs on `fg_wan_create_ti2v` / `fg_wan_set_first_frame`: `Wan`'s state dict (no
+image keys), `in_channels == out_channels` (48), the condition `{"text_embeds", "first_frame_cond"}` with `first_frame_cond`
+[B, C, 1, H, W] (or [B, C, F, H, W], of which only frame 0 is read).  Frame 0 of the network's input is the condition's, frame 0's
+timestep (and r) is zero, frame 0 of every result - `forward` whatever `fwd_pred_type`, `few_step_sample`, `sample` - is the condition's,
+and `preserve_conditioning` does the replacement.  PARITY UNPINNED like everything here.
+
+Raises (never falls back): everything `Wan` raises, any other mixture of the three flags, the MeanFlow loop on the TI2V convention, the
+image embedder's `pos_embed` (FLF2V)."""
 from __future__ import annotations
 
 import weakref
@@ -34,16 +41,39 @@ class WanI2V(Wan):
     # the reference's hook returns x unchanged under concat_mask (the first frame is part of the network's input, not of the latents):
     # FastGenModel.generator_fn may keep the fused loop
     preserve_conditioning_is_identity = True
+    # (an instance attribute, False, on the Wan2.2 TI2V convention, where the hook replaces frame 0.)  There the engine replaces it too:
+    # the network reads the condition in frame 0's place and every prediction carries it, which leaves the hook's effect on
+    # intermediate states unobservable in the result (tests/test_gpu_wan_ti2v.py: bit-equal to the generic loop), so
+    # FastGenModel.generator_fn keeps the fused loop for a network that sets this
+    fused_loop_preserves_conditioning = True
 
     def __init__(self, num_attention_heads: int = 40, attention_head_dim: int = 128, in_channels: int = 36, out_channels: int = 16,
                  text_dim: int = 4096, freq_dim: int = 256, ffn_dim: int = 13824, num_layers: int = 40, image_dim: Optional[int] = 1280,
                  concat_mask: bool = True, use_image_encoder: bool = True, expand_timesteps: bool = False, pos_embed_seq_len: Optional[int] = None,
                  **kwargs):
-        if not concat_mask or expand_timesteps:
-            raise NotImplementedError("the Wan2.2 TI2V convention (concat_mask=False, expand_timesteps=True: first-frame replacement and "
-                                      "per-token timesteps) is not implemented; WanI2V serves Wan2.1 I2V (concat_mask=True)")
+        flags = (bool(concat_mask), bool(use_image_encoder), bool(expand_timesteps))
+        self.is_ti2v = flags == (False, False, True)
+        if not self.is_ti2v and (not concat_mask or expand_timesteps):
+            raise NotImplementedError(f"concat_mask={concat_mask}, use_image_encoder={use_image_encoder}, expand_timesteps={expand_timesteps} is "
+                                      "not implemented: WanI2V serves Wan2.1 I2V (concat_mask=True, expand_timesteps=False) and Wan2.2 TI2V "
+                                      "(concat_mask=False, use_image_encoder=False, expand_timesteps=True)")
         if pos_embed_seq_len is not None:
             raise NotImplementedError("pos_embed of the image embedder (pos_embed_seq_len, FLF2V) is not implemented")
+        if self.is_ti2v:
+            if in_channels != out_channels:
+                raise ValueError(f"Wan2.2 TI2V: in_channels {in_channels} must equal out_channels {out_channels} (no mask or condition channels)")
+            if image_dim:
+                raise ValueError(f"Wan2.2 TI2V has no image encoder: image_dim must be None, got {image_dim}")
+            ti2v = _lib.fg_wan_ti2v_config()
+            ti2v.latent_channels = out_channels
+            self._i2v_cfg, self._ti2v_cfg, self._i2v_key = None, ti2v, None
+            self.concat_mask, self.use_image_encoder, self.image_dim, self.latent_channels = False, False, 0, out_channels
+            self.preserve_conditioning_is_identity, self.fused_loop_preserves_conditioning = False, True
+            super().__init__(num_attention_heads=num_attention_heads, attention_head_dim=attention_head_dim, in_channels=in_channels,
+                             out_channels=out_channels, text_dim=text_dim, freq_dim=freq_dim, ffn_dim=ffn_dim, num_layers=num_layers,
+                             expand_timesteps=True, **kwargs)
+            return
+        self._ti2v_cfg = None
         i2v = _lib.fg_wan_i2v_config()
         i2v.latent_channels, i2v.mask_channels, i2v.image_dim = out_channels, _MASK_CHANNELS, int(image_dim or 0)
         self._i2v_cfg, self._i2v_key = i2v, None
@@ -53,11 +83,16 @@ class WanI2V(Wan):
                          out_channels=out_channels, text_dim=text_dim, freq_dim=freq_dim, ffn_dim=ffn_dim, num_layers=num_layers, **kwargs)
 
     def _build_engine(self, **kw) -> None:
-        super()._build_engine(i2v=self._i2v_cfg, **kw)
+        super()._build_engine(i2v=self._i2v_cfg, ti2v=self._ti2v_cfg, **kw)
 
     # ---- the reference's surface -------------------------------------------------------------------------------------------
     def preserve_conditioning(self, x: torch.Tensor, condition: Any) -> torch.Tensor:
-        """`WanI2V.preserve_conditioning` under concat_mask: the latents carry no conditioning frame, x is returned as it is."""
+        """`WanI2V.preserve_conditioning` (WanI2V/network.py:228-252).  Under concat_mask the latents carry no conditioning frame and x is
+        returned as it is; Wan2.2 TI2V: a clone of x with frame 0 set from the condition's `first_frame_cond`."""
+        if self.concat_mask or not isinstance(condition, dict) or "first_frame_cond" not in condition:
+            return x
+        x = x.clone()
+        x[:, :, 0] = condition["first_frame_cond"][:, :, 0].to(device=x.device, dtype=x.dtype)
         return x
 
     # ---- the condition -----------------------------------------------------------------------------------------------------
@@ -79,8 +114,22 @@ class WanI2V(Wan):
         super()._forget_text()
         self._i2v_key = None  # packing invalidates the image-to-video condition together with the text
 
+    def _set_first_frame(self, ff: torch.Tensor, B: int, F: int, H: int, W: int, dev) -> None:
+        """Wan2.2 TI2V: frame 0 of `first_frame_cond` into the handle, once per (tensor object, version, shape) as `_set_text`."""
+        C = self.latent_channels
+        if ff.ndim != 5 or tuple(ff.shape[:2]) != (B, C) or ff.shape[2] not in (1, F) or tuple(ff.shape[3:]) != (H, W):
+            raise ValueError(f"first_frame_cond must be {(B, C, 1, H, W)} (or {(B, C, F, H, W)}: only frame 0 is read), got {tuple(ff.shape)}")
+        key = (weakref.ref(ff), 0 if ff.is_inference() else ff._version, tuple(ff.shape))
+        if self._i2v_key is not None and self._i2v_key[0]() is ff and self._i2v_key[1:] == key[1:]:
+            return
+        ff32 = ff.detach()[:, :, :1].to(device=dev, dtype=torch.float32).contiguous()
+        _lib.check(_lib.lib().fg_wan_set_first_frame(self._h, ptr(ff32), B, H, W, self._stream(dev)))
+        self._i2v_key = key
+
     def _set_i2v(self, ff: torch.Tensor, image: Optional[torch.Tensor], B: int, F: int, H: int, W: int, dev) -> None:
         """First-frame latents and image tokens into the handle, once per (tensor objects, versions, shapes) as `_set_text`."""
+        if self.is_ti2v:
+            return self._set_first_frame(ff, B, F, H, W, dev)
         if self.image_dim == 0 or not self.use_image_encoder:
             image = None
         if tuple(ff.shape) != (B, self.latent_channels, F, H, W):
@@ -122,7 +171,16 @@ class WanI2V(Wan):
             raise NotImplementedError("feature taps / logvar are not implemented for the bidirectional video DiT path")
         self._no_autograd(x_t)
         self._prepare(x_t, "x_t", ff, image)
-        return super().forward(x_t, t, condition=text, r=r, **kwargs)
+        out = super().forward(x_t, t, condition=text, r=r, **kwargs)
+        if self.is_ti2v:
+            # `_replace_first_frame` behind convert_model_output (WanI2V/network.py:506-510): the conversion ran on the caller's x_t, the
+            # condition's frame 0 lands last whatever fwd_pred_type is (the engine wrote it into the raw output already)
+            out[:, :, 0] = ff[:, :, 0].to(device=out.device, dtype=out.dtype)
+        return out
+
+    def supports_fused_loop(self, kind: str) -> bool:
+        # (the MeanFlow loop would write the first-frame latents into a velocity: refused by the engine on this convention)
+        return super().supports_fused_loop(kind) and not (self.is_ti2v and kind == "meanflow")
 
     def few_step_sample(self, noise: torch.Tensor, condition: Any, t_list, **kwargs) -> torch.Tensor:
         """`Wan.few_step_sample` under the image-to-video condition: one `fg_wan_full_sampler_run` / one hipGraph replay.  New
@@ -136,9 +194,12 @@ class WanI2V(Wan):
     def sample(self, noise: torch.Tensor, condition: Optional[Dict[str, torch.Tensor]] = None,
                neg_condition: Optional[Dict[str, torch.Tensor]] = None, guidance_scale: Optional[float] = 5.0, num_steps: int = 40,
                shift: float = 3.0, skip_layers: Optional[List[int]] = None, skip_layers_start_percent: float = 0.0, **kwargs) -> torch.Tensor:
-        """`WanI2V.sample` (WanI2V/network.py:344-419, concat_mask: no first-frame replacement) over `Wan.sample`'s one call: when
-        guided, the stacked batch [x; x] runs against the text, first frame and image tokens of [condition; neg_condition]."""
+        """`WanI2V.sample` (WanI2V/network.py:344-419) over `Wan.sample`'s one call: when guided, the stacked batch [x; x] runs against
+        the text, first frame and image tokens of [condition; neg_condition].  Wan2.2 TI2V: frame 0 of the latents is `condition`'s
+        after every solver step (the engine restores it), so the returned latents carry it."""
         text, ff, image = self._unpack(condition)
+        if self.is_ti2v:
+            ff = ff[:, :, :1]  # (only frame 0 is read; the stacked tensor below is a fresh one either way)
         guided = guidance_scale is not None and neg_condition is not None
         neg_text = None
         if guided:
@@ -146,7 +207,7 @@ class WanI2V(Wan):
             if (image is None) != (nimage is None):
                 raise ValueError("condition and neg_condition must both carry encoder_hidden_states_image, or neither")
             dev = noise.device
-            ff = torch.cat([ff.to(dev), nff.to(dev)], dim=0)
+            ff = torch.cat([ff.to(dev), (nff[:, :, :1] if self.is_ti2v else nff).to(dev)], dim=0)
             image = None if image is None else torch.cat([image.to(dev), nimage.to(dev)], dim=0)
         self._prepare(noise, "noise", ff, image, stack=2 if guided else 1)
         try:

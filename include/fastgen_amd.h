@@ -604,7 +604,7 @@ FG_API int fg_dit_sampler_run(fg_dit* h, const fg_dit_sampler_config* cfg, const
  * restatement in oracle/wan_ref.py - PARITY UNPINNED.  bf16 token tensors and GEMM operands with fp32 accumulation,
  * fp32 norms / softmax / modulation: the reference runs this network in bf16 (configs/experiments/WanT2V/config_sf.py:19).
  * fg_wan_config = the fields of the transformer's config the path reads.  Supported: head_dim 128, inner dim (heads x 128) in
- * {256, 384, 1536 (1.3B), 2048, 5120 (14B)}, patch (1,2,2), ffn_dim / text_dim % 64 == 0, freq_dim 256, cross_attn_norm.
+ * {256, 384, 1536 (1.3B), 2048, 3072 (5B), 5120 (14B)}, patch (1,2,2), ffn_dim / text_dim % 64 == 0, freq_dim 256, cross_attn_norm.
  * compute_dtype FG_DTYPE_FP8: the six linears of a block that read the video tokens - attn1 to_q | to_k | to_v (one fused GEMM),
  * attn1.to_out.0, attn2.to_q, attn2.to_out.0, ffn.net.0.proj, ffn.net.2 - run on e4m3fn operands (FG_DTYPE_FP8 above: weights
  * re-quantised per output channel on every pack, the LayerNorm-modulate outputs, the two attention outputs and the GELU hidden
@@ -809,8 +809,8 @@ FG_API int fg_wan_full_guided_sampler_run(fg_wan* h, const fg_wan_guided_sampler
  * take x_t / noise / x with latent_channels channels and need the condition set for the batch and (frames, height, width) of the
  * call (FG_ENOTREADY otherwise; the guided loop runs at 2 B: set text and condition for [cond; neg_cond]); the chunked and causal
  * entry points (fg_wan_forward, fg_wan_forward_block_causal, fg_wan_forward_features in those modes, fg_wan_sampler_run,
- * fg_wan_guided_sampler_run) return FG_EINVAL "not implemented for an image-to-video handle".  Not implemented: the Wan2.2-TI2V
- * convention (concat_mask = False, expanded timesteps), the image embedder's pos_embed (FLF2V). */
+ * fg_wan_guided_sampler_run) return FG_EINVAL "not implemented for an image-to-video handle".  The Wan2.2-TI2V convention
+ * (concat_mask = False, expanded timesteps) is fg_wan_create_ti2v below.  Not implemented: the image embedder's pos_embed (FLF2V). */
 typedef struct fg_wan_i2v_config {
     int latent_channels;   /* 16: channels of x_t and of first_frame_cond */
     int mask_channels;     /* 4 (scale_factor_temporal): anything else FG_EINVAL */
@@ -832,6 +832,29 @@ FG_API int fg_wan_set_i2v_cond(fg_wan* h, const float* first_frame_cond, const f
 /* Exposed for the parity tests: fp32 copies of the condition's embedded image tokens [B, image_len, D] and of block `block`'s k_img /
  * v_img [B, image_len, D] each (all nullable).  FG_ENOTREADY without an image context.  Synchronises the stream. */
 FG_API int fg_wan_i2v_cond_read(fg_wan* h, int block, float* img_tokens, float* k_img, float* v_img, void* stream);
+/* Wan2.2 TI2V-5B's image-to-video convention on the bidirectional network (reference fastgen/networks/WanI2V/network.py `WanI2V` with
+ * concat_mask = False, use_image_encoder = False, expand_timesteps = True).  PARITY UNPINNED like the rest of fg_wan_*.  Parameter
+ * table: exactly fg_wan_create_ex's (no image keys).  FG_EINVAL unless cfg->in_channels == cfg->out_channels == latent_channels.
+ * The condition is frame 0 of the first-frame latents (fg_wan_set_first_frame).  On such a handle fg_wan_forward_full,
+ * fg_wan_forward_full_features, fg_wan_full_sampler_run (FG_LOOP_X0) and fg_wan_full_guided_sampler_run
+ *   - read frame 0's tokens from the condition instead of x_t (`_replace_first_frame`; the replaced latents are never formed),
+ *   - zero the t and r embedder rows of frame 0 (the expanded per-token timesteps `mask * t` are constant within a latent frame, so
+ *     they are the per-frame rows with frame 0's at zero),
+ *   - write the condition into frame 0 of their result: of the network output (forward: a caller that converts the prediction type
+ *     writes the condition's frame 0 again behind its conversion, as the reference does), of every x0 prediction of the x0 loop and of
+ *     the latents after every solver step of the guided loop.
+ * FG_ENOTREADY without a condition for the call's batch and size (the guided loop runs at 2 B: [cond; neg_cond]).  FG_EINVAL: the
+ * chunked and causal entry points, and FG_LOOP_MEANFLOW (there the reference writes latents into a velocity, which a fused loop does
+ * not reproduce). */
+typedef struct fg_wan_ti2v_config {
+    int latent_channels;   /* 48: channels of x_t, of the result and of the first-frame condition */
+} fg_wan_ti2v_config;
+FG_API int fg_wan_create_ti2v(const fg_wan_config* cfg, const fg_wan_ext_config* ext /* nullable */, const fg_wan_ti2v_config* ti2v, fg_wan** out);
+/* first_frame [batch, latent_channels, 1, height, width] fp32 (device) is copied into a buffer of the handle, rewritten in place while
+ * the shape stays (a captured loop replays on the new contents) and reallocated otherwise.  FG_EINVAL on any other handle. */
+FG_API int fg_wan_set_first_frame(fg_wan* h, const float* first_frame, int batch, int height, int width, void* stream);
+/* Exposed for the tests: the handle's copy into out [batch, latent_channels, 1, height, width].  FG_ENOTREADY before a condition is set. */
+FG_API int fg_wan_first_frame_read(fg_wan* h, float* out, void* stream);
 /* One step of that solver, in place (misc.hip guided_multistep_kernel): with the eight DEVICE doubles tab = {s, g, c0, c1, c2, p0, p1, p2}
  * each rounded once to fp32, v = guided ? v[total + i] + g (v[i] - v[total + i]) : v[i]; m = x - s v; x_corr = c0 x_last + c1 m_prev +
  * c2 m (first != 0: x_last := x, m_prev := m, neither buffer is read); x_next = p0 x_corr + p1 m_prev + p2 m; then x <- x_next (and
@@ -910,6 +933,18 @@ FG_API int fg_op_attention_ex(const void* q, int ldq, int64_t q_bs, const void* 
 FG_API int fg_op_wan_dual_cross_attention(const void* q, int ldq, int64_t q_bs, const void* k_txt, const void* v_txt, int ldk_txt,
                                           int64_t kv_bs_txt, int l_txt, const void* k_img, const void* v_img, int ldk_img, int64_t kv_bs_img,
                                           int l_img, void* out, int ldo, int64_t o_bs, int batch, int heads, int lq, void* stream);
+/* The two ends of the video DiT on their own (wan.hip / wan_ti2v.hip), for the per-element tests and timing.  first_frame (nullable)
+ * [batch, channels, 1, height, width]: the second source - frame 0's tokens are computed from it / frame 0 of the head's result is
+ * its copy.  path 0: what the engine launches (channels == 48: the tiled kernels of wan_ti2v.hip), 1: never the tiled kernels
+ * (the per-output embedding / the wave-per-token head of wan.hip), 2: the tiled kernels, FG_EINVAL where they do not apply.
+ * fg_op_wan_patch_embed: x [batch, channels, frames, height, width] fp32, w [d, channels, 1, 2, 2], bias [d] -> tokens bf16
+ * [batch, frames * height/2 * width/2, d].  fg_op_wan_final: tokens bf16 [batch * frames * gh * gw, d], mod [batch * frames][2][d]
+ * {shift, scale}, w [4 * channels, d], bias [4 * channels] -> out fp32 [batch, channels, frames, 2 gh, 2 gw]; d in {256, 384, 1536,
+ * 2048, 3072, 5120} for the head of wan.hip, d % 32 == 0 for the tiled one. */
+FG_API int fg_op_wan_patch_embed(const float* x, const float* first_frame, const float* w, const float* bias, void* out, int batch, int channels,
+                                 int frames, int height, int width, int d, int path, void* stream);
+FG_API int fg_op_wan_final(const void* tokens, const float* mod, const float* w, const float* bias, const float* first_frame, float* out, int batch,
+                           int channels, int frames, int gh, int gw, int d, float eps, int path, void* stream);
 /* The transformer blocks' token GEMM in the bf16 compute mode (gemm.hip; reference: the nn.Linear calls of DiTBlock,
  * fastgen/networks/DiT/network.py:168-198, under bf16 autocast): out[m][n] = resid[m][n] + gate[(m / gate_rows) * gate_stride + n] *
  * act(sum_k a[m][k] w[n][k] + bias[n]) with a [m][k], w [n][k], resid / out [m][n] in bf16, fp32 accumulation, bias / gate fp32;
@@ -974,7 +1009,7 @@ FG_API int fg_op_gemm_fp8(const void* a, const void* w, const float* bias, void*
 /* LayerNorm (eps 1e-6, no affine) + adaLN modulation with the quantising store of the fp8 mode (dit.hip): y = LN(x[tok]) * (1 +
  * mod[n][scale_off + c]) + mod[n][shift_off + c], n = tok / tokens_per_image, written as e4m3fn bytes y [ntok][d] + y_scale [ntok]
  * (the scheme of fg_op_quant_rows_fp8 applied to the fp32 y).  x bf16 [ntok][d]; d in {384, 768, 1024, 1152} (DiT) or {256, 1536,
- * 2048, 5120} (the causal video DiT, tokens_per_image = tokens per frame); mod_stride and the offsets multiples of 4. */
+ * 2048, 3072, 5120} (the causal video DiT, tokens_per_image = tokens per frame); mod_stride and the offsets multiples of 4. */
 FG_API int fg_op_dit_ln_modulate_fp8(const void* x, const float* mod, int mod_stride, int shift_off, int scale_off, void* y, float* y_scale,
                                      int ntok, int d, int tokens_per_image, void* stream);
 /* The same token GEMM in the split-bf16 (FG_DTYPE_BF16X3) mode, the DiT's default: a [m][k] and w [n][k] fp32 are split into bf16

@@ -3,7 +3,12 @@ Wan2.1-T2V-1.3B, latents [16, 21, 60, 104] = 480p, chunk of 3 frames, t_list of 
 chunk k (4680 query tokens over (3 k + 3) * 1560 cached + own keys), and the whole 21-frame 4-step loop (7 chunks x (4 + 1) calls).
 Random-init weights of the 1.3B architecture, synthetic latents and text embeddings.
     python scripts/wan_bench.py [--layers=30] [--loop] [--compute-dtype=bf16[,fp8]] [--case=chunks|bc|guided] [--chunks=0,6]
-                                [--widths=1.3b|14b] [--trace=CALLS] [--bidirectional] [--i2v]
+                                [--widths=1.3b|14b] [--trace=CALLS] [--bidirectional] [--i2v] [--ti2v [--first-frame=both|yes|no]]
+--ti2v: Wan2.2-TI2V-5B (configs/experiments/Wan{T2V,I2V}/config_*_wan22_5b.py: 24 heads x 128, 48 latent channels, ffn 14336, 30 layers)
+  on latents [1, 48, 21, 44, 80] (18 480 tokens): one forward and the 2-step x0 student loop t_list = [0.999, 0.833, 0.0] (one hipGraph)
+  per arm, as the text-to-video network `Wan(expand_timesteps=True)` ("no first frame") and as the image-to-video network
+  `WanI2V(concat_mask=False, ...)` ("first frame").  Random weights, no checkpoint, parity unpinned.  --trace=CALLS: one arm, one
+  network (--first-frame=yes|no), one warm-up + CALLS forwards and nothing else, for `rocprofv3 --kernel-trace --stats`.
 --i2v (with --bidirectional): the image-to-video network `WanI2V` (fastgen_amd/networks/WanI2V/network.py: 36 input channels, 257 CLIP
   image tokens of width 1280) next to `Wan` of the same widths and depth in the same run, one call at [1,16,21,60,104] each: the cost of
   the image branch (the dual cross-attention, the two-source patch embedding) is the difference of the two numbers.  Also the call
@@ -38,13 +43,18 @@ ARMS = _opt("compute-dtype", "bf16").split(",")
 CASE = _opt("case", "chunks")
 CHUNKS = [int(c) for c in _opt("chunks", "0,1,2,3,4,5,6").split(",")]
 TRACE = int(_opt("trace", "0"))
+TI2V = "--ti2v" in sys.argv
+FIRST_FRAME = _opt("first-frame", "both")
+assert FIRST_FRAME in ("both", "yes", "no") and (not (TI2V and TRACE) or FIRST_FRAME != "both")
+if TI2V and not any(a.startswith("--layers=") for a in sys.argv[1:]):
+    LAYERS = 30
 assert WIDTHS in ("1.3b", "14b") and CASE in ("chunks", "bc", "guided") and all(a in ("bf16", "fp8") for a in ARMS) and (not TRACE or len(ARMS) == 1)
 H, Fd = (12, 8960) if WIDTHS == "1.3b" else (40, 13824)
 D, fs, Lt = H * 128, 1560, 512
 B = 2 if CASE == "guided" else 1
 
 nets = {}
-for arm in ([] if "--i2v" in sys.argv else ARMS):
+for arm in ([] if "--i2v" in sys.argv or TI2V else ARMS):
     torch.manual_seed(0)  # the same weights in every arm
     nets[arm] = CausalWan(num_attention_heads=H, ffn_dim=Fd, num_layers=LAYERS, compute_dtype=arm).cuda().eval()
 x = torch.randn(B, 16, 21, 60, 104, device="cuda")
@@ -80,6 +90,40 @@ def side_by_side(label, fns, n, gf=None, rounds=3):
     print(f"{label}: " + "   ".join(parts) + ratio, flush=True)
     return med
 
+
+if TI2V:
+    from fastgen_amd.methods.model import FastGenModel
+    from fastgen_amd.networks.Wan.network import Wan
+    from fastgen_amd.networks.WanI2V.network import WanI2V
+
+    KW5B = dict(num_attention_heads=24, attention_head_dim=128, in_channels=48, out_channels=48, ffn_dim=14336, num_layers=LAYERS)
+    x5 = torch.randn(1, 48, 21, 44, 80, device="cuda")
+    ff5 = torch.randn(1, 48, 1, 44, 80, device="cuda")
+    text1, t1 = text[:1], t[:1]
+    print(f"Wan2.2-TI2V-5B widths, {LAYERS} layers, latents {tuple(x5.shape)}, 18480 tokens: random weights, no checkpoint, parity unpinned")
+    for arm in ARMS:
+        for first in (("no", "yes") if FIRST_FRAME == "both" else (FIRST_FRAME,)):
+            torch.manual_seed(0)
+            if first == "yes":
+                net = WanI2V(concat_mask=False, use_image_encoder=False, expand_timesteps=True, image_dim=None, compute_dtype=arm, **KW5B)
+                cond = {"text_embeds": text1, "first_frame_cond": ff5}
+            else:
+                net = Wan(expand_timesteps=True, compute_dtype=arm, **KW5B)
+                cond = text1
+            net = net.cuda().eval()
+            with torch.inference_mode():
+                fwd = lambda: net(x5, t1, condition=cond, fwd_pred_type="flow")  # noqa: E731
+                if TRACE:
+                    window(fwd, 1 + TRACE)
+                else:
+                    label = f"{arm}, {'first frame' if first == 'yes' else 'no first frame'}"
+                    side_by_side(f"{label}: one forward", {arm: fwd}, 2)
+                    side_by_side(f"{label}: 2-step x0 student loop (2 network calls, one graph)",
+                                 {arm: lambda: FastGenModel.generator_fn(net, x5, student_sample_steps=2, t_list=[0.999, 0.833, 0.0], condition=cond,
+                                                                         student_sample_type="sde", seed=1)}, 2)
+            del net
+            torch.cuda.empty_cache()
+    sys.exit(0)
 
 if "--bidirectional" in sys.argv and "--i2v" in sys.argv:
     from fastgen_amd.networks.Wan.network import Wan
