@@ -66,6 +66,10 @@ class fg_wan_ti2v_config(ctypes.Structure):
     _fields_ = [("latent_channels", c_int)]
 
 
+class fg_wan_vace_config(ctypes.Structure):
+    _fields_ = [("vace_in_channels", c_int), ("num_vace_layers", c_int), ("vace_layers", c_int * 64)]
+
+
 class fg_wan_block_taps(ctypes.Structure):
     _fields_ = [("attn1", c_void_p), ("x_attn1", c_void_p), ("attn2", c_void_p), ("x_attn2", c_void_p), ("x_ffn", c_void_p)]
 
@@ -260,6 +264,12 @@ SIGNATURES = {
     "fg_wan_create_ti2v": (c_int, [POINTER(fg_wan_config), POINTER(fg_wan_ext_config), POINTER(fg_wan_ti2v_config), POINTER(c_void_p)]),
     "fg_wan_set_first_frame": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
     "fg_wan_first_frame_read": (c_int, [c_void_p, c_void_p, c_void_p]),
+    "fg_wan_create_vace": (c_int, [POINTER(fg_wan_config), POINTER(fg_wan_ext_config), POINTER(fg_wan_vace_config), POINTER(c_void_p)]),
+    "fg_wan_set_vace_scale": (c_int, [c_void_p, POINTER(c_float), c_int, c_void_p]),
+    "fg_wan_vace_context_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int, c_int, c_int]),
+    "fg_wan_set_vace_context": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p]),
+    "fg_wan_vace_context_read": (c_int, [c_void_p, c_void_p, c_void_p]),
+    "fg_op_wan_vace_patch_embed": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
     "fg_op_wan_patch_embed": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
     "fg_op_wan_final": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_int,
                                 c_void_p]),

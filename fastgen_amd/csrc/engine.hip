@@ -1725,6 +1725,17 @@ int fg_op_wan_patch_embed(const float* x, const float* first_frame, const float*
     HIP_TRY(launch_wan_ti2v_patch_embed(x, first_frame, w, bias, out, batch, channels, frames, height, width, d, path, (hipStream_t)stream));
     return FG_OK;
 }
+int fg_op_wan_vace_patch_embed(const float* x, const float* w, const float* bias, void* out, int batch, int channels, int frames, int height, int width,
+                               int d, int path, void* stream) {
+    if (!x || !w || !bias || !out || batch <= 0 || channels <= 0 || channels > 128 || frames <= 0 || height <= 0 || width <= 0 || (height & 1) ||
+        (width & 1) || d <= 0 || (d % 2) || path < 0 || path > 2)
+        return fail(FG_EINVAL, "fg_op_wan_vace_patch_embed: bad argument (null pointer, channels outside [1, 128], odd height / width / d, path outside [0, 2])");
+    if ((int64_t)batch * frames * (height / 2) * (width / 2) > INT32_MAX / 2) return fail(FG_EINVAL, "fg_op_wan_vace_patch_embed: too many tokens");
+    if (path == 2 && channels != 96) return fail(FG_EINVAL, "fg_op_wan_vace_patch_embed: the tiled kernel serves 96 channels, got %d", channels);
+    HIP_TRY(launch_wan_vace_patch_embed(x, w, bias, out, batch, channels, frames, height, width, d, (int64_t)frames * (height / 2) * (width / 2), path,
+                                        (hipStream_t)stream));
+    return FG_OK;
+}
 int fg_op_wan_final(const void* tokens, const float* mod, const float* w, const float* bias, const float* first_frame, float* out, int batch,
                     int channels, int frames, int gh, int gw, int d, float eps, int path, void* stream) {
     if (!tokens || !mod || !w || !bias || !out || batch <= 0 || channels <= 0 || channels > 64 || frames <= 0 || gh <= 0 || gw <= 0 || path < 0 ||

@@ -184,6 +184,7 @@ int fg_wan_sampler_run(fg_wan* h, const fg_wan_sampler_config* sc, float* x, con
                        int use_graph, void* stream) {
     if (!h || !sc || !x || !t_list) return fail(FG_EINVAL, "null argument");
     if (h->is_i2v || h->is_ti2v) return fail(FG_EINVAL, "the chunked / causal loops are not implemented for an image-to-video handle");
+    if (h->is_vace) return fail(FG_EINVAL, "the chunked / causal loops are not implemented for a VACE handle");
     int rc = check_sampler_args(t_list, steps, sample_type, FG_LOOP_X0, sc->schedule);
     if (rc) return rc;
     if (!(sc->t_scale > 0.0)) return fail(FG_EINVAL, "t_scale must be positive");
@@ -366,6 +367,7 @@ int fg_wan_guided_sampler_run(fg_wan* h, const fg_wan_guided_sampler_config* sc,
                               size_t workspace_bytes, int use_graph, void* stream) {
     if (!h || !sc || !x || !t_list || !table) return fail(FG_EINVAL, "null argument");
     if (h->is_i2v || h->is_ti2v) return fail(FG_EINVAL, "the chunked / causal loops are not implemented for an image-to-video handle");
+    if (h->is_vace) return fail(FG_EINVAL, "the chunked / causal loops are not implemented for a VACE handle");
     if (steps < 1 || steps > kGuidedMaxSteps) return fail(FG_EINVAL, "steps must be in [1, %d]", kGuidedMaxSteps);
     if (!(sc->t_scale > 0.0)) return fail(FG_EINVAL, "t_scale must be positive");
     if (sc->guidance != 0 && sc->guidance != 1) return fail(FG_EINVAL, "guidance must be 0 (batch B) or 1 (stacked batch 2 B)");
@@ -549,6 +551,8 @@ int fg_wan_full_sampler_run(fg_wan* h, const fg_wan_sampler_config* sc, const fl
         return fail(FG_ENOTREADY, "no image-to-video condition for batch %d, %d frames of %d x %d (call fg_wan_set_i2v_cond)", batch, frames, height, width);
     if (h->is_ti2v && !h->has_first_frame(batch, height, width))
         return fail(FG_ENOTREADY, "no first frame for batch %d of %d x %d (call fg_wan_set_first_frame)", batch, height, width);
+    if (h->is_vace && !h->has_vace_context(batch, frames, height, width))
+        return fail(FG_ENOTREADY, "no VACE context for batch %d, %d frames of %d x %d (call fg_wan_set_vace_context)", batch, frames, height, width);
     const int rows = batch * frames;
     const int64_t total = (int64_t)batch * h->vch() * frames * height * width, hw1 = (int64_t)height * width;
     auto enqueue = [&](hipStream_t q) -> int {
@@ -581,7 +585,8 @@ int fg_wan_full_sampler_run(fg_wan* h, const fg_wan_sampler_config* sc, const fl
                           {frames, height, width, (int64_t)(uintptr_t)noise, (int64_t)(uintptr_t)eps, (int64_t)(uintptr_t)out,
                            (int64_t)(uintptr_t)workspace, tsb, sc->net_pred_flow, sc->schedule, (int64_t)h->text_L,
                            (int64_t)(uintptr_t)h->blocks[0].kv2, (int64_t)h->fp8, h->ext.time_cond_diff,
-                           (int64_t)(uintptr_t)h->ff, (int64_t)(uintptr_t)h->blocks[0].kvi, (int64_t)h->img_L, (int64_t)(uintptr_t)h->ff0},
+                           (int64_t)(uintptr_t)h->ff, (int64_t)(uintptr_t)h->blocks[0].kvi, (int64_t)h->img_L, (int64_t)(uintptr_t)h->ff0,
+                           (int64_t)(uintptr_t)h->vctx, (int64_t)(uintptr_t)h->vscale},
                           (hipStream_t)stream, enqueue);
 }
 
@@ -621,6 +626,9 @@ int fg_wan_full_guided_sampler_run(fg_wan* h, const fg_wan_guided_sampler_config
     if (h->is_ti2v && !h->has_first_frame(Be, height, width))
         return fail(FG_ENOTREADY, "no first frame for batch %d of %d x %d (call fg_wan_set_first_frame%s)", Be, height, width,
                     guided ? " with [cond; neg_cond]" : "");
+    if (h->is_vace && !h->has_vace_context(Be, frames, height, width))
+        return fail(FG_ENOTREADY, "no VACE context for batch %d, %d frames of %d x %d (call fg_wan_set_vace_context%s)", Be, frames, height, width,
+                    guided ? " with [cond; neg_cond]" : "");
     hipStream_t s = (hipStream_t)stream;
     int rc;
     if ((rc = wan_upload_step_scalars(h, t_list, table, steps, 0, w.sc, s))) return rc;  // (no draw in this loop: the seed slot goes unread)
@@ -658,6 +666,6 @@ int fg_wan_full_guided_sampler_run(fg_wan* h, const fg_wan_guided_sampler_config
     const std::vector<int64_t> key = {batch, guided, frames, height, width, steps, (int64_t)(uintptr_t)x, (int64_t)(uintptr_t)workspace, tsb,
                                       (int64_t)h->text_L, (int64_t)(uintptr_t)h->blocks[0].kv2, (int64_t)h->fp8, h->ext.time_cond_diff,
                                       (int64_t)(uintptr_t)h->ff, (int64_t)(uintptr_t)h->blocks[0].kvi, (int64_t)h->img_L,
-                                      (int64_t)(uintptr_t)h->ff0};
+                                      (int64_t)(uintptr_t)h->ff0, (int64_t)(uintptr_t)h->vctx, (int64_t)(uintptr_t)h->vscale};
     return graph_run(h->full_guided_graph, key, h->sampler.cap, s, enqueue);
 }

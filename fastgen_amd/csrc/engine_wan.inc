@@ -26,8 +26,35 @@ struct fg_wan : HandleBase {
         void* p_akv = nullptr;               // add_k_proj | add_v_proj, bf16 [2 D][D] in every mode (as p_kv2)
         float* b_akv = nullptr;
         void* kvi = nullptr;                 // image cross-attention cache [B][ceil32(Li)][2 D] bf16 (k normalised | v), zero-filled
+        int pin_w = -1, pin_b = -1, pout_w = -1, pout_b = -1;  // a VACE block's proj_in (block 0 only) / proj_out (fg_wan_create_vace)
+        void *p_pin = nullptr, *p_pout = nullptr;              // ... bf16 [D][D] in every mode
+        // every parameter index of the block (fg_wan_pack_group's all-or-none check on a VACE block)
+        template <typename F>
+        void each_param(F&& f) const {
+            for (int idx : {sst, q_w, q_b, k_w, k_b, v_w, v_b, o_w, o_b, nq, nk, q2_w, q2_b, k2_w, k2_b, v2_w, v2_b, o2_w, o2_b, nq2, nk2, n2_w, n2_b,
+                            f0_w, f0_b, f2_w, f2_b, ak_w, ak_b, av_w, av_b, nak, pin_w, pin_b, pout_w, pout_b})
+                if (idx >= 0) f(idx);
+        }
     };
     std::vector<Blk> blocks;
+    // fg_wan_create_vace: the control branch (VaceWan/network.py).  `vblocks` are the VACE blocks - main blocks with their own weights,
+    // their own text k / v (kv2) and proj_in / proj_out; no self-attention cache (the bidirectional calls alone serve such a handle).
+    // The context (fg_wan_set_vace_context) is `vctx` = proj_in(pad(vace_patch_embedding(vid_context))) [B][L][D] bf16, owned here and
+    // rewritten in place while its shape stays (the loops' graphs name it); the hint scales are `vscale` [n][D] fp32, the gate rows of
+    // the injection GEMM, rewritten in place too (`vscale_host`: their values, ones until fg_wan_set_vace_scale; the rows exist from
+    // the first pack on).
+    bool is_vace = false;
+    fg_wan_vace_config vace{};
+    std::vector<Blk> vblocks;
+    int vpe_w = -1, vpe_b = -1;  // vace_patch_embedding
+    void* vctx = nullptr;
+    int vctx_B = 0, vctx_F = 0, vctx_H = 0, vctx_W = 0;  // vctx_B == 0: no context set
+    size_t vctx_elems = 0;
+    float* vscale = nullptr;
+    std::vector<float> vscale_host;
+    bool has_vace_context(int batch, int frames, int height, int width) const {
+        return vctx_B == batch && vctx_F == frames && vctx_H == height && vctx_W == width;
+    }
     int sst = -1, pe_w = -1, pe_b = -1, t1_w = -1, t1_b = -1, t2_w = -1, t2_b = -1, tp_w = -1, tp_b = -1, x1_w = -1, x1_b = -1, x2_w = -1,
         x2_b = -1, po_w = -1, po_b = -1;
     void *p_x1 = nullptr, *p_x2 = nullptr;  // text embedder weights, bf16
@@ -74,6 +101,7 @@ struct fg_wan : HandleBase {
     // its tag is first selected and used: a handle that stays on tag 0 allocates nothing more.
     struct CacheSet {
         std::vector<void*> kc, vc, kv2;  // per block
+        std::vector<void*> vkv2;         // per VACE block
         int cache_B = 0, cache_cap = 0, text_B = 0, text_L = 0, stored_rows = 0;
         size_t kv2_rows = 0;
     };
@@ -114,6 +142,7 @@ struct WanWs {
     size_t gs_bytes;
     void *y8, *hid8;  // fp8 mode: the quantised A operands [M][D] (LayerNorm-modulate and attention outputs) / [M][ffn] (GELU hidden) ...
     float *ys, *hs;   // ... and their per-token scales [M]
+    void *c0, *c1;    // VACE handle, bidirectional call: the control stream's ping-pong pair [M][D] bf16
 };
 
 size_t wan_plan(const fg_wan* h, int B, int Fr, int gh, int gw, Arena& A, WanWs& w, bool all_frames_kv = false) {
@@ -146,6 +175,11 @@ size_t wan_plan(const fg_wan* h, int B, int Fr, int gh, int gw, Arena& A, WanWs&
     w.hid8 = A.take(h->fp8 ? M * (size_t)h->Fd : 0);
     w.ys = A.get<float>(h->fp8 ? M : 0);
     w.hs = A.get<float>(h->fp8 ? M : 0);
+    // (VACE: the control stream's pair and nothing per hint - a hint is consumed by the GEMM that forms it.  The stream is seeded from
+    // x0 before the first block overwrites it, so no copy of x0 is kept.)
+    const bool vace = h->is_vace && all_frames_kv;
+    w.c0 = A.take(vace ? M * D * 2 : 0);
+    w.c1 = A.take(vace ? M * D * 2 : 0);
     return (A.off + 255) & ~(size_t)255;
 }
 
@@ -253,13 +287,27 @@ int wan_pack(fg_wan* h, const ParamGroup& in_group, hipStream_t s) {
     int rc;
     if (!h->device_ready) {
         if ((rc = h->alloc(&h->p_x1, D * Td * 2)) || (rc = h->alloc(&h->p_x2, D * D * 2))) return rc;
-        for (fg_wan::Blk& b : h->blocks) {
+        const auto alloc_block = [&](fg_wan::Blk& b) -> int {
             if ((rc = h->alloc(&b.p_qkv, 3 * D * D * 2)) || (rc = h->alloc(&b.p_o, D * D * 2)) || (rc = h->alloc(&b.p_q2, D * D * 2)) ||
                 (rc = h->alloc(&b.p_kv2, 2 * D * D * 2)) || (rc = h->alloc(&b.p_o2, D * D * 2)) || (rc = h->alloc(&b.p_f0, Fd * D * 2)) ||
                 (rc = h->alloc(&b.p_f2, D * Fd * 2)) || (rc = h->alloc((void**)&b.b_qkv, 3 * D * 4)) ||
                 (rc = h->alloc((void**)&b.b_kv2, 2 * D * 4)) || (rc = h->alloc((void**)&b.n2mod, 2 * D * 4)))
                 return rc;
             if (h->i2v.image_dim > 0 && ((rc = h->alloc(&b.p_akv, 2 * D * D * 2)) || (rc = h->alloc((void**)&b.b_akv, 2 * D * 4)))) return rc;
+            if (b.pin_w >= 0 && (rc = h->alloc(&b.p_pin, D * D * 2))) return rc;
+            if (b.pout_w >= 0 && (rc = h->alloc(&b.p_pout, D * D * 2))) return rc;
+            return FG_OK;
+        };
+        for (fg_wan::Blk& b : h->blocks)
+            if ((rc = alloc_block(b))) return rc;
+        for (fg_wan::Blk& b : h->vblocks)
+            if ((rc = alloc_block(b))) return rc;
+        if (h->is_vace) {
+            const int n = h->vace.num_vace_layers;
+            if ((rc = h->alloc((void**)&h->vscale, (size_t)n * D * 4))) return rc;
+            WanVaceScales sc{};
+            for (int j = 0; j < n; ++j) sc.v[j] = h->vscale_host[j];
+            HIP_TRY(launch_wan_vace_scale_rows(sc, h->vscale, n, (int)D, s));
         }
         if (h->i2v.image_dim > 0) {
             const size_t Di = h->i2v.image_dim;
@@ -283,8 +331,7 @@ int wan_pack(fg_wan* h, const ParamGroup& in_group, hipStream_t s) {
         }
     }
     const int g1 = (int)((D + 255) / 256);
-    for (fg_wan::Blk& b : h->blocks) {
-        if (!in_group(h->params[b.q_w].name)) continue;  // (a block's parameters share their prefix: all of them in the group or none)
+    const auto pack_block = [&](fg_wan::Blk& b) -> int {
         const auto lin = [&](int idx, void* dst, size_t row0, size_t Ntot, size_t N, size_t K) {
             return wan_pack_linear(h, raw(idx), dst, row0, Ntot, N, K, s);
         };
@@ -305,9 +352,33 @@ int wan_pack(fg_wan* h, const ParamGroup& in_group, hipStream_t s) {
             hipLaunchKernelGGL(wan_cat_kernel, dim3(g1), dim3(256), 0, s, raw(b.ak_b), raw(b.av_b), (const float*)nullptr, b.b_akv, (int)D);
         }
         HIP_TRY(hipGetLastError());
+        if (b.p_pin) HIP_TRY(launch_cvt_bf16(raw(b.pin_w), b.p_pin, D * D, s));  // (bf16 in every mode: see fastgen_amd.h)
+        if (b.p_pout) HIP_TRY(launch_cvt_bf16(raw(b.pout_w), b.p_pout, D * D, s));
+        return FG_OK;
+    };
+    for (fg_wan::Blk& b : h->blocks) {
+        if (!in_group(h->params[b.q_w].name)) continue;  // (a block's parameters share their prefix: all of them in the group or none)
+        if ((rc = pack_block(b))) return rc;
+    }
+    for (size_t k = 0; k < h->vblocks.size(); ++k) {
+        // A VACE block's parameters arrive with the root group (the reference's fully_shard wraps `blocks` only), whose prefix says
+        // nothing about them: the block is packed when ALL of its parameters are in the group - and bound, so that no null pointer is
+        // read -, passed over when none is, and a group that holds some of them is refused.
+        fg_wan::Blk& b = h->vblocks[k];
+        int in = 0, total = 0, unbound = -1;
+        b.each_param([&](int idx) {
+            ++total;
+            if (in_group(h->params[idx].name)) ++in;
+            if (!h->params[idx].ptr) unbound = idx;
+        });
+        if (in == 0) continue;
+        if (in != total) return fail(FG_ENOTREADY, "the group holds %d of the %d parameters of VACE block %d: a VACE block is packed whole", in, total, (int)k);
+        if (unbound >= 0) return fail(FG_ENOTREADY, "parameter '%s' is not bound", h->params[unbound].name.c_str());
+        if ((rc = pack_block(b))) return rc;
     }
     h->text_B = h->other.text_B = 0;  // the text caches (of both tags) were computed with the previous weights
     h->ff_B = 0;                      // ... and so was the image-to-video condition
+    h->vctx_B = 0;                    // ... and the VACE context (proj_in, vace_patch_embedding)
     return FG_OK;
 }
 
@@ -318,11 +389,20 @@ extern "C" {
 }  // extern "C" (reopened below)
 
 namespace {
-// fg_wan_create_ex, fg_wan_create_i2v and fg_wan_create_ti2v: one table builder.  i2v == nullptr: the plain network's table (ti2v
-// adds no parameter).
+// fg_wan_create_ex, fg_wan_create_i2v, fg_wan_create_ti2v and fg_wan_create_vace: one table builder.  i2v == nullptr: the plain
+// network's table (ti2v adds no parameter); vace: that table with the control branch's keys inserted.
 int wan_create(const fg_wan_config* cfg, const fg_wan_ext_config* ext, const fg_wan_i2v_config* i2v, fg_wan** out,
-               const fg_wan_ti2v_config* ti2v = nullptr) {
+               const fg_wan_ti2v_config* ti2v = nullptr, const fg_wan_vace_config* vace = nullptr) {
     if (!cfg || !out) return fail(FG_EINVAL, "null argument");
+    if (vace) {
+        if (vace->vace_in_channels <= 0 || vace->vace_in_channels > 128)
+            return fail(FG_EINVAL, "vace_in_channels %d outside (0, 128]", vace->vace_in_channels);
+        if (vace->num_vace_layers < 1 || vace->num_vace_layers > 64) return fail(FG_EINVAL, "num_vace_layers %d outside [1, 64]", vace->num_vace_layers);
+        for (int j = 0; j < vace->num_vace_layers; ++j)
+            if (vace->vace_layers[j] < 0 || vace->vace_layers[j] >= cfg->num_layers || (j > 0 && vace->vace_layers[j] <= vace->vace_layers[j - 1]))
+                return fail(FG_EINVAL, "vace_layers[%d] = %d: vace_layers must be strictly ascending in [0, num_layers = %d)", j, vace->vace_layers[j],
+                            cfg->num_layers);
+    }
     if (ti2v && (ti2v->latent_channels <= 0 || cfg->in_channels != ti2v->latent_channels || cfg->out_channels != ti2v->latent_channels))
         return fail(FG_EINVAL, "in_channels %d and out_channels %d must both equal latent_channels %d", cfg->in_channels, cfg->out_channels,
                     ti2v->latent_channels);
@@ -363,6 +443,12 @@ int wan_create(const fg_wan_config* cfg, const fg_wan_ext_config* ext, const fg_
     h->params.back().ndim = 5;                                  // (reported as 5-d through fg_wan_param_info)
     h->params.back().numel = (int64_t)D * C * 4;
     h->pe_b = h->add("patch_embedding.bias", {D});
+    if (vace) {  // (UNPINNED: the VACE keys and their places follow diffusers' module order as read, not a recorded list)
+        h->vpe_w = h->add("vace_patch_embedding.weight", {D, vace->vace_in_channels, 1, 2});
+        h->params.back().ndim = 5;
+        h->params.back().numel = (int64_t)D * vace->vace_in_channels * 4;
+        h->vpe_b = h->add("vace_patch_embedding.bias", {D});
+    }
     h->t1_w = h->add("condition_embedder.time_embedder.linear_1.weight", {D, cfg->freq_dim});
     h->t1_b = h->add("condition_embedder.time_embedder.linear_1.bias", {D});
     h->t2_w = h->add("condition_embedder.time_embedder.linear_2.weight", {D, D});
@@ -382,10 +468,14 @@ int wan_create(const fg_wan_config* cfg, const fg_wan_ext_config* ext, const fg_
         h->if2_w = h->add(ie + "ff.net.2.weight", {D, Di}); h->if2_b = h->add(ie + "ff.net.2.bias", {D});
         h->in2_w = h->add(ie + "norm2.weight", {D}); h->in2_b = h->add(ie + "norm2.bias", {D});
     }
-    for (int i = 0; i < cfg->num_layers; ++i) {
-        const std::string b = "blocks." + std::to_string(i) + ".";
+    const int nvace = vace ? vace->num_vace_layers : 0;
+    for (int i = 0; i < cfg->num_layers + nvace; ++i) {
+        // (behind the main blocks the VACE blocks: scale_shift_table, proj_in (block 0 only), the main block's keys, proj_out)
+        const bool vb = i >= cfg->num_layers;
+        const std::string b = (vb ? "vace_blocks." + std::to_string(i - cfg->num_layers) : "blocks." + std::to_string(i)) + ".";
         fg_wan::Blk k;
         k.sst = h->add(b + "scale_shift_table", {1, 6, D});
+        if (vb && i == cfg->num_layers) k.pin_w = h->add(b + "proj_in.weight", {D, D}), k.pin_b = h->add(b + "proj_in.bias", {D});
         k.q_w = h->add(b + "attn1.to_q.weight", {D, D}); k.q_b = h->add(b + "attn1.to_q.bias", {D});
         k.k_w = h->add(b + "attn1.to_k.weight", {D, D}); k.k_b = h->add(b + "attn1.to_k.bias", {D});
         k.v_w = h->add(b + "attn1.to_v.weight", {D, D}); k.v_b = h->add(b + "attn1.to_v.bias", {D});
@@ -404,7 +494,8 @@ int wan_create(const fg_wan_config* cfg, const fg_wan_ext_config* ext, const fg_
         k.n2_w = h->add(b + "norm2.weight", {D}); k.n2_b = h->add(b + "norm2.bias", {D});
         k.f0_w = h->add(b + "ffn.net.0.proj.weight", {Fd, D}); k.f0_b = h->add(b + "ffn.net.0.proj.bias", {Fd});
         k.f2_w = h->add(b + "ffn.net.2.weight", {D, Fd}); k.f2_b = h->add(b + "ffn.net.2.bias", {D});
-        h->blocks.push_back(k);
+        if (vb) k.pout_w = h->add(b + "proj_out.weight", {D, D}), k.pout_b = h->add(b + "proj_out.bias", {D});
+        (vb ? h->vblocks : h->blocks).push_back(k);
     }
     h->po_w = h->add("proj_out.weight", {cfg->out_channels * 4, D});
     h->po_b = h->add("proj_out.bias", {cfg->out_channels * 4});
@@ -425,12 +516,17 @@ int wan_create(const fg_wan_config* cfg, const fg_wan_ext_config* ext, const fg_
     h->pack_only.assign(h->params.size(), 0);
     h->dirty.assign(h->params.size(), 1);
     h->pack_only[h->x1_w] = h->pack_only[h->x2_w] = 1;
-    for (const fg_wan::Blk& k : h->blocks)
-        for (int idx : {k.q_w, k.k_w, k.v_w, k.o_w, k.q2_w, k.k2_w, k.v2_w, k.o2_w, k.f0_w, k.f2_w, k.ak_w, k.av_w})
-            if (idx >= 0) h->pack_only[idx] = 1;
+    for (const std::vector<fg_wan::Blk>* bl : {&h->blocks, &h->vblocks})
+        for (const fg_wan::Blk& k : *bl)
+            for (int idx : {k.q_w, k.k_w, k.v_w, k.o_w, k.q2_w, k.k2_w, k.v2_w, k.o2_w, k.f0_w, k.f2_w, k.ak_w, k.av_w, k.pin_w, k.pout_w})
+                if (idx >= 0) h->pack_only[idx] = 1;
     if (Di > 0) h->pack_only[h->if0_w] = h->pack_only[h->if2_w] = 1;
     if (i2v) h->is_i2v = true, h->i2v = *i2v;
     if (ti2v) h->is_ti2v = true, h->ti2v = *ti2v;
+    if (vace) {
+        h->is_vace = true, h->vace = *vace;
+        h->vscale_host.assign(nvace, 1.0f);  // (the reference's `new_ones(len(vace_layers))` when no scale is given, VaceWan/network.py:64-65)
+    }
     *out = h;
     return FG_OK;
 }
@@ -448,6 +544,26 @@ int fg_wan_create_i2v(const fg_wan_config* cfg, const fg_wan_ext_config* ext, co
 int fg_wan_create_ti2v(const fg_wan_config* cfg, const fg_wan_ext_config* ext, const fg_wan_ti2v_config* ti2v, fg_wan** out) {
     if (!ti2v) return fail(FG_EINVAL, "null argument");
     return wan_create(cfg, ext, nullptr, out, ti2v);
+}
+
+int fg_wan_create_vace(const fg_wan_config* cfg, const fg_wan_ext_config* ext, const fg_wan_vace_config* vace, fg_wan** out) {
+    if (!vace) return fail(FG_EINVAL, "null argument");
+    return wan_create(cfg, ext, nullptr, out, nullptr, vace);
+}
+
+int fg_wan_set_vace_scale(fg_wan* h, const float* scales_host, int n, void* stream) {
+    if (!h || !scales_host) return fail(FG_EINVAL, "null argument");
+    if (!h->is_vace) return fail(FG_EINVAL, "not a VACE handle (fg_wan_create_vace)");
+    if (n != h->vace.num_vace_layers) return fail(FG_EINVAL, "%d scales for %d VACE layers", n, h->vace.num_vace_layers);
+    for (int j = 0; j < n; ++j)
+        if (!std::isfinite(scales_host[j])) return fail(FG_EINVAL, "scale %d is not finite", j);
+    h->vscale_host.assign(scales_host, scales_host + n);
+    if (h->vscale) {  // (before the first pack there are no rows yet: the pack writes them from vscale_host)
+        WanVaceScales sc{};
+        for (int j = 0; j < n; ++j) sc.v[j] = scales_host[j];
+        HIP_TRY(launch_wan_vace_scale_rows(sc, h->vscale, n, h->D, (hipStream_t)stream));
+    }
+    return FG_OK;
 }
 
 int fg_wan_set_first_frame(fg_wan* h, const float* first_frame, int batch, int height, int width, void* stream) {
@@ -560,6 +676,8 @@ int fg_wan_select_cache_tag(fg_wan* h, int tag) {
         std::swap(h->blocks[i].vc, o.vc[i]);
         std::swap(h->blocks[i].kv2, o.kv2[i]);
     }
+    o.vkv2.resize(h->vblocks.size(), nullptr);
+    for (size_t i = 0; i < h->vblocks.size(); ++i) std::swap(h->vblocks[i].kv2, o.vkv2[i]);
     std::swap(h->cache_B, o.cache_B);
     std::swap(h->cache_cap, o.cache_cap);
     std::swap(h->text_B, o.text_B);
@@ -587,12 +705,13 @@ int fg_wan_set_text(fg_wan* h, const float* text, int batch, int text_len, void*
     if (h->kv2_rows != M) {
         h->drop_graphs();
         h->kv2_rows = 0;
-        for (fg_wan::Blk& b : h->blocks) {
-            h->free(b.kv2);
-            b.kv2 = nullptr;
-            int rc = h->alloc(&b.kv2, M * 2 * D * 2);
-            if (rc) return rc;
-        }
+        for (std::vector<fg_wan::Blk>* bl : {&h->blocks, &h->vblocks})  // (a VACE block has its own attn2.to_k / to_v / norm_k)
+            for (fg_wan::Blk& b : *bl) {
+                h->free(b.kv2);
+                b.kv2 = nullptr;
+                int rc = h->alloc(&b.kv2, M * 2 * D * 2);
+                if (rc) return rc;
+            }
         h->kv2_rows = M;
     }
     // text_embedder: Linear - GELU(tanh) - Linear (PixArtAlphaTextProjection); then per block k = norm_k(to_k(ctx)), v = to_v(ctx)
@@ -601,11 +720,12 @@ int fg_wan_set_text(fg_wan* h, const float* text, int batch, int text_len, void*
     // (bf16 operands in every mode: this runs once per text)
     if ((rc = wan_gemm(WanOperand{tb}, h->p_x1, h->P(h->x1_b), e1, (int)M, (int)D, (int)Td, s, 1))) return rc;
     if ((rc = wan_gemm(WanOperand{e1}, h->p_x2, h->P(h->x2_b), e2, (int)M, (int)D, (int)D, s))) return rc;
-    for (fg_wan::Blk& b : h->blocks) {
-        if ((rc = wan_gemm(WanOperand{e2}, b.p_kv2, b.b_kv2, b.kv2, (int)M, (int)(2 * D), (int)D, s))) return rc;
-        HIP_TRY(launch_rms_rope((int)D, b.kv2, (int)(2 * D), h->P(b.nk2), h->cfg.eps, nullptr, b.kv2, (int64_t)text_len * 2 * D, 0, (int)(2 * D),
-                                (int)M, text_len, s));
-    }
+    for (std::vector<fg_wan::Blk>* bl : {&h->blocks, &h->vblocks})
+        for (fg_wan::Blk& b : *bl) {
+            if ((rc = wan_gemm(WanOperand{e2}, b.p_kv2, b.b_kv2, b.kv2, (int)M, (int)(2 * D), (int)D, s))) return rc;
+            HIP_TRY(launch_rms_rope((int)D, b.kv2, (int)(2 * D), h->P(b.nk2), h->cfg.eps, nullptr, b.kv2, (int64_t)text_len * 2 * D, 0, (int)(2 * D),
+                                    (int)M, text_len, s));
+        }
     h->text_B = batch, h->text_L = text_len;
     return FG_OK;
 }
@@ -718,6 +838,53 @@ int fg_wan_i2v_cond_read(fg_wan* h, int block, float* img_tokens, float* k_img, 
     return FG_OK;
 }
 
+// fg_wan_set_vace_context's scratch: the embedded context zero-padded to the video's token count, bf16 [B * L][D]
+size_t fg_wan_vace_context_workspace_bytes(const fg_wan* h, int batch, int frames, int height, int width) {
+    if (!h || !h->is_vace || batch <= 0 || frames <= 0 || height <= 0 || width <= 0 || (height & 1) || (width & 1)) return 0;
+    return ((size_t)batch * frames * (height / 2) * (width / 2) * h->D * 2 + 255) & ~(size_t)255;
+}
+
+int fg_wan_set_vace_context(fg_wan* h, const float* vid_context, int batch, int frames, int ctx_frames, int height, int width, void* workspace,
+                            size_t workspace_bytes, void* stream) {
+    if (!h || !vid_context) return fail(FG_EINVAL, "null argument");
+    if (!h->is_vace) return fail(FG_EINVAL, "not a VACE handle (fg_wan_create_vace)");
+    if (batch <= 0 || frames <= 0 || height <= 0 || width <= 0 || (height & 1) || (width & 1)) return fail(FG_EINVAL, "bad batch / frames / size");
+    if (ctx_frames <= 0 || ctx_frames > frames) return fail(FG_EINVAL, "ctx_frames %d outside [1, frames = %d]", ctx_frames, frames);
+    if ((int64_t)batch * frames * (height / 2) * (width / 2) > INT32_MAX / 2) return fail(FG_EINVAL, "batch x tokens exceeds the kernels' 32-bit row index");
+    if (!h->packed) return fail(FG_ENOTREADY, "weights are not packed (call fg_wan_pack_weights)");
+    const size_t need = fg_wan_vace_context_workspace_bytes(h, batch, frames, height, width);
+    if (!workspace || (((uintptr_t)workspace) & 255)) return fail(FG_EINVAL, "bad workspace");
+    if (need > workspace_bytes) return fail(FG_ENOMEM, "workspace too small: need %zu bytes, got %zu", need, workspace_bytes);
+    hipStream_t s = (hipStream_t)stream;
+    const size_t D = h->D, L = (size_t)frames * (height / 2) * (width / 2), M = (size_t)batch * L;
+    int rc;
+    h->vctx_B = 0;  // (nothing valid until everything below is in place)
+    if (M * D != h->vctx_elems) {
+        h->drop_graphs();
+        h->free(h->vctx);
+        h->vctx = nullptr, h->vctx_elems = 0;
+        if ((rc = h->alloc(&h->vctx, M * D * 2))) return rc;
+        h->vctx_elems = M * D;
+    }
+    // `processed_control_states` (VaceWan/network.py:81-88): the embedded context's tokens, THEN zero rows up to the video's token
+    // count; proj_in over all of them (a padded row becomes the bias).  bf16 operands in every mode: once per context, like the text.
+    if (ctx_frames < frames) HIP_TRY(hipMemsetAsync(workspace, 0, M * D * 2, s));
+    HIP_TRY(launch_wan_vace_patch_embed(vid_context, h->P(h->vpe_w), h->P(h->vpe_b), workspace, batch, h->vace.vace_in_channels, ctx_frames, height,
+                                        width, (int)D, (int64_t)L, 0, s));
+    const fg_wan::Blk& b0 = h->vblocks[0];
+    if ((rc = wan_gemm(WanOperand{workspace}, b0.p_pin, h->P(b0.pin_b), h->vctx, (int)M, (int)D, (int)D, s))) return rc;
+    h->vctx_B = batch, h->vctx_F = frames, h->vctx_H = height, h->vctx_W = width;
+    return FG_OK;
+}
+
+int fg_wan_vace_context_read(fg_wan* h, float* ctx_in_out, void* stream) {
+    if (!h || !ctx_in_out) return fail(FG_EINVAL, "null argument");
+    if (!h->is_vace) return fail(FG_EINVAL, "not a VACE handle (fg_wan_create_vace)");
+    if (h->vctx_B == 0) return fail(FG_ENOTREADY, "no VACE context is set (call fg_wan_set_vace_context)");
+    HIP_TRY(launch_from_act(1, h->vctx, ctx_in_out, (int64_t)h->vctx_elems, (hipStream_t)stream));
+    return FG_OK;
+}
+
 namespace {
 // self-attention caches: [B][total_num_frames * frame_seqlen][D] per block, (re)allocated and zeroed when batch or frame size change
 // (`_create_external_caches`, network_causal.py:708-812)
@@ -757,6 +924,110 @@ struct WanFull {
     int num_skip;
 };
 
+// What one bidirectional / chunked / block-causal call hands every block: the call's shapes, its workspace and where the keys live
+struct WanBlockCall {
+    WanWs& w;
+    hipStream_t s;
+    int batch, frames, fs, L, M, BF, block_causal, cache_start;
+    int64_t cbs, MD;
+    bool full;
+};
+
+// One transformer block on the token stream (x, xn) - the pair is swapped behind every residual GEMM, x is the stream on return.  The
+// main blocks run it on the video tokens, the VACE blocks (fg_wan_create_vace) on the control stream: the same launches either way.
+// bt (nullable): the block's taps.
+int wan_block(fg_wan* h, fg_wan::Blk& b, void*& x, void*& xn, const fg_wan_block_taps* bt, const WanBlockCall& k) {
+    const fg_wan_config& c = h->cfg;
+    WanWs& w = k.w;
+    hipStream_t s = k.s;
+    const int D = h->D, batch = k.batch, frames = k.frames, fs = k.fs, L = k.L, M = k.M, BF = k.BF, block_causal = k.block_causal,
+              cache_start = k.cache_start;
+    const int64_t cbs = k.cbs, MD = k.MD;
+    const bool full = k.full;
+    int rc;
+    HIP_TRY(launch_wan_mod(h->P(b.sst), w.tproj, w.mod, BF, 6, D, s));
+    // 1. self-attention over the cached frames and this chunk.  K / V of the chunk go to their cache rows in every call (a call
+    // with store_kv = 0 leaves rows that the chunk's store_kv = 1 call rewrites; the reference's cache length only moves there)
+    WanOperand a;  // the operand the next linear reads
+    if ((rc = wan_modulate(h, x, w.mod, 6 * D, 0, D, M, fs, w, s, a)) || (rc = wan_gemm(a, b.p_qkv, b.b_qkv, w.qkv, M, 3 * D, D, s))) return rc;
+    const __bf16* qkv = (const __bf16*)w.qkv;
+    HIP_TRY(launch_rms_rope(D, qkv, 3 * D, h->P(b.nq), c.eps, w.cs, w.qn, (int64_t)L * D, 0, D, M, L, s));
+    if (block_causal) {
+        // teacher / diffusion forcing over all frames (`_prepare_blockwise_causal_attn_mask`, network_causal.py:131-196): a query sees the
+        // keys up to the end of its own chunk; the first chunk takes the remainder frames.  One attention launch per chunk over a
+        // growing prefix of this call's K / V (the caches are the autoregressive calls' and stay untouched).
+        HIP_TRY(launch_rms_rope(D, qkv + D, 3 * D, h->P(b.nk), c.eps, w.cs, w.kf, (int64_t)L * D, 0, D, M, L, s));
+        HIP_TRY(launch_rms_rope(D, qkv + 2 * D, 3 * D, nullptr, c.eps, nullptr, w.vf, (int64_t)L * D, 0, D, M, L, s));
+        const int chunk = full ? frames : c.chunk_size;  // (full attention: the one chunk sees every key)
+        const int nch = frames / chunk, rem = frames % chunk;
+        for (int ci = 0, f0 = 0; ci < (nch > 0 ? nch : 1); ++ci) {
+            const int nf = nch == 0 ? rem : chunk + (ci == 0 ? rem : 0);
+            const size_t q_off = (size_t)f0 * fs * D;
+            HIP_TRY(launch_fa128((const __bf16*)w.qn + q_off, D, (int64_t)L * D, w.kf, w.vf, D, (int64_t)L * D, (__bf16*)w.att + q_off, D, (int64_t)L * D,
+                                 batch, h->H, nf * fs, (f0 + nf) * fs, s, w.fa));
+            f0 += nf;
+        }
+    } else {
+        HIP_TRY(launch_rms_rope(D, qkv + D, 3 * D, h->P(b.nk), c.eps, w.cs, b.kc, cbs, cache_start, D, M, L, s));
+        HIP_TRY(launch_rms_rope(D, qkv + 2 * D, 3 * D, nullptr, c.eps, nullptr, b.vc, cbs, cache_start, D, M, L, s));
+        HIP_TRY(launch_fa128(w.qn, D, (int64_t)L * D, b.kc, b.vc, D, cbs, w.att, D, (int64_t)L * D, batch, h->H, L, cache_start + L, s, w.fa));
+    }
+    if (bt && bt->attn1) HIP_TRY(launch_from_act(1, w.att, bt->attn1, MD, s));
+    if ((rc = wan_stage(h, w.att, D, w.y8, w.ys, M, s, a)) ||
+        (rc = wan_gemm(a, b.p_o, h->P(b.o_b), xn, M, D, D, s, 0, w.mod + 2 * D, 6 * D, fs, x, w.gs, w.gs_bytes)))
+        return rc;
+    std::swap(x, xn);
+    if (bt && bt->x_attn1) HIP_TRY(launch_from_act(1, x, bt->x_attn1, MD, s));
+    // 2. cross-attention to the text
+    if ((rc = wan_modulate(h, x, b.n2mod, 0, 0, D, M, M, w, s, a)) ||
+        (rc = wan_gemm(a, b.p_q2, h->P(b.q2_b), w.qkv, M, D, D, s, 0, nullptr, 0, 1, nullptr, w.gs, w.gs_bytes)))
+        return rc;
+    HIP_TRY(launch_rms_rope(D, w.qkv, D, h->P(b.nq2), c.eps, nullptr, w.qn, (int64_t)L * D, 0, D, M, L, s));
+    const int64_t tbs = (int64_t)h->text_L * 2 * D;
+    if (h->is_i2v && h->img_L > 0) {
+        // ... and, separately normalised, to the image tokens; the two outputs summed (network_causal.py:294-358)
+        const int64_t ibs = (int64_t)((h->img_L + 31) & ~31) * 2 * D;
+        HIP_TRY(launch_wan_dual_xattn(w.qn, D, (int64_t)L * D, b.kv2, (const __bf16*)b.kv2 + D, 2 * D, tbs, h->text_L, b.kvi, (const __bf16*)b.kvi + D,
+                                      2 * D, ibs, h->img_L, w.att, D, (int64_t)L * D, batch, h->H, L, s));
+    } else {
+        HIP_TRY(launch_fa128(w.qn, D, (int64_t)L * D, b.kv2, (const __bf16*)b.kv2 + D, 2 * D, tbs, w.att, D, (int64_t)L * D, batch, h->H, L,
+                             h->text_L, s, w.fa));
+    }
+    if (bt && bt->attn2) HIP_TRY(launch_from_act(1, w.att, bt->attn2, MD, s));
+    if ((rc = wan_stage(h, w.att, D, w.y8, w.ys, M, s, a)) ||
+        (rc = wan_gemm(a, b.p_o2, h->P(b.o2_b), xn, M, D, D, s, 0, nullptr, 0, 1, x, w.gs, w.gs_bytes)))
+        return rc;
+    std::swap(x, xn);
+    if (bt && bt->x_attn2) HIP_TRY(launch_from_act(1, x, bt->x_attn2, MD, s));
+    // 3. feed-forward
+    if ((rc = wan_modulate(h, x, w.mod, 6 * D, 3 * D, 4 * D, M, fs, w, s, a)) || (rc = wan_gemm(a, b.p_f0, h->P(b.f0_b), w.hid, M, h->Fd, D, s, 1)))
+        return rc;
+    if ((rc = wan_stage(h, w.hid, h->Fd, w.hid8, w.hs, M, s, a)) ||
+        (rc = wan_gemm(a, b.p_f2, h->P(b.f2_b), xn, M, D, h->Fd, s, 0, w.mod + 5 * D, 6 * D, fs, x, w.gs, w.gs_bytes)))
+        return rc;
+    std::swap(x, xn);
+    if (bt && bt->x_ffn) HIP_TRY(launch_from_act(1, x, bt->x_ffn, MD, s));
+    return FG_OK;
+}
+
+bool wan_is_vace_layer(const fg_wan* h, int block) {
+    for (int j = 0; j < h->vace.num_vace_layers; ++j)
+        if (h->vace.vace_layers[j] == block) return true;
+    return false;
+}
+
+// How many hints (= VACE blocks) a bidirectional call consumes: the VACE layers among the blocks it executes
+int wan_vace_hints_consumed(const fg_wan* h, const WanFull* full) {
+    if (!h->is_vace) return 0;
+    int n = 0;
+    for (int j = 0; j < h->vace.num_vace_layers; ++j) {
+        bool skipped = false;
+        for (int i = 0; full && i < full->num_skip; ++i) skipped |= full->skip[i] == h->vace.vace_layers[j];
+        n += !skipped;
+    }
+    return n;
+}
+
 // block_causal: 0 - the autoregressive call on the caches; 1 - all total_num_frames frames under the block-wise causal mask; 2 - `full`
 // given: all frames under full self-attention, the block-causal path with ONE chunk of `frames` frames (the same launches when
 // chunk_size >= frames == total_num_frames), bounded by the RoPE table instead of total_num_frames
@@ -774,6 +1045,7 @@ int wan_forward(fg_wan* h, const float* x_t, const float* t_frames, float* out, 
             return fail(FG_EINVAL, "%d frames exceed the RoPE table (rope_max_seq_len = %d)", frames, h->cfg.rope_max_seq_len);
     }
     if ((h->is_i2v || h->is_ti2v) && !full) return fail(FG_EINVAL, "the chunked / causal calls are not implemented for an image-to-video handle");
+    if (h->is_vace && !full) return fail(FG_EINVAL, "the chunked / causal calls are not implemented for a VACE handle");
     if (!h->packed) return fail(FG_ENOTREADY, "weights are not packed (call fg_wan_pack_weights)");
     if (batch <= 0 || frames <= 0 || height <= 0 || width <= 0 || (height & 1) || (width & 1) || !workspace || (((uintptr_t)workspace) & 255))
         return fail(FG_EINVAL, "bad batch / frames / size / workspace");
@@ -782,6 +1054,12 @@ int wan_forward(fg_wan* h, const float* x_t, const float* t_frames, float* out, 
         return fail(FG_ENOTREADY, "no image-to-video condition for batch %d, %d frames of %d x %d (call fg_wan_set_i2v_cond)", batch, frames, height, width);
     if (h->is_ti2v && !h->has_first_frame(batch, height, width))
         return fail(FG_ENOTREADY, "no first frame for batch %d of %d x %d (call fg_wan_set_first_frame)", batch, height, width);
+    if (h->is_vace && !h->has_vace_context(batch, frames, height, width))
+        return fail(FG_ENOTREADY, "no VACE context for batch %d, %d frames of %d x %d (call fg_wan_set_vace_context)", batch, frames, height, width);
+    if (tp)  // a VACE block that the call's skip_layers keep from running has nothing to tap
+        for (int i = 0; i < tp->n; ++i)
+            if (tp->blocks[i] >= (int)h->blocks.size() && tp->blocks[i] - (int)h->blocks.size() >= wan_vace_hints_consumed(h, full))
+                return fail(FG_EINVAL, "VACE block %d is tapped but does not run under this call's skip_layers", tp->blocks[i] - (int)h->blocks.size());
     if (out == x_t) return fail(FG_EINVAL, "out must not alias x_t");
     hipStream_t s = (hipStream_t)stream;
     const fg_wan_config& c = h->cfg;
@@ -853,6 +1131,12 @@ int wan_forward(fg_wan* h, const float* x_t, const float* t_frames, float* out, 
     // (before the block loop: the r_embedder's scratch was w.mod, which the first launch_wan_mod rewrites from this very buffer)
     if (tp && tp->tproj) HIP_TRY(hipMemcpyAsync(tp->tproj, w.tproj, sizeof(float) * (size_t)BF * 6 * D, hipMemcpyDeviceToDevice, s));
     if (tp && tp->tokens) HIP_TRY(launch_from_act(1, x, tp->tokens, MD, s));
+    const WanBlockCall call{w, s, batch, frames, fs, L, M, BF, block_causal, cache_start, cbs, MD, full != nullptr};
+    // VACE: the control stream starts as c = proj_in(ctx) + x0 (ctx_in is the handle's, formed once per context), here, while x0 is
+    // still whole.  vj: the hints consumed so far = the VACE blocks run so far.
+    void *cx = w.c0, *cxn = w.c1;
+    int vj = 0;
+    if (h->is_vace) HIP_TRY(launch_wan_vace_seed(h->vctx, x, cx, MD, s));
     int ti = 0, blk_idx = 0, si = 0;
     for (fg_wan::Blk& b : h->blocks) {
         const fg_wan_block_taps* bt = (tp && ti < tp->n && tp->blocks[ti] == blk_idx) ? &tp->taps[ti++] : nullptr;
@@ -862,68 +1146,22 @@ int wan_forward(fg_wan* h, const float* x_t, const float* t_frames, float* out, 
             ++si;
             continue;
         }
-        HIP_TRY(launch_wan_mod(h->P(b.sst), w.tproj, w.mod, BF, 6, D, s));
-        // 1. self-attention over the cached frames and this chunk.  K / V of the chunk go to their cache rows in every call (a call
-        // with store_kv = 0 leaves rows that the chunk's store_kv = 1 call rewrites; the reference's cache length only moves there)
-        WanOperand a;  // the operand the next linear reads
-        if ((rc = wan_modulate(h, x, w.mod, 6 * D, 0, D, M, fs, w, s, a)) || (rc = wan_gemm(a, b.p_qkv, b.b_qkv, w.qkv, M, 3 * D, D, s))) return rc;
-        const __bf16* qkv = (const __bf16*)w.qkv;
-        HIP_TRY(launch_rms_rope(D, qkv, 3 * D, h->P(b.nq), c.eps, w.cs, w.qn, (int64_t)L * D, 0, D, M, L, s));
-        if (block_causal) {
-            // teacher / diffusion forcing over all frames (`_prepare_blockwise_causal_attn_mask`, network_causal.py:131-196): a query sees the
-            // keys up to the end of its own chunk; the first chunk takes the remainder frames.  One attention launch per chunk over a
-            // growing prefix of this call's K / V (the caches are the autoregressive calls' and stay untouched).
-            HIP_TRY(launch_rms_rope(D, qkv + D, 3 * D, h->P(b.nk), c.eps, w.cs, w.kf, (int64_t)L * D, 0, D, M, L, s));
-            HIP_TRY(launch_rms_rope(D, qkv + 2 * D, 3 * D, nullptr, c.eps, nullptr, w.vf, (int64_t)L * D, 0, D, M, L, s));
-            const int chunk = full ? frames : c.chunk_size;  // (full attention: the one chunk sees every key)
-            const int nch = frames / chunk, rem = frames % chunk;
-            for (int ci = 0, f0 = 0; ci < (nch > 0 ? nch : 1); ++ci) {
-                const int nf = nch == 0 ? rem : chunk + (ci == 0 ? rem : 0);
-                const size_t q_off = (size_t)f0 * fs * D;
-                HIP_TRY(launch_fa128((const __bf16*)w.qn + q_off, D, (int64_t)L * D, w.kf, w.vf, D, (int64_t)L * D, (__bf16*)w.att + q_off, D, (int64_t)L * D,
-                                     batch, h->H, nf * fs, (f0 + nf) * fs, s, w.fa));
-                f0 += nf;
-            }
-        } else {
-            HIP_TRY(launch_rms_rope(D, qkv + D, 3 * D, h->P(b.nk), c.eps, w.cs, b.kc, cbs, cache_start, D, M, L, s));
-            HIP_TRY(launch_rms_rope(D, qkv + 2 * D, 3 * D, nullptr, c.eps, nullptr, b.vc, cbs, cache_start, D, M, L, s));
-            HIP_TRY(launch_fa128(w.qn, D, (int64_t)L * D, b.kc, b.vc, D, cbs, w.att, D, (int64_t)L * D, batch, h->H, L, cache_start + L, s, w.fa));
+        if ((rc = wan_block(h, b, x, xn, bt, call))) return rc;
+        if (h->is_vace && wan_is_vace_layer(h, blk_idx - 1)) {
+            // `hidden_states = hidden_states + control_hint * scale` with (hint, scale) popped from the FRONT of the list
+            // (VaceWan/network.py:242-245): the j-th executed VACE layer takes hint j.  VACE block j depends on x0 and block j - 1 alone,
+            // so it runs here, directly before its hint is consumed, and the hint proj_out_j(c) is the product of the GEMM that adds it:
+            // x = x + scale_j * (c Wout^T + b), rounded once.  A hint that no executed layer consumes is never computed.
+            fg_wan::Blk& vb = h->vblocks[vj];
+            const fg_wan_block_taps* vt = nullptr;
+            for (int i = 0; tp && i < tp->n; ++i)
+                if (tp->blocks[i] == (int)h->blocks.size() + vj) vt = &tp->taps[i];
+            if ((rc = wan_block(h, vb, cx, cxn, vt, call)) ||
+                (rc = wan_gemm(WanOperand{cx}, vb.p_pout, h->P(vb.pout_b), xn, M, D, D, s, 0, h->vscale + (size_t)vj * D, D, M, x, w.gs, w.gs_bytes)))
+                return rc;
+            std::swap(x, xn);
+            ++vj;
         }
-        if (bt && bt->attn1) HIP_TRY(launch_from_act(1, w.att, bt->attn1, MD, s));
-        if ((rc = wan_stage(h, w.att, D, w.y8, w.ys, M, s, a)) ||
-            (rc = wan_gemm(a, b.p_o, h->P(b.o_b), xn, M, D, D, s, 0, w.mod + 2 * D, 6 * D, fs, x, w.gs, w.gs_bytes)))
-            return rc;
-        std::swap(x, xn);
-        if (bt && bt->x_attn1) HIP_TRY(launch_from_act(1, x, bt->x_attn1, MD, s));
-        // 2. cross-attention to the text
-        if ((rc = wan_modulate(h, x, b.n2mod, 0, 0, D, M, M, w, s, a)) ||
-            (rc = wan_gemm(a, b.p_q2, h->P(b.q2_b), w.qkv, M, D, D, s, 0, nullptr, 0, 1, nullptr, w.gs, w.gs_bytes)))
-            return rc;
-        HIP_TRY(launch_rms_rope(D, w.qkv, D, h->P(b.nq2), c.eps, nullptr, w.qn, (int64_t)L * D, 0, D, M, L, s));
-        const int64_t tbs = (int64_t)h->text_L * 2 * D;
-        if (h->is_i2v && h->img_L > 0) {
-            // ... and, separately normalised, to the image tokens; the two outputs summed (network_causal.py:294-358)
-            const int64_t ibs = (int64_t)((h->img_L + 31) & ~31) * 2 * D;
-            HIP_TRY(launch_wan_dual_xattn(w.qn, D, (int64_t)L * D, b.kv2, (const __bf16*)b.kv2 + D, 2 * D, tbs, h->text_L, b.kvi, (const __bf16*)b.kvi + D,
-                                          2 * D, ibs, h->img_L, w.att, D, (int64_t)L * D, batch, h->H, L, s));
-        } else {
-            HIP_TRY(launch_fa128(w.qn, D, (int64_t)L * D, b.kv2, (const __bf16*)b.kv2 + D, 2 * D, tbs, w.att, D, (int64_t)L * D, batch, h->H, L,
-                                 h->text_L, s, w.fa));
-        }
-        if (bt && bt->attn2) HIP_TRY(launch_from_act(1, w.att, bt->attn2, MD, s));
-        if ((rc = wan_stage(h, w.att, D, w.y8, w.ys, M, s, a)) ||
-            (rc = wan_gemm(a, b.p_o2, h->P(b.o2_b), xn, M, D, D, s, 0, nullptr, 0, 1, x, w.gs, w.gs_bytes)))
-            return rc;
-        std::swap(x, xn);
-        if (bt && bt->x_attn2) HIP_TRY(launch_from_act(1, x, bt->x_attn2, MD, s));
-        // 3. feed-forward
-        if ((rc = wan_modulate(h, x, w.mod, 6 * D, 3 * D, 4 * D, M, fs, w, s, a)) || (rc = wan_gemm(a, b.p_f0, h->P(b.f0_b), w.hid, M, h->Fd, D, s, 1)))
-            return rc;
-        if ((rc = wan_stage(h, w.hid, h->Fd, w.hid8, w.hs, M, s, a)) ||
-            (rc = wan_gemm(a, b.p_f2, h->P(b.f2_b), xn, M, D, h->Fd, s, 0, w.mod + 5 * D, 6 * D, fs, x, w.gs, w.gs_bytes)))
-            return rc;
-        std::swap(x, xn);
-        if (bt && bt->x_ffn) HIP_TRY(launch_from_act(1, x, bt->x_ffn, MD, s));
     }
     if (!block_causal && store_kv && cache_start + L > h->stored_rows) h->stored_rows = cache_start + L;
     HIP_TRY(launch_wan_outmod(h->P(h->sst), w.temb, w.omod, BF, D, s));
@@ -948,8 +1186,8 @@ int wan_check_taps(const fg_wan* h, const int* tap_blocks, const fg_wan_block_ta
     if (!h) return fail(FG_EINVAL, "null argument");
     if (num_taps < 0 || (num_taps > 0 && (!tap_blocks || !taps))) return fail(FG_EINVAL, "bad tap arguments");
     for (int i = 0; i < num_taps; ++i)
-        if (tap_blocks[i] < 0 || tap_blocks[i] >= (int)h->blocks.size() || (i > 0 && tap_blocks[i] <= tap_blocks[i - 1]))
-            return fail(FG_EINVAL, "tap_blocks must be ascending block indices in [0, %d)", (int)h->blocks.size());
+        if (tap_blocks[i] < 0 || tap_blocks[i] >= (int)(h->blocks.size() + h->vblocks.size()) || (i > 0 && tap_blocks[i] <= tap_blocks[i - 1]))
+            return fail(FG_EINVAL, "tap_blocks must be ascending block indices in [0, %d)", (int)(h->blocks.size() + h->vblocks.size()));
     return FG_OK;
 }
 }  // namespace

@@ -293,3 +293,16 @@ int launch_wan_ti2v_final(int D, const void* x, const float* mod, const float* w
                           int gh, int gw, int C, float eps, int path, hipStream_t s);
 // dst[i] = i % Fr == 0 ? 0 : src[i] over n = rows of (sample, frame): the embedder rows under the first-frame mask (in place allowed)
 int launch_wan_ti2v_zero_frame0(const float* src, float* dst, int n, int Fr, hipStream_t s);
+// wan_vace.hip: the two ends of the VACE control branch (reference fastgen/networks/VaceWan/network.py).  The patch embedding of the
+// control video x [B][C][Fc][H][W]: sample b's Fc gh gw tokens go to rows [b * out_rows, ...) of out (out_rows >= Fc gh gw: the rows
+// behind them are the caller's zero padding and stay untouched).  path 0: the tiled kernel at C == 96, else wan.hip's per-output
+// kernel; 1: never the tiled kernel; 2: the tiled kernel or hipErrorInvalidValue.
+int launch_wan_vace_patch_embed(const float* x, const float* w, const float* bias, void* out, int B, int C, int Fc, int H, int W, int D,
+                                int64_t out_rows, int path, hipStream_t s);
+// c = ctx_in + x0 over n bf16 values (n % 8 == 0, 16-byte aligned), rounded once
+int launch_wan_vace_seed(const void* ctx_in, const void* x0, void* c, int64_t n, hipStream_t s);
+// rows [n][D] fp32 with rows[j][:] = sc.v[j] (n <= 64): the hint scales as gate rows, passed by value so that the fill is stream-ordered
+struct WanVaceScales {
+    float v[64];
+};
+int launch_wan_vace_scale_rows(const WanVaceScales& sc, float* rows, int n, int D, hipStream_t s);

@@ -43,11 +43,11 @@ class WanEngineNetwork(FastGenNetwork):
 
     def _build_engine(self, *, num_attention_heads, attention_head_dim, in_channels, out_channels, text_dim, freq_dim, ffn_dim, num_layers, eps,
                       rope_max_seq_len, chunk_size, total_num_frames, compute_dtype, enable_logvar_linear, ext=None, init_value=None, i2v=None,
-                      ti2v=None) -> None:
+                      ti2v=None, vace=None) -> None:
         """The handle (`ext`: an `fg_wan_ext_config` for fg_wan_create_ex, None: fg_wan_create; `i2v`: an `fg_wan_i2v_config` for
-        fg_wan_create_i2v, `ti2v`: an `fg_wan_ti2v_config` for fg_wan_create_ti2v, either with `ext` or without) and the parameters under their
-        state-dict paths, initial values drawn in plan order from one seeded generator (`init_value(name, shape, g)`, default
-        `_init_value`)."""
+        fg_wan_create_i2v, `ti2v`: an `fg_wan_ti2v_config` for fg_wan_create_ti2v, `vace`: an `fg_wan_vace_config` for fg_wan_create_vace,
+        each with `ext` or without) and the parameters under their state-dict paths, initial values drawn in plan order from one seeded
+        generator (`init_value(name, shape, g)`, default `_init_value`)."""
         self.compute_dtype = compute_dtype
         cfg = _lib.fg_wan_config()
         cfg.compute_dtype = _lib.DTYPE_NAMES[compute_dtype or "bf16"]
@@ -57,13 +57,15 @@ class WanEngineNetwork(FastGenNetwork):
         self._cfg, self.in_channels = cfg, in_channels
         self._eng = _engine.Handles("wan", cfg)  # one handle: the mode is fixed at construction
         create = None
-        if ext is not None or i2v is not None or ti2v is not None:
+        if ext is not None or i2v is not None or ti2v is not None or vace is not None:
             def create(dt):
                 c = type(cfg).from_buffer_copy(cfg)
                 c.compute_dtype = dt
                 h = ctypes.c_void_p()
                 e = ctypes.byref(ext) if ext is not None else None
-                if ti2v is not None:
+                if vace is not None:
+                    _lib.check(_lib.lib().fg_wan_create_vace(ctypes.byref(c), e, ctypes.byref(vace), ctypes.byref(h)))
+                elif ti2v is not None:
                     _lib.check(_lib.lib().fg_wan_create_ti2v(ctypes.byref(c), e, ctypes.byref(ti2v), ctypes.byref(h)))
                 elif i2v is not None:
                     _lib.check(_lib.lib().fg_wan_create_i2v(ctypes.byref(c), e, ctypes.byref(i2v), ctypes.byref(h)))

@@ -855,6 +855,51 @@ FG_API int fg_wan_create_ti2v(const fg_wan_config* cfg, const fg_wan_ext_config*
 FG_API int fg_wan_set_first_frame(fg_wan* h, const float* first_frame, int batch, int height, int width, void* stream);
 /* Exposed for the tests: the handle's copy into out [batch, latent_channels, 1, height, width].  FG_ENOTREADY before a condition is set. */
 FG_API int fg_wan_first_frame_read(fg_wan* h, float* out, void* stream);
+/* VACE: video-to-video control on the bidirectional network (reference fastgen/networks/VaceWan/network.py `VACEWan`,
+ * vace_classify_forward_*; the block body is diffusers' WanVACETransformerBlock).  PARITY UNPINNED like the rest of fg_wan_*; in
+ * addition the VACE keys and their order are read from diffusers' module order, not recorded from a run.  A second stack of
+ * num_vace_layers "VACE blocks" runs on a control stream c and adds scaled hints into the main token stream:
+ *   x0 = patch_embedding(x_t);  ctx = vace_patch_embedding(vid_context) flattened to tokens and THEN zero-padded to x0's token count
+ *   (a context may have fewer frames than the video);  c = proj_in(ctx) + x0 (a padded row is proj_in.bias + x0);  VACE block k is a
+ *   main block with its own weights (its own scale_shift_table and its own text k / v among them) on c, with the same timestep_proj
+ *   (the r term included), text and RoPE; hint_k = proj_out_k(c) and block k + 1 continues from c, not from the hint.  Behind main
+ *   block i, i in vace_layers: x = x + hint * scale with (hint, scale) taken from the FRONT of the list - a block in skip_layers is
+ *   passed over before that, so the j-th EXECUTED VACE layer receives hint j with scale j whatever its own index is.
+ * VACE block j runs directly before hint j is consumed, and the injection is one token GEMM x + scale_j * (c Wout^T + b): the hint is
+ * never materialised, the sum is rounded once, and hints that no executed layer consumes are not computed.
+ * Parameter table: fg_wan_create_ex's with `vace_patch_embedding.{weight [D, vace_in_channels, 1, 2, 2], bias}` directly behind
+ * `patch_embedding.*` and `vace_blocks.{k}.*` behind the last `blocks.*` key; per VACE block: scale_shift_table, proj_in.{weight,
+ * bias} (k = 0 only), the main block's keys in the main block's order, proj_out.{weight, bias}.
+ * fp8 mode: the six linears of every VACE block follow the handle's mode, as the main blocks' do (one block body serves both);
+ * proj_in (once per context) and proj_out stay bf16 in both modes - the rule is "the six linears of a block", and proj_out has no
+ * quantising producer in front of it.
+ * FG_EINVAL (the field named): vace_layers not strictly ascending in [0, num_layers), num_vace_layers outside [1, 64],
+ * vace_in_channels outside (0, 128].  On such a handle fg_wan_forward_full, fg_wan_forward_full_features, fg_wan_full_sampler_run and
+ * fg_wan_full_guided_sampler_run (context set at batch 2 B) work; the chunked and causal entry points return FG_EINVAL.  In
+ * fg_wan_forward_full_features tap_blocks may also name num_layers + k: VACE block k, its five taps taken from the control stream
+ * (FG_EINVAL when that block does not run under the call's skip_layers, and on every other handle).  fg_wan_set_text also fills the
+ * VACE blocks' own text k / v.  fg_wan_pack_group packs a VACE block only when all of its parameters are in the group (they arrive
+ * with the root group: the reference's fully_shard wraps `blocks` only); a group that holds some of them is FG_ENOTREADY. */
+typedef struct fg_wan_vace_config {
+    int vace_in_channels;   /* 96: channels of the control video (inactive | reactive latents | 64 mask channels) */
+    int num_vace_layers;
+    int vace_layers[64];    /* the main blocks behind which a hint is added, strictly ascending */
+} fg_wan_vace_config;
+FG_API int fg_wan_create_vace(const fg_wan_config* cfg, const fg_wan_ext_config* ext /* nullable */, const fg_wan_vace_config* vace, fg_wan** out);
+/* The hint scales (`context_scale`): n == num_vace_layers host floats, kept on the handle as [n][D] fp32 rows (the gate rows of the
+ * injection GEMM) and rewritten in place, so that a captured loop replays with the new scales.  Ones after creation. */
+FG_API int fg_wan_set_vace_scale(fg_wan* h, const float* scales_host, int n, void* stream);
+/* vid_context [batch, vace_in_channels, ctx_frames, height, width] fp32 (device), ctx_frames <= frames.  Neither the context nor
+ * proj_in depends on the step: ctx_in = proj_in(pad(vace_patch_embedding(vid_context))), bf16 [batch, frames * height/2 * width/2, D],
+ * is computed once here (padded rows equal the bias, rounded to bf16).  The handle owns it: rewritten in place while the shapes stay
+ * (a captured loop replays on the new contents), reallocated otherwise.  Packing weights invalidates it; FG_ENOTREADY before packing,
+ * and from a forward without a context of the call's batch, frames and size.  The workspace (256-byte aligned,
+ * fg_wan_vace_context_workspace_bytes) is scratch of this call only. */
+FG_API size_t fg_wan_vace_context_workspace_bytes(const fg_wan* h, int batch, int frames, int height, int width);
+FG_API int fg_wan_set_vace_context(fg_wan* h, const float* vid_context, int batch, int frames, int ctx_frames, int height, int width,
+                                   void* workspace, size_t workspace_bytes, void* stream);
+/* Exposed for the tests: ctx_in as fp32 [batch, frames * height/2 * width/2, D].  FG_ENOTREADY before a context is set. */
+FG_API int fg_wan_vace_context_read(fg_wan* h, float* ctx_in_out, void* stream);
 /* One step of that solver, in place (misc.hip guided_multistep_kernel): with the eight DEVICE doubles tab = {s, g, c0, c1, c2, p0, p1, p2}
  * each rounded once to fp32, v = guided ? v[total + i] + g (v[i] - v[total + i]) : v[i]; m = x - s v; x_corr = c0 x_last + c1 m_prev +
  * c2 m (first != 0: x_last := x, m_prev := m, neither buffer is read); x_next = p0 x_corr + p1 m_prev + p2 m; then x <- x_next (and
@@ -945,6 +990,11 @@ FG_API int fg_op_wan_patch_embed(const float* x, const float* first_frame, const
                                  int frames, int height, int width, int d, int path, void* stream);
 FG_API int fg_op_wan_final(const void* tokens, const float* mod, const float* w, const float* bias, const float* first_frame, float* out, int batch,
                            int channels, int frames, int gh, int gw, int d, float eps, int path, void* stream);
+/* The control branch's patch embedding on its own (wan_vace.hip): fg_op_wan_patch_embed's arithmetic for up to 128 channels, without a
+ * second source.  path 0: what fg_wan_set_vace_context launches (channels == 96: the tiled kernel), 1: the per-output kernel of
+ * wan.hip, 2: the tiled kernel, FG_EINVAL unless channels == 96.  The two are bit-identical (one fmaf chain per output). */
+FG_API int fg_op_wan_vace_patch_embed(const float* x, const float* w, const float* bias, void* out, int batch, int channels, int frames, int height,
+                                      int width, int d, int path, void* stream);
 /* The transformer blocks' token GEMM in the bf16 compute mode (gemm.hip; reference: the nn.Linear calls of DiTBlock,
  * fastgen/networks/DiT/network.py:168-198, under bf16 autocast): out[m][n] = resid[m][n] + gate[(m / gate_rows) * gate_stride + n] *
  * act(sum_k a[m][k] w[n][k] + bias[n]) with a [m][k], w [n][k], resid / out [m][n] in bf16, fp32 accumulation, bias / gate fp32;

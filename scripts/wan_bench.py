@@ -3,7 +3,13 @@ Wan2.1-T2V-1.3B, latents [16, 21, 60, 104] = 480p, chunk of 3 frames, t_list of 
 chunk k (4680 query tokens over (3 k + 3) * 1560 cached + own keys), and the whole 21-frame 4-step loop (7 chunks x (4 + 1) calls).
 Random-init weights of the 1.3B architecture, synthetic latents and text embeddings.
     python scripts/wan_bench.py [--layers=30] [--loop] [--compute-dtype=bf16[,fp8]] [--case=chunks|bc|guided] [--chunks=0,6]
-                                [--widths=1.3b|14b] [--trace=CALLS] [--bidirectional] [--i2v] [--ti2v [--first-frame=both|yes|no]]
+                                [--widths=1.3b|14b] [--trace=CALLS] [--bidirectional] [--i2v] [--vace] [--ti2v [--first-frame=both|yes|no]]
+--vace (with --bidirectional): the video-to-video network `VACEWan` (fastgen_amd/networks/VaceWan/network.py: a VACE block behind every
+  second layer, a 96-channel control video of 21 frames) next to `Wan` of the same widths and depth in the same run, at [1,16,21,60,104]:
+  one forward, the 4-step x0 student loop (one hipGraph), one fg_wan_set_vace_context, and the tiled 96-channel patch embedding against
+  the per-output kernel (fg_op_wan_vace_patch_embed path 2 vs 1) on that context.  The expected ratio of the forwards is
+  (layers + VACE layers) / layers plus one D x D injection GEMM per VACE layer.  --trace=CALLS: one arm, `VACEWan` alone, one warm-up +
+  CALLS forwards and nothing else, for `rocprofv3 --kernel-trace --stats`.
 --ti2v: Wan2.2-TI2V-5B (configs/experiments/Wan{T2V,I2V}/config_*_wan22_5b.py: 24 heads x 128, 48 latent channels, ffn 14336, 30 layers)
   on latents [1, 48, 21, 44, 80] (18 480 tokens): one forward and the 2-step x0 student loop t_list = [0.999, 0.833, 0.0] (one hipGraph)
   per arm, as the text-to-video network `Wan(expand_timesteps=True)` ("no first frame") and as the image-to-video network
@@ -54,7 +60,7 @@ D, fs, Lt = H * 128, 1560, 512
 B = 2 if CASE == "guided" else 1
 
 nets = {}
-for arm in ([] if "--i2v" in sys.argv or TI2V else ARMS):
+for arm in ([] if "--i2v" in sys.argv or "--vace" in sys.argv or TI2V else ARMS):
     torch.manual_seed(0)  # the same weights in every arm
     nets[arm] = CausalWan(num_attention_heads=H, ffn_dim=Fd, num_layers=LAYERS, compute_dtype=arm).cuda().eval()
 x = torch.randn(B, 16, 21, 60, 104, device="cuda")
@@ -151,6 +157,53 @@ if "--bidirectional" in sys.argv and "--i2v" in sys.argv:
                 i2v._prepare(x1, "x_t", ff, img)
             side_by_side(f"{arm}: fg_wan_set_i2v_cond (257 image tokens, {LAYERS} layers)", {"set": set_cond}, 3)
             del plain, i2v
+    sys.exit(0)
+
+if "--bidirectional" in sys.argv and "--vace" in sys.argv:
+    from fastgen_amd import _lib
+    from fastgen_amd.methods.model import FastGenModel
+    from fastgen_amd.networks._engine import ptr
+    from fastgen_amd.networks.VaceWan.network import VACEWan
+    from fastgen_amd.networks.Wan.network import Wan
+
+    x1, text1, t1, L = x[:1], text[:1], t[:1], 21 * fs
+    ctx = torch.cat([torch.randn(1, 32, 21, 60, 104, device="cuda"), torch.ones(1, 64, 21, 60, 104, device="cuda")], dim=1)
+    cond = {"text_embeds": text1, "vid_context": ctx}
+    vace_layers = list(range(0, LAYERS, 2))
+    for arm in ARMS:
+        torch.manual_seed(0)
+        vace = VACEWan(num_attention_heads=H, ffn_dim=Fd, num_layers=LAYERS, vace_layers=vace_layers, compute_dtype=arm).cuda().eval()
+        plain = None if TRACE else Wan(num_attention_heads=H, ffn_dim=Fd, num_layers=LAYERS, compute_dtype=arm).cuda().eval()
+        with torch.inference_mode():
+            if TRACE:
+                window(lambda: vace(x1, t1, condition=cond, fwd_pred_type="flow"), 1 + TRACE)
+                sys.exit(0)
+            nv = len(vace_layers)
+            expect = (LAYERS + nv) / LAYERS
+            med = side_by_side(f"{arm}: one forward, {L} tokens, {LAYERS} layers + {nv} VACE blocks, {WIDTHS}",
+                               {"Wan": lambda: plain(x1, t1, condition=text1, fwd_pred_type="flow"),
+                                "VACEWan": lambda: vace(x1, t1, condition=cond, fwd_pred_type="flow")}, 2)
+            print(f"   VACEWan / Wan = {med['VACEWan'] / med['Wan']:.3f} (blocks alone: {expect:.3f}; + {nv} injection GEMMs of "
+                  f"{2 * L * D * D / 1e9:.0f} GFLOP each)")
+            loop = lambda net, c: FastGenModel.generator_fn(net, x1, student_sample_steps=4, t_list=[0.999, 0.937, 0.833, 0.624, 0.0],  # noqa: E731
+                                                            condition=c, student_sample_type="sde", seed=1)
+            med = side_by_side(f"{arm}: 4-step x0 student loop (4 network calls, one graph)",
+                               {"Wan": lambda: loop(plain, text1), "VACEWan": lambda: loop(vace, cond)}, 1)
+            print(f"   VACEWan / Wan = {med['VACEWan'] / med['Wan']:.3f}")
+
+            def set_ctx():  # a fresh context every time: embed it, pad it, proj_in
+                vace._vace_key = None
+                vace._prepare(x1, "x_t", ctx)
+            side_by_side(f"{arm}: fg_wan_set_vace_context (21 context frames)", {"set": set_ctx}, 3)
+            del plain, vace
+            torch.cuda.empty_cache()
+    with torch.inference_mode():
+        w = torch.randn(D, 96, 1, 2, 2, device="cuda") * 384 ** -0.5
+        b = torch.zeros(D, device="cuda")
+        out = torch.empty(1, L, D, dtype=torch.bfloat16, device="cuda")
+        op = lambda path: _lib.check(_lib.lib().fg_op_wan_vace_patch_embed(ptr(ctx), ptr(w), ptr(b), ptr(out), 1, 96, 21, 60, 104, D, path, None))  # noqa: E731
+        med = side_by_side(f"96-channel patch embedding, {L} tokens, D {D}", {"generic": lambda: op(1), "tiled": lambda: op(2)}, 5)
+        print(f"   generic / tiled = {med['generic'] / med['tiled']:.2f}")
     sys.exit(0)
 
 if "--bidirectional" in sys.argv:
