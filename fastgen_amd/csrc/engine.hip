@@ -1722,7 +1722,8 @@ int fg_op_wan_patch_embed(const float* x, const float* first_frame, const float*
         return fail(FG_EINVAL, "fg_op_wan_patch_embed: bad argument (null pointer, channels outside [1, 64], odd height / width / d, path outside [0, 2])");
     if ((int64_t)batch * frames * (height / 2) * (width / 2) > INT32_MAX / 2) return fail(FG_EINVAL, "fg_op_wan_patch_embed: too many tokens");
     if (path == 2 && channels != 48) return fail(FG_EINVAL, "fg_op_wan_patch_embed: the tiled kernel serves 48 channels, got %d", channels);
-    HIP_TRY(launch_wan_ti2v_patch_embed(x, first_frame, w, bias, out, batch, channels, frames, height, width, d, path, (hipStream_t)stream));
+    HIP_TRY(launch_wan_embed(WanEmbedSrc{x, first_frame, first_frame ? WAN_EMBED_FRAME0 : WAN_EMBED_PLAIN, channels, frames, height, width}, w, bias, out,
+                             batch, d, (int64_t)frames * (height / 2) * (width / 2), path, (hipStream_t)stream));
     return FG_OK;
 }
 int fg_op_wan_vace_patch_embed(const float* x, const float* w, const float* bias, void* out, int batch, int channels, int frames, int height, int width,
@@ -1732,8 +1733,8 @@ int fg_op_wan_vace_patch_embed(const float* x, const float* w, const float* bias
         return fail(FG_EINVAL, "fg_op_wan_vace_patch_embed: bad argument (null pointer, channels outside [1, 128], odd height / width / d, path outside [0, 2])");
     if ((int64_t)batch * frames * (height / 2) * (width / 2) > INT32_MAX / 2) return fail(FG_EINVAL, "fg_op_wan_vace_patch_embed: too many tokens");
     if (path == 2 && channels != 96) return fail(FG_EINVAL, "fg_op_wan_vace_patch_embed: the tiled kernel serves 96 channels, got %d", channels);
-    HIP_TRY(launch_wan_vace_patch_embed(x, w, bias, out, batch, channels, frames, height, width, d, (int64_t)frames * (height / 2) * (width / 2), path,
-                                        (hipStream_t)stream));
+    HIP_TRY(launch_wan_embed(WanEmbedSrc{x, nullptr, WAN_EMBED_PLAIN, channels, frames, height, width}, w, bias, out, batch, d,
+                             (int64_t)frames * (height / 2) * (width / 2), path, (hipStream_t)stream));
     return FG_OK;
 }
 int fg_op_wan_final(const void* tokens, const float* mod, const float* w, const float* bias, const float* first_frame, float* out, int batch,

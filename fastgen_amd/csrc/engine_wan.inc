@@ -869,8 +869,8 @@ int fg_wan_set_vace_context(fg_wan* h, const float* vid_context, int batch, int 
     // `processed_control_states` (VaceWan/network.py:81-88): the embedded context's tokens, THEN zero rows up to the video's token
     // count; proj_in over all of them (a padded row becomes the bias).  bf16 operands in every mode: once per context, like the text.
     if (ctx_frames < frames) HIP_TRY(hipMemsetAsync(workspace, 0, M * D * 2, s));
-    HIP_TRY(launch_wan_vace_patch_embed(vid_context, h->P(h->vpe_w), h->P(h->vpe_b), workspace, batch, h->vace.vace_in_channels, ctx_frames, height,
-                                        width, (int)D, (int64_t)L, 0, s));
+    HIP_TRY(launch_wan_embed(WanEmbedSrc{vid_context, nullptr, WAN_EMBED_PLAIN, h->vace.vace_in_channels, ctx_frames, height, width}, h->P(h->vpe_w),
+                             h->P(h->vpe_b), workspace, batch, (int)D, (int64_t)L, 0, s));
     const fg_wan::Blk& b0 = h->vblocks[0];
     if ((rc = wan_gemm(WanOperand{workspace}, b0.p_pin, h->P(b0.pin_b), h->vctx, (int)M, (int)D, (int)D, s))) return rc;
     h->vctx_B = batch, h->vctx_F = frames, h->vctx_H = height, h->vctx_W = width;
@@ -886,6 +886,14 @@ int fg_wan_vace_context_read(fg_wan* h, float* ctx_in_out, void* stream) {
 }
 
 namespace {
+// where the handle's patch embedding reads its input: the virtual concat [x_t | mask | first_frame_cond] (image-to-video), x_t with
+// frame 0's tokens from the first-frame condition (first-frame replacement), or x_t alone
+WanEmbedSrc wan_embed_src(const fg_wan* h, const float* x_t, int frames, int height, int width) {
+    if (h->is_i2v) return {x_t, h->ff, WAN_EMBED_CONCAT, h->i2v.latent_channels, frames, height, width};
+    if (h->is_ti2v) return {x_t, h->ff0, WAN_EMBED_FRAME0, h->cfg.in_channels, frames, height, width};
+    return {x_t, nullptr, WAN_EMBED_PLAIN, h->cfg.in_channels, frames, height, width};
+}
+
 // self-attention caches: [B][total_num_frames * frame_seqlen][D] per block, (re)allocated and zeroed when batch or frame size change
 // (`_create_external_caches`, network_causal.py:708-812)
 int wan_ensure_caches(fg_wan* h, int batch, int height, int width, hipStream_t s) {
@@ -1118,11 +1126,7 @@ int wan_forward(fg_wan* h, const float* x_t, const float* t_frames, float* out, 
         HIP_TRY(launch_wan_add_r(w.temb, remb, (int64_t)BF * D, w.tproj, rproj, (int64_t)BF * 6 * D, s));
     }
     HIP_TRY(launch_wan_rope_table(h->tab_t, h->tab_h, h->tab_w, w.cs, L, fs, gw, cur_start_frame, c.rope_max_seq_len, h->npt, h->nph, h->npw, s));
-    if (h->is_i2v)  // the virtual concat [x_t | mask | first_frame_cond] (WanI2V/network.py:310-327)
-        HIP_TRY(launch_wan_i2v_patch_embed(x_t, h->ff, h->P(h->pe_w), h->P(h->pe_b), w.x0, batch, h->i2v.latent_channels, frames, height, width, D, s));
-    else  // (first-frame replacement: frame 0's tokens from the condition, `_replace_first_frame` WanI2V/network.py:254-277)
-        HIP_TRY(launch_wan_ti2v_patch_embed(x_t, h->is_ti2v ? h->ff0 : nullptr, h->P(h->pe_w), h->P(h->pe_b), w.x0, batch, c.in_channels, frames,
-                                            height, width, D, 0, s));
+    HIP_TRY(launch_wan_embed(wan_embed_src(h, x_t, frames, height, width), h->P(h->pe_w), h->P(h->pe_b), w.x0, batch, D, L, 0, s));
     void *x = w.x0, *xn = w.x1;
     int rc;
     const int64_t cbs = (int64_t)cap * D;

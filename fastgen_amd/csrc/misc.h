@@ -235,8 +235,22 @@ int launch_gemm_x3(const GemmArgs& a, int out_mode, hipStream_t s);
 int launch_split3_weights(const float* w, void* out, int N, int K, hipStream_t s);
 int launch_split_planes(const float* x, void* out, int64_t M, int K, hipStream_t s);
 
+// wan_embed.hip: the patch embedding of every Wan network, Conv3d(kernel = stride = (1,2,2)) + bias, w [D][Ct][4], bf16 tokens out.
+// The source view says where virtual channel c of a token comes from (C = latent channels):
+//   WAN_EMBED_PLAIN    x [B][C][Fr][H][W], Ct = C
+//   WAN_EMBED_FRAME0   the same with frame 0 read from alt [B][C][1][H][W] (Wan2.2 TI2V's first-frame replacement)
+//   WAN_EMBED_CONCAT   [x (C) | mask (4: ones on frame 0) | alt (C)], alt [B][C][Fr][H][W], Ct = 2 C + 4 (Wan2.1 I2V)
+enum { WAN_EMBED_PLAIN = 0, WAN_EMBED_FRAME0 = 1, WAN_EMBED_CONCAT = 2 };
+struct WanEmbedSrc {
+    const float *x, *alt;
+    int mode, C, Fr, H, W;
+};
+// Sample b's Fr gh gw tokens go to rows [b * out_rows, ...) of out (out_rows >= Fr gh gw; rows behind them stay untouched).  Every
+// kernel is bit-identical to the per-output one.  path 0: the plan's rule (rows in registers at plain Ct 16 and concat Ct 36, phased
+// sums at plain / frame-0 Ct 48 and plain Ct 96, else per output); 1: always per output; 2: the phased kernel or hipErrorInvalidValue.
+// D even wherever the plan is not per output or concat Ct 36.
+int launch_wan_embed(const WanEmbedSrc& src, const float* w, const float* bias, void* out, int B, int D, int64_t out_rows, int path, hipStream_t s);
 // wan.hip: the non-GEMM pieces of the causal video DiT (reference fastgen/networks/Wan/network_causal.py); bf16 token tensors
-int launch_wan_patch_embed(const float* x, const float* w, const float* bias, void* out, int B, int C, int Fr, int H, int W, int D, hipStream_t s);
 int launch_wan_mod(const float* table, const float* tproj, float* mod, int rows, int J, int D, hipStream_t s);
 int launch_wan_outmod(const float* table, const float* temb, float* mod, int rows, int D, hipStream_t s);
 int launch_silu(const float* x, float* y, int64_t n, hipStream_t s);
@@ -276,29 +290,18 @@ int launch_wan_final(int D, const void* x, const float* mod, const float* w, con
 int launch_wan_dual_xattn(const void* q, int ldq, int64_t q_bs, const void* k_txt, const void* v_txt, int ldk_txt, int64_t kv_bs_txt, int l_txt,
                           const void* k_img, const void* v_img, int ldk_img, int64_t kv_bs_img, int l_img, void* out, int ldo, int64_t o_bs, int B,
                           int heads, int Lq, hipStream_t s);
-// launch_wan_patch_embed on the virtual [x (C) | mask (4: ones on frame 0) | ff (C)] input; w [D][2 C + 4][4]
-int launch_wan_i2v_patch_embed(const float* x, const float* ff, const float* w, const float* bias, void* out, int B, int C, int Fr, int H, int W, int D,
-                               hipStream_t s);
 // fp32 LayerNorm (affine) of rows [rows][n] (fp32, or bf16 when in_bf16) into bf16; exact (erf) GELU in place on n bf16 values
 int launch_wan_ln_rows(int in_bf16, const void* x, const float* w, const float* b, void* y, int rows, int n, float eps, hipStream_t s);
 int launch_wan_gelu_erf(void* x, int64_t n, hipStream_t s);
-// wan_ti2v.hip: the two ends of the network at 48 latent channels (Wan2.2 TI2V-5B) and the first-frame replacement of that model's
-// image-to-video convention (reference fastgen/networks/WanI2V/network.py, concat_mask = False).  ff0 (nullable) [B][C][1][H][W]: the
-// source of frame 0's tokens / of frame 0 of the head's result.  path 0: the launcher's choice - the tiled kernels at C == 48, else
-// the kernels of wan.hip (launch_wan_patch_embed / launch_wan_final; with ff0 the per-output embedding with the second source, and a
-// copy of ff0 behind the head); 1: never the tiled kernels; 2: the tiled kernels or hipErrorInvalidValue.
-int launch_wan_ti2v_patch_embed(const float* x, const float* ff0, const float* w, const float* bias, void* out, int B, int C, int Fr, int H, int W,
-                                int D, int path, hipStream_t s);
+// wan_ti2v.hip: the output head at 48 latent channels (Wan2.2 TI2V-5B) and the first-frame replacement of that model's image-to-video
+// convention (reference fastgen/networks/WanI2V/network.py, concat_mask = False).  ff0 (nullable) [B][C][1][H][W]: the source of frame
+// 0 of the head's result.  path 0: the launcher's choice - the tiled kernel at C == 48, else launch_wan_final of wan.hip (and a copy of
+// ff0 behind the head); 1: never the tiled kernel; 2: the tiled kernel or hipErrorInvalidValue.
 int launch_wan_ti2v_final(int D, const void* x, const float* mod, const float* w, const float* bias, const float* ff0, float* out, int ntok, int Fr,
                           int gh, int gw, int C, float eps, int path, hipStream_t s);
 // dst[i] = i % Fr == 0 ? 0 : src[i] over n = rows of (sample, frame): the embedder rows under the first-frame mask (in place allowed)
 int launch_wan_ti2v_zero_frame0(const float* src, float* dst, int n, int Fr, hipStream_t s);
-// wan_vace.hip: the two ends of the VACE control branch (reference fastgen/networks/VaceWan/network.py).  The patch embedding of the
-// control video x [B][C][Fc][H][W]: sample b's Fc gh gw tokens go to rows [b * out_rows, ...) of out (out_rows >= Fc gh gw: the rows
-// behind them are the caller's zero padding and stay untouched).  path 0: the tiled kernel at C == 96, else wan.hip's per-output
-// kernel; 1: never the tiled kernel; 2: the tiled kernel or hipErrorInvalidValue.
-int launch_wan_vace_patch_embed(const float* x, const float* w, const float* bias, void* out, int B, int C, int Fc, int H, int W, int D,
-                                int64_t out_rows, int path, hipStream_t s);
+// wan_vace.hip: the control stream's first state and the hint scales (reference fastgen/networks/VaceWan/network.py)
 // c = ctx_in + x0 over n bf16 values (n % 8 == 0, 16-byte aligned), rounded once
 int launch_wan_vace_seed(const void* ctx_in, const void* x0, void* c, int64_t n, hipStream_t s);
 // rows [n][D] fp32 with rows[j][:] = sc.v[j] (n <= 64): the hint scales as gate rows, passed by value so that the fill is stream-ordered

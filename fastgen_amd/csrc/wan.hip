@@ -1,8 +1,7 @@
 // Causal video DiT (SURVEY 8(f)3 / 8(a) "CausVid"): the pieces of the reference's CausalWan forward that are not GEMMs
-// (fastgen/networks/Wan/network_causal.py; the block linears run on gemm.hip).  bf16 token tensors, fp32 statistics / softmax /
+// (fastgen/networks/Wan/network_causal.py; the block linears run on gemm.hip, the patch embedding is wan_embed.hip).  bf16 token tensors, fp32 statistics / softmax /
 // modulation: the arithmetic the reference runs this network in (`precision = "bfloat16"`, configs/experiments/WanT2V/config_sf.py:19;
 // the norms and the adaLN arithmetic in fp32: `_wan_block_forward_inline_cache`, :467-550).
-//   wan_patch_embed_kernel   Conv3d(kernel = stride = (1,2,2)) + bias, tokens ordered (frame, row, column)
 //   wan_mod_kernel           {shift, scale, gate} x {attention, feed-forward} = scale_shift_table + time_proj(silu(temb)) per frame (:478-480)
 //   wan_rope_table_kernel    cos / sin of the chunk's tokens with the temporal offset of `_rope_forward_with_time_offset` (:79-128)
 //   rms_rope_kernel          RMSNorm over the full inner dimension ("rms_norm_across_heads") * weight, interleaved-pair RoPE
@@ -24,71 +23,6 @@ __device__ __forceinline__ float wsum(float v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
     return v;
-}
-
-// The same for 16 latent channels (K = 64 inputs per token, every Wan 2.1 network): a workgroup stages 32 tokens' inputs in LDS
-// (8 KB) and every thread keeps the weight rows of TWO adjacent outputs in registers while it walks the 32 tokens (broadcast LDS
-// reads): each weight row is fetched once per 32 tokens instead of once per token - the per-output form below spent a 64-term dot
-// product's worth of scattered 4-byte loads on every output (412 us per call of the 1.3B network at 480p).
-__global__ __launch_bounds__(256) void wan_patch_embed16_kernel(const float* __restrict__ x, const float* __restrict__ w, const float* __restrict__ bias,
-                                                                __bf16* __restrict__ out, int B, int Fr, int H, int W, int D) {
-    constexpr int C = 16, K = 64, TOK = 32;
-    __shared__ __attribute__((aligned(16))) float xs[TOK][K];
-    const int gh = H / 2, gw = W / 2, fs = gh * gw;
-    const int64_t ntok = (int64_t)B * Fr * fs, tok0 = (int64_t)blockIdx.x * TOK;
-    const int tid = threadIdx.x;
-#pragma unroll
-    for (int i = 0; i < TOK * K / 256; ++i) {
-        const int idx = tid + 256 * i, tl = idx >> 6, k = idx & 63, c = k >> 2, py = (k >> 1) & 1, px = k & 1;
-        const int64_t tok = tok0 + tl < ntok ? tok0 + tl : ntok - 1;
-        const int hw = (int)(tok % fs), f = (int)((tok / fs) % Fr), b = (int)(tok / ((int64_t)fs * Fr));
-        const int gy = hw / gw, gx = hw - gy * gw;
-        xs[tl][k] = x[((((size_t)b * C + c) * Fr + f) * H + 2 * gy + py) * W + 2 * gx + px];
-    }
-    __syncthreads();
-    for (int d = 2 * tid; d < D; d += 512) {
-        f32x4 w0[16], w1[16];
-#pragma unroll
-        for (int q = 0; q < 16; ++q) {
-            w0[q] = *reinterpret_cast<const f32x4*>(w + (size_t)d * K + 4 * q);
-            w1[q] = *reinterpret_cast<const f32x4*>(w + (size_t)(d + 1) * K + 4 * q);
-        }
-        const float b0 = bias[d], b1 = bias[d + 1];
-        for (int t = 0; t < TOK && tok0 + t < ntok; ++t) {
-            float a0 = b0, a1 = b1;
-#pragma unroll
-            for (int q = 0; q < 16; ++q) {
-                const f32x4 xv = *reinterpret_cast<const f32x4*>(&xs[t][4 * q]);
-#pragma unroll
-                for (int e = 0; e < 4; ++e) a0 = fmaf(w0[q][e], xv[e], a0), a1 = fmaf(w1[q][e], xv[e], a1);
-            }
-            typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2_;
-            *reinterpret_cast<bf16x2_*>(out + (size_t)(tok0 + t) * D + d) = bf16x2_{(__bf16)a0, (__bf16)a1};
-        }
-    }
-}
-
-// x [B][C][F][H][W] fp32 -> tokens [B][F * gh * gw][D] bf16
-__global__ __launch_bounds__(256) void wan_patch_embed_kernel(const float* __restrict__ x, const float* __restrict__ w, const float* __restrict__ bias,
-                                                              __bf16* __restrict__ out, int B, int C, int Fr, int H, int W, int D) {
-    const int gh = H / 2, gw = W / 2, fs = gh * gw;
-    const int64_t total = (int64_t)B * Fr * fs * D;
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
-        const int d = (int)(i % D);
-        const int64_t tok = i / D;
-        const int hw = (int)(tok % fs), f = (int)((tok / fs) % Fr), b = (int)(tok / ((int64_t)fs * Fr));
-        const int gy = hw / gw, gx = hw - gy * gw;
-        float a = bias[d];
-        const float* wr = w + (size_t)d * C * 4;
-        for (int c = 0; c < C; ++c) {
-            const float* xp = x + ((((size_t)b * C + c) * Fr + f) * H + 2 * gy) * W + 2 * gx;
-            a = fmaf(wr[c * 4 + 0], xp[0], a);
-            a = fmaf(wr[c * 4 + 1], xp[1], a);
-            a = fmaf(wr[c * 4 + 2], xp[W], a);
-            a = fmaf(wr[c * 4 + 3], xp[W + 1], a);
-        }
-        out[i] = (__bf16)a;
-    }
 }
 
 // mod[bf][j][d] = table[j][d] + tproj[bf][j * D + d]
@@ -1398,18 +1332,6 @@ __global__ __launch_bounds__(256) void wan_final_kernel(const __bf16* __restrict
 
 }  // namespace
 
-int launch_wan_patch_embed(const float* x, const float* w, const float* bias, void* out, int B, int C, int Fr, int H, int W, int D, hipStream_t s) {
-    const int64_t total = (int64_t)B * Fr * (H / 2) * (W / 2) * D;
-    if (C == 16 && (D % 2) == 0) {
-        const int64_t ntok = (int64_t)B * Fr * (H / 2) * (W / 2);
-        hipLaunchKernelGGL(wan_patch_embed16_kernel, dim3((unsigned)((ntok + 31) / 32)), dim3(256), 0, s, x, w, bias, (__bf16*)out, B, Fr, H, W, D);
-        WAN_RET();
-    }
-    const int64_t blocks = (total + 255) / 256;
-    hipLaunchKernelGGL(wan_patch_embed_kernel, dim3((unsigned)(blocks > 262144 ? 262144 : blocks)), dim3(256), 0, s, x, w, bias, (__bf16*)out, B, C,
-                       Fr, H, W, D);
-    WAN_RET();
-}
 int launch_wan_mod(const float* table, const float* tproj, float* mod, int rows, int J, int D, hipStream_t s) {
     const int64_t n = (int64_t)rows * J * D;
     hipLaunchKernelGGL(wan_mod_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, table, tproj, mod, rows, J, D);

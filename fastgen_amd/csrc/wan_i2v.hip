@@ -1,9 +1,8 @@
 // Image-to-video on the bidirectional video DiT (reference fastgen/networks/WanI2V/network.py `WanI2V`, the Wan2.1-I2V convention:
-// concat_mask = True, use_image_encoder = True): what that network adds to wan.hip's kernels.
+// concat_mask = True, use_image_encoder = True): what that network adds to wan.hip's kernels.  (Its patch embedding of the virtual
+// concat [x_t | mask | first_frame_cond] is wan_embed.hip's concat view.)
 //   wan_dual_xattn_kernel        cross-attention of an I2V block: softmax(q K_txt^T) V_txt + softmax(q K_img^T) V_img, two independent
 //                                online softmaxes (steps 4 + 5 and `hidden_states + hidden_states_img` of Wan/network_causal.py:294-358)
-//   wan_i2v_patch_embed_kernel   patch embedding of the virtual concat [x_t | mask | first_frame_cond] (WanI2V/network.py:310-327);
-//   wan_i2v_patch_embed16_kernel   the LDS-staged form for 16 latent channels
 //   wan_ln_rows_kernel           the image embedder's FP32LayerNorm (eps 1e-5, affine) over fp32 or bf16 rows, bf16 out
 //   wan_gelu_erf_kernel          its exact (erf) GELU, in place on bf16 (the token GEMM's `act` knows the tanh form only)
 // PARITY UNPINNED like the rest of the video DiT: the image branch lives in un-vendored diffusers (WanTimeTextImageEmbedding's
@@ -184,87 +183,6 @@ __global__ __launch_bounds__(256, 2) void wan_dual_xattn_kernel(const __bf16* __
     }
 }
 
-// Tokens of the virtual 2 C + 4 channel input [x_t (C) | mask (4) | first_frame_cond (C)] with w [D][2 C + 4][1][2][2]: the mask is
-// never materialised - the reshuffle of WanI2V/network.py:311-327 leaves ones on latent frame 0 and zeros elsewhere, on all four
-// channels.  Channel order and fmaf chain of wan_patch_embed_kernel: bit-identical to that kernel on the concatenated tensor.
-__global__ __launch_bounds__(256) void wan_i2v_patch_embed_kernel(const float* __restrict__ x, const float* __restrict__ ff, const float* __restrict__ w,
-                                                                  const float* __restrict__ bias, __bf16* __restrict__ out, int B, int C, int Fr, int H,
-                                                                  int W, int D) {
-    const int gh = H / 2, gw = W / 2, fs = gh * gw, Ct = 2 * C + 4;
-    const int64_t total = (int64_t)B * Fr * fs * D;
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
-        const int d = (int)(i % D);
-        const int64_t tok = i / D;
-        const int hw = (int)(tok % fs), f = (int)((tok / fs) % Fr), b = (int)(tok / ((int64_t)fs * Fr));
-        const int gy = hw / gw, gx = hw - gy * gw;
-        float a = bias[d];
-        const float* wr = w + (size_t)d * Ct * 4;
-        const float mk = f == 0 ? 1.0f : 0.0f;
-        for (int c = 0; c < Ct; ++c) {
-            float x0, x1, x2, x3;
-            if (c >= C && c < C + 4) {
-                x0 = x1 = x2 = x3 = mk;
-            } else {
-                const float* src = c < C ? x : ff;
-                const int cc = c < C ? c : c - C - 4;
-                const float* xp = src + ((((size_t)b * C + cc) * Fr + f) * H + 2 * gy) * W + 2 * gx;
-                x0 = xp[0], x1 = xp[1], x2 = xp[W], x3 = xp[W + 1];
-            }
-            a = fmaf(wr[c * 4 + 0], x0, a);
-            a = fmaf(wr[c * 4 + 1], x1, a);
-            a = fmaf(wr[c * 4 + 2], x2, a);
-            a = fmaf(wr[c * 4 + 3], x3, a);
-        }
-        out[i] = (__bf16)a;
-    }
-}
-
-// The same for 16 latent channels (K = 144 inputs per token, Wan 2.1 I2V), in the form of wan_patch_embed16_kernel: a workgroup stages
-// 32 tokens' virtual inputs in LDS (18 KiB) and every thread keeps ONE output's weight row (144 floats) in registers while it walks
-// the 32 tokens (broadcast LDS reads) - the per-output form above fetches the row once per token with scattered 4-byte loads (24 ms per
-// call at the 14B widths and 480p x 21 frames).  The same fmaf chain in the same order: bit-identical to both.
-__global__ __launch_bounds__(256) void wan_i2v_patch_embed16_kernel(const float* __restrict__ x, const float* __restrict__ ff,
-                                                                    const float* __restrict__ w, const float* __restrict__ bias,
-                                                                    __bf16* __restrict__ out, int B, int Fr, int H, int W, int D) {
-    constexpr int C = 16, K = 4 * (2 * C + 4), TOK = 32;
-    __shared__ __attribute__((aligned(16))) float xs[TOK][K];
-    const int gh = H / 2, gw = W / 2, fs = gh * gw;
-    const int64_t ntok = (int64_t)B * Fr * fs, tok0 = (int64_t)blockIdx.x * TOK;
-    const int tid = threadIdx.x;
-    for (int idx = tid; idx < TOK * K; idx += 256) {
-        const int tl = idx / K, k = idx - tl * K, c = k >> 2, py = (k >> 1) & 1, px = k & 1;
-        const int64_t tok = tok0 + tl < ntok ? tok0 + tl : ntok - 1;
-        const int hw = (int)(tok % fs), f = (int)((tok / fs) % Fr), b = (int)(tok / ((int64_t)fs * Fr));
-        const int gy = hw / gw, gx = hw - gy * gw;
-        float v;
-        if (c >= C && c < C + 4) {
-            v = f == 0 ? 1.0f : 0.0f;
-        } else {
-            const float* src = c < C ? x : ff;
-            const int cc = c < C ? c : c - C - 4;
-            v = src[((((size_t)b * C + cc) * Fr + f) * H + 2 * gy + py) * W + 2 * gx + px];
-        }
-        xs[tl][k] = v;
-    }
-    __syncthreads();
-    for (int d = tid; d < D; d += 256) {
-        f32x4 wr[K / 4];
-#pragma unroll
-        for (int q = 0; q < K / 4; ++q) wr[q] = *reinterpret_cast<const f32x4*>(w + (size_t)d * K + 4 * q);
-        const float b0 = bias[d];
-        for (int t = 0; t < TOK && tok0 + t < ntok; ++t) {
-            float a = b0;
-#pragma unroll
-            for (int q = 0; q < K / 4; ++q) {
-                const f32x4 xv = *reinterpret_cast<const f32x4*>(&xs[t][4 * q]);
-#pragma unroll
-                for (int e = 0; e < 4; ++e) a = fmaf(wr[q][e], xv[e], a);
-            }
-            out[(size_t)(tok0 + t) * D + d] = (__bf16)a;
-        }
-    }
-}
-
 // One wave per row of n elements: y = (x - mean) * rsqrt(var + eps) * w + b in fp32 (two-pass statistics), bf16 out
 template <typename T>
 __global__ __launch_bounds__(256) void wan_ln_rows_kernel(const T* __restrict__ x, const float* __restrict__ w, const float* __restrict__ b,
@@ -305,19 +223,6 @@ int launch_wan_dual_xattn(const void* q, int ldq, int64_t q_bs, const void* k_tx
     hipLaunchKernelGGL(wan_dual_xattn_kernel, g, dim3(256), 32768, s, (const __bf16*)q, ldq, q_bs, (const __bf16*)k_txt, (const __bf16*)v_txt, ldk_txt,
                        kv_bs_txt, l_txt, (const __bf16*)k_img, (const __bf16*)v_img, ldk_img, kv_bs_img, l_img, (__bf16*)out, ldo, o_bs, Lq,
                        1.44269504088896341f / sqrtf(128.0f), heads, B);
-    return (int)hipGetLastError();
-}
-
-int launch_wan_i2v_patch_embed(const float* x, const float* ff, const float* w, const float* bias, void* out, int B, int C, int Fr, int H, int W, int D,
-                               hipStream_t s) {
-    if (C == 16) {
-        const int64_t ntok = (int64_t)B * Fr * (H / 2) * (W / 2);
-        hipLaunchKernelGGL(wan_i2v_patch_embed16_kernel, dim3((unsigned)((ntok + 31) / 32)), dim3(256), 0, s, x, ff, w, bias, (__bf16*)out, B, Fr, H, W, D);
-        return (int)hipGetLastError();
-    }
-    const int64_t total = (int64_t)B * Fr * (H / 2) * (W / 2) * D, blocks = (total + 255) / 256;
-    hipLaunchKernelGGL(wan_i2v_patch_embed_kernel, dim3((unsigned)(blocks > 262144 ? 262144 : blocks)), dim3(256), 0, s, x, ff, w, bias, (__bf16*)out, B,
-                       C, Fr, H, W, D);
     return (int)hipGetLastError();
 }
 

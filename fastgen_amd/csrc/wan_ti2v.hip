@@ -1,15 +1,12 @@
 // Wan2.2 TI2V-5B (reference fastgen/networks/WanI2V/network.py, concat_mask = False, expand_timesteps = True; Wan/network.py with 48
-// latent channels): the two ends of the network at 48 channels, where K = 4 C = 192 inputs per token and 4 C = 192 outputs per token
-// make the per-output patch embedding and the wave-per-token head of wan.hip re-read their whole weight once per token.
-//   wan_ti2v_patch_embed48_kernel   Conv3d(kernel = stride = (1,2,2)) + bias on 32-token tiles staged in LDS; every weight row is
-//                                   fetched once per tile.  The fmaf chain of wan_patch_embed_kernel in its order: bit-identical to it.
-//   wan_ti2v_patch_embed_kernel     wan_patch_embed_kernel with the second source (any channel count)
-//   wan_ti2v_final48_kernel         LayerNorm -> modulate -> proj_out (D -> 192) -> un-patchify on 32-token tiles: an fp32 tile
+// latent channels): the output head at 48 channels, where 4 C = 192 outputs per token make the wave-per-token head of wan.hip re-read
+// its whole weight once per token, and the first-frame mask of the time embedder.  (The patch embedding is wan_embed.hip.)
+//   wan_ti2v_final48_kernel        LayerNorm -> modulate -> proj_out (D -> 192) -> un-patchify on 32-token tiles: an fp32 tile
 //                                   product with the normalised tokens and the weight staged through LDS in chunks of 32 inputs
 //   wan_ti2v_zero_frame0_kernel     the embedder rows of latent frame 0 set to zero (`_compute_timestep_inputs` under the
 //                                   first-frame mask, WanI2V/network.py:334-340)
-// The optional second source `ff0` [B][C][1][H][W] is the first-frame condition: frame 0's tokens are read from it (the replaced
-// latents of `_replace_first_frame`, :254-277, are never materialised) and the head writes it into frame 0 of its result.
+// The optional second source `ff0` [B][C][1][H][W] is the first-frame condition: the head writes it into frame 0 of its result (the
+// replaced latents of `_replace_first_frame`, :254-277, are never materialised; the embedding reads frame 0's tokens from it).
 #include "common.h"
 #include "misc.h"
 
@@ -19,83 +16,6 @@ __device__ __forceinline__ float wsum_ti2v(float v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
     return v;
-}
-
-// x [B][48][F][H][W] fp32 -> tokens [B][F gh gw][D] bf16.  A workgroup stages 32 tokens' inputs in LDS (24 KiB, as [input quad][token]
-// so that a wave's staging loads walk image rows); a thread owns two adjacent outputs and keeps their 32 + 32 running sums in
-// registers while it takes the weight rows in four phases of 48 inputs (96 weight registers): a 192-float row does not fit beside
-// the sums.  Per output the sums run k = 0 .. 191 upwards from the bias, as wan_patch_embed_kernel's.
-__global__ __launch_bounds__(256) void wan_ti2v_patch_embed48_kernel(const float* __restrict__ x, const float* __restrict__ ff0,
-                                                                     const float* __restrict__ w, const float* __restrict__ bias,
-                                                                     __bf16* __restrict__ out, int B, int Fr, int H, int W, int D) {
-    constexpr int C = 48, K = 4 * C, TOK = 32, QP = 12, NPH = K / (4 * QP);
-    __shared__ f32x4 xs[K / 4][TOK];
-    const int gh = H / 2, gw = W / 2, fs = gh * gw;
-    const int64_t ntok = (int64_t)B * Fr * fs, tok0 = (int64_t)blockIdx.x * TOK;
-    const int tid = threadIdx.x;
-    float* xsf = reinterpret_cast<float*>(&xs[0][0]);
-#pragma unroll 4
-    for (int i = 0; i < TOK * K / 256; ++i) {
-        const int idx = tid + 256 * i, px = idx & 1, tl = (idx >> 1) & (TOK - 1), cp = idx >> 6, c = cp >> 1, py = cp & 1;
-        const int64_t tok = tok0 + tl < ntok ? tok0 + tl : ntok - 1;
-        const int hw = (int)(tok % fs), f = (int)((tok / fs) % Fr), b = (int)(tok / ((int64_t)fs * Fr));
-        const int gy = hw / gw, gx = hw - gy * gw;
-        const size_t pos = (size_t)(2 * gy + py) * W + 2 * gx + px;
-        const float v = (ff0 && f == 0) ? ff0[((size_t)b * C + c) * H * W + pos] : x[(((size_t)b * C + c) * Fr + f) * H * W + pos];
-        xsf[((size_t)c * TOK + tl) * 4 + 2 * py + px] = v;
-    }
-    __syncthreads();
-    for (int d = 2 * tid; d < D; d += 512) {
-        float a0[TOK], a1[TOK];
-        const float b0 = bias[d], b1 = bias[d + 1];
-#pragma unroll
-        for (int t = 0; t < TOK; ++t) a0[t] = b0, a1[t] = b1;
-#pragma unroll 1
-        for (int ph = 0; ph < NPH; ++ph) {
-            f32x4 w0[QP], w1[QP];
-#pragma unroll
-            for (int q = 0; q < QP; ++q) {
-                w0[q] = *reinterpret_cast<const f32x4*>(w + (size_t)d * K + 4 * (ph * QP + q));
-                w1[q] = *reinterpret_cast<const f32x4*>(w + (size_t)(d + 1) * K + 4 * (ph * QP + q));
-            }
-#pragma unroll
-            for (int t = 0; t < TOK; ++t)
-#pragma unroll
-                for (int q = 0; q < QP; ++q) {
-                    const f32x4 xv = xs[ph * QP + q][t];
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) a0[t] = fmaf(w0[q][e], xv[e], a0[t]), a1[t] = fmaf(w1[q][e], xv[e], a1[t]);
-                }
-        }
-        typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2_;
-#pragma unroll
-        for (int t = 0; t < TOK; ++t)
-            if (tok0 + t < ntok) *reinterpret_cast<bf16x2_*>(out + (size_t)(tok0 + t) * D + d) = bf16x2_{(__bf16)a0[t], (__bf16)a1[t]};
-    }
-}
-
-// wan_patch_embed_kernel (any channel count) with frame 0 read from ff0: the same chain, bit-identical to it on the replaced tensor
-__global__ __launch_bounds__(256) void wan_ti2v_patch_embed_kernel(const float* __restrict__ x, const float* __restrict__ ff0,
-                                                                   const float* __restrict__ w, const float* __restrict__ bias,
-                                                                   __bf16* __restrict__ out, int B, int C, int Fr, int H, int W, int D) {
-    const int gh = H / 2, gw = W / 2, fs = gh * gw;
-    const int64_t total = (int64_t)B * Fr * fs * D;
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
-        const int d = (int)(i % D);
-        const int64_t tok = i / D;
-        const int hw = (int)(tok % fs), f = (int)((tok / fs) % Fr), b = (int)(tok / ((int64_t)fs * Fr));
-        const int gy = hw / gw, gx = hw - gy * gw;
-        float a = bias[d];
-        const float* wr = w + (size_t)d * C * 4;
-        for (int c = 0; c < C; ++c) {
-            const float* xp = (f == 0 ? ff0 + ((size_t)b * C + c) * H * W : x + (((size_t)b * C + c) * Fr + f) * H * W) + (size_t)(2 * gy) * W + 2 * gx;
-            a = fmaf(wr[c * 4 + 0], xp[0], a);
-            a = fmaf(wr[c * 4 + 1], xp[1], a);
-            a = fmaf(wr[c * 4 + 2], xp[W], a);
-            a = fmaf(wr[c * 4 + 3], xp[W + 1], a);
-        }
-        out[i] = (__bf16)a;
-    }
 }
 
 // LayerNorm(eps, no affine) -> (1 + scale) y + shift with mod[tok / (gh gw)] = {shift, scale} [2][D] -> proj_out -> un-patchify for 48
@@ -209,24 +129,6 @@ __global__ void wan_ti2v_zero_frame0_kernel(const float* __restrict__ src, float
 }
 
 }  // namespace
-
-int launch_wan_ti2v_patch_embed(const float* x, const float* ff0, const float* w, const float* bias, void* out, int B, int C, int Fr, int H, int W,
-                                int D, int path, hipStream_t s) {
-    if (path < 0 || path > 2 || B <= 0 || C <= 0 || Fr <= 0 || H <= 0 || W <= 0 || (H & 1) || (W & 1) || D <= 0) return (int)hipErrorInvalidValue;
-    const bool tiled_ok = C == 48 && (D % 2) == 0;
-    if (path == 2 && !tiled_ok) return (int)hipErrorInvalidValue;
-    const int64_t ntok = (int64_t)B * Fr * (H / 2) * (W / 2);
-    if (tiled_ok && path != 1) {
-        hipLaunchKernelGGL(wan_ti2v_patch_embed48_kernel, dim3((unsigned)((ntok + 31) / 32)), dim3(256), 0, s, x, ff0, w, bias, (__bf16*)out, B, Fr, H,
-                           W, D);
-        return (int)hipGetLastError();
-    }
-    if (!ff0) return launch_wan_patch_embed(x, w, bias, out, B, C, Fr, H, W, D, s);
-    const int64_t blocks = (ntok * D + 255) / 256;
-    hipLaunchKernelGGL(wan_ti2v_patch_embed_kernel, dim3((unsigned)(blocks > 262144 ? 262144 : blocks)), dim3(256), 0, s, x, ff0, w, bias,
-                       (__bf16*)out, B, C, Fr, H, W, D);
-    return (int)hipGetLastError();
-}
 
 int launch_wan_ti2v_final(int D, const void* x, const float* mod, const float* w, const float* bias, const float* ff0, float* out, int ntok, int Fr,
                           int gh, int gw, int C, float eps, int path, hipStream_t s) {

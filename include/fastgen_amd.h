@@ -978,10 +978,11 @@ FG_API int fg_op_attention_ex(const void* q, int ldq, int64_t q_bs, const void* 
 FG_API int fg_op_wan_dual_cross_attention(const void* q, int ldq, int64_t q_bs, const void* k_txt, const void* v_txt, int ldk_txt,
                                           int64_t kv_bs_txt, int l_txt, const void* k_img, const void* v_img, int ldk_img, int64_t kv_bs_img,
                                           int l_img, void* out, int ldo, int64_t o_bs, int batch, int heads, int lq, void* stream);
-/* The two ends of the video DiT on their own (wan.hip / wan_ti2v.hip), for the per-element tests and timing.  first_frame (nullable)
- * [batch, channels, 1, height, width]: the second source - frame 0's tokens are computed from it / frame 0 of the head's result is
- * its copy.  path 0: what the engine launches (channels == 48: the tiled kernels of wan_ti2v.hip), 1: never the tiled kernels
- * (the per-output embedding / the wave-per-token head of wan.hip), 2: the tiled kernels, FG_EINVAL where they do not apply.
+/* The two ends of the video DiT on their own (wan_embed.hip; wan.hip / wan_ti2v.hip), for the per-element tests and timing.  first_frame
+ * (nullable) [batch, channels, 1, height, width]: the second source - frame 0's tokens are computed from it / frame 0 of the head's
+ * result is its copy.  path 0: what the engine launches (channels == 48: the phased embedding of wan_embed.hip, the tiled head of
+ * wan_ti2v.hip; 16 channels without a second source: the rows-in-registers embedding), 1: the per-output embedding / the
+ * wave-per-token head of wan.hip, 2: the 48-channel kernels, FG_EINVAL where they do not apply.  The embedding kernels are bit-identical.
  * fg_op_wan_patch_embed: x [batch, channels, frames, height, width] fp32, w [d, channels, 1, 2, 2], bias [d] -> tokens bf16
  * [batch, frames * height/2 * width/2, d].  fg_op_wan_final: tokens bf16 [batch * frames * gh * gw, d], mod [batch * frames][2][d]
  * {shift, scale}, w [4 * channels, d], bias [4 * channels] -> out fp32 [batch, channels, frames, 2 gh, 2 gw]; d in {256, 384, 1536,
@@ -990,9 +991,9 @@ FG_API int fg_op_wan_patch_embed(const float* x, const float* first_frame, const
                                  int frames, int height, int width, int d, int path, void* stream);
 FG_API int fg_op_wan_final(const void* tokens, const float* mod, const float* w, const float* bias, const float* first_frame, float* out, int batch,
                            int channels, int frames, int gh, int gw, int d, float eps, int path, void* stream);
-/* The control branch's patch embedding on its own (wan_vace.hip): fg_op_wan_patch_embed's arithmetic for up to 128 channels, without a
- * second source.  path 0: what fg_wan_set_vace_context launches (channels == 96: the tiled kernel), 1: the per-output kernel of
- * wan.hip, 2: the tiled kernel, FG_EINVAL unless channels == 96.  The two are bit-identical (one fmaf chain per output). */
+/* The control branch's patch embedding on its own (wan_embed.hip): fg_op_wan_patch_embed's arithmetic for up to 128 channels, without a
+ * second source.  path 0: what fg_wan_set_vace_context launches (channels == 96: the phased kernel), 1: the per-output kernel,
+ * 2: the phased kernel, FG_EINVAL unless channels == 96.  The two are bit-identical (one fmaf chain per output). */
 FG_API int fg_op_wan_vace_patch_embed(const float* x, const float* w, const float* bias, void* out, int batch, int channels, int frames, int height,
                                       int width, int d, int path, void* stream);
 /* The transformer blocks' token GEMM in the bf16 compute mode (gemm.hip; reference: the nn.Linear calls of DiTBlock,

@@ -18,7 +18,8 @@ Random-init weights of the 1.3B architecture, synthetic latents and text embeddi
 --i2v (with --bidirectional): the image-to-video network `WanI2V` (fastgen_amd/networks/WanI2V/network.py: 36 input channels, 257 CLIP
   image tokens of width 1280) next to `Wan` of the same widths and depth in the same run, one call at [1,16,21,60,104] each: the cost of
   the image branch (the dual cross-attention, the two-source patch embedding) is the difference of the two numbers.  Also the call
-  without image tokens, and the condition's own cost (fg_wan_set_i2v_cond, once per condition).
+  without image tokens, and the condition's own cost (fg_wan_set_i2v_cond, once per condition).  --trace=CALLS: one arm, `WanI2V` alone,
+  one warm-up + CALLS forwards and nothing else, for `rocprofv3 --kernel-trace --stats`.
 --bidirectional: the bidirectional network `Wan` (fastgen_amd/networks/Wan/network.py) instead, per arm next to the block-causal call of
   a `CausalWan` of the same weights in the same run: one call at [1,16,21,60,104] (full attention: 7 / 4 of the block mask's key
   pairs), the 4-step x0 student loop (FastGenModel.generator_fn, one hipGraph) and one guided step (the call at the stacked batch 2).
@@ -142,9 +143,12 @@ if "--bidirectional" in sys.argv and "--i2v" in sys.argv:
                         {"text_embeds": text1, "first_frame_cond": ff})
     for arm in ARMS:
         torch.manual_seed(0)
-        plain = Wan(num_attention_heads=H, ffn_dim=Fd, num_layers=LAYERS, compute_dtype=arm).cuda().eval()
+        plain = None if TRACE else Wan(num_attention_heads=H, ffn_dim=Fd, num_layers=LAYERS, compute_dtype=arm).cuda().eval()
         i2v = WanI2V(num_attention_heads=H, ffn_dim=Fd, num_layers=LAYERS, image_dim=1280, compute_dtype=arm).cuda().eval()
         with torch.inference_mode():
+            if TRACE:
+                window(lambda: i2v(x1, t1, condition=cond, fwd_pred_type="flow"), 1 + TRACE)
+                break
             med = side_by_side(f"{arm}: one call, {L} tokens, {LAYERS} layers, {WIDTHS}",
                                {"Wan": lambda: plain(x1, t1, condition=text1, fwd_pred_type="flow"),
                                 "WanI2V": lambda: i2v(x1, t1, condition=cond, fwd_pred_type="flow"),

@@ -1,7 +1,7 @@
-"""The two ends of the Wan2.2-TI2V-5B network on their own (fastgen_amd/csrc/wan_ti2v.hip) at the 5B shape [1, 48, 21, 44, 80], D 3072:
-the tiled 48-channel patch embedding and output head (path 2) against the kernels of wan.hip on the same inputs (path 1), through
-fg_op_wan_patch_embed / fg_op_wan_final, with and without the first-frame source.  us per launch from device events, median / min /
-max of 10 launches after 3 warm-ups.
+"""The output head of the Wan2.2-TI2V-5B network on its own (fastgen_amd/csrc/wan_ti2v.hip) at the 5B shape [1, 48, 21, 44, 80], D 3072:
+the tiled 48-channel head (path 2) against the wave-per-token head of wan.hip on the same inputs (path 1), through fg_op_wan_final, with
+and without the first-frame source.  us per launch from device events, median / min / max of 10 launches after 3 warm-ups.  (The patch
+embedding: scripts/wan_embed_bench.py.)
     python scripts/wan_ti2v_ops_bench.py"""
 import torch
 
@@ -11,12 +11,9 @@ from fastgen_amd.networks._engine import ptr
 B, C, F, H, W, D = 1, 48, 21, 44, 80, 3072
 L = _lib.lib()
 g = torch.Generator().manual_seed(0)
-x = torch.randn(B, C, F, H, W, generator=g).cuda()
 ff = torch.randn(B, C, 1, H, W, generator=g).cuda()
-w = (torch.randn(D, C * 4, generator=g) * 192 ** -0.5).cuda()
-b = torch.randn(D, generator=g).cuda()
 ntok = B * F * (H // 2) * (W // 2)
-tok = torch.empty(ntok, D, dtype=torch.bfloat16, device="cuda")
+tok = torch.randn(ntok, D, generator=g).bfloat16().cuda()
 mod = (0.5 * torch.randn(B * F, 2, D, generator=g)).cuda()
 wo = (torch.randn(4 * C, D, generator=g) * D ** -0.5).cuda()
 bo = torch.randn(4 * C, generator=g).cuda()
@@ -39,14 +36,8 @@ def timeit(fn, n=10, warm=3):
 res = {}
 for name, src in (("plain", None), ("first_frame", ff)):
     for path in (2, 1):
-        pe = lambda: _lib.check(L.fg_op_wan_patch_embed(ptr(x), ptr(src), ptr(w), ptr(b), ptr(tok), B, C, F, H, W, D, path, None))
-        res[("embed", name, path)] = timeit(pe)
-        print("patch_embed", name, "path", path, "us median/min/max", res[("embed", name, path)], flush=True)
-    t2 = tok.clone()
-    for path in (2, 1):
-        fn = lambda: _lib.check(L.fg_op_wan_final(ptr(t2), ptr(mod), ptr(wo), ptr(bo), ptr(src), ptr(out), B, C, F, H // 2, W // 2, D, 1e-6, path, None))
-        res[("final", name, path)] = timeit(fn)
-        print("final", name, "path", path, "us median/min/max", res[("final", name, path)], flush=True)
-for op in ("embed", "final"):
-    for name in ("plain", "first_frame"):
-        print(op, name, "ratio old/new", res[(op, name, 1)][0] / res[(op, name, 2)][0])
+        fn = lambda: _lib.check(L.fg_op_wan_final(ptr(tok), ptr(mod), ptr(wo), ptr(bo), ptr(src), ptr(out), B, C, F, H // 2, W // 2, D, 1e-6, path, None))
+        res[(name, path)] = timeit(fn)
+        print("final", name, "path", path, "us median/min/max", res[(name, path)], flush=True)
+for name in ("plain", "first_frame"):
+    print("final", name, "ratio old/new", res[(name, 1)][0] / res[(name, 2)][0])

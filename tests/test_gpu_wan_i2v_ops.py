@@ -1,4 +1,4 @@
-"""The image-to-video kernels per op (fastgen_amd/csrc/wan_i2v.hip) against fp64.
+"""The image-to-video kernels per op (fastgen_amd/csrc/wan_i2v.hip, the concat view of wan_embed.hip) against fp64.
 
 Dual cross-attention (fg_op_wan_dual_cross_attention), per ELEMENT: |got - want| <= bound(text) + bound(image) + U (A_txt + A_img) with
 tests/token_attention_ref.py's `bound` per context (derived there, not measured) and the last term for the kernel's sum: it rounds each

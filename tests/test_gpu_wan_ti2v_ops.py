@@ -1,5 +1,6 @@
-"""The two ends of the video DiT per op and per ELEMENT against fp64 (fastgen_amd/csrc/wan_ti2v.hip through fg_op_wan_patch_embed and
-fg_op_wan_final; path 0 / 2 = the tiled 48-channel kernels, path 1 = the per-output embedding and the wave-per-token head of wan.hip).
+"""The two ends of the video DiT per op and per ELEMENT against fp64 (fastgen_amd/csrc/wan_embed.hip through fg_op_wan_patch_embed and
+wan_ti2v.hip through fg_op_wan_final; path 0 / 2 = the tiled 48-channel kernels, path 1 = the per-output embedding and the wave-per-token
+head of wan.hip).
 Bounds are derived from the arithmetic, not measured (u = 2^-24, the unit roundoff of fp32; a sum of n terms in any order is off by at
 most n u sum |terms| to first order, taken with a 1 % allowance for the higher orders):
 

@@ -1,5 +1,5 @@
-"""The two ends of the VACE control branch per op and per ELEMENT against fp64 (fastgen_amd/csrc/wan_vace.hip through
-fg_op_wan_vace_patch_embed - path 0 / 2 = the tiled 96-channel kernel, path 1 = the per-output kernel of wan.hip - and through
+"""The two ends of the VACE control branch per op and per ELEMENT against fp64 (fastgen_amd/csrc/wan_embed.hip through
+fg_op_wan_vace_patch_embed - path 0 / 2 = the phased kernel at 96 channels, path 1 = the per-output kernel - and through
 fg_wan_set_vace_context / fg_wan_vace_context_read).  Bounds are derived from the arithmetic as tests/test_gpu_wan_ti2v_ops.py derives
 its own (u = 2^-24; a sum of n terms in any order is off by at most n u sum |terms| to first order, with a 1 % allowance):
 
@@ -68,12 +68,31 @@ def test_tiled_embedding_is_the_generic_one_bit_for_bit_and_both_meet_fp64(shape
         _lib.check(_lib.lib().fg_op_wan_vace_patch_embed(ptr(x[:, :48].contiguous()), ptr(w), ptr(b), ptr(tiled), Bc, 48, Fc, Hh, Ww, D, 2, None))
 
 
-@pytest.mark.parametrize("ctx_frames", [5, 3])
+def _straddle_case(vace_in):
+    """Batch 3, video [3, 16, 2, 4, 6] (12 tokens per sample), a context of 1 frame: 6 context tokens per sample, 18 in all - ONE 32-token
+    tile that crosses two sample boundaries and writes rows 0-5, 12-17, 24-29 of the padded context (out_rows = 12 > 6).  The
+    cases of wan_vace_ref.case() have 480 / 288 tokens per sample: whole tiles, no tile across a boundary.  vace_in 96: the phased
+    kernel; 32: the per-output kernel with padded rows."""
+    sd = V.random_state_dict(V.TINY, V.SEED, vace_in=vace_in)
+    g = torch.Generator().manual_seed(V.SEED + 2)
+    x = torch.randn(3, 16, 2, 4, 6, generator=g)
+    lat = torch.randn(3, vace_in // 3, 1, 4, 6, generator=g)
+    ctx = torch.cat([lat, torch.ones(3, vace_in - vace_in // 3, 1, 4, 6)], dim=1).contiguous()
+    return sd, x, {"ctx": ctx}
+
+
+@pytest.mark.parametrize("ctx_frames", [5, 3, pytest.param((1, 96), id="straddle-96"), pytest.param((1, 32), id="straddle-32")])
 def test_context_setter_against_fp64_and_padded_rows_are_the_bias(ctx_frames):
     from fastgen_amd.networks.VaceWan.network import VACEWan
 
-    sd, x, _, cond, _ = V.case("full" if ctx_frames == 5 else "short")
-    net = VACEWan(num_attention_heads=2, attention_head_dim=128, text_dim=128, ffn_dim=512, num_layers=3, vace_layers=V.VACE_LAYERS)
+    vace_in = V.VACE_IN
+    if isinstance(ctx_frames, tuple):
+        ctx_frames, vace_in = ctx_frames
+        sd, x, cond = _straddle_case(vace_in)
+    else:
+        sd, x, _, cond, _ = V.case("full" if ctx_frames == 5 else "short")
+    net = VACEWan(num_attention_heads=2, attention_head_dim=128, text_dim=128, ffn_dim=512, num_layers=3, vace_layers=V.VACE_LAYERS,
+                  vace_in_channels=vace_in)
     net.load_state_dict(sd, strict=True)
     net = net.cuda().eval()
     Bc, _, F, H, W = x.shape
