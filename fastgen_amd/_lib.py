@@ -159,6 +159,10 @@ SIGNATURES = {
     "fg_op_edm2_attention": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
     "fg_op_edm2_prep_weight": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_float, c_float, c_int, c_void_p]),
     "fg_op_edm2_pixel_norm": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
+    "fg_op_edm2_attention_jvp": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
+    "fg_op_edm2_pixel_norm_jvp": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
+    "fg_op_edm2_silu_operand_jvp": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p,
+                                            c_int, c_int, c_void_p]),
     "fg_op_linear": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
     "fg_op_adm_map_in": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p]),
     "fg_op_latents": (c_int, [c_void_p, c_double, c_void_p, c_int64, c_void_p]),
@@ -199,6 +203,11 @@ SIGNATURES = {
                                    POINTER(c_int), POINTER(c_int)]),
     "fg_edm2_run_block": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p,
                                   c_size_t, c_void_p]),
+    "fg_edm2_jvp_workspace_bytes": (c_size_t, [c_void_p, c_int]),
+    "fg_edm2_jvp": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_size_t,
+                            c_void_p]),
+    "fg_edm2_run_block_jvp": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
+                                      c_void_p, c_int, c_void_p, c_size_t, c_void_p]),
     "fg_dit_create": (c_int, [POINTER(fg_dit_config), POINTER(c_void_p)]),
     "fg_dit_destroy": (None, [c_void_p]),
     "fg_dit_num_params": (c_int, [c_void_p]),

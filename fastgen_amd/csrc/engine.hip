@@ -1438,6 +1438,7 @@ int fg_edm_run_block(fg_edm* h, int index, const float* x1, int c1, const float*
 #include "engine_wan.inc"    // the causal video DiT engine (fg_wan_*)
 #include "engine_sampler.inc"  // fg_dit_sampler_run / fg_wan_sampler_run: the student loops of the two transformer networks
 #include "engine_edm2.inc"     // the EDM2 U-Net engine (fg_edm2_*)
+#include "engine_edm2_jvp.inc"  // its forward-mode derivative (fg_edm2_jvp, fg_edm2_run_block_jvp, fg_op_edm2_*_jvp)
 #include "engine_train_ops.inc"  // fg_op_* entry points over the launchers of the training kernels (bwd.hip, attn_bwd.hip)
 #include "engine_edm_ops.inc"    // fg_op_edm_* entry points over the launchers of the SongUNet inference kernels
 

@@ -11,9 +11,10 @@ Parameters hold the raw (un-normalised) weights, as in the reference; the librar
 storage or version changes.  `supports_fused_loop("x0")` / `few_step_sample` let `FastGenModel.generator_fn` run the whole student
 loop as one library call (one hipGraph replay).
 
-Forward and sampling only, in the 'bf16x3' (default for fp32 tensors) and 'bf16' (under bf16 autocast) compute modes.  Autograd,
-train() mode with dropout, jvp, fully_shard, feature taps, r_timestep, the positional embedding, exact fp32, channels_per_head != 64
-and resample_filter != [1, 1] raise NotImplementedError.  There is no CPU path.
+Forward, sampling and `jvp` (the forward-mode derivative sCM's TrigFlowPrecond.jvp takes, fg_edm2_jvp), in the 'bf16x3' (default for
+fp32 tensors) and 'bf16' (under bf16 autocast) compute modes.  Autograd, train() mode with dropout, fully_shard, feature taps,
+r_timestep, the positional embedding, exact fp32, channels_per_head != 64 and resample_filter != [1, 1] raise NotImplementedError.
+There is no CPU path (`jvp` on CPU tensors raises NotImplementedError too).
 """
 from __future__ import annotations
 
@@ -190,8 +191,40 @@ class EDM2Precond(FastGenNetwork):
     def fully_shard(self, **kwargs):
         raise NotImplementedError("fully_shard is not implemented for EDM2 by the fused MI355X path (forward and sampling only)")
 
-    def jvp(self, *args, **kwargs):
-        raise NotImplementedError("jvp is not implemented for EDM2 by the fused MI355X path (forward and sampling only)")
+    @torch.no_grad()
+    def jvp(self, x_t: torch.Tensor, t: torch.Tensor, v_x: torch.Tensor, v_t: Optional[torch.Tensor] = None,
+            condition: Optional[torch.Tensor] = None, r: Optional[torch.Tensor] = None, v_r: Optional[torch.Tensor] = None,
+            fwd_pred_type: Optional[str] = None):
+        """(output, directional derivative) of `forward(x_t, t, condition=condition)` along (v_x, v_t) - what
+        `torch.func.jvp(net_wrapper, (x_t, t), tangents)` returns in sCM's TrigFlowPrecond.jvp (SCMModel._jvp) - as one library call
+        (fg_edm2_jvp): the primal and the tangent stream run block by block in the active compute mode, and the output is forward()'s
+        bit for bit.  The contract of EDMPrecond.jvp: no graph is built (the reference detaches the result too)."""
+        if fwd_pred_type is not None and fwd_pred_type != self.net_pred_type:
+            raise NotImplementedError("jvp is provided for the network's own prediction type")
+        if r is not None or v_r is not None:
+            raise ValueError("r / v_r provided, but EDM2 has no r_timestep")
+        self._refuse_training()
+        self._select_dtype()
+        if x_t.device.type != "cuda":  # no CPU path: not implemented, like the module's other refusals
+            raise NotImplementedError("EDM2Precond.jvp runs on a HIP GPU only (there is no CPU path); got a tensor on " + str(x_t.device))
+        R, C = self.img_resolution, self.img_channels
+        if x_t.dim() != 4 or tuple(x_t.shape[1:]) != (C, R, R):
+            raise ValueError(f"x_t must be [B,{C},{R},{R}], got {tuple(x_t.shape)}")
+        if v_x.shape != x_t.shape:
+            raise ValueError(f"v_x must have x_t's shape {tuple(x_t.shape)}, got {tuple(v_x.shape)}")
+        B, dev = x_t.shape[0], x_t.device
+        x32 = x_t.detach().to(torch.float32).contiguous()
+        vx = v_x.detach().to(device=dev, dtype=torch.float32).contiguous()
+        t64 = _engine.per_sample("t", t, B, dev, torch.float64)
+        vt = None if v_t is None else _engine.per_sample("v_t", v_t, B, dev, torch.float32)
+        labels = self._labels(condition, B, dev)
+        dt, h = self._engine(dev)
+        L = _lib.lib()
+        ws = self._eng.workspace(("jvp", dt), L.fg_edm2_jvp_workspace_bytes(h, B), dev)  # its own: forward()'s stays where a captured sampler saw it
+        out, jv = torch.empty_like(x32), torch.empty_like(x32)
+        _lib.check(L.fg_edm2_jvp(h, ptr(x32), ptr(t64), ptr(labels), ptr(vx), ptr(vt), ptr(out), ptr(jv), B, ptr(ws), ws.numel(),
+                                 self._stream(dev)))
+        return out.to(x_t.dtype), jv.to(x_t.dtype)
 
     def _c_noise(self, t64: torch.Tensor) -> torch.Tensor:
         if self.drop_precond in ("input", "both"):

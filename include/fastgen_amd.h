@@ -245,6 +245,18 @@ FG_API int fg_op_edm2_prep_weight(const float* w, float* out, int cout, int cin,
 /* Pixel norm x / (1e-4 + |x| / sqrt(c)) over the channels of every pixel, NHWC: down == 0: x, out [batch][h][h][c], out == x allowed;
  * down == 1: x [batch][2h][2h][c] is averaged over 2x2 first (out must not alias x). */
 FG_API int fg_op_edm2_pixel_norm(const float* x, float* out, int batch, int h, int c, int down, void* stream);
+/* ---- EDM2 tangent kernels (the ones fg_edm2_jvp runs beside the forward's), same checks.  `_d` is a tangent. */
+/* jvp of fg_op_edm2_attention in one pass over the keys: qkv_d in qkv's layout, out_d [batch][t][heads * 64]; out (nullable) receives
+ * the primal, bit-equal to fg_op_edm2_attention.  Row x with n = 1e-4 + |x| / 8: x^_d = x_d / n - x (x . x_d) / (8 |x| n^2), 0 where
+ * |x| = 0. */
+FG_API int fg_op_edm2_attention_jvp(const float* qkv, const float* qkv_d, float* out, float* out_d, int batch, int t, int heads, void* stream);
+/* jvp of fg_op_edm2_pixel_norm: with down == 1 both x and x_d are averaged over 2x2 first.  out_d == x_d allowed with down == 0. */
+FG_API int fg_op_edm2_pixel_norm_jvp(const float* x, const float* x_d, float* out_d, int batch, int h, int c, int down, void* stream);
+/* The tangent convolution's operand behind a SiLU prologue, out [batch][hw][c1 + c2] = silu'(a x + b) (a x_d + a_d x) over the virtual
+ * concat [x1 | x2] (tangents d1 | d2): {a, b} = ab[2 * (img * ab_stride + c)] (float pairs; ab_stride 0: one row for every image),
+ * a_d = ad ? ad[img * ad_stride + c] : 0.  c1, c2 multiples of 4; tensors 16-byte aligned. */
+FG_API int fg_op_edm2_silu_operand_jvp(const float* x1, const float* x2, const float* d1, const float* d2, int c1, int c2, const float* ab,
+                                       int ab_stride, const float* ad, int ad_stride, float* out, int batch, int hw, void* stream);
 /* y [batch][out] = act(x [batch][in] w[out][in]^T + bias): the linear layer of all four engines (embeddings, modulations).  bias nullable;
  * act_silu != 0: SiLU after the bias.  Shapes with in % 16 == 0 and out % 32 == 0 run on the fp32 matrix pipe with 16-byte loads: there
  * x and w must be 16-byte aligned (FG_EINVAL otherwise; the engines' buffers always are).  Every other shape runs the FMA kernel, which
@@ -1146,6 +1158,19 @@ FG_API int fg_edm2_block_info(const fg_edm2* h, int index, const char** key, int
                               int* has_attention);
 FG_API int fg_edm2_run_block(fg_edm2* h, int index, const float* x1, int c1, const float* x2, int c2, const float* emb, float* out,
                              int batch, void* workspace, size_t workspace_bytes, void* stream);
+/* Forward-mode derivative of fg_edm2_forward along (vx [B, C, R, R], vt fp32 [B] or NULL = 0) - what torch.func.jvp of
+ * EDM2Precond.forward(x_t, t) returns: out = fg_edm2_forward's output, bit for bit (the same kernels in the same order), jvp its
+ * directional derivative, both NCHW fp32.  The primal and the tangent run block by block, interleaved; the compute mode applies to the
+ * convolutions of both, everything else is fp32.  The clamp's tangent is 0 where the clamped activation has |y| >= clip_act
+ * (torch passes it where the unclamped value equals +-clip_act exactly).  Workspace: fg_edm2_jvp_workspace_bytes (256-byte aligned); a
+ * smaller one is FG_EINVAL.  Arguments are checked before anything is launched. */
+FG_API size_t fg_edm2_jvp_workspace_bytes(const fg_edm2* h, int batch);
+FG_API int fg_edm2_jvp(fg_edm2* h, const float* x_t, const double* t, const float* class_labels, const float* vx, const float* vt,
+                       float* out, float* jvp, int batch, void* workspace, size_t workspace_bytes, void* stream);
+/* fg_edm2_run_block with tangents (x1_d, x2_d, emb_d -> out_d): workspace of fg_edm2_jvp_workspace_bytes. */
+FG_API int fg_edm2_run_block_jvp(fg_edm2* h, int index, const float* x1, const float* x1_d, int c1, const float* x2, const float* x2_d,
+                                 int c2, const float* emb, const float* emb_d, float* out, float* out_d, int batch, void* workspace,
+                                 size_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }
