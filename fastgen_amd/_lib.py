@@ -257,6 +257,17 @@ SIGNATURES = {
     "fg_wan_full_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int, c_int, c_int]),
     "fg_wan_forward_full": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, POINTER(c_int), c_int, c_void_p,
                                     c_size_t, c_void_p]),
+    "fg_wan_jvp_workspace_bytes": (c_size_t, [c_void_p, c_int, c_int, c_int, c_int]),
+    "fg_wan_jvp": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
+                           POINTER(c_int), c_int, c_void_p, c_size_t, c_void_p]),
+    "fg_op_wan_attention_jvp": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int64, c_void_p, c_void_p,
+                                        c_int, c_int64, c_int, c_int, c_int, c_int, c_void_p]),
+    "fg_op_wan_modulate_jvp": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_float,
+                                       c_void_p]),
+    "fg_op_wan_rms_rope_jvp": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_float, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
+    "fg_op_wan_gelu_jvp": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
+    "fg_op_wan_final_jvp": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int,
+                                    c_int, c_float, c_void_p]),
     "fg_wan_forward_full_features": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, POINTER(c_int), c_int,
                                              POINTER(c_int), POINTER(fg_wan_block_taps), c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t,
                                              c_void_p]),

@@ -1436,6 +1436,7 @@ int fg_edm_run_block(fg_edm* h, int index, const float* x1, int c1, const float*
 #include "engine_train.inc"  // block / network backward, forward-mode pass and their entry points
 #include "engine_dit.inc"    // the DiT engine (fg_dit_*)
 #include "engine_wan.inc"    // the causal video DiT engine (fg_wan_*)
+#include "engine_wan_jvp.inc"  // the bidirectional call's forward-mode derivative (fg_wan_jvp, fg_op_wan_*_jvp)
 #include "engine_sampler.inc"  // fg_dit_sampler_run / fg_wan_sampler_run: the student loops of the two transformer networks
 #include "engine_edm2.inc"     // the EDM2 U-Net engine (fg_edm2_*)
 #include "engine_edm2_jvp.inc"  // its forward-mode derivative (fg_edm2_jvp, fg_edm2_run_block_jvp, fg_op_edm2_*_jvp)

@@ -284,6 +284,26 @@ int launch_fa128(const void* q, int ldq, int64_t q_bs, const void* k, const void
                  int B, int heads, int Lq, int Lkv, hipStream_t s, void* scratch = nullptr);
 int launch_wan_final(int D, const void* x, const float* mod, const float* w, const float* bias, float* out, int ntok, int Fr, int gh, int gw, int C,
                      float eps, hipStream_t s);
+// wan_jvp.hip: the non-GEMM pieces of the bidirectional video DiT's forward-mode derivative: a primal and a tangent stream, bf16 tokens
+// LayerNorm-modulate with tangent: x, xd, y, yd bf16 [ntok][D]; mod / modd fp32 rows of mod_stride (row = token / tokens_per_row),
+// modd nullable (a constant affine); even stride / offsets
+int launch_wan_ln_modulate_jvp(int D, const void* x, const void* xd, const float* mod, const float* modd, int mod_stride, int shift_off,
+                               int scale_off, void* y, void* yd, int ntok, int tokens_per_row, float eps, hipStream_t s);
+// launch_rms_rope (w != nullptr, dst_row0 = 0) with tangent: srcd / dstd laid out as src / dst
+int launch_wan_rms_rope_jvp(int D, const void* src, const void* srcd, int ld_src, const float* w, float eps, const float2* cs, void* dst, void* dstd,
+                            int64_t dst_bs, int ld_dst, int rows, int L, hipStream_t s);
+// launch_fa128's operands with tangents: qd laid out as q, kd / vd as k / v, outd as out; qd, kd, vd nullable (= 0).  Nothing is read
+// past key Lkv - 1.
+int launch_wan_attention_jvp(const void* q, const void* qd, int ldq, int64_t q_bs, const void* k, const void* v, const void* kd, const void* vd,
+                             int ldk, int64_t kv_bs, void* out, void* outd, int ldo, int64_t o_bs, int B, int heads, int Lq, int Lkv,
+                             hipStream_t s);
+// a = gelu_tanh(h), ad = gelu_tanh'(h) hd over n bf16 values (n % 4 == 0); a / ad may be h / hd
+int launch_wan_gelu_jvp(const void* h, const void* hd, void* a, void* ad, int64_t n, hipStream_t s);
+// modd[r][0][:] = modd[r][1][:] = tembd[r][:] (the tangent of launch_wan_outmod's rows)
+int launch_wan_dup2(const float* tembd, float* modd, int rows, int D, hipStream_t s);
+// launch_wan_final with tangent: xd as x, modd as mod, outd as out
+int launch_wan_final_jvp(int D, const void* x, const void* xd, const float* mod, const float* modd, const float* w, const float* bias, float* out,
+                         float* outd, int ntok, int Fr, int gh, int gw, int C, float eps, hipStream_t s);
 // wan_i2v.hip: what the image-to-video network adds (reference fastgen/networks/WanI2V/network.py, the Wan2.1-I2V convention)
 // softmax(q k_txt^T / sqrt(128)) v_txt + softmax(q k_img^T / sqrt(128)) v_img, head dim 128, operands as launch_fa128's; l_img == 0:
 // the text term alone.  Nothing is read past key l_txt - 1 / l_img - 1.

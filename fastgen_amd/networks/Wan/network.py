@@ -159,6 +159,63 @@ class Wan(WanEngineNetwork):
         return self.noise_scheduler.convert_model_output(x_t, out.to(x_t.dtype), _engine.per_sample("t", t_in, B, dev),
                                                          src_pred_type=self.net_pred_type, target_pred_type=fwd_pred_type)
 
+    @torch.no_grad()
+    def jvp(self, x_t: torch.Tensor, t: torch.Tensor, v_x: torch.Tensor, v_t: Optional[torch.Tensor] = None, condition: Optional[Any] = None,
+            r: Optional[torch.Tensor] = None, v_r: Optional[torch.Tensor] = None, fwd_pred_type: Optional[str] = None):
+        """(output, directional derivative) of `forward(x_t, t, condition=condition, r=r)` along (v_x, v_t, v_r) - what
+        `torch.func.jvp(net_wrapper, (x_t, t, r), tangents)` would return in MeanFlowModel._jvp (mean_flow.py:240-250; the reference
+        itself falls back to a finite difference for this network) - as one library call (`fg_wan_jvp`: a bf16 tangent stream beside
+        the bf16 primal stream).  Forward-only and stateless: no graph is built.  `forward()`'s preparation of (t, r) - `rescale_t`,
+        one row per frame - is applied here, and its derivative to (v_t, v_r); under time_cond_type "diff" the engine forms t - r and
+        v_t - v_r.  Raises NotImplementedError (never falls back): compute_dtype "fp8", the image-to-video and VACE subclasses, another
+        prediction type than the network's own, CPU tensors."""
+        L = _lib.lib()
+        # the handle's kind first (an image-to-video or VACE subclass, the fp8 mode): its refusal comes before any look at the shapes,
+        # which those networks define differently
+        if L.fg_wan_jvp_workspace_bytes(self._h, 1, 1, 2, 2) == 0:
+            raise NotImplementedError(f"fastgen_amd.{type(self).__name__}.jvp: this network has no forward-mode derivative (a plain "
+                                      f"text-to-video Wan in the bf16 compute mode has one)")
+        if fwd_pred_type is not None and fwd_pred_type != self.net_pred_type:
+            raise NotImplementedError("jvp is provided for the network's own prediction type")
+        if r is None and self.r_timestep:
+            raise ValueError("this network was built with r_timestep=True: jvp() needs r")
+        if r is not None and not self.r_timestep:
+            raise ValueError("r_timestep provided but no r_embedder is present")
+        if not x_t.is_cuda:
+            raise NotImplementedError("fastgen_amd.Wan.jvp runs on a HIP GPU only (no CPU path)")
+        B, F, H, W = self._check_video(x_t, "x_t")
+        if v_x.shape != x_t.shape:
+            raise ValueError(f"v_x must be shaped like x_t {tuple(x_t.shape)}, got {tuple(v_x.shape)}")
+        need = L.fg_wan_jvp_workspace_bytes(self._h, B, F, H, W)
+        if need == 0:
+            raise ValueError(f"bad video shape: batch {B}, frames {F}, {H}x{W} (height and width must be even)")
+        dev = x_t.device
+        condition = self._text(condition)
+        sch = self.noise_scheduler
+
+        def rows(v):  # one embedder row per frame, as forward() builds them
+            return v.to(torch.float32).view(B, 1).expand(B, F).contiguous()
+
+        def tangent(name, v):  # the derivative of rescale_t, a multiplication by num_steps or 1
+            if v is None:
+                return None
+            return rows(sch._rescale(_engine.per_sample(name, v, B, dev).to(torch.float32)))
+
+        ts = rows(sch.rescale_t(_engine.per_sample("t", torch.atleast_1d(t.detach()).to(dev), B, dev)))
+        rs = rows(sch.rescale_t(_engine.per_sample("r", r, B, dev))) if r is not None else None
+        vts, vrs = tangent("v_t", v_t), (tangent("v_r", v_r) if r is not None else None)
+        self._bind(dev)
+        # a workspace of its own, also for the text embedding's scratch (the query at the smallest video is that scratch): forward()'s is
+        # neither used nor regrown here, it stays where a captured sampler saw it
+        ws = self._eng.workspace(("jvp", self._cfg.compute_dtype), max(need, L.fg_wan_full_workspace_bytes(self._h, B, 1, 2, 2)), dev)
+        self._set_text(condition, B, dev, ws)
+        x32 = x_t.detach().to(torch.float32).contiguous()
+        vx = v_x.detach().to(device=dev, dtype=torch.float32).contiguous()
+        out, jv = torch.empty_like(x32), torch.empty_like(x32)
+        _lib.check(L.fg_wan_jvp(self._h, ptr(x32), ptr(ts), ptr(rs), ptr(vx), ptr(vts), ptr(vrs), ptr(out), ptr(jv), B, F, H, W, None, 0, ptr(ws),
+                                ws.numel(), self._stream(dev)))
+        return out.to(x_t.dtype), jv.to(x_t.dtype)
+
     # ---- the student loops over the whole video as one library call --------------------------------------------------------------
     def supports_fused_loop(self, kind: str) -> bool:
         """Which loops `fg_wan_full_sampler_run` restates for this network: 'x0' (FastGenModel._student_sample_loop; flow- or

@@ -786,6 +786,39 @@ FG_API int fg_wan_forward_full_features(fg_wan* h, const float* x_t, const float
                                         int frames, int height, int width, const int* skip_layers, int num_skip, const int* tap_blocks,
                                         const fg_wan_block_taps* taps, int num_taps, float* tokens_out, float* temb_out, float* tproj_out,
                                         void* workspace, size_t workspace_bytes, void* stream);
+/* Forward-mode derivative of fg_wan_forward_full (Wan.jvp; MeanFlow's tangent): out = net(x_t, t, r) and jvp = d net . (v_x, vt, vr),
+ * both [B, C, frames, H, W] fp32, from one schedule that carries a bf16 tangent stream beside the bf16 primal stream (engine_wan_jvp.inc,
+ * kernels wan_jvp.hip).  t_frames, r_frames (nullable, needs the r_embedder), vt_frames, vr_frames (nullable = 0): one fp32 row entry per
+ * (sample, frame), as fg_wan_forward_full takes them; under time_cond_diff the engine forms t - r and vt - vr itself.  The text is
+ * fg_wan_set_text's.  `out` is fg_wan_forward_full's result up to bf16 rounding (the GELU runs on the stored bf16 pre-activation and
+ * the attention kernel is the jvp's own), not to the bit.  Stateless and forward-only.  FG_EINVAL with a message, and a workspace
+ * query of 0: an fp8, image-to-video (i2v / ti2v) or VACE handle; FG_EINVAL: skip_layers (non-null or num_skip != 0 - the arguments
+ * exist so that a caller's skip list is refused instead of ignored), out aliasing x_t / v_x, jvp aliasing any argument, vr_frames
+ * without r_frames.  FG_ENOMEM: a workspace smaller than fg_wan_jvp_workspace_bytes. */
+FG_API size_t fg_wan_jvp_workspace_bytes(const fg_wan* h, int batch, int frames, int height, int width);
+FG_API int fg_wan_jvp(fg_wan* h, const float* x_t, const float* t_frames, const float* r_frames, const float* v_x, const float* vt_frames,
+                      const float* vr_frames, float* out, float* jvp, int batch, int frames, int height, int width, const int* skip_layers,
+                      int num_skip, void* workspace, size_t workspace_bytes, void* stream);
+/* Exposed for the per-op tests (tests/test_gpu_wan_jvp_ops.py) and timings: the kernels of wan_jvp.hip on their own; bf16 token tensors.
+ * fg_op_wan_attention_jvp: fg_op_attention_ex's operands (head dim 128) with tangents - qd as q, kd / vd as k / v, outd as out; qd,
+ * kd, vd nullable (= 0); nothing is read past key lkv - 1.  ldq, ldk, q_bs, kv_bs % 8 and 16-byte aligned q / qd / k / v / kd / vd; ldo,
+ * o_bs % 4 and 8-byte aligned out / outd (FG_EINVAL otherwise).
+ * fg_op_wan_modulate_jvp: y = LN(x) (1 + s) + b and its tangent; mod / modd fp32 rows of mod_stride floats (row = token /
+ * tokens_per_row) with shift at shift_off and scale at scale_off; modd nullable (a constant affine).  d: 256, 384, 1536, 2048, 3072, 5120.
+ * fg_op_wan_rms_rope_jvp: RMSNorm over d times w, then the pair rotation cs [l][64] {cos, sin} (nullable: none), rows [rows][ld_src] ->
+ * [rows][d], token = row % l.
+ * fg_op_wan_gelu_jvp: a = gelu_tanh(h), ad = gelu_tanh'(h) hd over n values (n % 4 == 0; a / ad may be h / hd).
+ * fg_op_wan_final_jvp: fg_op_wan_final's wave-per-token head with tangent (modd laid out as mod: [B * frames][2][d]). */
+FG_API int fg_op_wan_attention_jvp(const void* q, const void* qd, int ldq, int64_t q_bs, const void* k, const void* v, const void* kd,
+                                   const void* vd, int ldk, int64_t kv_bs, void* out, void* outd, int ldo, int64_t o_bs, int batch, int heads,
+                                   int lq, int lkv, void* stream);
+FG_API int fg_op_wan_modulate_jvp(const void* x, const void* xd, const float* mod, const float* modd, int mod_stride, int shift_off, int scale_off,
+                                  void* y, void* yd, int ntok, int d, int tokens_per_row, float eps, void* stream);
+FG_API int fg_op_wan_rms_rope_jvp(const void* src, const void* srcd, int ld_src, const float* w, float eps, const float* cs, void* dst, void* dstd,
+                                  int rows, int l, int d, void* stream);
+FG_API int fg_op_wan_gelu_jvp(const void* h, const void* hd, void* a, void* ad, int64_t n, void* stream);
+FG_API int fg_op_wan_final_jvp(const void* tokens, const void* tokens_d, const float* mod, const float* modd, const float* w, const float* bias,
+                               float* out, float* outd, int batch, int channels, int frames, int gh, int gw, int d, float eps, void* stream);
 /* The few-step student loops over the whole video as ONE call and one hipGraph, as fg_dit_sampler_run: loop_kind FG_LOOP_X0
  * (`FastGenModel._student_sample_loop`, methods/model.py:315-372) or FG_LOOP_MEANFLOW (`MeanFlowModel._student_sample_loop`,
  * consistency_model/mean_flow.py:336-381: r = 0 for 'sde', t_{i+1} for 'ode'; needs the r_embedder and net_pred_flow, else FG_EINVAL).
