@@ -365,12 +365,12 @@ int check_sampler_args(const double* t_list, int steps, int sample_type, int loo
 // graph keyed by the call's shape, its host-decided branches (zero_mask) and what the entry point adds in `more` (its buffers, settings).
 template <typename F>
 int sampler_launch(SamplerCache& st, int batch, const double* t_list, int steps, int sample_type, int loop_kind, uint64_t seed, double* tl_dev,
-                   uint64_t* seed_dev, bool use_graph, std::initializer_list<int64_t> more, hipStream_t s, F&& enqueue) {
+                   uint64_t* seed_dev, bool use_graph, const std::vector<int64_t>& more, hipStream_t s, F&& enqueue) {
     const int rc = st.ring.upload(t_list, steps + 1, seed, tl_dev, seed_dev, s);
     if (rc) return rc;
     if (!use_graph) return enqueue(s);
     std::vector<int64_t> key = {batch, steps, sample_type, loop_kind, zero_mask(t_list, steps)};
-    key.insert(key.end(), more);
+    key.insert(key.end(), more.data(), more.data() + more.size());
     return graph_run(st.graph, key, st.cap, s, enqueue);
 }
 

@@ -171,7 +171,7 @@ void wan_chunks(int frames, int chunk, std::vector<std::pair<int, int>>& out) {
 extern "C" {
 
 size_t fg_wan_sampler_workspace_bytes(const fg_wan* h, int batch, int frames, int height, int width) {
-    if (!h || batch <= 0 || frames <= 0 || height <= 0 || width <= 0 || (height & 1) || (width & 1)) return 0;
+    if (!h || !wan_shape_ok(batch, frames, height, width)) return 0;
     const int chunk = h->cfg.chunk_size, fmax = frames < chunk ? frames : chunk + frames % chunk;
     Arena A;
     A.dry = true;
@@ -183,13 +183,10 @@ int fg_wan_sampler_run(fg_wan* h, const fg_wan_sampler_config* sc, float* x, con
                        const float* eps, uint64_t seed, int batch, int frames, int height, int width, void* workspace, size_t workspace_bytes,
                        int use_graph, void* stream) {
     if (!h || !sc || !x || !t_list) return fail(FG_EINVAL, "null argument");
-    if (h->is_i2v || h->is_ti2v) return fail(FG_EINVAL, "the chunked / causal loops are not implemented for an image-to-video handle");
-    if (h->is_vace) return fail(FG_EINVAL, "the chunked / causal loops are not implemented for a VACE handle");
-    int rc = check_sampler_args(t_list, steps, sample_type, FG_LOOP_X0, sc->schedule);
-    if (rc) return rc;
+    int rc;
+    if ((rc = wan_refuse_chunked(h, "loops")) || (rc = check_sampler_args(t_list, steps, sample_type, FG_LOOP_X0, sc->schedule))) return rc;
     if (!(sc->t_scale > 0.0)) return fail(FG_EINVAL, "t_scale must be positive");
-    if (batch <= 0 || frames <= 0 || frames > h->cfg.total_num_frames || height <= 0 || width <= 0 || (height & 1) || (width & 1) || !workspace ||
-        (((uintptr_t)workspace) & 255))
+    if (!wan_shape_ok(batch, frames, height, width) || frames > h->cfg.total_num_frames || !workspace || (((uintptr_t)workspace) & 255))
         return fail(FG_EINVAL, "bad batch / frames (<= total_num_frames = %d) / size / workspace", h->cfg.total_num_frames);
     const int chunk = h->cfg.chunk_size, prefill = sc->prefill_frames;
     if (prefill < 0 || prefill >= frames || (prefill > 0 && ((prefill % chunk) || (frames % chunk))))
@@ -209,13 +206,13 @@ int fg_wan_sampler_run(fg_wan* h, const fg_wan_sampler_config* sc, float* x, con
     const size_t need = wan_sampler_plan(h, batch, fmax, height, width, A, w);
     if (need > workspace_bytes) return fail(FG_ENOMEM, "workspace too small: need %zu bytes, got %zu", need, workspace_bytes);
     if (!h->packed) return fail(FG_ENOTREADY, "weights are not packed (call fg_wan_pack_weights)");
-    if (h->text_B != batch) return fail(FG_ENOTREADY, "no text condition for batch %d (call fg_wan_set_text)", batch);
+    if ((rc = wan_conditions_ready(h, batch, frames, height, width))) return rc;
     hipStream_t s = (hipStream_t)stream;
     // `net.clear_caches()` of the loop's first line (causvid.py:113): nothing is stored any more.  (No memset here: this loop writes every
     // cache row before any call reads it; the clear at the end of the loop leaves the buffers zeroed for whoever calls next.  The text
     // condition stays: the caller set it for THIS call.)
     if ((rc = wan_ensure_caches(h, batch, height, width, s))) return rc;  // (allocation must not fall inside a capture)
-    h->stored_rows = 0;
+    h->cur.stored_rows = 0;
     SamplerCache& st = h->sampler;
     if ((rc = st.ring.upload(t_list, steps + 1, seed, w.tl, w.seed, s))) return rc;
     if (h->chunk_graphs.size() < chunks.size()) h->chunk_graphs.resize(chunks.size());
@@ -277,18 +274,18 @@ int fg_wan_sampler_run(fg_wan* h, const fg_wan_sampler_config* sc, float* x, con
         int64_t tsb, cnb;
         memcpy(&tsb, &sc->t_scale, 8);
         memcpy(&cnb, &sc->context_noise, 8);
-        const std::vector<int64_t> key = {batch, frames, height, width, steps, sample_type, last, f0, f1, fill_only, zero_mask(t_list, steps),
-                                          (int64_t)(uintptr_t)x, (int64_t)(uintptr_t)eps, (int64_t)(uintptr_t)workspace, tsb, cnb, sc->net_pred_flow,
-                                          sc->schedule, nsde, (int64_t)h->text_L, (int64_t)(uintptr_t)h->blocks[0].kc,
-                                          (int64_t)(uintptr_t)h->blocks[0].kv2};
+        std::vector<int64_t> key = {batch, frames, height, width, steps, sample_type, last, f0, f1, fill_only, zero_mask(t_list, steps),
+                                    (int64_t)(uintptr_t)x, (int64_t)(uintptr_t)eps, (int64_t)(uintptr_t)workspace, tsb, cnb, sc->net_pred_flow,
+                                    sc->schedule, nsde};
+        wan_graph_key_tail(h, key);
         // (capture runs the same host bookkeeping as an eager pass; a replay must apply it too)
-        const int stored_before = h->stored_rows;
+        const int stored_before = h->cur.stored_rows;
         GraphEntry& ge = h->chunk_graphs[ci];
         const bool hit = ge.exec && ge.key == key;
         if ((rc = graph_run(ge, key, st.cap, s, enqueue))) return rc;
         if (hit) {
             const int end_rows = f1 * (height / 2) * (width / 2);
-            h->stored_rows = end_rows > stored_before ? end_rows : stored_before;
+            h->cur.stored_rows = end_rows > stored_before ? end_rows : stored_before;
         }
     }
     // `net.clear_caches()` at the end of the loop (causvid.py:184): the next call starts from empty caches (and sets its text again)
@@ -300,30 +297,45 @@ int fg_wan_sampler_run(fg_wan* h, const fg_wan_sampler_config* sc, float* x, con
 // ---- causal video DiT: the guided teacher sampler -----------------------------------------------------------------------------------
 namespace {
 
+// The two guided loops' workspace: a chunk of the chunked loop (Fr = its longest chunk), the whole video of the bidirectional one
 struct WanGuidedWs {
     float *xin, *v;          // the network's input [Be, C, f, H, W] (guided: the chunk twice, rows [0, B) and [B, 2 B)) and its flow
-    float *xl, *mp, *eps;    // x_last, m_prev of the multistep solver and the cache call's noise, [B, C, f, H, W]
+    float *xl, *mp, *eps;    // x_last, m_prev of the multistep solver and the cache call's noise (chunked loop only), [B, C, f, H, W]
     float* te;
     double* sc;              // [steps + 1 timesteps | steps x 8 solver table | seed, offset as 2 x uint64]
     void* net;
     size_t net_bytes;
 };
 
-size_t wan_guided_plan(const fg_wan* h, int B, int stack, int fmax, int H, int W, int steps, Arena& A, WanGuidedWs& w) {
-    const size_t per = (size_t)B * h->cfg.in_channels * fmax * H * W;
+// C: the video's channels (cfg.in_channels in the chunked loop, vch() in the bidirectional one); full: the bidirectional loop - no
+// cache call, so no noise buffer, and the bidirectional call's workspace
+size_t wan_guided_plan(const fg_wan* h, int B, int stack, int C, int Fr, int H, int W, int steps, bool full, Arena& A, WanGuidedWs& w) {
+    const size_t per = (size_t)B * C * Fr * H * W;
     w.xin = A.get<float>(per * stack);
     w.v = A.get<float>(per * stack);
     w.xl = A.get<float>(per);
     w.mp = A.get<float>(per);
-    w.eps = A.get<float>(per);
-    w.te = A.get<float>((size_t)B * stack * fmax);
+    w.eps = A.get<float>(full ? 0 : per);
+    w.te = A.get<float>((size_t)B * stack * Fr);
     w.sc = A.get<double>(9 * (size_t)steps + 3);
-    w.net_bytes = fg_wan_workspace_bytes(h, B * stack, fmax, H, W);
+    w.net_bytes = full ? fg_wan_full_workspace_bytes(h, B * stack, Fr, H, W) : fg_wan_workspace_bytes(h, B * stack, Fr, H, W);
     w.net = A.take(w.net_bytes);
     return (A.off + 255) & ~(size_t)255;
 }
 
 constexpr int kGuidedMaxSteps = 4096;  // a sanity bound on the table's size, not a property of the loop
+
+// What the two guided loops ask of their step arguments before they look at the video or the handle's state
+int wan_check_guided_args(const fg_wan_guided_sampler_config* sc, const double* t_list, const double* table, int steps) {
+    if (steps < 1 || steps > kGuidedMaxSteps) return fail(FG_EINVAL, "steps must be in [1, %d]", kGuidedMaxSteps);
+    if (!(sc->t_scale > 0.0)) return fail(FG_EINVAL, "t_scale must be positive");
+    if (sc->guidance != 0 && sc->guidance != 1) return fail(FG_EINVAL, "guidance must be 0 (batch B) or 1 (stacked batch 2 B)");
+    for (int i = 0; i < steps; ++i)
+        if (!(t_list[i] >= 0.0 && t_list[i] <= 1.0)) return fail(FG_EINVAL, "t_list[%d] = %g outside [0, 1]", i, t_list[i]);
+    for (int i = 0; i < 8 * steps; ++i)
+        if (!std::isfinite(table[i])) return fail(FG_EINVAL, "table[%d][%d] is not finite", i / 8, i % 8);
+    return FG_OK;
+}
 
 // The guided loops' step scalars [steps + 1 timesteps (the last 0: the cache-fill call's) | steps x 8 solver table | seed, offset] do
 // not fit the scalar ring: they go up from one pinned host copy of 9 steps + 3 doubles, on the caller's stream before any graph
@@ -354,32 +366,24 @@ int wan_upload_step_scalars(fg_wan* h, const double* t_list, const double* table
 extern "C" {
 
 size_t fg_wan_guided_sampler_workspace_bytes(const fg_wan* h, int batch, int frames, int height, int width, int steps, int guidance) {
-    if (!h || batch <= 0 || frames <= 0 || height <= 0 || width <= 0 || (height & 1) || (width & 1) || steps < 1 || steps > kGuidedMaxSteps) return 0;
+    if (!h || !wan_shape_ok(batch, frames, height, width) || steps < 1 || steps > kGuidedMaxSteps) return 0;
     const int chunk = h->cfg.chunk_size, fmax = frames < chunk ? frames : chunk + frames % chunk;
     Arena A;
     A.dry = true;
     WanGuidedWs w;
-    return wan_guided_plan(h, batch, guidance ? 2 : 1, fmax, height, width, steps, A, w);
+    return wan_guided_plan(h, batch, guidance ? 2 : 1, h->cfg.in_channels, fmax, height, width, steps, false, A, w);
 }
 
 int fg_wan_guided_sampler_run(fg_wan* h, const fg_wan_guided_sampler_config* sc, float* x, const double* t_list, const double* table, int steps,
                               const float* eps, uint64_t seed, int batch, int frames, int height, int width, void* workspace,
                               size_t workspace_bytes, int use_graph, void* stream) {
     if (!h || !sc || !x || !t_list || !table) return fail(FG_EINVAL, "null argument");
-    if (h->is_i2v || h->is_ti2v) return fail(FG_EINVAL, "the chunked / causal loops are not implemented for an image-to-video handle");
-    if (h->is_vace) return fail(FG_EINVAL, "the chunked / causal loops are not implemented for a VACE handle");
-    if (steps < 1 || steps > kGuidedMaxSteps) return fail(FG_EINVAL, "steps must be in [1, %d]", kGuidedMaxSteps);
-    if (!(sc->t_scale > 0.0)) return fail(FG_EINVAL, "t_scale must be positive");
-    if (sc->guidance != 0 && sc->guidance != 1) return fail(FG_EINVAL, "guidance must be 0 (batch B) or 1 (stacked batch 2 B)");
-    if (batch <= 0 || frames <= 0 || frames > h->cfg.total_num_frames || height <= 0 || width <= 0 || (height & 1) || (width & 1) || !workspace ||
-        (((uintptr_t)workspace) & 255))
+    int rc;
+    if ((rc = wan_refuse_chunked(h, "loops")) || (rc = wan_check_guided_args(sc, t_list, table, steps))) return rc;
+    if (!wan_shape_ok(batch, frames, height, width) || frames > h->cfg.total_num_frames || !workspace || (((uintptr_t)workspace) & 255))
         return fail(FG_EINVAL, "bad batch / frames (<= total_num_frames = %d) / size / workspace", h->cfg.total_num_frames);
     const float cn32 = (float)sc->context_noise;  // (t_cache is a tensor of the latents' dtype, network_causal.py:1268)
     if (!(sc->context_noise >= 0.0) || (double)cn32 > 0.999) return fail(FG_EINVAL, "context_noise outside [0, 0.999]");
-    for (int i = 0; i < steps; ++i)
-        if (!(t_list[i] >= 0.0 && t_list[i] <= 1.0)) return fail(FG_EINVAL, "t_list[%d] = %g outside [0, 1]", i, t_list[i]);
-    for (int i = 0; i < 8 * steps; ++i)
-        if (!std::isfinite(table[i])) return fail(FG_EINVAL, "table[%d][%d] is not finite", i / 8, i % 8);
     if (h->tag != 0) return fail(FG_EINVAL, "the guided loop runs on cache tag 0 (call fg_wan_select_cache_tag(h, 0))");
     const int guided = sc->guidance, stack = guided ? 2 : 1, Be = batch * stack;
     const int chunk = h->cfg.chunk_size, fmax = frames < chunk ? frames : chunk + frames % chunk;
@@ -388,16 +392,14 @@ int fg_wan_guided_sampler_run(fg_wan* h, const fg_wan_guided_sampler_config* sc,
     Arena A;
     A.base = (char*)workspace;
     WanGuidedWs w;
-    const size_t need = wan_guided_plan(h, batch, stack, fmax, height, width, steps, A, w);
+    const size_t need = wan_guided_plan(h, batch, stack, h->cfg.in_channels, fmax, height, width, steps, false, A, w);
     if (need > workspace_bytes) return fail(FG_ENOMEM, "workspace too small: need %zu bytes, got %zu", need, workspace_bytes);
     if (!h->packed) return fail(FG_ENOTREADY, "weights are not packed (call fg_wan_pack_weights)");
-    if (h->text_B != Be)
-        return fail(FG_ENOTREADY, "no text condition for batch %d (call fg_wan_set_text%s)", Be, guided ? " with [cond; neg_cond]" : "");
+    if ((rc = wan_conditions_ready(h, Be, frames, height, width, guided ? " with [cond; neg_cond]" : ""))) return rc;
     hipStream_t s = (hipStream_t)stream;
-    int rc;
     // as in fg_wan_sampler_run: `self.clear_caches()` of the loop's first lines (network_causal.py:1216) without a memset, the text stays
     if ((rc = wan_ensure_caches(h, Be, height, width, s))) return rc;  // (allocation must not fall inside a capture)
-    h->stored_rows = 0;
+    h->cur.stored_rows = 0;
     if ((rc = wan_upload_step_scalars(h, t_list, table, steps, seed, w.sc, s))) return rc;
     const double* tl = w.sc;
     const double* tab = w.sc + steps + 1;
@@ -441,16 +443,16 @@ int fg_wan_guided_sampler_run(fg_wan* h, const fg_wan_guided_sampler_config* sc,
         int64_t tsb, cnb;
         memcpy(&tsb, &sc->t_scale, 8);
         memcpy(&cnb, &sc->context_noise, 8);
-        const std::vector<int64_t> key = {batch, guided, frames, height, width, steps, f0, f1, (int64_t)(uintptr_t)x, (int64_t)(uintptr_t)eps,
-                                          (int64_t)(uintptr_t)workspace, tsb, cnb, (int64_t)h->text_L, (int64_t)(uintptr_t)h->blocks[0].kc,
-                                          (int64_t)(uintptr_t)h->blocks[0].kv2};
-        const int stored_before = h->stored_rows;
+        std::vector<int64_t> key = {batch, guided, frames, height, width, steps, f0, f1, (int64_t)(uintptr_t)x, (int64_t)(uintptr_t)eps,
+                                    (int64_t)(uintptr_t)workspace, tsb, cnb};
+        wan_graph_key_tail(h, key);
+        const int stored_before = h->cur.stored_rows;
         GraphEntry& ge = h->guided_graphs[ci];
         const bool hit = ge.exec && ge.key == key;
         if ((rc = graph_run(ge, key, h->sampler.cap, s, enqueue))) return rc;
         if (hit) {  // (capture runs the same host bookkeeping as an eager pass; a replay must apply it too)
             const int end_rows = f1 * (height / 2) * (width / 2);
-            h->stored_rows = end_rows > stored_before ? end_rows : stored_before;
+            h->cur.stored_rows = end_rows > stored_before ? end_rows : stored_before;
         }
     }
     return fg_wan_clear_caches(h, s);  // `self.clear_caches()` after the last chunk (:1292)
@@ -488,28 +490,8 @@ size_t wan_full_sampler_plan(const fg_wan* h, int B, int Fr, int H, int W, Arena
     return (A.off + 255) & ~(size_t)255;
 }
 
-struct WanFullGuidedWs {
-    float *xin, *v, *xl, *mp, *te;  // as WanGuidedWs, over the whole video
-    double* sc;
-    void* net;
-    size_t net_bytes;
-};
-
-size_t wan_full_guided_plan(const fg_wan* h, int B, int stack, int Fr, int H, int W, int steps, Arena& A, WanFullGuidedWs& w) {
-    const size_t per = (size_t)B * h->vch() * Fr * H * W;  // (the video's channels: the latents alone on an image-to-video handle)
-    w.xin = A.get<float>(per * stack);
-    w.v = A.get<float>(per * stack);
-    w.xl = A.get<float>(per);
-    w.mp = A.get<float>(per);
-    w.te = A.get<float>((size_t)B * stack * Fr);
-    w.sc = A.get<double>(9 * (size_t)steps + 3);
-    w.net_bytes = fg_wan_full_workspace_bytes(h, B * stack, Fr, H, W);
-    w.net = A.take(w.net_bytes);
-    return (A.off + 255) & ~(size_t)255;
-}
-
 bool wan_full_shape_ok(const fg_wan* h, int batch, int frames, int height, int width) {
-    return h && batch > 0 && frames > 0 && frames <= h->cfg.rope_max_seq_len && height > 0 && width > 0 && !(height & 1) && !(width & 1);
+    return h && wan_shape_ok(batch, frames, height, width) && frames <= h->cfg.rope_max_seq_len;
 }
 
 }  // namespace
@@ -546,13 +528,7 @@ int fg_wan_full_sampler_run(fg_wan* h, const fg_wan_sampler_config* sc, const fl
     const size_t need = wan_full_sampler_plan(h, batch, frames, height, width, A, w);
     if (need > workspace_bytes) return fail(FG_ENOMEM, "workspace too small: need %zu bytes, got %zu", need, workspace_bytes);
     if (!h->packed) return fail(FG_ENOTREADY, "weights are not packed (call fg_wan_pack_weights)");
-    if (h->text_B != batch) return fail(FG_ENOTREADY, "no text condition for batch %d (call fg_wan_set_text)", batch);
-    if (h->is_i2v && (h->ff_B != batch || h->ff_F != frames || h->ff_H != height || h->ff_W != width))
-        return fail(FG_ENOTREADY, "no image-to-video condition for batch %d, %d frames of %d x %d (call fg_wan_set_i2v_cond)", batch, frames, height, width);
-    if (h->is_ti2v && !h->has_first_frame(batch, height, width))
-        return fail(FG_ENOTREADY, "no first frame for batch %d of %d x %d (call fg_wan_set_first_frame)", batch, height, width);
-    if (h->is_vace && !h->has_vace_context(batch, frames, height, width))
-        return fail(FG_ENOTREADY, "no VACE context for batch %d, %d frames of %d x %d (call fg_wan_set_vace_context)", batch, frames, height, width);
+    if ((rc = wan_conditions_ready(h, batch, frames, height, width))) return rc;
     const int rows = batch * frames;
     const int64_t total = (int64_t)batch * h->vch() * frames * height * width, hw1 = (int64_t)height * width;
     auto enqueue = [&](hipStream_t q) -> int {
@@ -580,57 +556,39 @@ int fg_wan_full_sampler_run(fg_wan* h, const fg_wan_sampler_config* sc, const fl
     };
     int64_t tsb;
     memcpy(&tsb, &sc->t_scale, 8);
-    // everything the capture bakes in: shapes, buffers, the text's length and k / v buffer, compute mode, what the r rows mean
-    return sampler_launch(h->sampler, batch, t_list, steps, sample_type, loop_kind, seed, w.tl, w.seed, use_graph,
-                          {frames, height, width, (int64_t)(uintptr_t)noise, (int64_t)(uintptr_t)eps, (int64_t)(uintptr_t)out,
-                           (int64_t)(uintptr_t)workspace, tsb, sc->net_pred_flow, sc->schedule, (int64_t)h->text_L,
-                           (int64_t)(uintptr_t)h->blocks[0].kv2, (int64_t)h->fp8, h->ext.time_cond_diff,
-                           (int64_t)(uintptr_t)h->ff, (int64_t)(uintptr_t)h->blocks[0].kvi, (int64_t)h->img_L, (int64_t)(uintptr_t)h->ff0,
-                           (int64_t)(uintptr_t)h->vctx, (int64_t)(uintptr_t)h->vscale},
-                          (hipStream_t)stream, enqueue);
+    // everything the capture bakes in: the call's shapes, buffers and settings, then what the handle owns
+    std::vector<int64_t> more = {frames, height, width, (int64_t)(uintptr_t)noise, (int64_t)(uintptr_t)eps, (int64_t)(uintptr_t)out,
+                                 (int64_t)(uintptr_t)workspace, tsb, sc->net_pred_flow, sc->schedule};
+    wan_graph_key_tail(h, more);
+    return sampler_launch(h->sampler, batch, t_list, steps, sample_type, loop_kind, seed, w.tl, w.seed, use_graph, more, (hipStream_t)stream, enqueue);
 }
 
 size_t fg_wan_full_guided_sampler_workspace_bytes(const fg_wan* h, int batch, int frames, int height, int width, int steps, int guidance) {
     if (!wan_full_shape_ok(h, batch, frames, height, width) || steps < 1 || steps > kGuidedMaxSteps) return 0;
     Arena A;
     A.dry = true;
-    WanFullGuidedWs w;
-    return wan_full_guided_plan(h, batch, guidance ? 2 : 1, frames, height, width, steps, A, w);
+    WanGuidedWs w;
+    return wan_guided_plan(h, batch, guidance ? 2 : 1, h->vch(), frames, height, width, steps, true, A, w);
 }
 
 int fg_wan_full_guided_sampler_run(fg_wan* h, const fg_wan_guided_sampler_config* sc, float* x, const double* t_list, const double* table,
                                    int steps, int batch, int frames, int height, int width, void* workspace, size_t workspace_bytes,
                                    int use_graph, void* stream) {
     if (!h || !sc || !x || !t_list || !table) return fail(FG_EINVAL, "null argument");
-    if (steps < 1 || steps > kGuidedMaxSteps) return fail(FG_EINVAL, "steps must be in [1, %d]", kGuidedMaxSteps);
-    if (!(sc->t_scale > 0.0)) return fail(FG_EINVAL, "t_scale must be positive");
-    if (sc->guidance != 0 && sc->guidance != 1) return fail(FG_EINVAL, "guidance must be 0 (batch B) or 1 (stacked batch 2 B)");
+    int rc;
+    if ((rc = wan_check_guided_args(sc, t_list, table, steps))) return rc;
     if (sc->context_noise != 0.0) return fail(FG_EINVAL, "context_noise must be 0: there is no cache to fill");
     if (!wan_full_shape_ok(h, batch, frames, height, width) || !workspace || (((uintptr_t)workspace) & 255))
         return fail(FG_EINVAL, "bad batch / frames (<= rope_max_seq_len = %d) / size / workspace", h->cfg.rope_max_seq_len);
-    for (int i = 0; i < steps; ++i)
-        if (!(t_list[i] >= 0.0 && t_list[i] <= 1.0)) return fail(FG_EINVAL, "t_list[%d] = %g outside [0, 1]", i, t_list[i]);
-    for (int i = 0; i < 8 * steps; ++i)
-        if (!std::isfinite(table[i])) return fail(FG_EINVAL, "table[%d][%d] is not finite", i / 8, i % 8);
     const int guided = sc->guidance, stack = guided ? 2 : 1, Be = batch * stack;
     Arena A;
     A.base = (char*)workspace;
-    WanFullGuidedWs w;
-    const size_t need = wan_full_guided_plan(h, batch, stack, frames, height, width, steps, A, w);
+    WanGuidedWs w;
+    const size_t need = wan_guided_plan(h, batch, stack, h->vch(), frames, height, width, steps, true, A, w);
     if (need > workspace_bytes) return fail(FG_ENOMEM, "workspace too small: need %zu bytes, got %zu", need, workspace_bytes);
     if (!h->packed) return fail(FG_ENOTREADY, "weights are not packed (call fg_wan_pack_weights)");
-    if (h->text_B != Be)
-        return fail(FG_ENOTREADY, "no text condition for batch %d (call fg_wan_set_text%s)", Be, guided ? " with [cond; neg_cond]" : "");
-    if (h->is_i2v && (h->ff_B != Be || h->ff_F != frames || h->ff_H != height || h->ff_W != width))
-        return fail(FG_ENOTREADY, "no image-to-video condition for batch %d, %d frames of %d x %d (call fg_wan_set_i2v_cond)", Be, frames, height, width);
-    if (h->is_ti2v && !h->has_first_frame(Be, height, width))
-        return fail(FG_ENOTREADY, "no first frame for batch %d of %d x %d (call fg_wan_set_first_frame%s)", Be, height, width,
-                    guided ? " with [cond; neg_cond]" : "");
-    if (h->is_vace && !h->has_vace_context(Be, frames, height, width))
-        return fail(FG_ENOTREADY, "no VACE context for batch %d, %d frames of %d x %d (call fg_wan_set_vace_context%s)", Be, frames, height, width,
-                    guided ? " with [cond; neg_cond]" : "");
+    if ((rc = wan_conditions_ready(h, Be, frames, height, width, guided ? " with [cond; neg_cond]" : ""))) return rc;
     hipStream_t s = (hipStream_t)stream;
-    int rc;
     if ((rc = wan_upload_step_scalars(h, t_list, table, steps, 0, w.sc, s))) return rc;  // (no draw in this loop: the seed slot goes unread)
     const double* tl = w.sc;
     const double* tab = w.sc + steps + 1;
@@ -663,9 +621,7 @@ int fg_wan_full_guided_sampler_run(fg_wan* h, const fg_wan_guided_sampler_config
     // what the launches bake in (timesteps and the table with the guidance scale are device memory)
     int64_t tsb;
     memcpy(&tsb, &sc->t_scale, 8);
-    const std::vector<int64_t> key = {batch, guided, frames, height, width, steps, (int64_t)(uintptr_t)x, (int64_t)(uintptr_t)workspace, tsb,
-                                      (int64_t)h->text_L, (int64_t)(uintptr_t)h->blocks[0].kv2, (int64_t)h->fp8, h->ext.time_cond_diff,
-                                      (int64_t)(uintptr_t)h->ff, (int64_t)(uintptr_t)h->blocks[0].kvi, (int64_t)h->img_L,
-                                      (int64_t)(uintptr_t)h->ff0, (int64_t)(uintptr_t)h->vctx, (int64_t)(uintptr_t)h->vscale};
+    std::vector<int64_t> key = {batch, guided, frames, height, width, steps, (int64_t)(uintptr_t)x, (int64_t)(uintptr_t)workspace, tsb};
+    wan_graph_key_tail(h, key);
     return graph_run(h->full_guided_graph, key, h->sampler.cap, s, enqueue);
 }

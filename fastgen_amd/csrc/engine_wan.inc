@@ -49,7 +49,7 @@ struct fg_wan : HandleBase {
     int vpe_w = -1, vpe_b = -1;  // vace_patch_embedding
     void* vctx = nullptr;
     int vctx_B = 0, vctx_F = 0, vctx_H = 0, vctx_W = 0;  // vctx_B == 0: no context set
-    size_t vctx_elems = 0;
+    size_t vctx_bytes = 0;
     float* vscale = nullptr;
     std::vector<float> vscale_host;
     bool has_vace_context(int batch, int frames, int height, int width) const {
@@ -75,7 +75,7 @@ struct fg_wan : HandleBase {
     void* img_tok = nullptr;
     int ff_B = 0, ff_F = 0, ff_H = 0, ff_W = 0;  // ff_B == 0: no condition set
     int img_L = 0;                               // image tokens per sample of the condition (0: no image context)
-    size_t ff_elems = 0, img_rows = 0;           // what ff / img_tok + kvi are allocated for
+    size_t ff_bytes = 0, img_rows = 0;           // what ff / img_tok + kvi are allocated for
     // fg_wan_create_ti2v: the Wan2.2-TI2V convention (WanI2V/network.py, concat_mask = False, expand_timesteps = True).  No extra
     // channels and no image keys; the condition (fg_wan_set_first_frame) is frame 0 of the first-frame latents, `ff0`
     // [B][latent][1][H][W] fp32, owned here and rewritten in place while its shape stays (the loops' graphs name it).  It feeds
@@ -84,7 +84,7 @@ struct fg_wan : HandleBase {
     fg_wan_ti2v_config ti2v{0};
     float* ff0 = nullptr;
     int ff0_B = 0, ff0_H = 0, ff0_W = 0;  // ff0_B == 0: no condition set
-    size_t ff0_elems = 0;
+    size_t ff0_bytes = 0;
     bool has_first_frame(int batch, int height, int width) const { return ff0_B == batch && ff0_H == height && ff0_W == width; }
     int r1_w = -1, r1_b = -1, r2_w = -1, r2_b = -1, rp_w = -1, rp_b = -1;
     float2 *tab_t = nullptr, *tab_h = nullptr, *tab_w = nullptr;  // RoPE axis tables
@@ -93,20 +93,28 @@ struct fg_wan : HandleBase {
     // start frame, frame count and key length are baked in) in place of sampler.graph
     SamplerCache sampler;
     std::vector<GraphEntry> chunk_graphs;
-    int cache_B = 0, cache_cap = 0, text_B = 0, text_L = 0;
-    size_t kv2_rows = 0;  // text rows (batch * text_len) the blocks' kv2 are allocated for; outlives clear_caches, which only zeroes text_B
-    int stored_rows = 0;  // cache rows [0, stored_rows) hold K / V that a store_kv = 1 call wrote (the reference's per_tag["len"], network_causal.py:385-390)
-    // The reference keeps one cache sub-dict per cache_tag ("pos" / "neg", network_causal.py:331-412).  The fields above and the blocks'
+    struct CacheState {
+        int cache_B = 0, cache_cap = 0, text_B = 0, text_L = 0;
+        size_t kv2_rows = 0;  // text rows (batch * text_len) the blocks' kv2 are allocated for; outlives clear_caches, which only zeroes text_B
+        int stored_rows = 0;  // cache rows [0, stored_rows) hold K / V that a store_kv = 1 call wrote (the reference's per_tag["len"], network_causal.py:385-390)
+    };
+    // The reference keeps one cache sub-dict per cache_tag ("pos" / "neg", network_causal.py:331-412).  `cur` and the blocks'
     // kc / vc / kv2 are the SELECTED tag's set; the other tag's set waits here (fg_wan_select_cache_tag swaps them).  It is empty until
     // its tag is first selected and used: a handle that stays on tag 0 allocates nothing more.
     struct CacheSet {
         std::vector<void*> kc, vc, kv2;  // per block
         std::vector<void*> vkv2;         // per VACE block
-        int cache_B = 0, cache_cap = 0, text_B = 0, text_L = 0, stored_rows = 0;
-        size_t kv2_rows = 0;
+        CacheState state;
     };
+    CacheState cur;
     CacheSet other;
     int tag = 0;
+    // f(state, kv, n) on the selected tag's set, then on the waiting one: kv(i) is block i's {kc, vc}, i < n
+    template <typename F>
+    int each_cache_set(F&& f) {
+        if (int rc = f(cur, [&](size_t i) { return std::pair<void*, void*>(blocks[i].kc, blocks[i].vc); }, blocks.size())) return rc;
+        return f(other.state, [&](size_t i) { return std::pair<void*, void*>(other.kc[i], other.vc[i]); }, other.kc.size());
+    }
     // fg_wan_guided_sampler_run (engine_sampler.inc): its per-chunk graphs and the pinned host copy of the step scalars
     std::vector<GraphEntry> guided_graphs;
     GraphEntry full_guided_graph;  // fg_wan_full_guided_sampler_run: one graph for the video (fg_wan_full_sampler_run's is sampler.graph)
@@ -121,17 +129,39 @@ struct fg_wan : HandleBase {
     std::vector<char> pack_only, dirty;
     const float* P(int idx) const { return idx < 0 ? nullptr : (own[idx] ? own[idx] : params[idx].ptr); }
     bool is_logvar(int idx) const { return params[idx].name.find("logvar_linear") != std::string::npos; }
-    // Before a cache buffer is freed: the chunk graphs name every block's kc / vc / kv2 and their keys hold block 0's addresses only,
-    // which the allocator may hand out again - no graph outlives a buffer it was captured on.
+    // Before a buffer is freed: the graphs name every block's kc / vc / kv2 / kvi and the conditions, and their keys hold block 0's
+    // addresses only, which the allocator may hand out again - no graph outlives a buffer it was captured on.
     void drop_graphs() {
         for (GraphEntry& g : chunk_graphs) g.drop();
         for (GraphEntry& g : guided_graphs) g.drop();
         full_guided_graph.drop();
         sampler.graph.drop();
     }
+    // The one place a handle-owned buffer that the forward reads changes its address (wan_graph_key_tail names them): a buffer of the
+    // wanted size stays where it is, and the graphs that name it stay valid; any other is freed behind the graphs and allocated anew
+    // (want_bytes == 0: freed).  have_bytes is the buffer's own record - buffers that share one size field are given a copy of it each.
+    int resize(void*& p, size_t& have_bytes, size_t want_bytes) {
+        if (have_bytes == want_bytes) return FG_OK;
+        drop_graphs();
+        free(p);
+        p = nullptr, have_bytes = 0;
+        if (want_bytes == 0) return FG_OK;
+        if (int rc = alloc(&p, want_bytes)) return rc;
+        have_bytes = want_bytes;
+        return FG_OK;
+    }
 };
 
 namespace {
+
+// What every entry point asks of a video: positive counts and whole 2 x 2 patches (a call without frames passes 1)
+bool wan_shape_ok(int batch, int frames, int height, int width) {
+    return batch > 0 && frames > 0 && height > 0 && width > 0 && !(height & 1) && !(width & 1);
+}
+// ... and of the bidirectional calls' token count: the kernels index rows with 32 bits
+bool wan_rows_fit(int batch, int frames, int height, int width) {
+    return (int64_t)batch * frames * (height / 2) * (width / 2) <= INT32_MAX / 2;
+}
 
 struct WanWs {
     float *tf, *th, *temb, *st, *tproj, *mod, *omod;
@@ -376,24 +406,29 @@ int wan_pack(fg_wan* h, const ParamGroup& in_group, hipStream_t s) {
         if (unbound >= 0) return fail(FG_ENOTREADY, "parameter '%s' is not bound", h->params[unbound].name.c_str());
         if ((rc = pack_block(b))) return rc;
     }
-    h->text_B = h->other.text_B = 0;  // the text caches (of both tags) were computed with the previous weights
+    // the text caches (of both tags) were computed with the previous weights
+    (void)h->each_cache_set([](fg_wan::CacheState& st, auto&&, size_t) {
+        st.text_B = 0;
+        return FG_OK;
+    });
     h->ff_B = 0;                      // ... and so was the image-to-video condition
     h->vctx_B = 0;                    // ... and the VACE context (proj_in, vace_patch_embedding)
     return FG_OK;
 }
 
-}  // namespace
+// What fg_wan_create_ex / _i2v / _ti2v / _vace add to the plain network, each nullable
+struct WanVariant {
+    const fg_wan_ext_config* ext = nullptr;
+    const fg_wan_i2v_config* i2v = nullptr;
+    const fg_wan_ti2v_config* ti2v = nullptr;
+    const fg_wan_vace_config* vace = nullptr;
+};
 
-extern "C" {
-
-}  // extern "C" (reopened below)
-
-namespace {
-// fg_wan_create_ex, fg_wan_create_i2v, fg_wan_create_ti2v and fg_wan_create_vace: one table builder.  i2v == nullptr: the plain
-// network's table (ti2v adds no parameter); vace: that table with the control branch's keys inserted.
-int wan_create(const fg_wan_config* cfg, const fg_wan_ext_config* ext, const fg_wan_i2v_config* i2v, fg_wan** out,
-               const fg_wan_ti2v_config* ti2v = nullptr, const fg_wan_vace_config* vace = nullptr) {
+// The five fg_wan_create* entry points: one table builder.  i2v == nullptr: the plain network's table (ti2v adds no parameter); vace:
+// that table with the control branch's keys inserted.
+int wan_create(const fg_wan_config* cfg, const WanVariant& var, fg_wan** out) {
     if (!cfg || !out) return fail(FG_EINVAL, "null argument");
+    const auto [ext, i2v, ti2v, vace] = var;
     if (vace) {
         if (vace->vace_in_channels <= 0 || vace->vace_in_channels > 128)
             return fail(FG_EINVAL, "vace_in_channels %d outside (0, 128]", vace->vace_in_channels);
@@ -534,21 +569,21 @@ int wan_create(const fg_wan_config* cfg, const fg_wan_ext_config* ext, const fg_
 
 extern "C" {
 
-int fg_wan_create(const fg_wan_config* cfg, fg_wan** out) { return wan_create(cfg, nullptr, nullptr, out); }
-int fg_wan_create_ex(const fg_wan_config* cfg, const fg_wan_ext_config* ext, fg_wan** out) { return wan_create(cfg, ext, nullptr, out); }
+int fg_wan_create(const fg_wan_config* cfg, fg_wan** out) { return wan_create(cfg, {}, out); }
+int fg_wan_create_ex(const fg_wan_config* cfg, const fg_wan_ext_config* ext, fg_wan** out) { return wan_create(cfg, {ext}, out); }
 int fg_wan_create_i2v(const fg_wan_config* cfg, const fg_wan_ext_config* ext, const fg_wan_i2v_config* i2v, fg_wan** out) {
     if (!i2v) return fail(FG_EINVAL, "null argument");
-    return wan_create(cfg, ext, i2v, out);
+    return wan_create(cfg, {ext, i2v}, out);
 }
 
 int fg_wan_create_ti2v(const fg_wan_config* cfg, const fg_wan_ext_config* ext, const fg_wan_ti2v_config* ti2v, fg_wan** out) {
     if (!ti2v) return fail(FG_EINVAL, "null argument");
-    return wan_create(cfg, ext, nullptr, out, ti2v);
+    return wan_create(cfg, {ext, nullptr, ti2v}, out);
 }
 
 int fg_wan_create_vace(const fg_wan_config* cfg, const fg_wan_ext_config* ext, const fg_wan_vace_config* vace, fg_wan** out) {
     if (!vace) return fail(FG_EINVAL, "null argument");
-    return wan_create(cfg, ext, nullptr, out, nullptr, vace);
+    return wan_create(cfg, {ext, nullptr, nullptr, vace}, out);
 }
 
 int fg_wan_set_vace_scale(fg_wan* h, const float* scales_host, int n, void* stream) {
@@ -569,17 +604,11 @@ int fg_wan_set_vace_scale(fg_wan* h, const float* scales_host, int n, void* stre
 int fg_wan_set_first_frame(fg_wan* h, const float* first_frame, int batch, int height, int width, void* stream) {
     if (!h || !first_frame) return fail(FG_EINVAL, "null argument");
     if (!h->is_ti2v) return fail(FG_EINVAL, "not a first-frame-replacement handle (fg_wan_create_ti2v)");
-    if (batch <= 0 || height <= 0 || width <= 0 || (height & 1) || (width & 1)) return fail(FG_EINVAL, "bad batch / size");
-    const size_t elems = (size_t)batch * h->ti2v.latent_channels * height * width;
+    if (!wan_shape_ok(batch, 1, height, width)) return fail(FG_EINVAL, "bad batch / size");
+    const size_t bytes = (size_t)batch * h->ti2v.latent_channels * height * width * sizeof(float);
     h->ff0_B = 0;  // (nothing valid until the copy is enqueued)
-    if (elems != h->ff0_elems) {
-        h->drop_graphs();
-        h->free(h->ff0);
-        h->ff0 = nullptr, h->ff0_elems = 0;
-        if (int rc = h->alloc((void**)&h->ff0, elems * sizeof(float))) return rc;
-        h->ff0_elems = elems;
-    }
-    HIP_TRY(hipMemcpyAsync(h->ff0, first_frame, elems * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    if (int rc = h->resize((void*&)h->ff0, h->ff0_bytes, bytes)) return rc;
+    HIP_TRY(hipMemcpyAsync(h->ff0, first_frame, bytes, hipMemcpyDeviceToDevice, (hipStream_t)stream));
     h->ff0_B = batch, h->ff0_H = height, h->ff0_W = width;
     return FG_OK;
 }
@@ -588,7 +617,7 @@ int fg_wan_first_frame_read(fg_wan* h, float* out, void* stream) {
     if (!h || !out) return fail(FG_EINVAL, "null argument");
     if (!h->is_ti2v) return fail(FG_EINVAL, "not a first-frame-replacement handle (fg_wan_create_ti2v)");
     if (h->ff0_B == 0) return fail(FG_ENOTREADY, "no first frame is set (call fg_wan_set_first_frame)");
-    HIP_TRY(hipMemcpyAsync(out, h->ff0, h->ff0_elems * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    HIP_TRY(hipMemcpyAsync(out, h->ff0, h->ff0_bytes, hipMemcpyDeviceToDevice, (hipStream_t)stream));
     return FG_OK;
 }
 
@@ -631,7 +660,7 @@ int fg_wan_pack_group(fg_wan* h, const char* prefix, const char* exclude, void* 
 }
 
 size_t fg_wan_workspace_bytes(const fg_wan* h, int batch, int frames, int height, int width) {
-    if (!h || batch <= 0 || frames <= 0 || height <= 0 || width <= 0 || (height & 1) || (width & 1)) return 0;
+    if (!h || !wan_shape_ok(batch, frames, height, width)) return 0;
     Arena A;
     A.dry = true;
     WanWs w;
@@ -643,25 +672,17 @@ size_t fg_wan_workspace_bytes(const fg_wan* h, int batch, int frames, int height
 
 int fg_wan_clear_caches(fg_wan* h, void* stream) {
     if (!h) return fail(FG_EINVAL, "null handle");
-    if (h->cache_B > 0)
-        for (fg_wan::Blk& b : h->blocks) {
-            const size_t bytes = (size_t)h->cache_B * h->cache_cap * h->D * 2;
-            HIP_TRY(hipMemsetAsync(b.kc, 0, bytes, (hipStream_t)stream));
-            HIP_TRY(hipMemsetAsync(b.vc, 0, bytes, (hipStream_t)stream));
+    // the selected tag's set, and the same for the one that is not (the reference resets every tag's sub-dict)
+    return h->each_cache_set([&](fg_wan::CacheState& st, auto&& kv, size_t n) -> int {
+        const size_t bytes = (size_t)st.cache_B * st.cache_cap * h->D * 2;
+        for (size_t i = 0; bytes > 0 && i < n; ++i) {
+            HIP_TRY(hipMemsetAsync(kv(i).first, 0, bytes, (hipStream_t)stream));
+            HIP_TRY(hipMemsetAsync(kv(i).second, 0, bytes, (hipStream_t)stream));
         }
-    h->stored_rows = 0;
-    h->text_B = 0;  // `is_init = False` of the cross-attention caches (network_causal.py:1046-1054)
-    // ... and the same for the tag that is not selected (the reference resets every tag's sub-dict)
-    fg_wan::CacheSet& o = h->other;
-    if (o.cache_B > 0)
-        for (size_t i = 0; i < o.kc.size(); ++i) {
-            const size_t bytes = (size_t)o.cache_B * o.cache_cap * h->D * 2;
-            HIP_TRY(hipMemsetAsync(o.kc[i], 0, bytes, (hipStream_t)stream));
-            HIP_TRY(hipMemsetAsync(o.vc[i], 0, bytes, (hipStream_t)stream));
-        }
-    o.stored_rows = 0;
-    o.text_B = 0;
-    return FG_OK;
+        st.stored_rows = 0;
+        st.text_B = 0;  // `is_init = False` of the cross-attention caches (network_causal.py:1046-1054)
+        return FG_OK;
+    });
 }
 
 int fg_wan_select_cache_tag(fg_wan* h, int tag) {
@@ -678,12 +699,7 @@ int fg_wan_select_cache_tag(fg_wan* h, int tag) {
     }
     o.vkv2.resize(h->vblocks.size(), nullptr);
     for (size_t i = 0; i < h->vblocks.size(); ++i) std::swap(h->vblocks[i].kv2, o.vkv2[i]);
-    std::swap(h->cache_B, o.cache_B);
-    std::swap(h->cache_cap, o.cache_cap);
-    std::swap(h->text_B, o.text_B);
-    std::swap(h->text_L, o.text_L);
-    std::swap(h->kv2_rows, o.kv2_rows);
-    std::swap(h->stored_rows, o.stored_rows);
+    std::swap(h->cur, o.state);
     h->tag = tag;
     return FG_OK;
 }
@@ -702,21 +718,18 @@ int fg_wan_set_text(fg_wan* h, const float* text, int batch, int text_len, void*
     void* e2 = (char*)e1 + ((M * D * 2 + 255) & ~(size_t)255);
     // (the sampler loops end with clear_caches, so every call sets its text again: the buffers stay where they are while their size
     // does, and the chunk graphs that name them stay valid)
-    if (h->kv2_rows != M) {
-        h->drop_graphs();
-        h->kv2_rows = 0;
-        for (std::vector<fg_wan::Blk>* bl : {&h->blocks, &h->vblocks})  // (a VACE block has its own attn2.to_k / to_v / norm_k)
-            for (fg_wan::Blk& b : *bl) {
-                h->free(b.kv2);
-                b.kv2 = nullptr;
-                int rc = h->alloc(&b.kv2, M * 2 * D * 2);
-                if (rc) return rc;
-            }
-        h->kv2_rows = M;
-    }
+    fg_wan::CacheState& st = h->cur;
+    const size_t had = st.kv2_rows * 2 * D * 2;
+    int rc;
+    st.text_B = 0, st.kv2_rows = 0;  // (nothing valid until every block has its buffer and its keys)
+    for (std::vector<fg_wan::Blk>* bl : {&h->blocks, &h->vblocks})  // (a VACE block has its own attn2.to_k / to_v / norm_k)
+        for (fg_wan::Blk& b : *bl) {
+            size_t have = had;
+            if ((rc = h->resize(b.kv2, have, M * 2 * D * 2))) return rc;
+        }
+    st.kv2_rows = M;
     // text_embedder: Linear - GELU(tanh) - Linear (PixArtAlphaTextProjection); then per block k = norm_k(to_k(ctx)), v = to_v(ctx)
     HIP_TRY(launch_cvt_rows_bf16(text, tb, (int64_t)(M * Td), s));
-    int rc;
     // (bf16 operands in every mode: this runs once per text)
     if ((rc = wan_gemm(WanOperand{tb}, h->p_x1, h->P(h->x1_b), e1, (int)M, (int)D, (int)Td, s, 1))) return rc;
     if ((rc = wan_gemm(WanOperand{e1}, h->p_x2, h->P(h->x2_b), e2, (int)M, (int)D, (int)D, s))) return rc;
@@ -726,7 +739,7 @@ int fg_wan_set_text(fg_wan* h, const float* text, int batch, int text_len, void*
             HIP_TRY(launch_rms_rope((int)D, b.kv2, (int)(2 * D), h->P(b.nk2), h->cfg.eps, nullptr, b.kv2, (int64_t)text_len * 2 * D, 0, (int)(2 * D),
                                     (int)M, text_len, s));
         }
-    h->text_B = batch, h->text_L = text_len;
+    st.text_B = batch, st.text_L = text_len;
     return FG_OK;
 }
 
@@ -742,7 +755,7 @@ int fg_wan_set_i2v_cond(fg_wan* h, const float* first_frame_cond, const float* i
                         void* workspace, size_t workspace_bytes, void* stream) {
     if (!h || !first_frame_cond) return fail(FG_EINVAL, "null argument");
     if (!h->is_i2v) return fail(FG_EINVAL, "not an image-to-video handle (fg_wan_create_i2v)");
-    if (batch <= 0 || frames <= 0 || height <= 0 || width <= 0 || (height & 1) || (width & 1)) return fail(FG_EINVAL, "bad batch / frames / size");
+    if (!wan_shape_ok(batch, frames, height, width)) return fail(FG_EINVAL, "bad batch / frames / size");
     if (image_len < 0 || image_len > 1024) return fail(FG_EINVAL, "image_len %d outside [0, 1024]", image_len);
     if (!h->packed) return fail(FG_ENOTREADY, "weights are not packed (call fg_wan_pack_weights)");
     hipStream_t s = (hipStream_t)stream;
@@ -755,35 +768,21 @@ int fg_wan_set_i2v_cond(fg_wan* h, const float* first_frame_cond, const float* i
         if (!workspace || (((uintptr_t)workspace) & 255)) return fail(FG_EINVAL, "bad workspace");
         if (need > workspace_bytes) return fail(FG_ENOMEM, "workspace too small: need %zu bytes, got %zu", need, workspace_bytes);
     }
-    const size_t elems = (size_t)batch * h->i2v.latent_channels * frames * height * width;
+    const size_t ff_bytes = (size_t)batch * h->i2v.latent_channels * frames * height * width * sizeof(float);
     int rc;
     h->ff_B = 0;  // (nothing valid until everything below is in place)
-    if (elems != h->ff_elems) {
-        h->drop_graphs();
-        h->free(h->ff);
-        h->ff = nullptr, h->ff_elems = 0;
-        if ((rc = h->alloc((void**)&h->ff, elems * sizeof(float)))) return rc;
-        h->ff_elems = elems;
+    if ((rc = h->resize((void*&)h->ff, h->ff_bytes, ff_bytes))) return rc;
+    const size_t had = h->img_rows;
+    h->img_rows = 0;
+    size_t have = had * D * 2;
+    if ((rc = h->resize(h->img_tok, have, rows * D * 2))) return rc;
+    for (fg_wan::Blk& b : h->blocks) {  // whole 32-key tiles per sample, zero-filled: the padding rows stay zero
+        have = had * 2 * D * 2;
+        if ((rc = h->resize(b.kvi, have, rows * 2 * D * 2))) return rc;
+        if (rows != had && rows > 0) HIP_TRY(hipMemsetAsync(b.kvi, 0, rows * 2 * D * 2, s));
     }
-    if (rows != h->img_rows) {
-        h->drop_graphs();
-        h->img_rows = 0;
-        h->free(h->img_tok);
-        h->img_tok = nullptr;
-        for (fg_wan::Blk& b : h->blocks) {
-            h->free(b.kvi);
-            b.kvi = nullptr;
-        }
-        if (rows > 0) {
-            if ((rc = h->alloc(&h->img_tok, rows * D * 2))) return rc;
-            for (fg_wan::Blk& b : h->blocks) {  // whole 32-key tiles per sample, zero-filled: the padding rows stay zero
-                if ((rc = h->alloc(&b.kvi, rows * 2 * D * 2))) return rc;
-                HIP_TRY(hipMemsetAsync(b.kvi, 0, rows * 2 * D * 2, s));
-            }
-        }
-        h->img_rows = rows;
-    }
-    HIP_TRY(hipMemcpyAsync(h->ff, first_frame_cond, elems * sizeof(float), hipMemcpyDeviceToDevice, s));
+    h->img_rows = rows;
+    HIP_TRY(hipMemcpyAsync(h->ff, first_frame_cond, ff_bytes, hipMemcpyDeviceToDevice, s));
     if (Li > 0) {
         auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
         char* ws = (char*)workspace;
@@ -840,7 +839,7 @@ int fg_wan_i2v_cond_read(fg_wan* h, int block, float* img_tokens, float* k_img, 
 
 // fg_wan_set_vace_context's scratch: the embedded context zero-padded to the video's token count, bf16 [B * L][D]
 size_t fg_wan_vace_context_workspace_bytes(const fg_wan* h, int batch, int frames, int height, int width) {
-    if (!h || !h->is_vace || batch <= 0 || frames <= 0 || height <= 0 || width <= 0 || (height & 1) || (width & 1)) return 0;
+    if (!h || !h->is_vace || !wan_shape_ok(batch, frames, height, width)) return 0;
     return ((size_t)batch * frames * (height / 2) * (width / 2) * h->D * 2 + 255) & ~(size_t)255;
 }
 
@@ -848,9 +847,9 @@ int fg_wan_set_vace_context(fg_wan* h, const float* vid_context, int batch, int 
                             size_t workspace_bytes, void* stream) {
     if (!h || !vid_context) return fail(FG_EINVAL, "null argument");
     if (!h->is_vace) return fail(FG_EINVAL, "not a VACE handle (fg_wan_create_vace)");
-    if (batch <= 0 || frames <= 0 || height <= 0 || width <= 0 || (height & 1) || (width & 1)) return fail(FG_EINVAL, "bad batch / frames / size");
+    if (!wan_shape_ok(batch, frames, height, width)) return fail(FG_EINVAL, "bad batch / frames / size");
     if (ctx_frames <= 0 || ctx_frames > frames) return fail(FG_EINVAL, "ctx_frames %d outside [1, frames = %d]", ctx_frames, frames);
-    if ((int64_t)batch * frames * (height / 2) * (width / 2) > INT32_MAX / 2) return fail(FG_EINVAL, "batch x tokens exceeds the kernels' 32-bit row index");
+    if (!wan_rows_fit(batch, frames, height, width)) return fail(FG_EINVAL, "batch x tokens exceeds the kernels' 32-bit row index");
     if (!h->packed) return fail(FG_ENOTREADY, "weights are not packed (call fg_wan_pack_weights)");
     const size_t need = fg_wan_vace_context_workspace_bytes(h, batch, frames, height, width);
     if (!workspace || (((uintptr_t)workspace) & 255)) return fail(FG_EINVAL, "bad workspace");
@@ -859,13 +858,7 @@ int fg_wan_set_vace_context(fg_wan* h, const float* vid_context, int batch, int 
     const size_t D = h->D, L = (size_t)frames * (height / 2) * (width / 2), M = (size_t)batch * L;
     int rc;
     h->vctx_B = 0;  // (nothing valid until everything below is in place)
-    if (M * D != h->vctx_elems) {
-        h->drop_graphs();
-        h->free(h->vctx);
-        h->vctx = nullptr, h->vctx_elems = 0;
-        if ((rc = h->alloc(&h->vctx, M * D * 2))) return rc;
-        h->vctx_elems = M * D;
-    }
+    if ((rc = h->resize(h->vctx, h->vctx_bytes, M * D * 2))) return rc;
     // `processed_control_states` (VaceWan/network.py:81-88): the embedded context's tokens, THEN zero rows up to the video's token
     // count; proj_in over all of them (a padded row becomes the bias).  bf16 operands in every mode: once per context, like the text.
     if (ctx_frames < frames) HIP_TRY(hipMemsetAsync(workspace, 0, M * D * 2, s));
@@ -881,7 +874,7 @@ int fg_wan_vace_context_read(fg_wan* h, float* ctx_in_out, void* stream) {
     if (!h || !ctx_in_out) return fail(FG_EINVAL, "null argument");
     if (!h->is_vace) return fail(FG_EINVAL, "not a VACE handle (fg_wan_create_vace)");
     if (h->vctx_B == 0) return fail(FG_ENOTREADY, "no VACE context is set (call fg_wan_set_vace_context)");
-    HIP_TRY(launch_from_act(1, h->vctx, ctx_in_out, (int64_t)h->vctx_elems, (hipStream_t)stream));
+    HIP_TRY(launch_from_act(1, h->vctx, ctx_in_out, (int64_t)(h->vctx_bytes / 2), (hipStream_t)stream));
     return FG_OK;
 }
 
@@ -898,21 +891,69 @@ WanEmbedSrc wan_embed_src(const fg_wan* h, const float* x_t, int frames, int hei
 // (`_create_external_caches`, network_causal.py:708-812)
 int wan_ensure_caches(fg_wan* h, int batch, int height, int width, hipStream_t s) {
     const int cap = h->cfg.total_num_frames * (height / 2) * (width / 2), D = h->D;
-    if (h->cache_B == batch && h->cache_cap == cap) return FG_OK;
-    h->drop_graphs();
-    h->cache_B = h->cache_cap = 0;  // (nothing valid until every block has its new buffers)
+    fg_wan::CacheState& st = h->cur;
+    if (st.cache_B == batch && st.cache_cap == cap) return FG_OK;
+    const size_t had = (size_t)st.cache_B * st.cache_cap * D * 2, bytes = (size_t)batch * cap * D * 2;
+    st.cache_B = st.cache_cap = 0;  // (nothing valid until every block has its new buffers)
     for (fg_wan::Blk& b : h->blocks) {
-        h->free(b.kc);
-        h->free(b.vc);
-        b.kc = b.vc = nullptr;
-        const size_t bytes = (size_t)batch * cap * D * 2;
+        size_t have_k = had, have_v = had;
         int rc;
-        if ((rc = h->alloc(&b.kc, bytes)) || (rc = h->alloc(&b.vc, bytes))) return rc;
+        if ((rc = h->resize(b.kc, have_k, bytes)) || (rc = h->resize(b.vc, have_v, bytes))) return rc;
         HIP_TRY(hipMemsetAsync(b.kc, 0, bytes, s));
         HIP_TRY(hipMemsetAsync(b.vc, 0, bytes, s));
     }
-    h->cache_B = batch, h->cache_cap = cap;
-    h->stored_rows = 0;
+    st.cache_B = batch, st.cache_cap = cap;
+    st.stored_rows = 0;
+    return FG_OK;
+}
+
+// FG_ENOTREADY unless the text and the handle's own condition are set for this call's shape.  batch: what the network is called with
+// (a guided loop's stacked batch); hint: what the text, first-frame and VACE messages add to the setter's name ("", or the guided
+// loops' " with [cond; neg_cond]" - the image-to-video message never carries it).
+int wan_conditions_ready(const fg_wan* h, int batch, int frames, int height, int width, const char* hint = "") {
+    if (h->cur.text_B != batch) return fail(FG_ENOTREADY, "no text condition for batch %d (call fg_wan_set_text%s)", batch, hint);
+    if (h->is_i2v && (h->ff_B != batch || h->ff_F != frames || h->ff_H != height || h->ff_W != width))
+        return fail(FG_ENOTREADY, "no image-to-video condition for batch %d, %d frames of %d x %d (call fg_wan_set_i2v_cond)", batch, frames, height, width);
+    if (h->is_ti2v && !h->has_first_frame(batch, height, width))
+        return fail(FG_ENOTREADY, "no first frame for batch %d of %d x %d (call fg_wan_set_first_frame%s)", batch, height, width, hint);
+    if (h->is_vace && !h->has_vace_context(batch, frames, height, width))
+        return fail(FG_ENOTREADY, "no VACE context for batch %d, %d frames of %d x %d (call fg_wan_set_vace_context%s)", batch, frames, height, width, hint);
+    return FG_OK;
+}
+
+// What the handle is besides the plain network, as the refusals name it (nullptr: nothing): the bidirectional calls alone serve these
+const char* wan_variant(const fg_wan* h) {
+    if (h->is_i2v || h->is_ti2v) return "an image-to-video handle";
+    return h->is_vace ? "a VACE handle" : nullptr;
+}
+
+// FG_EINVAL on such a handle; what: "calls" (wan_forward) or "loops" (the chunked samplers)
+int wan_refuse_chunked(const fg_wan* h, const char* what) {
+    if (const char* v = wan_variant(h)) return fail(FG_EINVAL, "the chunked / causal %s are not implemented for %s", what, v);
+    return FG_OK;
+}
+
+// Everything handle-owned that a capture of wan_forward can bake in, behind the call's own arguments in the key of every Wan loop:
+// the buffers' addresses (block 0's stand for every block's: they are resized together), the text's and image's lengths and the
+// settings that choose a launch.  THE RULE: a new handle-owned buffer that wan_forward reads is added here and changes its address
+// through fg_wan::resize alone - a key that misses it, or a free that does not drop the graphs, is a replay on freed memory.
+void wan_graph_key_tail(const fg_wan* h, std::vector<int64_t>& key) {
+    const fg_wan::Blk& b0 = h->blocks[0];
+    const void* const bufs[] = {b0.kc, b0.kv2, b0.kvi, h->ff, h->ff0, h->vctx, h->vscale};
+    for (const void* p : bufs) key.push_back((int64_t)(uintptr_t)p);
+    key.insert(key.end(), {(int64_t)h->cur.text_L, (int64_t)h->img_L, (int64_t)h->fp8, (int64_t)h->ext.time_cond_diff});
+}
+
+// One time embedder on `rows` [BF]: Timesteps(256) -> Linear - SiLU - Linear into emb [BF][D], then time_proj(silu(emb)) into proj
+// [BF][6 D] (w.tf, w.th and w.st are its scratch)
+int wan_time_embedder(const fg_wan* h, const float* rows, int w1, int b1, int w2, int b2, int wp, int bp, float* emb, float* proj, int BF, WanWs& w,
+                      hipStream_t s) {
+    const int D = h->D, fq = h->cfg.freq_dim;
+    HIP_TRY(launch_dit_fourier(rows, w.tf, BF, fq, s));
+    HIP_TRY(launch_linear(w.tf, h->P(w1), h->P(b1), w.th, BF, fq, D, 1, s));
+    HIP_TRY(launch_linear(w.th, h->P(w2), h->P(b2), emb, BF, D, D, 0, s));
+    HIP_TRY(launch_silu(emb, w.st, (int64_t)BF * D, s));
+    HIP_TRY(launch_linear(w.st, h->P(wp), h->P(bp), proj, BF, D, 6 * D, 0, s));
     return FG_OK;
 }
 
@@ -991,15 +1032,15 @@ int wan_block(fg_wan* h, fg_wan::Blk& b, void*& x, void*& xn, const fg_wan_block
         (rc = wan_gemm(a, b.p_q2, h->P(b.q2_b), w.qkv, M, D, D, s, 0, nullptr, 0, 1, nullptr, w.gs, w.gs_bytes)))
         return rc;
     HIP_TRY(launch_rms_rope(D, w.qkv, D, h->P(b.nq2), c.eps, nullptr, w.qn, (int64_t)L * D, 0, D, M, L, s));
-    const int64_t tbs = (int64_t)h->text_L * 2 * D;
+    const int64_t tbs = (int64_t)h->cur.text_L * 2 * D;
     if (h->is_i2v && h->img_L > 0) {
         // ... and, separately normalised, to the image tokens; the two outputs summed (network_causal.py:294-358)
         const int64_t ibs = (int64_t)((h->img_L + 31) & ~31) * 2 * D;
-        HIP_TRY(launch_wan_dual_xattn(w.qn, D, (int64_t)L * D, b.kv2, (const __bf16*)b.kv2 + D, 2 * D, tbs, h->text_L, b.kvi, (const __bf16*)b.kvi + D,
+        HIP_TRY(launch_wan_dual_xattn(w.qn, D, (int64_t)L * D, b.kv2, (const __bf16*)b.kv2 + D, 2 * D, tbs, h->cur.text_L, b.kvi, (const __bf16*)b.kvi + D,
                                       2 * D, ibs, h->img_L, w.att, D, (int64_t)L * D, batch, h->H, L, s));
     } else {
         HIP_TRY(launch_fa128(w.qn, D, (int64_t)L * D, b.kv2, (const __bf16*)b.kv2 + D, 2 * D, tbs, w.att, D, (int64_t)L * D, batch, h->H, L,
-                             h->text_L, s, w.fa));
+                             h->cur.text_L, s, w.fa));
     }
     if (bt && bt->attn2) HIP_TRY(launch_from_act(1, w.att, bt->attn2, MD, s));
     if ((rc = wan_stage(h, w.att, D, w.y8, w.ys, M, s, a)) ||
@@ -1052,18 +1093,12 @@ int wan_forward(fg_wan* h, const float* x_t, const float* t_frames, float* out, 
         if (frames > h->cfg.rope_max_seq_len)
             return fail(FG_EINVAL, "%d frames exceed the RoPE table (rope_max_seq_len = %d)", frames, h->cfg.rope_max_seq_len);
     }
-    if ((h->is_i2v || h->is_ti2v) && !full) return fail(FG_EINVAL, "the chunked / causal calls are not implemented for an image-to-video handle");
-    if (h->is_vace && !full) return fail(FG_EINVAL, "the chunked / causal calls are not implemented for a VACE handle");
+    int rc;
+    if (!full && (rc = wan_refuse_chunked(h, "calls"))) return rc;
     if (!h->packed) return fail(FG_ENOTREADY, "weights are not packed (call fg_wan_pack_weights)");
-    if (batch <= 0 || frames <= 0 || height <= 0 || width <= 0 || (height & 1) || (width & 1) || !workspace || (((uintptr_t)workspace) & 255))
+    if (!wan_shape_ok(batch, frames, height, width) || !workspace || (((uintptr_t)workspace) & 255))
         return fail(FG_EINVAL, "bad batch / frames / size / workspace");
-    if (h->text_B != batch) return fail(FG_ENOTREADY, "no text condition for batch %d (call fg_wan_set_text)", batch);
-    if (h->is_i2v && (h->ff_B != batch || h->ff_F != frames || h->ff_H != height || h->ff_W != width))
-        return fail(FG_ENOTREADY, "no image-to-video condition for batch %d, %d frames of %d x %d (call fg_wan_set_i2v_cond)", batch, frames, height, width);
-    if (h->is_ti2v && !h->has_first_frame(batch, height, width))
-        return fail(FG_ENOTREADY, "no first frame for batch %d of %d x %d (call fg_wan_set_first_frame)", batch, height, width);
-    if (h->is_vace && !h->has_vace_context(batch, frames, height, width))
-        return fail(FG_ENOTREADY, "no VACE context for batch %d, %d frames of %d x %d (call fg_wan_set_vace_context)", batch, frames, height, width);
+    if ((rc = wan_conditions_ready(h, batch, frames, height, width))) return rc;
     if (tp)  // a VACE block that the call's skip_layers keep from running has nothing to tap
         for (int i = 0; i < tp->n; ++i)
             if (tp->blocks[i] >= (int)h->blocks.size() && tp->blocks[i] - (int)h->blocks.size() >= wan_vace_hints_consumed(h, full))
@@ -1074,7 +1109,7 @@ int wan_forward(fg_wan* h, const float* x_t, const float* t_frames, float* out, 
     const int D = h->D, gh = height / 2, gw = width / 2, fs = gh * gw, BF = batch * frames, L = frames * fs, M = batch * L;
     const int cap = c.total_num_frames * fs;
     if (full) {
-        if ((int64_t)batch * frames * fs > INT32_MAX / 2) return fail(FG_EINVAL, "batch x tokens exceeds the kernels' 32-bit row index");
+        if (!wan_rows_fit(batch, frames, height, width)) return fail(FG_EINVAL, "batch x tokens exceeds the kernels' 32-bit row index");
     } else if (cur_start_frame < 0 || (cur_start_frame + frames) * fs > cap)
         return fail(FG_EINVAL, "frames [%d, %d) exceed the cache of total_num_frames = %d", cur_start_frame, cur_start_frame + frames, c.total_num_frames);
     if (fs > c.rope_max_seq_len * c.rope_max_seq_len || gh > c.rope_max_seq_len || gw > c.rope_max_seq_len) return fail(FG_EINVAL, "grid exceeds the RoPE table");
@@ -1085,18 +1120,15 @@ int wan_forward(fg_wan* h, const float* x_t, const float* t_frames, float* out, 
     if (need > workspace_bytes) return fail(FG_ENOMEM, "workspace too small: need %zu bytes, got %zu", need, workspace_bytes);
     if (block_causal && !full && frames != c.total_num_frames)
         return fail(FG_EINVAL, "the block-causal call takes all total_num_frames = %d frames, got %d", c.total_num_frames, frames);
-    if (!block_causal) {
-        int rc0 = wan_ensure_caches(h, batch, height, width, s);
-        if (rc0) return rc0;
-    }
+    if (!block_causal && (rc = wan_ensure_caches(h, batch, height, width, s))) return rc;
     const int cache_start = cur_start_frame * fs;
     // The chunk's K / V go to their cache rows in EVERY call (attention then reads one contiguous prefix), where the reference writes
     // them only under store_kv and attends over [cache[:start] | current] (network_causal.py:385-400).  The two agree as long as a
     // store_kv = 0 call does not land on rows an earlier store_kv = 1 call filled - those are later chunks' context.  The student
     // loops (causvid.py:150-172, self_forcing.py:92-241) never do that; anything else is refused, not silently answered differently.
-    if (!block_causal && !store_kv && cache_start < h->stored_rows)
+    if (!block_causal && !store_kv && cache_start < h->cur.stored_rows)
         return fail(FG_EINVAL, "store_kv = 0 at frame %d would overwrite cached keys / values (frames [0, %d) are stored): re-evaluating a stored "
-                    "chunk without storing it is not implemented", cur_start_frame, h->stored_rows / fs);
+                    "chunk without storing it is not implemented", cur_start_frame, h->cur.stored_rows / fs);
     // condition embedder, per frame (:586-590): Timesteps(256) -> Linear - SiLU - Linear; time_proj(silu(temb))
     const float* t_rows_in = t_frames;  // the caller's rows
     if (h->is_ti2v) {
@@ -1105,11 +1137,7 @@ int wan_forward(fg_wan* h, const float* x_t, const float* t_frames, float* out, 
         HIP_TRY(launch_wan_ti2v_zero_frame0(t_frames, w.st, BF, frames, s));
         t_frames = w.st;
     }
-    HIP_TRY(launch_dit_fourier(t_frames, w.tf, BF, c.freq_dim, s));
-    HIP_TRY(launch_linear(w.tf, h->P(h->t1_w), h->P(h->t1_b), w.th, BF, c.freq_dim, D, 1, s));
-    HIP_TRY(launch_linear(w.th, h->P(h->t2_w), h->P(h->t2_b), w.temb, BF, D, D, 0, s));
-    HIP_TRY(launch_silu(w.temb, w.st, (int64_t)BF * D, s));
-    HIP_TRY(launch_linear(w.st, h->P(h->tp_w), h->P(h->tp_b), w.tproj, BF, D, 6 * D, 0, s));
+    if ((rc = wan_time_embedder(h, t_frames, h->t1_w, h->t1_b, h->t2_w, h->t2_b, h->tp_w, h->tp_b, w.temb, w.tproj, BF, w, s))) return rc;
     if (full && full->r_frames) {
         // r_embedder on r (or t - r), the `encoder_depth is None` branch (Wan/network.py:330-351): temb += remb, timestep_proj +=
         // r_timestep_proj.  Its scratch is the blocks' and the output layer's modulation rows, which nothing has written yet.
@@ -1118,17 +1146,12 @@ int wan_forward(fg_wan* h, const float* x_t, const float* t_frames, float* out, 
         // frame 0 zeroed behind them - both masked rows are zero there, and so is their difference)
         HIP_TRY(launch_wan_r_rows(t_rows_in, full->r_frames, h->ext.time_cond_diff, rrow, BF, s));
         if (h->is_ti2v) HIP_TRY(launch_wan_ti2v_zero_frame0(rrow, rrow, BF, frames, s));
-        HIP_TRY(launch_dit_fourier(rrow, w.tf, BF, c.freq_dim, s));
-        HIP_TRY(launch_linear(w.tf, h->P(h->r1_w), h->P(h->r1_b), w.th, BF, c.freq_dim, D, 1, s));
-        HIP_TRY(launch_linear(w.th, h->P(h->r2_w), h->P(h->r2_b), remb, BF, D, D, 0, s));
-        HIP_TRY(launch_silu(remb, w.st, (int64_t)BF * D, s));
-        HIP_TRY(launch_linear(w.st, h->P(h->rp_w), h->P(h->rp_b), rproj, BF, D, 6 * D, 0, s));
+        if ((rc = wan_time_embedder(h, rrow, h->r1_w, h->r1_b, h->r2_w, h->r2_b, h->rp_w, h->rp_b, remb, rproj, BF, w, s))) return rc;
         HIP_TRY(launch_wan_add_r(w.temb, remb, (int64_t)BF * D, w.tproj, rproj, (int64_t)BF * 6 * D, s));
     }
     HIP_TRY(launch_wan_rope_table(h->tab_t, h->tab_h, h->tab_w, w.cs, L, fs, gw, cur_start_frame, c.rope_max_seq_len, h->npt, h->nph, h->npw, s));
     HIP_TRY(launch_wan_embed(wan_embed_src(h, x_t, frames, height, width), h->P(h->pe_w), h->P(h->pe_b), w.x0, batch, D, L, 0, s));
     void *x = w.x0, *xn = w.x1;
-    int rc;
     const int64_t cbs = (int64_t)cap * D;
     const int64_t MD = (int64_t)M * D;
     if (tp && tp->temb) HIP_TRY(hipMemcpyAsync(tp->temb, w.temb, sizeof(float) * (size_t)BF * D, hipMemcpyDeviceToDevice, s));
@@ -1167,7 +1190,7 @@ int wan_forward(fg_wan* h, const float* x_t, const float* t_frames, float* out, 
             ++vj;
         }
     }
-    if (!block_causal && store_kv && cache_start + L > h->stored_rows) h->stored_rows = cache_start + L;
+    if (!block_causal && store_kv && cache_start + L > h->cur.stored_rows) h->cur.stored_rows = cache_start + L;
     HIP_TRY(launch_wan_outmod(h->P(h->sst), w.temb, w.omod, BF, D, s));
     HIP_TRY(launch_wan_ti2v_final(D, x, w.omod, h->P(h->po_w), h->P(h->po_b), h->is_ti2v ? h->ff0 : nullptr, out, M, frames, gh, gw, c.out_channels,
                                   c.eps, 0, s));
@@ -1207,7 +1230,7 @@ int fg_wan_forward_features(fg_wan* h, const float* x_t, const float* t_frames, 
 }
 
 size_t fg_wan_full_workspace_bytes(const fg_wan* h, int batch, int frames, int height, int width) {
-    if (!h || batch <= 0 || frames <= 0 || height <= 0 || width <= 0 || (height & 1) || (width & 1)) return 0;
+    if (!h || !wan_shape_ok(batch, frames, height, width)) return 0;
     Arena A;
     A.dry = true;
     WanWs w;

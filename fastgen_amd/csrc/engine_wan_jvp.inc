@@ -51,12 +51,11 @@ size_t wan_jvp_plan(const fg_wan* h, int B, int Fr, int gh, int gw, Arena& A, Wa
     return (A.off + 255) & ~(size_t)255;
 }
 
-// why this handle has no jvp (nullptr: it has one)
-const char* wan_jvp_refusal(const fg_wan* h) {
-    if (h->fp8) return "fg_wan_jvp: the fp8 compute mode has no forward-mode derivative (bf16 handles only)";
-    if (h->is_i2v || h->is_ti2v) return "fg_wan_jvp: not implemented for an image-to-video handle";
-    if (h->is_vace) return "fg_wan_jvp: not implemented for a VACE handle";
-    return nullptr;
+// FG_EINVAL on a handle that has no jvp
+int wan_jvp_refusal(const fg_wan* h) {
+    if (h->fp8) return fail(FG_EINVAL, "fg_wan_jvp: the fp8 compute mode has no forward-mode derivative (bf16 handles only)");
+    if (const char* v = wan_variant(h)) return fail(FG_EINVAL, "fg_wan_jvp: not implemented for %s", v);
+    return FG_OK;
 }
 
 // One time embedder with tangent: rows t / td -> embedding e / ed [BF][D] and projection p / pd [BF][6 D]
@@ -117,8 +116,8 @@ int wan_jvp_block(fg_wan* h, fg_wan::Blk& b, WanJvpWs& w, int batch, int fs, int
         (rc = wan_gemm(WanOperand{w.yd}, b.p_q2, nullptr, w.qkvd, M, D, D, s, 0, nullptr, 0, 1, nullptr, w.gs, w.gs_bytes)))
         return rc;
     HIP_TRY(launch_wan_rms_rope_jvp(D, w.qkv, w.qkvd, D, h->P(b.nq2), c.eps, nullptr, w.qn, w.qnd, LD, D, M, L, s));
-    HIP_TRY(launch_wan_attention_jvp(w.qn, w.qnd, D, LD, b.kv2, (const __bf16*)b.kv2 + D, nullptr, nullptr, 2 * D, (int64_t)h->text_L * 2 * D, w.att,
-                                     w.attd, D, LD, batch, h->H, L, h->text_L, s));
+    HIP_TRY(launch_wan_attention_jvp(w.qn, w.qnd, D, LD, b.kv2, (const __bf16*)b.kv2 + D, nullptr, nullptr, 2 * D, (int64_t)h->cur.text_L * 2 * D, w.att,
+                                     w.attd, D, LD, batch, h->H, L, h->cur.text_L, s));
     if ((rc = wan_jvp_residual(w, w.att, w.attd, b.p_o2, h->P(b.o2_b), nullptr, nullptr, 0, 1, M, D, D, s))) return rc;
     // 3. feed-forward: the pre-activation is stored (bf16, the token GEMM's output type) and the GELU is a pass of its own
     HIP_TRY(launch_wan_ln_modulate_jvp(D, w.x[0], w.xd[0], w.mod, modd, 6 * D, 3 * D, 4 * D, w.y, w.yd, M, fs, 1e-6f, s));
@@ -130,8 +129,7 @@ int wan_jvp_block(fg_wan* h, fg_wan::Blk& b, WanJvpWs& w, int batch, int fs, int
 }
 
 bool wan_jvp_shape_ok(int batch, int frames, int height, int width) {
-    return batch > 0 && frames > 0 && height > 0 && width > 0 && !(height & 1) && !(width & 1) &&
-           (int64_t)batch * frames * (height / 2) * (width / 2) <= INT32_MAX / 2;
+    return wan_shape_ok(batch, frames, height, width) && wan_rows_fit(batch, frames, height, width);
 }
 
 }  // namespace
@@ -139,7 +137,7 @@ bool wan_jvp_shape_ok(int batch, int frames, int height, int width) {
 extern "C" {
 
 size_t fg_wan_jvp_workspace_bytes(const fg_wan* h, int batch, int frames, int height, int width) {
-    if (!h || wan_jvp_refusal(h) || !wan_jvp_shape_ok(batch, frames, height, width)) return 0;
+    if (!h || h->fp8 || wan_variant(h) || !wan_jvp_shape_ok(batch, frames, height, width)) return 0;
     Arena A;
     A.dry = true;
     WanJvpWs w;
@@ -150,7 +148,8 @@ int fg_wan_jvp(fg_wan* h, const float* x_t, const float* t_frames, const float* 
                const float* vr_frames, float* out, float* jvp, int batch, int frames, int height, int width, const int* skip_layers, int num_skip,
                void* workspace, size_t workspace_bytes, void* stream) {
     if (!h || !x_t || !t_frames || !v_x || !out || !jvp) return fail(FG_EINVAL, "fg_wan_jvp: null argument");
-    if (const char* why = wan_jvp_refusal(h)) return fail(FG_EINVAL, "%s", why);
+    int rc;
+    if ((rc = wan_jvp_refusal(h))) return rc;
     if (skip_layers || num_skip != 0) return fail(FG_EINVAL, "fg_wan_jvp: skip_layers is not implemented");
     if (r_frames && !h->ext.r_timestep) return fail(FG_EINVAL, "fg_wan_jvp: r_frames given, but the handle has no r_embedder (fg_wan_create_ex, r_timestep = 1)");
     if (vr_frames && !r_frames) return fail(FG_EINVAL, "fg_wan_jvp: vr_frames given without r_frames");
@@ -165,14 +164,13 @@ int fg_wan_jvp(fg_wan* h, const float* x_t, const float* t_frames, const float* 
     const int D = h->D, gh = height / 2, gw = width / 2, fs = gh * gw, BF = batch * frames, L = frames * fs, M = batch * L;
     if (gh > c.rope_max_seq_len || gw > c.rope_max_seq_len) return fail(FG_EINVAL, "fg_wan_jvp: grid exceeds the RoPE table");
     if (!h->packed) return fail(FG_ENOTREADY, "weights are not packed (call fg_wan_pack_weights)");
-    if (h->text_B != batch) return fail(FG_ENOTREADY, "no text condition for batch %d (call fg_wan_set_text)", batch);
+    if ((rc = wan_conditions_ready(h, batch, frames, height, width))) return rc;
     Arena A;
     A.base = (char*)workspace;
     WanJvpWs w;
     const size_t need = wan_jvp_plan(h, batch, frames, gh, gw, A, w);
     if (need > workspace_bytes) return fail(FG_ENOMEM, "workspace too small: need %zu bytes, got %zu", need, workspace_bytes);
     hipStream_t s = (hipStream_t)stream;
-    int rc;
     // the zero rows: a null vt / vr, and the bias of the tangent's patch embedding (zrow | zbias are neighbours in the plan)
     HIP_TRY(hipMemsetAsync(w.zrow, 0, (size_t)((char*)w.rrow - (char*)w.zrow), s));
     const float* vt = vt_frames ? vt_frames : w.zrow;
