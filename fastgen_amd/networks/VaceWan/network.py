@@ -21,19 +21,19 @@ than the video, `prepare_vid_conditioning` without ready-made latents (the depth
 from __future__ import annotations
 
 import ctypes
-import weakref
 from typing import Any, Dict, List, Optional, Sequence, Union
 
 import torch
 
 from fastgen_amd import _lib
-from fastgen_amd.networks import _engine
 from fastgen_amd.networks._engine import ptr
+from fastgen_amd.networks.Wan._shared import ConditionSlot
 from fastgen_amd.networks.Wan.network import Wan
 
 
 class VACEWan(Wan):
     is_vid2vid = True
+    _SLOTS = ("text", "vace")  # (packing invalidates the context - proj_in, vace_patch_embedding - together with the text)
 
     def __init__(self, num_attention_heads: int = 12, attention_head_dim: int = 128, in_channels: int = 16, out_channels: int = 16,
                  text_dim: int = 4096, freq_dim: int = 256, ffn_dim: int = 8960, num_layers: int = 30,
@@ -48,7 +48,7 @@ class VACEWan(Wan):
         v.vace_in_channels, v.num_vace_layers = int(vace_in_channels), len(layers)
         for j, i in enumerate(layers):
             v.vace_layers[j] = i
-        self._vace_cfg, self._vace_key, self._scale_key = v, None, None
+        self._vace_cfg, self._scale_slot = v, ConditionSlot()  # (the scales outlive a packing)
         self.vace_layers, self.vace_in_channels = tuple(layers), int(vace_in_channels)
         self.context_scale, self.depth_model_path = context_scale, depth_model_path
         self._all_zero_latent = None
@@ -81,12 +81,12 @@ class VACEWan(Wan):
 
     # ---- the condition -----------------------------------------------------------------------------------------------------
     @staticmethod
-    def _unpack(condition: Any, what: str = "condition"):
-        assert isinstance(condition, dict), f"{what} must be a dict"
+    def _split_condition(condition: Any, what: str = "condition"):
+        assert isinstance(condition, dict), f"{what} must be a dict"  # (the reference's asserts, VaceWan/network.py:679-681)
         assert "text_embeds" in condition, f"{what} must contain 'text_embeds'"
         assert "vid_context" in condition, f"{what} must contain 'vid_context'"
         text = condition["text_embeds"]
-        return (torch.stack(text, dim=0) if isinstance(text, list) else text), condition["vid_context"]
+        return (torch.stack(text, dim=0) if isinstance(text, list) else text), (condition["vid_context"],)
 
     def _scales(self) -> List[float]:
         """`control_hidden_states_scale` as `VACEWan.forward` forms it (VaceWan/network.py:698-715), with its error texts."""
@@ -103,16 +103,12 @@ class VACEWan(Wan):
             return [float(v) for v in s.detach().cpu().reshape(-1).tolist()]
         raise TypeError(f"context_scale must be a number, a list or a tensor, got {type(s).__name__}")
 
-    def _forget_text(self) -> None:
-        super()._forget_text()
-        self._vace_key = None  # packing invalidates the context (proj_in, vace_patch_embedding) together with the text
-
     def _set_scales(self, dev) -> None:
         s = self._scales()
-        if self._scale_key == s:
+        if self._scale_slot.same(extra=s):
             return
         _lib.check(_lib.lib().fg_wan_set_vace_scale(self._h, (ctypes.c_float * len(s))(*s), len(s), self._stream(dev)))
-        self._scale_key = s
+        self._scale_slot.remember(extra=s)
 
     def _set_context(self, ctx: torch.Tensor, B: int, F: int, H: int, W: int, dev) -> None:
         """The control video into the handle, once per (tensor object, version, shape) as `_set_text`."""
@@ -123,40 +119,32 @@ class VACEWan(Wan):
             raise ValueError(f"vid_context is {ctx.shape[3]}x{ctx.shape[4]}, the video {H}x{W}: the context must have the video's height and width")
         if not 1 <= ctx.shape[2] <= F:
             raise ValueError(f"vid_context has {ctx.shape[2]} frames, the video {F}: a context with more frames than the video is not implemented")
-        key = (weakref.ref(ctx), 0 if ctx.is_inference() else ctx._version, tuple(ctx.shape), F)
-        if self._vace_key is not None and self._vace_key[0]() is ctx and self._vace_key[1:] == key[1:]:
+        slot = self._slots["vace"]
+        if slot.same(ctx, extra=(F,)):
             return
         c32 = ctx.detach().to(device=dev, dtype=torch.float32).contiguous()
         L = _lib.lib()
         ws = self._eng.workspace(("vace", self._cfg.compute_dtype), L.fg_wan_vace_context_workspace_bytes(self._h, B, F, H, W), dev)
         _lib.check(L.fg_wan_set_vace_context(self._h, ptr(c32), B, F, ctx.shape[2], H, W, ptr(ws), ws.numel(), self._stream(dev)))
-        self._vace_key = key
+        slot.remember(ctx, extra=(F,))
 
-    def _prepare(self, x: torch.Tensor, what: str, ctx: torch.Tensor, stack: int = 1) -> None:
-        _engine.require_gpu(x)
-        B, F, H, W = self._check_video(x, what)
-        self._bind(x.device)  # (first: packing would invalidate what is set below)
-        self._set_scales(x.device)
-        self._set_context(ctx, B * stack, F, H, W, x.device)
+    def _set_rest(self, rest, B: int, F: int, H: int, W: int, dev) -> None:
+        self._set_scales(dev)  # (read at every call, as the reference reads `context_scale`)
+        self._set_context(*rest, B, F, H, W, dev)
 
-    # ---- calls -------------------------------------------------------------------------------------------------------------
+    def _sample_rest(self, rest, neg_rest, dev):
+        if neg_rest is None:
+            return rest
+        (ctx,), (nctx,) = rest, neg_rest
+        if nctx.shape != ctx.shape:
+            raise ValueError(f"neg_condition's vid_context {tuple(nctx.shape)} must be shaped like condition's {tuple(ctx.shape)}")
+        return (torch.cat([ctx.to(dev), nctx.to(dev)], dim=0),)
+
+    # ---- calls: `Wan`'s, under the control video (a new context or new scales at the same shapes replay the fused loops' graphs) ----
     def forward(self, x_t: torch.Tensor, t: torch.Tensor, condition: Optional[Dict[str, torch.Tensor]] = None, r: Optional[torch.Tensor] = None,
                 **kwargs):
-        text, ctx = self._unpack(condition)  # (the reference's asserts, VaceWan/network.py:679-681)
-        if kwargs.get("feature_indices") or kwargs.get("return_features_early") or kwargs.get("return_logvar"):
-            raise NotImplementedError("feature taps / logvar are not implemented for the bidirectional video DiT path")
         self._scales()  # (the reference's length check comes before the transformer runs)
-        self._no_autograd(x_t)
-        self._prepare(x_t, "x_t", ctx)
-        return super().forward(x_t, t, condition=text, r=r, **kwargs)
-
-    def few_step_sample(self, noise: torch.Tensor, condition: Any, t_list, **kwargs) -> torch.Tensor:
-        """`Wan.few_step_sample` under the control video: one `fg_wan_full_sampler_run` / one hipGraph replay.  A new context or new
-        scales at the same shapes replay the same graph (the handle's buffers are rewritten in place)."""
-        text, ctx = self._unpack(condition)
-        self._no_autograd()
-        self._prepare(noise, "noise", ctx)
-        return super().few_step_sample(noise, text, t_list, **kwargs)
+        return super().forward(x_t, t, condition=condition, r=r, **kwargs)
 
     @torch.no_grad()
     def sample(self, noise: torch.Tensor, condition: Optional[Dict[str, torch.Tensor]] = None,
@@ -164,21 +152,8 @@ class VACEWan(Wan):
                shift: float = 16.0, **kwargs) -> torch.Tensor:
         """`VACEWan.sample` (VaceWan/network.py:626-641: `Wan.sample` with guidance_scale 5.0, 50 steps, shift 16.0) over `Wan.sample`'s
         one call: when guided, the stacked batch [x; x] runs against the text and the control video of [condition; neg_condition]."""
-        text, ctx = self._unpack(condition)
-        guided = guidance_scale is not None and neg_condition is not None
-        neg_text = None
-        if guided:
-            neg_text, nctx = self._unpack(neg_condition, "neg_condition")
-            if nctx.shape != ctx.shape:
-                raise ValueError(f"neg_condition's vid_context {tuple(nctx.shape)} must be shaped like condition's {tuple(ctx.shape)}")
-            ctx = torch.cat([ctx.to(noise.device), nctx.to(noise.device)], dim=0)
-        self._prepare(noise, "noise", ctx, stack=2 if guided else 1)
-        try:
-            return super().sample(noise, condition=text, neg_condition=neg_text, guidance_scale=guidance_scale, num_steps=num_steps, shift=shift,
-                                  **kwargs)
-        finally:
-            if guided:
-                self._vace_key = None  # the handle holds the stacked context: the next call sets its own
+        return super().sample(noise, condition=condition, neg_condition=neg_condition, guidance_scale=guidance_scale, num_steps=num_steps,
+                              shift=shift, **kwargs)
 
 
 class CausalVACEWan:

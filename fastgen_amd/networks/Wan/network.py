@@ -93,29 +93,32 @@ class Wan(WanEngineNetwork):
             else:  # time_embedder.linear_1.weight, the one parameter that stays random
                 p.copy_((torch.randn(p.shape, generator=g) * 0.02).to(p.device))
 
-    # ---- one network call ---------------------------------------------------------------------------------------------------
-    def _check_video(self, x: torch.Tensor, what: str):
-        if x.ndim != 5 or x.shape[1] != self.in_channels:
-            raise ValueError(f"{what} must be [B, {self.in_channels}, F, H, W], got {tuple(x.shape)}")
-        return x.shape[0], x.shape[2], x.shape[3], x.shape[4]
-
+    # ---- the condition beside the text: what a dict-conditioned subclass (WanI2V, VACEWan) states ------------------------------------
     @staticmethod
-    def _text(condition: Any, what: str = "condition") -> torch.Tensor:
-        if condition is None:
-            raise ValueError(f"Wan needs the text {what} [B, L, text_dim]")
-        if isinstance(condition, dict):
-            raise NotImplementedError("image conditioning (a condition dict) is not implemented: pass the text embeddings")
-        return torch.stack(condition, dim=0) if isinstance(condition, list) else condition
+    def _split_condition(condition: Any, what: str = "condition"):
+        """`condition` as (the text, the rest: a tuple of what `_set_rest` takes).  A subclass asserts its dict's keys here."""
+        return condition, ()
 
-    def _no_autograd(self, *tensors) -> None:
-        if torch.is_grad_enabled() and (any(t.requires_grad for t in tensors) or any(p.requires_grad for p in self.parameters())):
-            raise NotImplementedError("fastgen_amd.Wan: the backward pass is not implemented; call under torch.no_grad() / "
-                                      "torch.inference_mode() (sampling)")
+    def _set_rest(self, rest, B: int, F: int, H: int, W: int, dev) -> None:
+        """Hand the rest of the condition to the handle for a call at batch B on an [F, H, W] video (after `_bind`: packing forgets it)."""
 
+    def _sample_rest(self, rest, neg_rest, dev):
+        """The rest of the condition for `sample`: stacked [condition; neg_condition] when guided (`neg_rest` is not None)."""
+        return rest
+
+    def _prepare(self, x: torch.Tensor, what: str, *rest, stack: int = 1) -> None:
+        """The rest of the condition into the handle as a call on `x` (`what` in the messages) at `stack` times its batch would set it."""
+        _engine.require_gpu(x)
+        B, F, H, W = self._check_video(x, what)
+        self._bind(x.device)  # (first: packing would invalidate what is set below)
+        self._set_rest(rest, B * stack, F, H, W, x.device)
+
+    # ---- one network call ---------------------------------------------------------------------------------------------------
     def forward(self, x_t: torch.Tensor, t: torch.Tensor, condition: Optional[Any] = None, r: Optional[torch.Tensor] = None,
                 return_features_early: bool = False, feature_indices: Optional[Set[int]] = None, return_logvar: bool = False,
                 unpatchify_features: bool = True, fwd_pred_type: Optional[str] = None, skip_layers: Optional[List[int]] = None,
                 **fwd_kwargs):
+        text, rest = self._split_condition(condition)
         if feature_indices or return_features_early or return_logvar:
             raise NotImplementedError("feature taps / logvar are not implemented for the bidirectional video DiT path")
         if fwd_kwargs:
@@ -126,32 +129,25 @@ class Wan(WanEngineNetwork):
             fwd_pred_type = self.net_pred_type
         else:
             assert fwd_pred_type in NET_PRED_TYPES, f"{fwd_pred_type} is not supported as fwd_pred_type"
-        dev = x_t.device
-        t_in = torch.atleast_1d(t.detach()).to(dev)
+        t_in = torch.atleast_1d(t.detach()).to(x_t.device)
         if t_in.ndim != 1:
             raise NotImplementedError(f"t must be [B] (timesteps given per token, [B, seq_len], are not implemented: expand_timesteps "
                                       f"expands a [B] t inside the network), got {tuple(t_in.shape)}")
         self._no_autograd(x_t)
-        _engine.require_gpu(x_t)
-        condition = self._text(condition)
-        B, F, H, W = self._check_video(x_t, "x_t")
+        text = self._text(text)
+        L = _lib.lib()
+        B, F, H, W, dev, ws = self._setup(x_t, "x_t", L.fg_wan_full_workspace_bytes)
         skip = sorted(set(int(i) for i in skip_layers)) if skip_layers else []
         if skip and (skip[0] < 0 or skip[-1] >= self.num_layers):
             raise ValueError(f"skip_layers must be block indices in [0, {self.num_layers}), got {list(skip_layers)}")
 
-        def rows(name, v):  # [B] in the schedule's units -> one embedder row per frame (`_compute_timestep_inputs`, :904-917)
-            v = self.noise_scheduler.rescale_t(_engine.per_sample(name, v, B, dev))
-            return v.to(torch.float32).view(B, 1).expand(B, F).contiguous()
+        def rows(name, v):  # [B] in the schedule's units -> one embedder row per frame
+            return self._frame_rows(self.noise_scheduler.rescale_t(_engine.per_sample(name, v, B, dev)), B, F)
 
         ts = rows("t", t_in)
         rs = rows("r", r) if r is not None else None
-        self._bind(dev)
-        L = _lib.lib()
-        need = L.fg_wan_full_workspace_bytes(self._h, B, F, H, W)
-        if need == 0:
-            raise ValueError(f"bad video shape: batch {B}, frames {F}, {H}x{W} (height and width must be even)")
-        ws = self._ws(need, dev)
-        self._set_text(condition, B, dev, ws)
+        self._set_rest(rest, B, F, H, W, dev)
+        self._set_text(text, B, dev, ws)
         x32 = x_t.detach().to(torch.float32).contiguous()
         out = torch.empty_like(x32)
         _lib.check(L.fg_wan_forward_full(self._h, ptr(x32), ptr(ts), ptr(rs), ptr(out), B, F, H, W,
@@ -183,31 +179,26 @@ class Wan(WanEngineNetwork):
             raise ValueError("r_timestep provided but no r_embedder is present")
         if not x_t.is_cuda:
             raise NotImplementedError("fastgen_amd.Wan.jvp runs on a HIP GPU only (no CPU path)")
-        B, F, H, W = self._check_video(x_t, "x_t")
+
+        def need(h, B, F, H, W):  # also the text embedding's scratch (the query at the smallest video is that scratch)
+            n = L.fg_wan_jvp_workspace_bytes(h, B, F, H, W)
+            return n and max(n, L.fg_wan_full_workspace_bytes(h, B, 1, 2, 2))
+
+        # a workspace of its own: forward()'s is neither used nor regrown here, it stays where a captured sampler saw it
+        B, F, H, W, dev, ws = self._setup(x_t, "x_t", need, key=("jvp", self._cfg.compute_dtype))
         if v_x.shape != x_t.shape:
             raise ValueError(f"v_x must be shaped like x_t {tuple(x_t.shape)}, got {tuple(v_x.shape)}")
-        need = L.fg_wan_jvp_workspace_bytes(self._h, B, F, H, W)
-        if need == 0:
-            raise ValueError(f"bad video shape: batch {B}, frames {F}, {H}x{W} (height and width must be even)")
-        dev = x_t.device
         condition = self._text(condition)
         sch = self.noise_scheduler
-
-        def rows(v):  # one embedder row per frame, as forward() builds them
-            return v.to(torch.float32).view(B, 1).expand(B, F).contiguous()
 
         def tangent(name, v):  # the derivative of rescale_t, a multiplication by num_steps or 1
             if v is None:
                 return None
-            return rows(sch._rescale(_engine.per_sample(name, v, B, dev).to(torch.float32)))
+            return self._frame_rows(sch._rescale(_engine.per_sample(name, v, B, dev).to(torch.float32)), B, F)
 
-        ts = rows(sch.rescale_t(_engine.per_sample("t", torch.atleast_1d(t.detach()).to(dev), B, dev)))
-        rs = rows(sch.rescale_t(_engine.per_sample("r", r, B, dev))) if r is not None else None
+        ts = self._frame_rows(sch.rescale_t(_engine.per_sample("t", torch.atleast_1d(t.detach()).to(dev), B, dev)), B, F)
+        rs = self._frame_rows(sch.rescale_t(_engine.per_sample("r", r, B, dev)), B, F) if r is not None else None
         vts, vrs = tangent("v_t", v_t), (tangent("v_r", v_r) if r is not None else None)
-        self._bind(dev)
-        # a workspace of its own, also for the text embedding's scratch (the query at the smallest video is that scratch): forward()'s is
-        # neither used nor regrown here, it stays where a captured sampler saw it
-        ws = self._eng.workspace(("jvp", self._cfg.compute_dtype), max(need, L.fg_wan_full_workspace_bytes(self._h, B, 1, 2, 2)), dev)
         self._set_text(condition, B, dev, ws)
         x32 = x_t.detach().to(torch.float32).contiguous()
         vx = v_x.detach().to(device=dev, dtype=torch.float32).contiguous()
@@ -229,26 +220,18 @@ class Wan(WanEngineNetwork):
         """The whole sampling loop over the whole video as ONE `fg_wan_full_sampler_run` call / one hipGraph replay: latents = noise *
         sigma(t_list[0]), then per step the network call and the schedule arithmetic of `loop` ('x0' | 'meanflow').  'sde' re-noises with
         `eps` ([steps - 1, B, C, F, H, W], injected) or device normals drawn from `seed`."""
+        text, rest = self._split_condition(condition)
         self._no_autograd()
         if not self.supports_fused_loop(loop):
             raise NotImplementedError(f"the fused sampler has no loop {loop!r} for net_pred_type={self.net_pred_type!r}, "
                                       f"r_timestep={self.r_timestep}, schedule_type={self.schedule_type!r}")
         n32, steps, tl_arr, eps, seed = _fused_sample_args(noise, t_list, sample_type, eps, seed)
-        condition = self._text(condition)
-        B, F, H, W = self._check_video(noise, "noise")
-        dev = noise.device
-        self._bind(dev)
+        text = self._text(text)
         L = _lib.lib()
-        need = L.fg_wan_full_sampler_workspace_bytes(self._h, B, F, H, W)
-        if need == 0:
-            raise ValueError(f"bad video shape: batch {B}, frames {F}, {H}x{W} (height and width must be even)")
-        ws = self._ws(need, dev)
-        self._set_text(condition, B, dev, ws)
-        sc = _lib.fg_wan_sampler_config()
-        rf = self.schedule_type != "edm"
-        sc.t_scale = float(self.noise_scheduler.num_steps) if rf else 1.0
-        sc.net_pred_flow = int(self.net_pred_type == "flow")
-        sc.schedule = _lib.FG_SCHEDULE_RF if rf else _lib.FG_SCHEDULE_EDM
+        B, F, H, W, dev, ws = self._setup(noise, "noise", L.fg_wan_full_sampler_workspace_bytes)
+        self._set_rest(rest, B, F, H, W, dev)
+        self._set_text(text, B, dev, ws)
+        sc = self._sampler_config()
         # every device pointer of the call is in the graph's key: the call runs on the handle's staging tensors, so that a second call
         # with the same shapes replays the graph whatever tensors the caller passes
         dt, st = self._cfg.compute_dtype, self._eng.staged
@@ -272,51 +255,33 @@ class Wan(WanEngineNetwork):
         PARITY UNPINNED: solver "unipc" (the default) restates diffusers' UniPCMultistepScheduler and "euler" is the plain flow-ODE
         step (Wan/solvers.py).  The network sees t_i = min(floor(1000 sigma_i) / 1000, max_t): the scheduler's integer timestep over
         num_train_timesteps, clamped as the reference clamps it (:958-961)."""
+        text, rest = self._split_condition(condition)
         assert self.schedule_type == "rf", f"{self.schedule_type} is not supported"
         if kwargs:
             raise TypeError(f"unexpected sample kwargs: {sorted(kwargs)}")
         if skip_layers:
             raise NotImplementedError("skip_layers in sample() (skip-layer guidance on the unconditional call) is not implemented; "
                                       "forward(skip_layers=...) serves a loop of separate calls")
-        _engine.require_gpu(noise)
         if self.net_pred_type != "flow":
             raise NotImplementedError(f"sample() needs a flow-predicting network, got net_pred_type {self.net_pred_type!r}")
-        from fastgen_amd.networks.Wan import solvers
-
-        condition = self._text(condition)
-        guided = guidance_scale is not None and neg_condition is not None
-        B, F, H, W = self._check_video(noise, "noise")
-        dev = noise.device
-        if guided:
-            neg_condition = self._text(neg_condition, "neg_condition")
-            if neg_condition.shape != condition.shape:
-                raise ValueError(f"neg_condition {tuple(neg_condition.shape)} must be shaped like condition {tuple(condition.shape)}")
-            text = torch.cat([condition.to(dev), neg_condition.to(dev)], dim=0)
-        else:
-            text = condition
+        neg_text, neg_rest = None, None
+        if guidance_scale is not None and neg_condition is not None:
+            neg_text, neg_rest = self._split_condition(neg_condition, "neg_condition")
+        rest = self._sample_rest(rest, neg_rest, noise.device)
         steps = int(num_steps)
-        sch = self.noise_scheduler
-        sigmas = solvers.flow_shift_sigmas(steps, float(shift))
-        table = solvers.multistep_table(sigmas, solver, float(guidance_scale) if guided else 1.0)
-        t_net = sch.safe_clamp(torch.floor(sigmas[:-1] * 1000.0) / 1000.0, min=sch.min_t, max=sch.max_t)
-        self._bind(dev)
+        text, guided, t_net, sc, t_arr, table_arr = self._guided_plan(text, neg_text, guidance_scale, steps, shift, solver, noise.device, clamp=True)
         L = _lib.lib()
-        need = L.fg_wan_full_guided_sampler_workspace_bytes(self._h, B, F, H, W, steps, int(guided))
-        if need == 0:
-            raise ValueError(f"bad video shape or step count: batch {B}, frames {F}, {H}x{W} (height and width must be even), {steps} steps")
-        ws = self._ws(need, dev)
-        self._text_key = None  # (a fresh `text` tensor when guided: embedded for this call)
+        B, F, H, W, dev, ws = self._setup(noise, "noise", L.fg_wan_full_guided_sampler_workspace_bytes, steps, int(guided),
+                                          bad=f"bad video shape or step count: {{}}, {steps} steps")
+        self._set_rest(rest, B * (2 if guided else 1), F, H, W, dev)
+        self._text_slot.forget()  # (a fresh `text` tensor when guided: embedded for this call)
         self._set_text(text, text.shape[0], dev, ws)
-        latents = sch.latents(noise=noise.to(torch.float32), t_init=t_net[0].to(dev))  # (:952-954)
-        sc = _lib.fg_wan_guided_sampler_config()
-        sc.t_scale, sc.context_noise, sc.guidance = float(sch.num_steps), 0.0, int(guided)
+        latents = self.noise_scheduler.latents(noise=noise.to(torch.float32), t_init=t_net[0].to(dev))  # (:952-954)
         xs = self._eng.staged(self._cfg.compute_dtype, "x", latents.contiguous())  # (staging tensor as in few_step_sample)
         try:
-            _lib.check(L.fg_wan_full_guided_sampler_run(
-                self._h, ctypes.byref(sc), ptr(xs), (ctypes.c_double * steps)(*t_net.tolist()),
-                (ctypes.c_double * (8 * steps))(*table.reshape(-1).tolist()), steps, B, F, H, W, ptr(ws), ws.numel(),
-                1 if use_graph else 0, self._stream(dev)))
+            _lib.check(L.fg_wan_full_guided_sampler_run(self._h, ctypes.byref(sc), ptr(xs), t_arr, table_arr, steps, B, F, H, W, ptr(ws), ws.numel(),
+                                                        1 if use_graph else 0, self._stream(dev)))
         finally:
             if guided:
-                self._text_key = None  # the handle holds the stacked text: the next call embeds its own
+                self._forget_text()  # the handle holds the stacked condition: the next call sets its own
         return xs.to(noise.dtype, copy=True)

@@ -27,13 +27,17 @@ from typing import Any, Optional, Set
 import torch
 
 from fastgen_amd import _lib
-from fastgen_amd.networks import _engine
 from fastgen_amd.networks._engine import ptr
 from fastgen_amd.networks.Wan._shared import WanEngineNetwork
+from fastgen_amd.networks.network import _fused_sample_args
 from fastgen_amd.networks.noise_schedule import NET_PRED_TYPES
 
 
 class CausalWan(WanEngineNetwork):
+    _NAME = "CausalWan"
+    CACHE_TAGS = {"pos": 0, "neg": 1}
+    _SLOTS = tuple(CACHE_TAGS)  # one text per cache tag
+
     def __init__(self, num_attention_heads: int = 12, attention_head_dim: int = 128, in_channels: int = 16, out_channels: int = 16,
                  text_dim: int = 4096, freq_dim: int = 256, ffn_dim: int = 8960, num_layers: int = 30, eps: float = 1e-6,
                  rope_max_seq_len: int = 1024, r_timestep: bool = False, net_pred_type: str = "flow", schedule_type: str = "rf",
@@ -51,33 +55,29 @@ class CausalWan(WanEngineNetwork):
                            out_channels=out_channels, text_dim=text_dim, freq_dim=freq_dim, ffn_dim=ffn_dim, num_layers=num_layers, eps=eps,
                            rope_max_seq_len=rope_max_seq_len, chunk_size=chunk_size, total_num_frames=total_num_frames,
                            compute_dtype=compute_dtype, enable_logvar_linear=enable_logvar_linear)
-        # _text_key: of the selected cache tag ("pos" outside a forward(cache_tag="neg") call); the other tag's:
-        self._text_key_other, self._tag = None, "pos"
+        self._tag = "pos"  # the selected cache tag ("pos" outside a forward(cache_tag="neg") call)
 
     # ---- library plumbing (the rest: WanEngineNetwork) -----------------------------------------------------------------------
-    def _forget_text(self) -> None:
-        self._text_key = self._text_key_other = None
+    @property
+    def _text_slot(self):
+        return self._slots[self._tag]
 
-    def _workspace(self, dev, B, F, H, W) -> torch.Tensor:
-        need = _lib.lib().fg_wan_workspace_bytes(self._h, B, F, H, W)
-        if need == 0:
-            raise ValueError(f"bad chunk shape: batch {B}, frames {F}, {H}x{W} (height and width must be even)")
-        return self._eng.workspace(self._cfg.compute_dtype, need, dev)
+    def _check_video(self, x: torch.Tensor, what: str):
+        B, C, F, H, W = x.shape
+        if C != self.in_channels:
+            raise ValueError(f"{what} must have {self.in_channels} channels, got {C}")
+        return B, F, H, W
 
     def clear_caches(self) -> None:
         """`CausalWan.clear_caches` (network_causal.py:1030-1054)."""
         if torch.cuda.is_available():
             _lib.check(_lib.lib().fg_wan_clear_caches(self._h, self._stream(torch.device("cuda", torch.cuda.current_device()))))
-        self._text_key = self._text_key_other = None
-
-    CACHE_TAGS = {"pos": 0, "neg": 1}
+        self._forget_text()
 
     def _select_tag(self, tag: str) -> None:
-        """Make `tag`'s cache set (and its text key) the one the library calls and `_set_text` act on."""
+        """Make `tag`'s cache set (and its text slot) the one the library calls and `_set_text` act on."""
         _lib.check(_lib.lib().fg_wan_select_cache_tag(self._h, self.CACHE_TAGS[tag]))
-        if tag != self._tag:
-            self._text_key, self._text_key_other = self._text_key_other, self._text_key
-            self._tag = tag
+        self._tag = tag
 
     def forward(self, x_t: torch.Tensor, t: torch.Tensor, condition: Optional[Any] = None, r: Optional[torch.Tensor] = None,
                 return_features_early: bool = False, feature_indices: Optional[Set[int]] = None, return_logvar: bool = False,
@@ -97,19 +97,9 @@ class CausalWan(WanEngineNetwork):
             fwd_pred_type = self.net_pred_type
         else:
             assert fwd_pred_type in NET_PRED_TYPES, f"{fwd_pred_type} is not supported as fwd_pred_type"
-        if torch.is_grad_enabled() and (x_t.requires_grad or any(p.requires_grad for p in self.parameters())):
-            raise NotImplementedError("fastgen_amd.CausalWan: the backward pass is not implemented; call under torch.no_grad() / "
-                                      "torch.inference_mode() (sampling)")
-        _engine.require_gpu(x_t)
-        if condition is None:
-            raise ValueError("CausalWan.forward needs the text condition [B, L, text_dim]")
-        condition = torch.stack(condition, dim=0) if isinstance(condition, list) else condition
-        B, C, F, H, W = x_t.shape
-        dev = x_t.device
-        if C != self.in_channels:
-            raise ValueError(f"x_t must have {self.in_channels} channels, got {C}")
-        self._bind(dev)
-        ws = self._workspace(dev, B, F, H, W)
+        self._no_autograd(x_t)
+        condition = self._text(condition, who="CausalWan.forward")
+        B, F, H, W, dev, ws = self._setup(x_t, "x_t", _lib.lib().fg_wan_workspace_bytes, bad="bad chunk shape: {}")
         self._select_tag(cache_tag)  # the tag's own caches and text around the call; "pos" is selected again whatever happens
         try:
             out = self._forward_selected(x_t, t, condition, B, F, H, W, dev, ws, is_ar, cur_start_frame, store_kv)
@@ -124,10 +114,7 @@ class CausalWan(WanEngineNetwork):
         """The network call on the selected cache tag: the raw fp32 output."""
         L = _lib.lib()
         self._set_text(condition, B, dev, ws)
-        # per-frame timesteps in the embedder's units (`_compute_timestep_inputs`, :1063-1075: rescale_t, [B] -> [B, F])
-        t_in = torch.atleast_1d(t.detach()).to(dev)
-        ts = self.noise_scheduler.rescale_t(t_in)
-        ts = (ts.view(-1, 1).expand(B, F) if ts.ndim == 1 else ts).to(torch.float32).contiguous()
+        ts = self._frame_rows(self.noise_scheduler.rescale_t(torch.atleast_1d(t.detach()).to(dev)), B, F)
         x32 = x_t.detach().to(torch.float32).contiguous()
         out = torch.empty_like(x32)
         if is_ar:
@@ -148,43 +135,18 @@ class CausalWan(WanEngineNetwork):
         the head that only fill the caches (`generator_fn_extrapolation`'s bridged segment head); exit_steps: one exit index per chunk
         (`SelfForcingModel.rollout_with_gradient`).  eps: noise videos to inject instead of device draws, [steps - 1 (+ 1 if context_noise
         > 0), B, C, F, H, W].  The caches are empty afterwards, as after the reference's loop."""
-        _engine.require_gpu(x)
-        if sample_type not in _lib.SAMPLE_TYPES:
-            raise NotImplementedError(f"student_sample_type must be one of 'sde', 'ode' but got {sample_type}")
+        # (the count includes the context-noise video; checked here only for this call's own message: the shared check then passes)
+        n_eps = max(len(t_list) - 2, 0) + (1 if context_noise and context_noise > 0 else 0)
+        if eps is not None and eps.numel() != n_eps * x.numel():
+            raise ValueError(f"eps must hold {n_eps} noise videos shaped like x")
+        x32, steps, tl_arr, eps, seed = _fused_sample_args(x, t_list, sample_type, eps, seed, n_eps)
         if self.net_pred_type not in ("flow", "x0"):
             raise NotImplementedError(f"net_pred_type {self.net_pred_type!r} has no fused loop")
-        if condition is None:
-            raise ValueError("CausalWan needs the text condition [B, L, text_dim]")
-        condition = torch.stack(condition, dim=0) if isinstance(condition, list) else condition
-        B, C, F, H, W = x.shape
-        dev = x.device
-        if C != self.in_channels:
-            raise ValueError(f"x must have {self.in_channels} channels, got {C}")
-        tl = [float(v) for v in (t_list.tolist() if isinstance(t_list, torch.Tensor) else t_list)]
-        steps = len(tl) - 1
-        assert tl[-1] == 0, "t_list[-1] must be zero"
-        self._bind(dev)
+        condition = self._text(condition, who="CausalWan")
         L = _lib.lib()
-        need = L.fg_wan_sampler_workspace_bytes(self._h, B, F, H, W)
-        if need == 0:
-            raise ValueError(f"bad video shape: batch {B}, frames {F}, {H}x{W} (height and width must be even)")
-        ws = self._eng.workspace(self._cfg.compute_dtype, need, dev)
+        B, F, H, W, dev, ws = self._setup(x, "x", L.fg_wan_sampler_workspace_bytes)
         self._set_text(condition, B, dev, ws)
-        x32 = x if (x.dtype == torch.float32 and x.is_contiguous()) else x.to(torch.float32).contiguous()
-        n_eps = max(steps - 1, 0) + (1 if context_noise and context_noise > 0 else 0)
-        if eps is not None:
-            eps = eps.to(device=dev, dtype=torch.float32).contiguous()
-            if eps.numel() != n_eps * x32.numel():
-                raise ValueError(f"eps must hold {n_eps} noise videos shaped like x")
-        if seed is None:
-            seed = int(torch.randint(0, 2**62, (1,)).item())
-        sc = _lib.fg_wan_sampler_config()
-        rf = self.schedule_type != "edm"
-        sc.t_scale = float(self.noise_scheduler.num_steps) if rf else 1.0
-        sc.context_noise = float(context_noise or 0.0)
-        sc.net_pred_flow = int(self.net_pred_type == "flow")
-        sc.schedule = _lib.FG_SCHEDULE_RF if rf else _lib.FG_SCHEDULE_EDM
-        sc.prefill_frames = int(prefill_frames)
+        sc = self._sampler_config(context_noise, prefill_frames)
         ex = None
         if exit_steps is not None:
             ex = (ctypes.c_int * len(exit_steps))(*[int(e) for e in exit_steps])
@@ -197,10 +159,10 @@ class CausalWan(WanEngineNetwork):
         xs, eps = self._eng.staged(dt, "x", x32), self._eng.staged(dt, "eps", eps)
         try:
             _lib.check(L.fg_wan_sampler_run(
-                self._h, ctypes.byref(sc), ptr(xs), (ctypes.c_double * (steps + 1))(*tl), steps, _lib.SAMPLE_TYPES[sample_type], ex,
-                ptr(eps), ctypes.c_uint64(seed), B, F, H, W, ptr(ws), ws.numel(), 1 if use_graph else 0, self._stream(dev)))
+                self._h, ctypes.byref(sc), ptr(xs), tl_arr, steps, _lib.SAMPLE_TYPES[sample_type], ex, ptr(eps), ctypes.c_uint64(seed), B, F, H, W,
+                ptr(ws), ws.numel(), 1 if use_graph else 0, self._stream(dev)))
         finally:
-            self._text_key = self._text_key_other = None  # the loop ends with clear_caches(): the text is forgotten with them
+            self._forget_text()  # the loop ends with clear_caches(): the text is forgotten with them
         x.copy_(xs)
         return x
 
@@ -226,59 +188,31 @@ class CausalWan(WanEngineNetwork):
         assert self.schedule_type == "rf", f"{self.schedule_type} is not supported"
         if kwargs:
             raise TypeError(f"unexpected sample kwargs: {sorted(kwargs)}")
-        _engine.require_gpu(noise)
         if self.net_pred_type != "flow":
             raise NotImplementedError(f"sample() needs a flow-predicting network, got net_pred_type {self.net_pred_type!r}")
-        if condition is None:
-            raise ValueError("CausalWan needs the text condition [B, L, text_dim]")
-        from fastgen_amd.networks.Wan import solvers
-
-        guided = guidance_scale is not None and neg_condition is not None
-        condition = torch.stack(condition, dim=0) if isinstance(condition, list) else condition
-        B, C, F, H, W = noise.shape
-        dev = noise.device
-        if C != self.in_channels:
-            raise ValueError(f"noise must have {self.in_channels} channels, got {C}")
-        if guided:
-            neg_condition = torch.stack(neg_condition, dim=0) if isinstance(neg_condition, list) else neg_condition
-            if neg_condition.shape != condition.shape:
-                raise ValueError(f"neg_condition {tuple(neg_condition.shape)} must be shaped like condition {tuple(condition.shape)}")
-            text = torch.cat([condition.to(dev), neg_condition.to(dev)], dim=0)
-        else:
-            text = condition
-        steps = int(sample_steps)
-        sigmas = solvers.flow_shift_sigmas(steps, float(shift))
-        table = solvers.multistep_table(sigmas, solver, float(guidance_scale) if guided else 1.0)
-        t_net = torch.floor(sigmas[:-1] * 1000.0) / 1000.0
-        self._bind(dev)
+        steps, cn = int(sample_steps), float(context_noise or 0.0)
+        text, guided, _, sc, t_arr, table_arr = self._guided_plan(condition, neg_condition, guidance_scale, steps, shift, solver, noise.device,
+                                                                  clamp=False, context_noise=cn)
         L = _lib.lib()
-        need = L.fg_wan_guided_sampler_workspace_bytes(self._h, B, F, H, W, steps, int(guided))
-        if need == 0:
-            raise ValueError(f"bad video shape or step count: batch {B}, frames {F}, {H}x{W} (height and width must be even), {steps} steps")
-        ws = self._eng.workspace(self._cfg.compute_dtype, need, dev)
+        B, F, H, W, dev, ws = self._setup(noise, "noise", L.fg_wan_guided_sampler_workspace_bytes, steps, int(guided),
+                                          bad=f"bad video shape or step count: {{}}, {steps} steps")
         self._select_tag("pos")
-        self._text_key = None  # (a fresh `text` tensor: embedded for this call)
+        self._text_slot.forget()  # (a fresh `text` tensor: embedded for this call)
         self._set_text(text, text.shape[0], dev, ws)
         x32 = noise if (noise.dtype == torch.float32 and noise.is_contiguous()) else noise.to(torch.float32).contiguous()
-        cn = float(context_noise or 0.0)
         if eps is not None:
             eps = eps.to(device=dev, dtype=torch.float32).contiguous()
             if eps.numel() != (x32.numel() if cn > 0 else 0):
                 raise ValueError("eps must hold one noise video shaped like noise (context_noise > 0 only)")
         if seed is None:
             seed = int(torch.randint(0, 2**62, (1,)).item())
-        sc = _lib.fg_wan_guided_sampler_config()
-        sc.t_scale = float(self.noise_scheduler.num_steps)
-        sc.context_noise = cn
-        sc.guidance = int(guided)
         dt = self._cfg.compute_dtype  # (staging tensors as in student_sample)
         xs, eps = self._eng.staged(dt, "x", x32), self._eng.staged(dt, "eps", eps)
         try:
             _lib.check(L.fg_wan_guided_sampler_run(
-                self._h, ctypes.byref(sc), ptr(xs), (ctypes.c_double * steps)(*t_net.tolist()),
-                (ctypes.c_double * (8 * steps))(*table.reshape(-1).tolist()), steps, ptr(eps), ctypes.c_uint64(seed), B, F, H, W,
-                ptr(ws), ws.numel(), 1 if use_graph else 0, self._stream(dev)))
+                self._h, ctypes.byref(sc), ptr(xs), t_arr, table_arr, steps, ptr(eps), ctypes.c_uint64(seed), B, F, H, W, ptr(ws), ws.numel(),
+                1 if use_graph else 0, self._stream(dev)))
         finally:
-            self._text_key = self._text_key_other = None  # the loop ends with clear_caches(): the text is forgotten with them
+            self._forget_text()  # the loop ends with clear_caches(): the text is forgotten with them
         noise.copy_(xs)
         return noise

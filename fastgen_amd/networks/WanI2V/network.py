@@ -6,7 +6,8 @@ handle.  The network of configs/experiments/WanI2V/config_dmd2_14b.py / config_s
 
 The condition is a dict: `text_embeds` [B, L, text_dim], `first_frame_cond` [B, 16, F, H, W] and, optionally,
 `encoder_hidden_states_image` [B, 257, image_dim] (absent, or `image_dim=0`: no image context - the blocks run the text attention alone).
-It is handed to the engine once per (tensor objects, versions, shapes), like the text.
+It is handed to the engine once per (tensor objects, versions, shapes), like the text; new first-frame contents or image tokens at
+the same shapes replay the fused loops' graphs (the handle's buffers are rewritten in place).
 
 PARITY UNPINNED like `Wan`; in addition the thirteen image keys (`transformer.condition_embedder.image_embedder.*`, per block
 `attn2.add_k_proj.*`, `attn2.add_v_proj.*`, `attn2.norm_added_k.weight`) and their order are read from the reference's key map
@@ -23,13 +24,11 @@ Raises (never falls back): everything `Wan` raises, any other mixture of the thr
 image embedder's `pos_embed` (FLF2V)."""
 from __future__ import annotations
 
-import weakref
 from typing import Any, Dict, List, Optional
 
 import torch
 
 from fastgen_amd import _lib
-from fastgen_amd.networks import _engine
 from fastgen_amd.networks._engine import ptr
 from fastgen_amd.networks.Wan.network import Wan
 
@@ -46,6 +45,7 @@ class WanI2V(Wan):
     # intermediate states unobservable in the result (tests/test_gpu_wan_ti2v.py: bit-equal to the generic loop), so
     # FastGenModel.generator_fn keeps the fused loop for a network that sets this
     fused_loop_preserves_conditioning = True
+    _SLOTS = ("text", "i2v")  # (packing invalidates the image-to-video condition together with the text)
 
     def __init__(self, num_attention_heads: int = 40, attention_head_dim: int = 128, in_channels: int = 36, out_channels: int = 16,
                  text_dim: int = 4096, freq_dim: int = 256, ffn_dim: int = 13824, num_layers: int = 40, image_dim: Optional[int] = 1280,
@@ -66,7 +66,7 @@ class WanI2V(Wan):
                 raise ValueError(f"Wan2.2 TI2V has no image encoder: image_dim must be None, got {image_dim}")
             ti2v = _lib.fg_wan_ti2v_config()
             ti2v.latent_channels = out_channels
-            self._i2v_cfg, self._ti2v_cfg, self._i2v_key = None, ti2v, None
+            self._i2v_cfg, self._ti2v_cfg = None, ti2v
             self.concat_mask, self.use_image_encoder, self.image_dim, self.latent_channels = False, False, 0, out_channels
             self.preserve_conditioning_is_identity, self.fused_loop_preserves_conditioning = False, True
             super().__init__(num_attention_heads=num_attention_heads, attention_head_dim=attention_head_dim, in_channels=in_channels,
@@ -76,7 +76,7 @@ class WanI2V(Wan):
         self._ti2v_cfg = None
         i2v = _lib.fg_wan_i2v_config()
         i2v.latent_channels, i2v.mask_channels, i2v.image_dim = out_channels, _MASK_CHANNELS, int(image_dim or 0)
-        self._i2v_cfg, self._i2v_key = i2v, None
+        self._i2v_cfg = i2v
         self.concat_mask, self.use_image_encoder, self.image_dim = True, bool(use_image_encoder), int(image_dim or 0)
         self.latent_channels = out_channels
         super().__init__(num_attention_heads=num_attention_heads, attention_head_dim=attention_head_dim, in_channels=in_channels,
@@ -96,35 +96,30 @@ class WanI2V(Wan):
         return x
 
     # ---- the condition -----------------------------------------------------------------------------------------------------
-    def _check_video(self, x: torch.Tensor, what: str):
-        if x.ndim != 5 or x.shape[1] != self.latent_channels:
-            raise ValueError(f"{what} must be [B, {self.latent_channels}, F, H, W], got {tuple(x.shape)}")
-        return x.shape[0], x.shape[2], x.shape[3], x.shape[4]
+    @property
+    def _video_channels(self) -> int:
+        return self.latent_channels
 
     @staticmethod
-    def _unpack(condition: Any, what: str = "condition"):
-        assert isinstance(condition, dict), f"{what} must be a dict"
+    def _split_condition(condition: Any, what: str = "condition"):
+        assert isinstance(condition, dict), f"{what} must be a dict"  # (the reference's asserts, WanI2V/network.py:457-459)
         assert "text_embeds" in condition, f"{what} must contain 'text_embeds'"
         assert "first_frame_cond" in condition, f"{what} must contain 'first_frame_cond'"
         text = condition["text_embeds"]
         text = torch.stack(text, dim=0) if isinstance(text, list) else text
-        return text, condition["first_frame_cond"], condition.get("encoder_hidden_states_image")
-
-    def _forget_text(self) -> None:
-        super()._forget_text()
-        self._i2v_key = None  # packing invalidates the image-to-video condition together with the text
+        return text, (condition["first_frame_cond"], condition.get("encoder_hidden_states_image"))
 
     def _set_first_frame(self, ff: torch.Tensor, B: int, F: int, H: int, W: int, dev) -> None:
         """Wan2.2 TI2V: frame 0 of `first_frame_cond` into the handle, once per (tensor object, version, shape) as `_set_text`."""
         C = self.latent_channels
         if ff.ndim != 5 or tuple(ff.shape[:2]) != (B, C) or ff.shape[2] not in (1, F) or tuple(ff.shape[3:]) != (H, W):
             raise ValueError(f"first_frame_cond must be {(B, C, 1, H, W)} (or {(B, C, F, H, W)}: only frame 0 is read), got {tuple(ff.shape)}")
-        key = (weakref.ref(ff), 0 if ff.is_inference() else ff._version, tuple(ff.shape))
-        if self._i2v_key is not None and self._i2v_key[0]() is ff and self._i2v_key[1:] == key[1:]:
+        slot = self._slots["i2v"]
+        if slot.same(ff):
             return
         ff32 = ff.detach()[:, :, :1].to(device=dev, dtype=torch.float32).contiguous()
         _lib.check(_lib.lib().fg_wan_set_first_frame(self._h, ptr(ff32), B, H, W, self._stream(dev)))
-        self._i2v_key = key
+        slot.remember(ff)
 
     def _set_i2v(self, ff: torch.Tensor, image: Optional[torch.Tensor], B: int, F: int, H: int, W: int, dev) -> None:
         """First-frame latents and image tokens into the handle, once per (tensor objects, versions, shapes) as `_set_text`."""
@@ -136,15 +131,8 @@ class WanI2V(Wan):
             raise ValueError(f"first_frame_cond must be {(B, self.latent_channels, F, H, W)} (zero-padded to the video's frames), got {tuple(ff.shape)}")
         if image is not None and (image.ndim != 3 or image.shape[0] != B or image.shape[2] != self.image_dim or not 1 <= image.shape[1] <= 1024):
             raise ValueError(f"encoder_hidden_states_image must be [{B}, 1 .. 1024, {self.image_dim}], got {tuple(image.shape)}")
-
-        def ident(t):
-            return None if t is None else (weakref.ref(t), 0 if t.is_inference() else t._version, tuple(t.shape))
-
-        def same(a, b):
-            return (a is None and b is None) or (a is not None and b is not None and a[0]() is b[0]() and a[1:] == b[1:])
-
-        key = (ident(ff), ident(image))
-        if self._i2v_key is not None and same(self._i2v_key[0], key[0]) and same(self._i2v_key[1], key[1]):
+        slot = self._slots["i2v"]
+        if slot.same(ff, image):
             return
         ff32 = ff.detach().to(device=dev, dtype=torch.float32).contiguous()
         im32 = None if image is None else image.detach().to(device=dev, dtype=torch.float32).contiguous()
@@ -155,40 +143,36 @@ class WanI2V(Wan):
             ws = self._eng.workspace(("i2v", self._cfg.compute_dtype), L.fg_wan_i2v_cond_workspace_bytes(self._h, B, Li), dev)
         _lib.check(L.fg_wan_set_i2v_cond(self._h, ptr(ff32), ptr(im32), B, F, H, W, Li, ptr(ws), ws.numel() if ws is not None else 0,
                                          self._stream(dev)))
-        self._i2v_key = key
+        slot.remember(ff, image)
 
-    def _prepare(self, x: torch.Tensor, what: str, ff: torch.Tensor, image: Optional[torch.Tensor], stack: int = 1) -> None:
-        _engine.require_gpu(x)
-        B, F, H, W = self._check_video(x, what)
-        self._bind(x.device)  # (first: packing would invalidate what is set below)
-        self._set_i2v(ff, image, B * stack, F, H, W, x.device)
+    def _set_rest(self, rest, B: int, F: int, H: int, W: int, dev) -> None:
+        self._set_i2v(*rest, B, F, H, W, dev)
+
+    def _sample_rest(self, rest, neg_rest, dev):
+        ff, image = rest
+        if self.is_ti2v:
+            ff = ff[:, :, :1]  # (only frame 0 is read; the stacked tensor below is a fresh one either way)
+        if neg_rest is not None:
+            nff, nimage = neg_rest
+            if (image is None) != (nimage is None):
+                raise ValueError("condition and neg_condition must both carry encoder_hidden_states_image, or neither")
+            ff = torch.cat([ff.to(dev), (nff[:, :, :1] if self.is_ti2v else nff).to(dev)], dim=0)
+            image = None if image is None else torch.cat([image.to(dev), nimage.to(dev)], dim=0)
+        return ff, image
 
     # ---- calls -------------------------------------------------------------------------------------------------------------
     def forward(self, x_t: torch.Tensor, t: torch.Tensor, condition: Optional[Dict[str, torch.Tensor]] = None, r: Optional[torch.Tensor] = None,
                 **kwargs):
-        text, ff, image = self._unpack(condition)  # (the reference's asserts, WanI2V/network.py:457-459)
-        if kwargs.get("feature_indices") or kwargs.get("return_features_early") or kwargs.get("return_logvar"):
-            raise NotImplementedError("feature taps / logvar are not implemented for the bidirectional video DiT path")
-        self._no_autograd(x_t)
-        self._prepare(x_t, "x_t", ff, image)
-        out = super().forward(x_t, t, condition=text, r=r, **kwargs)
+        out = super().forward(x_t, t, condition=condition, r=r, **kwargs)
         if self.is_ti2v:
             # `_replace_first_frame` behind convert_model_output (WanI2V/network.py:506-510): the conversion ran on the caller's x_t, the
             # condition's frame 0 lands last whatever fwd_pred_type is (the engine wrote it into the raw output already)
-            out[:, :, 0] = ff[:, :, 0].to(device=out.device, dtype=out.dtype)
+            out[:, :, 0] = condition["first_frame_cond"][:, :, 0].to(device=out.device, dtype=out.dtype)
         return out
 
     def supports_fused_loop(self, kind: str) -> bool:
         # (the MeanFlow loop would write the first-frame latents into a velocity: refused by the engine on this convention)
         return super().supports_fused_loop(kind) and not (self.is_ti2v and kind == "meanflow")
-
-    def few_step_sample(self, noise: torch.Tensor, condition: Any, t_list, **kwargs) -> torch.Tensor:
-        """`Wan.few_step_sample` under the image-to-video condition: one `fg_wan_full_sampler_run` / one hipGraph replay.  New
-        first-frame contents or image tokens at the same shapes replay the same graph (the handle's buffers are rewritten in place)."""
-        text, ff, image = self._unpack(condition)
-        self._no_autograd()
-        self._prepare(noise, "noise", ff, image)
-        return super().few_step_sample(noise, text, t_list, **kwargs)
 
     @torch.no_grad()
     def sample(self, noise: torch.Tensor, condition: Optional[Dict[str, torch.Tensor]] = None,
@@ -197,22 +181,5 @@ class WanI2V(Wan):
         """`WanI2V.sample` (WanI2V/network.py:344-419) over `Wan.sample`'s one call: when guided, the stacked batch [x; x] runs against
         the text, first frame and image tokens of [condition; neg_condition].  Wan2.2 TI2V: frame 0 of the latents is `condition`'s
         after every solver step (the engine restores it), so the returned latents carry it."""
-        text, ff, image = self._unpack(condition)
-        if self.is_ti2v:
-            ff = ff[:, :, :1]  # (only frame 0 is read; the stacked tensor below is a fresh one either way)
-        guided = guidance_scale is not None and neg_condition is not None
-        neg_text = None
-        if guided:
-            neg_text, nff, nimage = self._unpack(neg_condition, "neg_condition")
-            if (image is None) != (nimage is None):
-                raise ValueError("condition and neg_condition must both carry encoder_hidden_states_image, or neither")
-            dev = noise.device
-            ff = torch.cat([ff.to(dev), (nff[:, :, :1] if self.is_ti2v else nff).to(dev)], dim=0)
-            image = None if image is None else torch.cat([image.to(dev), nimage.to(dev)], dim=0)
-        self._prepare(noise, "noise", ff, image, stack=2 if guided else 1)
-        try:
-            return super().sample(noise, condition=text, neg_condition=neg_text, guidance_scale=guidance_scale, num_steps=num_steps, shift=shift,
-                                  skip_layers=skip_layers, skip_layers_start_percent=skip_layers_start_percent, **kwargs)
-        finally:
-            if guided:
-                self._i2v_key = None  # the handle holds the stacked condition: the next call sets its own
+        return super().sample(noise, condition=condition, neg_condition=neg_condition, guidance_scale=guidance_scale, num_steps=num_steps,
+                              shift=shift, skip_layers=skip_layers, skip_layers_start_percent=skip_layers_start_percent, **kwargs)

@@ -43,9 +43,10 @@ class FastGenNetwork(ABC, torch.nn.Module):
         ...
 
 
-def _fused_sample_args(noise: torch.Tensor, t_list, sample_type: str, eps: Optional[torch.Tensor], seed: Optional[int]):
+def _fused_sample_args(noise: torch.Tensor, t_list, sample_type: str, eps: Optional[torch.Tensor], seed: Optional[int],
+                       n_eps: Optional[int] = None):
     """The checks and conversions every `few_step_sample` makes before its library call: noise on the GPU, a known sample_type,
-    t_list ending in 0, `eps` holding steps-1 noise tensors shaped like `noise`, a seed drawn from the host RNG (it follows
+    t_list ending in 0, `eps` holding steps-1 (or `n_eps`) noise tensors shaped like `noise`, a seed drawn from the host RNG (it follows
     torch.manual_seed / set_random_seed) when none is given.  Returns (fp32 contiguous noise, steps, t_list as a ctypes double array,
     eps as fp32 contiguous on noise's device or None, seed)."""
     if noise.device.type != "cuda":
@@ -58,7 +59,7 @@ def _fused_sample_args(noise: torch.Tensor, t_list, sample_type: str, eps: Optio
     n32 = noise if (noise.dtype == torch.float32 and noise.is_contiguous()) else noise.to(torch.float32).contiguous()
     if eps is not None:
         eps = eps.to(device=noise.device, dtype=torch.float32).contiguous()
-        if eps.numel() != max(steps - 1, 0) * n32.numel():
+        if eps.numel() != (max(steps - 1, 0) if n_eps is None else n_eps) * n32.numel():
             raise ValueError(f"eps must hold steps-1 = {steps - 1} noise tensors shaped like `noise`")
     if seed is None:
         seed = int(torch.randint(0, 2**62, (1,)).item())

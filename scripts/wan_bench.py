@@ -157,7 +157,7 @@ if "--bidirectional" in sys.argv and "--i2v" in sys.argv:
                   f"layer ({(med['WanI2V'] / med['Wan'] - 1) * 100:.1f} %); without image tokens {(med['WanI2V, no image tokens'] - med['Wan']) * 1e3:+.2f} ms")
 
             def set_cond():  # a fresh condition every time: embed the image, project it per block
-                i2v._i2v_key = None
+                i2v._slots["i2v"].forget()
                 i2v._prepare(x1, "x_t", ff, img)
             side_by_side(f"{arm}: fg_wan_set_i2v_cond (257 image tokens, {LAYERS} layers)", {"set": set_cond}, 3)
             del plain, i2v
@@ -196,7 +196,7 @@ if "--bidirectional" in sys.argv and "--vace" in sys.argv:
             print(f"   VACEWan / Wan = {med['VACEWan'] / med['Wan']:.3f}")
 
             def set_ctx():  # a fresh context every time: embed it, pad it, proj_in
-                vace._vace_key = None
+                vace._slots["vace"].forget()
                 vace._prepare(x1, "x_t", ctx)
             side_by_side(f"{arm}: fg_wan_set_vace_context (21 context frames)", {"set": set_ctx}, 3)
             del plain, vace
