@@ -10,7 +10,7 @@
 //                             S1[n,g] = sum_{c in g} gamma_c P1,  S2[n,g] = sum_{c in g} gamma_c P2
 //                             dx = a dy - rstd (S1 + xhat S2) / m,                   m = (C / groups) * H * W
 // which is torch's native_group_norm_backward followed by silu_backward, evaluated in fp32.
-#include "common.h"
+#include "token.h"
 #include "misc.h"
 
 namespace {
@@ -80,15 +80,6 @@ __device__ __forceinline__ const T* cat_ptr(const T* x1, int C1, const T* x2, in
 // factors (0 or 1 / (1 - p)) of the 8 consecutive elements starting at flat index e0 (a multiple of 8) of block `blk`'s operand
 // come from Philox4x32-10 keyed by the call's seed with counter (e0 / 4 + {0, 1}, blk), so the backward and the forward-mode pass
 // regenerate exactly the mask the forward used.  p == 0: all ones.
-__device__ __forceinline__ void philox4(uint32_t (&c)[4], uint32_t k0, uint32_t k1) {
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const uint64_t p0 = (uint64_t)0xD2511F53u * c[0], p1 = (uint64_t)0xCD9E8D57u * c[2];
-        const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c[1] ^ k0, n2 = (uint32_t)(p0 >> 32) ^ c[3] ^ k1;
-        c[1] = (uint32_t)p1, c[3] = (uint32_t)p0, c[0] = n0, c[2] = n2;
-        k0 += 0x9E3779B9u, k1 += 0xBB67AE85u;
-    }
-}
 __device__ __forceinline__ void dropout_keep8(const DropArgs& d, uint64_t e0, float (&k)[8]) {
     if (d.p <= 0.f) {
 #pragma unroll
@@ -101,7 +92,7 @@ __device__ __forceinline__ void dropout_keep8(const DropArgs& d, uint64_t e0, fl
     for (int hq = 0; hq < 2; ++hq) {
         const uint64_t q = e0 / 4 + hq;
         uint32_t c[4] = {(uint32_t)q, (uint32_t)(q >> 32), d.block, 0x5eedu};
-        philox4(c, (uint32_t)d.seed, (uint32_t)(d.seed >> 32));
+        philox4x32_10(c, (uint32_t)d.seed, (uint32_t)(d.seed >> 32));
 #pragma unroll
         for (int j = 0; j < 4; ++j) k[4 * hq + j] = c[j] >= thr ? inv : 0.f;
     }

@@ -25,7 +25,7 @@
 // {4-11,16-19,28-31}, ... (MI355X_MICROARCH.md, LDS table), i.e. columns {0-3,12-15} of plane g with columns {4-11} of plane
 // g+1: with a 16-byte pixel pitch inside a plane and planes 3072 B (= 0 mod 256 B) apart, every group covers one 256-byte
 // LDS line exactly, for every tap shift.
-#include "common.h"
+#include "token.h"
 #include "conv.h"
 
 namespace {
@@ -53,12 +53,6 @@ struct WsGeom {
 };
 
 constexpr size_t ws_lds_bytes() { return (size_t)WS_DBYTES + 2 * (size_t)WsGeom<5>::ABUF; }
-
-__device__ __forceinline__ void ws_barrier() {
-    // LDS traffic of this wave retired, then the workgroup barrier.  Deliberately NOT __syncthreads(): its fence would
-    // also drain vmcnt, i.e. the consumers' weight prefetch ring and the producers' stores, at every step.
-    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-}
 
 // TRANSPOSED product (A operand = weights [16 ch x 32 k], B operand = activations [32 k x 16 px]; both operands have the same lane
 // layout, so this is just the argument order): a lane ends with 4 CONSECUTIVE channels of one pixel and the hand-off is 32
@@ -124,7 +118,7 @@ __global__ __launch_bounds__(WS_NTHR) void conv3_ws_kernel(const ConvArgs a, con
 
         const int lane_off = g * G::PLANE + col * WS_PA;
 
-        ws_barrier();  // step 0 is staged
+        lds_barrier();  // step 0 is staged
         int c = 0;
         for (int s = 0; s < S; ++s) {
             const char* abase = abuf0 + (s & 1) * G::ABUF + lane_off;
@@ -179,7 +173,7 @@ __global__ __launch_bounds__(WS_NTHR) void conv3_ws_kernel(const ConvArgs a, con
                     }
             }
             c = cn;
-            ws_barrier();
+            lds_barrier();
         }
         return;
     }
@@ -366,7 +360,7 @@ __global__ __launch_bounds__(WS_NTHR) void conv3_ws_kernel(const ConvArgs a, con
     stage_load(st, t1, c1);
     stage_store(st, abuf0);
     advance(t1, c1);
-    ws_barrier();
+    lds_barrier();
     for (int s = 0; s < S; ++s) {
         const bool more = s + 1 < S && !(ABL & 1);
         const bool retiring = !(ABL & 2) && c < WS_NQ && s >= nchunk;
@@ -379,7 +373,7 @@ __global__ __launch_bounds__(WS_NTHR) void conv3_ws_kernel(const ConvArgs a, con
         }
         advance(t_cur, c);
         advance(t1, c1);
-        ws_barrier();
+        lds_barrier();
     }
     if (!(ABL & 2)) {
         const int t_last = wg + (my_tiles - 1) * gstride;

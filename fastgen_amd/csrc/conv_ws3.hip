@@ -31,7 +31,7 @@
 // tile's last step s, the producers retire that half during step s+1, group B dumps at the end of s+2, retired during s+3, and
 // A's next dump comes at s + (steps per tile >= 4).  Every hand-off and every halo buffer changes hands across the ONE
 // s_barrier that ends each step; no flags, no atomics.  Cost of the skew: two idle steps per launch and group.
-#include "common.h"
+#include "token.h"
 #include "conv.h"
 
 namespace {
@@ -61,11 +61,6 @@ struct X3Geom {
     static constexpr int RS = HW_ * X3_PA;        // 288 (8x8: 304)
     static_assert(HALO_PIX * X3_PA <= X3_PLANE && HALO_PIX <= 192, "one halo plane; three producer passes of 64 pixels");
 };
-
-__device__ __forceinline__ void x3_barrier() {
-    // this wave's LDS traffic retired, then the workgroup barrier; vmcnt is NOT drained (weight ring, stores stay in flight)
-    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-}
 
 struct X3Frag {
     bf16x8 hi, lo;
@@ -142,7 +137,7 @@ __global__ __launch_bounds__(X3_NTHR) void conv3_x3ws_kernel(const ConvArgs a, c
         const int dl0 = col * 512 + ((8 * wl + ((g4) ^ (col & 7))) << 4);
         const int dl1 = col * 512 + ((8 * wl + ((4 + g4) ^ (col & 7))) << 4);
 
-        x3_barrier();  // step 0 is staged
+        lds_barrier();  // step 0 is staged
         int c = 0;
         for (int s = 0; s < NSTEP; ++s) {
             const int ls = s - 2 * grp;  // this group's step
@@ -263,7 +258,7 @@ __global__ __launch_bounds__(X3_NTHR) void conv3_x3ws_kernel(const ConvArgs a, c
                 c = cn;
                 tcur = tnext;
             }
-            x3_barrier();
+            lds_barrier();
         }
         return;
     }
@@ -472,7 +467,7 @@ __global__ __launch_bounds__(X3_NTHR) void conv3_x3ws_kernel(const ConvArgs a, c
     stage_load(st, t1, c1);
     stage_store(st, ring);
     advance(t1, c1);
-    x3_barrier();
+    lds_barrier();
     int sa = 0;  // s % nchunk, tracked incrementally
     for (int s = 0; s < NSTEP; ++s) {
         const bool more = s + 1 < S;
@@ -486,7 +481,7 @@ __global__ __launch_bounds__(X3_NTHR) void conv3_x3ws_kernel(const ConvArgs a, c
             advance(t1, c1);
         }
         if (++sa == nchunk) sa = 0;
-        x3_barrier();
+        lds_barrier();
     }
 }
 

@@ -11,27 +11,10 @@
 // its storage type DT<T>::ST.
 #include <type_traits>
 
-#include "common.h"
+#include "token.h"
 #include "misc.h"
 
 namespace {
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-__device__ __forceinline__ f32x2 ld2(const float* p) { return *reinterpret_cast<const f32x2*>(p); }
-__device__ __forceinline__ f32x2 ld2(const __bf16* p) {
-    typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
-    const bf16x2 q = *reinterpret_cast<const bf16x2*>(p);
-    return f32x2{(float)q[0], (float)q[1]};
-}
-__device__ __forceinline__ void st2(float* p, f32x2 v) { *reinterpret_cast<f32x2*>(p) = v; }
-__device__ __forceinline__ void st2(__bf16* p, f32x2 v) {
-    typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
-    *reinterpret_cast<bf16x2*>(p) = bf16x2{(__bf16)v[0], (__bf16)v[1]};
-}
 
 // One wave per token: lane l holds the channel pairs 2l + 128j.  LayerNorm statistics in two passes over the registers (fp32).
 template <typename ST, int D>
@@ -40,7 +23,7 @@ __device__ __forceinline__ void ln_token(const ST* __restrict__ xrow, int lane, 
     float s = 0.f;
 #pragma unroll
     for (int j = 0; j < NP; ++j) {
-        const f32x2 q = ld2(xrow + 2 * lane + 128 * j);
+        const f32x2 q = load2(xrow + 2 * lane + 128 * j);
         v[2 * j] = q[0], v[2 * j + 1] = q[1];
         s += q[0] + q[1];
     }
@@ -55,14 +38,6 @@ __device__ __forceinline__ void ln_token(const ST* __restrict__ xrow, int lane, 
 #pragma unroll
     for (int e = 0; e < D / 64; ++e) v[e] *= rstd;
 }
-
-__device__ __forceinline__ f32x4 ld4(const float* p) { return *reinterpret_cast<const f32x4*>(p); }
-__device__ __forceinline__ f32x4 ld4(const __bf16* p) {
-    const bf16x4 q = *reinterpret_cast<const bf16x4*>(p);
-    return f32x4{(float)q[0], (float)q[1], (float)q[2], (float)q[3]};
-}
-__device__ __forceinline__ void st4(float* p, f32x4 v) { *reinterpret_cast<f32x4*>(p) = v; }
-__device__ __forceinline__ void st4(__bf16* p, f32x4 v) { *reinterpret_cast<bf16x4*>(p) = bf16x4{(__bf16)v[0], (__bf16)v[1], (__bf16)v[2], (__bf16)v[3]}; }
 
 // y[tok][c] = LN(x[tok])[c] * (1 + scale[n][c]) + shift[n][c];  mod [B][mod_stride] holds shift at shift_off, scale at scale_off.
 // One wave walks FOUR consecutive tokens; lane l holds the channel quads 4 l + 256 j.  The kernel is bound by the NUMBER of its
@@ -94,8 +69,8 @@ __global__ __launch_bounds__(256) void ln_modulate_kernel(const ST* __restrict__
 #pragma unroll
             for (int j = 0; j < NJ; ++j)
                 if (has(j)) {
-                    sc[j] = ld4(mrow + scale_off + 4 * lane + 256 * j) + 1.0f;
-                    sh[j] = ld4(mrow + shift_off + 4 * lane + 256 * j);
+                    sc[j] = load4(mrow + scale_off + 4 * lane + 256 * j) + 1.0f;
+                    sh[j] = load4(mrow + shift_off + 4 * lane + 256 * j);
                 }
             n_have = n;
         }
@@ -105,7 +80,7 @@ __global__ __launch_bounds__(256) void ln_modulate_kernel(const ST* __restrict__
 #pragma unroll
         for (int j = 0; j < NJ; ++j) {
             v[j] = f32x4{0.f, 0.f, 0.f, 0.f};
-            if (has(j)) v[j] = ld4(xrow + 4 * lane + 256 * j);
+            if (has(j)) v[j] = load4(xrow + 4 * lane + 256 * j);
             s += (v[j][0] + v[j][1]) + (v[j][2] + v[j][3]);
         }
         const float mean = wave_sum(s) * (1.0f / D);
@@ -128,7 +103,7 @@ __global__ __launch_bounds__(256) void ln_modulate_kernel(const ST* __restrict__
                         amax = fmaxf(amax, fabsf(v[j][e]));
                     }
                 }
-            amax = fp8_wave_max(amax);
+            amax = wave_max(amax);
             const float inv = fp8_row_inv(amax);
             if (lane == 0) y_scale[tok] = fp8_row_scale(amax);
             unsigned* yrow = reinterpret_cast<unsigned*>(reinterpret_cast<unsigned char*>(y) + (size_t)tok * D);
@@ -143,7 +118,7 @@ __global__ __launch_bounds__(256) void ln_modulate_kernel(const ST* __restrict__
                     f32x4 o;
 #pragma unroll
                     for (int e = 0; e < 4; ++e) o[e] = fmaf(v[j][e] * rstd, sc[j][e], sh[j][e]);
-                    st4(yrow + 4 * lane + 256 * j, o);
+                    store4(yrow + 4 * lane + 256 * j, o);
                 }
         }
     }
@@ -153,7 +128,6 @@ __global__ __launch_bounds__(256) void ln_modulate_kernel(const ST* __restrict__
 template <int D>
 __global__ __launch_bounds__(256) void ln_modulate_split_kernel(const float* __restrict__ x, const float* __restrict__ mod, int mod_stride,
                                                                 int shift_off, int scale_off, __bf16* __restrict__ y, int ntok, int tpi) {
-    typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
     const int lane = threadIdx.x & 63;
     const int tok = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (tok >= ntok) return;
@@ -164,7 +138,7 @@ __global__ __launch_bounds__(256) void ln_modulate_split_kernel(const float* __r
 #pragma unroll
     for (int j = 0; j < D / 128; ++j) {
         const int c = 2 * lane + 128 * j;
-        const f32x2 sc = ld2(mrow + scale_off + c), sh = ld2(mrow + shift_off + c);
+        const f32x2 sc = load2(mrow + scale_off + c), sh = load2(mrow + shift_off + c);
         const float a = fmaf(v[2 * j], 1.0f + sc[0], sh[0]), b = fmaf(v[2 * j + 1], 1.0f + sc[1], sh[1]);
         const bf16x2 hi = {(__bf16)a, (__bf16)b};
         const bf16x2 lo = {(__bf16)(a - (float)hi[0]), (__bf16)(b - (float)hi[1])};
@@ -188,7 +162,7 @@ __global__ __launch_bounds__(256) void final_kernel(const ST* __restrict__ x, co
 #pragma unroll
     for (int j = 0; j < D / 128; ++j) {
         const int c = 2 * lane + 128 * j;
-        const f32x2 sh = ld2(mrow + c), sc = ld2(mrow + D + c);
+        const f32x2 sh = load2(mrow + c), sc = load2(mrow + D + c);
         v[2 * j] = fmaf(v[2 * j], 1.0f + sc[0], sh[0]);
         v[2 * j + 1] = fmaf(v[2 * j + 1], 1.0f + sc[1], sh[1]);
     }
@@ -198,7 +172,7 @@ __global__ __launch_bounds__(256) void final_kernel(const ST* __restrict__ x, co
         float a = 0.f;
 #pragma unroll
         for (int j = 0; j < D / 128; ++j) {
-            const f32x2 q = ld2(w + (size_t)o * D + 2 * lane + 128 * j);
+            const f32x2 q = load2(w + (size_t)o * D + 2 * lane + 128 * j);
             a = fmaf(v[2 * j], q[0], a);
             a = fmaf(v[2 * j + 1], q[1], a);
         }
@@ -662,31 +636,15 @@ template <typename ST>
 int ln_mod_d(int D, const void* x, const float* mod, int ms, int so, int co, void* y, int ntok, int tpi, hipStream_t s) {
     if ((ms % 4) || (so % 4) || (co % 4)) return (int)hipErrorInvalidValue;  // (16-byte loads of the modulation vectors)
     dim3 g((ntok + 15) / 16), b(256);  // 4 waves x 4 tokens
-    switch (D) {
-        case 384: hipLaunchKernelGGL((ln_modulate_kernel<ST, 384>), g, b, 0, s, (const ST*)x, mod, ms, so, co, (ST*)y, ntok, tpi); break;
-        case 768: hipLaunchKernelGGL((ln_modulate_kernel<ST, 768>), g, b, 0, s, (const ST*)x, mod, ms, so, co, (ST*)y, ntok, tpi); break;
-        case 1024: hipLaunchKernelGGL((ln_modulate_kernel<ST, 1024>), g, b, 0, s, (const ST*)x, mod, ms, so, co, (ST*)y, ntok, tpi); break;
-        case 1152: hipLaunchKernelGGL((ln_modulate_kernel<ST, 1152>), g, b, 0, s, (const ST*)x, mod, ms, so, co, (ST*)y, ntok, tpi); break;
-        // the causal video DiT's widths (engine_wan.inc)
-        case 256: hipLaunchKernelGGL((ln_modulate_kernel<ST, 256>), g, b, 0, s, (const ST*)x, mod, ms, so, co, (ST*)y, ntok, tpi); break;
-        case 1536: hipLaunchKernelGGL((ln_modulate_kernel<ST, 1536>), g, b, 0, s, (const ST*)x, mod, ms, so, co, (ST*)y, ntok, tpi); break;
-        case 2048: hipLaunchKernelGGL((ln_modulate_kernel<ST, 2048>), g, b, 0, s, (const ST*)x, mod, ms, so, co, (ST*)y, ntok, tpi); break;
-        case 3072: hipLaunchKernelGGL((ln_modulate_kernel<ST, 3072>), g, b, 0, s, (const ST*)x, mod, ms, so, co, (ST*)y, ntok, tpi); break;
-        case 5120: hipLaunchKernelGGL((ln_modulate_kernel<ST, 5120>), g, b, 0, s, (const ST*)x, mod, ms, so, co, (ST*)y, ntok, tpi); break;
-        default: return (int)hipErrorInvalidValue;
-    }
+    const auto go = [&](auto d) { hipLaunchKernelGGL((ln_modulate_kernel<ST, decltype(d)::value>), g, b, 0, s, (const ST*)x, mod, ms, so, co, (ST*)y, ntok, tpi); };
+    if (!fg_dit_width_call(D, go) && !fg_wan_width_call(D, go)) return (int)hipErrorInvalidValue;  // (the video DiT runs this kernel too: engine_wan.inc)
     DIT_RET();
 }
 template <typename ST>
 int final_d(int D, const void* x, const float* mod, const float* w, const float* bias, float* out, int ntok, int grid, int p, int C, hipStream_t s) {
     dim3 g((ntok + 3) / 4), b(256);
-    switch (D) {
-        case 384: hipLaunchKernelGGL((final_kernel<ST, 384>), g, b, 0, s, (const ST*)x, mod, w, bias, out, ntok, grid, p, C); break;
-        case 768: hipLaunchKernelGGL((final_kernel<ST, 768>), g, b, 0, s, (const ST*)x, mod, w, bias, out, ntok, grid, p, C); break;
-        case 1024: hipLaunchKernelGGL((final_kernel<ST, 1024>), g, b, 0, s, (const ST*)x, mod, w, bias, out, ntok, grid, p, C); break;
-        case 1152: hipLaunchKernelGGL((final_kernel<ST, 1152>), g, b, 0, s, (const ST*)x, mod, w, bias, out, ntok, grid, p, C); break;
-        default: return (int)hipErrorInvalidValue;
-    }
+    if (!fg_dit_width_call(D, [&](auto d) { hipLaunchKernelGGL((final_kernel<ST, decltype(d)::value>), g, b, 0, s, (const ST*)x, mod, w, bias, out, ntok, grid, p, C); }))
+        return (int)hipErrorInvalidValue;
     DIT_RET();
 }
 
@@ -695,36 +653,21 @@ int final_d(int D, const void* x, const float* mod, const float* w, const float*
 int launch_dit_ln_modulate_split(int D, const float* x, const float* mod, int mod_stride, int shift_off, int scale_off, void* y, int ntok,
                                  int tokens_per_image, hipStream_t s) {
     dim3 g((ntok + 3) / 4), b(256);
-#define LNS(DD) hipLaunchKernelGGL((ln_modulate_split_kernel<DD>), g, b, 0, s, x, mod, mod_stride, shift_off, scale_off, (__bf16*)y, ntok, tokens_per_image)
-    switch (D) {
-        case 384: LNS(384); break;
-        case 768: LNS(768); break;
-        case 1024: LNS(1024); break;
-        case 1152: LNS(1152); break;
-        default: return (int)hipErrorInvalidValue;
-    }
-#undef LNS
+    if (!fg_dit_width_call(D, [&](auto d) {
+            hipLaunchKernelGGL((ln_modulate_split_kernel<decltype(d)::value>), g, b, 0, s, x, mod, mod_stride, shift_off, scale_off, (__bf16*)y, ntok, tokens_per_image);
+        }))
+        return (int)hipErrorInvalidValue;
     DIT_RET();
 }
 int launch_dit_ln_modulate_fp8(int D, const void* x, const float* mod, int mod_stride, int shift_off, int scale_off, void* y, float* y_scale,
                                int ntok, int tokens_per_image, hipStream_t s) {
     if ((mod_stride % 4) || (shift_off % 4) || (scale_off % 4)) return (int)hipErrorInvalidValue;  // (16-byte loads of the modulation vectors)
     dim3 g((ntok + 15) / 16), b(256);  // 4 waves x 4 tokens
-#define LN8(DD) hipLaunchKernelGGL((ln_modulate_kernel<__bf16, DD, true>), g, b, 0, s, (const __bf16*)x, mod, mod_stride, shift_off, scale_off, (__bf16*)y, ntok, tokens_per_image, y_scale)
-    switch (D) {
-        case 384: LN8(384); break;
-        case 768: LN8(768); break;
-        case 1024: LN8(1024); break;
-        case 1152: LN8(1152); break;
-        // the causal video DiT's widths (engine_wan.inc)
-        case 256: LN8(256); break;
-        case 1536: LN8(1536); break;
-        case 2048: LN8(2048); break;
-        case 3072: LN8(3072); break;
-        case 5120: LN8(5120); break;
-        default: return (int)hipErrorInvalidValue;
-    }
-#undef LN8
+    const auto go = [&](auto d) {
+        hipLaunchKernelGGL((ln_modulate_kernel<__bf16, decltype(d)::value, true>), g, b, 0, s, (const __bf16*)x, mod, mod_stride, shift_off, scale_off, (__bf16*)y,
+                           ntok, tokens_per_image, y_scale);
+    };
+    if (!fg_dit_width_call(D, go) && !fg_wan_width_call(D, go)) return (int)hipErrorInvalidValue;  // (the video DiT's fp8 mode too: engine_wan.inc)
     DIT_RET();
 }
 // dtype: storage of the token tensors (1 bf16, 0 fp32)

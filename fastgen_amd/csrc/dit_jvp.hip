@@ -10,18 +10,10 @@
 //   gelu_jvp_kernel          a = gelu_tanh(h), ad = gelu_tanh'(h) hd as planes                                  (:176)
 //   gate_update_kernel       x' = x + g h;  xd' += gd h   (xd' arrives as xd + g (W od) from the GEMM's gate + residual epilogue)
 //   final_jvp_kernel         OutputProjection + unpatchify of both streams                                        (:218-225, 437-455)
-#include "common.h"
+#include "token.h"
 #include "misc.h"
 
 namespace {
-
-__device__ __forceinline__ float jv_wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-__device__ __forceinline__ f32x2 jv_ld2(const float* p) { return *reinterpret_cast<const f32x2*>(p); }
-typedef __attribute__((ext_vector_type(2))) __bf16 jv_bf16x2;
 
 __global__ void fourier_jvp_kernel(const float* __restrict__ t, const float* __restrict__ td, float* __restrict__ f, float* __restrict__ fd,
                                    int B, int dim) {
@@ -64,32 +56,32 @@ __global__ __launch_bounds__(256) void ln_modulate_jvp_kernel(const float* __res
     float s = 0.f, sd = 0.f;
 #pragma unroll
     for (int j = 0; j < NE / 2; ++j) {
-        const f32x2 q = jv_ld2(xrow + 2 * lane + 128 * j), p = jv_ld2(drow + 2 * lane + 128 * j);
+        const f32x2 q = load2(xrow + 2 * lane + 128 * j), p = load2(drow + 2 * lane + 128 * j);
         v[2 * j] = q[0], v[2 * j + 1] = q[1], d[2 * j] = p[0], d[2 * j + 1] = p[1];
         s += q[0] + q[1];
         sd += p[0] + p[1];
     }
-    const float mean = jv_wave_sum(s) * (1.0f / D), dmean = jv_wave_sum(sd) * (1.0f / D);
+    const float mean = wave_sum(s) * (1.0f / D), dmean = wave_sum(sd) * (1.0f / D);
     float ss = 0.f;
 #pragma unroll
     for (int e = 0; e < NE; ++e) {
         v[e] -= mean;
         ss = fmaf(v[e], v[e], ss);
     }
-    const float rstd = 1.0f / sqrtf(jv_wave_sum(ss) * (1.0f / D) + 1e-6f);
+    const float rstd = 1.0f / sqrtf(wave_sum(ss) * (1.0f / D) + 1e-6f);
     float nd = 0.f;
 #pragma unroll
     for (int e = 0; e < NE; ++e) {
         v[e] *= rstd;
         nd = fmaf(v[e], d[e], nd);
     }
-    const float m2 = jv_wave_sum(nd) * (1.0f / D);
+    const float m2 = wave_sum(nd) * (1.0f / D);
     const float *mrow = mod + (size_t)n * mod_stride, *mdrow = modd + (size_t)n * mod_stride;
 #pragma unroll
     for (int j = 0; j < NE / 2; ++j) {
         const int c = 2 * lane + 128 * j;
-        const f32x2 sc = jv_ld2(mrow + scale_off + c), sh = jv_ld2(mrow + shift_off + c);
-        const f32x2 scd = jv_ld2(mdrow + scale_off + c), shd = jv_ld2(mdrow + shift_off + c);
+        const f32x2 sc = load2(mrow + scale_off + c), sh = load2(mrow + shift_off + c);
+        const f32x2 scd = load2(mdrow + scale_off + c), shd = load2(mdrow + shift_off + c);
         float o[2], od[2];
 #pragma unroll
         for (int e = 0; e < 2; ++e) {
@@ -97,13 +89,13 @@ __global__ __launch_bounds__(256) void ln_modulate_jvp_kernel(const float* __res
             o[e] = fmaf(nn, 1.0f + sc[e], sh[e]);
             od[e] = fmaf(ndv, 1.0f + sc[e], fmaf(nn, scd[e], shd[e]));
         }
-        const jv_bf16x2 hi = {(__bf16)o[0], (__bf16)o[1]}, hid = {(__bf16)od[0], (__bf16)od[1]};
-        const jv_bf16x2 lo = {(__bf16)(o[0] - (float)hi[0]), (__bf16)(o[1] - (float)hi[1])};
-        const jv_bf16x2 lod = {(__bf16)(od[0] - (float)hid[0]), (__bf16)(od[1] - (float)hid[1])};
-        *reinterpret_cast<jv_bf16x2*>(y + (size_t)tok * 2 * D + c) = hi;
-        *reinterpret_cast<jv_bf16x2*>(y + (size_t)tok * 2 * D + D + c) = lo;
-        *reinterpret_cast<jv_bf16x2*>(yd + (size_t)tok * 2 * D + c) = hid;
-        *reinterpret_cast<jv_bf16x2*>(yd + (size_t)tok * 2 * D + D + c) = lod;
+        const bf16x2 hi = {(__bf16)o[0], (__bf16)o[1]}, hid = {(__bf16)od[0], (__bf16)od[1]};
+        const bf16x2 lo = {(__bf16)(o[0] - (float)hi[0]), (__bf16)(o[1] - (float)hi[1])};
+        const bf16x2 lod = {(__bf16)(od[0] - (float)hid[0]), (__bf16)(od[1] - (float)hid[1])};
+        *reinterpret_cast<bf16x2*>(y + (size_t)tok * 2 * D + c) = hi;
+        *reinterpret_cast<bf16x2*>(y + (size_t)tok * 2 * D + D + c) = lo;
+        *reinterpret_cast<bf16x2*>(yd + (size_t)tok * 2 * D + c) = hid;
+        *reinterpret_cast<bf16x2*>(yd + (size_t)tok * 2 * D + D + c) = lod;
     }
 }
 
@@ -275,7 +267,7 @@ __global__ __launch_bounds__(256, 1) void dit_attention_jvp_kernel(const __bf16*
         }
 }
 
-// a = gelu_tanh(h) = h sig(2 u), u = sqrt(2/pi) (h + 0.044715 h^3);  ad = (sig + h sig (1 - sig) 2 u') hd,  u' = sqrt(2/pi) (1 + 3 * 0.044715 h^2)
+// a = gelu_tanh(h), ad = gelu_tanh'(h) hd (token.h's gelu_tanh_jvp)
 // h, hd fp32 [M][K]; a, ad [hi | lo] planes [M][2 K]; one thread = 4 columns of a row
 __global__ __launch_bounds__(256) void gelu_jvp_kernel(const float* __restrict__ h, const float* __restrict__ hd, __bf16* __restrict__ a,
                                                        __bf16* __restrict__ ad, int64_t M, int K) {
@@ -288,12 +280,8 @@ __global__ __launch_bounds__(256) void gelu_jvp_kernel(const float* __restrict__
     bf16x4 hi, lo, hid, lod;
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
-        constexpr float c0 = 0.7978845608028654f, c1 = 0.044715f;
-        const float v = x[e], v2 = v * v;
-        const float u2 = 2.0f * c0 * v * fmaf(c1, v2, 1.0f);
-        const float sig = 1.0f / (1.0f + expf(-u2));
-        const float g = v * sig;
-        const float gd = (sig + g * (1.0f - sig) * (2.0f * c0 * fmaf(3.0f * c1, v2, 1.0f))) * xd[e];
+        float g;
+        const float gd = gelu_tanh_jvp(x[e], g) * xd[e];
         hi[e] = (__bf16)g, lo[e] = (__bf16)(g - (float)hi[e]);
         hid[e] = (__bf16)gd, lod[e] = (__bf16)(gd - (float)hid[e]);
     }
@@ -340,31 +328,31 @@ __global__ __launch_bounds__(256) void final_jvp_kernel(const float* __restrict_
     float s = 0.f, sd = 0.f;
 #pragma unroll
     for (int j = 0; j < NE / 2; ++j) {
-        const f32x2 q = jv_ld2(xrow + 2 * lane + 128 * j), pp = jv_ld2(drow + 2 * lane + 128 * j);
+        const f32x2 q = load2(xrow + 2 * lane + 128 * j), pp = load2(drow + 2 * lane + 128 * j);
         v[2 * j] = q[0], v[2 * j + 1] = q[1], d[2 * j] = pp[0], d[2 * j + 1] = pp[1];
         s += q[0] + q[1];
         sd += pp[0] + pp[1];
     }
-    const float mean = jv_wave_sum(s) * (1.0f / D), dmean = jv_wave_sum(sd) * (1.0f / D);
+    const float mean = wave_sum(s) * (1.0f / D), dmean = wave_sum(sd) * (1.0f / D);
     float ss = 0.f;
 #pragma unroll
     for (int e = 0; e < NE; ++e) {
         v[e] -= mean;
         ss = fmaf(v[e], v[e], ss);
     }
-    const float rstd = 1.0f / sqrtf(jv_wave_sum(ss) * (1.0f / D) + 1e-6f);
+    const float rstd = 1.0f / sqrtf(wave_sum(ss) * (1.0f / D) + 1e-6f);
     float nd = 0.f;
 #pragma unroll
     for (int e = 0; e < NE; ++e) {
         v[e] *= rstd;
         nd = fmaf(v[e], d[e], nd);
     }
-    const float m2 = jv_wave_sum(nd) * (1.0f / D);
+    const float m2 = wave_sum(nd) * (1.0f / D);
     const float *mrow = mod + (size_t)n * 2 * D, *mdrow = modd + (size_t)n * 2 * D;
 #pragma unroll
     for (int j = 0; j < NE / 2; ++j) {
         const int c = 2 * lane + 128 * j;
-        const f32x2 sh = jv_ld2(mrow + c), sc = jv_ld2(mrow + D + c), shd = jv_ld2(mdrow + c), scd = jv_ld2(mdrow + D + c);
+        const f32x2 sh = load2(mrow + c), sc = load2(mrow + D + c), shd = load2(mdrow + c), scd = load2(mdrow + D + c);
 #pragma unroll
         for (int e = 0; e < 2; ++e) {
             const float nn = v[2 * j + e], ndv = (d[2 * j + e] - dmean - nn * m2) * rstd;
@@ -378,12 +366,12 @@ __global__ __launch_bounds__(256) void final_jvp_kernel(const float* __restrict_
         float a = 0.f, ad = 0.f;
 #pragma unroll
         for (int j = 0; j < NE / 2; ++j) {
-            const f32x2 q = jv_ld2(w + (size_t)o * D + 2 * lane + 128 * j);
+            const f32x2 q = load2(w + (size_t)o * D + 2 * lane + 128 * j);
             a = fmaf(v[2 * j], q[0], a), a = fmaf(v[2 * j + 1], q[1], a);
             ad = fmaf(d[2 * j], q[0], ad), ad = fmaf(d[2 * j + 1], q[1], ad);
         }
-        a = jv_wave_sum(a);
-        ad = jv_wave_sum(ad);
+        a = wave_sum(a);
+        ad = wave_sum(ad);
         if (lane == 0) {
             const int c = o % C, pq = o / C, py = pq / p, px = pq - py * p;
             const size_t at = (((size_t)n * C + c) * res + gy * p + py) * res + gx * p + px;
@@ -409,15 +397,11 @@ int launch_dit_ln_modulate_jvp(int D, const float* x, const float* xd, const flo
                                int scale_off, void* y, void* yd, int ntok, int tokens_per_image, hipStream_t s) {
     if (ntok <= 0 || tokens_per_image <= 0 || (mod_stride % 2) || (shift_off % 2) || (scale_off % 2)) return (int)hipErrorInvalidValue;  // (8-byte loads)
     dim3 g((ntok + 3) / 4), b(256);
-#define LNJ(DD) hipLaunchKernelGGL((ln_modulate_jvp_kernel<DD>), g, b, 0, s, x, xd, mod, modd, mod_stride, shift_off, scale_off, (__bf16*)y, (__bf16*)yd, ntok, tokens_per_image)
-    switch (D) {
-        case 384: LNJ(384); break;
-        case 768: LNJ(768); break;
-        case 1024: LNJ(1024); break;
-        case 1152: LNJ(1152); break;
-        default: return (int)hipErrorInvalidValue;
-    }
-#undef LNJ
+    if (!fg_dit_width_call(D, [&](auto d) {
+            hipLaunchKernelGGL((ln_modulate_jvp_kernel<decltype(d)::value>), g, b, 0, s, x, xd, mod, modd, mod_stride, shift_off, scale_off, (__bf16*)y,
+                               (__bf16*)yd, ntok, tokens_per_image);
+        }))
+        return (int)hipErrorInvalidValue;
     JVP_RET();
 }
 int launch_dit_attention_jvp(const void* q, const void* k, const void* vt, const void* qd, const void* kd, const void* vtd, float* out, float* outd,
@@ -448,14 +432,9 @@ int launch_dit_gate_update(const float* h, const float* g, const float* gd, int 
 int launch_dit_final_jvp(int D, const float* x, const float* xd, const float* mod, const float* modd, const float* w, const float* bias, float* out,
                          float* outd, int ntok, int grid, int p, int C, hipStream_t s) {
     dim3 g((ntok + 3) / 4), b(256);
-#define FNJ(DD) hipLaunchKernelGGL((final_jvp_kernel<DD>), g, b, 0, s, x, xd, mod, modd, w, bias, out, outd, ntok, grid, p, C)
-    switch (D) {
-        case 384: FNJ(384); break;
-        case 768: FNJ(768); break;
-        case 1024: FNJ(1024); break;
-        case 1152: FNJ(1152); break;
-        default: return (int)hipErrorInvalidValue;
-    }
-#undef FNJ
+    if (!fg_dit_width_call(D, [&](auto d) {
+            hipLaunchKernelGGL((final_jvp_kernel<decltype(d)::value>), g, b, 0, s, x, xd, mod, modd, w, bias, out, outd, ntok, grid, p, C);
+        }))
+        return (int)hipErrorInvalidValue;
     JVP_RET();
 }

@@ -1747,8 +1747,8 @@ int fg_op_wan_final(const void* tokens, const float* mod, const float* w, const 
     if ((int64_t)batch * frames * gh * gw > INT32_MAX / 2) return fail(FG_EINVAL, "fg_op_wan_final: too many tokens");
     const bool tiled = channels == 48 && (d % 32) == 0 && path != 1;
     if (path == 2 && !tiled) return fail(FG_EINVAL, "fg_op_wan_final: the tiled kernel serves 48 channels and d %% 32 == 0, got %d, %d", channels, d);
-    if (!tiled && d != 256 && d != 384 && d != 1536 && d != 2048 && d != 3072 && d != 5120)
-        return fail(FG_EINVAL, "fg_op_wan_final: d %d unsupported by the wave-per-token head (256, 384, 1536, 2048, 3072, 5120)", d);
+    if (!tiled && !fg_wan_width_ok(d))
+        return fail(FG_EINVAL, "fg_op_wan_final: d %d unsupported by the wave-per-token head (one of" FG_WAN_WIDTHS_STR ")", d);
     if (tiled && d <= 0) return fail(FG_EINVAL, "fg_op_wan_final: bad d");
     HIP_TRY(launch_wan_ti2v_final(d, tokens, mod, w, bias, first_frame, out, batch * frames * gh * gw, frames, gh, gw, channels, eps, path,
                                   (hipStream_t)stream));
@@ -1895,8 +1895,8 @@ int fg_op_gemm_fp8(const void* a, const void* w, const float* bias, void* out, i
 int fg_op_dit_ln_modulate_fp8(const void* x, const float* mod, int mod_stride, int shift_off, int scale_off, void* y, float* y_scale, int ntok,
                               int d, int tokens_per_image, void* stream) {
     if (!x || !mod || !y || !y_scale || ntok <= 0 || tokens_per_image <= 0) return fail(FG_EINVAL, "fg_op_dit_ln_modulate_fp8: bad argument");
-    if (d != 384 && d != 768 && d != 1024 && d != 1152 && d != 256 && d != 1536 && d != 2048 && d != 5120)
-        return fail(FG_EINVAL, "fg_op_dit_ln_modulate_fp8: d %d unsupported (384, 768, 1024, 1152; the video DiT's 256, 1536, 2048, 5120)", d);
+    if (!fg_dit_width_ok(d) && !fg_wan_width_ok(d))
+        return fail(FG_EINVAL, "fg_op_dit_ln_modulate_fp8: d %d unsupported (one of" FG_DIT_WIDTHS_STR "; the video DiT's" FG_WAN_WIDTHS_STR ")", d);
     if ((mod_stride % 4) || (shift_off % 4) || (scale_off % 4) || shift_off < 0 || scale_off < 0)
         return fail(FG_EINVAL, "fg_op_dit_ln_modulate_fp8: mod_stride / shift_off / scale_off must be multiples of 4");
     HIP_TRY(launch_dit_ln_modulate_fp8(d, x, mod, mod_stride, shift_off, scale_off, y, y_scale, ntok, tokens_per_image, (hipStream_t)stream));

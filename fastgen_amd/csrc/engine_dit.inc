@@ -447,7 +447,7 @@ int fg_dit_create(const fg_dit_config* cfg, fg_dit** out) {
         if (e && e[0] == '0') return fail(FG_EINVAL, "the fp8 mode runs on the token GEMM: FASTGEN_AMD_DIT_GEMM=0 excludes it");
     }
     const int D = cfg->hidden_size;
-    if (D != 384 && D != 768 && D != 1024 && D != 1152) return fail(FG_EINVAL, "hidden_size %d unsupported (384, 768, 1024, 1152)", D);
+    if (!fg_dit_width_ok(D)) return fail(FG_EINVAL, "hidden_size %d unsupported (one of" FG_DIT_WIDTHS_STR ")", D);
     if (cfg->num_heads <= 0 || D % cfg->num_heads) return fail(FG_EINVAL, "hidden_size must be a multiple of num_heads");
     const int hd = D / cfg->num_heads;
     if (hd != 64 && hd != 72) return fail(FG_EINVAL, "head dim %d unsupported (64, 72)", hd);
@@ -621,7 +621,7 @@ int fg_op_dit_ln_modulate_jvp(const float* x, const float* xd, const float* mod,
     if ((((uintptr_t)x) | ((uintptr_t)xd) | ((uintptr_t)mod) | ((uintptr_t)modd) | ((uintptr_t)y) | ((uintptr_t)yd)) & 15)
         return fail(FG_EINVAL, "fg_op_dit_ln_modulate_jvp: tensors must be 16-byte aligned");
     if (ntok <= 0 || tokens_per_image <= 0) return fail(FG_EINVAL, "fg_op_dit_ln_modulate_jvp: ntok %d and tokens_per_image %d must be positive", ntok, tokens_per_image);
-    if (d != 384 && d != 768 && d != 1024 && d != 1152) return fail(FG_EINVAL, "fg_op_dit_ln_modulate_jvp: d %d unsupported (384, 768, 1024, 1152)", d);
+    if (!fg_dit_width_ok(d)) return fail(FG_EINVAL, "fg_op_dit_ln_modulate_jvp: d %d unsupported (one of" FG_DIT_WIDTHS_STR ")", d);
     if (shift_off < 0 || scale_off < 0 || (mod_stride % 2) || (shift_off % 2) || (scale_off % 2) || mod_stride < shift_off + d || mod_stride < scale_off + d)
         return fail(FG_EINVAL, "fg_op_dit_ln_modulate_jvp: mod_stride / shift_off / scale_off must be even, the offsets + d inside the stride");
     if (y == yd || (const void*)x == y || (const void*)xd == y || (const void*)x == yd || (const void*)xd == yd)

@@ -455,8 +455,7 @@ int wan_create(const fg_wan_config* cfg, const WanVariant& var, fg_wan** out) {
         return fail(FG_EINVAL, "r_timestep and time_cond_diff must be 0 or 1");
     if (cfg->head_dim != 128) return fail(FG_EINVAL, "head_dim %d unsupported (128)", cfg->head_dim);
     const int D = cfg->num_heads * cfg->head_dim;
-    if (D != 256 && D != 384 && D != 1536 && D != 2048 && D != 3072 && D != 5120)
-        return fail(FG_EINVAL, "inner dim %d unsupported (256, 384, 1536, 2048, 3072, 5120)", D);
+    if (!fg_wan_width_ok(D)) return fail(FG_EINVAL, "inner dim %d unsupported (one of" FG_WAN_WIDTHS_STR ")", D);
     if (cfg->in_channels <= 0 || cfg->in_channels > 64 || cfg->out_channels <= 0 || cfg->out_channels > 64 || cfg->num_layers <= 0 ||
         (cfg->ffn_dim % 64) || (cfg->text_dim % 64) || cfg->freq_dim != 256 || cfg->rope_max_seq_len <= 0 || cfg->chunk_size <= 0 ||
         cfg->total_num_frames <= 0)

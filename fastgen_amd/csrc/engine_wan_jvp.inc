@@ -219,25 +219,21 @@ int fg_op_wan_attention_jvp(const void* q, const void* qd, int ldq, int64_t q_bs
     return FG_OK;
 }
 
-namespace {
-bool wan_jvp_width_ok(int d) { return d == 256 || d == 384 || d == 1536 || d == 2048 || d == 3072 || d == 5120; }
-}  // namespace
-
 int fg_op_wan_modulate_jvp(const void* x, const void* xd, const float* mod, const float* modd, int mod_stride, int shift_off, int scale_off, void* y,
                            void* yd, int ntok, int d, int tokens_per_row, float eps, void* stream) {
-    if (!x || !xd || !mod || !y || !yd || y == yd || ntok <= 0 || tokens_per_row <= 0 || !wan_jvp_width_ok(d) || mod_stride < 0 || (mod_stride % 2) ||
+    if (!x || !xd || !mod || !y || !yd || y == yd || ntok <= 0 || tokens_per_row <= 0 || !fg_wan_width_ok(d) || mod_stride < 0 || (mod_stride % 2) ||
         shift_off < 0 || (shift_off % 2) || scale_off < 0 || (scale_off % 2))
-        return fail(FG_EINVAL, "fg_op_wan_modulate_jvp: bad argument (null pointer, y == yd, a count <= 0, d not one of 256, 384, 1536, 2048, 3072, "
-                    "5120, an odd or negative stride / offset)");
+        return fail(FG_EINVAL, "fg_op_wan_modulate_jvp: bad argument (null pointer, y == yd, a count <= 0, d not one of" FG_WAN_WIDTHS_STR
+                    ", an odd or negative stride / offset)");
     HIP_TRY(launch_wan_ln_modulate_jvp(d, x, xd, mod, modd, mod_stride, shift_off, scale_off, y, yd, ntok, tokens_per_row, eps, (hipStream_t)stream));
     return FG_OK;
 }
 
 int fg_op_wan_rms_rope_jvp(const void* src, const void* srcd, int ld_src, const float* w, float eps, const float* cs, void* dst, void* dstd, int rows,
                            int l, int d, void* stream) {
-    if (!src || !srcd || !w || !dst || !dstd || dst == dstd || rows <= 0 || l <= 0 || (rows % l) || !wan_jvp_width_ok(d) || ld_src < d || (ld_src % 2))
-        return fail(FG_EINVAL, "fg_op_wan_rms_rope_jvp: bad argument (null pointer, dst == dstd, rows not a multiple of l, d not one of 256, 384, "
-                    "1536, 2048, 3072, 5120, ld_src < d or odd)");
+    if (!src || !srcd || !w || !dst || !dstd || dst == dstd || rows <= 0 || l <= 0 || (rows % l) || !fg_wan_width_ok(d) || ld_src < d || (ld_src % 2))
+        return fail(FG_EINVAL, "fg_op_wan_rms_rope_jvp: bad argument (null pointer, dst == dstd, rows not a multiple of l, d not one of" FG_WAN_WIDTHS_STR
+                    ", ld_src < d or odd)");
     HIP_TRY(launch_wan_rms_rope_jvp(d, src, srcd, ld_src, w, eps, (const float2*)cs, dst, dstd, (int64_t)l * d, d, rows, l, (hipStream_t)stream));
     return FG_OK;
 }
@@ -251,9 +247,9 @@ int fg_op_wan_gelu_jvp(const void* h, const void* hd, void* a, void* ad, int64_t
 int fg_op_wan_final_jvp(const void* tokens, const void* tokens_d, const float* mod, const float* modd, const float* w, const float* bias, float* out,
                         float* outd, int batch, int channels, int frames, int gh, int gw, int d, float eps, void* stream) {
     if (!tokens || !tokens_d || !mod || !modd || !w || !bias || !out || !outd || out == outd || batch <= 0 || channels <= 0 || channels > 64 ||
-        frames <= 0 || gh <= 0 || gw <= 0 || !wan_jvp_width_ok(d))
-        return fail(FG_EINVAL, "fg_op_wan_final_jvp: bad argument (null pointer, out == outd, channels outside [1, 64], a count <= 0, d not one of "
-                    "256, 384, 1536, 2048, 3072, 5120)");
+        frames <= 0 || gh <= 0 || gw <= 0 || !fg_wan_width_ok(d))
+        return fail(FG_EINVAL, "fg_op_wan_final_jvp: bad argument (null pointer, out == outd, channels outside [1, 64], a count <= 0, d not one of" FG_WAN_WIDTHS_STR
+                    ")");
     if ((int64_t)batch * frames * gh * gw > INT32_MAX / 2) return fail(FG_EINVAL, "fg_op_wan_final_jvp: too many tokens");
     HIP_TRY(launch_wan_final_jvp(d, tokens, tokens_d, mod, modd, w, bias, out, outd, batch * frames * gh * gw, frames, gh, gw, channels, eps,
                                  (hipStream_t)stream));

@@ -30,7 +30,7 @@
 #include <type_traits>
 
 #include "../../include/fastgen_amd.h"
-#include "common.h"
+#include "token.h"
 #include "misc.h"
 
 namespace {
@@ -39,11 +39,6 @@ constexpr int GM_NTHR = 512;
 constexpr int GM_TM = 256;   // tokens per tile
 constexpr int GM_KC = 64;    // k per pipeline step
 constexpr int GM_PA = GM_TM * 16 + 16;  // bytes between the octet planes of the A image
-
-__device__ __forceinline__ void gm_barrier() {
-    // this wave's LDS traffic retired, then the workgroup barrier; vmcnt is NOT drained (epilogue stores stay in flight)
-    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-}
 
 __device__ __forceinline__ float gm_gelu_tanh(float x) {
     // torch.nn.GELU(approximate="tanh") (DiT/network.py:176): 0.5 x (1 + tanh(u)) = x sigmoid(2 u), u = sqrt(2/pi) (x + 0.044715 x^3),
@@ -285,7 +280,7 @@ __global__ __launch_bounds__(GM_NTHR) void gemm_bf16_kernel(const GemmArgs a) {
     issue(0);
     park(smem);
     if (++kn == nk) kn = 0, ++tn;
-    gm_barrier();
+    lds_barrier();
     for (int s = 0; s < S; ++s) {
         // (the step behind the last one is staged too, from clamped - valid - addresses into the stage nobody reads any more:
         // unconditional loads let the compiler count them, a conditional issue makes it drain vmcnt before every step's LDS reads)
@@ -296,7 +291,7 @@ __global__ __launch_bounds__(GM_NTHR) void gemm_bf16_kernel(const GemmArgs a) {
         park(smem + ((s + 1) & 1) * STAGE);
         if (++kn == nk) kn = 0, ++tn;
         if (++kk == nk) kk = 0, ++ti;
-        gm_barrier();
+        lds_barrier();
     }
 }
 
@@ -339,7 +334,6 @@ __global__ __launch_bounds__(GM_NTHR) void gemm_bf16_pp_kernel(const GemmArgs a)
     constexpr int TN = 256;
     constexpr int EB = F8 ? 1 : 2;  // bytes per operand element
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    typedef __attribute__((address_space(3))) void* lds_ptr;
 
     const int tid = threadIdx.x;
     const int lane = tid & 63;
@@ -877,7 +871,6 @@ __global__ __launch_bounds__(GM_NTHR) void gemm_bf16_pp2_kernel(const GemmArgs a
     constexpr int TN = 128;
     constexpr int BUFB = 49152;  // bytes per stage: A rows 0-127 at 0, A rows 128-255 at 16384, W at 32768
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    typedef __attribute__((address_space(3))) void* lds_ptr;
 
     const int tid = threadIdx.x;
     const int lane = tid & 63;
@@ -1211,7 +1204,7 @@ __global__ __launch_bounds__(256) void quant_rows_fp8_kernel(const ST* __restric
         const f32x4 v = gm_ld4(xr + c);
         amax = fmaxf(amax, fmaxf(fmaxf(fabsf(v[0]), fabsf(v[1])), fmaxf(fabsf(v[2]), fabsf(v[3]))));
     }
-    amax = fp8_wave_max(amax);
+    amax = wave_max(amax);
     const float inv = fp8_row_inv(amax);
     if (lane == 0) scale[row] = fp8_row_scale(amax);
     unsigned* qr = reinterpret_cast<unsigned*>(q + row * K);

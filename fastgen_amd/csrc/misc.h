@@ -3,6 +3,28 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
+
+// The token widths D that have kernel instances: the one table behind every launcher's switch, the engines' width checks and the
+// text of their refusals.  DiT: S / B / L / XL.  Wan: two test widths, 1536 = the 1.3B network, 2048, 3072 = the 5B, 5120 = the 14B.
+#define FG_DIT_WIDTHS(X) X(384) X(768) X(1024) X(1152)
+#define FG_WAN_WIDTHS(X) X(256) X(384) X(1536) X(2048) X(3072) X(5120)
+#define FG_WIDTH_CASE_(D) case D: f(std::integral_constant<int, D>{}); return true;
+#define FG_WIDTH_STR_(D) " " #D
+#define FG_DIT_WIDTHS_STR FG_DIT_WIDTHS(FG_WIDTH_STR_)  // " 384 768 1024 1152": pastes into a message's string literal
+#define FG_WAN_WIDTHS_STR FG_WAN_WIDTHS(FG_WIDTH_STR_)
+// f(std::integral_constant<int, D>) for the table's entry d == D (f a generic lambda: one instance per width of the table); false: no entry
+template <typename F>
+inline bool fg_dit_width_call(int d, F&& f) {
+    switch (d) { FG_DIT_WIDTHS(FG_WIDTH_CASE_) default: return false; }
+}
+template <typename F>
+inline bool fg_wan_width_call(int d, F&& f) {
+    switch (d) { FG_WAN_WIDTHS(FG_WIDTH_CASE_) default: return false; }
+}
+inline bool fg_dit_width_ok(int d) { return fg_dit_width_call(d, [](auto) {}); }
+inline bool fg_wan_width_ok(int d) { return fg_wan_width_call(d, [](auto) {}); }
+
 // dtype (0 fp32 / 1 bf16) is the storage type of activation tensors passed as void*
 int launch_gn_coeffs(int dtype, const void* x1, int c1, const void* x2, int c2, const float* gamma, const float* beta,
                      float eps, float2* ab, int batch, int hw, hipStream_t s, float2* mr = nullptr);  // mr[b][group] = {mean, rstd}

@@ -13,17 +13,11 @@
 
 #include <type_traits>
 
-#include "common.h"
+#include "token.h"
 #include "../../include/fastgen_amd.h"
 #include "misc.h"
 
 namespace {
-
-__device__ __forceinline__ float wsum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
 
 // mod[bf][j][d] = table[j][d] + tproj[bf][j * D + d]
 __global__ void wan_mod_kernel(const float* __restrict__ table, const float* __restrict__ tproj, float* __restrict__ mod, int rows, int J, int D) {
@@ -90,7 +84,6 @@ __global__ __launch_bounds__(256) void rms_rope_kernel(const __bf16* __restrict_
     const int lane = threadIdx.x & 63;
     const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (row >= rows) return;
-    typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
     const __bf16* x = src + (size_t)row * ld_src;
     float v[2 * NP];
     float ss = 0.f;
@@ -102,7 +95,7 @@ __global__ __launch_bounds__(256) void rms_rope_kernel(const __bf16* __restrict_
     }
     const int b = row / L, l = row - b * L;
     if (w) {
-        const float r = 1.0f / sqrtf(wsum(ss) * (1.0f / D) + eps);
+        const float r = 1.0f / sqrtf(wave_sum(ss) * (1.0f / D) + eps);
 #pragma unroll
         for (int j = 0; j < NP; ++j) {
             const f32x2 wq = *reinterpret_cast<const f32x2*>(w + 2 * (lane + 64 * j));
@@ -128,17 +121,8 @@ __global__ __launch_bounds__(256) void rms_rope_kernel(const __bf16* __restrict_
 // 32, each tile's K and V rows (32 x 128 bf16 = 8 KiB each) staged once in LDS for its four waves (double-buffered; the loads of
 // tile t + 1 are in flight during tile t).  S^T = K Q^T (keys on the accumulator rows, the QUERY on the lane) and
 // O^T = V^T P^T (output dims on the rows, the query on the lane): the online-softmax state of a query is one lane's scalars and
-// the P^T accumulators feed the second product directly as its B operand.  V stays row-major in memory and in LDS; its
-// K-contiguous fragments (8 keys of one output dim) come from ds_read_b64_tr_b16.  LDS image of both tiles: 256-byte rows,
-// 16-byte chunk ch of row r at 16 (ch ^ (((r & 3) << 2) | ((r >> 2) & 3))): conflict-free for the ds_read_b128 row reads of K and
-// for the transposed reads of V (cdna_hip_programming.md T10, image (b)).
-__device__ __forceinline__ int fa_off(int row, int ch) { return 256 * row + 16 * (ch ^ (((row & 3) << 2) | ((row >> 2) & 3))); }
-
-typedef __attribute__((ext_vector_type(4))) short s16x4;
-typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
-__device__ __forceinline__ s16x4 fa_tr_read(const char* lds_addr) {
-    return __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(uintptr_t)(uint32_t)(uintptr_t)lds_addr);
-}
+// the P^T accumulators feed the second product directly as its B operand.  The LDS image of the two tiles (swizzled 256-byte rows,
+// V read transposed) is token.h's fa128_off / lds_tr_read.
 
 // Timing experiments (scripts/fa_ablate.sh) skip one ingredient of the pipelined step each and compute garbage: they exist only in the
 // separately built libfastgen_amd_timing.so (`make timing`, -DFG_TIMING_BUILD); the product kernel has neither the argument nor the tests.
@@ -175,8 +159,8 @@ __global__ __launch_bounds__(256, MINW) void fa_kernel(const __bf16* __restrict_
     constexpr int BUF = TILE + 32 * VP;  // a buffer = K tile | V tile
     constexpr int CPR = HD / 8;          // 16-byte chunks per row
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    auto off = [](int row, int ch) { return HD == 128 ? fa_off(row, ch) : row * RP + ch * 16; };
-    auto offv = [](int row, int ch) { return HD == 128 ? fa_off(row, ch) : row * VP + ch * 16; };
+    auto off = [](int row, int ch) { return HD == 128 ? fa128_off(row, ch) : row * RP + ch * 16; };
+    auto offv = [](int row, int ch) { return HD == 128 ? fa128_off(row, ch) : row * VP + ch * 16; };
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int r = lane & 31, h = lane >> 5;
     // Workgroup -> (unit, query tile), unit = (sample, head, key split): the query tiles of a unit read the same K / V rows, so a unit
@@ -249,7 +233,6 @@ __global__ __launch_bounds__(256, MINW) void fa_kernel(const __bf16* __restrict_
     // the buffer resource's range and read as zeros.
     constexpr bool DMA = HD == 128 && FA_DMA;
     constexpr int NST = DMA ? 4 : 2;
-    typedef __attribute__((address_space(3))) void* lds_ptr;
     __amdgpu_buffer_rsrc_t rsK, rsV;
     unsigned dvo[2] = {0, 0};
     if constexpr (DMA) {
@@ -259,7 +242,7 @@ __global__ __launch_bounds__(256, MINW) void fa_kernel(const __bf16* __restrict_
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
             const int row = (wave * 2 + j) * 4 + (lane >> 4), pos = lane & 15;
-            dvo[j] = (unsigned)row * (unsigned)ldk * 2u + 16u * (unsigned)(pos ^ (((row & 3) << 2) | ((row >> 2) & 3)));
+            dvo[j] = (unsigned)row * (unsigned)ldk * 2u + 16u * (unsigned)(pos ^ fa128_swz(row));
         }
     }
     auto dma = [&](int t, int stage) {  // tile t -> ring buffer `stage`; 4 instructions per wave
@@ -341,8 +324,8 @@ __global__ __launch_bounds__(256, MINW) void fa_kernel(const __bf16* __restrict_
 #pragma unroll
                 for (int d = 0; d < DT_; ++d) {
                     const int r0 = 16 * sx + 4 * h, c0 = 4 * d + 2 * gc;
-                    vl[sx][d] = fa_tr_read(st + TILE + offv(r0 + gq, c0 + (gp >> 1)) + 8 * (gp & 1));
-                    vh[sx][d] = fa_tr_read(st + TILE + offv(r0 + 8 + gq, c0 + (gp >> 1)) + 8 * (gp & 1));
+                    vl[sx][d] = lds_tr_read(st + TILE + offv(r0 + gq, c0 + (gp >> 1)) + 8 * (gp & 1));
+                    vh[sx][d] = lds_tr_read(st + TILE + offv(r0 + 8 + gq, c0 + (gp >> 1)) + 8 * (gp & 1));
                 }
         }
         // S^T[key][query]
@@ -407,7 +390,6 @@ __global__ __launch_bounds__(256, MINW) void fa_kernel(const __bf16* __restrict_
             for (int j = 0; j < 4; ++j) pf[2 * j] = (__bf16)e2[4 * sx + j][0], pf[2 * j + 1] = (__bf16)e2[4 * sx + j][1];
 #pragma unroll
             for (int d = 0; d < DT_; ++d) {
-                typedef __attribute__((ext_vector_type(8))) short s16x8;
                 const s16x4 lo = vl[sx][d], hi = vh[sx][d];
                 const s16x8 vv = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
                 ot[d] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, vv), pf, ot[d], 0, 0, 0);
@@ -529,7 +511,6 @@ __global__ __launch_bounds__(256, MINW) void fa_kernel(const __bf16* __restrict_
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
             // (the two halves of an operand are joined BEFORE the tie to the wait: the register allocator can then give the two reads
             // the halves of one 4-register tuple instead of copying them together in front of every MFMA)
-            typedef __attribute__((ext_vector_type(8))) short s16x8;
             s16x8 vv[2][DT_];
 #pragma unroll
             for (int sx = 0; sx < 2; ++sx)
@@ -631,8 +612,6 @@ __global__ __launch_bounds__(256, 1) void fa2_kernel(const __bf16* __restrict__ 
     constexpr int HD = 128, KS = 8, DT_ = 4, TILE = 32 * 256, NST = 6;
     constexpr int VBASE = NST * TILE;  // LDS: the ring's K tiles, then its V tiles
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    typedef __attribute__((ext_vector_type(8))) short s16x8;
-    typedef __attribute__((address_space(3))) void* lds_ptr;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int r = lane & 31, h = lane >> 5;
     const int qtiles = (Lq + 255) / 256, units = batch * heads * nsplit;
@@ -678,7 +657,7 @@ __global__ __launch_bounds__(256, 1) void fa2_kernel(const __bf16* __restrict__ 
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
         const int row = (wave * 2 + j) * 4 + (lane >> 4), pos = lane & 15;
-        dvo[j] = (unsigned)row * (unsigned)ldk * 2u + 16u * (unsigned)(pos ^ (((row & 3) << 2) | ((row >> 2) & 3)));
+        dvo[j] = (unsigned)row * (unsigned)ldk * 2u + 16u * (unsigned)(pos ^ fa128_swz(row));
     }
     auto dma = [&](int t, int stage) {  // tile t -> ring buffer `stage`; 4 instructions per wave
         const int soff = t * 32 * ldk * 2;
@@ -706,11 +685,11 @@ __global__ __launch_bounds__(256, 1) void fa2_kernel(const __bf16* __restrict__ 
     const uint32_t s0 = (uint32_t)(uintptr_t)smem;
     uint32_t ka[KS], va[DT_][2];
 #pragma unroll
-    for (int kk = 0; kk < KS; ++kk) ka[kk] = s0 + (uint32_t)fa_off(r, 2 * kk + h);
+    for (int kk = 0; kk < KS; ++kk) ka[kk] = s0 + (uint32_t)fa128_off(r, 2 * kk + h);
 #pragma unroll
     for (int d = 0; d < DT_; ++d)
 #pragma unroll
-        for (int hi = 0; hi < 2; ++hi) va[d][hi] = s0 + VBASE + (uint32_t)(fa_off(4 * h + 8 * hi + gq, 4 * d + 2 * gc + (gp >> 1)) + 8 * (gp & 1));
+        for (int hi = 0; hi < 2; ++hi) va[d][hi] = s0 + VBASE + (uint32_t)(fa128_off(4 * h + 8 * hi + gq, 4 * d + 2 * gc + (gp >> 1)) + 8 * (gp & 1));
 
     // ---- the pipeline ---------------------------------------------------------------------------------------------------------------
     // With one wave per SIMD nothing else fills the gaps of this wave's MFMAs: a 32x32x16 MFMA occupies the matrix pipe for 32 cycles and
@@ -1095,8 +1074,6 @@ __global__ __launch_bounds__(256, 2) void fa72_seq_kernel(const __bf16* __restri
                                                           int64_t o_bs, int Lq, int Lkv, float scale_log2e, int heads, int batch) {
     constexpr int HD = 72, KS = 5, DT_ = 3, RP = 144, NKT = 8, MAT = 256 * RP;  // bytes of one matrix in LDS
     extern __shared__ __attribute__((aligned(16))) char smem[];                // K | V | 64 bytes of slack behind V's last row
-    typedef __attribute__((address_space(3))) void* lds_ptr;
-    typedef __attribute__((ext_vector_type(8))) short s16x8;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int r = lane & 31, h = lane >> 5;
     // all heads of a sample on one XCD (fa_kernel's sample-major mapping: a head's 144-byte rows straddle its neighbours' cache lines)
@@ -1281,7 +1258,6 @@ __global__ __launch_bounds__(256) void wan_final_kernel(const __bf16* __restrict
                                                         const float* __restrict__ bias, float* __restrict__ out, int ntok, int Fr, int gh, int gw,
                                                         int C, float eps) {
     constexpr int D = 128 * NP;
-    typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
     const int lane = threadIdx.x & 63;
     const int tok = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (tok >= ntok) return;
@@ -1295,14 +1271,14 @@ __global__ __launch_bounds__(256) void wan_final_kernel(const __bf16* __restrict
         v[2 * j] = (float)q[0], v[2 * j + 1] = (float)q[1];
         s += v[2 * j] + v[2 * j + 1];
     }
-    const float mean = wsum(s) * (1.0f / D);
+    const float mean = wave_sum(s) * (1.0f / D);
     float ss = 0.f;
 #pragma unroll
     for (int e = 0; e < 2 * NP; ++e) {
         v[e] -= mean;
         ss = fmaf(v[e], v[e], ss);
     }
-    const float rstd = 1.0f / sqrtf(wsum(ss) * (1.0f / D) + eps);
+    const float rstd = 1.0f / sqrtf(wave_sum(ss) * (1.0f / D) + eps);
     const float* mrow = mod + (size_t)bf * 2 * D;
 #pragma unroll
     for (int j = 0; j < NP; ++j) {
@@ -1320,7 +1296,7 @@ __global__ __launch_bounds__(256) void wan_final_kernel(const __bf16* __restrict
             a = fmaf(v[2 * j], q[0], a);
             a = fmaf(v[2 * j + 1], q[1], a);
         }
-        a = wsum(a);
+        a = wave_sum(a);
         if (lane == 0) {
             const int c = o % C, pq = o / C, py = pq >> 1, px = pq & 1;
             out[((((size_t)b * C + c) * Fr + f) * H + 2 * gy + py) * W + 2 * gx + px] = a + bias[o];
@@ -1365,21 +1341,14 @@ int launch_wan_rope_table(const float2* tab_t, const float2* tab_h, const float2
     hipLaunchKernelGGL(wan_rope_table_kernel, dim3((n + 255) / 256), dim3(256), 0, s, tab_t, tab_h, tab_w, cs, L, fs, gw, start, S, nt, nh, nw);
     WAN_RET();
 }
-// D = 128 NP with NP in {2, 3, 12, 16, 24, 40} (256, 384, 1536 = the 1.3B network, 2048, 3072 = the 5B network, 5120 = the 14B network)
+// D = 128 NP: one of misc.h's FG_WAN_WIDTHS
 int launch_rms_rope(int D, const void* src, int ld_src, const float* w, float eps, const float2* cs, void* dst, int64_t dst_bs, int dst_row0,
                     int ld_dst, int rows, int L, hipStream_t s) {
     dim3 g((rows + 3) / 4), b(256);
-#define RR(NP) hipLaunchKernelGGL(rms_rope_kernel<NP>, g, b, 0, s, (const __bf16*)src, ld_src, w, eps, cs, (__bf16*)dst, dst_bs, dst_row0, ld_dst, rows, L)
-    switch (D) {
-        case 256: RR(2); break;
-        case 384: RR(3); break;
-        case 1536: RR(12); break;
-        case 2048: RR(16); break;
-        case 3072: RR(24); break;
-        case 5120: RR(40); break;
-        default: return (int)hipErrorInvalidValue;
-    }
-#undef RR
+    if (!fg_wan_width_call(D, [&](auto d) {
+            hipLaunchKernelGGL(rms_rope_kernel<decltype(d)::value / 128>, g, b, 0, s, (const __bf16*)src, ld_src, w, eps, cs, (__bf16*)dst, dst_bs, dst_row0, ld_dst, rows, L);
+        }))
+        return (int)hipErrorInvalidValue;
     WAN_RET();
 }
 // Key splits: how many workgroups share one query tile's keys, so that short grids (one sample: ceil(Lq / 128) x heads workgroups)
@@ -1545,16 +1514,9 @@ int launch_fa128(const void* q, int ldq, int64_t q_bs, const void* k, const void
 int launch_wan_final(int D, const void* x, const float* mod, const float* w, const float* bias, float* out, int ntok, int Fr, int gh, int gw, int C,
                      float eps, hipStream_t s) {
     dim3 g((ntok + 3) / 4), b(256);
-#define WF(NP) hipLaunchKernelGGL(wan_final_kernel<NP>, g, b, 0, s, (const __bf16*)x, mod, w, bias, out, ntok, Fr, gh, gw, C, eps)
-    switch (D) {
-        case 256: WF(2); break;
-        case 384: WF(3); break;
-        case 1536: WF(12); break;
-        case 2048: WF(16); break;
-        case 3072: WF(24); break;
-        case 5120: WF(40); break;
-        default: return (int)hipErrorInvalidValue;
-    }
-#undef WF
+    if (!fg_wan_width_call(D, [&](auto d) {
+            hipLaunchKernelGGL(wan_final_kernel<decltype(d)::value / 128>, g, b, 0, s, (const __bf16*)x, mod, w, bias, out, ntok, Fr, gh, gw, C, eps);
+        }))
+        return (int)hipErrorInvalidValue;
     WAN_RET();
 }

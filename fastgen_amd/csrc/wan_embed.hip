@@ -11,7 +11,7 @@
 //                                     taken in phases of 48 inputs (a 192- or 384-float row does not fit beside the sums)
 // Token tok of sample b goes to row b * out_rows + (tok - b * per) of out, per = Fr gh gw <= out_rows: a caller may leave rows behind a
 // sample's tokens (VACE's zero padding, VaceWan/network.py:81-88); those rows are never touched.
-#include "common.h"
+#include "token.h"
 #include "misc.h"
 
 namespace {
@@ -62,7 +62,6 @@ __device__ __forceinline__ void wan_embed_tile_rows(int64_t (&orow)[TOK], int64_
     }
 }
 
-typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2_;
 
 template <int MODE>
 __global__ __launch_bounds__(256) void wan_embed_kernel(WanEmbedSrc s, const float* __restrict__ w, const float* __restrict__ bias,
@@ -132,7 +131,7 @@ __global__ __launch_bounds__(256) void wan_embed_rows_kernel(WanEmbedSrc s, cons
                     for (int o = 0; o < NOUT; ++o) a[o] = fmaf(wr[o][q][e], xv[e], a[o]);
             }
             __bf16* dst = out + (size_t)orow[t] * D + d;
-            if (NOUT == 2) *reinterpret_cast<bf16x2_*>(dst) = bf16x2_{(__bf16)a[0], (__bf16)a[NOUT - 1]};
+            if (NOUT == 2) *reinterpret_cast<bf16x2*>(dst) = bf16x2{(__bf16)a[0], (__bf16)a[NOUT - 1]};
             else *dst = (__bf16)a[0];
         }
     }
@@ -186,7 +185,7 @@ __global__ __launch_bounds__(256) void wan_embed_phased_kernel(WanEmbedSrc s, co
         asm volatile("" ::: "memory");
 #pragma unroll
         for (int t = 0; t < TOK; ++t)
-            if (tok0 + t < ntok) *reinterpret_cast<bf16x2_*>(out + (size_t)orow[t] * D + d) = bf16x2_{(__bf16)a0[t], (__bf16)a1[t]};
+            if (tok0 + t < ntok) *reinterpret_cast<bf16x2*>(out + (size_t)orow[t] * D + d) = bf16x2{(__bf16)a0[t], (__bf16)a1[t]};
     }
 }
 

@@ -7,31 +7,15 @@
 //   wan_gelu_erf_kernel          its exact (erf) GELU, in place on bf16 (the token GEMM's `act` knows the tanh form only)
 // PARITY UNPINNED like the rest of the video DiT: the image branch lives in un-vendored diffusers (WanTimeTextImageEmbedding's
 // WanImageEmbedding, WanAttention's add_k_proj / add_v_proj / norm_added_k); tests/wan_i2v_ref.py restates it.
-#include "common.h"
+#include "token.h"
 #include "../../include/fastgen_amd.h"
 #include "misc.h"
 
 namespace {
 
-__device__ __forceinline__ float wsum_i2v(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-
-// fa_kernel<128>'s LDS image (wan.hip): 256-byte rows, 16-byte chunk ch of row r at 16 (ch ^ (((r & 3) << 2) | ((r >> 2) & 3)))
-__device__ __forceinline__ int dx_off(int row, int ch) { return 256 * row + 16 * (ch ^ (((row & 3) << 2) | ((row >> 2) & 3))); }
-
-typedef __attribute__((ext_vector_type(4))) short dx_s16x4;
-typedef __attribute__((ext_vector_type(8))) short dx_s16x8;
-typedef __attribute__((address_space(3))) dx_s16x4 dx_lds_s16x4;
-__device__ __forceinline__ dx_s16x4 dx_tr_read(const char* lds_addr) {
-    return __builtin_amdgcn_ds_read_tr16_b64_v4i16((dx_lds_s16x4*)(uintptr_t)(uint32_t)(uintptr_t)lds_addr);
-}
-
 // One context of the dual attention: this wave's 32 queries (fragments qf, the query on the lane) over keys [0, Lkv) of kb / vb,
 // normalised, into ot (O^T[dim][query], dims 32 d + acc_row(i, h)).  fa_kernel<128>'s register-staged tile step: 32-key tiles, K and V
-// rows double-buffered in LDS (2 x 16 KiB), the next tile's global loads in flight during the current tile, S^T = K Q^T, online
+// rows double-buffered in LDS (2 x 16 KiB, token.h's fa128_off image), the next tile's global loads in flight during the current tile, S^T = K Q^T, online
 // softmax in the log2 domain, O^T += V^T P^T with transposed V reads.  Key rows are clamped to Lkv - 1 (nothing is read past the
 // last key) and masked to -inf in the last tile: they weigh exactly zero.  Every wave of the workgroup calls this (barriers inside).
 __device__ __forceinline__ void dx_context(const __bf16* __restrict__ kb, const __bf16* __restrict__ vb, int ldk, int Lkv, const bf16x8 (&qf)[8],
@@ -54,8 +38,8 @@ __device__ __forceinline__ void dx_context(const __bf16* __restrict__ kb, const 
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
             const int p = tid + 256 * i;
-            *reinterpret_cast<fg_u32x4*>(st + dx_off(p / 16, p % 16)) = kreg[i];
-            *reinterpret_cast<fg_u32x4*>(st + TILE + dx_off(p / 16, p % 16)) = vreg[i];
+            *reinterpret_cast<fg_u32x4*>(st + fa128_off(p / 16, p % 16)) = kreg[i];
+            *reinterpret_cast<fg_u32x4*>(st + TILE + fa128_off(p / 16, p % 16)) = vreg[i];
         }
     };
 #pragma unroll
@@ -72,7 +56,7 @@ __device__ __forceinline__ void dx_context(const __bf16* __restrict__ kb, const 
         if (t + 1 < ntiles) issue(t + 1);
         bf16x8 kf[8];
 #pragma unroll
-        for (int kk = 0; kk < 8; ++kk) kf[kk] = *reinterpret_cast<const bf16x8*>(st + dx_off(r, 2 * kk + h));
+        for (int kk = 0; kk < 8; ++kk) kf[kk] = *reinterpret_cast<const bf16x8*>(st + fa128_off(r, 2 * kk + h));
         f32x16 s;
 #pragma unroll
         for (int i = 0; i < 16; ++i) s[i] = 0.f;
@@ -115,9 +99,9 @@ __device__ __forceinline__ void dx_context(const __bf16* __restrict__ kb, const 
 #pragma unroll
             for (int d = 0; d < 4; ++d) {
                 const int r0 = 16 * sx + 4 * h, c0 = 4 * d + 2 * gc;
-                const dx_s16x4 lo = dx_tr_read(st + TILE + dx_off(r0 + gq, c0 + (gp >> 1)) + 8 * (gp & 1));
-                const dx_s16x4 hi = dx_tr_read(st + TILE + dx_off(r0 + 8 + gq, c0 + (gp >> 1)) + 8 * (gp & 1));
-                const dx_s16x8 vv = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+                const s16x4 lo = lds_tr_read(st + TILE + fa128_off(r0 + gq, c0 + (gp >> 1)) + 8 * (gp & 1));
+                const s16x4 hi = lds_tr_read(st + TILE + fa128_off(r0 + 8 + gq, c0 + (gp >> 1)) + 8 * (gp & 1));
+                const s16x8 vv = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
                 ot[d] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, vv), pf, ot[d], 0, 0, 0);
             }
         }
@@ -193,13 +177,13 @@ __global__ __launch_bounds__(256) void wan_ln_rows_kernel(const T* __restrict__ 
     const T* xr = x + (size_t)row * n;
     float s = 0.f;
     for (int i = lane; i < n; i += 64) s += (float)xr[i];
-    const float mean = wsum_i2v(s) / (float)n;
+    const float mean = wave_sum(s) / (float)n;
     float ss = 0.f;
     for (int i = lane; i < n; i += 64) {
         const float c = (float)xr[i] - mean;
         ss = fmaf(c, c, ss);
     }
-    const float rstd = 1.0f / sqrtf(wsum_i2v(ss) / (float)n + eps);
+    const float rstd = 1.0f / sqrtf(wave_sum(ss) / (float)n + eps);
     for (int i = lane; i < n; i += 64) y[(size_t)row * n + i] = (__bf16)fmaf(((float)xr[i] - mean) * rstd, w[i], b[i]);
 }
 

@@ -7,18 +7,10 @@
 //   wan_gelu_jvp_kernel         a = gelu_tanh(h), ad = gelu_tanh'(h) hd
 //   wan_final_jvp_kernel        wan_final_kernel with the tangent of the LayerNorm-modulate: out = b + W y, jvp = W yd
 //   wan_dup2_kernel             the output layer's {shift, scale} tangent rows: both are the tangent of temb
-#include "common.h"
+#include "token.h"
 #include "misc.h"
 
 namespace {
-
-typedef __attribute__((ext_vector_type(2))) __bf16 wj_bf16x2;
-
-__device__ __forceinline__ float wj_wsum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
 
 // One wave per token, D = 128 NP, lane l holds the channel pairs 2 (l + 64 j).  mod / modd [rows][mod_stride] fp32: shift at shift_off,
 // scale at scale_off, their tangents at the same places of modd (modd == nullptr: a constant affine, sd = bd = 0); row = tok / tpi.
@@ -36,27 +28,27 @@ __global__ __launch_bounds__(256) void wan_ln_modulate_jvp_kernel(const __bf16* 
     float s = 0.f, sd = 0.f;
 #pragma unroll
     for (int j = 0; j < NP; ++j) {
-        const wj_bf16x2 q = *reinterpret_cast<const wj_bf16x2*>(x + (size_t)tok * D + 2 * (lane + 64 * j));
-        const wj_bf16x2 p = *reinterpret_cast<const wj_bf16x2*>(xd + (size_t)tok * D + 2 * (lane + 64 * j));
+        const bf16x2 q = *reinterpret_cast<const bf16x2*>(x + (size_t)tok * D + 2 * (lane + 64 * j));
+        const bf16x2 p = *reinterpret_cast<const bf16x2*>(xd + (size_t)tok * D + 2 * (lane + 64 * j));
         v[2 * j] = (float)q[0], v[2 * j + 1] = (float)q[1], d[2 * j] = (float)p[0], d[2 * j + 1] = (float)p[1];
         s += v[2 * j] + v[2 * j + 1];
         sd += d[2 * j] + d[2 * j + 1];
     }
-    const float mean = wj_wsum(s) * (1.0f / D), dmean = wj_wsum(sd) * (1.0f / D);
+    const float mean = wave_sum(s) * (1.0f / D), dmean = wave_sum(sd) * (1.0f / D);
     float ss = 0.f;
 #pragma unroll
     for (int e = 0; e < 2 * NP; ++e) {
         v[e] -= mean;
         ss = fmaf(v[e], v[e], ss);
     }
-    const float rstd = 1.0f / sqrtf(wj_wsum(ss) * (1.0f / D) + eps);
+    const float rstd = 1.0f / sqrtf(wave_sum(ss) * (1.0f / D) + eps);
     float nd = 0.f;
 #pragma unroll
     for (int e = 0; e < 2 * NP; ++e) {
         v[e] *= rstd;
         nd = fmaf(v[e], d[e], nd);
     }
-    const float m2 = wj_wsum(nd) * (1.0f / D);
+    const float m2 = wave_sum(nd) * (1.0f / D);
     const float* mrow = mod + (size_t)n * mod_stride;
     const float* mdrow = modd ? modd + (size_t)n * mod_stride : nullptr;
 #pragma unroll
@@ -72,8 +64,8 @@ __global__ __launch_bounds__(256) void wan_ln_modulate_jvp_kernel(const __bf16* 
             o[e] = fmaf(nn, 1.0f + sc[e], sh[e]);
             od[e] = fmaf(ndv, 1.0f + sc[e], fmaf(nn, scd[e], shd[e]));
         }
-        *reinterpret_cast<wj_bf16x2*>(y + (size_t)tok * D + c) = wj_bf16x2{(__bf16)o[0], (__bf16)o[1]};
-        *reinterpret_cast<wj_bf16x2*>(yd + (size_t)tok * D + c) = wj_bf16x2{(__bf16)od[0], (__bf16)od[1]};
+        *reinterpret_cast<bf16x2*>(y + (size_t)tok * D + c) = bf16x2{(__bf16)o[0], (__bf16)o[1]};
+        *reinterpret_cast<bf16x2*>(yd + (size_t)tok * D + c) = bf16x2{(__bf16)od[0], (__bf16)od[1]};
     }
 }
 
@@ -92,19 +84,19 @@ __global__ __launch_bounds__(256) void wan_rms_rope_jvp_kernel(const __bf16* __r
     float ss = 0.f;
 #pragma unroll
     for (int j = 0; j < NP; ++j) {
-        const wj_bf16x2 q = *reinterpret_cast<const wj_bf16x2*>(src + (size_t)row * ld_src + 2 * (lane + 64 * j));
-        const wj_bf16x2 p = *reinterpret_cast<const wj_bf16x2*>(srcd + (size_t)row * ld_src + 2 * (lane + 64 * j));
+        const bf16x2 q = *reinterpret_cast<const bf16x2*>(src + (size_t)row * ld_src + 2 * (lane + 64 * j));
+        const bf16x2 p = *reinterpret_cast<const bf16x2*>(srcd + (size_t)row * ld_src + 2 * (lane + 64 * j));
         v[2 * j] = (float)q[0], v[2 * j + 1] = (float)q[1], d[2 * j] = (float)p[0], d[2 * j + 1] = (float)p[1];
         ss = fmaf(v[2 * j], v[2 * j], fmaf(v[2 * j + 1], v[2 * j + 1], ss));
     }
-    const float r = 1.0f / sqrtf(wj_wsum(ss) * (1.0f / D) + eps);
+    const float r = 1.0f / sqrtf(wave_sum(ss) * (1.0f / D) + eps);
     float nd = 0.f;
 #pragma unroll
     for (int e = 0; e < 2 * NP; ++e) {
         v[e] *= r;
         nd = fmaf(v[e], d[e], nd);
     }
-    const float m2 = wj_wsum(nd) * (1.0f / D);
+    const float m2 = wave_sum(nd) * (1.0f / D);
 #pragma unroll
     for (int j = 0; j < NP; ++j) {
         const f32x2 wq = *reinterpret_cast<const f32x2*>(w + 2 * (lane + 64 * j));
@@ -129,8 +121,8 @@ __global__ __launch_bounds__(256) void wan_rms_rope_jvp_kernel(const __bf16* __r
     const size_t at = (size_t)b * dst_bs + (size_t)l * ld_dst;
 #pragma unroll
     for (int j = 0; j < NP; ++j) {
-        *reinterpret_cast<wj_bf16x2*>(dst + at + 2 * (lane + 64 * j)) = wj_bf16x2{(__bf16)v[2 * j], (__bf16)v[2 * j + 1]};
-        *reinterpret_cast<wj_bf16x2*>(dstd + at + 2 * (lane + 64 * j)) = wj_bf16x2{(__bf16)d[2 * j], (__bf16)d[2 * j + 1]};
+        *reinterpret_cast<bf16x2*>(dst + at + 2 * (lane + 64 * j)) = bf16x2{(__bf16)v[2 * j], (__bf16)v[2 * j + 1]};
+        *reinterpret_cast<bf16x2*>(dstd + at + 2 * (lane + 64 * j)) = bf16x2{(__bf16)d[2 * j], (__bf16)d[2 * j + 1]};
     }
 }
 
@@ -146,16 +138,9 @@ __global__ __launch_bounds__(256) void wan_rms_rope_jvp_kernel(const __bf16* __r
 // Layout as wan.hip's fa_kernel<128> in its register-staged form: grid = (sample, head) units dealt to the XCDs x query tiles of 128,
 // a wave owns 32 queries; S^T = K Q^T and Sd^T = K Qd^T + Kd Q^T put the query on the lane (softmax state, c, w, l: one lane's
 // scalars), P^T and W^T are the B operands of O~^T = V^T P^T and T^T = V^T W^T + Vd^T P^T: five products per key tile.  The K, V,
-// Kd, Vd tiles of 32 keys (8 KiB each, fa_kernel's swizzled image) are double-buffered in 64 KiB of LDS; the next tile's rows are in
+// Kd, Vd tiles of 32 keys (8 KiB each, token.h's fa128_off image) are double-buffered in 64 KiB of LDS; the next tile's rows are in
 // flight in registers while a tile is computed.  Key rows are clamped to Lkv - 1 when loaded (nothing past the last key is read) and
 // masked in S.  Null qd / kd / vd: that tangent is zero and its product is skipped (the text keys of the cross-attention).
-__device__ __forceinline__ int wj_off(int row, int ch) { return 256 * row + 16 * (ch ^ (((row & 3) << 2) | ((row >> 2) & 3))); }
-typedef __attribute__((ext_vector_type(4))) short wj_s16x4;
-typedef __attribute__((ext_vector_type(8))) short wj_s16x8;
-typedef __attribute__((address_space(3))) wj_s16x4 wj_lds_s16x4;
-__device__ __forceinline__ wj_s16x4 wj_tr_read(const char* lds_addr) {
-    return __builtin_amdgcn_ds_read_tr16_b64_v4i16((wj_lds_s16x4*)(uintptr_t)(uint32_t)(uintptr_t)lds_addr);
-}
 // the value of the other lane half (lane ^ 32) combined with this one's
 __device__ __forceinline__ void wj_swap(float v, float& a_, float& b_) {
     a_ = v, b_ = v;
@@ -204,7 +189,7 @@ __global__ __launch_bounds__(256, 1) void wan_attn_jvp_kernel(const __bf16* __re
     auto park = [&](char* st) {
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
-            const int p = tid + 256 * i, o = wj_off(p >> 4, p & 15);
+            const int p = tid + 256 * i, o = fa128_off(p >> 4, p & 15);
             *reinterpret_cast<fg_u32x4*>(st + o) = kreg[i];
             *reinterpret_cast<fg_u32x4*>(st + TILE + o) = vreg[i];
             if (kd) *reinterpret_cast<fg_u32x4*>(st + 2 * TILE + o) = kdreg[i];
@@ -232,14 +217,14 @@ __global__ __launch_bounds__(256, 1) void wan_attn_jvp_kernel(const __bf16* __re
         for (int i = 0; i < 16; ++i) s[i] = 0.f, sd[i] = 0.f;
 #pragma unroll
         for (int kk = 0; kk < KS; ++kk) {
-            const bf16x8 kf = *reinterpret_cast<const bf16x8*>(st + wj_off(r, 2 * kk + h));
+            const bf16x8 kf = *reinterpret_cast<const bf16x8*>(st + fa128_off(r, 2 * kk + h));
             s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf, qf[kk], s, 0, 0, 0);
             if (qd) sd = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf, qdf[kk], sd, 0, 0, 0);
         }
         if (kd) {
 #pragma unroll
             for (int kk = 0; kk < KS; ++kk) {
-                const bf16x8 kdf = *reinterpret_cast<const bf16x8*>(st + 2 * TILE + wj_off(r, 2 * kk + h));
+                const bf16x8 kdf = *reinterpret_cast<const bf16x8*>(st + 2 * TILE + fa128_off(r, 2 * kk + h));
                 sd = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kdf, qf[kk], sd, 0, 0, 0);
             }
         }
@@ -291,14 +276,14 @@ __global__ __launch_bounds__(256, 1) void wan_attn_jvp_kernel(const __bf16* __re
 #pragma unroll
             for (int d = 0; d < DT_; ++d) {
                 const int r0 = 16 * sx + 4 * h, c0 = 4 * d + 2 * gc;
-                const int olo = wj_off(r0 + gq, c0 + (gp >> 1)) + 8 * (gp & 1), ohi = wj_off(r0 + 8 + gq, c0 + (gp >> 1)) + 8 * (gp & 1);
-                const wj_s16x4 lo = wj_tr_read(st + TILE + olo), hi = wj_tr_read(st + TILE + ohi);
-                const bf16x8 vv = __builtin_bit_cast(bf16x8, wj_s16x8{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]});
+                const int olo = fa128_off(r0 + gq, c0 + (gp >> 1)) + 8 * (gp & 1), ohi = fa128_off(r0 + 8 + gq, c0 + (gp >> 1)) + 8 * (gp & 1);
+                const s16x4 lo = lds_tr_read(st + TILE + olo), hi = lds_tr_read(st + TILE + ohi);
+                const bf16x8 vv = __builtin_bit_cast(bf16x8, s16x8{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]});
                 ot[d] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vv, pf, ot[d], 0, 0, 0);
                 tt[d] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vv, wf, tt[d], 0, 0, 0);
                 if (vd) {
-                    const wj_s16x4 dl = wj_tr_read(st + 3 * TILE + olo), dh = wj_tr_read(st + 3 * TILE + ohi);
-                    const bf16x8 dv = __builtin_bit_cast(bf16x8, wj_s16x8{dl[0], dl[1], dl[2], dl[3], dh[0], dh[1], dh[2], dh[3]});
+                    const s16x4 dl = lds_tr_read(st + 3 * TILE + olo), dh = lds_tr_read(st + 3 * TILE + ohi);
+                    const bf16x8 dv = __builtin_bit_cast(bf16x8, s16x8{dl[0], dl[1], dl[2], dl[3], dh[0], dh[1], dh[2], dh[3]});
                     tt[d] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(dv, pf, tt[d], 0, 0, 0);
                 }
             }
@@ -332,8 +317,7 @@ __global__ __launch_bounds__(256, 1) void wan_attn_jvp_kernel(const __bf16* __re
     }
 }
 
-// a = gelu_tanh(h) = h sig(2 u), u = sqrt(2/pi) (h + 0.044715 h^3);  ad = (sig + h sig (1 - sig) 2 u') hd (dit_jvp.hip's
-// gelu_jvp_kernel on bf16 tensors).  h, hd, a, ad bf16 [n]; one thread = 4 values; a / ad may be h / hd (each thread reads its four
+// a = gelu_tanh(h), ad = gelu_tanh'(h) hd (token.h's gelu_tanh_jvp: dit_jvp.hip's gelu_jvp_kernel on bf16 tensors).  h, hd, a, ad bf16 [n]; one thread = 4 values; a / ad may be h / hd (each thread reads its four
 // values before it writes them).
 __global__ __launch_bounds__(256) void wan_gelu_jvp_kernel(const __bf16* h, const __bf16* hd, __bf16* a, __bf16* ad, int64_t n4) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -342,13 +326,10 @@ __global__ __launch_bounds__(256) void wan_gelu_jvp_kernel(const __bf16* h, cons
     bf16x4 g4, gd4;
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
-        constexpr float c0 = 0.7978845608028654f, c1 = 0.044715f;
-        const float v = (float)x[e], v2 = v * v;
-        const float u2 = 2.0f * c0 * v * fmaf(c1, v2, 1.0f);
-        const float sig = 1.0f / (1.0f + expf(-u2));
-        const float g = v * sig;
+        float g;
+        const float dg = gelu_tanh_jvp((float)x[e], g);
         g4[e] = (__bf16)g;
-        gd4[e] = (__bf16)((sig + g * (1.0f - sig) * (2.0f * c0 * fmaf(3.0f * c1, v2, 1.0f))) * (float)xd[e]);
+        gd4[e] = (__bf16)(dg * (float)xd[e]);
     }
     *reinterpret_cast<bf16x4*>(a + 4 * i) = g4;
     *reinterpret_cast<bf16x4*>(ad + 4 * i) = gd4;
@@ -377,27 +358,27 @@ __global__ __launch_bounds__(256) void wan_final_jvp_kernel(const __bf16* __rest
     float s = 0.f, sd = 0.f;
 #pragma unroll
     for (int j = 0; j < NP; ++j) {
-        const wj_bf16x2 q = *reinterpret_cast<const wj_bf16x2*>(x + (size_t)tok * D + 2 * (lane + 64 * j));
-        const wj_bf16x2 p = *reinterpret_cast<const wj_bf16x2*>(xd + (size_t)tok * D + 2 * (lane + 64 * j));
+        const bf16x2 q = *reinterpret_cast<const bf16x2*>(x + (size_t)tok * D + 2 * (lane + 64 * j));
+        const bf16x2 p = *reinterpret_cast<const bf16x2*>(xd + (size_t)tok * D + 2 * (lane + 64 * j));
         v[2 * j] = (float)q[0], v[2 * j + 1] = (float)q[1], d[2 * j] = (float)p[0], d[2 * j + 1] = (float)p[1];
         s += v[2 * j] + v[2 * j + 1];
         sd += d[2 * j] + d[2 * j + 1];
     }
-    const float mean = wj_wsum(s) * (1.0f / D), dmean = wj_wsum(sd) * (1.0f / D);
+    const float mean = wave_sum(s) * (1.0f / D), dmean = wave_sum(sd) * (1.0f / D);
     float ss = 0.f;
 #pragma unroll
     for (int e = 0; e < 2 * NP; ++e) {
         v[e] -= mean;
         ss = fmaf(v[e], v[e], ss);
     }
-    const float rstd = 1.0f / sqrtf(wj_wsum(ss) * (1.0f / D) + eps);
+    const float rstd = 1.0f / sqrtf(wave_sum(ss) * (1.0f / D) + eps);
     float nd = 0.f;
 #pragma unroll
     for (int e = 0; e < 2 * NP; ++e) {
         v[e] *= rstd;
         nd = fmaf(v[e], d[e], nd);
     }
-    const float m2 = wj_wsum(nd) * (1.0f / D);
+    const float m2 = wave_sum(nd) * (1.0f / D);
     const float *mrow = mod + (size_t)bf * 2 * D, *mdrow = modd + (size_t)bf * 2 * D;
 #pragma unroll
     for (int j = 0; j < NP; ++j) {
@@ -420,8 +401,8 @@ __global__ __launch_bounds__(256) void wan_final_jvp_kernel(const __bf16* __rest
             a = fmaf(v[2 * j], q[0], a), a = fmaf(v[2 * j + 1], q[1], a);
             ad = fmaf(d[2 * j], q[0], ad), ad = fmaf(d[2 * j + 1], q[1], ad);
         }
-        a = wj_wsum(a);
-        ad = wj_wsum(ad);
+        a = wave_sum(a);
+        ad = wave_sum(ad);
         if (lane == 0) {
             const int c = o % C, pq = o / C, py = pq >> 1, px = pq & 1;
             const size_t at = ((((size_t)b * C + c) * Fr + f) * H + 2 * gy + py) * W + 2 * gx + px;
@@ -432,17 +413,8 @@ __global__ __launch_bounds__(256) void wan_final_jvp_kernel(const __bf16* __rest
 }
 
 #define WJ_RET() return (int)hipGetLastError()
-// D = 128 NP with NP in {2, 3, 12, 16, 24, 40}, as wan.hip's launchers
-#define WJ_SWITCH(D, GO)                           \
-    switch (D) {                                   \
-        case 256: GO(2); break;                    \
-        case 384: GO(3); break;                    \
-        case 1536: GO(12); break;                  \
-        case 2048: GO(16); break;                  \
-        case 3072: GO(24); break;                  \
-        case 5120: GO(40); break;                  \
-        default: return (int)hipErrorInvalidValue; \
-    }
+// D = 128 NP: one of misc.h's FG_WAN_WIDTHS, as wan.hip's launchers
+#define WJ_NP (decltype(d)::value / 128)
 
 }  // namespace
 
@@ -450,22 +422,22 @@ int launch_wan_ln_modulate_jvp(int D, const void* x, const void* xd, const float
                                int scale_off, void* y, void* yd, int ntok, int tokens_per_row, float eps, hipStream_t s) {
     if (ntok <= 0 || tokens_per_row <= 0 || (mod_stride % 2) || (shift_off % 2) || (scale_off % 2)) return (int)hipErrorInvalidValue;  // (8-byte loads)
     dim3 g((ntok + 3) / 4), b(256);
-#define GO(NP)                                                                                                                                    \
-    hipLaunchKernelGGL(wan_ln_modulate_jvp_kernel<NP>, g, b, 0, s, (const __bf16*)x, (const __bf16*)xd, mod, modd, mod_stride, shift_off, scale_off, \
-                       (__bf16*)y, (__bf16*)yd, ntok, tokens_per_row, eps)
-    WJ_SWITCH(D, GO)
-#undef GO
+    if (!fg_wan_width_call(D, [&](auto d) {
+            hipLaunchKernelGGL(wan_ln_modulate_jvp_kernel<WJ_NP>, g, b, 0, s, (const __bf16*)x, (const __bf16*)xd, mod, modd, mod_stride, shift_off,
+                               scale_off, (__bf16*)y, (__bf16*)yd, ntok, tokens_per_row, eps);
+        }))
+        return (int)hipErrorInvalidValue;
     WJ_RET();
 }
 int launch_wan_rms_rope_jvp(int D, const void* src, const void* srcd, int ld_src, const float* w, float eps, const float2* cs, void* dst, void* dstd,
                             int64_t dst_bs, int ld_dst, int rows, int L, hipStream_t s) {
     if (rows <= 0 || L <= 0 || !w || (ld_src % 2) || (ld_dst % 2)) return (int)hipErrorInvalidValue;
     dim3 g((rows + 3) / 4), b(256);
-#define GO(NP)                                                                                                                                  \
-    hipLaunchKernelGGL(wan_rms_rope_jvp_kernel<NP>, g, b, 0, s, (const __bf16*)src, (const __bf16*)srcd, ld_src, w, eps, cs, (__bf16*)dst, (__bf16*)dstd, \
-                       dst_bs, ld_dst, rows, L)
-    WJ_SWITCH(D, GO)
-#undef GO
+    if (!fg_wan_width_call(D, [&](auto d) {
+            hipLaunchKernelGGL(wan_rms_rope_jvp_kernel<WJ_NP>, g, b, 0, s, (const __bf16*)src, (const __bf16*)srcd, ld_src, w, eps, cs, (__bf16*)dst,
+                               (__bf16*)dstd, dst_bs, ld_dst, rows, L);
+        }))
+        return (int)hipErrorInvalidValue;
     WJ_RET();
 }
 int launch_wan_attention_jvp(const void* q, const void* qd, int ldq, int64_t q_bs, const void* k, const void* v, const void* kd, const void* vd,
@@ -497,10 +469,10 @@ int launch_wan_final_jvp(int D, const void* x, const void* xd, const float* mod,
                          float* outd, int ntok, int Fr, int gh, int gw, int C, float eps, hipStream_t s) {
     if (ntok <= 0 || Fr <= 0 || gh <= 0 || gw <= 0 || C <= 0) return (int)hipErrorInvalidValue;
     dim3 g((ntok + 3) / 4), b(256);
-#define GO(NP)                                                                                                                                   \
-    hipLaunchKernelGGL(wan_final_jvp_kernel<NP>, g, b, 0, s, (const __bf16*)x, (const __bf16*)xd, mod, modd, w, bias, out, outd, ntok, Fr, gh, gw, C, \
-                       eps)
-    WJ_SWITCH(D, GO)
-#undef GO
+    if (!fg_wan_width_call(D, [&](auto d) {
+            hipLaunchKernelGGL(wan_final_jvp_kernel<WJ_NP>, g, b, 0, s, (const __bf16*)x, (const __bf16*)xd, mod, modd, w, bias, out, outd, ntok, Fr, gh,
+                               gw, C, eps);
+        }))
+        return (int)hipErrorInvalidValue;
     WJ_RET();
 }

@@ -7,16 +7,10 @@
 //                                   first-frame mask, WanI2V/network.py:334-340)
 // The optional second source `ff0` [B][C][1][H][W] is the first-frame condition: the head writes it into frame 0 of its result (the
 // replaced latents of `_replace_first_frame`, :254-277, are never materialised; the embedding reads frame 0's tokens from it).
-#include "common.h"
+#include "token.h"
 #include "misc.h"
 
 namespace {
-
-__device__ __forceinline__ float wsum_ti2v(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
 
 // LayerNorm(eps, no affine) -> (1 + scale) y + shift with mod[tok / (gh gw)] = {shift, scale} [2][D] -> proj_out -> un-patchify for 48
 // channels: out [B][48][F][H][W] fp32, feature o = (py 2 + px) 48 + c.  A workgroup owns 32 tokens: two-pass fp32 statistics (one
@@ -28,7 +22,6 @@ __global__ __launch_bounds__(256) void wan_ti2v_final48_kernel(const __bf16* __r
                                                                const float* __restrict__ bias, const float* __restrict__ ff0,
                                                                float* __restrict__ out, int ntok, int Fr, int gh, int gw, int D, float eps) {
     constexpr int C = 48, NO = 4 * C, TOK = 32, KC = 32, LD = KC + 4, TI = 4, JO = NO / 32, WL = NO * (KC / 4) / 256;
-    typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2_;
     __shared__ __attribute__((aligned(16))) float ys[TOK][LD];
     __shared__ __attribute__((aligned(16))) float ws[NO][LD];
     __shared__ float s_mean[TOK], s_rstd[TOK];
@@ -39,18 +32,18 @@ __global__ __launch_bounds__(256) void wan_ti2v_final48_kernel(const __bf16* __r
         const __bf16* row = x + (size_t)tok * D;
         float s = 0.f;
         for (int c = 2 * lane; c < D; c += 128) {
-            const bf16x2_ q = *reinterpret_cast<const bf16x2_*>(row + c);
+            const bf16x2 q = *reinterpret_cast<const bf16x2*>(row + c);
             s += (float)q[0] + (float)q[1];
         }
-        const float mean = wsum_ti2v(s) * (1.0f / D);
+        const float mean = wave_sum(s) * (1.0f / D);
         float ss = 0.f;
         for (int c = 2 * lane; c < D; c += 128) {
-            const bf16x2_ q = *reinterpret_cast<const bf16x2_*>(row + c);
+            const bf16x2 q = *reinterpret_cast<const bf16x2*>(row + c);
             const float u0 = (float)q[0] - mean, u1 = (float)q[1] - mean;
             ss = fmaf(u0, u0, ss);
             ss = fmaf(u1, u1, ss);
         }
-        const float rstd = 1.0f / sqrtf(wsum_ti2v(ss) * (1.0f / D) + eps);
+        const float rstd = 1.0f / sqrtf(wave_sum(ss) * (1.0f / D) + eps);
         if (lane == 0) s_mean[tl] = mean, s_rstd[tl] = rstd;
     }
     __syncthreads();

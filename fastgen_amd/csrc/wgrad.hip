@@ -20,7 +20,7 @@
 // other's MFMAs; the tile loop itself is the plain load -> barrier -> MFMA -> barrier form (first correct version).
 #include <type_traits>
 
-#include "common.h"
+#include "token.h"
 #include "misc.h"
 
 namespace {
@@ -33,18 +33,9 @@ __host__ __device__ constexpr int wg_ci(int ks) { return ks == 1 ? WG_CI1 : WG_C
 constexpr int WG_TILE = 64;      // pixels per tile = 4 MFMA k-steps of 16 (128 = 8 rows for the 3x3 kernel at width >= 16)
 constexpr int WG_DYP = 2 * WG_CO + 64;  // dY tile row pitch in bytes: 4 consecutive rows tile the 64 banks (320 = 64 mod 256)
 
-typedef __attribute__((ext_vector_type(4))) short s16x4;
-typedef __attribute__((ext_vector_type(8))) short s16x8;
-typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
-
-__device__ __forceinline__ s16x4 tr_read(const char* lds_addr) {
-    // generic -> LDS address space: the low 32 bits of a generic LDS pointer are the LDS offset
-    return __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(uintptr_t)(uint32_t)(uintptr_t)lds_addr);
-}
-
 // One MFMA operand (8 consecutive K of this lane's row/column) = two transposed reads of 4 pixels each.
 __device__ __forceinline__ Frag8<__bf16> tr_frag(const char* p0, const char* p1) {
-    const s16x4 lo = tr_read(p0), hi = tr_read(p1);
+    const s16x4 lo = lds_tr_read(p0), hi = lds_tr_read(p1);
     s16x8 v;
 #pragma unroll
     for (int j = 0; j < 4; ++j) v[j] = lo[j], v[4 + j] = hi[j];

@@ -166,7 +166,7 @@ def test_quant_rows_is_the_mirror_bit_for_bit(dtype, k):
 
 
 @gpu
-@pytest.mark.parametrize("d", [384, 768, 1024, 1152])
+@pytest.mark.parametrize("d", [384, 768, 1024, 1152, 3072])  # (3072: the 5B video DiT's width, which the fp8 Wan engine runs through this op)
 def test_ln_modulate_fp8(d):
     from fastgen_amd import _lib
 

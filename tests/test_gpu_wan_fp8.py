@@ -43,7 +43,7 @@ def _module(cfg, sd, compute_dtype):
     return net.cuda().eval()
 
 
-@pytest.mark.parametrize("d", [256, 1536, 2048, 5120])
+@pytest.mark.parametrize("d", [256, 1536, 2048, 3072, 5120])
 def test_ln_modulate_fp8_at_the_video_widths(d):
     from fastgen_amd import _lib
 
