@@ -238,6 +238,12 @@ SIGNATURES = {
                                           c_void_p, c_uint64, c_int, c_int, c_int, c_int, c_void_p, c_size_t, c_int, c_void_p]),
     "fg_op_guided_multistep": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int64, c_void_p]),
     "fg_wan_select_cache_tag": (c_int, [c_void_p, c_int]),
+    "fg_wan_set_kv_cache_dtype": (c_int, [c_void_p, c_int]),
+    "fg_wan_kv_cache_bytes": (c_size_t, [c_void_p, c_int, c_int, c_int]),
+    "fg_op_wan_kv_quant": (c_int, [c_void_p, c_int, c_void_p, c_float, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_int, c_int,
+                                   c_void_p]),
+    "fg_op_wan_attention_kv8": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
+                                        c_int64, c_int64, c_int64, c_int64, c_void_p]),
     "fg_wan_create": (c_int, [POINTER(fg_wan_config), POINTER(c_void_p)]),
     "fg_wan_destroy": (None, [c_void_p]),
     "fg_wan_num_params": (c_int, [c_void_p]),

@@ -1717,6 +1717,39 @@ int fg_op_wan_dual_cross_attention(const void* q, int ldq, int64_t q_bs, const v
                                       batch, heads, lq, (hipStream_t)stream));
     return FG_OK;
 }
+int fg_op_wan_kv_quant(const void* src, int ld_src, const float* weight, float eps, const float* cs, void* k8, float* scale, int64_t dst_bs,
+                       int dst_start, int ld_dst, int rows, int l, int heads, void* stream) {
+    const int64_t d = (int64_t)heads * 128;
+    if (!src || !k8 || !scale || heads <= 0 || !fg_wan_width_ok((int)d) || rows <= 0 || l <= 0 || (rows % l) || dst_start < 0)
+        return fail(FG_EINVAL, "fg_op_wan_kv_quant: bad argument (null pointer, 128 heads not one of" FG_WAN_WIDTHS_STR ", rows not a multiple of l, "
+                    "a count <= 0 or dst_start < 0)");
+    if (ld_src < d || (ld_src % 2) || ld_dst < d || (ld_dst % 16) || dst_bs <= 0 || (dst_bs % ld_dst) || (int64_t)dst_start + l > dst_bs / ld_dst)
+        return fail(FG_EINVAL, "fg_op_wan_kv_quant: ld_src >= 128 heads and even, ld_dst >= 128 heads and %% 16, dst_bs a multiple of ld_dst that "
+                    "holds rows [dst_start, dst_start + l)");
+    if ((((uintptr_t)src) & 3) || (((uintptr_t)k8) & 15) || (((uintptr_t)scale) & 3) || (((uintptr_t)weight) & 7) || (((uintptr_t)cs) & 7))
+        return fail(FG_EINVAL, "fg_op_wan_kv_quant: src 4-byte, k8 16-byte, weight / cs 8-byte aligned");
+    HIP_TRY(launch_wan_kv_quant((int)d, src, ld_src, weight, eps, (const float2*)cs, k8, scale, dst_bs, dst_bs / ld_dst * heads, dst_start, ld_dst, rows,
+                                l, (hipStream_t)stream));
+    return FG_OK;
+}
+int fg_op_wan_attention_kv8(const void* q, const void* k8, const void* v8, const float* k_scale, const float* v_scale, void* out, int batch,
+                            int heads, int lq, int lkv, int ldq, int ldk, int ldo, int64_t q_bs, int64_t kv_bs, int64_t scale_bs, int64_t o_bs,
+                            void* stream) {
+    if (!q || !k8 || !v8 || !k_scale || !v_scale || !out || batch <= 0 || heads <= 0 || lq <= 0 || lkv <= 0)
+        return fail(FG_EINVAL, "fg_op_wan_attention_kv8: bad argument (null pointer or a count <= 0)");
+    const int64_t d = (int64_t)heads * 128;
+    if (ldq < d || (ldq % 8) || ldk < d || (ldk % 16) || ldo < d || (ldo % 4) || q_bs < 0 || (q_bs % 8) || kv_bs < 0 || (kv_bs % 16) || scale_bs < 0 ||
+        o_bs < 0 || (o_bs % 4))
+        return fail(FG_EINVAL, "fg_op_wan_attention_kv8: ldq / ldk / ldo >= 128 heads with ldq %% 8, ldk %% 16, ldo %% 4; q_bs %% 8, kv_bs %% 16, o_bs %% 4, "
+                    "no negative stride");
+    if (batch > 1 && (q_bs < (int64_t)lq * ldq - (ldq - d) || kv_bs < (int64_t)lkv * ldk - (ldk - d) || scale_bs < (int64_t)lkv * heads ||
+                      o_bs < (int64_t)lq * ldo - (ldo - d)))
+        return fail(FG_EINVAL, "fg_op_wan_attention_kv8: a batch stride is shorter than one sample's rows");
+    if ((((uintptr_t)q) | ((uintptr_t)k8) | ((uintptr_t)v8)) & 15 || (((uintptr_t)out) & 7) || ((((uintptr_t)k_scale) | ((uintptr_t)v_scale)) & 3))
+        return fail(FG_EINVAL, "fg_op_wan_attention_kv8: q / k8 / v8 must be 16-byte aligned, out 8-byte, the scales 4-byte");
+    HIP_TRY(launch_wan_fa_kv8(q, ldq, q_bs, k8, v8, ldk, kv_bs, k_scale, v_scale, scale_bs, out, ldo, o_bs, batch, heads, lq, lkv, (hipStream_t)stream));
+    return FG_OK;
+}
 int fg_op_wan_patch_embed(const float* x, const float* first_frame, const float* w, const float* bias, void* out, int batch, int channels, int frames,
                           int height, int width, int d, int path, void* stream) {
     if (!x || !w || !bias || !out || batch <= 0 || channels <= 0 || channels > 64 || frames <= 0 || height <= 0 || width <= 0 || (height & 1) ||

@@ -14,6 +14,12 @@ struct fg_wan : HandleBase {
     // followed by the N fp32 channel scales instead of bf16 (inside the same allocation), and their A operands are quantised per
     // token (wan_modulate / wan_stage); wan_gemm is the one place that launches either.  The text side (p_x1, p_x2, p_kv2) stays bf16.
     bool fp8 = false;
+    // fg_wan_set_kv_cache_dtype(FG_DTYPE_FP8): every self-attention cache buffer (kc, vc; both tags) holds [B][cap][D] e4m3fn bytes followed
+    // by the [B][cap][H] fp32 scales of its (token, head) pairs, inside the same allocation (wan_kv8.hip writes and reads it).  Independent of
+    // `fp8` (the linears' mode); fixed while a cache buffer exists.
+    bool kv8 = false;
+    size_t kv_bytes(size_t B, size_t cap) const { return kv8 ? B * cap * ((size_t)D + 4 * (size_t)H) : B * cap * (size_t)D * 2; }
+    float* kv_scales(void* buf, size_t B, size_t cap) const { return reinterpret_cast<float*>((char*)buf + B * cap * (size_t)D); }
     struct Blk {
         int sst, q_w, q_b, k_w, k_b, v_w, v_b, o_w, o_b, nq, nk;          // attn1
         int q2_w, q2_b, k2_w, k2_b, v2_w, v2_b, o2_w, o2_b, nq2, nk2;      // attn2
@@ -21,7 +27,7 @@ struct fg_wan : HandleBase {
         int ak_w = -1, ak_b = -1, av_w = -1, av_b = -1, nak = -1;  // attn2.add_k_proj / add_v_proj / norm_added_k (fg_wan_create_i2v, image_dim > 0)
         void *p_qkv = nullptr, *p_o = nullptr, *p_q2 = nullptr, *p_kv2 = nullptr, *p_o2 = nullptr, *p_f0 = nullptr, *p_f2 = nullptr;  // bf16 [N][K] (fp8: above)
         float *b_qkv = nullptr, *b_kv2 = nullptr, *n2mod = nullptr;  // fused biases; norm2 as {shift = bias, scale = weight - 1}
-        void *kc = nullptr, *vc = nullptr;   // self-attention cache [B][cap][D] bf16
+        void *kc = nullptr, *vc = nullptr;   // self-attention cache [B][cap][D] bf16 (kv8: fg_wan::kv_bytes)
         void* kv2 = nullptr;                 // cross-attention cache [B][Lt][2 D] bf16 (k normalised | v)
         void* p_akv = nullptr;               // add_k_proj | add_v_proj, bf16 [2 D][D] in every mode (as p_kv2)
         float* b_akv = nullptr;
@@ -673,7 +679,7 @@ int fg_wan_clear_caches(fg_wan* h, void* stream) {
     if (!h) return fail(FG_EINVAL, "null handle");
     // the selected tag's set, and the same for the one that is not (the reference resets every tag's sub-dict)
     return h->each_cache_set([&](fg_wan::CacheState& st, auto&& kv, size_t n) -> int {
-        const size_t bytes = (size_t)st.cache_B * st.cache_cap * h->D * 2;
+        const size_t bytes = h->kv_bytes(st.cache_B, st.cache_cap);  // (e4m3 zeros under zero scales: zero keys / values too)
         for (size_t i = 0; bytes > 0 && i < n; ++i) {
             HIP_TRY(hipMemsetAsync(kv(i).first, 0, bytes, (hipStream_t)stream));
             HIP_TRY(hipMemsetAsync(kv(i).second, 0, bytes, (hipStream_t)stream));
@@ -682,6 +688,28 @@ int fg_wan_clear_caches(fg_wan* h, void* stream) {
         st.text_B = 0;  // `is_init = False` of the cross-attention caches (network_causal.py:1046-1054)
         return FG_OK;
     });
+}
+
+int fg_wan_set_kv_cache_dtype(fg_wan* h, int dtype) {
+    if (!h) return fail(FG_EINVAL, "null handle");
+    if (dtype != FG_DTYPE_BF16 && dtype != FG_DTYPE_FP8)
+        return fail(FG_EINVAL, "fg_wan_set_kv_cache_dtype: kv_cache_dtype %d: FG_DTYPE_BF16 and FG_DTYPE_FP8 are implemented", dtype);
+    const bool kv8 = dtype == FG_DTYPE_FP8;
+    if (kv8 && (h->is_i2v || h->is_ti2v || h->is_vace))  // (no chunked / causal call exists there: nothing would ever read such a cache)
+        return fail(FG_EINVAL, "fg_wan_set_kv_cache_dtype: kv_cache_dtype fp8 is not implemented for an image-to-video or VACE handle");
+    if (kv8 == h->kv8) return FG_OK;
+    bool allocated = false;
+    for (const fg_wan::Blk& b : h->blocks) allocated |= b.kc != nullptr;
+    for (const void* p : h->other.kc) allocated |= p != nullptr;
+    if (allocated) return fail(FG_EINVAL, "fg_wan_set_kv_cache_dtype: kv_cache_dtype is fixed once a self-attention cache set is allocated");
+    h->kv8 = kv8;
+    return FG_OK;
+}
+
+size_t fg_wan_kv_cache_bytes(const fg_wan* h, int batch, int height, int width) {
+    if (!h || !wan_shape_ok(batch, 1, height, width)) return 0;
+    const size_t cap = (size_t)h->cfg.total_num_frames * (height / 2) * (width / 2);
+    return 2 * h->blocks.size() * h->kv_bytes(batch, cap);
 }
 
 int fg_wan_select_cache_tag(fg_wan* h, int tag) {
@@ -892,7 +920,7 @@ int wan_ensure_caches(fg_wan* h, int batch, int height, int width, hipStream_t s
     const int cap = h->cfg.total_num_frames * (height / 2) * (width / 2), D = h->D;
     fg_wan::CacheState& st = h->cur;
     if (st.cache_B == batch && st.cache_cap == cap) return FG_OK;
-    const size_t had = (size_t)st.cache_B * st.cache_cap * D * 2, bytes = (size_t)batch * cap * D * 2;
+    const size_t had = h->kv_bytes(st.cache_B, st.cache_cap), bytes = h->kv_bytes(batch, cap);
     st.cache_B = st.cache_cap = 0;  // (nothing valid until every block has its new buffers)
     for (fg_wan::Blk& b : h->blocks) {
         size_t have_k = had, have_v = had;
@@ -940,7 +968,7 @@ void wan_graph_key_tail(const fg_wan* h, std::vector<int64_t>& key) {
     const fg_wan::Blk& b0 = h->blocks[0];
     const void* const bufs[] = {b0.kc, b0.kv2, b0.kvi, h->ff, h->ff0, h->vctx, h->vscale};
     for (const void* p : bufs) key.push_back((int64_t)(uintptr_t)p);
-    key.insert(key.end(), {(int64_t)h->cur.text_L, (int64_t)h->img_L, (int64_t)h->fp8, (int64_t)h->ext.time_cond_diff});
+    key.insert(key.end(), {(int64_t)h->cur.text_L, (int64_t)h->img_L, (int64_t)h->fp8, (int64_t)h->ext.time_cond_diff, (int64_t)h->kv8});
 }
 
 // One time embedder on `rows` [BF]: Timesteps(256) -> Linear - SiLU - Linear into emb [BF][D], then time_proj(silu(emb)) into proj
@@ -1015,6 +1043,14 @@ int wan_block(fg_wan* h, fg_wan::Blk& b, void*& x, void*& xn, const fg_wan_block
                                  batch, h->H, nf * fs, (f0 + nf) * fs, s, w.fa));
             f0 += nf;
         }
+    } else if (h->kv8) {
+        // the e4m3 cache: the same two row kernels with a quantising store, and attention over the stored bytes - over this chunk's own
+        // rows too, so that a chunk sees the keys / values every later chunk will see
+        const int64_t sbs = cbs / D * h->H;
+        float *ksc = h->kv_scales(b.kc, batch, cbs / D), *vsc = h->kv_scales(b.vc, batch, cbs / D);
+        HIP_TRY(launch_wan_kv_quant(D, qkv + D, 3 * D, h->P(b.nk), c.eps, w.cs, b.kc, ksc, cbs, sbs, cache_start, D, M, L, s));
+        HIP_TRY(launch_wan_kv_quant(D, qkv + 2 * D, 3 * D, nullptr, c.eps, nullptr, b.vc, vsc, cbs, sbs, cache_start, D, M, L, s));
+        HIP_TRY(launch_wan_fa_kv8(w.qn, D, (int64_t)L * D, b.kc, b.vc, D, cbs, ksc, vsc, sbs, w.att, D, (int64_t)L * D, batch, h->H, L, cache_start + L, s));
     } else {
         HIP_TRY(launch_rms_rope(D, qkv + D, 3 * D, h->P(b.nk), c.eps, w.cs, b.kc, cbs, cache_start, D, M, L, s));
         HIP_TRY(launch_rms_rope(D, qkv + 2 * D, 3 * D, nullptr, c.eps, nullptr, b.vc, cbs, cache_start, D, M, L, s));

@@ -306,6 +306,16 @@ int launch_fa128(const void* q, int ldq, int64_t q_bs, const void* k, const void
                  int B, int heads, int Lq, int Lkv, hipStream_t s, void* scratch = nullptr);
 int launch_wan_final(int D, const void* x, const float* mod, const float* w, const float* bias, float* out, int ntok, int Fr, int gh, int gw, int C,
                      float eps, hipStream_t s);
+// wan_kv8.hip: the self-attention cache as e4m3fn bytes + one fp32 scale per (token, head), head dim 128.
+// launch_rms_rope with a quantising store: dst rows of ld_dst BYTES (dst_bs bytes between samples), scale [B][scale_bs floats] with
+// row (dst_row0 + l) of a sample at (dst_row0 + l) * (D / 128); scale = amax / 448 per (token, head), a zero head: scale 1, bytes 0
+int launch_wan_kv_quant(int D, const void* src, int ld_src, const float* w, float eps, const float2* cs, void* dst, float* scale, int64_t dst_bs,
+                        int64_t scale_bs, int dst_row0, int ld_dst, int rows, int L, hipStream_t s);
+// launch_fa128 over such a cache: k8 / v8 rows of ldk bytes (kv_bs bytes between samples), k_scale / v_scale [B][scale_bs floats] with
+// key l's heads at l * heads; nothing is read past key Lkv - 1.  q 16-byte aligned (ldq, q_bs % 8), k8 / v8 16-byte aligned (ldk, kv_bs
+// % 16), out 8-byte aligned (ldo, o_bs % 4).
+int launch_wan_fa_kv8(const void* q, int ldq, int64_t q_bs, const void* k8, const void* v8, int ldk, int64_t kv_bs, const float* k_scale,
+                      const float* v_scale, int64_t scale_bs, void* out, int ldo, int64_t o_bs, int B, int heads, int Lq, int Lkv, hipStream_t s);
 // wan_jvp.hip: the non-GEMM pieces of the bidirectional video DiT's forward-mode derivative: a primal and a tangent stream, bf16 tokens
 // LayerNorm-modulate with tangent: x, xd, y, yd bf16 [ntok][D]; mod / modd fp32 rows of mod_stride (row = token / tokens_per_row),
 // modd nullable (a constant affine); even stride / offsets

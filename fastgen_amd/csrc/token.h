@@ -33,7 +33,41 @@ __device__ __forceinline__ f32x2 load2(const __bf16* p) {
 __device__ __forceinline__ void store2(float* p, f32x2 v) { *reinterpret_cast<f32x2*>(p) = v; }
 __device__ __forceinline__ void store2(__bf16* p, f32x2 v) { *reinterpret_cast<bf16x2*>(p) = bf16x2{(__bf16)v[0], (__bf16)v[1]}; }
 
-// ---- attention tile, head dim 128: the LDS image ----------------------------------------------------------------------------
+// ---- one token row of the video DiT in one wave: RMSNorm over D = 128 NP (* w; w == nullptr: the row as it is), then (cs_row !=
+// nullptr) the interleaved-pair rotation of every head with the token's table row cs_row[64] {cos, sin}.  Lane l holds the pairs
+// l + 64 j of the row in v[2 j], v[2 j + 1] (elements 2 (l + 64 j), + 1): register pair j IS head j, pair l of that head.
+// Users: wan.hip rms_rope_kernel (bf16 store), wan_kv8.hip wan_kv_quant_kernel (e4m3 store).
+template <int NP>
+__device__ __forceinline__ void rms_rope_row(const __bf16* __restrict__ x, const float* __restrict__ w, float eps, const float2* __restrict__ cs_row,
+                                             int lane, float (&v)[2 * NP]) {
+    constexpr int D = 128 * NP;
+    float ss = 0.f;
+#pragma unroll
+    for (int j = 0; j < NP; ++j) {
+        const bf16x2 q = *reinterpret_cast<const bf16x2*>(x + 2 * (lane + 64 * j));
+        v[2 * j] = (float)q[0], v[2 * j + 1] = (float)q[1];
+        ss = fmaf(v[2 * j], v[2 * j], fmaf(v[2 * j + 1], v[2 * j + 1], ss));
+    }
+    if (w) {
+        const float r = 1.0f / sqrtf(wave_sum(ss) * (1.0f / D) + eps);
+#pragma unroll
+        for (int j = 0; j < NP; ++j) {
+            const f32x2 wq = *reinterpret_cast<const f32x2*>(w + 2 * (lane + 64 * j));
+            v[2 * j] *= r * wq[0], v[2 * j + 1] *= r * wq[1];
+        }
+    }
+    if (cs_row) {
+        const float2 c = cs_row[lane];
+#pragma unroll
+        for (int j = 0; j < NP; ++j) {
+            const float a = v[2 * j], bb = v[2 * j + 1];
+            v[2 * j] = a * c.x - bb * c.y;
+            v[2 * j + 1] = a * c.y + bb * c.x;
+        }
+    }
+}
+
+// ---- attention tile, head dim 128: the LDS image----------------------------------------------------------------------------
 // A tile is 32 keys x 128 bf16 (8 KiB), for K and for V alike.  V stays row-major in memory and in LDS; its K-contiguous fragments
 // (8 keys of one output dim) come from ds_read_b64_tr_b16.  LDS image of both tiles: 256-byte rows, 16-byte chunk ch of row r at
 // 16 (ch ^ fa128_swz(r)): conflict-free for the ds_read_b128 row reads of K and for the transposed reads of V

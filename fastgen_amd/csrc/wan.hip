@@ -84,33 +84,9 @@ __global__ __launch_bounds__(256) void rms_rope_kernel(const __bf16* __restrict_
     const int lane = threadIdx.x & 63;
     const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (row >= rows) return;
-    const __bf16* x = src + (size_t)row * ld_src;
-    float v[2 * NP];
-    float ss = 0.f;
-#pragma unroll
-    for (int j = 0; j < NP; ++j) {
-        const bf16x2 q = *reinterpret_cast<const bf16x2*>(x + 2 * (lane + 64 * j));
-        v[2 * j] = (float)q[0], v[2 * j + 1] = (float)q[1];
-        ss = fmaf(v[2 * j], v[2 * j], fmaf(v[2 * j + 1], v[2 * j + 1], ss));
-    }
     const int b = row / L, l = row - b * L;
-    if (w) {
-        const float r = 1.0f / sqrtf(wave_sum(ss) * (1.0f / D) + eps);
-#pragma unroll
-        for (int j = 0; j < NP; ++j) {
-            const f32x2 wq = *reinterpret_cast<const f32x2*>(w + 2 * (lane + 64 * j));
-            v[2 * j] *= r * wq[0], v[2 * j + 1] *= r * wq[1];
-        }
-    }
-    if (cs) {
-        const float2 c = cs[(size_t)l * 64 + lane];
-#pragma unroll
-        for (int j = 0; j < NP; ++j) {
-            const float a = v[2 * j], bb = v[2 * j + 1];
-            v[2 * j] = a * c.x - bb * c.y;
-            v[2 * j + 1] = a * c.y + bb * c.x;
-        }
-    }
+    float v[2 * NP];
+    rms_rope_row<NP>(src + (size_t)row * ld_src, w, eps, cs ? cs + (size_t)l * 64 : nullptr, lane, v);
     __bf16* y = dst + (size_t)b * dst_bs + (size_t)(dst_row0 + l) * ld_dst;
 #pragma unroll
     for (int j = 0; j < NP; ++j) *reinterpret_cast<bf16x2*>(y + 2 * (lane + 64 * j)) = bf16x2{(__bf16)v[2 * j], (__bf16)v[2 * j + 1]};

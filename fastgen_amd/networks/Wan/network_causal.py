@@ -18,6 +18,11 @@ feature taps, r / image conditioning, `is_ar=False` on fewer frames, any device 
 `compute_dtype="fp8"` (keyword only; default None = "bf16"): the six linears of every block that read the video tokens contract e4m3fn
 operands - weights quantised per output channel at every pack, activations per token - through every call above; the text side, the
 embedders, attention and the caches stay bf16.  What it costs and buys: DESIGN.md, section 10.
+
+`kv_cache_dtype="fp8"` (keyword only; default None = "bf16"): the self-attention K / V caches of both tags hold e4m3fn bytes with one
+fp32 scale per (token, head) - 0.516 of the bf16 cache - written by a quantising RMSNorm + RoPE kernel and read by an attention kernel
+that widens them back to bf16 in front of the same MFMA products (fastgen_amd/csrc/wan_kv8.hip); `forward(is_ar=True)`,
+`student_sample` and `sample`.  Independent of compute_dtype.  DESIGN.md, section 10.
 """
 from __future__ import annotations
 
@@ -42,10 +47,14 @@ class CausalWan(WanEngineNetwork):
                  text_dim: int = 4096, freq_dim: int = 256, ffn_dim: int = 8960, num_layers: int = 30, eps: float = 1e-6,
                  rope_max_seq_len: int = 1024, r_timestep: bool = False, net_pred_type: str = "flow", schedule_type: str = "rf",
                  chunk_size: int = 3, total_num_frames: int = 21, enable_logvar_linear: bool = True, *,
-                 compute_dtype: Optional[str] = None, **model_kwargs):
+                 compute_dtype: Optional[str] = None, kv_cache_dtype: Optional[str] = None, **model_kwargs):
         # compute_dtype: None / "bf16" - every GEMM on bf16 operands; "fp8" - the six linears of a block that read the video tokens on
         # e4m3fn operands (include/fastgen_amd.h, fg_wan_config).  Fixed at construction; the state dict (fp32 masters) is the same.
+        # kv_cache_dtype: None / "bf16" - bf16 self-attention caches; "fp8" - e4m3fn bytes + one fp32 scale per (token, head), every cached
+        # call and both cache tags (fg_wan_set_kv_cache_dtype).  Fixed at construction, independent of compute_dtype.
         self._check_compute_dtype(compute_dtype, ffn_dim, "causal video DiT")
+        if kv_cache_dtype not in (None, "bf16", "fp8"):
+            raise ValueError(f"kv_cache_dtype must be None, 'bf16' or 'fp8', got {kv_cache_dtype!r}")
         self._pop_reference_knobs(model_kwargs)
         super().__init__(net_pred_type=net_pred_type, schedule_type=schedule_type, **model_kwargs)
         if r_timestep:
@@ -56,6 +65,9 @@ class CausalWan(WanEngineNetwork):
                            rope_max_seq_len=rope_max_seq_len, chunk_size=chunk_size, total_num_frames=total_num_frames,
                            compute_dtype=compute_dtype, enable_logvar_linear=enable_logvar_linear)
         self._tag = "pos"  # the selected cache tag ("pos" outside a forward(cache_tag="neg") call)
+        self.kv_cache_dtype = kv_cache_dtype
+        if kv_cache_dtype == "fp8":  # (before the first cache allocation: a fresh handle holds none)
+            _lib.check(_lib.lib().fg_wan_set_kv_cache_dtype(self._h, _lib.DTYPE_NAMES["fp8"]))
 
     # ---- library plumbing (the rest: WanEngineNetwork) -----------------------------------------------------------------------
     @property
@@ -67,6 +79,10 @@ class CausalWan(WanEngineNetwork):
         if C != self.in_channels:
             raise ValueError(f"{what} must have {self.in_channels} channels, got {C}")
         return B, F, H, W
+
+    def kv_cache_bytes(self, batch: int, height: int, width: int) -> int:
+        """Bytes of one self-attention cache set (one cache tag) for `batch` videos of total_num_frames latent frames of height x width."""
+        return int(_lib.lib().fg_wan_kv_cache_bytes(self._h, int(batch), int(height), int(width)))
 
     def clear_caches(self) -> None:
         """`CausalWan.clear_caches` (network_causal.py:1030-1054)."""

@@ -663,6 +663,18 @@ FG_API int fg_wan_clear_caches(fg_wan* h, void* stream);
  * allocated when it is first used: a handle that never selects tag 1 holds one set, as before; using it costs a second set of memory.
  * A graph captured by a sampler loop under one tag is not replayed under the other (its key holds the set's pointers). */
 FG_API int fg_wan_select_cache_tag(fg_wan* h, int tag);
+/* How the self-attention K / V caches are stored.  FG_DTYPE_BF16 (the default): bf16.  FG_DTYPE_FP8: e4m3fn bytes with one fp32 scale
+ * per (token, head) - 0.516 of the bf16 bytes.  The chunk's keys / values are quantised as they are written (RMSNorm and RoPE first,
+ * scale = amax / 448 over the head's 128 dims) and attention reads them back as bf16 x scale - this chunk's own rows included, so a
+ * chunk sees the keys / values later chunks see; the products and the softmax are the bf16 mode's.  Both cache tags; fg_wan_forward,
+ * fg_wan_forward_features (cached call), fg_wan_sampler_run and fg_wan_guided_sampler_run; the setting is part of the loops' graph
+ * keys.  The calls that read no self-attention cache (block-causal, bidirectional) and the text / image keys are untouched, and the
+ * setting is independent of compute_dtype.  Allowed while no cache set of the handle is allocated (before the first cached call);
+ * afterwards a change is FG_EINVAL.  An image-to-video or VACE handle (no cached call) refuses FG_DTYPE_FP8.
+ * fg_wan_kv_cache_bytes: the bytes of ONE cache set (every block's K and V) under the current setting for `batch` rows of
+ * total_num_frames frames of height x width; 0 on a bad argument. */
+FG_API int fg_wan_set_kv_cache_dtype(fg_wan* h, int dtype);
+FG_API size_t fg_wan_kv_cache_bytes(const fg_wan* h, int batch, int height, int width);
 /* The text condition: text [B, text_len, text_dim] fp32 (the text encoder's output).  Runs condition_embedder.text_embedder and
  * every block's attn2 k / v projections (+ norm_k) once: the reference's static cross-attention cache (:331-360).  The caches are
  * rewritten in place while batch x text_len stays the same (the sampler loops' cached graphs name them); a change of that size
@@ -1023,6 +1035,22 @@ FG_API int fg_op_attention_ex(const void* q, int ldq, int64_t q_bs, const void* 
 FG_API int fg_op_wan_dual_cross_attention(const void* q, int ldq, int64_t q_bs, const void* k_txt, const void* v_txt, int ldk_txt,
                                           int64_t kv_bs_txt, int l_txt, const void* k_img, const void* v_img, int ldk_img, int64_t kv_bs_img,
                                           int l_img, void* out, int ldo, int64_t o_bs, int batch, int heads, int lq, void* stream);
+/* The e4m3 self-attention cache of the causal video DiT on its own (wan_kv8.hip; fg_wan_set_kv_cache_dtype), head dim 128, for the
+ * per-element tests.
+ * fg_op_wan_kv_quant: the cache write.  src: rows x ld_src bf16 (row = sample * l + token); RMSNorm over the 128 heads dims times weight
+ * (nullable: the row as it is), then the pair rotation cs [l][64] {cos, sin} (nullable: none) - the bf16 cache write's arithmetic -
+ * then per (token, head) scale = amax / 448 (a zero head: scale 1, bytes 0) and e4m3fn bytes of value / scale.  Token t of sample b goes
+ * to k8 + b * dst_bs + (dst_start + t) * ld_dst (bytes; dst_bs a multiple of ld_dst, ld_dst % 16 == 0) and its heads' scales to
+ * scale[(b * (dst_bs / ld_dst) + dst_start + t) * heads ..]; rows outside [dst_start, dst_start + l) are untouched.
+ * fg_op_wan_attention_kv8: out = softmax(q k^T / sqrt(128)) v with k = k8 bytes x k_scale, v = v8 bytes x v_scale (widened to bf16 in
+ * front of the bf16 products, the scales applied to the logits / to P in fp32), q and out bf16 rows of ldq / ldo elements as
+ * fg_op_attention_ex, k8 / v8 rows of ldk bytes (kv_bs bytes between samples), the scales [batch][scale_bs floats] with key j's heads at
+ * j * heads.  lkv >= 1 arbitrary; nothing is read past key lkv - 1.  16-byte aligned q / k8 / v8 (ldq % 8, ldk % 16), 8-byte out. */
+FG_API int fg_op_wan_kv_quant(const void* src, int ld_src, const float* weight, float eps, const float* cs, void* k8, float* scale,
+                              int64_t dst_bs, int dst_start, int ld_dst, int rows, int l, int heads, void* stream);
+FG_API int fg_op_wan_attention_kv8(const void* q, const void* k8, const void* v8, const float* k_scale, const float* v_scale, void* out,
+                                   int batch, int heads, int lq, int lkv, int ldq, int ldk, int ldo, int64_t q_bs, int64_t kv_bs,
+                                   int64_t scale_bs, int64_t o_bs, void* stream);
 /* The two ends of the video DiT on their own (wan_embed.hip; wan.hip / wan_ti2v.hip), for the per-element tests and timing.  first_frame
  * (nullable) [batch, channels, 1, height, width]: the second source - frame 0's tokens are computed from it / frame 0 of the head's
  * result is its copy.  path 0: what the engine launches (channels == 48: the phased embedding of wan_embed.hip, the tiled head of

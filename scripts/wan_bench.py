@@ -3,7 +3,7 @@ Wan2.1-T2V-1.3B, latents [16, 21, 60, 104] = 480p, chunk of 3 frames, t_list of 
 chunk k (4680 query tokens over (3 k + 3) * 1560 cached + own keys), and the whole 21-frame 4-step loop (7 chunks x (4 + 1) calls).
 Random-init weights of the 1.3B architecture, synthetic latents and text embeddings.
     python scripts/wan_bench.py [--layers=30] [--loop] [--compute-dtype=bf16[,fp8]] [--case=chunks|bc|guided] [--chunks=0,6]
-                                [--widths=1.3b|14b] [--trace=CALLS] [--bidirectional] [--i2v] [--vace] [--ti2v [--first-frame=both|yes|no]]
+                                [--widths=1.3b|14b] [--kv-cache-dtype=bf16[,fp8]] [--trace=CALLS] [--bidirectional] [--i2v] [--vace] [--ti2v [--first-frame=both|yes|no]]
 --vace (with --bidirectional): the video-to-video network `VACEWan` (fastgen_amd/networks/VaceWan/network.py: a VACE block behind every
   second layer, a 96-channel control video of 21 frames) next to `Wan` of the same widths and depth in the same run, at [1,16,21,60,104]:
   one forward, the 4-step x0 student loop (one hipGraph), one fg_wan_set_vace_context, and the tiled 96-channel patch embedding against
@@ -25,6 +25,8 @@ Random-init weights of the 1.3B architecture, synthetic latents and text embeddi
   pairs), the 4-step x0 student loop (FastGenModel.generator_fn, one hipGraph) and one guided step (the call at the stacked batch 2).
 --compute-dtype: the arms (default bf16).  Several arms are built on the same seed and timed SIDE BY SIDE in this one run: per shape
   three rounds of windows, the arms alternating inside a round, the median window per arm reported (and their ratio).
+--kv-cache-dtype: the self-attention cache's storage (default bf16), a second axis of arms ("bf16/kv-fp8" ...) in the same alternating
+  windows; the bytes of one cache set are printed per arm, and the time ratio kv-bf16 / kv-fp8 per compute dtype.
 --case: chunks (default) - one call per listed chunk (default all 7) over the cache the earlier chunks' calls left; bc - the all-frames
   block-causal call (32 760 tokens); guided - the chunk calls at the stacked batch 2 of the guided teacher sampler ([cond; neg]).
 --widths=14b: inner dim 5120, ffn 13 824 (Wan2.1-T2V-14B's; --layers defaults to 2 then: the weights of 40 layers are 56 GB of fp32).
@@ -47,6 +49,7 @@ def _opt(name, default):
 WIDTHS = _opt("widths", "1.3b")
 LAYERS = int(_opt("layers", "30" if WIDTHS == "1.3b" else "2"))
 ARMS = _opt("compute-dtype", "bf16").split(",")
+KV_ARMS = _opt("kv-cache-dtype", "bf16").split(",")
 CASE = _opt("case", "chunks")
 CHUNKS = [int(c) for c in _opt("chunks", "0,1,2,3,4,5,6").split(",")]
 TRACE = int(_opt("trace", "0"))
@@ -55,15 +58,21 @@ FIRST_FRAME = _opt("first-frame", "both")
 assert FIRST_FRAME in ("both", "yes", "no") and (not (TI2V and TRACE) or FIRST_FRAME != "both")
 if TI2V and not any(a.startswith("--layers=") for a in sys.argv[1:]):
     LAYERS = 30
-assert WIDTHS in ("1.3b", "14b") and CASE in ("chunks", "bc", "guided") and all(a in ("bf16", "fp8") for a in ARMS) and (not TRACE or len(ARMS) == 1)
+assert WIDTHS in ("1.3b", "14b") and CASE in ("chunks", "bc", "guided") and all(a in ("bf16", "fp8") for a in ARMS + KV_ARMS) and (not TRACE or len(ARMS) * len(KV_ARMS) == 1)
 H, Fd = (12, 8960) if WIDTHS == "1.3b" else (40, 13824)
 D, fs, Lt = H * 128, 1560, 512
 B = 2 if CASE == "guided" else 1
 
 nets = {}
 for arm in ([] if "--i2v" in sys.argv or "--vace" in sys.argv or TI2V else ARMS):
-    torch.manual_seed(0)  # the same weights in every arm
-    nets[arm] = CausalWan(num_attention_heads=H, ffn_dim=Fd, num_layers=LAYERS, compute_dtype=arm).cuda().eval()
+    for kv in KV_ARMS:
+        torch.manual_seed(0)  # the same weights in every arm
+        name = arm if KV_ARMS == ["bf16"] else f"{arm}/kv-{kv}"
+        nets[name] = CausalWan(num_attention_heads=H, ffn_dim=Fd, num_layers=LAYERS, compute_dtype=arm, kv_cache_dtype=kv).cuda().eval()
+        if KV_ARMS != ["bf16"]:
+            print(f"{name}: one cache set (batch {B}, 21 frames of 60 x 104) = {nets[name].kv_cache_bytes(B, 60, 104) / 2 ** 30:.3f} GiB", flush=True)
+if nets and "--bidirectional" not in sys.argv:  # (the causal cases below index the nets by arm name)
+    ARMS = list(nets)
 x = torch.randn(B, 16, 21, 60, 104, device="cuda")
 text = torch.randn(B, Lt, 4096, device="cuda")
 t = torch.tensor([0.7] * B, dtype=torch.float64, device="cuda")
@@ -94,6 +103,8 @@ def side_by_side(label, fns, n, gf=None, rounds=3):
     parts = [f"{a} {med[a] * 1e3:8.2f} ms (min {min(times[a]) * 1e3:.2f}, max {max(times[a]) * 1e3:.2f})" +
              (f" {gf / med[a] / 1e3:6.1f} TFLOP/s" if gf else "") for a in fns]
     ratio = f"   bf16 / fp8 = {med['bf16'] / med['fp8']:.3f}" if "bf16" in med and "fp8" in med else ""
+    ratio += "".join(f"   {a}: kv-bf16 / kv-fp8 = {med[f'{a}/kv-bf16'] / med[f'{a}/kv-fp8']:.3f}" for a in ("bf16", "fp8")
+                     if f"{a}/kv-bf16" in med and f"{a}/kv-fp8" in med)
     print(f"{label}: " + "   ".join(parts) + ratio, flush=True)
     return med
 
